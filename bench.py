@@ -10,6 +10,12 @@ A "step" is one `pnp_step` over the 64 slices resident on a GPU: U-Net denoiser 
 2-D FFT data-fidelity solve, dual update (the body of the reference's PnPEnv.step, env.py:74-100).
 Inputs are synthetic and already resident in HBM when the timed region starts.  Rank 0 prints ONE
 JSON line; see DESIGN.md "Measurement" for how `roofline` and `cpu_baseline` are obtained.
+
+A plain run does only what the headline needs: set-up, ONE episode of W warm-up + exactly K timed
+steps, the result line.  `--full` adds the rest of the record: 10 repetitions (median reported), the
+DT-driven leg, the configs[4] leg, the CPU baseline and the PSNR check against the CPU oracle.
+`--dump-outputs DIR` writes what the timed path returned after its last step as DIR/<name>.npy
+(float32; arrays above DUMP_CAP scalars as a fixed seeded sample), so two builds can be compared.
 """
 from __future__ import annotations
 
@@ -41,6 +47,26 @@ def mfma_conv_flops(n, h, w):
 
 
 TRAFFIC_ROUNDS = ("r05", "r04", "r03", "r02", "r01")     # newest first
+
+DUMP_CAP = 1 << 22         # scalars per dumped array (16 MB of float32): x, z, u stay under 64 MB together
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, arrays):
+    """Write each tensor as <path>/<name>.npy in float32 (complex as a trailing (re, im) axis).  An array of more than
+    DUMP_CAP scalars is written as [k, 2] (complex) or [k] elements at a fixed seeded sample of k of its flat element
+    indices (sorted): the same elements in every run of the same shape."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        a = (torch.view_as_real(t) if t.is_complex() else t).numpy().astype(np.float32)
+        if a.size > DUMP_CAP:
+            per = a.size // t.numel()
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), DUMP_CAP // per, replace=False))
+            a = a.reshape(t.numel(), per)[idx]
+            if per == 1:
+                a = a[:, 0]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def pmc_traffic(n, h, w, which, mode="f32"):
@@ -165,7 +191,7 @@ def greedy_leg(args, dev, sd_np, n, h, w, world):
                          if args.pipeline > 1 else "off (one batch per rank: policy and env step alternate on one stream)"),
             "steps": res.steps, "slices": total, "seconds_median": round(med, 5), "ms_per_step": round(1e3 * med / max(res.steps, 1), 4),
             "batch_iterations_per_sec": round(world * res.steps / med, 3), "episodes_timed": len(secs),
-            "psnr_mean_db": round(float(res.reward.mean()), 4), "stop_iteration_mean": float(res.stop_time.float().mean())}
+            "psnr_mean_db": round(float(res.reward.mean()), 4), "stop_iteration_mean": float(res.stop_time.float().mean())}, res
 
 
 def config4_leg(args, dev, sd_np, local_rank):
@@ -239,9 +265,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=10,
+    ap.add_argument("--full", action="store_true",
+                    help="the whole record, not just the headline: 10 repetitions unless --reps says otherwise, the DT-driven leg, "
+                         "the configs[4] leg, the CPU baseline and the PSNR check against the CPU oracle (each --no-* switch drops one)")
+    ap.add_argument("--reps", type=int, default=None,
                     help="repetitions of the [reset, W warm-up steps, K timed steps] episode; the line reports the MEDIAN "
-                         "repetition (each one is exactly K steps between barrier + synchronize brackets, max over ranks)")
+                         "repetition (each one is exactly K steps between barrier + synchronize brackets, max over ranks); "
+                         "default 1, with --full 10")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned after its last step as DIR/<name>.npy (float32)")
     ap.add_argument("--batch", type=int, default=64, help="slices per GPU")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--convs", choices=("f32", "bf16"), default="f32",
@@ -252,18 +284,20 @@ def main():
     ap.add_argument("--mode", choices=("engine", "greedy"), default="engine",
                     help="engine (headline): K pnp_step calls driven by a parameter table; greedy: BASELINE configs[2]'s DT-driven "
                          "sharded episode end to end is the timed thing (value = its batch-iterations/s)")
-    ap.add_argument("--no-greedy", action="store_true", help="skip the end-to-end DT-driven leg of the default line")
+    ap.add_argument("--no-greedy", action="store_true", help="skip the end-to-end DT-driven leg of the --full line")
     ap.add_argument("--pipeline", type=int, default=1,
                     help="DT-driven leg: sub-batches per rank that advance on their own streams (GreedyEvaluator.run_pipelined; "
                          "1 = off, the default: two sub-batches of 32 measured 9.64 against 9.39 ms per step - the policy's chain "
                          "of ~110 small kernels stretches under the other sub-batch's convs and two 32-slice steps cost more than "
                          "one 64-slice step)")
-    ap.add_argument("--no-config4", action="store_true", help="skip the BASELINE configs[4] leg of the default line (N = 1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-config4", action="store_true", help="skip the BASELINE configs[4] leg of the --full line (N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and oracle check of the --full line")
     ap.add_argument("--cpu-slices", type=int, default=16)
     ap.add_argument("--cpu-iters", type=int, default=6)
     ap.add_argument("--dump-layers", default=None, help="write the per-layer kernel time table (JSON) here")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 10 if args.full else 1
 
     # stdout carries exactly ONE line, the JSON result: libraries that print banners to fd 1 (RCCL prints its version block
     # when the first communicator is created) are sent to stderr for the duration of the run
@@ -325,12 +359,12 @@ def main():
         el = torch.tensor([dt], dtype=torch.float64, device=dev)
         if dist is not None:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
-        return float(el.item()), pr, p0, eng.psnr(x, gt)
+        return float(el.item()), pr, p0, eng.psnr(x, gt), (x, z, u)
 
     reps = max(1, args.reps)
     times, profs = [], []
     for _ in range(reps):
-        dt, pr, psnr0, psnr1 = episode()
+        dt, pr, psnr0, psnr1, xzu = episode()
         times.append(dt)
         profs.append(pr)
     order = sorted(range(reps), key=lambda i: times[i])
@@ -348,10 +382,15 @@ def main():
         psnr_all = torch.cat(allp)
     else:
         psnr_all = psnr1
+    if args.dump_outputs and rank == 0:
+        # the iterate pnp_step updates in place, after the last timed step of the last repetition (rank 0's shard)
+        dump_outputs(args.dump_outputs, dict(zip("xzu", xzu)))
 
     greedy = None
-    if not args.no_greedy or args.mode == "greedy":
-        greedy = greedy_leg(args, dev, sd_np, n, h, w, world)     # collective inside: every rank takes part
+    if (args.full and not args.no_greedy) or args.mode == "greedy":
+        greedy, gres = greedy_leg(args, dev, sd_np, n, h, w, world)     # collective inside: every rank takes part
+        if args.dump_outputs and rank == 0 and args.mode == "greedy":
+            dump_outputs(args.dump_outputs, {"greedy_psnr": gres.reward, "greedy_stop_iteration": gres.stop_time.float()})
 
     if rank == 0:
         steps = args.steps
@@ -431,7 +470,7 @@ def main():
                         "three LDS-resident passes actually move 81 B/px (two round trips of the complex scratch, which a "
                         "256x256 slice = 512 KiB > LDS cannot avoid) = moved_gbs",
             }
-        if world == 1 and not args.no_config4 and not bf16 and (n, h, w) == (64, 256, 256):
+        if args.full and world == 1 and not args.no_config4 and not bf16 and (n, h, w) == (64, 256, 256):
             out["config4"] = config4_leg(args, dev, sd_np, local_rank)
         if greedy is not None:
             out["greedy"] = greedy
@@ -451,7 +490,7 @@ def main():
                              "tflops": round(fl / (per * 1e-3) / 1e12, 2) if per > 0 else None})
             with open(args.dump_layers, "w") as f:
                 json.dump(rows, f, indent=1)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             args.cpu_slices = min(args.cpu_slices, n)              # the sample is a prefix of the batch
             mu_c, sg_c = synthetic.param_table(n, total_iters, seed=77)
             g8 = g8_reference(h, w, args.accel, total_iters, mu_tab, sig_tab) if bf16 else None

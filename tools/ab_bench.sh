@@ -3,7 +3,7 @@
 #   lib: path relative to the repo root (default: the in-tree library); each variant runs `bench.py --dump-layers` once.
 # Output: gpurun_out/bench_TAG_NAME.json, gpurun_out/layers_TAG_NAME.json and a summary line per variant.
 tag=$1; shift
-args=${AB_ARGS:---no-cpu-baseline --no-greedy --reps 5}
+args=${AB_ARGS:---full --no-cpu-baseline --no-greedy --reps 5}
 mkdir -p gpurun_out
 for spec in "$@"; do
     IFS=: read -r name lib envs <<< "$spec"

@@ -10,12 +10,12 @@ TAG=${1:-r05}; shift || true
 ARGS=("$@")
 R=$(pwd); G=$R/gpurun_out; mkdir -p "$G"
 if [ ${#ARGS[@]} -eq 0 ]; then
-  python3 bench.py > "$G/bench_$TAG.json" 2> "$G/bench_$TAG.err"
+  python3 bench.py --full > "$G/bench_$TAG.json" 2> "$G/bench_$TAG.err"
 else
-  python3 bench.py "${ARGS[@]}" --no-greedy > "$G/bench_$TAG.json" 2> "$G/bench_$TAG.err"
+  python3 bench.py "${ARGS[@]}" --full --no-greedy > "$G/bench_$TAG.json" 2> "$G/bench_$TAG.err"
 fi
 echo "bench done: $(cut -c1-120 "$G/bench_$TAG.json")"
-python3 bench.py "${ARGS[@]}" --no-cpu-baseline --no-greedy --no-config4 --dump-layers "$G/layers_$TAG.json" > "$G/bench_layers_$TAG.json" 2>> "$G/bench_$TAG.err"   # an event pair per launch
+python3 bench.py "${ARGS[@]}" --full --no-cpu-baseline --no-greedy --no-config4 --dump-layers "$G/layers_$TAG.json" > "$G/bench_layers_$TAG.json" 2>> "$G/bench_$TAG.err"   # an event pair per launch
 echo "layer table done"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$G/prof_$TAG" -o runc -- python3 "$R/bench.py" "${ARGS[@]}" --steps 10 --warmup 2 --reps 3 --no-cpu-baseline --no-greedy --no-config4 > "$G/bench_prof_$TAG.json" 2> "$G/prof_$TAG.err"

@@ -14,20 +14,26 @@ kernel with bf16 / f16 / fp8 MFMAs (the matrix pipe runs beside the vector pipe:
 tests/test_host_logic.py run it on the bf16 kernels' sources.  Kernels whose only MFMAs are f32 (they hold the vector port)
 and kernels without MFMAs are listed, not failed: 350 such ops in the FFT and F(4x4) kernels are stress-clean.
 """
+import atexit
 import os
 import re
+import shutil
 import subprocess
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_patch as ip  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dt4image_restoration_amd", "csrc")
+# scratch files go to a directory of this process's own: fixed names in a shared /tmp fail for the next user and race a parallel run
+TMP = tempfile.mkdtemp(prefix="isa_audit_")
+atexit.register(shutil.rmtree, TMP, True)
 
 
 def asm_of(src, extra=()):
-    out = "/tmp/_isa_audit_%s.s" % os.path.basename(src)
+    out = os.path.join(TMP, "%s.s" % os.path.basename(src))
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
                     "-S", "--cuda-device-only", src, "-o", out, *extra], check=True, stderr=subprocess.DEVNULL)
     return out
@@ -56,7 +62,7 @@ def disassemble(lib):
     """llvm-objdump of every embedded code object, rewritten to the `name:` / instruction / `.Lfunc_end` shape audit_asm() reads"""
     paths = []
     for i, co in enumerate(code_objects(lib)):
-        f = "/tmp/_isa_audit_co%d.o" % i
+        f = os.path.join(TMP, "co%d.o" % i)
         open(f, "wb").write(co)
         txt = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", "--no-show-raw-insn", f], check=True, capture_output=True, text=True).stdout
         lines = []
@@ -69,7 +75,7 @@ def disassemble(lib):
             else:
                 lines.append(l.split("//")[0].rstrip())
         lines.append(".Lfunc_end")
-        out = "/tmp/_isa_audit_co%d.s" % i
+        out = os.path.join(TMP, "co%d.s" % i)
         open(out, "w").write("\n".join(lines))
         paths.append(out)
     return paths
