@@ -13,6 +13,7 @@ PNP_FLAG_NO_DENOISER = 2
 PNP_FLAG_KEEP_STAGES = 4
 PNP_FLAG_BF16_CONVS = 8
 PNP_FLAG_PROFILE_LAYERS = 16
+PNP_SSIM_CLAMP_X = 1
 PROFILE_CLASSES = 6
 PROFILE_CLASS_NAMES = ("conv3x3_mfma", "conv_first", "conv_last", "fft_rows", "fft_cols_prox", "other")
 N_LAYERS = 28
@@ -38,6 +39,7 @@ SIGNATURES = {
     "pnp_fft2c": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "pnp_prox_dual": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _fp, _vp]),
     "pnp_psnr": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),
+    "pnp_ssim": (C.c_int, [C.c_void_p, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _fp, _fp, _vp]),
     "pnp_snapshot_bytes": (C.c_size_t, [C.c_void_p]),
     "pnp_snapshot": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _vp, _vp]),
     "pnp_restore": (C.c_int, [C.c_void_p, _vp, _fp, _fp, _fp, _fp, _vp]),

@@ -91,7 +91,7 @@ def main(argv=None):
     if args.mode == "eval":
         model, env, _ = _build(args, "norm")
         ev = GreedyEvaluator(model, env, max_timesteps=args.max_timesteps, block_size=args.block_size,
-                             device_type=torch.device("cuda", torch.cuda.current_device()), sync_every=5)
+                             device_type=torch.device("cuda", torch.cuda.current_device()), sync_every=5, ssim=True)
         for name, total, load in _sets(args):
             def load_shard(a, b, load=load):
                 batch, tokens = load(a, b)
@@ -100,7 +100,8 @@ def main(argv=None):
             r = run_sharded_greedy(ev, total, load_shard, sync=torch.cuda.synchronize)
             out.append({"set": name, "n": total, "psnr": float(r.reward.mean()),
                         "psnr_increment": float((r.reward - r.initial_reward).mean()),
-                        "mean_stop_iteration": float(r.stop_time.float().mean()), "ranks": world})
+                        "mean_stop_iteration": float(r.stop_time.float().mean()), "ranks": world,
+                        "ssim": float(r.ssim.mean()), "ssim_increment": float((r.ssim - r.initial_ssim).mean())})
             if rank == 0:
                 print(json.dumps(out[-1]), flush=True)
         if dist is not None:
@@ -131,9 +132,9 @@ def main(argv=None):
         # the ranks like `eval` (every rank a contiguous shard of each set, one gather per set)
         model, env, _ = _build(args, "flex")
         ev = GreedyEvaluator(model, env, max_timesteps=args.max_timesteps, block_size=args.block_size,
-                             device_type=torch.device("cuda", torch.cuda.current_device()))
+                             device_type=torch.device("cuda", torch.cuda.current_device()), ssim=True)
         for target in (1.5, 3, 3.5, 4, 4.5):                       # main.py:198
-            incs = []
+            incs, ssims, ssim_incs = [], [], []
             for name, total, load in _sets(args, flex_target=target):
                 def load_shard(a, b, load=load):
                     batch, tokens = load(a, b)
@@ -141,7 +142,10 @@ def main(argv=None):
                     return mat, torch.full((b - a,), D.normalised_rtg(target, flex=True)), torch.from_numpy(tokens)
                 r = run_sharded_greedy(ev, total, load_shard, sync=torch.cuda.synchronize)
                 incs.append(float((r.reward - r.initial_reward).mean()))
-            out.append({"rtg_target": target, "average_increment": float(np.mean(incs)), "ranks": world})
+                ssims.append(float(r.ssim.mean()))
+                ssim_incs.append(float((r.ssim - r.initial_ssim).mean()))
+            out.append({"rtg_target": target, "average_increment": float(np.mean(incs)), "ranks": world,
+                        "ssim": float(np.mean(ssims)), "ssim_increment": float(np.mean(ssim_incs))})
             if rank == 0:
                 print(json.dumps(out[-1]), flush=True)
         if dist is not None:

@@ -102,6 +102,7 @@ struct pnp_engine {
     unsigned fftq_epoch = 0;    // launches of that kernel since the counters were zeroed (they are never reset: the kernel subtracts epoch x per-launch advance)
     float2* d_y0s = nullptr;    // [N,H,W] sgn * S y0
     uint8_t* d_masks = nullptr; // [mask_n,H,W] S mask
+    double* d_ssim_part = nullptr; // [N, ssim_tiles(H, W)] per-tile SSIM sums (pnp_ssim)
     int mask_n = 1;
     size_t ws_bytes = 0;
     // profiling
@@ -447,6 +448,9 @@ static int create_impl(const pnp_config* cfg, pnp_engine* e) {
         hipMalloc((void**)&e->d_masks, N * H * W) != hipSuccess)
         return fail(PNP_ERR_NOMEM, "k-space scratch");
     e->ws_bytes += 2 * cbytes + N * H * W;
+    const size_t sbytes = N * (size_t)ssim_tiles(cfg->h, cfg->w) * sizeof(double);
+    if (hipMalloc((void**)&e->d_ssim_part, sbytes) != hipSuccess) return fail(PNP_ERR_NOMEM, "SSIM partial sums");
+    e->ws_bytes += sbytes;
     if (e->tune.fft_xcd && admm_xcd_usable(cfg->n, cfg->h, cfg->w)) {
         if (hipMalloc((void**)&e->d_fftq, admm_xcd_counter_bytes()) != hipSuccess || hipMemset(e->d_fftq, 0, admm_xcd_counter_bytes()) != hipSuccess)
             return fail(PNP_ERR_NOMEM, "data-fidelity work queues");
@@ -498,7 +502,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipDeviceSynchronize();
     for (int i = 0; i < N_LAYERS; ++i) { (void)hipFree(e->d_wpack[i]); (void)hipFree(e->d_bias[i]); }
     for (auto& L : e->lv) { (void)hipFree(L.p); (void)hipFree(L.q); (void)hipFree(L.s); (void)hipFree(L.pool); }
-    (void)hipFree(e->d_work); (void)hipFree(e->d_fftq); (void)hipFree(e->d_y0s); (void)hipFree(e->d_masks); (void)hipFree(e->d_partial); (void)hipFree(e->d_arrive);
+    (void)hipFree(e->d_work); (void)hipFree(e->d_fftq); (void)hipFree(e->d_y0s); (void)hipFree(e->d_masks); (void)hipFree(e->d_ssim_part); (void)hipFree(e->d_partial); (void)hipFree(e->d_arrive);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     delete e;
@@ -677,6 +681,31 @@ int pnp_psnr(pnp_handle e, const float* x, const float* gt, float* out, void* st
     HIP_TRY(launch_psnr(x, gt, out, e->cfg.n, e->cfg.h * e->cfg.w, (hipStream_t)stream));
     return PNP_OK;
     PNP_API_END("pnp_psnr")
+}
+
+int pnp_ssim(pnp_handle e, const float* x, const float* gt, float data_range, float k1, float k2, int radius, int flags, float* out,
+             float* map, void* stream) {
+    PNP_API_BEGIN
+    // scalar arguments first, so that every rejection happens before any HIP call
+    if (radius < 1 || radius > kSsimMaxRadius) return fail(PNP_ERR_INVALID, "pnp_ssim: radius must be 1..%d (got %d)", kSsimMaxRadius, radius);
+    if (!(data_range > 0.f) || !std::isfinite(data_range)) return fail(PNP_ERR_INVALID, "pnp_ssim: data_range must be > 0 (got %g)", (double)data_range);
+    if (!std::isfinite(k1) || !std::isfinite(k2)) return fail(PNP_ERR_INVALID, "pnp_ssim: k1, k2 must be finite");
+    if (flags & ~PNP_SSIM_CLAMP_X) return fail(PNP_ERR_INVALID, "pnp_ssim: unknown flag bits 0x%x", (unsigned)(flags & ~PNP_SSIM_CLAMP_X));
+    if (!e || !x || !gt || !out) return fail(PNP_ERR_INVALID, "pnp_ssim: null argument");
+    PNP_ON_DEVICE(e);
+    SsimArgs a{};
+    a.x = x; a.gt = gt; a.map = map; a.partial = e->d_ssim_part; a.out = out;
+    a.H = e->cfg.h; a.W = e->cfg.w; a.radius = radius; a.clamp_x = (flags & PNP_SSIM_CLAMP_X) ? 1 : 0;
+    const double c1 = (double)k1 * data_range, c2 = (double)k2 * data_range;
+    a.c1 = (float)(c1 * c1); a.c2 = (float)(c2 * c2);
+    // scipy.ndimage._gaussian_kernel1d(sigma = 1.5, order 0, radius): exp(-x^2 / (2 sigma^2)) normalised to sum 1, in double
+    double tap[2 * kSsimMaxRadius + 1], sum = 0.0;
+    for (int i = -radius; i <= radius; ++i) sum += (tap[i + radius] = std::exp(-0.5 / (1.5 * 1.5) * (double)i * (double)i));
+    for (int i = 0; i <= 2 * radius; ++i) a.w[i] = (float)(tap[i] / sum);
+    Prof p(e, (hipStream_t)stream, 5, -1);
+    HIP_TRY(launch_ssim(a, e->cfg.n, (hipStream_t)stream));
+    return PNP_OK;
+    PNP_API_END("pnp_ssim")
 }
 
 size_t pnp_snapshot_bytes(pnp_handle e) {

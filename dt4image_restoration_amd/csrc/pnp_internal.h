@@ -184,4 +184,21 @@ hipError_t launch_admm_xcd(const float* x, float2* z, float2* u, float2* work, c
                            const uint8_t* masks, int mask_n, const float* mu, const float* tact, unsigned* ctr, unsigned epoch, int N, int H, hipStream_t s);
 hipError_t launch_psnr(const float* x, const float* gt, float* out, int N, int HW, hipStream_t s);
 
+// ---- metrics (metrics_kernels.hip) ---------------------------------------------------------------
+static constexpr int kSsimMaxRadius = 16;
+struct SsimArgs {
+    const float* x;      // [N,H,W]
+    const float* gt;     // [N,H,W]
+    float* map;          // [N,H,W] or nullptr (no map store)
+    double* partial;     // [N, ssim_tiles(H, W)] per-tile sums
+    float* out;          // [N] mean of the map
+    int H, W;
+    int radius;          // 1..kSsimMaxRadius
+    int clamp_x;         // clamp x to [0, 1] on load
+    float c1, c2;
+    float w[2 * kSsimMaxRadius + 1];   // normalised Gaussian taps (computed in double on the host), w[0 .. 2 radius]
+};
+int ssim_tiles(int H, int W);
+hipError_t launch_ssim(const SsimArgs& a, int N, hipStream_t s);
+
 }  // namespace pnp

@@ -46,6 +46,8 @@ class GreedyResult:
     stop_time: torch.Tensor     # [N] step at which each slice stopped (1..max_timesteps)
     actions: torch.Tensor       # [N, max_timesteps, 3] actions handed to the env (model order)
     x: torch.Tensor             # [N,1,H,W] final images (device)
+    ssim: Optional[torch.Tensor] = None          # [N,1] final SSIM (CPU), env.compute_ssim beside `reward` (GreedyEvaluator(ssim=True))
+    initial_ssim: Optional[torch.Tensor] = None  # [N,1] SSIM of x0
 
 
 @dataclass
@@ -67,7 +69,7 @@ class PolicyContext:
 class GreedyEvaluator:
     def __init__(self, model, env, action_dim: int = 3, max_timesteps: int = 30, block_size: int = 18,
                  device_type="cuda", cache_state_embeddings: bool = True, sync_every: int = 1,
-                 use_graphs: Optional[bool] = None):
+                 use_graphs: Optional[bool] = None, ssim: bool = False):
         self.model = model.to(device_type).eval()
         self.env = env
         self.action_dim = action_dim
@@ -85,6 +87,8 @@ class GreedyEvaluator:
         self.use_graphs = (self.device.type == "cuda" and cache_state_embeddings) if use_graphs is None else \
             (bool(use_graphs) and self.device.type == "cuda" and cache_state_embeddings)
         self._graphs = {}
+        # also score SSIM (env.compute_ssim) wherever PSNR (env.compute_reward) is scored: GreedyResult.ssim / initial_ssim
+        self.ssim = bool(ssim)
 
     # ---- context ---------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -320,6 +324,8 @@ class GreedyEvaluator:
             out["reward"] = torch.as_tensor(scorer(states)).reshape(n, 1).float().cpu()
         else:
             out["reward"] = env.compute_reward(states["x"], states["gt"])
+            if self.ssim:
+                out["ssim"] = env.compute_ssim(states["x"], states["gt"])
         out["stop_time"] = stop_time.cpu()
 
     def rollout_rows(self, states, action, pred_rtg, start_times: torch.Tensor, ctx: PolicyContext, scorer=None,
@@ -384,12 +390,13 @@ class GreedyEvaluator:
         self.observe(ctx, 0, policy_observation(first_state.to(dev).float().reshape(n, 1, *states["z"].shape[-2:])))
         ctx.er[:, 0, 0] = rtg.reshape(n).to(dev).float()
         initial_reward = env.compute_reward(states["x"], states["gt"])
+        initial_ssim = env.compute_ssim(states["x"], states["gt"]) if self.ssim else None
         action, pred_rtg = self._initial(ctx)
         yield "policy"
         ro: Dict[str, torch.Tensor] = {}
         yield from self._rollout_phases(states, action, pred_rtg, 1, ctx, None, env, ro)
         out["result"] = GreedyResult(reward=ro["reward"], initial_reward=initial_reward, stop_time=ro["stop_time"],
-                                     actions=ctx.ea.cpu(), x=states["x"])
+                                     actions=ctx.ea.cpu(), x=states["x"], ssim=ro.get("ssim"), initial_ssim=initial_ssim)
 
     def run_pipelined(self, mat: Dict[str, torch.Tensor], rtg: torch.Tensor, task: torch.Tensor, parts: int = 2) -> GreedyResult:
         """`run` with the batch cut into `parts` contiguous sub-batches that advance on their own HIP streams, half a period
@@ -452,9 +459,11 @@ class GreedyEvaluator:
             cur.wait_stream(streams[k])
         res = [o["result"] for o in outs]
         for r in res:                                       # allocated on a sub-batch's stream, read from here on on the caller's
-            for t in (r.reward, r.initial_reward, r.stop_time, r.actions, r.x):
-                if t.is_cuda:
+            for t in (r.reward, r.initial_reward, r.stop_time, r.actions, r.x, r.ssim, r.initial_ssim):
+                if t is not None and t.is_cuda:
                     t.record_stream(cur)
         return GreedyResult(reward=torch.cat([r.reward for r in res]), initial_reward=torch.cat([r.initial_reward for r in res]),
                             stop_time=torch.cat([r.stop_time for r in res]), actions=torch.cat([r.actions for r in res]),
-                            x=torch.cat([r.x for r in res]))
+                            x=torch.cat([r.x for r in res]),
+                            ssim=torch.cat([r.ssim for r in res]) if self.ssim else None,
+                            initial_ssim=torch.cat([r.initial_ssim for r in res]) if self.ssim else None)

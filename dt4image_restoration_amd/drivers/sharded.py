@@ -3,7 +3,8 @@
 The loop the reference runs one image at a time on one GPU (`Evaluator._generate` / `run_greedy`,
 /root/reference/evaluation/eval.py:105-143,189-220) is cut by slices: rank r of W owns the contiguous shard
 `sharding.shard_range(total, r, W)`, runs the batched greedy rollout on it with NO data-path collective (slices are
-independent units, env.py:74-100), and the per-slice results - final PSNR, initial PSNR, stop iteration - are assembled on
+independent units, env.py:74-100), and the per-slice results - final PSNR, initial PSNR, stop iteration (and final / initial SSIM
+when the evaluator scores it) - are assembled on
 every rank by ONE padded all_gather each (`sharding.gather_per_slice`: RCCL over xGMI on GPUs via backend "nccl", gloo on
 CPU in the tests).  Weights are replicated.  One process per GPU; launched by `torch.distributed.run` (bench.py --mode
 greedy, `python -m torch.distributed.run ... -m dt4image_restoration_amd.cli ... eval`) or stand-alone (world size 1).
@@ -28,6 +29,8 @@ class ShardedResult:
     local_range: Tuple[int, int]  # this rank's [start, stop)
     seconds: float                # this rank's rollout wall time (reset + DT-driven steps), max over ranks
     steps: int                    # env steps of the longest episode in the job (max stop_time)
+    ssim: Optional[torch.Tensor] = None          # [total, 1] final SSIM (evaluator built with ssim=True), gathered like `reward`
+    initial_ssim: Optional[torch.Tensor] = None  # [total, 1] SSIM of x0
 
 
 def world_info(group=None) -> Tuple[int, int]:
@@ -56,8 +59,10 @@ def run_sharded_greedy(evaluator: GreedyEvaluator, total: int,
     if b > a:
         res = evaluator.run_pipelined(mat, rtg, task, pipeline) if pipeline > 1 else evaluator.run(mat, rtg, task)
         local = (res.reward.to(dev).float(), res.initial_reward.to(dev).float(), res.stop_time.to(dev))
+        local_ssim = (res.ssim.to(dev).float(), res.initial_ssim.to(dev).float()) if evaluator.ssim else None
     else:                                                 # more ranks than slices: an empty shard still joins the gather
         local = (torch.zeros((0, 1), device=dev), torch.zeros((0, 1), device=dev), torch.zeros((0,), dtype=torch.int64, device=dev))
+        local_ssim = (torch.zeros((0, 1), device=dev), torch.zeros((0, 1), device=dev)) if evaluator.ssim else None
     if sync is not None:
         sync()
     if world > 1:
@@ -69,8 +74,12 @@ def run_sharded_greedy(evaluator: GreedyEvaluator, total: int,
     reward = sharding.gather_per_slice(local[0], total, group)
     initial = sharding.gather_per_slice(local[1], total, group)
     stop = sharding.gather_per_slice(local[2], total, group)
+    ssim = initial_ssim = None
+    if local_ssim is not None:                            # outside the timed region too
+        ssim = sharding.gather_per_slice(local_ssim[0], total, group).cpu()
+        initial_ssim = sharding.gather_per_slice(local_ssim[1], total, group).cpu()
     return ShardedResult(reward=reward.cpu(), initial_reward=initial.cpu(), stop_time=stop.cpu(), local_range=(a, b),
-                         seconds=float(dt.item()), steps=int(stop.max()) if total else 0)
+                         seconds=float(dt.item()), steps=int(stop.max()) if total else 0, ssim=ssim, initial_ssim=initial_ssim)
 
 
 def run_sharded_mcts(tree, total: int, load_shard: Callable[[int, int], Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor]],

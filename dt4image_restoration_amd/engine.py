@@ -168,6 +168,19 @@ class PnPEngine:
         _lib.check(self.lib.pnp_psnr(self._h, x.data_ptr(), gt.data_ptr(), out.data_ptr(), self._stream()), "pnp_psnr")
         return out
 
+    def ssim(self, x: torch.Tensor, gt: torch.Tensor, data_range: float = 1.0, k1: float = 0.01, k2: float = 0.03,
+             radius: int = 8, clamp: bool = True, return_map: bool = False):
+        """Per-slice SSIM (pnp_ssim): Gaussian window sigma 1.5 with `radius` taps each side (8 = the reference's win_size 11),
+        'reflect' border, mean over all H x W pixels.  clamp: x clamped to [0, 1] first, like `psnr`.  Returns [N] on the device,
+        and with return_map also the SSIM map [N,1,H,W]."""
+        nhw = self.n * self.h * self.w
+        self._chk(x, torch.float32, nhw, "x"); self._chk(gt, torch.float32, nhw, "gt")
+        out = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        smap = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device) if return_map else None
+        _lib.check(self.lib.pnp_ssim(self._h, x.data_ptr(), gt.data_ptr(), float(data_range), float(k1), float(k2), int(radius),
+                                     _lib.PNP_SSIM_CLAMP_X if clamp else 0, out.data_ptr(), _ptr(smap), self._stream()), "pnp_ssim")
+        return (out, smap) if return_map else out
+
     def snapshot(self, x: torch.Tensor, z: torch.Tensor, u: torch.Tensor, t_state: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One packed device buffer [x | z | u | T] (pnp_snapshot): a tree-search node's copy of the iterate."""

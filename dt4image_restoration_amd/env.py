@@ -5,6 +5,8 @@ reference (`Evaluator.run_greedy` eval.py:189-220, `run_mcts` mcts.py:212-258) c
     reset(data, device) -> OrderedDict          step(states, action_dict) -> (states, done)
     get_policy_ob(states)                       compute_reward(x, gt)       run_no_ref_reward(states)
 
+plus `compute_ssim(x, gt)`, the reference's `calculate_ssim` on the image `compute_reward` judges.
+
 Differences, all documented in DESIGN.md:
   * any batch N and any power-of-two H, W (the reference is hard-wired to 1 x 128 x 128, env.py:44,64,115)
   * per-slice mu / sigma_d / T (1-element tensors broadcast, as the reference's drivers pass)
@@ -135,6 +137,17 @@ class PnPEnv:
         eng = self._engine if self._engine is not None and (self._engine.n, self._engine.h, self._engine.w) == (n, h, w) \
             else self._engine_for(n, h, w, x.device)
         return eng.psnr(xr, gt.reshape(n, 1, h, w).contiguous()).reshape(n, 1).cpu()
+
+    def compute_ssim(self, x: torch.Tensor, gt: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
+        """SSIM of clamp(Re x, 0, 1) against gt (the image `compute_reward` judges), [N,1] on the CPU: calculate_ssim
+        (evaluation/utils/transformations.py:61-95) with the reference's window (win_size 11) and k1, k2, per slice."""
+        gt = gt.to(x.device).float()
+        h, w = gt.shape[-2:]
+        n = gt.numel() // (h * w)
+        xr = (x.real if x.is_complex() else x).float().reshape(n, 1, h, w).contiguous()
+        eng = self._engine if self._engine is not None and (self._engine.n, self._engine.h, self._engine.w) == (n, h, w) \
+            else self._engine_for(n, h, w, x.device)
+        return eng.ssim(xr, gt.reshape(n, 1, h, w).contiguous(), data_range=data_range, clamp=True).reshape(n, 1).cpu()
 
     def run_no_ref_reward(self, state) -> float:
         """env.py:42-54 scored with ARNIQA fetched from the network; here an injected callable

@@ -143,6 +143,19 @@ int pnp_prox_dual(pnp_handle h, const float* mu, const float* t_action, const fl
  * 10*log10(1/mean((clamp(x,0,1)-gt)^2)).  x, gt DEVICE float32 [N,1,H,W]; out DEVICE float32 [N]. */
 int pnp_psnr(pnp_handle h, const float* x, const float* gt, float* out, void* stream);
 
+/* Replaces: calculate_ssim (evaluation/utils/transformations.py:61-95), per slice, on the device:
+ *   G = gaussian_filter(sigma = 1.5) with `radius` taps each side (scipy's radius int(1.5 * truncate + 0.5), truncate =
+ *   win_size // 2: 8 for the default win_size 11), boundary 'reflect';  c1 = (k1 data_range)^2, c2 = (k2 data_range)^2;
+ *   map = ((2 mu_x mu_y + c1)(2 sigma_xy + c2)) / ((mu_x^2 + mu_y^2 + c1)(sigma_x^2 + sigma_y^2 + c2)), out[n] = mean of
+ *   slice n's map over all H x W pixels (no border crop).
+ *   x, gt : DEVICE float32 [N,1,H,W] of the handle's shape;  out : DEVICE float32 [N];  map : DEVICE float32 [N,H,W] or NULL
+ *   (no map store).  flags: PNP_SSIM_CLAMP_X or 0.  radius 1..16, data_range > 0; any handle (PNP_FLAG_NO_DENOISER too).
+ * Filters in float32 with the taps computed in double; the per-slice mean is summed in double in a fixed order (bitwise
+ * reproducible, no atomics).  Uses a partial-sum buffer of the handle's workspace: calls on one handle are stream-ordered. */
+#define PNP_SSIM_CLAMP_X 1   /* clamp x to [0,1] before filtering (what pnp_psnr does); 0 = the reference's calculate_ssim */
+int pnp_ssim(pnp_handle h, const float* x, const float* gt, float data_range, float k1, float k2, int radius, int flags,
+             float* out, float* map, void* stream);
+
 /* ---- tree search support --------------------------------------------------------------------- */
 
 /* Replaces: the per-child copy of `states` in expand_tree (evaluation/mcts.py:118-128), which the reference gets for
