@@ -17,16 +17,14 @@
 //                  (16 adjacent columns per workgroup so every global access is a 128-B line)
 //   rows-inverse : row IFFT -> z;  u += x - z                         (reads 20 B/px, writes 16)
 // Twiddles come from a host-computed (double precision) table.
+// Every kernel here serves handles whose H and W are both powers of two; a side of 2^a * 5^b (80 .. 800) runs the
+// mixed-radix kernels of fft_mixed_kernels.hip instead.
 #include "pnp_internal.h"
+#include "fft_common.h"
 #include <cstdlib>
 
 namespace pnp {
 
-// (explicit fused form: `a.x * b.x - a.y * b.y` has two legal contractions with different roundings, and hipcc picked different ones for the
-// same pass body inlined into two kernels - the per-XCD persistent kernel and the three-launch path must agree bit for bit)
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
-}
 // A complex64 load that never hits (or fills) the CU's vector L1: agent-scope relaxed atomic load = `global_load_dwordx2 ... sc1`.  The per-XCD
 // persistent kernel reads the scratch other CUs of its XCD wrote earlier in the SAME launch through this (the L2 they share is coherent, the L1s are not;
 // `buffer_inv sc0` is a no-op outside threadgroup-split mode and `buffer_inv sc1` drops the whole L2: both measured, profiles/r05_ablation.md).
@@ -39,8 +37,6 @@ __device__ __forceinline__ float2 ld_c64(const float2* p) {
         return *p;
     }
 }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 
 // `lines` independent length-L transforms, line i at [i*lstr, i*lstr+L) of src; ping-pongs src <-> dst.
 // tw[m] = exp(-2 pi i m / L) in LDS.  Caller has synchronised the loads; returns the buffer holding the
@@ -213,13 +209,6 @@ __device__ __forceinline__ void fft_lines_inplace(float2* buf, const float2* tw)
 // distinct banks in all three), lines SK256_LS elements apart.
 static constexpr int SK256_LS = 273;
 __device__ __forceinline__ int sk256(int i) { return i + (i >> 4); }
-
-template <bool INV>
-__device__ __forceinline__ void dft4_inplace(float2& a, float2& b, float2& c, float2& d) {
-    const float2 t0 = cadd(a, c), t1 = csub(a, c), t2 = cadd(b, d), e = csub(b, d);
-    const float2 t3 = INV ? make_float2(-e.y, e.x) : make_float2(e.y, -e.x);        // (+/- i) * (b - d)
-    a = cadd(t0, t2); b = cadd(t1, t3); c = csub(t0, t2); d = csub(t1, t3);
-}
 
 // v[0..15] -> its 16-point DFT, result X[p + 4 s] in v[4 p + s] (two radix-4 stages, constant twiddles w16^(r p) between)
 template <bool INV>
@@ -1094,7 +1083,10 @@ __global__ void reset_kernel(const float2* __restrict__ x0, const float2* __rest
             z[i] = v;
             u[i] = make_float2(0.f, 0.f);
         }
-        const size_t ps = (size_t)(k1 ^ (H >> 1)) * W + (k2 ^ (W >> 1));      // S: index + N/2 mod N (N power of two)
+        // S: index + N/2 mod N (add-mod: the XOR form is only right for powers of two; the same indices there).  The sign stays
+        // (-1)^(k1 + k2) for every accepted size: N/2 is even, so rolling by N/2 multiplies bin k by (-1)^k
+        const int s1 = k1 < (H >> 1) ? k1 + (H >> 1) : k1 - (H >> 1), s2 = k2 < (W >> 1) ? k2 + (W >> 1) : k2 - (W >> 1);
+        const size_t ps = (size_t)s1 * W + s2;
         const float sg = ((k1 + k2) & 1) ? -1.f : 1.f;
         const float2 yy = y0[n * hw + ps];
         y0s[i] = make_float2(sg * yy.x, sg * yy.y);

@@ -117,6 +117,7 @@ struct pnp_engine {
 namespace {
 
 bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+#define PNP_KSPACE_SIZES "16, 32, 64, 80, 128, 160, 256, 320, 400, 512, 640, 800, 1024"   // every L with kspace_len_ok(L)
 
 // One HIP event pair around a kernel launch - or, with `defer_end`, around a RUN of same-class launches that follow each
 // other on the stream (the 26 conv3x3 launches of a denoiser forward): `count` launches, closed by end().  Event records
@@ -293,6 +294,19 @@ int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float
         Prof p(e, s, 4, -1);
         HIP_TRY(launch_admm_xcd(x, z, u, e->d_work, e->plan.tw_w, e->d_y0s, e->d_masks, e->mask_n, mu, tact, e->d_fftq, e->fftq_epoch, N, H, s));
         ++e->fftq_epoch;
+        return PNP_OK;
+    }
+    if (!is_pow2(H) || !is_pow2(W)) {                     // a side of 2^a * 5^b: the mixed-radix passes (fft_mixed_kernels.hip)
+        {
+            Prof p(e, s, 3, -1);
+            HIP_TRY(launch_fft_rows_fwd_mixed(x, u, e->d_work, e->plan.tw_w, tact, N, H, W, s));
+        }
+        {
+            Prof p(e, s, 4, -1);
+            HIP_TRY(launch_fft_cols_prox_mixed(e->d_work, e->plan.tw_h, e->d_y0s, e->d_masks, e->mask_n, mu, tact, N, H, W, s));
+        }
+        Prof p(e, s, 3, -1);
+        HIP_TRY(launch_fft_rows_inv_mixed(e->d_work, x, z, u, e->plan.tw_w, tact, N, H, W, s));
         return PNP_OK;
     }
     {
@@ -581,8 +595,8 @@ int pnp_reset(pnp_handle e, const float* x0, const float* y0, const uint8_t* mas
     PNP_API_BEGIN
     if (!e || !x0 || !y0 || !mask || !x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_reset: null argument");
     if (mask_n != 1 && mask_n != e->cfg.n) return fail(PNP_ERR_INVALID, "pnp_reset: mask_n must be 1 or n=%d", e->cfg.n);
-    if (!is_pow2(e->cfg.h) || !is_pow2(e->cfg.w))
-        return fail(PNP_ERR_INVALID, "pnp_reset: the k-space stage needs power-of-two h, w (got %dx%d)", e->cfg.h, e->cfg.w);
+    if (!kspace_len_ok(e->cfg.h) || !kspace_len_ok(e->cfg.w))
+        return fail(PNP_ERR_INVALID, "pnp_reset: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", e->cfg.h, e->cfg.w);
     PNP_ON_DEVICE(e);
     e->mask_n = mask_n;
     // the two experimental in-launch hand-over schemes keep counters between launches (PNP_SPLITK_INLAUNCH: arrival counters that return to zero;
@@ -601,8 +615,8 @@ int pnp_set_kspace(pnp_handle e, const float* y0, const uint8_t* mask, int mask_
     PNP_API_BEGIN
     if (!e || !y0 || !mask) return fail(PNP_ERR_INVALID, "pnp_set_kspace: null argument");
     if (mask_n != 1 && mask_n != e->cfg.n) return fail(PNP_ERR_INVALID, "pnp_set_kspace: mask_n must be 1 or n=%d", e->cfg.n);
-    if (!is_pow2(e->cfg.h) || !is_pow2(e->cfg.w))
-        return fail(PNP_ERR_INVALID, "pnp_set_kspace: the k-space stage needs power-of-two h, w (got %dx%d)", e->cfg.h, e->cfg.w);
+    if (!kspace_len_ok(e->cfg.h) || !kspace_len_ok(e->cfg.w))
+        return fail(PNP_ERR_INVALID, "pnp_set_kspace: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", e->cfg.h, e->cfg.w);
     PNP_ON_DEVICE(e);
     e->mask_n = mask_n;
     HIP_TRY(launch_reset(nullptr, (const float2*)y0, mask, mask_n, nullptr, nullptr, nullptr, e->d_y0s, e->d_masks,
@@ -646,9 +660,19 @@ int pnp_fft2c(pnp_handle e, const float* in, float* out, int batch, int hh, int 
     if (hh != e->cfg.h || ww != e->cfg.w || batch < 1 || batch > e->cfg.n)
         return fail(PNP_ERR_INVALID, "pnp_fft2c: shape [%d,%d,%d] does not fit the engine [%d,%d,%d]", batch, hh, ww,
                     e->cfg.n, e->cfg.h, e->cfg.w);
-    if (!is_pow2(hh) || !is_pow2(ww)) return fail(PNP_ERR_INVALID, "pnp_fft2c: power-of-two sizes only");
+    if (!kspace_len_ok(hh) || !kspace_len_ok(ww))
+        return fail(PNP_ERR_INVALID, "pnp_fft2c: h, w must be in {" PNP_KSPACE_SIZES "} (got %dx%d)", hh, ww);
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
+    if (!is_pow2(hh) || !is_pow2(ww)) {                   // a side of 2^a * 5^b: the mixed-radix passes, shifts as add-mod by L/2
+        {
+            Prof p(e, s, 3, -1);
+            HIP_TRY(launch_fft_rows_mixed((const float2*)in, (float2*)out, e->plan.tw_w, batch, hh, ww, inverse, ww / 2, s));
+        }
+        Prof p(e, s, 4, -1);
+        HIP_TRY(launch_fft_cols_mixed((float2*)out, e->plan.tw_h, batch, hh, ww, inverse, hh / 2, s));
+        return PNP_OK;
+    }
     // fft_c = S . FFT . S : fold both shifts into the load/store indices of the two passes
     {
         Prof p(e, s, 3, -1);

@@ -167,6 +167,17 @@ hipError_t launch_fft_cols_prox(float2* work, const float2* tw, const float2* y0
                                 int mask_n, const float* mu, const float* tact, int N, int H, int W, hipStream_t s);
 hipError_t launch_fft_rows_inv_admm(const float2* work, const float* x, float2* z, float2* u, const float2* tw,
                                     const float* tact, int N, int H, int W, hipStream_t s);
+// sides of 2^a * 5^b (fft_mixed_kernels.hip): the same passes for a handle with a side that is not a power of two
+bool kspace_len_ok(int L);   // 16 <= L <= 1024, 16 | L, L = 2^a * 5^b
+hipError_t launch_fft_rows_mixed(const float2* in, float2* out, const float2* tw, int batch, int H, int W, int inverse, int shift,
+                                 hipStream_t s);
+hipError_t launch_fft_cols_mixed(float2* data, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s);
+hipError_t launch_fft_rows_fwd_mixed(const float* x, const float2* u, float2* work, const float2* tw, const float* tact, int N, int H,
+                                     int W, hipStream_t s);
+hipError_t launch_fft_cols_prox_mixed(float2* work, const float2* tw, const float2* y0s, const uint8_t* masks, int mask_n,
+                                      const float* mu, const float* tact, int N, int H, int W, hipStream_t s);
+hipError_t launch_fft_rows_inv_mixed(const float2* work, const float* x, float2* z, float2* u, const float2* tw, const float* tact,
+                                     int N, int H, int W, hipStream_t s);
 
 // x0 / x / z / u may all be null: only the episode constants (y0s, masks) are rebuilt
 // 128 x 128 only: the whole stage (both transforms each way, the solve, the dual update) in one workgroup per slice

@@ -8,7 +8,8 @@ reference (`Evaluator.run_greedy` eval.py:189-220, `run_mcts` mcts.py:212-258) c
 plus `compute_ssim(x, gt)`, the reference's `calculate_ssim` on the image `compute_reward` judges.
 
 Differences, all documented in DESIGN.md:
-  * any batch N and any power-of-two H, W (the reference is hard-wired to 1 x 128 x 128, env.py:44,64,115)
+  * any batch N and H, W each one of 16..1024 of the form 2^a * 5^b: the powers of two and 80, 160, 320, 400, 640, 800
+    (fastMRI's 320 x 320, 640 x 320; the reference is hard-wired to 1 x 128 x 128, env.py:44,64,115)
   * per-slice mu / sigma_d / T (1-element tensors broadcast, as the reference's drivers pass)
   * states['x'|'z'|'u'] are persistent device tensors updated IN PLACE by `step` (the reference rebinds
     freshly allocated tensors, env.py:95-97); use `snapshot`/`restore` to keep an old state (MCTS)

@@ -1,6 +1,7 @@
 """`fft` / `ifft`: drop-ins for the reference's centred orthonormal FFT pair
 (/root/reference/evaluation/utils/transformations.py:6-19), running the LDS Stockham kernels of
-libpnpadmm.so.  Power-of-two sizes >= 16 (the reference only ever passes 128 x 128).
+libpnpadmm.so.  Sides of 16..1024 of the form 2^a * 5^b: the powers of two and 80, 160, 320, 400, 640, 800 (the
+reference only ever passes 128 x 128).
 
 `calculate_ssim`: drop-in for the reference's Gaussian-window SSIM (transformations.py:61-95, scipy on the host),
 running pnp_ssim on the GPU.  Sides that are multiples of 16 (16..1024)."""

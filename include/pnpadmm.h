@@ -23,8 +23,10 @@
  *     float*; images are [N,1,H,W] contiguous exactly like the reference's tensors.
  *   - returns PNP_OK (0) or a negative pnp_status; pnp_last_error() gives the message of the last
  *     failure on the calling thread.  A handle is not thread-safe; use one per GPU/process.
- *   - H and W must be powers of two >= 16 for the ADMM step / FFT (the reference is hard-wired to
- *     128, env.py:64) and multiples of 16 for the denoiser alone (noise.py:49-53 pad is then a no-op).
+ *   - H and W must each be one of 16, 32, 64, 80, 128, 160, 256, 320, 400, 512, 640, 800, 1024 (the
+ *     multiples of 16 up to 1024 of the form 2^a * 5^b, mixed freely, e.g. 640 x 320) for the ADMM step /
+ *     FFT (the reference is hard-wired to 128, env.py:64); any other size is refused with PNP_ERR_INVALID.
+ *     The denoiser alone takes multiples of 16 up to 1024 (noise.py:49-53 pad is then a no-op).
  */
 #ifndef PNPADMM_H
 #define PNPADMM_H
@@ -130,7 +132,8 @@ int pnp_denoise(pnp_handle h, const float* x_in, const float* sigma, float* out,
 
 /* Replaces: fft(img) / ifft(img) (evaluation/utils/transformations.py:6-12 / :14-19): centred
  * (ifftshift -> fftn/ifftn norm='ortho' -> fftshift) 2-D transform over the last two dims.
- * in/out DEVICE complex64 [batch,H,W] (may alias); batch*H*W must fit the engine's n*h*w. */
+ * in/out DEVICE complex64 [batch,H,W] (may alias); hh, ww are the engine's h, w and batch <= n.
+ * Sides of 2^a * 5^b (80 .. 800) run mixed-radix passes (radix 5, then radix 4 / 2); other sizes are refused. */
 int pnp_fft2c(pnp_handle h, const float* in, float* out, int batch, int hh, int ww, int inverse, void* stream);
 
 /* Replaces: the data-fidelity half of PnPEnv.step (evaluation/env.py:87-93) on its own:
