@@ -14,6 +14,10 @@ PNP_FLAG_KEEP_STAGES = 4
 PNP_FLAG_BF16_CONVS = 8
 PNP_FLAG_PROFILE_LAYERS = 16
 PNP_SSIM_CLAMP_X = 1
+PNP_RES_COLS = 6
+PNP_RES_DELTA = 1
+PNP_RES_DC = 2
+RESIDUAL_COLUMNS = ("primal", "dx", "dz", "du", "delta", "dc")      # columns of pnp_residuals' [N, 6] output
 PROFILE_CLASSES = 6
 PROFILE_CLASS_NAMES = ("conv3x3_mfma", "conv_first", "conv_last", "fft_rows", "fft_cols_prox", "other")
 N_LAYERS = 28
@@ -40,6 +44,7 @@ SIGNATURES = {
     "pnp_prox_dual": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _fp, _vp]),
     "pnp_psnr": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),
     "pnp_ssim": (C.c_int, [C.c_void_p, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _fp, _fp, _vp]),
+    "pnp_residuals": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp, C.c_int, _fp, _vp]),
     "pnp_snapshot_bytes": (C.c_size_t, [C.c_void_p]),
     "pnp_snapshot": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _vp, _vp]),
     "pnp_restore": (C.c_int, [C.c_void_p, _vp, _fp, _fp, _fp, _fp, _vp]),

@@ -4,6 +4,15 @@
     python -m dt4image_restoration_amd.cli --block_size 18 --n_embeds 9 mcts --rtg 5  --max_timesteps 30
     python -m dt4image_restoration_amd.cli --block_size 18 --n_embeds 6 flex --max_timesteps 30
 
+plus `fixed`, which the reference does not have: plain PnP-ADMM with a fixed mu and a geometric sigma_d schedule, stopped per slice
+by the fixed-point criterion delta <= tol (drivers/fixed.py; no policy involved):
+
+    python -m dt4image_restoration_amd.cli --block_size 18 --n_embeds 9 --size 320 fixed --mu 0.3 --sigma-start 50 --sigma-end 5 \
+        --tol 0.005 --max_iter 30 --dc
+
+`eval` and `flex` take `--residuals` (adds the final iterate's primal residual and k-space data misfit to their lines), `mcts` takes
+`--scorer neg_dc` (rollouts scored by minus the data misfit - a reference-free number - instead of the smoothness stub).
+
 Multi-GPU (BASELINE configs[2]): launch the same command under `python -m torch.distributed.run --nproc-per-node N
 --master-addr 127.0.0.1 -m dt4image_restoration_amd.cli ... eval|mcts|flex ...`: every rank takes a contiguous shard of each
 set's images (drivers/sharded.py), the per-image PSNR / stop iteration are gathered over RCCL, rank 0 prints.
@@ -36,7 +45,10 @@ def _build(args, mode):
         model.load_state_dict(weights.generate_policy_weights(model, args.seed, t_bias=-1.0, head_gain=8.0))
     den = UNetDenoiser2D(ckpt_path=args.denoiser_ckpt) if args.denoiser_ckpt else UNetDenoiser2D.seeded(args.seed)
     scorer = (lambda st: 1.0 / (1e-3 + (st["x"] - torch.nn.functional.avg_pool2d(st["x"], 3, 1, 1)).pow(2).mean(dim=(1, 2, 3))))
-    return model, PnPEnv(max_episode_step=30, denoiser=den, device_type="cuda", no_ref_scorer=None), scorer
+    env = PnPEnv(max_episode_step=30, denoiser=den, device_type="cuda", no_ref_scorer=None)
+    if getattr(args, "scorer", "stub") == "neg_dc":            # minus the k-space data misfit of the rollout's final iterate (pnp_residuals)
+        scorer = (lambda st: -env.residuals(st, dc=True)[:, 5])
+    return model, env, scorer
 
 
 def _sets(args, flex_target=None):
@@ -74,13 +86,26 @@ def main(argv=None):
         sp.add_argument("--max_timesteps", type=int, default=30)
         if name == "mcts":
             sp.add_argument("--rollouts", type=int, default=30)
-    sub.add_parser("flex").add_argument("--max_timesteps", type=int, default=30)
+            sp.add_argument("--scorer", choices=("stub", "neg_dc"), default="stub",
+                            help="no-reference score of a rollout: the smoothness stub, or minus the k-space data misfit")
+        else:
+            sp.add_argument("--residuals", action="store_true", help="add `primal` and `dc` of the final iterates to each line")
+    sp = sub.add_parser("flex")
+    sp.add_argument("--max_timesteps", type=int, default=30)
+    sp.add_argument("--residuals", action="store_true", help="add `primal` and `dc` of the final iterates to each line")
+    sp = sub.add_parser("fixed", help="plain PnP-ADMM: fixed mu, geometric sigma_d schedule, stopped by delta <= tol")
+    sp.add_argument("--mu", type=float, default=0.3)
+    sp.add_argument("--sigma-start", type=float, default=50.0, help="sigma_d of the first iteration, in /255 units")
+    sp.add_argument("--sigma-end", type=float, default=5.0, help="sigma_d of iteration max_iter (geometric decay), in /255 units")
+    sp.add_argument("--tol", type=float, default=None, help="stop a slice once delta <= tol (default: run max_iter iterations)")
+    sp.add_argument("--max_iter", type=int, default=30)
+    sp.add_argument("--dc", action="store_true", help="add the final k-space data misfit to each line")
     args = ap.parse_args(argv)
 
     from . import data as D
     from .drivers.greedy import GreedyEvaluator
     from .drivers.mcts import MCTS
-    from .drivers.sharded import run_sharded_greedy, run_sharded_mcts
+    from .drivers.sharded import run_sharded_fixed, run_sharded_greedy, run_sharded_mcts
     out = []
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     dist = None
@@ -88,10 +113,38 @@ def main(argv=None):
         import torch.distributed as dist
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl", device_id=torch.device("cuda", torch.cuda.current_device()))
+    if args.mode == "fixed":
+        from .denoiser import UNetDenoiser2D
+        from .drivers.fixed import FixedScheduleSolver
+        from .env import PnPEnv
+        den = UNetDenoiser2D(ckpt_path=args.denoiser_ckpt) if args.denoiser_ckpt else UNetDenoiser2D.seeded(args.seed)
+        env = PnPEnv(max_episode_step=args.max_iter, denoiser=den, device_type="cuda")
+        solver = FixedScheduleSolver(env, max_iter=args.max_iter, tol=args.tol, sync_every=5, dc=args.dc,
+                                     device_type=torch.device("cuda", torch.cuda.current_device()))
+        t = np.arange(args.max_iter) / max(args.max_iter - 1, 1)
+        sigma = (args.sigma_start * (args.sigma_end / args.sigma_start) ** t / 255.0).astype(np.float32)
+        for name, total, load in _sets(args):
+            def load_shard(a, b, load=load):
+                batch, _ = load(a, b)
+                mat = {k: torch.from_numpy(np.asarray(v)) for k, v in batch.items()}
+                return mat, np.full((b - a, args.max_iter), args.mu, dtype=np.float32), np.tile(sigma, (b - a, 1))
+            r = run_sharded_fixed(solver, total, load_shard, sync=torch.cuda.synchronize)
+            out.append({"set": name, "n": total, "psnr": float(r.psnr.mean()),
+                        "psnr_increment": float((r.psnr - r.initial_psnr).mean()),
+                        "mean_stop_iteration": float(r.iterations.float().mean()), "ranks": world,
+                        "iterations": [int(v) for v in r.iterations], "delta": float(r.delta.mean()), "primal": float(r.primal.mean())})
+            if args.dc:
+                out[-1]["dc"] = float(r.dc.mean())
+            if rank == 0:
+                print(json.dumps(out[-1]), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return out
     if args.mode == "eval":
         model, env, _ = _build(args, "norm")
         ev = GreedyEvaluator(model, env, max_timesteps=args.max_timesteps, block_size=args.block_size,
-                             device_type=torch.device("cuda", torch.cuda.current_device()), sync_every=5, ssim=True)
+                             device_type=torch.device("cuda", torch.cuda.current_device()), sync_every=5, ssim=True,
+                             residuals=args.residuals)
         for name, total, load in _sets(args):
             def load_shard(a, b, load=load):
                 batch, tokens = load(a, b)
@@ -102,6 +155,8 @@ def main(argv=None):
                         "psnr_increment": float((r.reward - r.initial_reward).mean()),
                         "mean_stop_iteration": float(r.stop_time.float().mean()), "ranks": world,
                         "ssim": float(r.ssim.mean()), "ssim_increment": float((r.ssim - r.initial_ssim).mean())})
+            if args.residuals:
+                out[-1].update(primal=float(r.residuals[:, 0].mean()), dc=float(r.residuals[:, 5].mean()))
             if rank == 0:
                 print(json.dumps(out[-1]), flush=True)
         if dist is not None:
@@ -132,9 +187,9 @@ def main(argv=None):
         # the ranks like `eval` (every rank a contiguous shard of each set, one gather per set)
         model, env, _ = _build(args, "flex")
         ev = GreedyEvaluator(model, env, max_timesteps=args.max_timesteps, block_size=args.block_size,
-                             device_type=torch.device("cuda", torch.cuda.current_device()), ssim=True)
+                             device_type=torch.device("cuda", torch.cuda.current_device()), ssim=True, residuals=args.residuals)
         for target in (1.5, 3, 3.5, 4, 4.5):                       # main.py:198
-            incs, ssims, ssim_incs = [], [], []
+            incs, ssims, ssim_incs, primals, dcs = [], [], [], [], []
             for name, total, load in _sets(args, flex_target=target):
                 def load_shard(a, b, load=load):
                     batch, tokens = load(a, b)
@@ -144,8 +199,13 @@ def main(argv=None):
                 incs.append(float((r.reward - r.initial_reward).mean()))
                 ssims.append(float(r.ssim.mean()))
                 ssim_incs.append(float((r.ssim - r.initial_ssim).mean()))
+                if args.residuals:
+                    primals.append(float(r.residuals[:, 0].mean()))
+                    dcs.append(float(r.residuals[:, 5].mean()))
             out.append({"rtg_target": target, "average_increment": float(np.mean(incs)), "ranks": world,
                         "ssim": float(np.mean(ssims)), "ssim_increment": float(np.mean(ssim_incs))})
+            if args.residuals:
+                out[-1].update(primal=float(np.mean(primals)), dc=float(np.mean(dcs)))
             if rank == 0:
                 print(json.dumps(out[-1]), flush=True)
         if dist is not None:

@@ -374,7 +374,8 @@ __device__ __forceinline__ void fft512_radix8_inplace(float2* buf, const float2*
 
 static constexpr int ROW_ELEMS = 2048;   // complex elements per workgroup in the row passes
 
-// MODE 0 generic (in -> out, index shifts), 1 ADMM forward (x + u -> work), 2 ADMM inverse (work -> z, u)
+// MODE 0 generic (in -> out, index shifts), 1 ADMM forward (x + u -> work), 2 ADMM inverse (work -> z, u), 3 real image x -> out (forward,
+// pnp_residuals' data misfit; stores as MODE 0 with shift_out = 0)
 // R16 (256-point rows of the ADMM passes): SIXTEEN rows per workgroup, each as two radix-16 passes in place in one skewed buffer
 // (fft256_radix16_inplace: every thread owns a butterfly, 2 LDS round trips per transform instead of 4, and the skew keeps the
 // Stockham strides off each other's banks - the radix-4 passes over unpadded 256-element lines spent 0.40 of their LDS cycles
@@ -407,13 +408,14 @@ __device__ __forceinline__ void fft_rows_body(float2* smem, const float2* in, fl
             const int e = e0 + k * 256;
             if (e < tot) {
                 if (MODE == 1) { v[k] = u[base + e]; xv[k] = x[base + e]; }
+                else if (MODE == 3) xv[k] = x[base + e];
                 else { const int r = e >> lw, c = e & (W - 1); v[k] = ld_c64<COH>(&in[base + (size_t)r * W + (c ^ shift_in)]); }
             }
         }
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
             const int e = e0 + k * 256;
-            if (e < tot) buf0[slot(e)] = MODE == 1 ? make_float2(xv[k] + v[k].x, v[k].y) : v[k];
+            if (e < tot) buf0[slot(e)] = MODE == 1 ? make_float2(xv[k] + v[k].x, v[k].y) : (MODE == 3 ? make_float2(xv[k], 0.f) : v[k]);
         }
     }
     __syncthreads();
@@ -945,6 +947,12 @@ hipError_t launch_fft_cols_generic(float2* data, const float2* tw, int batch, in
     if (hipError_t e = raise_lds_cap()) return e;
     hipLaunchKernelGGL((fft_cols_kernel<0, 0>), dim3(batch * (W / cw)), dim3(256), lds, s, data, tw, nullptr, nullptr, 1,
                        nullptr, nullptr, H, W, cw, inverse, shift_in, shift_out);
+    return hipGetLastError();
+}
+hipError_t launch_fft_rows_real(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s) {
+    const int rpb = rows_per_block(H, W);
+    const size_t lds = (size_t)(2 * rpb * W + W) * sizeof(float2);
+    hipLaunchKernelGGL((fft_rows_kernel<3, 0>), dim3(N * (H / rpb)), dim3(256), lds, s, nullptr, work, x, nullptr, tw, nullptr, H, W, rpb, 0, 0, 0);
     return hipGetLastError();
 }
 // 256-point rows: the radix-16 variant (16 rows per workgroup); PNP_FFT_ROWS_R4 (experiments) keeps the radix-4 passes

@@ -172,6 +172,45 @@ __global__ __launch_bounds__(256) void fft_rows_mixed_kernel(const float2* in, f
     }
 }
 
+// Row pass of a REAL image into complex scratch, forward, no index shift (pnp_residuals' data misfit reads the plain transform of x):
+// rows [y0, y0 + rpb) of slice n per workgroup, LDS and line transform as fft_rows_mixed_kernel.  A kernel of its own, so the three shipped
+// instantiations above keep their instruction streams.
+__global__ __launch_bounds__(256) void fft_rows_real_m5_kernel(const float* __restrict__ x, float2* __restrict__ out,
+                                                               const float2* __restrict__ twg, int H, int W, int rpb) {
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    const int blocks_per_img = H / rpb;
+    const int n = blockIdx.x / blocks_per_img;
+    const int y0 = (blockIdx.x % blocks_per_img) * rpb;
+    float2* const buf0 = smem;
+    float2* const buf1 = smem + rpb * W;
+    float2* const tw = smem + 2 * rpb * W;
+    const size_t base = ((size_t)n * H + y0) * W;
+    const int tot = rpb * W;
+    for (int i = threadIdx.x; i < W; i += blockDim.x) tw[i] = twg[i];
+    constexpr int NB = 8;                                  // independent global requests per thread and batch
+    for (int e0 = threadIdx.x; e0 < tot; e0 += NB * 256) {
+        float xv[NB];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const int e = e0 + k * 256;
+            if (e < tot) xv[k] = x[base + e];
+        }
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const int e = e0 + k * 256;
+            if (e < tot) buf0[e] = make_float2(xv[k], 0.f);
+        }
+    }
+    __syncthreads();
+    float2* const res = fft_lines_mixed<false>(buf0, buf1, tw, W, rpb, W);
+    const float sc = rsqrtf((float)W);
+    for (int e = threadIdx.x; e < tot; e += 256) {
+        float2 v = res[e];
+        v.x *= sc; v.y *= sc;
+        out[base + e] = v;
+    }
+}
+
 // Columns [x0, x0 + cw) of slice n per workgroup; cw (16, 8 or 4: a power of two) divides W.  LDS: two cw x H buffers whose lines (columns)
 // are H + 1 elements apart - odd, so the cw lanes that stage or solve one row across the columns sit on distinct banks - + H twiddles.
 // MODE 0: in-place centred pass with the row index rolled by `shift` (0 or H/2) in and out; 1: forward -> masked solve -> inverse.
@@ -309,6 +348,11 @@ hipError_t launch_fft_rows_fwd_mixed(const float* x, const float2* u, float2* wo
     const int rpb = mixed_rows_per_block(W);
     hipLaunchKernelGGL((fft_rows_mixed_kernel<1>), dim3(N * (H / rpb)), dim3(256), mixed_rows_lds(W), s, nullptr, work, x,
                        const_cast<float2*>(u), tw, tact, H, W, rpb, 0, 0);
+    return hipGetLastError();
+}
+hipError_t launch_fft_rows_real_mixed(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s) {
+    const int rpb = mixed_rows_per_block(W);
+    hipLaunchKernelGGL(fft_rows_real_m5_kernel, dim3(N * (H / rpb)), dim3(256), mixed_rows_lds(W), s, x, work, tw, H, W, rpb);
     return hipGetLastError();
 }
 hipError_t launch_fft_cols_prox_mixed(float2* work, const float2* tw, const float2* y0s, const uint8_t* masks, int mask_n, const float* mu,

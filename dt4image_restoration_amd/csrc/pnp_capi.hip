@@ -103,6 +103,7 @@ struct pnp_engine {
     float2* d_y0s = nullptr;    // [N,H,W] sgn * S y0
     uint8_t* d_masks = nullptr; // [mask_n,H,W] S mask
     double* d_ssim_part = nullptr; // [N, ssim_tiles(H, W)] per-tile SSIM sums (pnp_ssim)
+    double* d_res_part = nullptr;  // [N, residual_chunks(H, W), 4] + [N, residual_chunks(H, W)] per-workgroup sums of squares (pnp_residuals)
     int mask_n = 1;
     size_t ws_bytes = 0;
     // profiling
@@ -465,6 +466,10 @@ static int create_impl(const pnp_config* cfg, pnp_engine* e) {
     const size_t sbytes = N * (size_t)ssim_tiles(cfg->h, cfg->w) * sizeof(double);
     if (hipMalloc((void**)&e->d_ssim_part, sbytes) != hipSuccess) return fail(PNP_ERR_NOMEM, "SSIM partial sums");
     e->ws_bytes += sbytes;
+    // pnp_residuals: its own partial sums (the SSIM buffer holds one double per 32 x 32 tile - fewer than five per 2048 pixels on small slices)
+    const size_t rbytes = N * (size_t)residual_chunks(cfg->h, cfg->w) * 5 * sizeof(double);
+    if (hipMalloc((void**)&e->d_res_part, rbytes) != hipSuccess) return fail(PNP_ERR_NOMEM, "residual partial sums");
+    e->ws_bytes += rbytes;
     if (e->tune.fft_xcd && admm_xcd_usable(cfg->n, cfg->h, cfg->w)) {
         if (hipMalloc((void**)&e->d_fftq, admm_xcd_counter_bytes()) != hipSuccess || hipMemset(e->d_fftq, 0, admm_xcd_counter_bytes()) != hipSuccess)
             return fail(PNP_ERR_NOMEM, "data-fidelity work queues");
@@ -516,7 +521,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipDeviceSynchronize();
     for (int i = 0; i < N_LAYERS; ++i) { (void)hipFree(e->d_wpack[i]); (void)hipFree(e->d_bias[i]); }
     for (auto& L : e->lv) { (void)hipFree(L.p); (void)hipFree(L.q); (void)hipFree(L.s); (void)hipFree(L.pool); }
-    (void)hipFree(e->d_work); (void)hipFree(e->d_fftq); (void)hipFree(e->d_y0s); (void)hipFree(e->d_masks); (void)hipFree(e->d_ssim_part); (void)hipFree(e->d_partial); (void)hipFree(e->d_arrive);
+    (void)hipFree(e->d_work); (void)hipFree(e->d_fftq); (void)hipFree(e->d_y0s); (void)hipFree(e->d_masks); (void)hipFree(e->d_ssim_part); (void)hipFree(e->d_res_part); (void)hipFree(e->d_partial); (void)hipFree(e->d_arrive);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     delete e;
@@ -730,6 +735,61 @@ int pnp_ssim(pnp_handle e, const float* x, const float* gt, float data_range, fl
     HIP_TRY(launch_ssim(a, e->cfg.n, (hipStream_t)stream));
     return PNP_OK;
     PNP_API_END("pnp_ssim")
+}
+
+int pnp_residuals(pnp_handle e, const float* x, const float* z, const float* u, const void* prev, int flags, float* out, void* stream) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call, and leaves `out` untouched
+    if (flags & ~(PNP_RES_DELTA | PNP_RES_DC))
+        return fail(PNP_ERR_INVALID, "pnp_residuals: unknown flag bits 0x%x", (unsigned)(flags & ~(PNP_RES_DELTA | PNP_RES_DC)));
+    if (!x) return fail(PNP_ERR_INVALID, "pnp_residuals: null x");
+    if (!z) return fail(PNP_ERR_INVALID, "pnp_residuals: null z");
+    if (!u) return fail(PNP_ERR_INVALID, "pnp_residuals: null u");
+    if (!out) return fail(PNP_ERR_INVALID, "pnp_residuals: null out");
+    if ((flags & PNP_RES_DELTA) && !prev) return fail(PNP_ERR_INVALID, "pnp_residuals: PNP_RES_DELTA needs prev (a pnp_snapshot buffer), got null");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_residuals: null handle");
+    // the tile kernels read with 16-byte loads
+    const struct { const void* p; const char* name; } al[] = {{x, "x"}, {z, "z"}, {u, "u"}, {prev, "prev"}};
+    for (const auto& a : al)
+        if ((reinterpret_cast<uintptr_t>(a.p) & 15u) != 0) return fail(PNP_ERR_INVALID, "pnp_residuals: %s must be 16-byte aligned", a.name);
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (flags & PNP_RES_DC) {
+        if (!kspace_len_ok(H) || !kspace_len_ok(W))
+            return fail(PNP_ERR_INVALID, "pnp_residuals: PNP_RES_DC takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", H, W);
+        if (!e->reset_done) return fail(PNP_ERR_STATE, "pnp_residuals: PNP_RES_DC needs the episode's k-space constants (pnp_reset / pnp_set_kspace)");
+    }
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t px = (size_t)N * H * W;
+    double* const part = e->d_res_part;
+    double* const dcpart = part + (size_t)N * residual_chunks(H, W) * 4;
+    {
+        const char* pv = static_cast<const char*>((flags & PNP_RES_DELTA) ? prev : nullptr);   // [x | z | u | t] as pnp_snapshot packs them
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_residual_tiles(x, (const float2*)z, (const float2*)u, (const float*)pv, pv ? (const float2*)(pv + px * 4) : nullptr,
+                                      pv ? (const float2*)(pv + px * 12) : nullptr, part, N, H, W, s));
+    }
+    if (flags & PNP_RES_DC) {
+        // the plain (unshifted) transform of x into the data-fidelity stage's scratch, by the passes pnp_fft2c would choose; the shifts
+        // of fft_c live in the stored constants (reset_kernel)
+        const bool mixed = !is_pow2(H) || !is_pow2(W);
+        {
+            Prof p(e, s, 3, -1);
+            if (mixed) HIP_TRY(launch_fft_rows_real_mixed(x, e->d_work, e->plan.tw_w, N, H, W, s));
+            else HIP_TRY(launch_fft_rows_real(x, e->d_work, e->plan.tw_w, N, H, W, s));
+        }
+        {
+            Prof p(e, s, 4, -1);
+            if (mixed) HIP_TRY(launch_fft_cols_mixed(e->d_work, e->plan.tw_h, N, H, W, 0, 0, s));
+            else HIP_TRY(launch_fft_cols_generic(e->d_work, e->plan.tw_h, N, H, W, 0, 0, 0, s));
+        }
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_misfit_tiles(e->d_work, e->d_y0s, e->d_masks, e->mask_n, dcpart, N, H, W, s));
+    }
+    Prof p(e, s, 5, -1);
+    HIP_TRY(launch_residual_reduce(part, dcpart, (flags & PNP_RES_DELTA) ? 1 : 0, (flags & PNP_RES_DC) ? 1 : 0, out, N, H, W, s));
+    return PNP_OK;
+    PNP_API_END("pnp_residuals")
 }
 
 size_t pnp_snapshot_bytes(pnp_handle e) {

@@ -212,4 +212,20 @@ struct SsimArgs {
 int ssim_tiles(int H, int W);
 hipError_t launch_ssim(const SsimArgs& a, int N, hipStream_t s);
 
+// ---- ADMM residuals (residual_kernels.hip) ---------------------------------------------------------
+static constexpr int kResChunk = 2048;   // contiguous pixels of one slice per workgroup of the tile kernels
+int residual_chunks(int H, int W);       // workgroups (= float64 partials per quantity) per slice
+// partial: [N, residual_chunks, 4] sums of |x - z|^2, |x - xp|^2, |z - zp|^2, |u - up|^2; xp == nullptr: only the first is formed (u, zp, up unread)
+hipError_t launch_residual_tiles(const float* x, const float2* z, const float2* u, const float* xp, const float2* zp, const float2* up,
+                                 double* partial, int N, int H, int W, hipStream_t s);
+// fx: the plain orthonormal transform of x (unshifted), y0s / masks: the episode constants as reset_kernel stores them; dcpartial: [N, residual_chunks]
+hipError_t launch_misfit_tiles(const float2* fx, const float2* y0s, const uint8_t* masks, int mask_n, double* dcpartial, int N, int H, int W,
+                               hipStream_t s);
+hipError_t launch_residual_reduce(const double* partial, const double* dcpartial, int has_delta, int has_dc, float* out, int N, int H, int W,
+                                  hipStream_t s);
+// row pass of a REAL image into complex scratch, no index shift (the first half of the plain transform the misfit reads): fft_kernels.hip for
+// power-of-two handles (a new instantiation, MODE 3, of the row kernel), fft_mixed_kernels.hip otherwise (a kernel of its own)
+hipError_t launch_fft_rows_real(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s);
+hipError_t launch_fft_rows_real_mixed(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s);
+
 }  // namespace pnp

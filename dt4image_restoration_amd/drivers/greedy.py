@@ -48,6 +48,8 @@ class GreedyResult:
     x: torch.Tensor             # [N,1,H,W] final images (device)
     ssim: Optional[torch.Tensor] = None          # [N,1] final SSIM (CPU), env.compute_ssim beside `reward` (GreedyEvaluator(ssim=True))
     initial_ssim: Optional[torch.Tensor] = None  # [N,1] SSIM of x0
+    residuals: Optional[torch.Tensor] = None     # [N,6] env.residuals(dc=True) of the final iterate (CPU; GreedyEvaluator(residuals=True)):
+                                                 # primal ||x - z|| in column 0, the data misfit in column 5
 
 
 @dataclass
@@ -69,7 +71,7 @@ class PolicyContext:
 class GreedyEvaluator:
     def __init__(self, model, env, action_dim: int = 3, max_timesteps: int = 30, block_size: int = 18,
                  device_type="cuda", cache_state_embeddings: bool = True, sync_every: int = 1,
-                 use_graphs: Optional[bool] = None, ssim: bool = False):
+                 use_graphs: Optional[bool] = None, ssim: bool = False, residuals: bool = False):
         self.model = model.to(device_type).eval()
         self.env = env
         self.action_dim = action_dim
@@ -89,6 +91,8 @@ class GreedyEvaluator:
         self._graphs = {}
         # also score SSIM (env.compute_ssim) wherever PSNR (env.compute_reward) is scored: GreedyResult.ssim / initial_ssim
         self.ssim = bool(ssim)
+        # also report the final iterate's primal residual and k-space data misfit (env.residuals): GreedyResult.residuals
+        self.residuals = bool(residuals)
 
     # ---- context ---------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -326,6 +330,8 @@ class GreedyEvaluator:
             out["reward"] = env.compute_reward(states["x"], states["gt"])
             if self.ssim:
                 out["ssim"] = env.compute_ssim(states["x"], states["gt"])
+            if self.residuals:
+                out["residuals"] = env.residuals(states, dc=True).cpu()
         out["stop_time"] = stop_time.cpu()
 
     def rollout_rows(self, states, action, pred_rtg, start_times: torch.Tensor, ctx: PolicyContext, scorer=None,
@@ -396,7 +402,8 @@ class GreedyEvaluator:
         ro: Dict[str, torch.Tensor] = {}
         yield from self._rollout_phases(states, action, pred_rtg, 1, ctx, None, env, ro)
         out["result"] = GreedyResult(reward=ro["reward"], initial_reward=initial_reward, stop_time=ro["stop_time"],
-                                     actions=ctx.ea.cpu(), x=states["x"], ssim=ro.get("ssim"), initial_ssim=initial_ssim)
+                                     actions=ctx.ea.cpu(), x=states["x"], ssim=ro.get("ssim"), initial_ssim=initial_ssim,
+                                     residuals=ro.get("residuals"))
 
     def run_pipelined(self, mat: Dict[str, torch.Tensor], rtg: torch.Tensor, task: torch.Tensor, parts: int = 2) -> GreedyResult:
         """`run` with the batch cut into `parts` contiguous sub-batches that advance on their own HIP streams, half a period
@@ -466,4 +473,5 @@ class GreedyEvaluator:
                             stop_time=torch.cat([r.stop_time for r in res]), actions=torch.cat([r.actions for r in res]),
                             x=torch.cat([r.x for r in res]),
                             ssim=torch.cat([r.ssim for r in res]) if self.ssim else None,
-                            initial_ssim=torch.cat([r.initial_ssim for r in res]) if self.ssim else None)
+                            initial_ssim=torch.cat([r.initial_ssim for r in res]) if self.ssim else None,
+                            residuals=torch.cat([r.residuals for r in res]) if self.residuals else None)

@@ -13,6 +13,8 @@ import torch
 from . import _lib
 from .weights import flatten_state_dict
 
+RESIDUAL_COLUMNS = _lib.RESIDUAL_COLUMNS
+
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
@@ -180,6 +182,26 @@ class PnPEngine:
         _lib.check(self.lib.pnp_ssim(self._h, x.data_ptr(), gt.data_ptr(), float(data_range), float(k1), float(k2), int(radius),
                                      _lib.PNP_SSIM_CLAMP_X if clamp else 0, out.data_ptr(), _ptr(smap), self._stream()), "pnp_ssim")
         return (out, smap) if return_map else out
+
+    def residuals(self, x: torch.Tensor, z: torch.Tensor, u: torch.Tensor, prev: Optional[torch.Tensor] = None, dc: bool = False,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ADMM residuals of the iterate (pnp_residuals): float32 [N, 6] on the device, columns `RESIDUAL_COLUMNS` = primal ||x - z||,
+        dx, dz, du (change against `prev`, a buffer `snapshot` returned), delta = (dx + dz + du) / sqrt(H W), dc = the k-space data
+        misfit ||where(mask, fft_c(x) - y0, 0)|| of the live episode.  Without `prev` columns 1-4 are 0, without `dc` column 5 is."""
+        nhw = self.n * self.h * self.w
+        self._chk(x, torch.float32, nhw, "x"); self._chk(z, torch.complex64, nhw, "z"); self._chk(u, torch.complex64, nhw, "u")
+        flags = (_lib.PNP_RES_DC if dc else 0)
+        if prev is not None:
+            if prev.device != self.device or not prev.is_contiguous() or \
+                    prev.numel() * prev.element_size() != self.lib.pnp_snapshot_bytes(self._h):
+                raise ValueError("prev: not a snapshot of this engine")
+            flags |= _lib.PNP_RES_DELTA
+        if out is None:
+            out = torch.empty((self.n, _lib.PNP_RES_COLS), dtype=torch.float32, device=self.device)
+        self._chk(out, torch.float32, self.n * _lib.PNP_RES_COLS, "out")
+        _lib.check(self.lib.pnp_residuals(self._h, x.data_ptr(), z.data_ptr(), u.data_ptr(), _ptr(prev), flags, out.data_ptr(),
+                                          self._stream()), "pnp_residuals")
+        return out
 
     def snapshot(self, x: torch.Tensor, z: torch.Tensor, u: torch.Tensor, t_state: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -158,6 +158,31 @@ class PnPEnv:
                                "(the reference fetches ARNIQA with torch.hub, unavailable offline)")
         return float(self.no_ref_model(state["x"]))
 
+    def residuals(self, states, prev=None, dc: bool = False) -> torch.Tensor:
+        """ADMM residuals of `states` on the device: float32 [N, 6], columns `engine.RESIDUAL_COLUMNS` (primal, dx, dz, du, delta,
+        dc).  `prev` = what `snapshot` returned for the iterate before the step: the packed form goes straight to the kernel, the
+        per-tensor form (row slices, states of another size) is packed first.  dc=True adds the k-space data misfit against the y0 /
+        mask of the states' own episode (re-installed first when the engine holds another one's)."""
+        x, z, u = states["x"], states["z"], states["u"]
+        n, _, h, w = z.shape
+        eng = self._engine if self._engine is not None and (self._engine.n, self._engine.h, self._engine.w) == (n, h, w) \
+            else self._engine_for(n, h, w, z.device)
+        if x.is_complex():
+            x = x.real.contiguous()
+        packed = None
+        if prev is not None:
+            if "packed" in prev:
+                packed = prev["packed"]
+            else:
+                for k in ("x", "z", "u"):
+                    if prev[k].numel() != states[k].numel():
+                        raise ValueError(f"prev['{k}'] has {prev[k].numel()} elements, the states have {states[k].numel()}")
+                px = prev["x"].real if prev["x"].is_complex() else prev["x"]
+                packed = eng.snapshot(px.float().contiguous(), prev["z"].contiguous(), prev["u"].contiguous())
+        if dc:
+            self._bind_episode(eng, states)
+        return eng.residuals(x.contiguous(), z.contiguous(), u.contiguous(), prev=packed, dc=dc)
+
     # ---- explicit state copies (the reference rebinds tensors; this engine updates in place) ----
     def snapshot(self, states) -> Dict[str, torch.Tensor]:
         """A node's copy of the iterate.  Whole-batch states of the live engine go through pnp_snapshot into one packed

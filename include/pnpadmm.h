@@ -159,6 +159,28 @@ int pnp_psnr(pnp_handle h, const float* x, const float* gt, float* out, void* st
 int pnp_ssim(pnp_handle h, const float* x, const float* gt, float data_range, float k1, float k2, int radius, int flags,
              float* out, float* map, void* stream);
 
+/* ADMM residuals of the iterate (x, z, u), per slice, on the device - what a convergence test needs and the reference never computes
+ * (its drivers stop on the policy's T only).  With (x_p, z_p, u_p) the iterate stored in `prev` and ||.|| the Euclidean norm over the
+ * slice's H x W pixels (complex modulus for z, u), out[n] holds PNP_RES_COLS float32 columns:
+ *   0 primal = ||x - z||   (x taken as complex with zero imaginary part)
+ *   1 dx = ||x - x_p||     2 dz = ||z - z_p||     3 du = ||u - u_p||
+ *   4 delta = (dx + dz + du) / sqrt(H W)   - the fixed-point stopping quantity of Chan, Wang, Elgendy (2017)
+ *   5 dc = ||where(mask, fft_c(x) - y0, 0)||, fft_c = the centred orthonormal transform of pnp_fft2c, mask / y0 = the episode constants
+ *   x : DEVICE float32 [N,1,H,W];  z, u : DEVICE complex64 [N,1,H,W];  out : DEVICE float32 [N, PNP_RES_COLS]
+ *   prev : DEVICE buffer written by pnp_snapshot (only its x, z, u planes are read) or NULL without PNP_RES_DELTA
+ *   flags : PNP_RES_DELTA (columns 1-4) | PNP_RES_DC (column 5).  Column 0 is always written; columns not asked for are written as 0.
+ * x, z, u and prev must be 16-byte aligned (any hipMalloc / torch allocation is).  PNP_RES_DC needs pnp_reset / pnp_set_kspace
+ * (PNP_ERR_STATE otherwise), sides the k-space stage accepts, and uses the data-fidelity stage's scratch plane.  Every argument error
+ * is reported before any HIP call and leaves `out` untouched.  Any handle kind (PNP_FLAG_NO_DENOISER, bf16 convs).
+ * Differences are formed in float32 (one rounding), squared and summed in float64 in a fixed order: no atomics, bitwise reproducible,
+ * and a slice gives the same bits in columns 0-4 wherever it sits in the batch.  Uses a partial-sum buffer of the handle's workspace:
+ * calls on one handle are stream-ordered. */
+#define PNP_RES_COLS   6
+#define PNP_RES_DELTA  1   /* columns 1-4; needs prev */
+#define PNP_RES_DC     2   /* column 5; needs pnp_reset / pnp_set_kspace */
+int pnp_residuals(pnp_handle h, const float* x, const float* z, const float* u, const void* prev, int flags, float* out,
+                  void* stream);
+
 /* ---- tree search support --------------------------------------------------------------------- */
 
 /* Replaces: the per-child copy of `states` in expand_tree (evaluation/mcts.py:118-128), which the reference gets for
