@@ -45,6 +45,7 @@ SIGNATURES = {
     "pnp_psnr": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),
     "pnp_ssim": (C.c_int, [C.c_void_p, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _fp, _fp, _vp]),
     "pnp_residuals": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp, C.c_int, _fp, _vp]),
+    "pnp_acquire": (C.c_int, [C.c_void_p, _fp, _u8p, C.c_int, C.c_double, C.c_uint64, C.c_int, _fp, _fp, _fp, _vp]),
     "pnp_snapshot_bytes": (C.c_size_t, [C.c_void_p]),
     "pnp_snapshot": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _vp, _vp]),
     "pnp_restore": (C.c_int, [C.c_void_p, _vp, _fp, _fp, _fp, _fp, _vp]),

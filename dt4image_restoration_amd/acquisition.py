@@ -1,0 +1,126 @@
+"""Simulated CS-MRI acquisition on the device: ground-truth images in, the reference's evaluation-data layout out.
+
+The reference evaluates on `.mat` files holding `x0, y0, ATy0, mask, gt` (dataset/datasets.py:153-160,191-199), one folder per
+task `2x_5 ... 8x_15`; the files are an external download.  `synthetic.make_problem` builds the same dict on the CPU in numpy
+float64 from an analytic phantom.  `simulate` builds it on the GPU (pnp_acquire) from ANY ground truth - phantoms or a folder of
+images read by `data.load_gt_dir` - with the noise `make_problem` draws, number for number:
+
+    y0 = mask * (fft_c(gt) + sigma_n * (g_re + i g_im)),  ATy0 = ifft_c(y0),  x0 = max(ATy0, 0) on both planes
+
+and `PnPEnv.reset` takes the result as it stands, without a trip through host memory.
+"""
+from __future__ import annotations
+
+import math
+import re
+from typing import Dict, Tuple
+
+import numpy as np
+import torch
+
+from . import synthetic
+from .weights import hash_uniform
+
+MASK_KINDS = ("radial", "cartesian")
+
+
+def _engine(engine_or_env, n: int, h: int, w: int, device: torch.device):
+    if hasattr(engine_or_env, "acquire"):
+        return engine_or_env
+    if hasattr(engine_or_env, "_engine_for"):                # a PnPEnv: the handle its reset will use for this shape
+        return engine_or_env._engine_for(n, h, w, device)
+    raise TypeError(f"simulate: expected a PnPEngine or a PnPEnv, got {type(engine_or_env).__name__}")
+
+
+def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: int = 0) -> Dict[str, torch.Tensor]:
+    """The collated `.mat` dict `PnPEnv.reset` reads, acquired on the device: x0, y0, ATy0 float32 [N,1,H,W,2] (real views of the
+    complex outputs), mask bool [H,W] (or [N,H,W]), gt float32 [N,1,H,W], x0_raw = Re ATy0 [N,1,H,W]; every tensor on the GPU.
+    gt: [N,H,W] or [N,1,H,W] in [0, 1] (array or tensor), mask: [H,W] or [N,H,W] in the centred layout.  Slice i draws the noise of
+    seed + first_slice + i, so shards of one job agree with the unsharded job (as in `synthetic.make_problem`)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("simulate needs a ROCm GPU; the CPU route is synthetic.make_problem")
+    g = torch.as_tensor(gt)
+    if g.dim() not in (3, 4) or (g.dim() == 4 and g.shape[1] != 1):
+        raise ValueError(f"gt: expected [N,H,W] or [N,1,H,W], got {tuple(g.shape)}")
+    h, w = int(g.shape[-2]), int(g.shape[-1])
+    n = g.numel() // (h * w)
+    eng = engine_or_env if hasattr(engine_or_env, "acquire") else None
+    device = eng.device if eng is not None else torch.device("cuda", torch.cuda.current_device())
+    eng = _engine(engine_or_env, n, h, w, device)
+    if (eng.n, eng.h, eng.w) != (n, h, w):
+        raise ValueError(f"gt {tuple(g.shape)} does not fit the engine [{eng.n},{eng.h},{eng.w}]")
+    g = g.to(eng.device, torch.float32).reshape(n, 1, h, w).contiguous()
+    m = torch.as_tensor(mask)
+    if m.numel() == h * w:
+        m = m.reshape(h, w)
+    elif m.numel() == n * h * w:
+        m = m.reshape(n, h, w)
+    else:
+        raise ValueError(f"mask: expected [{h},{w}] or [{n},{h},{w}], got {tuple(m.shape)}")
+    m = (m != 0).to(eng.device).contiguous()
+    y0, aty0, x0 = eng.acquire(g, m, float(sigma_n), int(seed) + int(first_slice))
+    return {"x0": torch.view_as_real(x0), "y0": torch.view_as_real(y0), "ATy0": torch.view_as_real(aty0), "mask": m, "gt": g,
+            "x0_raw": aty0.real.contiguous()}
+
+
+def _centre_block(w: int, center_fraction: float) -> np.ndarray:
+    nc = int(round(w * center_fraction))
+    lo = (w - nc) // 2
+    centre = np.zeros(w, dtype=bool)
+    centre[lo:lo + nc] = True
+    return centre
+
+
+def cartesian_mask(h: int, w: int, accel: float, center_fraction: float = 0.08, seed: int = 0, kind: str = "random") -> np.ndarray:
+    """Bool [h,w] of whole columns (constant along H), centred layout.  A centred block of round(w * center_fraction) columns is
+    always sampled.  "random": exactly ceil(w / accel) columns; the outer ones are those with the smallest keys of
+    hash_uniform(seed, 9101, w) (ties by column index).  "equispaced": a comb of K columns floor((2 j + 1) w / (2 K)) over the whole
+    width, laid under the centre block, with the smallest K whose sampled fraction reaches 1 / accel; neighbouring teeth are floor or
+    ceil of w / K apart, so the gaps between consecutive outer columns on one side of the centre block differ by at most 1."""
+    if kind not in ("random", "equispaced"):
+        raise ValueError(f"kind must be 'random' or 'equispaced', got {kind!r}")
+    if not accel >= 1.0:
+        raise ValueError(f"accel must be >= 1, got {accel}")
+    centre = _centre_block(w, center_fraction)
+    target = int(math.ceil(w / accel))
+    cols = centre.copy()
+    if kind == "random":
+        outer = np.flatnonzero(~centre)
+        k = min(max(target - int(centre.sum()), 0), len(outer))
+        keys = hash_uniform(seed, 9101, w).astype(np.float64)[outer]
+        cols[outer[np.argsort(keys, kind="stable")[:k]]] = True
+    else:
+        for k in range(0, w + 1):
+            cols = centre.copy()
+            if k:
+                cols[((2 * np.arange(k) + 1) * w) // (2 * k)] = True
+            if cols.sum() >= target:
+                break
+    return np.broadcast_to(cols[None, :], (h, w)).copy()
+
+
+def parse_task(task: str) -> Tuple[int, float]:
+    """'4x_10' -> (4, 10 / 255): the task names `data.task_from_filename` produces."""
+    m = re.fullmatch(r"(\d+)x_(\d+)", task)
+    if m is None:
+        raise ValueError(f"task {task!r} is not '<accel>x_<sigma>'")
+    return int(m.group(1)), int(m.group(2)) / 255.0
+
+
+def make_mask(h: int, w: int, accel: float, kind: str = "radial", seed: int = 0) -> np.ndarray:
+    if kind == "radial":
+        return synthetic.radial_mask(h, w, accel)
+    if kind == "cartesian":
+        return cartesian_mask(h, w, accel, seed=seed)
+    raise ValueError(f"mask kind must be one of {MASK_KINDS}, got {kind!r}")
+
+
+def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int = 0, mask_kind: str = "radial",
+                 mask=None) -> Dict[str, torch.Tensor]:
+    """`simulate` for a named task: '4x_10' = acceleration 4, sigma_n = 10 / 255.  mask: a ready mask, or None for
+    `make_mask(h, w, accel, mask_kind, seed)` (the same for every shard of a job)."""
+    accel, sigma_n = parse_task(task)
+    h, w = (int(v) for v in torch.as_tensor(gt).shape[-2:])
+    if mask is None:
+        mask = make_mask(h, w, accel, mask_kind, seed)
+    return simulate(engine_or_env, gt, mask, sigma_n, seed, first_slice)

@@ -13,6 +13,12 @@ by the fixed-point criterion delta <= tol (drivers/fixed.py; no policy involved)
 `eval` and `flex` take `--residuals` (adds the final iterate's primal residual and k-space data misfit to their lines), `mcts` takes
 `--scorer neg_dc` (rollouts scored by minus the data misfit - a reference-free number - instead of the smoothness stub).
 
+Evaluation data made on the GPU (acquisition.py, pnp_acquire) instead of read from `.mat` files or built on the CPU:
+
+    ... --gt DIR [DIR ...] --tasks 4x_10,8x_10 --mask cartesian eval ...    one set per (folder of ground-truth images, task)
+    ... --acquire device eval ...                                           the synthetic sets, phantoms acquired on the device
+    ... acquire --gt DIR --out DIR                                          writes DIR/<task>/gt_<accel>_<sigma>_<image>.mat
+
 Multi-GPU (BASELINE configs[2]): launch the same command under `python -m torch.distributed.run --nproc-per-node N
 --master-addr 127.0.0.1 -m dt4image_restoration_amd.cli ... eval|mcts|flex ...`: every rank takes a contiguous shard of each
 set's images (drivers/sharded.py), the per-image PSNR / stop iteration are gathered over RCCL, rank 0 prints.
@@ -51,10 +57,31 @@ def _build(args, mode):
     return model, env, scorer
 
 
-def _sets(args, flex_target=None):
+def _mat(batch):
+    """Batch dict -> tensors; what the device acquisition returns stays where it is."""
+    return {k: v if torch.is_tensor(v) else torch.from_numpy(np.asarray(v)) for k, v in batch.items()}
+
+
+def _tasks(args):
+    from . import acquisition, data as D
+    tasks = [t for t in (args.tasks.split(",") if args.tasks else D.OPTIMAL_TASKS) if t]
+    for t in tasks:
+        acquisition.parse_task(t)
+    return tasks
+
+
+def _sets(args, flex_target=None, env=None):
     """(name, number of images, load(start, stop) -> (batch dict, task tokens)) per evaluation set."""
-    from . import data as D, synthetic
-    if args.data:
+    from . import acquisition, data as D, synthetic
+    if args.gt:
+        for d in args.gt:
+            for task in _tasks(args):
+                def load(a, b, d=d, task=task):
+                    gt, _ = D.load_gt_dir(d, limit=args.limit, start=a, stop=b)
+                    batch = acquisition.task_problem(task, gt, env, seed=args.seed, first_slice=a, mask_kind=args.mask)
+                    return batch, D.task_tokens([task] * (b - a), flex_target)
+                yield f"{d} {task}", D.count_gt_dir(d, args.limit), load
+    elif args.data:
         for d in args.data:
             def load(a, b, d=d):
                 batch, tasks = D.load_dir(d, limit=args.limit, start=a, stop=b)
@@ -63,10 +90,54 @@ def _sets(args, flex_target=None):
     else:
         for accel, sig in ((4, 10), (8, 10)):
             def load(a, b, accel=accel, sig=sig):
+                if args.acquire == "device":                   # make_problem's phantoms, mask and noise; the transforms on the GPU
+                    gt = np.stack([synthetic.phantom(args.size, args.size, args.seed + accel + i) for i in range(a, b)])
+                    p = acquisition.simulate(env, gt.astype(np.float32), synthetic.radial_mask(args.size, args.size, accel), sig / 255.0,
+                                             args.seed + accel, first_slice=a)
+                    return p, D.task_tokens([f"{accel}x_{sig}"] * (b - a), flex_target)
                 p = synthetic.make_problem(b - a, args.size, args.size, accel=accel, sigma_n=sig / 255.0, seed=args.seed + accel,
                                            first_slice=a)
                 return p, D.task_tokens([f"{accel}x_{sig}"] * (b - a), flex_target)
             yield f"synthetic {accel}x_{sig}", args.limit or 7, load
+
+
+def acquired_name(task: str, image: str) -> str:
+    """File name of one acquired image: carries `_<accel>_<sigma>_` first, so that `data.task_from_filename` (the reference's
+    `extract_task`, which takes the FIRST `<digits>_<digits>`) reads the task back whatever digits the image name holds."""
+    accel, sig = task.split("x_")
+    return f"gt_{accel}_{sig}_{image}.mat"
+
+
+def _acquire(args):
+    """`acquire`: every image of every --gt folder through pnp_acquire for every task, written by `data.save_mat` into
+    <out>/<task>/ (one folder per task, as the reference's data is laid out); with several folders, <out>/<folder name>/<task>/."""
+    from . import acquisition, data as D
+    from .engine import PnPEngine
+    if not args.gt:
+        raise SystemExit("acquire: --gt DIR is required")
+    out, engines = [], {}
+    tasks, step = _tasks(args), max(args.batch, 1)
+    for d in args.gt:
+        index = D.gt_index(d, args.limit)                      # the folder's headers, read once
+        total = sum(n for _, n, _ in index)
+        dsts = {t: os.path.join(args.out, t) if len(args.gt) == 1 else os.path.join(args.out, os.path.basename(os.path.normpath(d)), t)
+                for t in tasks}
+        for dst in dsts.values():
+            os.makedirs(dst, exist_ok=True)
+        for a in range(0, total, step):                        # every batch is read once and acquired for every task
+            gt, names = D.load_gt_dir(d, limit=args.limit, start=a, stop=min(a + step, total), index=index)
+            key = gt.shape[0], gt.shape[-2], gt.shape[-1]
+            if key not in engines:
+                engines[key] = PnPEngine(*key, denoiser=False)
+            for task in tasks:
+                p = acquisition.task_problem(task, gt, engines[key], seed=args.seed, first_slice=a, mask_kind=args.mask)
+                host = {k: v.cpu().numpy() for k, v in p.items()}
+                for i, name in enumerate(names):
+                    D.save_mat(os.path.join(dsts[task], acquired_name(task, name)), host, i)
+        for task in tasks:
+            out.append({"set": d, "task": task, "n": total, "dir": dsts[task], "mask": args.mask})
+            print(json.dumps(out[-1]), flush=True)
+    return out
 
 
 def main(argv=None):
@@ -76,7 +147,14 @@ def main(argv=None):
     ap.add_argument("--denoiser-ckpt", default=None)
     ap.add_argument("--policy-ckpt", default=None)
     ap.add_argument("--data", nargs="*", default=None, help="directories of .mat files (one batch each)")
-    ap.add_argument("--limit", type=int, default=7, help="images per directory (the reference averages the first 7)")
+    ap.add_argument("--gt", nargs="+", default=None, help="directories of ground-truth images (.npy / .mat with a `gt` key), "
+                    "acquired on the device: one set per (directory, task)")
+    ap.add_argument("--tasks", default=None, help="comma-separated tasks for --gt, e.g. 4x_10,8x_15 (default: the reference's nine)")
+    ap.add_argument("--mask", choices=("radial", "cartesian"), default="radial", help="sampling mask of the --gt sets")
+    ap.add_argument("--acquire", choices=("cpu", "device"), default="cpu",
+                    help="where the synthetic sets are acquired: synthetic.make_problem on the CPU, or pnp_acquire on the GPU")
+    ap.add_argument("--limit", type=int, default=None, help="images per directory (default 7: the reference averages the first 7; "
+                    "`acquire` defaults to all)")
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--seed", type=int, default=0)
     sub = ap.add_subparsers(dest="mode", required=True)
@@ -100,7 +178,15 @@ def main(argv=None):
     sp.add_argument("--tol", type=float, default=None, help="stop a slice once delta <= tol (default: run max_iter iterations)")
     sp.add_argument("--max_iter", type=int, default=30)
     sp.add_argument("--dc", action="store_true", help="add the final k-space data misfit to each line")
+    sp = sub.add_parser("acquire", help="write the reference's evaluation .mat files for a folder of ground-truth images")
+    sp.add_argument("--gt", nargs="+", default=argparse.SUPPRESS, help="directories of ground-truth images")
+    sp.add_argument("--out", required=True, help="output directory: one sub-folder per task")
+    sp.add_argument("--batch", type=int, default=16, help="images acquired per call")
     args = ap.parse_args(argv)
+    if args.limit is None:
+        args.limit = 0 if args.mode == "acquire" else 7
+    if args.mode == "acquire":
+        return _acquire(args)
 
     from . import data as D
     from .drivers.greedy import GreedyEvaluator
@@ -123,10 +209,10 @@ def main(argv=None):
                                      device_type=torch.device("cuda", torch.cuda.current_device()))
         t = np.arange(args.max_iter) / max(args.max_iter - 1, 1)
         sigma = (args.sigma_start * (args.sigma_end / args.sigma_start) ** t / 255.0).astype(np.float32)
-        for name, total, load in _sets(args):
+        for name, total, load in _sets(args, env=env):
             def load_shard(a, b, load=load):
                 batch, _ = load(a, b)
-                mat = {k: torch.from_numpy(np.asarray(v)) for k, v in batch.items()}
+                mat = _mat(batch)
                 return mat, np.full((b - a, args.max_iter), args.mu, dtype=np.float32), np.tile(sigma, (b - a, 1))
             r = run_sharded_fixed(solver, total, load_shard, sync=torch.cuda.synchronize)
             out.append({"set": name, "n": total, "psnr": float(r.psnr.mean()),
@@ -145,10 +231,10 @@ def main(argv=None):
         ev = GreedyEvaluator(model, env, max_timesteps=args.max_timesteps, block_size=args.block_size,
                              device_type=torch.device("cuda", torch.cuda.current_device()), sync_every=5, ssim=True,
                              residuals=args.residuals)
-        for name, total, load in _sets(args):
+        for name, total, load in _sets(args, env=env):
             def load_shard(a, b, load=load):
                 batch, tokens = load(a, b)
-                mat = {k: torch.from_numpy(np.asarray(v)) for k, v in batch.items()}
+                mat = _mat(batch)
                 return mat, torch.full((b - a,), D.normalised_rtg(args.rtg)), torch.from_numpy(tokens)
             r = run_sharded_greedy(ev, total, load_shard, sync=torch.cuda.synchronize)
             out.append({"set": name, "n": total, "psnr": float(r.reward.mean()),
@@ -166,10 +252,10 @@ def main(argv=None):
         model, env, scorer = _build(args, "norm")
         ev = GreedyEvaluator(model, env, max_timesteps=args.max_timesteps, block_size=args.block_size,
                              device_type=torch.device("cuda", torch.cuda.current_device()), sync_every=4)
-        for name, total, load in _sets(args):
+        for name, total, load in _sets(args, env=env):
             def load_shard(a, b, load=load):
                 batch, tokens = load(a, b)
-                mat = {k: torch.from_numpy(np.asarray(v)) for k, v in batch.items()}
+                mat = _mat(batch)
                 return mat, torch.full((b - a,), D.normalised_rtg(args.rtg)), torch.from_numpy(tokens)
             # all images of a rank's shard are searched at once: one tree per image, children and rollouts batched over images;
             # the policy's first token is the UNclipped Re x0 (datasets.py:162; `x0_raw` of the batch)
@@ -190,10 +276,10 @@ def main(argv=None):
                              device_type=torch.device("cuda", torch.cuda.current_device()), ssim=True, residuals=args.residuals)
         for target in (1.5, 3, 3.5, 4, 4.5):                       # main.py:198
             incs, ssims, ssim_incs, primals, dcs = [], [], [], [], []
-            for name, total, load in _sets(args, flex_target=target):
+            for name, total, load in _sets(args, flex_target=target, env=env):
                 def load_shard(a, b, load=load):
                     batch, tokens = load(a, b)
-                    mat = {k: torch.from_numpy(np.asarray(v)) for k, v in batch.items()}
+                    mat = _mat(batch)
                     return mat, torch.full((b - a,), D.normalised_rtg(target, flex=True)), torch.from_numpy(tokens)
                 r = run_sharded_greedy(ev, total, load_shard, sync=torch.cuda.synchronize)
                 incs.append(float((r.reward - r.initial_reward).mean()))

@@ -792,6 +792,59 @@ int pnp_residuals(pnp_handle e, const float* x, const float* z, const float* u, 
     PNP_API_END("pnp_residuals")
 }
 
+int pnp_acquire(pnp_handle e, const float* gt, const uint8_t* mask, int mask_n, double sigma_n, uint64_t seed, int flags, float* y0,
+                float* aty0, float* x0, void* stream) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call, and leaves the outputs untouched
+    if (flags != 0) return fail(PNP_ERR_INVALID, "pnp_acquire: flags must be 0 (got 0x%x)", (unsigned)flags);
+    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "pnp_acquire: sigma_n must be finite and >= 0 (got %g)", sigma_n);
+    if (!gt) return fail(PNP_ERR_INVALID, "pnp_acquire: null gt");
+    if (!mask) return fail(PNP_ERR_INVALID, "pnp_acquire: null mask");
+    if (!y0) return fail(PNP_ERR_INVALID, "pnp_acquire: null y0");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_acquire: null handle");
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (mask_n != 1 && mask_n != N) return fail(PNP_ERR_INVALID, "pnp_acquire: mask_n must be 1 or n=%d", N);
+    if (!kspace_len_ok(H) || !kspace_len_ok(W))
+        return fail(PNP_ERR_INVALID, "pnp_acquire: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", H, W);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    const bool mixed = !is_pow2(H) || !is_pow2(W);
+    // the plain (unshifted) transform of gt into the data-fidelity stage's scratch, by the passes pnp_residuals' misfit uses; the shifts of
+    // fft_c live in the epilogue's indices and sign
+    {
+        Prof p(e, s, 3, -1);
+        if (mixed) HIP_TRY(launch_fft_rows_real_mixed(gt, e->d_work, e->plan.tw_w, N, H, W, s));
+        else HIP_TRY(launch_fft_rows_real(gt, e->d_work, e->plan.tw_w, N, H, W, s));
+    }
+    {
+        Prof p(e, s, 4, -1);
+        if (mixed) HIP_TRY(launch_fft_cols_mixed(e->d_work, e->plan.tw_h, N, H, W, 0, 0, s));
+        else HIP_TRY(launch_fft_cols_generic(e->d_work, e->plan.tw_h, N, H, W, 0, 0, 0, s));
+    }
+    {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_acquire_epilogue(e->d_work, mask, mask_n, (float2*)y0, sigma_n, seed, N, H, W, s));
+    }
+    if (!aty0 && !x0) return PNP_OK;
+    {
+        Prof p(e, s, 4, -1);
+        if (mixed) HIP_TRY(launch_fft_cols_mixed(e->d_work, e->plan.tw_h, N, H, W, 1, 0, s));
+        else HIP_TRY(launch_fft_cols_generic(e->d_work, e->plan.tw_h, N, H, W, 1, 0, 0, s));
+    }
+    float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the row pass runs in place: a workgroup reads and writes its own rows only
+    {
+        Prof p(e, s, 3, -1);
+        if (mixed) HIP_TRY(launch_fft_rows_mixed(e->d_work, a, e->plan.tw_w, N, H, W, 1, 0, s));
+        else HIP_TRY(launch_fft_rows_generic(e->d_work, a, e->plan.tw_w, N, H, W, 1, 0, 0, s));
+    }
+    if (x0) {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
+    }
+    return PNP_OK;
+    PNP_API_END("pnp_acquire")
+}
+
 size_t pnp_snapshot_bytes(pnp_handle e) {
     if (!e) return 0;
     const size_t px = (size_t)e->cfg.n * e->cfg.h * e->cfg.w;

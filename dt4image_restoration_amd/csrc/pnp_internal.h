@@ -228,4 +228,11 @@ hipError_t launch_residual_reduce(const double* partial, const double* dcpartial
 hipError_t launch_fft_rows_real(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s);
 hipError_t launch_fft_rows_real_mixed(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s);
 
+// ---- simulated acquisition (acquire_kernels.hip) ---------------------------------------------------
+// work: the plain orthonormal transform of gt (unshifted); mask, y0: centred layout.  Stores y0 and leaves sgn * S y0 in work (reset_kernel's y0s
+// convention), whose plain inverse transform is ifft_c(y0).  Noise: synthetic._gauss of (seed + n, 9001 / 9003, centred pixel), float64.
+hipError_t launch_acquire_epilogue(float2* work, const uint8_t* mask, int mask_n, float2* y0, double sigma, uint64_t seed, int N, int H, int W,
+                                   hipStream_t s);
+hipError_t launch_acquire_clamp(const float2* aty0, float2* x0, int N, int H, int W, hipStream_t s);
+
 }  // namespace pnp

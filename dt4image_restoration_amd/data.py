@@ -85,6 +85,84 @@ def load_dir(data_dir: str, limit: int = 0, start: int = 0, stop: int = None) ->
     return batch, [task_from_filename(f) for f in fns]
 
 
+def _gt_index(gt_dir: str, limit: int = 0) -> List[Tuple[str, int, Tuple[int, int]]]:
+    """(file, images in it, (H, W)) for the `.npy` / `.mat` files of a directory, sorted by name, cut after the first `limit`
+    images; only headers are read."""
+    out, total = [], 0
+    for f in sorted(os.listdir(gt_dir)):
+        path = os.path.join(gt_dir, f)
+        if f.endswith(".npy"):
+            shape = np.load(path, mmap_mode="r").shape
+        elif f.endswith(".mat"):
+            from scipy.io import whosmat
+            found = [sh for name, sh, _ in whosmat(path) if name == "gt"]
+            if not found:
+                raise KeyError(f"{path}: no 'gt' key")
+            shape = tuple(found[0])
+        else:
+            continue
+        if len(shape) == 2:
+            shape = (1,) + tuple(shape)
+        if len(shape) != 3:
+            raise ValueError(f"{path}: expected [H,W] or [n,H,W], got {tuple(shape)}")
+        n = int(shape[0])
+        if limit and total + n > limit:
+            n = limit - total
+        if n > 0:
+            out.append((f, n, (int(shape[1]), int(shape[2]))))
+            total += n
+        if limit and total >= limit:
+            break
+    if not out:
+        raise FileNotFoundError(f"no .npy / .mat ground-truth files in {gt_dir}")
+    sizes = {hw for _, _, hw in out}
+    if len(sizes) != 1:
+        raise ValueError(f"{gt_dir}: all images of one folder must share one size, found {sorted(sizes)}")
+    return out
+
+
+gt_index = _gt_index
+
+
+def count_gt_dir(gt_dir: str, limit: int = 0) -> int:
+    """Number of ground-truth images `load_gt_dir(gt_dir, limit)` would return."""
+    return sum(n for _, n, _ in _gt_index(gt_dir, limit))
+
+
+def load_gt_dir(gt_dir: str, limit: int = 0, start: int = 0, stop: int = None, index=None) -> Tuple[np.ndarray, List[str]]:
+    """Ground-truth images [start, stop) of a folder (of its first `limit` images; files sorted by name): float32 [N,1,H,W] and
+    one name per image.  Reads `.npy` files ([H,W] or [n,H,W], any float type) and `.mat` files with a `gt` key ([H,W], [1,H,W] or
+    [n,H,W]); a rank of a sharded run opens only the files its range touches.  Mixed sizes and values outside [0, 1] are refused
+    (the acquisition and the PSNR both assume the reference's unit range).  index: what `gt_index(gt_dir, limit)` returned, for a
+    caller that reads one folder in several ranges (the headers are then read once)."""
+    if index is None:
+        index = _gt_index(gt_dir, limit)
+    total = sum(n for _, n, _ in index)
+    stop = total if stop is None else min(stop, total)
+    if not 0 <= start < stop:
+        raise FileNotFoundError(f"no ground-truth images in {gt_dir} [{start}:{stop}]")
+    imgs, names, first = [], [], 0
+    for f, n, (h, w) in index:
+        a, b = max(start, first), min(stop, first + n)
+        if a < b:
+            path = os.path.join(gt_dir, f)
+            if f.endswith(".npy"):
+                arr = np.load(path, mmap_mode="r")
+            else:
+                from scipy.io import loadmat
+                arr = loadmat(path)["gt"]
+            if not np.issubdtype(arr.dtype, np.floating):
+                raise ValueError(f"{path}: expected a float array, got {arr.dtype}")
+            arr = np.asarray(arr.reshape(-1, h, w)[a - first:b - first], dtype=np.float32)
+            if not np.isfinite(arr).all() or arr.min() < 0.0 or arr.max() > 1.0:
+                raise ValueError(f"{path}: ground-truth values must lie in [0, 1] (found {arr.min():g} .. {arr.max():g})")
+            imgs.append(arr)
+            stem = os.path.splitext(f)[0]
+            names += [stem if n == 1 else f"{stem}-{i:04d}" for i in range(a - first, b - first)]
+        first += n
+    return np.concatenate(imgs).reshape(-1, 1, h, w), names
+
+
 def task_tokens(tasks: Sequence[str], flex_target: float = None) -> np.ndarray:
     if flex_target is not None:
         key = "rtg_" + (str(int(flex_target)) if float(flex_target).is_integer() else str(flex_target))

@@ -203,6 +203,27 @@ class PnPEngine:
                                           self._stream()), "pnp_residuals")
         return out
 
+    def acquire(self, gt: torch.Tensor, mask: torch.Tensor, sigma_n: float, seed: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Simulated CS-MRI acquisition of the engine's N slices on the device (pnp_acquire): gt float32 [N,1,H,W] in [0, 1], mask
+        bool/uint8 [H,W] (or [N,H,W]) in the centred layout.  Returns complex64 [N,1,H,W] tensors (y0, ATy0, x0) with
+        y0 = mask * (fft_c(gt) + sigma_n * noise), ATy0 = ifft_c(y0), x0 = max(ATy0, 0) on both planes; slice n draws the noise
+        `synthetic.make_problem` draws for seed + n."""
+        nhw = self.n * self.h * self.w
+        gt = self._chk(gt, torch.float32, nhw, "gt")
+        m = mask.to(torch.uint8).contiguous()
+        if m.numel() not in (self.h * self.w, nhw):
+            raise ValueError(f"mask: expected {self.h * self.w} or {nhw} elements, got {tuple(mask.shape)}")
+        self._chk(m, torch.uint8, m.numel(), "mask")
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64 - self.n:
+            raise ValueError(f"seed: expected 0 <= seed < 2**64 - n, got {seed}")
+        y0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+        aty0, x0 = torch.empty_like(y0), torch.empty_like(y0)
+        _lib.check(self.lib.pnp_acquire(self._h, gt.data_ptr(), m.data_ptr(), 1 if m.numel() == self.h * self.w else self.n,
+                                        float(sigma_n), seed, 0, y0.data_ptr(), aty0.data_ptr(), x0.data_ptr(), self._stream()),
+                   "pnp_acquire")
+        return y0, aty0, x0
+
     def snapshot(self, x: torch.Tensor, z: torch.Tensor, u: torch.Tensor, t_state: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One packed device buffer [x | z | u | T] (pnp_snapshot): a tree-search node's copy of the iterate."""

@@ -181,6 +181,29 @@ int pnp_ssim(pnp_handle h, const float* x, const float* gt, float data_range, fl
 int pnp_residuals(pnp_handle h, const float* x, const float* z, const float* u, const void* prev, int flags, float* out,
                   void* stream);
 
+/* Replaces: the preparation of the evaluation `.mat` files the reference loads (dataset/datasets.py:153-160,191-199: keys x0, y0, ATy0,
+ * mask, gt), which it leaves to an external download - the simulated CS-MRI acquisition of N ground-truth slices, on the device:
+ *   y0   = mask ? fft_c(gt) + sigma_n (g_re + i g_im) : 0        (off-mask bins are stored as +0.0)
+ *   aty0 = ifft_c(y0)
+ *   x0   = max(aty0, 0) on the real AND the imaginary plane      (the np.clip of datasets.py:160 on the stacked array)
+ * fft_c / ifft_c = the centred orthonormal transforms of pnp_fft2c.
+ *   gt   : DEVICE float32 [N,1,H,W]
+ *   mask : DEVICE uint8 [H,W] (mask_n == 1) or [N,H,W] (mask_n == N), the reference's centred layout, as pnp_reset takes it
+ *   y0   : DEVICE complex64 [N,1,H,W];  aty0, x0 : the same or NULL (not stored).  No output may alias gt.
+ *   sigma_n : standard deviation of the noise per component, finite and >= 0;  flags : reserved, must be 0
+ * Noise: g_re[p] = gauss(seed + n, 9001, p), g_im[p] = gauss(seed + n, 9003, p), p = y W + x the row-major index of the centred bin and
+ * gauss(s, t, p) = sqrt(-2 ln u1) cos(2 pi u2) with u = (24 top bits of splitmix64(p ^ splitmix64(s * 0x100000001B3 + t'))) / 2^24 for
+ * t' = t (u1, clamped below at 2^-25) and t + 1 (u2) - the counter hash of the Python package's weights.hash_uniform and its
+ * synthetic.make_problem, so that a problem built there in float64 and one acquired here agree to rounding.  The integer hash is exact;
+ * Box-Muller, the product with sigma_n and the sum with the transform are formed in float64 and rounded to float32 once.
+ * With sigma_n == 0 nothing is drawn: a sampled bin holds the transform's own float32 value (its sign of zero included).
+ * A slice's outputs depend on (its gt, its mask, sigma_n, seed + n) only: not on N, not on its place in the batch; bitwise reproducible.
+ * Sides the k-space stage accepts (any other is refused); any handle kind (PNP_FLAG_NO_DENOISER, bf16 convs).  Uses the data-fidelity
+ * stage's scratch plane and allocates nothing: calls on one handle are stream-ordered.  Every argument error (NULL gt, mask or y0, mask_n
+ * not 1 or N, sigma_n negative or not finite, flags != 0) is reported before any HIP call and leaves the outputs untouched. */
+int pnp_acquire(pnp_handle h, const float* gt, const uint8_t* mask, int mask_n, double sigma_n, uint64_t seed, int flags,
+                float* y0, float* aty0, float* x0, void* stream);
+
 /* ---- tree search support --------------------------------------------------------------------- */
 
 /* Replaces: the per-child copy of `states` in expand_tree (evaluation/mcts.py:118-128), which the reference gets for
