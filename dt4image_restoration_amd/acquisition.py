@@ -32,11 +32,13 @@ def _engine(engine_or_env, n: int, h: int, w: int, device: torch.device):
     raise TypeError(f"simulate: expected a PnPEngine or a PnPEnv, got {type(engine_or_env).__name__}")
 
 
-def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: int = 0) -> Dict[str, torch.Tensor]:
+def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: int = 0, sens=None) -> Dict[str, torch.Tensor]:
     """The collated `.mat` dict `PnPEnv.reset` reads, acquired on the device: x0, y0, ATy0 float32 [N,1,H,W,2] (real views of the
     complex outputs), mask bool [H,W] (or [N,H,W]), gt float32 [N,1,H,W], x0_raw = Re ATy0 [N,1,H,W]; every tensor on the GPU.
     gt: [N,H,W] or [N,1,H,W] in [0, 1] (array or tensor), mask: [H,W] or [N,H,W] in the centred layout.  Slice i draws the noise of
-    seed + first_slice + i, so shards of one job agree with the unsharded job (as in `synthetic.make_problem`)."""
+    seed + first_slice + i, so shards of one job agree with the unsharded job (as in `synthetic.make_problem`).
+    sens: coil sensitivity maps, complex [C,H,W] (shared) or [N,C,H,W] - the multi-coil acquisition (pnp_acquire_mc): y0 is then
+    [N,C,H,W,2], ATy0 = sum_c conj(S_c) ifft_c(y_c), and the dict carries `sens` (complex64, on the GPU) for `PnPEnv.reset`."""
     if not torch.cuda.is_available():
         raise RuntimeError("simulate needs a ROCm GPU; the CPU route is synthetic.make_problem")
     g = torch.as_tensor(gt)
@@ -58,9 +60,14 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
     else:
         raise ValueError(f"mask: expected [{h},{w}] or [{n},{h},{w}], got {tuple(m.shape)}")
     m = (m != 0).to(eng.device).contiguous()
-    y0, aty0, x0 = eng.acquire(g, m, float(sigma_n), int(seed) + int(first_slice))
-    return {"x0": torch.view_as_real(x0), "y0": torch.view_as_real(y0), "ATy0": torch.view_as_real(aty0), "mask": m, "gt": g,
-            "x0_raw": aty0.real.contiguous()}
+    if sens is not None:
+        sens = torch.as_tensor(sens).to(eng.device, torch.complex64).contiguous()
+    y0, aty0, x0 = eng.acquire(g, m, float(sigma_n), int(seed) + int(first_slice), sens=sens)
+    out = {"x0": torch.view_as_real(x0), "y0": torch.view_as_real(y0), "ATy0": torch.view_as_real(aty0), "mask": m, "gt": g,
+           "x0_raw": aty0.real.contiguous()}
+    if sens is not None:
+        out["sens"] = sens
+    return out
 
 
 def _centre_block(w: int, center_fraction: float) -> np.ndarray:
@@ -116,11 +123,13 @@ def make_mask(h: int, w: int, accel: float, kind: str = "radial", seed: int = 0)
 
 
 def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int = 0, mask_kind: str = "radial",
-                 mask=None) -> Dict[str, torch.Tensor]:
+                 mask=None, coils: int = 0) -> Dict[str, torch.Tensor]:
     """`simulate` for a named task: '4x_10' = acceleration 4, sigma_n = 10 / 255.  mask: a ready mask, or None for
-    `make_mask(h, w, accel, mask_kind, seed)` (the same for every shard of a job)."""
+    `make_mask(h, w, accel, mask_kind, seed)` (the same for every shard of a job).  coils > 0: a multi-coil acquisition with the
+    analytic maps `synthetic.coil_maps(coils, h, w)`."""
     accel, sigma_n = parse_task(task)
     h, w = (int(v) for v in torch.as_tensor(gt).shape[-2:])
     if mask is None:
         mask = make_mask(h, w, accel, mask_kind, seed)
-    return simulate(engine_or_env, gt, mask, sigma_n, seed, first_slice)
+    sens = synthetic.coil_maps(coils, h, w).astype(np.complex64) if coils else None
+    return simulate(engine_or_env, gt, mask, sigma_n, seed, first_slice, sens=sens)

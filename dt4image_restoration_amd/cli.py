@@ -19,6 +19,12 @@ Evaluation data made on the GPU (acquisition.py, pnp_acquire) instead of read fr
     ... --acquire device eval ...                                           the synthetic sets, phantoms acquired on the device
     ... acquire --gt DIR --out DIR                                          writes DIR/<task>/gt_<accel>_<sigma>_<image>.mat
 
+Multi-coil (SENSE) problems, on synthetic data and on --gt folders, with the analytic maps of `synthetic.coil_maps`; the k-space
+subproblem is then solved by K conjugate-gradient iterations per step (`acquire` has no coil axis to write: the reference's `.mat`
+layout has none):
+
+    ... --coils 4 --cg-iters 8 eval|flex|mcts|fixed ...
+
 Multi-GPU (BASELINE configs[2]): launch the same command under `python -m torch.distributed.run --nproc-per-node N
 --master-addr 127.0.0.1 -m dt4image_restoration_amd.cli ... eval|mcts|flex ...`: every rank takes a contiguous shard of each
 set's images (drivers/sharded.py), the per-image PSNR / stop iteration are gathered over RCCL, rank 0 prints.
@@ -51,7 +57,7 @@ def _build(args, mode):
         model.load_state_dict(weights.generate_policy_weights(model, args.seed, t_bias=-1.0, head_gain=8.0))
     den = UNetDenoiser2D(ckpt_path=args.denoiser_ckpt) if args.denoiser_ckpt else UNetDenoiser2D.seeded(args.seed)
     scorer = (lambda st: 1.0 / (1e-3 + (st["x"] - torch.nn.functional.avg_pool2d(st["x"], 3, 1, 1)).pow(2).mean(dim=(1, 2, 3))))
-    env = PnPEnv(max_episode_step=30, denoiser=den, device_type="cuda", no_ref_scorer=None)
+    env = PnPEnv(max_episode_step=30, denoiser=den, device_type="cuda", no_ref_scorer=None, cg_iters=args.cg_iters)
     if getattr(args, "scorer", "stub") == "neg_dc":            # minus the k-space data misfit of the rollout's final iterate (pnp_residuals)
         scorer = (lambda st: -env.residuals(st, dc=True)[:, 5])
     return model, env, scorer
@@ -78,10 +84,12 @@ def _sets(args, flex_target=None, env=None):
             for task in _tasks(args):
                 def load(a, b, d=d, task=task):
                     gt, _ = D.load_gt_dir(d, limit=args.limit, start=a, stop=b)
-                    batch = acquisition.task_problem(task, gt, env, seed=args.seed, first_slice=a, mask_kind=args.mask)
+                    batch = acquisition.task_problem(task, gt, env, seed=args.seed, first_slice=a, mask_kind=args.mask, coils=args.coils)
                     return batch, D.task_tokens([task] * (b - a), flex_target)
                 yield f"{d} {task}", D.count_gt_dir(d, args.limit), load
     elif args.data:
+        if args.coils:
+            raise SystemExit("--coils: the reference's .mat layout (--data) has no coil axis; use the synthetic sets or --gt")
         for d in args.data:
             def load(a, b, d=d):
                 batch, tasks = D.load_dir(d, limit=args.limit, start=a, stop=b)
@@ -92,8 +100,13 @@ def _sets(args, flex_target=None, env=None):
             def load(a, b, accel=accel, sig=sig):
                 if args.acquire == "device":                   # make_problem's phantoms, mask and noise; the transforms on the GPU
                     gt = np.stack([synthetic.phantom(args.size, args.size, args.seed + accel + i) for i in range(a, b)])
+                    sens = synthetic.coil_maps(args.coils, args.size, args.size).astype(np.complex64) if args.coils else None
                     p = acquisition.simulate(env, gt.astype(np.float32), synthetic.radial_mask(args.size, args.size, accel), sig / 255.0,
-                                             args.seed + accel, first_slice=a)
+                                             args.seed + accel, first_slice=a, sens=sens)
+                    return p, D.task_tokens([f"{accel}x_{sig}"] * (b - a), flex_target)
+                if args.coils:
+                    p = synthetic.make_problem_mc(b - a, args.size, args.size, args.coils, accel=accel, sigma_n=sig / 255.0,
+                                                  seed=args.seed + accel, first_slice=a)
                     return p, D.task_tokens([f"{accel}x_{sig}"] * (b - a), flex_target)
                 p = synthetic.make_problem(b - a, args.size, args.size, accel=accel, sigma_n=sig / 255.0, seed=args.seed + accel,
                                            first_slice=a)
@@ -156,6 +169,9 @@ def main(argv=None):
     ap.add_argument("--limit", type=int, default=None, help="images per directory (default 7: the reference averages the first 7; "
                     "`acquire` defaults to all)")
     ap.add_argument("--size", type=int, default=128)
+    ap.add_argument("--coils", type=int, default=0, help="multi-coil (SENSE) problems with this many analytic coil maps (1..32; "
+                    "default 0: single-coil)")
+    ap.add_argument("--cg-iters", type=int, default=8, help="conjugate-gradient iterations per step of a multi-coil problem (1..64)")
     ap.add_argument("--seed", type=int, default=0)
     sub = ap.add_subparsers(dest="mode", required=True)
     for name in ("eval", "mcts"):
@@ -185,7 +201,13 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.limit is None:
         args.limit = 0 if args.mode == "acquire" else 7
+    if args.coils and not 1 <= args.coils <= 32:
+        raise SystemExit(f"--coils must be 1..32, got {args.coils}")
+    if not 1 <= args.cg_iters <= 64:
+        raise SystemExit(f"--cg-iters must be 1..64, got {args.cg_iters}")
     if args.mode == "acquire":
+        if args.coils:
+            raise SystemExit("acquire --coils: refused - the reference's .mat layout this command writes has no coil axis")
         return _acquire(args)
 
     from . import data as D
@@ -204,7 +226,7 @@ def main(argv=None):
         from .drivers.fixed import FixedScheduleSolver
         from .env import PnPEnv
         den = UNetDenoiser2D(ckpt_path=args.denoiser_ckpt) if args.denoiser_ckpt else UNetDenoiser2D.seeded(args.seed)
-        env = PnPEnv(max_episode_step=args.max_iter, denoiser=den, device_type="cuda")
+        env = PnPEnv(max_episode_step=args.max_iter, denoiser=den, device_type="cuda", cg_iters=args.cg_iters)
         solver = FixedScheduleSolver(env, max_iter=args.max_iter, tol=args.tol, sync_every=5, dc=args.dc,
                                      device_type=torch.device("cuda", torch.cuda.current_device()))
         t = np.arange(args.max_iter) / max(args.max_iter - 1, 1)

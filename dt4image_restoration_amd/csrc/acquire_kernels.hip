@@ -54,14 +54,15 @@ __device__ __forceinline__ double gauss64(unsigned long long b1, unsigned long l
 // (LDS atomics) varies from run to run; a pixel's value does not depend on it.
 __global__ __launch_bounds__(kAcqThreads) void acquire_epilogue_kernel(float2* __restrict__ work, const uint8_t* __restrict__ mask, int mask_n,
                                                                        float2* __restrict__ y0, double sigma, unsigned long long seed,
-                                                                       int H, int W) {
+                                                                       int H, int W, int coils) {
     __shared__ int list[kAcqChunk];
     __shared__ int count;
     constexpr int PER = kAcqChunk / kAcqThreads;
-    const int n = blockIdx.y, hw = H * W, hh = H >> 1, hwd = W >> 1;
+    // plane blockIdx.y = coil c of slice n (pnp_acquire: one plane per slice, c = 0)
+    const int n = blockIdx.y / coils, c = blockIdx.y - n * coils, hw = H * W, hh = H >> 1, hwd = W >> 1;
     const int p0 = blockIdx.x * kAcqChunk + threadIdx.x;
-    const size_t base = (size_t)n * hw;
-    const uint8_t* const mk = mask + (mask_n > 1 ? base : 0);
+    const size_t base = (size_t)blockIdx.y * hw;
+    const uint8_t* const mk = mask + (mask_n > 1 ? (size_t)n * hw : 0);
     // plain bin k = S^-1 p of the centred pixel p (H/2, W/2 even: the parities of p's and k's coordinates agree)
     auto plain = [&](int p, int& par) {
         const int r = p / W, c = p - r * W;
@@ -92,8 +93,9 @@ __global__ __launch_bounds__(kAcqThreads) void acquire_epilogue_kernel(float2* _
     __syncthreads();
     const int cnt = count;
     const unsigned long long sn = (seed + (unsigned long long)n) * 0x100000001B3ull;
-    const unsigned long long bre1 = splitmix64(sn + kStreamRe), bre2 = splitmix64(sn + kStreamRe + 1u);
-    const unsigned long long bim1 = splitmix64(sn + kStreamIm), bim2 = splitmix64(sn + kStreamIm + 1u);
+    const unsigned tre = kStreamRe + 4u * (unsigned)c, tim = kStreamIm + 4u * (unsigned)c;     // coil c draws the streams 9001 + 4 c, 9003 + 4 c
+    const unsigned long long bre1 = splitmix64(sn + tre), bre2 = splitmix64(sn + tre + 1u);
+    const unsigned long long bim1 = splitmix64(sn + tim), bim2 = splitmix64(sn + tim + 1u);
     for (int i = threadIdx.x; i < cnt; i += kAcqThreads) {
         const int p = list[i];
         int par;
@@ -121,10 +123,10 @@ __global__ __launch_bounds__(kAcqThreads) void acquire_clamp_kernel(const float2
 }  // namespace
 
 hipError_t launch_acquire_epilogue(float2* work, const uint8_t* mask, int mask_n, float2* y0, double sigma, uint64_t seed, int N, int H, int W,
-                                   hipStream_t s) {
+                                   hipStream_t s, int coils) {
     const int hw = H * W;
-    hipLaunchKernelGGL(acquire_epilogue_kernel, dim3((hw + kAcqChunk - 1) / kAcqChunk, N), dim3(kAcqThreads), 0, s, work, mask, mask_n, y0,
-                       sigma, (unsigned long long)seed, H, W);
+    hipLaunchKernelGGL(acquire_epilogue_kernel, dim3((hw + kAcqChunk - 1) / kAcqChunk, N * coils), dim3(kAcqThreads), 0, s, work, mask, mask_n, y0,
+                       sigma, (unsigned long long)seed, H, W, coils);
     return hipGetLastError();
 }
 

@@ -106,6 +106,17 @@ struct pnp_engine {
     double* d_res_part = nullptr;  // [N, residual_chunks(H, W), 4] + [N, residual_chunks(H, W)] per-workgroup sums of squares (pnp_residuals)
     int mask_n = 1;
     size_t ws_bytes = 0;
+    // multi-coil (SENSE) data-fidelity stage: allocated / grown by pnp_set_kspace_mc, pnp_reset_mc, pnp_acquire_mc
+    int mc_coils = 0;            // coils of the installed constants; 0: the single-coil stage runs
+    int mc_cg = 0;               // CG iterations per step
+    int mc_sens_n = 1;
+    float2* mc_y = nullptr;      // [N,C,H,W] sgn * S y per coil (reset_kernel's y0s convention)
+    float2* mc_work = nullptr;   // [N,C,H,W] coil-image scratch
+    float2* mc_sens = nullptr;   // [sens_n,C,H,W]
+    size_t mc_y_cap = 0, mc_work_cap = 0, mc_sens_cap = 0;   // capacities in complex elements
+    float2* mc_vec = nullptr;    // [4,N,H,W]: A^H y and the CG vectors r, p, q
+    double* mc_part = nullptr;   // [N, sense_chunks, 2] per-workgroup sums
+    double* mc_sc = nullptr;     // [N, 8] CG scalars (rs, bb, alpha, beta, frozen)
     // profiling
     std::vector<EventPair> events;
     size_t ev_used = 0;
@@ -283,9 +294,167 @@ int run_unet(pnp_engine* e, const float* ximg, const float2* z, const float2* u,
     return PNP_OK;
 }
 
+// ---- multi-coil stage -------------------------------------------------------------------------------
+// plain (unshifted) orthonormal 2-D transform of `batch` planes in place, by the passes pnp_fft2c would choose
+int mc_fft2(pnp_engine* e, float2* data, int batch, int inverse, hipStream_t s) {
+    const int H = e->cfg.h, W = e->cfg.w;
+    const bool mixed = !is_pow2(H) || !is_pow2(W);
+    auto rows = [&]() -> int {
+        Prof p(e, s, 3, -1);
+        if (mixed) HIP_TRY(launch_fft_rows_mixed(data, data, e->plan.tw_w, batch, H, W, inverse, 0, s));
+        else HIP_TRY(launch_fft_rows_generic(data, data, e->plan.tw_w, batch, H, W, inverse, 0, 0, s));
+        return PNP_OK;
+    };
+    auto cols = [&]() -> int {
+        Prof p(e, s, 4, -1);
+        if (mixed) HIP_TRY(launch_fft_cols_mixed(data, e->plan.tw_h, batch, H, W, inverse, 0, s));
+        else HIP_TRY(launch_fft_cols_generic(data, e->plan.tw_h, batch, H, W, inverse, 0, 0, s));
+        return PNP_OK;
+    };
+    int rc;
+    if (inverse) { if ((rc = cols()) || (rc = rows())) return rc; }
+    else { if ((rc = rows()) || (rc = cols())) return rc; }
+    return PNP_OK;
+}
+
+float2* mc_aty(pnp_engine* e) { return e->mc_vec; }
+float2* mc_r(pnp_engine* e) { return e->mc_vec + (size_t)e->cfg.n * e->cfg.h * e->cfg.w; }
+float2* mc_p(pnp_engine* e) { return e->mc_vec + 2 * (size_t)e->cfg.n * e->cfg.h * e->cfg.w; }
+float2* mc_q(pnp_engine* e) { return e->mc_vec + 3 * (size_t)e->cfg.n * e->cfg.h * e->cfg.w; }
+
+// q = A^H A pv + mu pv; the partial sums of Re<pv, q> go to mc_part.  Unfused: seven launches.
+int mc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, C = e->mc_coils;
+    int rc;
+    {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_sense_expand(pv, nullptr, e->mc_sens, e->mc_sens_n, C, tact, e->mc_work, N, H, W, s));
+    }
+    if ((rc = mc_fft2(e, e->mc_work, N * C, 0, s))) return rc;
+    {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_sense_mask(e->mc_work, e->d_masks, e->mask_n, C, N, H, W, s));
+    }
+    if ((rc = mc_fft2(e, e->mc_work, N * C, 1, s))) return rc;
+    Prof p(e, s, 5, -1);
+    HIP_TRY(launch_sense_combine(e->mc_work, e->mc_sens, e->mc_sens_n, C, pv, mu, tact, q, e->mc_part, N, H, W, s));
+    return PNP_OK;
+}
+
+// the K-step CG solve of (A^H A + mu I) z = A^H y + mu (x + u), warm-started from z, then u <- u + x - z
+int run_prox_dual_mc(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u, hipStream_t s) {
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    int rc;
+    if ((rc = mc_normal(e, z, mu, tact, mc_q(e), s))) return rc;
+    {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_sense_cg_init(mc_aty(e), x, u, mc_q(e), mu, tact, mc_r(e), mc_p(e), e->mc_part, N, H, W, s));
+        HIP_TRY(launch_sense_scalar(e->mc_part, 0, tact, e->mc_sc, N, H, W, s));
+        p.end(2);
+    }
+    for (int k = 0; k < e->mc_cg; ++k) {
+        if ((rc = mc_normal(e, mc_p(e), mu, tact, mc_q(e), s))) return rc;
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_sense_scalar(e->mc_part, 1, tact, e->mc_sc, N, H, W, s));
+        HIP_TRY(launch_sense_cg_update(z, mc_r(e), mc_p(e), mc_q(e), e->mc_sc, tact, e->mc_part, N, H, W, s));
+        HIP_TRY(launch_sense_scalar(e->mc_part, 2, tact, e->mc_sc, N, H, W, s));
+        HIP_TRY(launch_sense_cg_dir(mc_r(e), mc_p(e), e->mc_sc, tact, N, H, W, s));
+        p.end(4);
+    }
+    Prof p(e, s, 5, -1);
+    HIP_TRY(launch_sense_dual(x, z, u, tact, N, H, W, s));
+    return PNP_OK;
+}
+
+// Grow the coil workspace to hold `y_need`, `work_need`, `sens_need` complex elements (0: leave that buffer alone) and the per-slice vectors.
+// All-or-nothing: every new buffer is allocated before any old one is released; buffers that grow lose their contents (their callers rewrite them).
+int mc_ensure(pnp_engine* e, size_t y_need, size_t work_need, size_t sens_need) {
+    const size_t px = (size_t)e->cfg.n * e->cfg.h * e->cfg.w;
+    const size_t part_bytes = (size_t)e->cfg.n * sense_chunks(e->cfg.h, e->cfg.w) * 2 * sizeof(double), sc_bytes = (size_t)e->cfg.n * 8 * sizeof(double);
+    struct Want { void** slot; size_t bytes, old_bytes; void* fresh; size_t* cap; size_t new_cap; };
+    Want w[6] = {
+        {(void**)&e->mc_y, y_need > e->mc_y_cap ? y_need * sizeof(float2) : 0, e->mc_y_cap * sizeof(float2), nullptr, &e->mc_y_cap, y_need},
+        {(void**)&e->mc_work, work_need > e->mc_work_cap ? work_need * sizeof(float2) : 0, e->mc_work_cap * sizeof(float2), nullptr, &e->mc_work_cap, work_need},
+        {(void**)&e->mc_sens, sens_need > e->mc_sens_cap ? sens_need * sizeof(float2) : 0, e->mc_sens_cap * sizeof(float2), nullptr, &e->mc_sens_cap, sens_need},
+        {(void**)&e->mc_vec, e->mc_vec ? 0 : 4 * px * sizeof(float2), 0, nullptr, nullptr, 0},
+        {(void**)&e->mc_part, e->mc_part ? 0 : part_bytes, 0, nullptr, nullptr, 0},
+        {(void**)&e->mc_sc, e->mc_sc ? 0 : sc_bytes, 0, nullptr, nullptr, 0},
+    };
+    bool any = false;
+    for (auto& q : w) {
+        if (q.bytes == 0) continue;
+        any = true;
+        if (hipMalloc(&q.fresh, q.bytes) != hipSuccess) {
+            for (auto& r : w) (void)hipFree(r.fresh);
+            return fail(PNP_ERR_NOMEM, "coil workspace: %zu bytes (the handle keeps the workspace it had)", q.bytes);
+        }
+    }
+    if (!any) return PNP_OK;
+    if (w[5].fresh && hipMemset(w[5].fresh, 0, sc_bytes) != hipSuccess) {
+        for (auto& r : w) (void)hipFree(r.fresh);
+        return fail(PNP_ERR_HIP, "coil workspace: hipMemset failed");
+    }
+    (void)hipDeviceSynchronize();                          // no launch still reads a buffer being replaced
+    for (auto& q : w) {
+        if (!q.fresh) continue;
+        (void)hipFree(*q.slot);
+        *q.slot = q.fresh;
+        e->ws_bytes += q.bytes - q.old_bytes;
+        if (q.cap) *q.cap = q.new_cap;
+    }
+    return PNP_OK;
+}
+
+// argument errors shared by the three multi-coil entry points that take maps and a mask: before any HIP call
+// (the scalar ranges come first and need no handle: they are reported whatever else is wrong)
+int mc_check_scalars(const char* fn, int coils, int sens_n, int mask_n) {
+    if (coils < 1 || coils > PNP_MC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_MC_MAX_COILS, coils);
+    if (sens_n < 1) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n (got %d)", fn, sens_n);
+    if (mask_n < 1) return fail(PNP_ERR_INVALID, "%s: mask_n must be 1 or n (got %d)", fn, mask_n);
+    return PNP_OK;
+}
+int mc_check(const char* fn, pnp_engine* e, int coils, int sens_n, int mask_n) {
+    const int N = e->cfg.n;
+    if (sens_n != 1 && sens_n != N) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n=%d", fn, N);
+    if (mask_n != 1 && mask_n != N) return fail(PNP_ERR_INVALID, "%s: mask_n must be 1 or n=%d", fn, N);
+    if (!kspace_len_ok(e->cfg.h) || !kspace_len_ok(e->cfg.w))
+        return fail(PNP_ERR_INVALID, "%s: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", fn, e->cfg.h, e->cfg.w);
+    if ((long long)N * coils > 65535) return fail(PNP_ERR_INVALID, "%s: n * coils must be <= 65535 (got %d * %d)", fn, N, coils);
+    return PNP_OK;
+}
+
+int mc_install(pnp_engine* e, const float2* x0, const float2* y0, const float2* sens, int coils, int sens_n, const uint8_t* mask, int mask_n,
+               int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    const size_t hw = (size_t)H * W, img = (size_t)N * coils * hw, sn = (size_t)sens_n * coils * hw;
+    int rc;
+    if ((rc = mc_ensure(e, img, img, sn))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->mc_sens, sens, sn * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
+    e->mask_n = mask_n;
+    e->mc_coils = coils; e->mc_cg = cg_iters; e->mc_sens_n = sens_n;
+    e->reset_done = true;
+    {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_sense_install(y0, mask, mask_n, coils, e->mc_y, e->mc_work, e->d_masks, N, H, W, s));
+    }
+    // aty = A^H y = sum_c conj(S_c) IFFT(masked ys_c)
+    if ((rc = mc_fft2(e, e->mc_work, N * coils, 1, s))) return rc;
+    {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_sense_combine(e->mc_work, e->mc_sens, sens_n, coils, nullptr, nullptr, nullptr, mc_aty(e), nullptr, N, H, W, s));
+    }
+    if (x0) {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
+    }
+    return PNP_OK;
+}
+
 int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                   hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (e->mc_coils > 0) return run_prox_dual_mc(e, mu, tact, x, z, u, s);   // multi-coil constants installed: the CG stage
     if (H == 128 && W == 128 && N >= e->tune.slice128_min_n) {   // chip-filling batches of the reference's slice size: 37 B/px
         Prof p(e, s, 4, -1);
         HIP_TRY(launch_admm_slice128(x, z, u, e->plan.tw_w, e->d_y0s, e->d_masks, e->mask_n, mu, tact, N, s));
@@ -522,6 +691,7 @@ int pnp_destroy(pnp_handle e) {
     for (int i = 0; i < N_LAYERS; ++i) { (void)hipFree(e->d_wpack[i]); (void)hipFree(e->d_bias[i]); }
     for (auto& L : e->lv) { (void)hipFree(L.p); (void)hipFree(L.q); (void)hipFree(L.s); (void)hipFree(L.pool); }
     (void)hipFree(e->d_work); (void)hipFree(e->d_fftq); (void)hipFree(e->d_y0s); (void)hipFree(e->d_masks); (void)hipFree(e->d_ssim_part); (void)hipFree(e->d_res_part); (void)hipFree(e->d_partial); (void)hipFree(e->d_arrive);
+    (void)hipFree(e->mc_y); (void)hipFree(e->mc_work); (void)hipFree(e->mc_sens); (void)hipFree(e->mc_vec); (void)hipFree(e->mc_part); (void)hipFree(e->mc_sc);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     delete e;
@@ -604,6 +774,7 @@ int pnp_reset(pnp_handle e, const float* x0, const float* y0, const uint8_t* mas
         return fail(PNP_ERR_INVALID, "pnp_reset: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", e->cfg.h, e->cfg.w);
     PNP_ON_DEVICE(e);
     e->mask_n = mask_n;
+    e->mc_coils = 0;                                       // back to the single-coil stage
     // the two experimental in-launch hand-over schemes keep counters between launches (PNP_SPLITK_INLAUNCH: arrival counters that return to zero;
     // PNP_FFT_XCD: ticket / completion counters read against a launch epoch): a launch that faulted half way would leave them out of step for good,
     // so an episode starts from zero
@@ -624,6 +795,7 @@ int pnp_set_kspace(pnp_handle e, const float* y0, const uint8_t* mask, int mask_
         return fail(PNP_ERR_INVALID, "pnp_set_kspace: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", e->cfg.h, e->cfg.w);
     PNP_ON_DEVICE(e);
     e->mask_n = mask_n;
+    e->mc_coils = 0;                                       // back to the single-coil stage
     HIP_TRY(launch_reset(nullptr, (const float2*)y0, mask, mask_n, nullptr, nullptr, nullptr, e->d_y0s, e->d_masks,
                          e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
     e->reset_done = true;
@@ -769,7 +941,17 @@ int pnp_residuals(pnp_handle e, const float* x, const float* z, const float* u, 
         HIP_TRY(launch_residual_tiles(x, (const float2*)z, (const float2*)u, (const float*)pv, pv ? (const float2*)(pv + px * 4) : nullptr,
                                       pv ? (const float2*)(pv + px * 12) : nullptr, part, N, H, W, s));
     }
-    if (flags & PNP_RES_DC) {
+    if ((flags & PNP_RES_DC) && e->mc_coils > 0) {
+        // multi-coil mode: the plain transforms of S_c x into the coil scratch, then sum_c ||M (FFT(S_c x) - ys_c)||^2
+        int rc;
+        {
+            Prof p(e, s, 5, -1);
+            HIP_TRY(launch_sense_expand(nullptr, x, e->mc_sens, e->mc_sens_n, e->mc_coils, nullptr, e->mc_work, N, H, W, s));
+        }
+        if ((rc = mc_fft2(e, e->mc_work, N * e->mc_coils, 0, s))) return rc;
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_sense_misfit(e->mc_work, e->mc_y, e->d_masks, e->mask_n, e->mc_coils, dcpart, N, H, W, s));
+    } else if (flags & PNP_RES_DC) {
         // the plain (unshifted) transform of x into the data-fidelity stage's scratch, by the passes pnp_fft2c would choose; the shifts
         // of fft_c live in the stored constants (reset_kernel)
         const bool mixed = !is_pow2(H) || !is_pow2(W);
@@ -843,6 +1025,108 @@ int pnp_acquire(pnp_handle e, const float* gt, const uint8_t* mask, int mask_n, 
     }
     return PNP_OK;
     PNP_API_END("pnp_acquire")
+}
+
+int pnp_set_kspace_mc(pnp_handle e, const float* y0, const float* sens, int coils, int sens_n, const uint8_t* mask, int mask_n, int cg_iters,
+                      void* stream) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call; scalar ranges first
+    if (cg_iters < 1 || cg_iters > PNP_MC_MAX_CG) return fail(PNP_ERR_INVALID, "pnp_set_kspace_mc: cg_iters must be 1..%d (got %d)", PNP_MC_MAX_CG, cg_iters);
+    if (int rc = mc_check_scalars("pnp_set_kspace_mc", coils, sens_n, mask_n)) return rc;
+    if (!y0) return fail(PNP_ERR_INVALID, "pnp_set_kspace_mc: null y0");
+    if (!sens) return fail(PNP_ERR_INVALID, "pnp_set_kspace_mc: null sens");
+    if (!mask) return fail(PNP_ERR_INVALID, "pnp_set_kspace_mc: null mask");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_set_kspace_mc: null handle");
+    if (int rc = mc_check("pnp_set_kspace_mc", e, coils, sens_n, mask_n)) return rc;
+    PNP_ON_DEVICE(e);
+    return mc_install(e, nullptr, (const float2*)y0, (const float2*)sens, coils, sens_n, mask, mask_n, cg_iters, nullptr, nullptr, nullptr,
+                      (hipStream_t)stream);
+    PNP_API_END("pnp_set_kspace_mc")
+}
+
+int pnp_reset_mc(pnp_handle e, const float* x0, const float* y0, const float* sens, int coils, int sens_n, const uint8_t* mask, int mask_n,
+                 int cg_iters, float* x, float* z, float* u, void* stream) {
+    PNP_API_BEGIN
+    if (cg_iters < 1 || cg_iters > PNP_MC_MAX_CG) return fail(PNP_ERR_INVALID, "pnp_reset_mc: cg_iters must be 1..%d (got %d)", PNP_MC_MAX_CG, cg_iters);
+    if (int rc = mc_check_scalars("pnp_reset_mc", coils, sens_n, mask_n)) return rc;
+    if (!x0) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null x0");
+    if (!y0) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null y0");
+    if (!sens) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null sens");
+    if (!mask) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null mask");
+    if (!x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null x, z or u");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null handle");
+    if (int rc = mc_check("pnp_reset_mc", e, coils, sens_n, mask_n)) return rc;
+    PNP_ON_DEVICE(e);
+    if (e->d_arrive) HIP_TRY(hipMemsetAsync(e->d_arrive, 0, 4096 * sizeof(unsigned), (hipStream_t)stream));   // as pnp_reset: an episode starts from zero
+    return mc_install(e, (const float2*)x0, (const float2*)y0, (const float2*)sens, coils, sens_n, mask, mask_n, cg_iters, x, (float2*)z,
+                      (float2*)u, (hipStream_t)stream);
+    PNP_API_END("pnp_reset_mc")
+}
+
+int pnp_mc_coils(pnp_handle e) { return e ? e->mc_coils : 0; }
+
+int pnp_mc_cg_residual(pnp_handle e, float* out, void* stream) {
+    PNP_API_BEGIN
+    if (!e || !out) return fail(PNP_ERR_INVALID, "pnp_mc_cg_residual: null argument");
+    if (e->mc_coils == 0) return fail(PNP_ERR_STATE, "pnp_mc_cg_residual: the handle is in single-coil mode (pnp_set_kspace_mc / pnp_reset_mc)");
+    PNP_ON_DEVICE(e);
+    Prof p(e, (hipStream_t)stream, 5, -1);
+    HIP_TRY(launch_sense_cgres(e->mc_sc, out, e->cfg.n, (hipStream_t)stream));
+    return PNP_OK;
+    PNP_API_END("pnp_mc_cg_residual")
+}
+
+int pnp_mc_normal(pnp_handle e, const float* pv, const float* mu, float* q, void* stream) {
+    PNP_API_BEGIN
+    if (!e || !pv || !mu || !q) return fail(PNP_ERR_INVALID, "pnp_mc_normal: null argument");
+    if (pv == q) return fail(PNP_ERR_INVALID, "pnp_mc_normal: p and q must not alias");
+    if (e->mc_coils == 0) return fail(PNP_ERR_STATE, "pnp_mc_normal: the handle is in single-coil mode (pnp_set_kspace_mc / pnp_reset_mc)");
+    PNP_ON_DEVICE(e);
+    return mc_normal(e, (const float2*)pv, mu, nullptr, (float2*)q, (hipStream_t)stream);
+    PNP_API_END("pnp_mc_normal")
+}
+
+int pnp_acquire_mc(pnp_handle e, const float* gt, const float* sens, int coils, int sens_n, const uint8_t* mask, int mask_n, double sigma_n,
+                   uint64_t seed, int flags, float* y0, float* aty0, float* x0, void* stream) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call, and leaves the outputs untouched
+    if (flags != 0) return fail(PNP_ERR_INVALID, "pnp_acquire_mc: flags must be 0 (got 0x%x)", (unsigned)flags);
+    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "pnp_acquire_mc: sigma_n must be finite and >= 0 (got %g)", sigma_n);
+    if (int rc = mc_check_scalars("pnp_acquire_mc", coils, sens_n, mask_n)) return rc;
+    if (!gt) return fail(PNP_ERR_INVALID, "pnp_acquire_mc: null gt");
+    if (!sens) return fail(PNP_ERR_INVALID, "pnp_acquire_mc: null sens");
+    if (!mask) return fail(PNP_ERR_INVALID, "pnp_acquire_mc: null mask");
+    if (!y0) return fail(PNP_ERR_INVALID, "pnp_acquire_mc: null y0");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_acquire_mc: null handle");
+    if (int rc = mc_check("pnp_acquire_mc", e, coils, sens_n, mask_n)) return rc;
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = mc_ensure(e, 0, (size_t)N * coils * H * W, 0))) return rc;
+    // the plain transforms of S_c gt in the coil scratch, by pnp_acquire's passes; the shifts of fft_c live in the epilogue's indices and sign
+    {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_sense_expand(nullptr, gt, (const float2*)sens, sens_n, coils, nullptr, e->mc_work, N, H, W, s));
+    }
+    if ((rc = mc_fft2(e, e->mc_work, N * coils, 0, s))) return rc;
+    {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_acquire_epilogue(e->mc_work, mask, mask_n, (float2*)y0, sigma_n, seed, N, H, W, s, coils));
+    }
+    if (!aty0 && !x0) return PNP_OK;
+    if ((rc = mc_fft2(e, e->mc_work, N * coils, 1, s))) return rc;
+    float2* const a = aty0 ? (float2*)aty0 : mc_q(e);       // without aty0 the coil sum goes to a CG vector (dead between steps)
+    {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_sense_combine(e->mc_work, (const float2*)sens, sens_n, coils, nullptr, nullptr, nullptr, a, nullptr, N, H, W, s));
+    }
+    if (x0) {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
+    }
+    return PNP_OK;
+    PNP_API_END("pnp_acquire_mc")
 }
 
 size_t pnp_snapshot_bytes(pnp_handle e) {

@@ -231,8 +231,35 @@ hipError_t launch_fft_rows_real_mixed(const float* x, float2* work, const float2
 // ---- simulated acquisition (acquire_kernels.hip) ---------------------------------------------------
 // work: the plain orthonormal transform of gt (unshifted); mask, y0: centred layout.  Stores y0 and leaves sgn * S y0 in work (reset_kernel's y0s
 // convention), whose plain inverse transform is ifft_c(y0).  Noise: synthetic._gauss of (seed + n, 9001 / 9003, centred pixel), float64.
+// coils > 1 (pnp_acquire_mc): work / y0 hold N * coils planes, plane n * coils + c takes slice n's mask and the streams 9001 + 4 c / 9003 + 4 c
 hipError_t launch_acquire_epilogue(float2* work, const uint8_t* mask, int mask_n, float2* y0, double sigma, uint64_t seed, int N, int H, int W,
-                                   hipStream_t s);
+                                   hipStream_t s, int coils = 1);
 hipError_t launch_acquire_clamp(const float2* aty0, float2* x0, int N, int H, int W, hipStream_t s);
+
+// ---- multi-coil (SENSE) data fidelity (sense_kernels.hip) -------------------------------------------
+// Pointwise kernels around the plain FFT passes at batch N * C; work / ys: [N, C, H, W] complex, sens: [sens_n, C, H, W], masks: the rolled
+// layout reset_kernel stores.  tact (or nullptr): slices with tact[n] > 0.5 are skipped.
+static constexpr int kSenseChunk = 2048;   // contiguous pixels of one slice per workgroup
+int sense_chunks(int H, int W);            // workgroups (= float64 partial pairs) per slice
+hipError_t launch_sense_expand(const float2* src, const float* src_real, const float2* sens, int sens_n, int C, const float* tact, float2* work,
+                               int N, int H, int W, hipStream_t s);                    // work = S_c . src (src_real != nullptr: a real image)
+hipError_t launch_sense_mask(float2* work, const uint8_t* masks, int mask_n, int C, int N, int H, int W, hipStream_t s);
+// q = sum_c conj(S_c) work (+ mu pv); partial ([N, chunks, 2], column 0) = Re<pv, q> per chunk; pv / partial may be nullptr
+hipError_t launch_sense_combine(const float2* work, const float2* sens, int sens_n, int C, const float2* pv, const float* mu, const float* tact,
+                                float2* q, double* partial, int N, int H, int W, hipStream_t s);
+hipError_t launch_sense_cg_init(const float2* aty, const float* x, const float2* u, const float2* q, const float* mu, const float* tact, float2* r,
+                                float2* pv, double* partial, int N, int H, int W, hipStream_t s);
+// sc: [N, 8] float64 (rs, bb, alpha, beta, frozen); mode 0: rs, bb from the init partials, 1: alpha from Re<p, q>, 2: beta and rs from <r, r>
+hipError_t launch_sense_scalar(const double* partial, int mode, const float* tact, double* sc, int N, int H, int W, hipStream_t s);
+hipError_t launch_sense_cg_update(float2* z, float2* r, const float2* pv, const float2* q, const double* sc, const float* tact, double* partial,
+                                  int N, int H, int W, hipStream_t s);
+hipError_t launch_sense_cg_dir(const float2* r, float2* pv, const double* sc, const float* tact, int N, int H, int W, hipStream_t s);
+hipError_t launch_sense_dual(const float* x, const float2* z, float2* u, const float* tact, int N, int H, int W, hipStream_t s);
+hipError_t launch_sense_cgres(const double* sc, float* out, int N, hipStream_t s);
+hipError_t launch_sense_misfit(const float2* fx, const float2* ys, const uint8_t* masks, int mask_n, int C, double* dcpartial, int N, int H, int W,
+                               hipStream_t s);
+hipError_t launch_sense_install(const float2* y, const uint8_t* mask, int mask_n, int C, float2* ys, float2* work, uint8_t* masks, int N, int H,
+                                int W, hipStream_t s);
+hipError_t launch_sense_iterate(const float2* x0, float* x, float2* z, float2* u, int N, int H, int W, hipStream_t s);
 
 }  // namespace pnp

@@ -89,11 +89,57 @@ class PnPEngine:
         blob = np.ascontiguousarray(flatten_state_dict(state_dict))
         _lib.check(self.lib.pnp_load_unet_weights(self._h, blob.ctypes.data, blob.size), "pnp_load_unet_weights")
 
+    # -- multi-coil helpers ----------------------------------------------------------------
+    def _sens(self, sens: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+        """Coil maps complex64 [C,H,W] (shared) or [N,C,H,W] -> (tensor, coils, sens_n)."""
+        hw = self.h * self.w
+        if sens.dim() not in (3, 4) or tuple(sens.shape[-2:]) != (self.h, self.w) or (sens.dim() == 4 and sens.shape[0] != self.n):
+            raise ValueError(f"sens: expected [C,{self.h},{self.w}] or [{self.n},C,{self.h},{self.w}], got {tuple(sens.shape)}")
+        coils = int(sens.shape[-3])
+        sens = self._chk(sens, torch.complex64, sens.numel(), "sens")
+        return sens, coils, (1 if sens.dim() == 3 else self.n)
+
+    @property
+    def coils(self) -> int:
+        """Coils of the installed multi-coil constants; 0 in single-coil mode."""
+        return int(self.lib.pnp_mc_coils(self._h))
+
+    def cg_residual(self) -> torch.Tensor:
+        """float32 [N]: the relative residual the CG solve of the last step ended with (pnp_mc_cg_residual; multi-coil mode only)."""
+        out = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pnp_mc_cg_residual(self._h, out.data_ptr(), self._stream()), "pnp_mc_cg_residual")
+        return out
+
+    def normal_op(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+        """q = A^H A p + mu p with the installed multi-coil constants (pnp_mc_normal); p complex64 [N,1,H,W], mu float32 [N]."""
+        nhw = self.n * self.h * self.w
+        self._chk(p, torch.complex64, nhw, "p"); self._chk(mu, torch.float32, self.n, "mu")
+        q = torch.empty_like(p)
+        _lib.check(self.lib.pnp_mc_normal(self._h, p.data_ptr(), mu.data_ptr(), q.data_ptr(), self._stream()), "pnp_mc_normal")
+        return q
+
     # -- hot path --------------------------------------------------------------------------
-    def reset(self, x0: torch.Tensor, y0: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """x0, y0 complex64 [N,1,H,W]; mask bool/uint8 [H,W] (or [N,H,W]).  Returns fresh (x f32, z c64, u c64)."""
+    def reset(self, x0: torch.Tensor, y0: torch.Tensor, mask: torch.Tensor, sens: Optional[torch.Tensor] = None,
+              cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """x0, y0 complex64 [N,1,H,W]; mask bool/uint8 [H,W] (or [N,H,W]).  Returns fresh (x f32, z c64, u c64).
+        With sens (complex64 [C,H,W] or [N,C,H,W]) y0 is [N,C,H,W] and the handle enters multi-coil mode (pnp_reset_mc): the k-space
+        subproblem is then solved by `cg_iters` conjugate-gradient iterations per step."""
         nhw = self.n * self.h * self.w
         x0 = self._chk(x0, torch.complex64, nhw, "x0")
+        if sens is not None:
+            sens, coils, sens_n = self._sens(sens)
+            y0 = self._chk(y0, torch.complex64, nhw * coils, "y0")
+            m = mask.to(torch.uint8).contiguous()
+            if m.numel() not in (self.h * self.w, nhw):
+                raise ValueError(f"mask: expected {self.h * self.w} or {nhw} elements, got {tuple(mask.shape)}")
+            x = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device)
+            z = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+            u = torch.empty_like(z)
+            _lib.check(self.lib.pnp_reset_mc(self._h, x0.data_ptr(), y0.data_ptr(), sens.data_ptr(), coils, sens_n, m.data_ptr(),
+                                             1 if m.numel() == self.h * self.w else self.n, int(cg_iters), x.data_ptr(), z.data_ptr(),
+                                             u.data_ptr(), self._stream()), "pnp_reset_mc")
+            self.live_episode = _next_episode()
+            return x, z, u
         y0 = self._chk(y0, torch.complex64, nhw, "y0")
         m = mask.to(torch.uint8).contiguous()
         if m.numel() == self.h * self.w:
@@ -111,15 +157,25 @@ class PnPEngine:
         self.live_episode = _next_episode()
         return x, z, u
 
-    def set_kspace(self, y0: torch.Tensor, mask: torch.Tensor, episode: int = 0) -> None:
+    def set_kspace(self, y0: torch.Tensor, mask: torch.Tensor, episode: int = 0, sens: Optional[torch.Tensor] = None,
+                   cg_iters: int = 8) -> None:
         """Re-install the k-space constants (y0, mask) of another episode without touching any iterate
-        (pnp_set_kspace); `episode` = the id that episode's reset returned (0: a fresh id)."""
+        (pnp_set_kspace); `episode` = the id that episode's reset returned (0: a fresh id).  With sens: a multi-coil episode's
+        constants (pnp_set_kspace_mc), as in `reset`."""
         nhw = self.n * self.h * self.w
-        y0 = self._chk(y0, torch.complex64, nhw, "y0")
         m = mask.to(torch.uint8).contiguous()
         if m.numel() not in (self.h * self.w, nhw):
             raise ValueError(f"mask: expected {self.h * self.w} or {nhw} elements, got {tuple(mask.shape)}")
         self._chk(m, torch.uint8, m.numel(), "mask")
+        if sens is not None:
+            sens, coils, sens_n = self._sens(sens)
+            y0 = self._chk(y0, torch.complex64, nhw * coils, "y0")
+            _lib.check(self.lib.pnp_set_kspace_mc(self._h, y0.data_ptr(), sens.data_ptr(), coils, sens_n, m.data_ptr(),
+                                                  1 if m.numel() == self.h * self.w else self.n, int(cg_iters), self._stream()),
+                       "pnp_set_kspace_mc")
+            self.live_episode = episode or _next_episode()
+            return
+        y0 = self._chk(y0, torch.complex64, nhw, "y0")
         _lib.check(self.lib.pnp_set_kspace(self._h, y0.data_ptr(), m.data_ptr(), 1 if m.numel() == self.h * self.w else self.n,
                                            self._stream()), "pnp_set_kspace")
         self.live_episode = episode or _next_episode()
@@ -203,8 +259,12 @@ class PnPEngine:
                                           self._stream()), "pnp_residuals")
         return out
 
-    def acquire(self, gt: torch.Tensor, mask: torch.Tensor, sigma_n: float, seed: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """Simulated CS-MRI acquisition of the engine's N slices on the device (pnp_acquire): gt float32 [N,1,H,W] in [0, 1], mask
+    def acquire(self, gt: torch.Tensor, mask: torch.Tensor, sigma_n: float, seed: int,
+                sens: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """With sens (complex64 [C,H,W] or [N,C,H,W]): the multi-coil acquisition (pnp_acquire_mc), y0 complex64 [N,C,H,W] with
+        y_c = mask * (fft_c(S_c gt) + sigma_n * noise_c), ATy0 = sum_c conj(S_c) ifft_c(y_c).  Without:
+
+        Simulated CS-MRI acquisition of the engine's N slices on the device (pnp_acquire): gt float32 [N,1,H,W] in [0, 1], mask
         bool/uint8 [H,W] (or [N,H,W]) in the centred layout.  Returns complex64 [N,1,H,W] tensors (y0, ATy0, x0) with
         y0 = mask * (fft_c(gt) + sigma_n * noise), ATy0 = ifft_c(y0), x0 = max(ATy0, 0) on both planes; slice n draws the noise
         `synthetic.make_problem` draws for seed + n."""
@@ -217,6 +277,15 @@ class PnPEngine:
         seed = int(seed)
         if not 0 <= seed < 2 ** 64 - self.n:
             raise ValueError(f"seed: expected 0 <= seed < 2**64 - n, got {seed}")
+        if sens is not None:
+            sens, coils, sens_n = self._sens(sens)
+            y0 = torch.empty((self.n, coils, self.h, self.w), dtype=torch.complex64, device=self.device)
+            aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+            x0 = torch.empty_like(aty0)
+            _lib.check(self.lib.pnp_acquire_mc(self._h, gt.data_ptr(), sens.data_ptr(), coils, sens_n, m.data_ptr(),
+                                               1 if m.numel() == self.h * self.w else self.n, float(sigma_n), seed, 0, y0.data_ptr(),
+                                               aty0.data_ptr(), x0.data_ptr(), self._stream()), "pnp_acquire_mc")
+            return y0, aty0, x0
         y0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
         aty0, x0 = torch.empty_like(y0), torch.empty_like(y0)
         _lib.check(self.lib.pnp_acquire(self._h, gt.data_ptr(), m.data_ptr(), 1 if m.numel() == self.h * self.w else self.n,

@@ -38,8 +38,9 @@ def _as_complex(t: torch.Tensor) -> torch.Tensor:
 
 class PnPEnv:
     def __init__(self, max_episode_step: int, denoiser: UNetDenoiser2D, device_type,
-                 no_ref_scorer: Optional[Callable[[torch.Tensor], float]] = None, replica: int = 0) -> None:
+                 no_ref_scorer: Optional[Callable[[torch.Tensor], float]] = None, replica: int = 0, cg_iters: int = 8) -> None:
         self.max_episode_step = max_episode_step
+        self.cg_iters = int(cg_iters)           # multi-coil episodes: conjugate-gradient iterations per step
         self.denoiser = denoiser.to(device_type)
         self.no_ref_model = no_ref_scorer
         self._engine: Optional[PnPEngine] = None
@@ -49,7 +50,7 @@ class PnPEnv:
     def fork(self, replica: int) -> "PnPEnv":
         """Another env on the same denoiser weights whose engines are replicas of their own (own workspace, own k-space
         constants): two sub-batches of one job can then be stepped concurrently on two streams."""
-        return PnPEnv(self.max_episode_step, self.denoiser, self._device_type, self.no_ref_model, replica=replica)
+        return PnPEnv(self.max_episode_step, self.denoiser, self._device_type, self.no_ref_model, replica=replica, cg_iters=self.cg_iters)
 
     # ---- engine management ------------------------------------------------------------------
     def _engine_for(self, n: int, h: int, w: int, device: torch.device) -> PnPEngine:
@@ -67,7 +68,17 @@ class PnPEnv:
         h, w = x0.shape[-2:]
         n = x0.numel() // (h * w)
         x0 = x0.reshape(n, 1, h, w).to(device).contiguous()
-        y0 = _as_complex(torch.as_tensor(data["y0"])).reshape(n, 1, h, w).to(device).contiguous()
+        sens = data.get("sens") if hasattr(data, "get") else None
+        if sens is not None:                    # a multi-coil problem: sens [C,H,W] or [N,C,H,W], y0 with a coil axis
+            sens = torch.as_tensor(sens)
+            sens = (sens if sens.is_complex() else _as_complex(sens)).to(torch.complex64)
+            if sens.dim() not in (3, 4) or tuple(sens.shape[-2:]) != (h, w) or (sens.dim() == 4 and sens.shape[0] != n):
+                raise ValueError(f"sens: expected [C,{h},{w}] or [{n},C,{h},{w}], got {tuple(sens.shape)}")
+            sens = sens.to(device).contiguous()
+            coils = sens.shape[-3]
+        else:
+            coils = 1
+        y0 = _as_complex(torch.as_tensor(data["y0"])).reshape(n, coils, h, w).to(device).contiguous()
         mask = torch.as_tensor(data["mask"])
         mask = mask.reshape(-1, h, w) if mask.numel() != h * w else mask.reshape(h, w)
         if mask.dim() == 3 and mask.shape[0] not in (1, n):
@@ -75,11 +86,11 @@ class PnPEnv:
         mask = mask.to(device).to(torch.bool).contiguous()
         gt = torch.as_tensor(data["gt"]).to(device).float()
         eng = self._engine_for(n, h, w, device)
-        x, z, u = eng.reset(x0, y0, mask)
+        x, z, u = eng.reset(x0, y0, mask, sens=sens, cg_iters=self.cg_iters)
         aty0 = torch.as_tensor(data["ATy0"])[..., 0] if "ATy0" in data else None
         return OrderedDict({"x": x, "y0": y0, "z": z, "u": u, "mask": mask, "gt": gt, "ATy0": aty0,
                             "T": torch.zeros(n, dtype=torch.float32, device=device),
-                            "complex_y0": data["y0"], "_episode": eng.live_episode})
+                            "complex_y0": data["y0"], "_episode": eng.live_episode, "sens": sens})
 
     def _bind_episode(self, eng: PnPEngine, states) -> None:
         """Make the engine's k-space constants those of `states` (env.py:88-90 reads y0 / mask from the dict)."""
@@ -89,10 +100,12 @@ class PnPEnv:
         if not ep:                              # a state dict built by hand the reference's way
             ep = states["_episode"] = _next_episode()
         n, h, w = eng.n, eng.h, eng.w
-        y0 = _as_complex(states["y0"]).reshape(n, 1, h, w).to(eng.device).contiguous()
+        sens = states.get("sens")
+        coils = 1 if sens is None else sens.shape[-3]
+        y0 = _as_complex(states["y0"]).reshape(n, coils, h, w).to(eng.device).contiguous()
         mask = torch.as_tensor(states["mask"]).to(eng.device)
         mask = mask.reshape(h, w) if mask.numel() == h * w else mask.reshape(n, h, w)
-        eng.set_kspace(y0, mask, episode=ep)
+        eng.set_kspace(y0, mask, episode=ep, sens=sens, cg_iters=self.cg_iters)
 
     def _param(self, v, n: int, device) -> torch.Tensor:
         t = torch.as_tensor(v, dtype=torch.float32, device=device).reshape(-1)

@@ -204,6 +204,58 @@ int pnp_residuals(pnp_handle h, const float* x, const float* z, const float* u, 
 int pnp_acquire(pnp_handle h, const float* gt, const uint8_t* mask, int mask_n, double sigma_n, uint64_t seed, int flags,
                 float* y0, float* aty0, float* x0, void* stream);
 
+/* ---- multi-coil (SENSE) data fidelity ----------------------------------------------------------
+ * The reference restores single-coil acquisitions only: its k-space subproblem has the closed form of pnp_prox_dual because the forward
+ * operator is M F.  With C coil sensitivity maps S_c the operator of slice n is
+ *     A p = [ M . fft_c(S_c . p) ]_c ,   A^H q = sum_c conj(S_c) . ifft_c(M . q_c) ,   Nop(p) = A^H A p + mu_n p
+ * (fft_c / ifft_c = the centred orthonormal pair of pnp_fft2c) and the subproblem (A^H A + mu I) z = A^H y + mu (x + u) is solved by a FIXED
+ * number K = cg_iters of conjugate-gradient iterations, warm-started from the incoming z.  Per slice that is not stopped:
+ *     v = x + u;  b = aty + mu v  (aty = A^H y, formed once when the constants are installed);  r = b - Nop(z);  p = r;  rs = <r,r>;  bb = <b,b>
+ *     K times:  q = Nop(p);  pq = Re<p,q>;  rs <= 0 or pq <= 0 ? (alpha = 0, beta = 0 : a frozen slice, never NaN) : alpha = rs / pq;
+ *               z += alpha p;  r -= alpha q;  rs' = <r,r>;  beta = rs' / rs (0 when frozen);  p = r + beta p;  rs = rs'
+ *     cg_res[n] = sqrt(rs / bb) (0 when bb == 0);   u <- u + x - z
+ * Inner products are per slice; their terms are float32 values, multiplied and summed in float64 in a fixed order (no atomics): bitwise
+ * reproducible, and a slice's bits depend neither on N nor on its place in the batch.  alpha and beta are computed in float64, live in
+ * device memory and are applied as float32; no entry point synchronises with the host during a step.  Stopped slices (t_action > 0.5)
+ * keep z and u bit for bit.  With C = 1 and S = 1 the operator has the two eigenvalues mu and 1 + mu, CG is exact after two iterations
+ * and the stage is the reference's closed form.
+ *
+ * WHICH stage pnp_step / pnp_prox_dual run is decided by the constants installed LAST: pnp_set_kspace_mc / pnp_reset_mc put the handle in
+ * multi-coil mode, pnp_set_kspace / pnp_reset return it to the single-coil stage (and it then gives the bits of a handle that never was in
+ * multi-coil mode).  In multi-coil mode pnp_residuals' PNP_RES_DC column is sqrt(sum_c ||M (fft_c(S_c x) - y_c)||^2).
+ * SETUP-TIME SEMANTICS: pnp_set_kspace_mc / pnp_reset_mc / pnp_acquire_mc allocate or grow the handle's coil workspace inside the call
+ * (y: N C H W complex, scratch: N C H W complex, the maps: sens_n C H W complex, A^H y and three CG vectors: N H W complex each, partial
+ * sums and scalars), which may synchronise the device; a call that does not need to grow it is asynchronous like pnp_reset.  The growth is
+ * all-or-nothing (on PNP_ERR_NOMEM the handle keeps the workspace and the mode it had) and is counted by pnp_workspace_bytes.
+ *   y0   : DEVICE complex64 [N,C,H,W], centred layout
+ *   sens : DEVICE complex64 [C,H,W] (sens_n == 1, shared by all slices) or [N,C,H,W] (sens_n == N); copied, need not outlive the call
+ *   mask : as in pnp_reset;   coils : 1..PNP_MC_MAX_COILS;   cg_iters : 1..PNP_MC_MAX_CG
+ * Sizes the k-space stage accepts (any other is refused); any handle kind (PNP_FLAG_NO_DENOISER, bf16 convs).  Every argument error (NULLs,
+ * coils outside 1..32, sens_n / mask_n not 1 or N, cg_iters outside 1..64, sigma_n negative or not finite) is reported before any HIP call
+ * and leaves the outputs untouched. */
+#define PNP_MC_MAX_COILS 32
+#define PNP_MC_MAX_CG 64
+int pnp_set_kspace_mc(pnp_handle h, const float* y0, const float* sens, int coils, int sens_n, const uint8_t* mask, int mask_n, int cg_iters,
+                      void* stream);
+/* pnp_set_kspace_mc plus pnp_reset's iterate: x = Re(x0), z = x0, u = 0 (x0 complex64 [N,1,H,W], e.g. pnp_acquire_mc's x0). */
+int pnp_reset_mc(pnp_handle h, const float* x0, const float* y0, const float* sens, int coils, int sens_n, const uint8_t* mask, int mask_n,
+                 int cg_iters, float* x, float* z, float* u, void* stream);
+/* Coils of the installed multi-coil constants; 0 on a handle in single-coil mode (and on NULL). */
+int pnp_mc_coils(pnp_handle h);
+/* out : DEVICE float32 [N], the relative residual sqrt(rs / bb) the CG solve of the last pnp_step / pnp_prox_dual ended with (a slice that
+ * was stopped in that call keeps its earlier value; 0 before the first solve).  PNP_ERR_STATE on a handle in single-coil mode. */
+int pnp_mc_cg_residual(pnp_handle h, float* out, void* stream);
+/* q = Nop(p) = A^H A p + mu p with the installed constants: p, q DEVICE complex64 [N,1,H,W] (must not alias), mu DEVICE float32 [N].  The
+ * operator on its own, for tests and timing.  PNP_ERR_STATE on a handle in single-coil mode. */
+int pnp_mc_normal(pnp_handle h, const float* p, const float* mu, float* q, void* stream);
+/* pnp_acquire for C coils:  y_c = mask ? fft_c(S_c gt) + sigma_n (g_re + i g_im) : +0.0;  aty0 = A^H y;  x0 = max(aty0, 0) on both planes.
+ *   gt : DEVICE float32 [N,1,H,W];  sens, mask : as above;  y0 : DEVICE complex64 [N,C,H,W];  aty0, x0 : complex64 [N,1,H,W] or NULL
+ * Noise: pnp_acquire's counter hash with the streams 9001 + 4 c (real) and 9003 + 4 c (imaginary) for coil c, seed + n for slice n; with
+ * C = 1 and S = 1 every output equals pnp_acquire's bit for bit.  flags : reserved, must be 0.  Does not change the handle's mode or
+ * installed constants; uses (and may grow) the coil scratch. */
+int pnp_acquire_mc(pnp_handle h, const float* gt, const float* sens, int coils, int sens_n, const uint8_t* mask, int mask_n, double sigma_n,
+                   uint64_t seed, int flags, float* y0, float* aty0, float* x0, void* stream);
+
 /* ---- tree search support --------------------------------------------------------------------- */
 
 /* Replaces: the per-child copy of `states` in expand_tree (evaluation/mcts.py:118-128), which the reference gets for
