@@ -70,6 +70,70 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
     return out
 
 
+def _centred_run(ok: np.ndarray) -> int:
+    """Largest even a with ok[L/2 - a/2 : L/2 + a/2] all true (ok: bool [L], L even)."""
+    half = len(ok) // 2
+    a = 0
+    while a < half and ok[half + a] and ok[half - 1 - a]:
+        a += 1
+    return 2 * a
+
+
+def acs_block(mask) -> Tuple[int, int]:
+    """(acs_h, acs_w): the largest centred rectangle with even sides that `mask` (bool [H,W], or [N,H,W]: the intersection over the
+    slices) samples completely - bins -acs_h/2 <= ky - H/2 < acs_h/2, -acs_w/2 <= kx - W/2 < acs_w/2 of the centred layout, the
+    calibration block `estimate_sens` reads.  A mask of whole columns gives (H, its centred run of columns), one of whole rows
+    (its centred run of rows, W); any other (radial) the centred square widened until a bin is missing.  ValueError when not even
+    the centre 2 x 2 bins are sampled."""
+    m = np.asarray(mask) != 0
+    if m.ndim == 3:
+        m = m.all(axis=0)
+    if m.ndim != 2 or m.shape[0] % 2 or m.shape[1] % 2:
+        raise ValueError(f"acs_block: expected a mask [H,W] or [N,H,W] with even H, W, got {tuple(np.asarray(mask).shape)}")
+    h, w = m.shape
+    a = _centred_run(m.all(axis=0))                          # whole columns
+    if a >= 2:
+        return h, a
+    a = _centred_run(m.all(axis=1))                          # whole rows
+    if a >= 2:
+        return a, w
+    a = 0
+    while 2 * (a + 1) <= min(h, w) and m[h // 2 - a - 1:h // 2 + a + 1, w // 2 - a - 1:w // 2 + a + 1].all():
+        a += 1
+    if a == 0:
+        raise ValueError("acs_block: the mask does not sample the centre 2 x 2 bins of k-space: no calibration block")
+    return 2 * a, 2 * a
+
+
+def estimate_sens(engine_or_env, y0, mask=None, acs=None, window: str = "hann", thresh: float = 0.05) -> torch.Tensor:
+    """Coil sensitivity maps estimated on the device from the calibration block of multi-coil k-space (pnp_estimate_sens): complex64
+    [N,C,H,W] on the GPU, ready for `data['sens']` / `PnPEngine.reset(..., sens=)`.  y0: [N,C,H,W] complex, or [N,C,H,W,2] real
+    (array or tensor), centred layout.  acs = (acs_h, acs_w), or None for `acs_block(mask)`: the largest centred block the mask
+    samples completely.  This is the low-resolution estimate (window, transform back, divide by the root-sum-of-squares over the
+    coils), not ESPIRiT."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("estimate_sens needs a ROCm GPU")
+    y = torch.as_tensor(y0)
+    if not y.is_complex():
+        if y.dim() != 5 or y.shape[-1] != 2:
+            raise ValueError(f"y0: expected complex [N,C,H,W] or real [N,C,H,W,2], got {tuple(y.shape)}")
+        y = torch.view_as_complex(y.float().contiguous())
+    if y.dim() != 4:
+        raise ValueError(f"y0: expected [N,C,H,W], got {tuple(y.shape)}")
+    n, _, h, w = (int(v) for v in y.shape)
+    if acs is None:
+        if mask is None:
+            raise ValueError("estimate_sens: give acs=(acs_h, acs_w) or the sampling mask")
+        acs = acs_block(torch.as_tensor(mask).cpu().numpy())
+    eng = engine_or_env if hasattr(engine_or_env, "estimate_sens") else None
+    device = eng.device if eng is not None else torch.device("cuda", torch.cuda.current_device())
+    if eng is None:
+        eng = _engine(engine_or_env, n, h, w, device)
+    if (eng.n, eng.h, eng.w) != (n, h, w):
+        raise ValueError(f"y0 {tuple(y.shape)} does not fit the engine [{eng.n},{eng.h},{eng.w}]")
+    return eng.estimate_sens(y.to(eng.device, torch.complex64).contiguous(), acs, window=window, thresh=thresh)
+
+
 def _centre_block(w: int, center_fraction: float) -> np.ndarray:
     nc = int(round(w * center_fraction))
     lo = (w - nc) // 2

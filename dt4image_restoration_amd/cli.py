@@ -24,6 +24,11 @@ subproblem is then solved by K conjugate-gradient iterations per step (`acquire`
 layout has none):
 
     ... --coils 4 --cg-iters 8 eval|flex|mcts|fixed ...
+    ... --coils 4 --sens estimate [--sens-window hann|box] [--sens-thresh 0.05] [--acs H W] --mask cartesian fixed ...
+
+`--sens estimate` does not hand the solver the maps that generated the measurements: the maps are estimated on the device from the
+fully sampled centre of each set's own y0 (pnp_estimate_sens; the block is the largest one the set's mask samples completely, or
+--acs).  The initial iterate x0 stays the one the set brings.
 
 Multi-GPU (BASELINE configs[2]): launch the same command under `python -m torch.distributed.run --nproc-per-node N
 --master-addr 127.0.0.1 -m dt4image_restoration_amd.cli ... eval|mcts|flex ...`: every rank takes a contiguous shard of each
@@ -76,6 +81,20 @@ def _tasks(args):
     return tasks
 
 
+def _with_sens(args, env, batch):
+    """--sens estimate: the batch with its coil maps replaced by the estimate from its own y0 and mask (on the device)."""
+    if args.sens != "estimate":
+        return batch
+    from . import acquisition
+    batch = dict(batch)
+    try:
+        batch["sens"] = acquisition.estimate_sens(env, batch["y0"], mask=batch["mask"], acs=args.acs, window=args.sens_window,
+                                                  thresh=args.sens_thresh)
+    except ValueError as e:                                    # a mask without a sampled centre, a block that does not fit
+        raise SystemExit(f"--sens estimate: {e}")
+    return batch
+
+
 def _sets(args, flex_target=None, env=None):
     """(name, number of images, load(start, stop) -> (batch dict, task tokens)) per evaluation set."""
     from . import acquisition, data as D, synthetic
@@ -85,7 +104,7 @@ def _sets(args, flex_target=None, env=None):
                 def load(a, b, d=d, task=task):
                     gt, _ = D.load_gt_dir(d, limit=args.limit, start=a, stop=b)
                     batch = acquisition.task_problem(task, gt, env, seed=args.seed, first_slice=a, mask_kind=args.mask, coils=args.coils)
-                    return batch, D.task_tokens([task] * (b - a), flex_target)
+                    return _with_sens(args, env, batch), D.task_tokens([task] * (b - a), flex_target)
                 yield f"{d} {task}", D.count_gt_dir(d, args.limit), load
     elif args.data:
         if args.coils:
@@ -98,16 +117,20 @@ def _sets(args, flex_target=None, env=None):
     else:
         for accel, sig in ((4, 10), (8, 10)):
             def load(a, b, accel=accel, sig=sig):
+                # the synthetic sets are radial; a --sens estimate run may ask for --mask cartesian, whose calibration block is H x the
+                # centre columns (None: the radial mask of make_problem, as every other run gets)
+                mask = acquisition.make_mask(args.size, args.size, accel, args.mask, args.seed) \
+                    if args.sens == "estimate" and args.mask != "radial" else None
                 if args.acquire == "device":                   # make_problem's phantoms, mask and noise; the transforms on the GPU
                     gt = np.stack([synthetic.phantom(args.size, args.size, args.seed + accel + i) for i in range(a, b)])
                     sens = synthetic.coil_maps(args.coils, args.size, args.size).astype(np.complex64) if args.coils else None
-                    p = acquisition.simulate(env, gt.astype(np.float32), synthetic.radial_mask(args.size, args.size, accel), sig / 255.0,
-                                             args.seed + accel, first_slice=a, sens=sens)
-                    return p, D.task_tokens([f"{accel}x_{sig}"] * (b - a), flex_target)
+                    p = acquisition.simulate(env, gt.astype(np.float32), synthetic.radial_mask(args.size, args.size, accel) if mask is None else mask,
+                                             sig / 255.0, args.seed + accel, first_slice=a, sens=sens)
+                    return (_with_sens(args, env, p) if args.coils else p), D.task_tokens([f"{accel}x_{sig}"] * (b - a), flex_target)
                 if args.coils:
                     p = synthetic.make_problem_mc(b - a, args.size, args.size, args.coils, accel=accel, sigma_n=sig / 255.0,
-                                                  seed=args.seed + accel, first_slice=a)
-                    return p, D.task_tokens([f"{accel}x_{sig}"] * (b - a), flex_target)
+                                                  seed=args.seed + accel, first_slice=a, mask=mask)
+                    return _with_sens(args, env, p), D.task_tokens([f"{accel}x_{sig}"] * (b - a), flex_target)
                 p = synthetic.make_problem(b - a, args.size, args.size, accel=accel, sigma_n=sig / 255.0, seed=args.seed + accel,
                                            first_slice=a)
                 return p, D.task_tokens([f"{accel}x_{sig}"] * (b - a), flex_target)
@@ -163,7 +186,8 @@ def main(argv=None):
     ap.add_argument("--gt", nargs="+", default=None, help="directories of ground-truth images (.npy / .mat with a `gt` key), "
                     "acquired on the device: one set per (directory, task)")
     ap.add_argument("--tasks", default=None, help="comma-separated tasks for --gt, e.g. 4x_10,8x_15 (default: the reference's nine)")
-    ap.add_argument("--mask", choices=("radial", "cartesian"), default="radial", help="sampling mask of the --gt sets")
+    ap.add_argument("--mask", choices=("radial", "cartesian"), default="radial", help="sampling mask of the --gt sets "
+                    "(and of the synthetic sets of a --sens estimate run)")
     ap.add_argument("--acquire", choices=("cpu", "device"), default="cpu",
                     help="where the synthetic sets are acquired: synthetic.make_problem on the CPU, or pnp_acquire on the GPU")
     ap.add_argument("--limit", type=int, default=None, help="images per directory (default 7: the reference averages the first 7; "
@@ -172,6 +196,13 @@ def main(argv=None):
     ap.add_argument("--coils", type=int, default=0, help="multi-coil (SENSE) problems with this many analytic coil maps (1..32; "
                     "default 0: single-coil)")
     ap.add_argument("--cg-iters", type=int, default=8, help="conjugate-gradient iterations per step of a multi-coil problem (1..64)")
+    ap.add_argument("--sens", choices=("true", "estimate"), default="true", help="coil maps of a --coils run: the analytic maps that "
+                    "generated the measurements, or maps estimated on the device from the calibration block of each set's own y0")
+    ap.add_argument("--sens-window", choices=("hann", "box"), default="hann", help="window of the calibration block (--sens estimate)")
+    ap.add_argument("--sens-thresh", type=float, default=0.05, help="--sens estimate: pixels whose root-sum-of-squares is not above this "
+                    "fraction of the slice's largest get zero maps (in [0, 1))")
+    ap.add_argument("--acs", type=int, nargs=2, default=None, metavar=("H", "W"), help="--sens estimate: even sides of the centred "
+                    "calibration block (default: the largest block the mask samples completely)")
     ap.add_argument("--seed", type=int, default=0)
     sub = ap.add_subparsers(dest="mode", required=True)
     for name in ("eval", "mcts"):
@@ -205,6 +236,13 @@ def main(argv=None):
         raise SystemExit(f"--coils must be 1..32, got {args.coils}")
     if not 1 <= args.cg_iters <= 64:
         raise SystemExit(f"--cg-iters must be 1..64, got {args.cg_iters}")
+    if args.sens == "estimate":
+        if not args.coils:
+            raise SystemExit("--sens estimate needs --coils: there are no coil maps to estimate on a single-coil problem")
+        if not 0.0 <= args.sens_thresh < 1.0:
+            raise SystemExit(f"--sens-thresh must be in [0, 1), got {args.sens_thresh}")
+        if args.acs is not None and any(v < 2 or v % 2 for v in args.acs):
+            raise SystemExit(f"--acs: sides must be even and >= 2, got {args.acs}")
     if args.mode == "acquire":
         if args.coils:
             raise SystemExit("acquire --coils: refused - the reference's .mat layout this command writes has no coil axis")

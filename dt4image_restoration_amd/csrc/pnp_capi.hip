@@ -117,6 +117,9 @@ struct pnp_engine {
     float2* mc_vec = nullptr;    // [4,N,H,W]: A^H y and the CG vectors r, p, q
     double* mc_part = nullptr;   // [N, sense_chunks, 2] per-workgroup sums
     double* mc_sc = nullptr;     // [N, 8] CG scalars (rs, bb, alpha, beta, frozen)
+    // coil map estimate (pnp_estimate_sens): allocated inside its first call
+    float* cm_max = nullptr;     // [N, coilmap_chunks] per-workgroup maxima of rss, then smax [N]
+    float* cm_rss = nullptr;     // [N,H,W] rss for callers that pass none
     // profiling
     std::vector<EventPair> events;
     size_t ev_used = 0;
@@ -451,6 +454,24 @@ int mc_install(pnp_engine* e, const float2* x0, const float2* y0, const float2* 
     return PNP_OK;
 }
 
+// The workspace of pnp_estimate_sens: the maxima / smax buffer and, with `own_rss`, the rss plane.  Neither is ever replaced, so nothing in flight
+// reads a buffer that goes away; all-or-nothing: both allocations are made before either is installed.
+int cm_ensure(pnp_engine* e, bool own_rss) {
+    const size_t max_bytes = (size_t)e->cfg.n * (coilmap_chunks(e->cfg.h, e->cfg.w) + 1) * sizeof(float);
+    const size_t rss_bytes = (size_t)e->cfg.n * e->cfg.h * e->cfg.w * sizeof(float);
+    void* fresh_max = nullptr;
+    void* fresh_rss = nullptr;
+    if (!e->cm_max && hipMalloc(&fresh_max, max_bytes) != hipSuccess)
+        return fail(PNP_ERR_NOMEM, "coil map workspace: %zu bytes (the handle keeps the workspace it had)", max_bytes);
+    if (own_rss && !e->cm_rss && hipMalloc(&fresh_rss, rss_bytes) != hipSuccess) {
+        (void)hipFree(fresh_max);
+        return fail(PNP_ERR_NOMEM, "coil map workspace: %zu bytes (the handle keeps the workspace it had)", rss_bytes);
+    }
+    if (fresh_max) { e->cm_max = (float*)fresh_max; e->ws_bytes += max_bytes; }
+    if (fresh_rss) { e->cm_rss = (float*)fresh_rss; e->ws_bytes += rss_bytes; }
+    return PNP_OK;
+}
+
 int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                   hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
@@ -692,6 +713,7 @@ int pnp_destroy(pnp_handle e) {
     for (auto& L : e->lv) { (void)hipFree(L.p); (void)hipFree(L.q); (void)hipFree(L.s); (void)hipFree(L.pool); }
     (void)hipFree(e->d_work); (void)hipFree(e->d_fftq); (void)hipFree(e->d_y0s); (void)hipFree(e->d_masks); (void)hipFree(e->d_ssim_part); (void)hipFree(e->d_res_part); (void)hipFree(e->d_partial); (void)hipFree(e->d_arrive);
     (void)hipFree(e->mc_y); (void)hipFree(e->mc_work); (void)hipFree(e->mc_sens); (void)hipFree(e->mc_vec); (void)hipFree(e->mc_part); (void)hipFree(e->mc_sc);
+    (void)hipFree(e->cm_max); (void)hipFree(e->cm_rss);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     delete e;
@@ -1127,6 +1149,48 @@ int pnp_acquire_mc(pnp_handle e, const float* gt, const float* sens, int coils, 
     }
     return PNP_OK;
     PNP_API_END("pnp_acquire_mc")
+}
+
+int pnp_estimate_sens(pnp_handle e, const float* y0, int coils, int acs_h, int acs_w, int window, double thresh, int flags, float* sens,
+                      float* rss, void* stream) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call, and leaves the outputs untouched; scalar ranges first
+    if (flags != 0) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: flags must be 0 (got 0x%x)", (unsigned)flags);
+    if (!(thresh >= 0.0) || !(thresh < 1.0)) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: thresh must be finite and in [0, 1) (got %g)", thresh);
+    if (window != PNP_SENS_BOX && window != PNP_SENS_HANN)
+        return fail(PNP_ERR_INVALID, "pnp_estimate_sens: window must be PNP_SENS_BOX or PNP_SENS_HANN (got %d)", window);
+    if (coils < 1 || coils > PNP_MC_MAX_COILS) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: coils must be 1..%d (got %d)", PNP_MC_MAX_COILS, coils);
+    if (acs_h < 2 || (acs_h & 1)) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: acs_h must be even and >= 2 (got %d)", acs_h);
+    if (acs_w < 2 || (acs_w & 1)) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: acs_w must be even and >= 2 (got %d)", acs_w);
+    if (!y0) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: null y0");
+    if (!sens) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: null sens");
+    if (sens == y0) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: sens must not alias y0");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: null handle");
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (acs_h > H) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: acs_h must be <= h=%d (got %d)", H, acs_h);
+    if (acs_w > W) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: acs_w must be <= w=%d (got %d)", W, acs_w);
+    if (!kspace_len_ok(H) || !kspace_len_ok(W))
+        return fail(PNP_ERR_INVALID, "pnp_estimate_sens: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", H, W);
+    if ((long long)N * coils > 65535) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: n * coils must be <= 65535 (got %d * %d)", N, coils);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = cm_ensure(e, rss == nullptr))) return rc;
+    float* const r = rss ? rss : e->cm_rss;
+    float* const smax = e->cm_max + (size_t)N * coilmap_chunks(H, W);
+    {
+        Prof p(e, s, 5, -1);
+        HIP_TRY(launch_coilmap_window((const float2*)y0, (float2*)sens, acs_h, acs_w, window == PNP_SENS_HANN, N, coils, H, W, s));
+    }
+    // l_c = the plain inverse transform of the windowed, sign-folded block, in place in the caller's buffer
+    if ((rc = mc_fft2(e, (float2*)sens, N * coils, 1, s))) return rc;
+    Prof p(e, s, 5, -1);
+    HIP_TRY(launch_coilmap_rss((const float2*)sens, coils, r, e->cm_max, N, H, W, s));
+    HIP_TRY(launch_coilmap_max(e->cm_max, smax, N, H, W, s));
+    HIP_TRY(launch_coilmap_normalise((float2*)sens, coils, r, smax, (float)thresh, N, H, W, s));
+    p.end(3);
+    return PNP_OK;
+    PNP_API_END("pnp_estimate_sens")
 }
 
 size_t pnp_snapshot_bytes(pnp_handle e) {

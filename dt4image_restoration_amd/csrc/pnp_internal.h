@@ -262,4 +262,16 @@ hipError_t launch_sense_install(const float2* y, const uint8_t* mask, int mask_n
                                 int W, hipStream_t s);
 hipError_t launch_sense_iterate(const float2* x0, float* x, float2* z, float2* u, int N, int H, int W, hipStream_t s);
 
+// ---- coil sensitivity maps from the calibration block (coilmap_kernels.hip) -------------------------
+// Pointwise kernels around the plain inverse FFT passes at batch N * C, in place in the caller's map buffer sens: [N, C, H, W] complex.
+static constexpr int kCoilmapChunk = 2048;   // contiguous pixels of one plane per workgroup
+int coilmap_chunks(int H, int W);            // workgroups (= float32 partial maxima) per slice
+// sens[n, c][k] = in block(S k) ? sgn[k] * win * y[n, c][S k] : 0 (plain bin k; y: centred layout, read inside the acs_h x acs_w block only)
+hipError_t launch_coilmap_window(const float2* y, float2* sens, int acs_h, int acs_w, int hann, int N, int C, int H, int W, hipStream_t s);
+// rss: [N, H, W] = sqrt(sum_c |l_c|^2) (float64 sum in coil order, one rounding); partial: [N, chunks] maxima of rss
+hipError_t launch_coilmap_rss(const float2* l, int C, float* rss, float* partial, int N, int H, int W, hipStream_t s);
+hipError_t launch_coilmap_max(const float* partial, float* smax, int N, int H, int W, hipStream_t s);   // smax: [N]
+// l <- (rss > 0 and rss > thresh * smax[n]) ? l / rss : 0
+hipError_t launch_coilmap_normalise(float2* l, int C, const float* rss, const float* smax, float thresh, int N, int H, int W, hipStream_t s);
+
 }  // namespace pnp

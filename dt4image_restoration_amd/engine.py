@@ -293,6 +293,25 @@ class PnPEngine:
                    "pnp_acquire")
         return y0, aty0, x0
 
+    def estimate_sens(self, y0: torch.Tensor, acs: Tuple[int, int], window: str = "hann", thresh: float = 0.0, return_rss: bool = False):
+        """Coil sensitivity maps from the fully sampled calibration block of multi-coil k-space (pnp_estimate_sens): y0 complex64
+        [N,C,H,W] in the centred layout, acs = (acs_h, acs_w) the even sides of the centred block, window "hann" or "box".  Each
+        coil's windowed block is transformed back and divided by the root-sum-of-squares over the coils; pixels whose rss is not
+        above thresh * (the slice's largest rss) get zero maps.  Returns complex64 [N,C,H,W] per-slice maps for `reset(..., sens=)`,
+        and with return_rss also rss float32 [N,H,W].  Does not change the engine's mode or its installed constants."""
+        if y0.dim() != 4 or y0.shape[0] != self.n or tuple(y0.shape[-2:]) != (self.h, self.w):
+            raise ValueError(f"y0: expected [{self.n},C,{self.h},{self.w}], got {tuple(y0.shape)}")
+        coils = int(y0.shape[1])
+        y0 = self._chk(y0, torch.complex64, self.n * coils * self.h * self.w, "y0")
+        if window not in _lib.SENS_WINDOWS:
+            raise ValueError(f"window must be one of {tuple(_lib.SENS_WINDOWS)}, got {window!r}")
+        acs_h, acs_w = (int(v) for v in acs)
+        sens = torch.empty_like(y0)
+        rss = torch.empty((self.n, self.h, self.w), dtype=torch.float32, device=self.device) if return_rss else None
+        _lib.check(self.lib.pnp_estimate_sens(self._h, y0.data_ptr(), coils, acs_h, acs_w, _lib.SENS_WINDOWS[window], float(thresh), 0,
+                                              sens.data_ptr(), _ptr(rss), self._stream()), "pnp_estimate_sens")
+        return (sens, rss) if return_rss else sens
+
     def snapshot(self, x: torch.Tensor, z: torch.Tensor, u: torch.Tensor, t_state: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One packed device buffer [x | z | u | T] (pnp_snapshot): a tree-search node's copy of the iterate."""

@@ -256,6 +256,41 @@ int pnp_mc_normal(pnp_handle h, const float* p, const float* mu, float* q, void*
 int pnp_acquire_mc(pnp_handle h, const float* gt, const float* sens, int coils, int sens_n, const uint8_t* mask, int mask_n, double sigma_n,
                    uint64_t seed, int flags, float* y0, float* aty0, float* x0, void* stream);
 
+/* Coil sensitivity maps from the fully sampled calibration (ACS) block of multi-coil k-space: the low-resolution estimate, the first stage of
+ * the multi-coil path when the acquisition brings no maps (the reference restores single-coil data and has no counterpart).  Per slice n, with
+ * the centred bin p = (ky, kx), dy = ky - H/2, dx = kx - W/2:
+ *     in block:  -acs_h/2 <= dy < acs_h/2  and  -acs_w/2 <= dx < acs_w/2
+ *     win(p)   = 1                                                                      (PNP_SENS_BOX)
+ *              = (0.5 + 0.5 cos(2 pi dy / acs_h)) (0.5 + 0.5 cos(2 pi dx / acs_w))      (PNP_SENS_HANN)
+ *     k_c      = in block ? float32(win) * y0[n,c] : 0
+ *     l_c      = ifft_c(k_c)                        (the centred orthonormal inverse of pnp_fft2c(..., inverse = 1))
+ *     rss      = sqrt(sum_c |l_c|^2)
+ *     smax_n   = max over the slice of rss
+ *     sens_c   = (rss > 0 and rss > float32(thresh) * smax_n) ? l_c / rss : 0
+ * The window factors and their product are formed in float64 and rounded to float32 once.  The terms of rss are the float32 components of l_c,
+ * squared and summed in float64 in coil order; the square root is taken in float64 and rounded to float32 once.  The threshold product and the
+ * division are float32 (an IEEE divide).  On the kept set the maps have unit root-sum-of-squares, so they absorb the object's slowly varying
+ * phase and the image left to restore is close to real - the iterate this engine keeps.  ESPIRiT (calibration-matrix SVD, per-pixel
+ * eigen-decomposition) is not built.
+ *   y0     : DEVICE complex64 [N,C,H,W], centred layout (what pnp_reset_mc takes); read inside the block only: the block must be fully sampled
+ *   coils  : 1..PNP_MC_MAX_COILS;   acs_h, acs_w : even, 2 <= acs_h <= H, 2 <= acs_w <= W;   window : PNP_SENS_BOX or PNP_SENS_HANN
+ *   thresh : in [0, 1);   flags : reserved, must be 0
+ *   sens   : DEVICE complex64 [N,C,H,W] out: per-slice maps (sens_n = N for pnp_set_kspace_mc / pnp_reset_mc); must not alias y0.  The transforms
+ *            run in place in this buffer: there is no [N,C,H,W] workspace
+ *   rss    : DEVICE float32 [N,H,W] out, or NULL (then a plane of the handle's workspace holds it)
+ * Any handle kind (single- or multi-coil mode, PNP_FLAG_NO_DENOISER, bf16 convs); the call changes neither the handle's mode nor its installed
+ * constants.  Sizes the k-space stage accepts (any other is refused), n * coils <= 65535.  A slice's bits depend on (y0[n], acs_h, acs_w, window,
+ * thresh) only: not on N, its place in the batch, the stream or the handle kind; no atomics, bitwise reproducible.
+ * SETUP-TIME SEMANTICS, as pnp_acquire_mc: the first call allocates 4 n ceil(H W / 2048) + 4 n bytes (per-workgroup maxima and smax) and, the first
+ * time rss is NULL, 4 n H W bytes more, inside the call, all-or-nothing (on PNP_ERR_NOMEM the handle keeps the workspace it had), counted by
+ * pnp_workspace_bytes; later calls allocate nothing and are asynchronous.  Calls on one handle are stream-ordered (they share that workspace).
+ * Every argument error (null handle, y0 or sens, sens == y0, coils outside 1..32, acs_h / acs_w odd, below 2 or above the handle's H / W, an
+ * unknown window, thresh negative, >= 1 or not finite, flags != 0) is reported before any HIP call and leaves the outputs untouched. */
+#define PNP_SENS_BOX  0
+#define PNP_SENS_HANN 1
+int pnp_estimate_sens(pnp_handle h, const float* y0, int coils, int acs_h, int acs_w, int window, double thresh, int flags,
+                      float* sens, float* rss /* may be NULL */, void* stream);
+
 /* ---- tree search support --------------------------------------------------------------------- */
 
 /* Replaces: the per-child copy of `states` in expand_tree (evaluation/mcts.py:118-128), which the reference gets for
