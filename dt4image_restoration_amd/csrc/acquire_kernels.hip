@@ -19,13 +19,13 @@
 // float32 once.  Only sampled bins pay for the float64 log / sqrt / cos (compacted per workgroup).  A workgroup owns a fixed range of one slice's pixels, and the
 // counter is (seed + n, p): a slice's bits do not depend on the batch or on its place in it.
 #include "pnp_internal.h"
+#include "block_reduce.h"
 
 namespace pnp {
 
 namespace {
 
 constexpr int kAcqThreads = 256;
-constexpr int kAcqChunk = 2048;                          // centred pixels of one slice per workgroup of the epilogue
 constexpr unsigned kStreamRe = 9001u, kStreamIm = 9003u;   // synthetic.make_problem: _gauss(s, 9001, .), _gauss(s, 9003, .)
 
 // weights._splitmix64
@@ -48,19 +48,19 @@ __device__ __forceinline__ double gauss64(unsigned long long b1, unsigned long l
     return sqrt(-2.0 * log(u1)) * cos((2.0 * 3.14159265358979323846) * u2);
 }
 
-// One workgroup per kAcqChunk consecutive centred pixels of one slice.  Pass 1 reads the mask, zeroes the unsampled bins and compacts the
+// One workgroup per kPixelChunk consecutive centred pixels of one slice.  Pass 1 reads the mask, zeroes the unsampled bins and compacts the
 // sampled pixels into an LDS list; pass 2 walks the list, so that the float64 Box-Muller (some 700 instructions a pixel, 4 cycles each on a
 // wave of 64) is issued by full waves over the sampled fraction instead of by every wave of a scattered radial mask.  The order of the list
 // (LDS atomics) varies from run to run; a pixel's value does not depend on it.
 __global__ __launch_bounds__(kAcqThreads) void acquire_epilogue_kernel(float2* __restrict__ work, const uint8_t* __restrict__ mask, int mask_n,
                                                                        float2* __restrict__ y0, double sigma, unsigned long long seed,
                                                                        int H, int W, int coils) {
-    __shared__ int list[kAcqChunk];
+    __shared__ int list[kPixelChunk];
     __shared__ int count;
-    constexpr int PER = kAcqChunk / kAcqThreads;
+    constexpr int PER = kPixelChunk / kAcqThreads;
     // plane blockIdx.y = coil c of slice n (pnp_acquire: one plane per slice, c = 0)
     const int n = blockIdx.y / coils, c = blockIdx.y - n * coils, hw = H * W, hh = H >> 1, hwd = W >> 1;
-    const int p0 = blockIdx.x * kAcqChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const size_t base = (size_t)blockIdx.y * hw;
     const uint8_t* const mk = mask + (mask_n > 1 ? (size_t)n * hw : 0);
     // plain bin k = S^-1 p of the centred pixel p (H/2, W/2 even: the parities of p's and k's coordinates agree)
@@ -124,8 +124,7 @@ __global__ __launch_bounds__(kAcqThreads) void acquire_clamp_kernel(const float2
 
 hipError_t launch_acquire_epilogue(float2* work, const uint8_t* mask, int mask_n, float2* y0, double sigma, uint64_t seed, int N, int H, int W,
                                    hipStream_t s, int coils) {
-    const int hw = H * W;
-    hipLaunchKernelGGL(acquire_epilogue_kernel, dim3((hw + kAcqChunk - 1) / kAcqChunk, N * coils), dim3(kAcqThreads), 0, s, work, mask, mask_n, y0,
+    hipLaunchKernelGGL(acquire_epilogue_kernel, dim3(pixel_chunks(H, W), N * coils), dim3(kAcqThreads), 0, s, work, mask, mask_n, y0,
                        sigma, (unsigned long long)seed, H, W, coils);
     return hipGetLastError();
 }

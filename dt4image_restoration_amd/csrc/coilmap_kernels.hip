@@ -12,29 +12,17 @@
 //   coilmap_max_kernel        smax[n] = max of the slice's partials
 //   coilmap_normalise_kernel  S_c in place (the float32 division is an IEEE divide)
 // The centred bin S k of the plain bin k has dy = k1 (k1 < H/2) or k1 - H: the block is the four corners of the plain plane.
-// Every workgroup owns kCoilmapChunk consecutive pixels of one plane (slice), no atomics: a slice's bits depend on (y[n], acs, window, thresh) only.
+// Every workgroup owns kPixelChunk consecutive pixels of one plane (slice), no atomics: a slice's bits depend on (y[n], acs, window, thresh) only.
 #include "pnp_internal.h"
+#include "block_reduce.h"
 
 namespace pnp {
 
 namespace {
 
 constexpr int kCoilmapThreads = 256;
-constexpr int kCoilmapPer = kCoilmapChunk / kCoilmapThreads;     // pixels per thread
-static_assert(kCoilmapChunk % kCoilmapThreads == 0, "whole pixels per thread");
-
-// maximum of the workgroup's values by a fixed tree (wave shuffles, then the wave leaders through LDS); thread 0 returns it.  `red`: kCoilmapThreads / 64 floats
-__device__ __forceinline__ float block_max_fixed(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = red[0];
-        for (int i = 1; i < kCoilmapThreads / 64; ++i) t = fmaxf(t, red[i]);
-        v = t;
-    }
-    return v;
-}
+constexpr int kCoilmapPer = kPixelChunk / kCoilmapThreads;     // pixels per thread
+static_assert(kPixelChunk % kCoilmapThreads == 0, "whole pixels per thread");
 
 // one Hann factor at offset d of a block side L, float64
 __device__ __forceinline__ double hann64(int d, int L) { return 0.5 + 0.5 * cos((2.0 * 3.14159265358979323846) * (double)d / (double)L); }
@@ -44,7 +32,7 @@ __global__ __launch_bounds__(kCoilmapThreads) void coilmap_window_kernel(const f
                                                                          int hann, int H, int W) {
     const int HW = H * W, hh = H >> 1, hw = W >> 1, ah = acs_h >> 1, aw = acs_w >> 1;
     const size_t base = (size_t)blockIdx.y * HW;
-    const int p0 = blockIdx.x * kCoilmapChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     int src[kCoilmapPer];                                   // centred index S k of an in-block bin, -1 outside the block (or the plane)
     float2 v[kCoilmapPer];
 #pragma unroll
@@ -79,7 +67,7 @@ __global__ __launch_bounds__(kCoilmapThreads) void coilmap_rss_kernel(const floa
                                                                       float* __restrict__ partial, int HW) {
     __shared__ float red[kCoilmapThreads / 64];
     const int n = blockIdx.y;
-    const int p0 = blockIdx.x * kCoilmapChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     double acc[kCoilmapPer];
 #pragma unroll
     for (int j = 0; j < kCoilmapPer; ++j) acc[j] = 0.0;
@@ -104,7 +92,7 @@ __global__ __launch_bounds__(kCoilmapThreads) void coilmap_rss_kernel(const floa
             m = fmaxf(m, r);
         }
     }
-    m = block_max_fixed(m, red);
+    m = block_max_fixed<kCoilmapThreads>(m, red);
     if (threadIdx.x == 0) partial[(size_t)n * gridDim.x + blockIdx.x] = m;
 }
 
@@ -114,7 +102,7 @@ __global__ __launch_bounds__(kCoilmapThreads) void coilmap_max_kernel(const floa
     const int n = blockIdx.x;
     float m = 0.f;
     for (int i = threadIdx.x; i < chunks; i += kCoilmapThreads) m = fmaxf(m, partial[(size_t)n * chunks + i]);
-    m = block_max_fixed(m, red);
+    m = block_max_fixed<kCoilmapThreads>(m, red);
     if (threadIdx.x == 0) smax[n] = m;
 }
 
@@ -122,7 +110,7 @@ __global__ __launch_bounds__(kCoilmapThreads) void coilmap_max_kernel(const floa
 __global__ __launch_bounds__(kCoilmapThreads) void coilmap_normalise_kernel(float2* __restrict__ l, int C, const float* __restrict__ rss,
                                                                             const float* __restrict__ smax, float thresh, int HW) {
     const int n = blockIdx.y;
-    const int p0 = blockIdx.x * kCoilmapChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const float cut = thresh * smax[n];
     float r[kCoilmapPer];
 #pragma unroll
@@ -149,11 +137,9 @@ __global__ __launch_bounds__(kCoilmapThreads) void coilmap_normalise_kernel(floa
     }
 }
 
-inline dim3 plane_grid(int H, int W, int batch) { return dim3((unsigned)coilmap_chunks(H, W), (unsigned)batch); }
+inline dim3 plane_grid(int H, int W, int batch) { return dim3((unsigned)pixel_chunks(H, W), (unsigned)batch); }
 
 }  // namespace
-
-int coilmap_chunks(int H, int W) { return (H * W + kCoilmapChunk - 1) / kCoilmapChunk; }
 
 hipError_t launch_coilmap_window(const float2* y, float2* sens, int acs_h, int acs_w, int hann, int N, int C, int H, int W, hipStream_t s) {
     hipLaunchKernelGGL(coilmap_window_kernel, plane_grid(H, W, N * C), dim3(kCoilmapThreads), 0, s, y, sens, acs_h, acs_w, hann, H, W);
@@ -166,7 +152,7 @@ hipError_t launch_coilmap_rss(const float2* l, int C, float* rss, float* partial
 }
 
 hipError_t launch_coilmap_max(const float* partial, float* smax, int N, int H, int W, hipStream_t s) {
-    hipLaunchKernelGGL(coilmap_max_kernel, dim3(N), dim3(kCoilmapThreads), 0, s, partial, coilmap_chunks(H, W), smax);
+    hipLaunchKernelGGL(coilmap_max_kernel, dim3(N), dim3(kCoilmapThreads), 0, s, partial, pixel_chunks(H, W), smax);
     return hipGetLastError();
 }
 

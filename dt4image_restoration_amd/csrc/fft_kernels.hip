@@ -21,6 +21,7 @@
 // mixed-radix kernels of fft_mixed_kernels.hip instead.
 #include "pnp_internal.h"
 #include "fft_common.h"
+#include "block_reduce.h"
 #include <cstdlib>
 
 namespace pnp {
@@ -932,21 +933,23 @@ static inline int cols_per_block(int H, int W) {
     return c;
 }
 
-hipError_t launch_fft_rows_generic(const float2* in, float2* out, const float2* tw, int batch, int H, int W, int inverse,
-                                   int shift_in, int shift_out, hipStream_t s) {
+// the power-of-two family of the six k-space passes: reached through the dispatch below only
+namespace pow2 {
+
+// (the kernels take the shift on load and the shift on store apart; every caller wants the same one for both)
+hipError_t launch_fft_rows(const float2* in, float2* out, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s) {
     const int rpb = rows_per_block(H, W);
     const size_t lds = (size_t)(2 * rpb * W + W) * sizeof(float2);
     hipLaunchKernelGGL((fft_rows_kernel<0, 0>), dim3(batch * (H / rpb)), dim3(256), lds, s, in, out, nullptr, nullptr, tw,
-                       nullptr, H, W, rpb, inverse, shift_in, shift_out);
+                       nullptr, H, W, rpb, inverse, shift, shift);
     return hipGetLastError();
 }
-hipError_t launch_fft_cols_generic(float2* data, const float2* tw, int batch, int H, int W, int inverse, int shift_in,
-                                   int shift_out, hipStream_t s) {
+hipError_t launch_fft_cols(float2* data, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s) {
     const int cw = cols_per_block(H, W);
     const size_t lds = (size_t)(2 * cw * (H + 1) + H) * sizeof(float2);
     if (hipError_t e = raise_lds_cap()) return e;
     hipLaunchKernelGGL((fft_cols_kernel<0, 0>), dim3(batch * (W / cw)), dim3(256), lds, s, data, tw, nullptr, nullptr, 1,
-                       nullptr, nullptr, H, W, cw, inverse, shift_in, shift_out);
+                       nullptr, nullptr, H, W, cw, inverse, shift, shift);
     return hipGetLastError();
 }
 hipError_t launch_fft_rows_real(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s) {
@@ -1026,6 +1029,44 @@ hipError_t launch_fft_rows_inv_admm(const float2* work, const float* x, float2* 
     else PNP_ROWS_INV(0);
 #undef PNP_ROWS_INV
     return hipGetLastError();
+}
+
+}  // namespace pow2
+
+// ---- the six k-space passes: ONE choice of family -----------------------------------------------------------------------------
+// A handle with a side that is not a power of two (2^a * 5^b: 80 .. 800) runs the mixed-radix kernels (fft_mixed_kernels.hip) for
+// every pass, its power-of-two side included; every other handle runs the kernels of this file.  The rule lives here and nowhere else.
+static bool mixed_radix(int H, int W) {
+    auto is_pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    return !is_pow2(H) || !is_pow2(W);
+}
+
+hipError_t launch_fft_rows(const float2* in, float2* out, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s) {
+    return mixed_radix(H, W) ? mixed::launch_fft_rows(in, out, tw, batch, H, W, inverse, shift, s)
+                             : pow2::launch_fft_rows(in, out, tw, batch, H, W, inverse, shift, s);
+}
+hipError_t launch_fft_cols(float2* data, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s) {
+    return mixed_radix(H, W) ? mixed::launch_fft_cols(data, tw, batch, H, W, inverse, shift, s)
+                             : pow2::launch_fft_cols(data, tw, batch, H, W, inverse, shift, s);
+}
+hipError_t launch_fft_rows_real(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s) {
+    return mixed_radix(H, W) ? mixed::launch_fft_rows_real(x, work, tw, N, H, W, s)
+                             : pow2::launch_fft_rows_real(x, work, tw, N, H, W, s);
+}
+hipError_t launch_fft_rows_fwd_admm(const float* x, const float2* u, float2* work, const float2* tw, const float* tact, int N, int H, int W,
+                                    hipStream_t s) {
+    return mixed_radix(H, W) ? mixed::launch_fft_rows_fwd_admm(x, u, work, tw, tact, N, H, W, s)
+                             : pow2::launch_fft_rows_fwd_admm(x, u, work, tw, tact, N, H, W, s);
+}
+hipError_t launch_fft_cols_prox(float2* work, const float2* tw, const float2* y0s, const uint8_t* masks, int mask_n, const float* mu,
+                                const float* tact, int N, int H, int W, hipStream_t s) {
+    return mixed_radix(H, W) ? mixed::launch_fft_cols_prox(work, tw, y0s, masks, mask_n, mu, tact, N, H, W, s)
+                             : pow2::launch_fft_cols_prox(work, tw, y0s, masks, mask_n, mu, tact, N, H, W, s);
+}
+hipError_t launch_fft_rows_inv_admm(const float2* work, const float* x, float2* z, float2* u, const float2* tw, const float* tact, int N,
+                                    int H, int W, hipStream_t s) {
+    return mixed_radix(H, W) ? mixed::launch_fft_rows_inv_admm(work, x, z, u, tw, tact, N, H, W, s)
+                             : pow2::launch_fft_rows_inv_admm(work, x, z, u, tw, tact, N, H, W, s);
 }
 
 // ---- the per-XCD persistent form of the stage (admm_xcd_kernel) --------------------------------------------------------------
@@ -1125,9 +1166,10 @@ hipError_t launch_finish(const float* tact, float* tstate, uint8_t* done, int N,
 }
 
 // ---- PSNR (env.py:120-125): one workgroup per slice, f64 accumulation of the squared error --------
-__global__ __launch_bounds__(1024) void psnr_kernel(const float* __restrict__ x, const float* __restrict__ gt,
+constexpr int kPsnrThreads = 1024;
+__global__ __launch_bounds__(kPsnrThreads) void psnr_kernel(const float* __restrict__ x, const float* __restrict__ gt,
                                                     float* __restrict__ out, int HW) {
-    __shared__ double part[16];
+    __shared__ double part[kPsnrThreads / 64];
     const int n = blockIdx.x;
     const float* xp = x + (size_t)n * HW;
     const float* gp = gt + (size_t)n * HW;
@@ -1136,18 +1178,14 @@ __global__ __launch_bounds__(1024) void psnr_kernel(const float* __restrict__ x,
         const float d = fminf(fmaxf(xp[i], 0.f), 1.f) - gp[i];
         acc += (double)d * (double)d;
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    const double t = block_sum_fixed<0>(acc, part);        // (0: this kernel takes its width from the launch)
     if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += part[i];
         const double mse = t / (double)HW;
         out[n] = (float)(10.0 * log10(1.0 / mse));
     }
 }
 hipError_t launch_psnr(const float* x, const float* gt, float* out, int N, int HW, hipStream_t s) {
-    hipLaunchKernelGGL(psnr_kernel, dim3(N), dim3(1024), 0, s, x, gt, out, HW);
+    hipLaunchKernelGGL(psnr_kernel, dim3(N), dim3(kPsnrThreads), 0, s, x, gt, out, HW);
     return hipGetLastError();
 }
 

@@ -330,45 +330,50 @@ bool kspace_len_ok(int L) {
     return (L & (L - 1)) == 0;
 }
 
-hipError_t launch_fft_rows_mixed(const float2* in, float2* out, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s) {
+// the mixed-radix family of the six k-space passes: reached through the dispatch in fft_kernels.hip only
+namespace mixed {
+
+hipError_t launch_fft_rows(const float2* in, float2* out, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s) {
     const int rpb = mixed_rows_per_block(W);
     hipLaunchKernelGGL((fft_rows_mixed_kernel<0>), dim3(batch * (H / rpb)), dim3(256), mixed_rows_lds(W), s, in, out, nullptr, nullptr, tw,
                        nullptr, H, W, rpb, inverse, shift);
     return hipGetLastError();
 }
-hipError_t launch_fft_cols_mixed(float2* data, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s) {
+hipError_t launch_fft_cols(float2* data, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s) {
     const int cw = mixed_cols_per_block(H);
     if (hipError_t e = raise_mixed_cols_lds_cap()) return e;
     hipLaunchKernelGGL((fft_cols_mixed_kernel<0>), dim3(batch * (W / cw)), dim3(256), mixed_cols_lds(H), s, data, tw, nullptr, nullptr, 1,
                        nullptr, nullptr, H, W, cw, inverse, shift);
     return hipGetLastError();
 }
-hipError_t launch_fft_rows_fwd_mixed(const float* x, const float2* u, float2* work, const float2* tw, const float* tact, int N, int H, int W,
-                                     hipStream_t s) {
+hipError_t launch_fft_rows_fwd_admm(const float* x, const float2* u, float2* work, const float2* tw, const float* tact, int N, int H, int W,
+                                    hipStream_t s) {
     const int rpb = mixed_rows_per_block(W);
     hipLaunchKernelGGL((fft_rows_mixed_kernel<1>), dim3(N * (H / rpb)), dim3(256), mixed_rows_lds(W), s, nullptr, work, x,
                        const_cast<float2*>(u), tw, tact, H, W, rpb, 0, 0);
     return hipGetLastError();
 }
-hipError_t launch_fft_rows_real_mixed(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s) {
+hipError_t launch_fft_rows_real(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s) {
     const int rpb = mixed_rows_per_block(W);
     hipLaunchKernelGGL(fft_rows_real_m5_kernel, dim3(N * (H / rpb)), dim3(256), mixed_rows_lds(W), s, x, work, tw, H, W, rpb);
     return hipGetLastError();
 }
-hipError_t launch_fft_cols_prox_mixed(float2* work, const float2* tw, const float2* y0s, const uint8_t* masks, int mask_n, const float* mu,
-                                      const float* tact, int N, int H, int W, hipStream_t s) {
+hipError_t launch_fft_cols_prox(float2* work, const float2* tw, const float2* y0s, const uint8_t* masks, int mask_n, const float* mu,
+                                const float* tact, int N, int H, int W, hipStream_t s) {
     const int cw = mixed_cols_per_block(H);
     if (hipError_t e = raise_mixed_cols_lds_cap()) return e;
     hipLaunchKernelGGL((fft_cols_mixed_kernel<1>), dim3(N * (W / cw)), dim3(256), mixed_cols_lds(H), s, work, tw, y0s, masks, mask_n, mu,
                        tact, H, W, cw, 0, 0);
     return hipGetLastError();
 }
-hipError_t launch_fft_rows_inv_mixed(const float2* work, const float* x, float2* z, float2* u, const float2* tw, const float* tact, int N,
-                                     int H, int W, hipStream_t s) {
+hipError_t launch_fft_rows_inv_admm(const float2* work, const float* x, float2* z, float2* u, const float2* tw, const float* tact, int N,
+                                    int H, int W, hipStream_t s) {
     const int rpb = mixed_rows_per_block(W);
     hipLaunchKernelGGL((fft_rows_mixed_kernel<2>), dim3(N * (H / rpb)), dim3(256), mixed_rows_lds(W), s, work, z, x, u, tw, tact, H, W, rpb,
                        1, 0);
     return hipGetLastError();
 }
+
+}  // namespace mixed
 
 }  // namespace pnp

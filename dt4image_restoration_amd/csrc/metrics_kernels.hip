@@ -13,6 +13,7 @@
 // The filter arithmetic is plain fmaf on tap weights the compiler holds in scalar registers (kernel arguments, unrolled R); the built
 // code objects carry no packed-FP32 op whose low result reads the high register of a pair (tools/isa_audit.py, tests/test_ssim_host.py).
 #include "pnp_internal.h"
+#include "block_reduce.h"
 
 namespace pnp {
 
@@ -35,17 +36,6 @@ __device__ __forceinline__ int reflect_index(int i, int n) {
     i = i < 0 ? -i - 1 : i;
     i = i >= n ? 2 * n - 1 - i : i;
     return min(max(i, 0), n - 1);
-}
-
-__device__ __forceinline__ double block_sum_fixed(double v, double* red) {
-    // fixed-order tree: the same sum bit for bit on every call
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < kSsimThreads / 64; ++i) t += red[i];
-    return t;
 }
 
 template <int R>
@@ -139,7 +129,7 @@ __global__ __launch_bounds__(kSsimThreads) void ssim_tile_kernel(SsimArgs a) {
             sum += (double)m;
         }
     }
-    const double t = block_sum_fixed(sum, red);
+    const double t = block_sum_fixed<kSsimThreads>(sum, red);
     if (tid == 0) a.partial[((size_t)n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = t;
 }
 
@@ -149,7 +139,7 @@ __global__ __launch_bounds__(kSsimThreads) void ssim_reduce_kernel(const double*
     const int n = blockIdx.x;
     double acc = 0.0;
     for (int i = threadIdx.x; i < tiles; i += kSsimThreads) acc += partial[(size_t)n * tiles + i];
-    const double t = block_sum_fixed(acc, red);
+    const double t = block_sum_fixed<kSsimThreads>(acc, red);
     if (threadIdx.x == 0) out[n] = (float)(t * inv_hw);
 }
 

@@ -2,6 +2,7 @@
 // sequencing of one PnP-ADMM iteration, kernel-level event timing.
 #include "../../include/pnpadmm.h"
 #include "pnp_internal.h"
+#include "block_reduce.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -58,6 +59,11 @@ struct DeviceGuard {
     if (dev_guard_.err != hipSuccess) return fail(PNP_ERR_HIP, "hipSetDevice(%d): %s", (e)->cfg.device, hipGetErrorString(dev_guard_.err))
 
 constexpr size_t kNParams = 11773857;
+constexpr size_t kSplitKCounters = 4096;   // split-K arrival counters (PNP_SPLITK_INLAUNCH): one per output tile of a launch, never more than this many tiles
+
+// the profile classes of pnp_profile_collect, in the order of _lib.PROFILE_CLASS_NAMES
+enum ProfClass : int { PROF_CONV3X3 = 0, PROF_CONV_FIRST = 1, PROF_CONV_LAST = 2, PROF_FFT_ROWS = 3, PROF_FFT_COLS = 4, PROF_OTHER = 5 };
+static_assert(PROF_OTHER + 1 == PNP_PROFILE_CLASSES, "one enumerator per profile class");
 
 struct EventPair {
     hipEvent_t a, b;
@@ -103,7 +109,7 @@ struct pnp_engine {
     float2* d_y0s = nullptr;    // [N,H,W] sgn * S y0
     uint8_t* d_masks = nullptr; // [mask_n,H,W] S mask
     double* d_ssim_part = nullptr; // [N, ssim_tiles(H, W)] per-tile SSIM sums (pnp_ssim)
-    double* d_res_part = nullptr;  // [N, residual_chunks(H, W), 4] + [N, residual_chunks(H, W)] per-workgroup sums of squares (pnp_residuals)
+    double* d_res_part = nullptr;  // [N, pixel_chunks(H, W), 4] + [N, pixel_chunks(H, W)] per-workgroup sums of squares (pnp_residuals)
     int mask_n = 1;
     size_t ws_bytes = 0;
     // multi-coil (SENSE) data-fidelity stage: allocated / grown by pnp_set_kspace_mc, pnp_reset_mc, pnp_acquire_mc
@@ -115,10 +121,10 @@ struct pnp_engine {
     float2* mc_sens = nullptr;   // [sens_n,C,H,W]
     size_t mc_y_cap = 0, mc_work_cap = 0, mc_sens_cap = 0;   // capacities in complex elements
     float2* mc_vec = nullptr;    // [4,N,H,W]: A^H y and the CG vectors r, p, q
-    double* mc_part = nullptr;   // [N, sense_chunks, 2] per-workgroup sums
+    double* mc_part = nullptr;   // [N, pixel_chunks, 2] per-workgroup sums
     double* mc_sc = nullptr;     // [N, 8] CG scalars (rs, bb, alpha, beta, frozen)
     // coil map estimate (pnp_estimate_sens): allocated inside its first call
-    float* cm_max = nullptr;     // [N, coilmap_chunks] per-workgroup maxima of rss, then smax [N]
+    float* cm_max = nullptr;     // [N, pixel_chunks] per-workgroup maxima of rss, then smax [N]
     float* cm_rss = nullptr;     // [N,H,W] rss for callers that pass none
     // profiling
     std::vector<EventPair> events;
@@ -131,8 +137,12 @@ struct pnp_engine {
 
 namespace {
 
-bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 #define PNP_KSPACE_SIZES "16, 32, 64, 80, 128, 160, 256, 320, 400, 512, 640, 800, 1024"   // every L with kspace_len_ok(L)
+// the rejection of a handle whose sides the k-space stage does not take; `what`: the words between the entry point's name and the size list
+int check_kspace_sizes(const char* fn, const pnp_engine* e, const char* what = "the k-space stage takes h, w in") {
+    if (kspace_len_ok(e->cfg.h) && kspace_len_ok(e->cfg.w)) return PNP_OK;
+    return fail(PNP_ERR_INVALID, "%s: %s {" PNP_KSPACE_SIZES "} (got %dx%d)", fn, what, e->cfg.h, e->cfg.w);
+}
 
 // One HIP event pair around a kernel launch - or, with `defer_end`, around a RUN of same-class launches that follow each
 // other on the stream (the 26 conv3x3 launches of a denoiser forward): `count` launches, closed by end().  Event records
@@ -165,6 +175,19 @@ struct Prof {
     }
 };
 
+// Layout of a pnp_snapshot buffer: [x float32 | z complex64 | u complex64] over the handle's n h w pixels, then t_state float32 [n]
+struct SnapLayout {
+    size_t px, n;
+    explicit SnapLayout(const pnp_engine* e) : px((size_t)e->cfg.n * e->cfg.h * e->cfg.w), n((size_t)e->cfg.n) {}
+    size_t x_bytes() const { return px * 4; }
+    size_t zu_bytes() const { return px * 8; }             // z and u each
+    size_t t_bytes() const { return n * 4; }
+    size_t z_off() const { return x_bytes(); }
+    size_t u_off() const { return z_off() + zu_bytes(); }
+    size_t t_off() const { return u_off() + zu_bytes(); }
+    size_t bytes() const { return t_off() + t_bytes(); }
+};
+
 int make_twiddles(int L, float2** out) {
     std::vector<float2> t(L);
     for (int m = 0; m < L; ++m) {
@@ -176,6 +199,13 @@ int make_twiddles(int L, float2** out) {
     return PNP_OK;
 }
 
+// conv3x3 layer `li` on the kernel family its weights were packed for (create_impl): F(4x4) Winograd, F(2x2) Winograd or the direct kernel
+hipError_t launch_conv_layer(const pnp_engine* e, int li, const ConvArgs& a, int src_mode, hipStream_t s) {
+    if (e->wino[li] && e->wplan[li].algo == 4) return launch_conv3x3_winograd4(a, e->wplan[li], src_mode, s);
+    if (e->wino[li]) return launch_conv3x3_winograd(a, e->wplan[li], src_mode, s);
+    return launch_conv3x3(a, e->cplan[li], src_mode, s);
+}
+
 // The 27 MFMA convs + first/last layer of one denoiser forward.  Image channel = ximg, or Re(z-u).
 int run_unet(pnp_engine* e, const float* ximg, const float2* z, const float2* u, const float* sigma,
              const float* tact, float* out, hipStream_t s) {
@@ -183,7 +213,7 @@ int run_unet(pnp_engine* e, const float* ximg, const float2* z, const float2* u,
     if (e->cfg.flags & PNP_FLAG_NO_DENOISER)
         return fail(PNP_ERR_STATE, "this handle was created with PNP_FLAG_NO_DENOISER");
     if (!e->fuse_first) {
-        Prof p(e, s, 1, 0);
+        Prof p(e, s, PROF_CONV_FIRST, 0);
         HIP_TRY(launch_conv_first(ximg, z, u, sigma, tact, e->d_wpack[0], e->d_bias[0], e->lv[0].p, N, H, W, s, e->act16));
     }
     const bool per_layer = (e->cfg.flags & PNP_FLAG_PROFILE_LAYERS) != 0;
@@ -206,7 +236,7 @@ int run_unet(pnp_engine* e, const float* ximg, const float2* z, const float2* u,
         ~DiagJoin() { if (k > 1) for (int i = 0; i < k; ++i) { (void)hipEventRecord(ev[i], pool[i]); (void)hipStreamWaitEvent(s, ev[i], 0); } }
     } diag_joiner{s, diag_k, diag_pool, diag_join};
 #endif
-    Prof run(e, s, 0, -1, !per_layer, true);              // one event pair around the whole conv3x3 run
+    Prof run(e, s, PROF_CONV3X3, -1, !per_layer, true);   // one event pair around the whole conv3x3 run
     int run_launches = 0;
     auto conv = [&](int li, const float* src0, const float* src1, float* dst, int lvl, float* pooled = nullptr,
                     bool src_is_pooled = false) -> int {
@@ -232,7 +262,7 @@ int run_unet(pnp_engine* e, const float* ximg, const float2* z, const float2* u,
         if (const char* dv = getenv("PNP_DIAG_L0")) a.diag = L.level == 0 ? atoi(dv) : 0;
         if (const char* dv = getenv("PNP_DIAG_ALL")) a.diag = atoi(dv);
 #endif
-        Prof p(e, s, 0, li, per_layer);
+        Prof p(e, s, PROF_CONV3X3, li, per_layer);
         ++run_launches;
         hipStream_t ls = s;
 #ifdef PNP_DIAG
@@ -240,9 +270,7 @@ int run_unet(pnp_engine* e, const float* ximg, const float2* z, const float2* u,
         // each other - the ceiling of any scheme that overlaps a layer's tail with its successor's head (profiles/r05_ablation.md)
         if (diag_k > 1) ls = diag_pool[li % diag_k];
 #endif
-        if (e->wino[li] && e->wplan[li].algo == 4) HIP_TRY(launch_conv3x3_winograd4(a, e->wplan[li], src_mode, ls));
-        else if (e->wino[li]) HIP_TRY(launch_conv3x3_winograd(a, e->wplan[li], src_mode, ls));
-        else HIP_TRY(launch_conv3x3(a, e->cplan[li], src_mode, ls));
+        HIP_TRY(launch_conv_layer(e, li, a, src_mode, ls));
         return PNP_OK;
     };
     int rc;
@@ -281,37 +309,36 @@ int run_unet(pnp_engine* e, const float* ximg, const float2* z, const float2* u,
         if (const char* dv = getenv("PNP_DIAG_L0")) a.diag = atoi(dv);
 #endif
         {
-            Prof p(e, s, 0, 26, per_layer);
+            Prof p(e, s, PROF_CONV3X3, 26, per_layer);
             ++run_launches;
-            if (e->wino[26] && e->wplan[26].algo == 4) HIP_TRY(launch_conv3x3_winograd4(a, e->wplan[26], SRC_PLAIN, s));
-            else if (e->wino[26]) HIP_TRY(launch_conv3x3_winograd(a, e->wplan[26], SRC_PLAIN, s));
-            else HIP_TRY(launch_conv3x3(a, e->cplan[26], SRC_PLAIN, s));
+            HIP_TRY(launch_conv_layer(e, 26, a, SRC_PLAIN, s));
         }
         run.end(run_launches);
     } else {
         if ((rc = conv(26, e->lv[0].q, nullptr, e->lv[0].p, 0))) return rc;
         run.end(run_launches);
-        Prof p(e, s, 2, 27);
+        Prof p(e, s, PROF_CONV_LAST, 27);
         HIP_TRY(launch_conv_last(e->lv[0].p, ximg, z, u, tact, e->d_wpack[27], e->d_bias[27], out, N, H, W, s));
     }
     return PNP_OK;
 }
 
-// ---- multi-coil stage -------------------------------------------------------------------------------
-// plain (unshifted) orthonormal 2-D transform of `batch` planes in place, by the passes pnp_fft2c would choose
-int mc_fft2(pnp_engine* e, float2* data, int batch, int inverse, hipStream_t s) {
+// ---- the plain transform ----------------------------------------------------------------------------
+// Plain (unshifted) orthonormal 2-D transform of `batch` planes, src -> dst; the shifts of fft_c live in the constants and indices of the
+// pointwise kernels around it.  Forward: rows src -> dst (or from `real_src`, a real image read once with no complex copy of it; src unused),
+// then columns in place in dst.  Inverse: columns in place in SRC, then rows src -> dst - the other order, which rounds differently.
+// src == dst is the in-place transform: a row workgroup reads and writes its own rows only.
+int plain_fft2(pnp_engine* e, float2* src, float2* dst, int batch, int inverse, hipStream_t s, const float* real_src = nullptr) {
     const int H = e->cfg.h, W = e->cfg.w;
-    const bool mixed = !is_pow2(H) || !is_pow2(W);
     auto rows = [&]() -> int {
-        Prof p(e, s, 3, -1);
-        if (mixed) HIP_TRY(launch_fft_rows_mixed(data, data, e->plan.tw_w, batch, H, W, inverse, 0, s));
-        else HIP_TRY(launch_fft_rows_generic(data, data, e->plan.tw_w, batch, H, W, inverse, 0, 0, s));
+        Prof p(e, s, PROF_FFT_ROWS, -1);
+        if (real_src) HIP_TRY(launch_fft_rows_real(real_src, dst, e->plan.tw_w, batch, H, W, s));
+        else HIP_TRY(launch_fft_rows(src, dst, e->plan.tw_w, batch, H, W, inverse, 0, s));
         return PNP_OK;
     };
     auto cols = [&]() -> int {
-        Prof p(e, s, 4, -1);
-        if (mixed) HIP_TRY(launch_fft_cols_mixed(data, e->plan.tw_h, batch, H, W, inverse, 0, s));
-        else HIP_TRY(launch_fft_cols_generic(data, e->plan.tw_h, batch, H, W, inverse, 0, 0, s));
+        Prof p(e, s, PROF_FFT_COLS, -1);
+        HIP_TRY(launch_fft_cols(inverse ? src : dst, e->plan.tw_h, batch, H, W, inverse, 0, s));
         return PNP_OK;
     };
     int rc;
@@ -320,6 +347,7 @@ int mc_fft2(pnp_engine* e, float2* data, int batch, int inverse, hipStream_t s) 
     return PNP_OK;
 }
 
+// ---- multi-coil stage -------------------------------------------------------------------------------
 float2* mc_aty(pnp_engine* e) { return e->mc_vec; }
 float2* mc_r(pnp_engine* e) { return e->mc_vec + (size_t)e->cfg.n * e->cfg.h * e->cfg.w; }
 float2* mc_p(pnp_engine* e) { return e->mc_vec + 2 * (size_t)e->cfg.n * e->cfg.h * e->cfg.w; }
@@ -330,16 +358,16 @@ int mc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, C = e->mc_coils;
     int rc;
     {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_expand(pv, nullptr, e->mc_sens, e->mc_sens_n, C, tact, e->mc_work, N, H, W, s));
     }
-    if ((rc = mc_fft2(e, e->mc_work, N * C, 0, s))) return rc;
+    if ((rc = plain_fft2(e, e->mc_work, e->mc_work, N * C, 0, s))) return rc;
     {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_mask(e->mc_work, e->d_masks, e->mask_n, C, N, H, W, s));
     }
-    if ((rc = mc_fft2(e, e->mc_work, N * C, 1, s))) return rc;
-    Prof p(e, s, 5, -1);
+    if ((rc = plain_fft2(e, e->mc_work, e->mc_work, N * C, 1, s))) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
     HIP_TRY(launch_sense_combine(e->mc_work, e->mc_sens, e->mc_sens_n, C, pv, mu, tact, q, e->mc_part, N, H, W, s));
     return PNP_OK;
 }
@@ -350,21 +378,21 @@ int run_prox_dual_mc(pnp_engine* e, const float* mu, const float* tact, const fl
     int rc;
     if ((rc = mc_normal(e, z, mu, tact, mc_q(e), s))) return rc;
     {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_cg_init(mc_aty(e), x, u, mc_q(e), mu, tact, mc_r(e), mc_p(e), e->mc_part, N, H, W, s));
         HIP_TRY(launch_sense_scalar(e->mc_part, 0, tact, e->mc_sc, N, H, W, s));
         p.end(2);
     }
     for (int k = 0; k < e->mc_cg; ++k) {
         if ((rc = mc_normal(e, mc_p(e), mu, tact, mc_q(e), s))) return rc;
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_scalar(e->mc_part, 1, tact, e->mc_sc, N, H, W, s));
         HIP_TRY(launch_sense_cg_update(z, mc_r(e), mc_p(e), mc_q(e), e->mc_sc, tact, e->mc_part, N, H, W, s));
         HIP_TRY(launch_sense_scalar(e->mc_part, 2, tact, e->mc_sc, N, H, W, s));
         HIP_TRY(launch_sense_cg_dir(mc_r(e), mc_p(e), e->mc_sc, tact, N, H, W, s));
         p.end(4);
     }
-    Prof p(e, s, 5, -1);
+    Prof p(e, s, PROF_OTHER, -1);
     HIP_TRY(launch_sense_dual(x, z, u, tact, N, H, W, s));
     return PNP_OK;
 }
@@ -373,7 +401,7 @@ int run_prox_dual_mc(pnp_engine* e, const float* mu, const float* tact, const fl
 // All-or-nothing: every new buffer is allocated before any old one is released; buffers that grow lose their contents (their callers rewrite them).
 int mc_ensure(pnp_engine* e, size_t y_need, size_t work_need, size_t sens_need) {
     const size_t px = (size_t)e->cfg.n * e->cfg.h * e->cfg.w;
-    const size_t part_bytes = (size_t)e->cfg.n * sense_chunks(e->cfg.h, e->cfg.w) * 2 * sizeof(double), sc_bytes = (size_t)e->cfg.n * 8 * sizeof(double);
+    const size_t part_bytes = (size_t)e->cfg.n * pixel_chunks(e->cfg.h, e->cfg.w) * 2 * sizeof(double), sc_bytes = (size_t)e->cfg.n * 8 * sizeof(double);
     struct Want { void** slot; size_t bytes, old_bytes; void* fresh; size_t* cap; size_t new_cap; };
     Want w[6] = {
         {(void**)&e->mc_y, y_need > e->mc_y_cap ? y_need * sizeof(float2) : 0, e->mc_y_cap * sizeof(float2), nullptr, &e->mc_y_cap, y_need},
@@ -420,8 +448,7 @@ int mc_check(const char* fn, pnp_engine* e, int coils, int sens_n, int mask_n) {
     const int N = e->cfg.n;
     if (sens_n != 1 && sens_n != N) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n=%d", fn, N);
     if (mask_n != 1 && mask_n != N) return fail(PNP_ERR_INVALID, "%s: mask_n must be 1 or n=%d", fn, N);
-    if (!kspace_len_ok(e->cfg.h) || !kspace_len_ok(e->cfg.w))
-        return fail(PNP_ERR_INVALID, "%s: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", fn, e->cfg.h, e->cfg.w);
+    if (int rc = check_kspace_sizes(fn, e)) return rc;
     if ((long long)N * coils > 65535) return fail(PNP_ERR_INVALID, "%s: n * coils must be <= 65535 (got %d * %d)", fn, N, coils);
     return PNP_OK;
 }
@@ -438,17 +465,17 @@ int mc_install(pnp_engine* e, const float2* x0, const float2* y0, const float2* 
     e->mc_coils = coils; e->mc_cg = cg_iters; e->mc_sens_n = sens_n;
     e->reset_done = true;
     {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_install(y0, mask, mask_n, coils, e->mc_y, e->mc_work, e->d_masks, N, H, W, s));
     }
     // aty = A^H y = sum_c conj(S_c) IFFT(masked ys_c)
-    if ((rc = mc_fft2(e, e->mc_work, N * coils, 1, s))) return rc;
+    if ((rc = plain_fft2(e, e->mc_work, e->mc_work, N * coils, 1, s))) return rc;
     {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_combine(e->mc_work, e->mc_sens, sens_n, coils, nullptr, nullptr, nullptr, mc_aty(e), nullptr, N, H, W, s));
     }
     if (x0) {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
     }
     return PNP_OK;
@@ -457,7 +484,7 @@ int mc_install(pnp_engine* e, const float2* x0, const float2* y0, const float2* 
 // The workspace of pnp_estimate_sens: the maxima / smax buffer and, with `own_rss`, the rss plane.  Neither is ever replaced, so nothing in flight
 // reads a buffer that goes away; all-or-nothing: both allocations are made before either is installed.
 int cm_ensure(pnp_engine* e, bool own_rss) {
-    const size_t max_bytes = (size_t)e->cfg.n * (coilmap_chunks(e->cfg.h, e->cfg.w) + 1) * sizeof(float);
+    const size_t max_bytes = (size_t)e->cfg.n * (pixel_chunks(e->cfg.h, e->cfg.w) + 1) * sizeof(float);
     const size_t rss_bytes = (size_t)e->cfg.n * e->cfg.h * e->cfg.w * sizeof(float);
     void* fresh_max = nullptr;
     void* fresh_rss = nullptr;
@@ -477,39 +504,26 @@ int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
     if (e->mc_coils > 0) return run_prox_dual_mc(e, mu, tact, x, z, u, s);   // multi-coil constants installed: the CG stage
     if (H == 128 && W == 128 && N >= e->tune.slice128_min_n) {   // chip-filling batches of the reference's slice size: 37 B/px
-        Prof p(e, s, 4, -1);
+        Prof p(e, s, PROF_FFT_COLS, -1);
         HIP_TRY(launch_admm_slice128(x, z, u, e->plan.tw_w, e->d_y0s, e->d_masks, e->mask_n, mu, tact, N, s));
         return PNP_OK;
     }
     if (e->d_fftq != nullptr) {                           // square 256 / 512 slices, >= 8 of them: one persistent launch, scratch stays in L2
-        Prof p(e, s, 4, -1);
+        Prof p(e, s, PROF_FFT_COLS, -1);
         HIP_TRY(launch_admm_xcd(x, z, u, e->d_work, e->plan.tw_w, e->d_y0s, e->d_masks, e->mask_n, mu, tact, e->d_fftq, e->fftq_epoch, N, H, s));
         ++e->fftq_epoch;
         return PNP_OK;
     }
-    if (!is_pow2(H) || !is_pow2(W)) {                     // a side of 2^a * 5^b: the mixed-radix passes (fft_mixed_kernels.hip)
-        {
-            Prof p(e, s, 3, -1);
-            HIP_TRY(launch_fft_rows_fwd_mixed(x, u, e->d_work, e->plan.tw_w, tact, N, H, W, s));
-        }
-        {
-            Prof p(e, s, 4, -1);
-            HIP_TRY(launch_fft_cols_prox_mixed(e->d_work, e->plan.tw_h, e->d_y0s, e->d_masks, e->mask_n, mu, tact, N, H, W, s));
-        }
-        Prof p(e, s, 3, -1);
-        HIP_TRY(launch_fft_rows_inv_mixed(e->d_work, x, z, u, e->plan.tw_w, tact, N, H, W, s));
-        return PNP_OK;
-    }
-    {
-        Prof p(e, s, 3, -1);
+    {                                                     // three launches; each picks the kernel family for the handle's sides
+        Prof p(e, s, PROF_FFT_ROWS, -1);
         HIP_TRY(launch_fft_rows_fwd_admm(x, u, e->d_work, e->plan.tw_w, tact, N, H, W, s));
     }
     {
-        Prof p(e, s, 4, -1);
+        Prof p(e, s, PROF_FFT_COLS, -1);
         HIP_TRY(launch_fft_cols_prox(e->d_work, e->plan.tw_h, e->d_y0s, e->d_masks, e->mask_n, mu, tact, N, H, W, s));
     }
     {
-        Prof p(e, s, 3, -1);
+        Prof p(e, s, PROF_FFT_ROWS, -1);
         HIP_TRY(launch_fft_rows_inv_admm(e->d_work, x, z, u, e->plan.tw_w, tact, N, H, W, s));
     }
     return PNP_OK;
@@ -593,9 +607,9 @@ static int create_impl(const pnp_config* cfg, pnp_engine* e) {
         if (pf > 0) {
             if (hipMalloc((void**)&e->d_partial, pf * sizeof(float)) != hipSuccess) return fail(PNP_ERR_NOMEM, "split-K workspace");
             e->ws_bytes += pf * sizeof(float);
-            if (e->tune.splitk_inlaunch) {                 // one counter per output tile of a split-K launch: never more than 4096 tiles
-                if (hipMalloc((void**)&e->d_arrive, 4096 * sizeof(unsigned)) != hipSuccess ||
-                    hipMemset(e->d_arrive, 0, 4096 * sizeof(unsigned)) != hipSuccess) return fail(PNP_ERR_NOMEM, "split-K counters");
+            if (e->tune.splitk_inlaunch) {                 // one counter per output tile of a split-K launch
+                if (hipMalloc((void**)&e->d_arrive, kSplitKCounters * sizeof(unsigned)) != hipSuccess ||
+                    hipMemset(e->d_arrive, 0, kSplitKCounters * sizeof(unsigned)) != hipSuccess) return fail(PNP_ERR_NOMEM, "split-K counters");
             }
         }
         // which stage outputs get a pooled copy: the producing conv (layers 2, 5, 8, 11) must run a kernel whose epilogue
@@ -657,7 +671,7 @@ static int create_impl(const pnp_config* cfg, pnp_engine* e) {
     if (hipMalloc((void**)&e->d_ssim_part, sbytes) != hipSuccess) return fail(PNP_ERR_NOMEM, "SSIM partial sums");
     e->ws_bytes += sbytes;
     // pnp_residuals: its own partial sums (the SSIM buffer holds one double per 32 x 32 tile - fewer than five per 2048 pixels on small slices)
-    const size_t rbytes = N * (size_t)residual_chunks(cfg->h, cfg->w) * 5 * sizeof(double);
+    const size_t rbytes = N * (size_t)pixel_chunks(cfg->h, cfg->w) * 5 * sizeof(double);
     if (hipMalloc((void**)&e->d_res_part, rbytes) != hipSuccess) return fail(PNP_ERR_NOMEM, "residual partial sums");
     e->ws_bytes += rbytes;
     if (e->tune.fft_xcd && admm_xcd_usable(cfg->n, cfg->h, cfg->w)) {
@@ -792,15 +806,14 @@ int pnp_reset(pnp_handle e, const float* x0, const float* y0, const uint8_t* mas
     PNP_API_BEGIN
     if (!e || !x0 || !y0 || !mask || !x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_reset: null argument");
     if (mask_n != 1 && mask_n != e->cfg.n) return fail(PNP_ERR_INVALID, "pnp_reset: mask_n must be 1 or n=%d", e->cfg.n);
-    if (!kspace_len_ok(e->cfg.h) || !kspace_len_ok(e->cfg.w))
-        return fail(PNP_ERR_INVALID, "pnp_reset: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", e->cfg.h, e->cfg.w);
+    if (int rc = check_kspace_sizes("pnp_reset", e)) return rc;
     PNP_ON_DEVICE(e);
     e->mask_n = mask_n;
     e->mc_coils = 0;                                       // back to the single-coil stage
     // the two experimental in-launch hand-over schemes keep counters between launches (PNP_SPLITK_INLAUNCH: arrival counters that return to zero;
     // PNP_FFT_XCD: ticket / completion counters read against a launch epoch): a launch that faulted half way would leave them out of step for good,
     // so an episode starts from zero
-    if (e->d_arrive) HIP_TRY(hipMemsetAsync(e->d_arrive, 0, 4096 * sizeof(unsigned), (hipStream_t)stream));
+    if (e->d_arrive) HIP_TRY(hipMemsetAsync(e->d_arrive, 0, kSplitKCounters * sizeof(unsigned), (hipStream_t)stream));
     if (e->d_fftq) { HIP_TRY(hipMemsetAsync(e->d_fftq, 0, admm_xcd_counter_bytes(), (hipStream_t)stream)); e->fftq_epoch = 0; }
     HIP_TRY(launch_reset((const float2*)x0, (const float2*)y0, mask, mask_n, x, (float2*)z, (float2*)u, e->d_y0s,
                          e->d_masks, e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
@@ -813,8 +826,7 @@ int pnp_set_kspace(pnp_handle e, const float* y0, const uint8_t* mask, int mask_
     PNP_API_BEGIN
     if (!e || !y0 || !mask) return fail(PNP_ERR_INVALID, "pnp_set_kspace: null argument");
     if (mask_n != 1 && mask_n != e->cfg.n) return fail(PNP_ERR_INVALID, "pnp_set_kspace: mask_n must be 1 or n=%d", e->cfg.n);
-    if (!kspace_len_ok(e->cfg.h) || !kspace_len_ok(e->cfg.w))
-        return fail(PNP_ERR_INVALID, "pnp_set_kspace: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", e->cfg.h, e->cfg.w);
+    if (int rc = check_kspace_sizes("pnp_set_kspace", e)) return rc;
     PNP_ON_DEVICE(e);
     e->mask_n = mask_n;
     e->mc_coils = 0;                                       // back to the single-coil stage
@@ -837,7 +849,7 @@ int pnp_step(pnp_handle e, const float* mu, const float* sigma_d, const float* t
     if ((rc = run_unet(e, nullptr, (const float2*)z, (const float2*)u, sigma_d, t_action, x, s))) return rc;
     if ((rc = run_prox_dual(e, mu, t_action, x, (float2*)z, (float2*)u, s))) return rc;
     if (t_state || done) {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_finish(t_action, t_state, done, e->cfg.n, s));
     }
     return PNP_OK;
@@ -859,28 +871,18 @@ int pnp_fft2c(pnp_handle e, const float* in, float* out, int batch, int hh, int 
     if (hh != e->cfg.h || ww != e->cfg.w || batch < 1 || batch > e->cfg.n)
         return fail(PNP_ERR_INVALID, "pnp_fft2c: shape [%d,%d,%d] does not fit the engine [%d,%d,%d]", batch, hh, ww,
                     e->cfg.n, e->cfg.h, e->cfg.w);
-    if (!kspace_len_ok(hh) || !kspace_len_ok(ww))
-        return fail(PNP_ERR_INVALID, "pnp_fft2c: h, w must be in {" PNP_KSPACE_SIZES "} (got %dx%d)", hh, ww);
+    if (int rc = check_kspace_sizes("pnp_fft2c", e, "h, w must be in")) return rc;   // (hh, ww are the handle's)
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
-    if (!is_pow2(hh) || !is_pow2(ww)) {                   // a side of 2^a * 5^b: the mixed-radix passes, shifts as add-mod by L/2
-        {
-            Prof p(e, s, 3, -1);
-            HIP_TRY(launch_fft_rows_mixed((const float2*)in, (float2*)out, e->plan.tw_w, batch, hh, ww, inverse, ww / 2, s));
-        }
-        Prof p(e, s, 4, -1);
-        HIP_TRY(launch_fft_cols_mixed((float2*)out, e->plan.tw_h, batch, hh, ww, inverse, hh / 2, s));
-        return PNP_OK;
-    }
-    // fft_c = S . FFT . S : fold both shifts into the load/store indices of the two passes
+    // fft_c = S . FFT . S : fold both shifts into the load/store indices of the two passes (add-mod by L/2); rows then columns in BOTH
+    // directions, unlike the plain transform
     {
-        Prof p(e, s, 3, -1);
-        HIP_TRY(launch_fft_rows_generic((const float2*)in, (float2*)out, e->plan.tw_w, batch, hh, ww, inverse, ww / 2,
-                                        ww / 2, s));
+        Prof p(e, s, PROF_FFT_ROWS, -1);
+        HIP_TRY(launch_fft_rows((const float2*)in, (float2*)out, e->plan.tw_w, batch, hh, ww, inverse, ww / 2, s));
     }
     {
-        Prof p(e, s, 4, -1);
-        HIP_TRY(launch_fft_cols_generic((float2*)out, e->plan.tw_h, batch, hh, ww, inverse, hh / 2, hh / 2, s));
+        Prof p(e, s, PROF_FFT_COLS, -1);
+        HIP_TRY(launch_fft_cols((float2*)out, e->plan.tw_h, batch, hh, ww, inverse, hh / 2, s));
     }
     return PNP_OK;
     PNP_API_END("pnp_fft2c")
@@ -900,7 +902,7 @@ int pnp_psnr(pnp_handle e, const float* x, const float* gt, float* out, void* st
     PNP_API_BEGIN
     if (!e || !x || !gt || !out) return fail(PNP_ERR_INVALID, "pnp_psnr: null argument");
     PNP_ON_DEVICE(e);
-    Prof p(e, (hipStream_t)stream, 5, -1);
+    Prof p(e, (hipStream_t)stream, PROF_OTHER, -1);
     HIP_TRY(launch_psnr(x, gt, out, e->cfg.n, e->cfg.h * e->cfg.w, (hipStream_t)stream));
     return PNP_OK;
     PNP_API_END("pnp_psnr")
@@ -925,7 +927,7 @@ int pnp_ssim(pnp_handle e, const float* x, const float* gt, float data_range, fl
     double tap[2 * kSsimMaxRadius + 1], sum = 0.0;
     for (int i = -radius; i <= radius; ++i) sum += (tap[i + radius] = std::exp(-0.5 / (1.5 * 1.5) * (double)i * (double)i));
     for (int i = 0; i <= 2 * radius; ++i) a.w[i] = (float)(tap[i] / sum);
-    Prof p(e, (hipStream_t)stream, 5, -1);
+    Prof p(e, (hipStream_t)stream, PROF_OTHER, -1);
     HIP_TRY(launch_ssim(a, e->cfg.n, (hipStream_t)stream));
     return PNP_OK;
     PNP_API_END("pnp_ssim")
@@ -948,49 +950,37 @@ int pnp_residuals(pnp_handle e, const float* x, const float* z, const float* u, 
         if ((reinterpret_cast<uintptr_t>(a.p) & 15u) != 0) return fail(PNP_ERR_INVALID, "pnp_residuals: %s must be 16-byte aligned", a.name);
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
     if (flags & PNP_RES_DC) {
-        if (!kspace_len_ok(H) || !kspace_len_ok(W))
-            return fail(PNP_ERR_INVALID, "pnp_residuals: PNP_RES_DC takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", H, W);
+        if (int rc = check_kspace_sizes("pnp_residuals", e, "PNP_RES_DC takes h, w in")) return rc;
         if (!e->reset_done) return fail(PNP_ERR_STATE, "pnp_residuals: PNP_RES_DC needs the episode's k-space constants (pnp_reset / pnp_set_kspace)");
     }
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
-    const size_t px = (size_t)N * H * W;
+    const SnapLayout snap(e);
     double* const part = e->d_res_part;
-    double* const dcpart = part + (size_t)N * residual_chunks(H, W) * 4;
+    double* const dcpart = part + (size_t)N * pixel_chunks(H, W) * 4;
     {
         const char* pv = static_cast<const char*>((flags & PNP_RES_DELTA) ? prev : nullptr);   // [x | z | u | t] as pnp_snapshot packs them
-        Prof p(e, s, 5, -1);
-        HIP_TRY(launch_residual_tiles(x, (const float2*)z, (const float2*)u, (const float*)pv, pv ? (const float2*)(pv + px * 4) : nullptr,
-                                      pv ? (const float2*)(pv + px * 12) : nullptr, part, N, H, W, s));
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_residual_tiles(x, (const float2*)z, (const float2*)u, (const float*)pv, pv ? (const float2*)(pv + snap.z_off()) : nullptr,
+                                      pv ? (const float2*)(pv + snap.u_off()) : nullptr, part, N, H, W, s));
     }
     if ((flags & PNP_RES_DC) && e->mc_coils > 0) {
         // multi-coil mode: the plain transforms of S_c x into the coil scratch, then sum_c ||M (FFT(S_c x) - ys_c)||^2
         int rc;
         {
-            Prof p(e, s, 5, -1);
+            Prof p(e, s, PROF_OTHER, -1);
             HIP_TRY(launch_sense_expand(nullptr, x, e->mc_sens, e->mc_sens_n, e->mc_coils, nullptr, e->mc_work, N, H, W, s));
         }
-        if ((rc = mc_fft2(e, e->mc_work, N * e->mc_coils, 0, s))) return rc;
-        Prof p(e, s, 5, -1);
+        if ((rc = plain_fft2(e, e->mc_work, e->mc_work, N * e->mc_coils, 0, s))) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_misfit(e->mc_work, e->mc_y, e->d_masks, e->mask_n, e->mc_coils, dcpart, N, H, W, s));
     } else if (flags & PNP_RES_DC) {
-        // the plain (unshifted) transform of x into the data-fidelity stage's scratch, by the passes pnp_fft2c would choose; the shifts
-        // of fft_c live in the stored constants (reset_kernel)
-        const bool mixed = !is_pow2(H) || !is_pow2(W);
-        {
-            Prof p(e, s, 3, -1);
-            if (mixed) HIP_TRY(launch_fft_rows_real_mixed(x, e->d_work, e->plan.tw_w, N, H, W, s));
-            else HIP_TRY(launch_fft_rows_real(x, e->d_work, e->plan.tw_w, N, H, W, s));
-        }
-        {
-            Prof p(e, s, 4, -1);
-            if (mixed) HIP_TRY(launch_fft_cols_mixed(e->d_work, e->plan.tw_h, N, H, W, 0, 0, s));
-            else HIP_TRY(launch_fft_cols_generic(e->d_work, e->plan.tw_h, N, H, W, 0, 0, 0, s));
-        }
-        Prof p(e, s, 5, -1);
+        // the plain transform of x into the data-fidelity stage's scratch; the shifts of fft_c live in the stored constants (reset_kernel)
+        if (int rc = plain_fft2(e, nullptr, e->d_work, N, 0, s, x)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_misfit_tiles(e->d_work, e->d_y0s, e->d_masks, e->mask_n, dcpart, N, H, W, s));
     }
-    Prof p(e, s, 5, -1);
+    Prof p(e, s, PROF_OTHER, -1);
     HIP_TRY(launch_residual_reduce(part, dcpart, (flags & PNP_RES_DELTA) ? 1 : 0, (flags & PNP_RES_DC) ? 1 : 0, out, N, H, W, s));
     return PNP_OK;
     PNP_API_END("pnp_residuals")
@@ -1008,41 +998,22 @@ int pnp_acquire(pnp_handle e, const float* gt, const uint8_t* mask, int mask_n, 
     if (!e) return fail(PNP_ERR_INVALID, "pnp_acquire: null handle");
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
     if (mask_n != 1 && mask_n != N) return fail(PNP_ERR_INVALID, "pnp_acquire: mask_n must be 1 or n=%d", N);
-    if (!kspace_len_ok(H) || !kspace_len_ok(W))
-        return fail(PNP_ERR_INVALID, "pnp_acquire: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", H, W);
+    if (int rc = check_kspace_sizes("pnp_acquire", e)) return rc;
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
-    const bool mixed = !is_pow2(H) || !is_pow2(W);
-    // the plain (unshifted) transform of gt into the data-fidelity stage's scratch, by the passes pnp_residuals' misfit uses; the shifts of
-    // fft_c live in the epilogue's indices and sign
+    int rc;
+    // the plain transform of gt into the data-fidelity stage's scratch, by the passes pnp_residuals' misfit uses; the shifts of fft_c live in
+    // the epilogue's indices and sign
+    if ((rc = plain_fft2(e, nullptr, e->d_work, N, 0, s, gt))) return rc;
     {
-        Prof p(e, s, 3, -1);
-        if (mixed) HIP_TRY(launch_fft_rows_real_mixed(gt, e->d_work, e->plan.tw_w, N, H, W, s));
-        else HIP_TRY(launch_fft_rows_real(gt, e->d_work, e->plan.tw_w, N, H, W, s));
-    }
-    {
-        Prof p(e, s, 4, -1);
-        if (mixed) HIP_TRY(launch_fft_cols_mixed(e->d_work, e->plan.tw_h, N, H, W, 0, 0, s));
-        else HIP_TRY(launch_fft_cols_generic(e->d_work, e->plan.tw_h, N, H, W, 0, 0, 0, s));
-    }
-    {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_acquire_epilogue(e->d_work, mask, mask_n, (float2*)y0, sigma_n, seed, N, H, W, s));
     }
     if (!aty0 && !x0) return PNP_OK;
-    {
-        Prof p(e, s, 4, -1);
-        if (mixed) HIP_TRY(launch_fft_cols_mixed(e->d_work, e->plan.tw_h, N, H, W, 1, 0, s));
-        else HIP_TRY(launch_fft_cols_generic(e->d_work, e->plan.tw_h, N, H, W, 1, 0, 0, s));
-    }
     float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the row pass runs in place: a workgroup reads and writes its own rows only
-    {
-        Prof p(e, s, 3, -1);
-        if (mixed) HIP_TRY(launch_fft_rows_mixed(e->d_work, a, e->plan.tw_w, N, H, W, 1, 0, s));
-        else HIP_TRY(launch_fft_rows_generic(e->d_work, a, e->plan.tw_w, N, H, W, 1, 0, 0, s));
-    }
+    if ((rc = plain_fft2(e, e->d_work, a, N, 1, s))) return rc;
     if (x0) {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
     }
     return PNP_OK;
@@ -1079,7 +1050,7 @@ int pnp_reset_mc(pnp_handle e, const float* x0, const float* y0, const float* se
     if (!e) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null handle");
     if (int rc = mc_check("pnp_reset_mc", e, coils, sens_n, mask_n)) return rc;
     PNP_ON_DEVICE(e);
-    if (e->d_arrive) HIP_TRY(hipMemsetAsync(e->d_arrive, 0, 4096 * sizeof(unsigned), (hipStream_t)stream));   // as pnp_reset: an episode starts from zero
+    if (e->d_arrive) HIP_TRY(hipMemsetAsync(e->d_arrive, 0, kSplitKCounters * sizeof(unsigned), (hipStream_t)stream));   // as pnp_reset: an episode starts from zero
     return mc_install(e, (const float2*)x0, (const float2*)y0, (const float2*)sens, coils, sens_n, mask, mask_n, cg_iters, x, (float2*)z,
                       (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_mc")
@@ -1092,7 +1063,7 @@ int pnp_mc_cg_residual(pnp_handle e, float* out, void* stream) {
     if (!e || !out) return fail(PNP_ERR_INVALID, "pnp_mc_cg_residual: null argument");
     if (e->mc_coils == 0) return fail(PNP_ERR_STATE, "pnp_mc_cg_residual: the handle is in single-coil mode (pnp_set_kspace_mc / pnp_reset_mc)");
     PNP_ON_DEVICE(e);
-    Prof p(e, (hipStream_t)stream, 5, -1);
+    Prof p(e, (hipStream_t)stream, PROF_OTHER, -1);
     HIP_TRY(launch_sense_cgres(e->mc_sc, out, e->cfg.n, (hipStream_t)stream));
     return PNP_OK;
     PNP_API_END("pnp_mc_cg_residual")
@@ -1128,23 +1099,23 @@ int pnp_acquire_mc(pnp_handle e, const float* gt, const float* sens, int coils, 
     if ((rc = mc_ensure(e, 0, (size_t)N * coils * H * W, 0))) return rc;
     // the plain transforms of S_c gt in the coil scratch, by pnp_acquire's passes; the shifts of fft_c live in the epilogue's indices and sign
     {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_expand(nullptr, gt, (const float2*)sens, sens_n, coils, nullptr, e->mc_work, N, H, W, s));
     }
-    if ((rc = mc_fft2(e, e->mc_work, N * coils, 0, s))) return rc;
+    if ((rc = plain_fft2(e, e->mc_work, e->mc_work, N * coils, 0, s))) return rc;
     {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_acquire_epilogue(e->mc_work, mask, mask_n, (float2*)y0, sigma_n, seed, N, H, W, s, coils));
     }
     if (!aty0 && !x0) return PNP_OK;
-    if ((rc = mc_fft2(e, e->mc_work, N * coils, 1, s))) return rc;
+    if ((rc = plain_fft2(e, e->mc_work, e->mc_work, N * coils, 1, s))) return rc;
     float2* const a = aty0 ? (float2*)aty0 : mc_q(e);       // without aty0 the coil sum goes to a CG vector (dead between steps)
     {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_combine(e->mc_work, (const float2*)sens, sens_n, coils, nullptr, nullptr, nullptr, a, nullptr, N, H, W, s));
     }
     if (x0) {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
     }
     return PNP_OK;
@@ -1169,22 +1140,21 @@ int pnp_estimate_sens(pnp_handle e, const float* y0, int coils, int acs_h, int a
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
     if (acs_h > H) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: acs_h must be <= h=%d (got %d)", H, acs_h);
     if (acs_w > W) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: acs_w must be <= w=%d (got %d)", W, acs_w);
-    if (!kspace_len_ok(H) || !kspace_len_ok(W))
-        return fail(PNP_ERR_INVALID, "pnp_estimate_sens: the k-space stage takes h, w in {" PNP_KSPACE_SIZES "} (got %dx%d)", H, W);
+    if (int rc = check_kspace_sizes("pnp_estimate_sens", e)) return rc;
     if ((long long)N * coils > 65535) return fail(PNP_ERR_INVALID, "pnp_estimate_sens: n * coils must be <= 65535 (got %d * %d)", N, coils);
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if ((rc = cm_ensure(e, rss == nullptr))) return rc;
     float* const r = rss ? rss : e->cm_rss;
-    float* const smax = e->cm_max + (size_t)N * coilmap_chunks(H, W);
+    float* const smax = e->cm_max + (size_t)N * pixel_chunks(H, W);
     {
-        Prof p(e, s, 5, -1);
+        Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_coilmap_window((const float2*)y0, (float2*)sens, acs_h, acs_w, window == PNP_SENS_HANN, N, coils, H, W, s));
     }
     // l_c = the plain inverse transform of the windowed, sign-folded block, in place in the caller's buffer
-    if ((rc = mc_fft2(e, (float2*)sens, N * coils, 1, s))) return rc;
-    Prof p(e, s, 5, -1);
+    if ((rc = plain_fft2(e, (float2*)sens, (float2*)sens, N * coils, 1, s))) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
     HIP_TRY(launch_coilmap_rss((const float2*)sens, coils, r, e->cm_max, N, H, W, s));
     HIP_TRY(launch_coilmap_max(e->cm_max, smax, N, H, W, s));
     HIP_TRY(launch_coilmap_normalise((float2*)sens, coils, r, smax, (float)thresh, N, H, W, s));
@@ -1194,9 +1164,7 @@ int pnp_estimate_sens(pnp_handle e, const float* y0, int coils, int acs_h, int a
 }
 
 size_t pnp_snapshot_bytes(pnp_handle e) {
-    if (!e) return 0;
-    const size_t px = (size_t)e->cfg.n * e->cfg.h * e->cfg.w;
-    return px * (4 + 8 + 8) + (size_t)e->cfg.n * 4;
+    return e ? SnapLayout(e).bytes() : 0;
 }
 
 int pnp_snapshot(pnp_handle e, const float* x, const float* z, const float* u, const float* t_state, void* dst,
@@ -1204,14 +1172,14 @@ int pnp_snapshot(pnp_handle e, const float* x, const float* z, const float* u, c
     PNP_API_BEGIN
     if (!e || !x || !z || !u || !dst) return fail(PNP_ERR_INVALID, "pnp_snapshot: null argument");
     PNP_ON_DEVICE(e);
-    const size_t px = (size_t)e->cfg.n * e->cfg.h * e->cfg.w;
+    const SnapLayout snap(e);
     char* d = static_cast<char*>(dst);
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(d, x, px * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + px * 4, z, px * 8, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + px * 12, u, px * 8, hipMemcpyDeviceToDevice, s));
-    if (t_state) HIP_TRY(hipMemcpyAsync(d + px * 20, t_state, (size_t)e->cfg.n * 4, hipMemcpyDeviceToDevice, s));
-    else HIP_TRY(hipMemsetAsync(d + px * 20, 0, (size_t)e->cfg.n * 4, s));
+    HIP_TRY(hipMemcpyAsync(d, x, snap.x_bytes(), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + snap.z_off(), z, snap.zu_bytes(), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + snap.u_off(), u, snap.zu_bytes(), hipMemcpyDeviceToDevice, s));
+    if (t_state) HIP_TRY(hipMemcpyAsync(d + snap.t_off(), t_state, snap.t_bytes(), hipMemcpyDeviceToDevice, s));
+    else HIP_TRY(hipMemsetAsync(d + snap.t_off(), 0, snap.t_bytes(), s));
     return PNP_OK;
     PNP_API_END("pnp_snapshot")
 }
@@ -1220,13 +1188,13 @@ int pnp_restore(pnp_handle e, const void* src, float* x, float* z, float* u, flo
     PNP_API_BEGIN
     if (!e || !x || !z || !u || !src) return fail(PNP_ERR_INVALID, "pnp_restore: null argument");
     PNP_ON_DEVICE(e);
-    const size_t px = (size_t)e->cfg.n * e->cfg.h * e->cfg.w;
+    const SnapLayout snap(e);
     const char* d = static_cast<const char*>(src);
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(x, d, px * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(z, d + px * 4, px * 8, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(u, d + px * 12, px * 8, hipMemcpyDeviceToDevice, s));
-    if (t_state) HIP_TRY(hipMemcpyAsync(t_state, d + px * 20, (size_t)e->cfg.n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(x, d, snap.x_bytes(), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(z, d + snap.z_off(), snap.zu_bytes(), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(u, d + snap.u_off(), snap.zu_bytes(), hipMemcpyDeviceToDevice, s));
+    if (t_state) HIP_TRY(hipMemcpyAsync(t_state, d + snap.t_off(), snap.t_bytes(), hipMemcpyDeviceToDevice, s));
     return PNP_OK;
     PNP_API_END("pnp_restore")
 }

@@ -155,29 +155,33 @@ struct FftPlan {
     float2* tw_w;
 };
 
-// generic centred-or-plain passes (pnp_fft2c)
-hipError_t launch_fft_rows_generic(const float2* in, float2* out, const float2* tw, int batch, int H, int W,
-                                   int inverse, int shift_in, int shift_out, hipStream_t s);
-hipError_t launch_fft_cols_generic(float2* data, const float2* tw, int batch, int H, int W, int inverse,
-                                   int shift_in, int shift_out, hipStream_t s);
-// ADMM passes
-hipError_t launch_fft_rows_fwd_admm(const float* x, const float2* u, float2* work, const float2* tw,
-                                    const float* tact, int N, int H, int W, hipStream_t s);
-hipError_t launch_fft_cols_prox(float2* work, const float2* tw, const float2* y0s, const uint8_t* masks,
-                                int mask_n, const float* mu, const float* tact, int N, int H, int W, hipStream_t s);
-hipError_t launch_fft_rows_inv_admm(const float2* work, const float* x, float2* z, float2* u, const float2* tw,
-                                    const float* tact, int N, int H, int W, hipStream_t s);
-// sides of 2^a * 5^b (fft_mixed_kernels.hip): the same passes for a handle with a side that is not a power of two
 bool kspace_len_ok(int L);   // 16 <= L <= 1024, 16 | L, L = 2^a * 5^b
-hipError_t launch_fft_rows_mixed(const float2* in, float2* out, const float2* tw, int batch, int H, int W, int inverse, int shift,
-                                 hipStream_t s);
-hipError_t launch_fft_cols_mixed(float2* data, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s);
-hipError_t launch_fft_rows_fwd_mixed(const float* x, const float2* u, float2* work, const float2* tw, const float* tact, int N, int H,
-                                     int W, hipStream_t s);
-hipError_t launch_fft_cols_prox_mixed(float2* work, const float2* tw, const float2* y0s, const uint8_t* masks, int mask_n,
-                                      const float* mu, const float* tact, int N, int H, int W, hipStream_t s);
-hipError_t launch_fft_rows_inv_mixed(const float2* work, const float* x, float2* z, float2* u, const float2* tw, const float* tact,
-                                     int N, int H, int W, hipStream_t s);
+// The six k-space passes.  Each picks its kernel family itself: the power-of-two kernels (fft_kernels.hip), or the mixed-radix ones
+// (fft_mixed_kernels.hip) for a handle with a side that is not a power of two - one rule, stated in fft_kernels.hip (mixed_radix).
+// generic passes, in place or not; shift: the index shift on load and on store (0: the plain transform, L / 2: the centred one of pnp_fft2c)
+hipError_t launch_fft_rows(const float2* in, float2* out, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s);
+hipError_t launch_fft_cols(float2* data, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s);
+// row pass of a REAL image into complex scratch, no index shift (the first half of the plain transform of an image)
+hipError_t launch_fft_rows_real(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s);
+// ADMM passes
+hipError_t launch_fft_rows_fwd_admm(const float* x, const float2* u, float2* work, const float2* tw, const float* tact, int N, int H, int W,
+                                    hipStream_t s);
+hipError_t launch_fft_cols_prox(float2* work, const float2* tw, const float2* y0s, const uint8_t* masks, int mask_n, const float* mu,
+                                const float* tact, int N, int H, int W, hipStream_t s);
+hipError_t launch_fft_rows_inv_admm(const float2* work, const float* x, float2* z, float2* u, const float2* tw, const float* tact, int N,
+                                    int H, int W, hipStream_t s);
+// the mixed-radix family behind them (fft_mixed_kernels.hip), same arguments: for the dispatch only
+namespace mixed {
+hipError_t launch_fft_rows(const float2* in, float2* out, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s);
+hipError_t launch_fft_cols(float2* data, const float2* tw, int batch, int H, int W, int inverse, int shift, hipStream_t s);
+hipError_t launch_fft_rows_real(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s);
+hipError_t launch_fft_rows_fwd_admm(const float* x, const float2* u, float2* work, const float2* tw, const float* tact, int N, int H, int W,
+                                    hipStream_t s);
+hipError_t launch_fft_cols_prox(float2* work, const float2* tw, const float2* y0s, const uint8_t* masks, int mask_n, const float* mu,
+                                const float* tact, int N, int H, int W, hipStream_t s);
+hipError_t launch_fft_rows_inv_admm(const float2* work, const float* x, float2* z, float2* u, const float2* tw, const float* tact, int N,
+                                    int H, int W, hipStream_t s);
+}  // namespace mixed
 
 // x0 / x / z / u may all be null: only the episode constants (y0s, masks) are rebuilt
 // 128 x 128 only: the whole stage (both transforms each way, the solve, the dual update) in one workgroup per slice
@@ -213,20 +217,15 @@ int ssim_tiles(int H, int W);
 hipError_t launch_ssim(const SsimArgs& a, int N, hipStream_t s);
 
 // ---- ADMM residuals (residual_kernels.hip) ---------------------------------------------------------
-static constexpr int kResChunk = 2048;   // contiguous pixels of one slice per workgroup of the tile kernels
-int residual_chunks(int H, int W);       // workgroups (= float64 partials per quantity) per slice
-// partial: [N, residual_chunks, 4] sums of |x - z|^2, |x - xp|^2, |z - zp|^2, |u - up|^2; xp == nullptr: only the first is formed (u, zp, up unread)
+// every partial buffer holds one entry per workgroup of pixel_chunks(H, W) (block_reduce.h) per slice
+// partial: [N, pixel_chunks, 4] sums of |x - z|^2, |x - xp|^2, |z - zp|^2, |u - up|^2; xp == nullptr: only the first is formed (u, zp, up unread)
 hipError_t launch_residual_tiles(const float* x, const float2* z, const float2* u, const float* xp, const float2* zp, const float2* up,
                                  double* partial, int N, int H, int W, hipStream_t s);
-// fx: the plain orthonormal transform of x (unshifted), y0s / masks: the episode constants as reset_kernel stores them; dcpartial: [N, residual_chunks]
+// fx: the plain orthonormal transform of x (unshifted), y0s / masks: the episode constants as reset_kernel stores them; dcpartial: [N, pixel_chunks]
 hipError_t launch_misfit_tiles(const float2* fx, const float2* y0s, const uint8_t* masks, int mask_n, double* dcpartial, int N, int H, int W,
                                hipStream_t s);
 hipError_t launch_residual_reduce(const double* partial, const double* dcpartial, int has_delta, int has_dc, float* out, int N, int H, int W,
                                   hipStream_t s);
-// row pass of a REAL image into complex scratch, no index shift (the first half of the plain transform the misfit reads): fft_kernels.hip for
-// power-of-two handles (a new instantiation, MODE 3, of the row kernel), fft_mixed_kernels.hip otherwise (a kernel of its own)
-hipError_t launch_fft_rows_real(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s);
-hipError_t launch_fft_rows_real_mixed(const float* x, float2* work, const float2* tw, int N, int H, int W, hipStream_t s);
 
 // ---- simulated acquisition (acquire_kernels.hip) ---------------------------------------------------
 // work: the plain orthonormal transform of gt (unshifted); mask, y0: centred layout.  Stores y0 and leaves sgn * S y0 in work (reset_kernel's y0s
@@ -239,8 +238,6 @@ hipError_t launch_acquire_clamp(const float2* aty0, float2* x0, int N, int H, in
 // ---- multi-coil (SENSE) data fidelity (sense_kernels.hip) -------------------------------------------
 // Pointwise kernels around the plain FFT passes at batch N * C; work / ys: [N, C, H, W] complex, sens: [sens_n, C, H, W], masks: the rolled
 // layout reset_kernel stores.  tact (or nullptr): slices with tact[n] > 0.5 are skipped.
-static constexpr int kSenseChunk = 2048;   // contiguous pixels of one slice per workgroup
-int sense_chunks(int H, int W);            // workgroups (= float64 partial pairs) per slice
 hipError_t launch_sense_expand(const float2* src, const float* src_real, const float2* sens, int sens_n, int C, const float* tact, float2* work,
                                int N, int H, int W, hipStream_t s);                    // work = S_c . src (src_real != nullptr: a real image)
 hipError_t launch_sense_mask(float2* work, const uint8_t* masks, int mask_n, int C, int N, int H, int W, hipStream_t s);
@@ -264,8 +261,6 @@ hipError_t launch_sense_iterate(const float2* x0, float* x, float2* z, float2* u
 
 // ---- coil sensitivity maps from the calibration block (coilmap_kernels.hip) -------------------------
 // Pointwise kernels around the plain inverse FFT passes at batch N * C, in place in the caller's map buffer sens: [N, C, H, W] complex.
-static constexpr int kCoilmapChunk = 2048;   // contiguous pixels of one plane per workgroup
-int coilmap_chunks(int H, int W);            // workgroups (= float32 partial maxima) per slice
 // sens[n, c][k] = in block(S k) ? sgn[k] * win * y[n, c][S k] : 0 (plain bin k; y: centred layout, read inside the acs_h x acs_w block only)
 hipError_t launch_coilmap_window(const float2* y, float2* sens, int acs_h, int acs_w, int hann, int N, int C, int H, int W, hipStream_t s);
 // rss: [N, H, W] = sqrt(sum_c |l_c|^2) (float64 sum in coil order, one rounding); partial: [N, chunks] maxima of rss

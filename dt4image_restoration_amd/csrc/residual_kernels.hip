@@ -2,7 +2,7 @@
 //   primal = ||x - z||,  dx = ||x - x_p||,  dz = ||z - z_p||,  du = ||u - u_p||,  delta = (dx + dz + du) / sqrt(H W)
 // (the fixed-point stopping quantity of Chan, Wang, Elgendy 2017), and the k-space data misfit  dc = ||where(mask, fft_c(x) - y0, 0)||.
 //
-// residual_tile_kernel<DELTA>: one workgroup (256 threads) per kResChunk contiguous pixels of ONE slice - the range a workgroup owns
+// residual_tile_kernel<DELTA>: one workgroup (256 threads) per kPixelChunk contiguous pixels of ONE slice - the range a workgroup owns
 // depends on the slice's size only, never on the batch, so a slice gives the same bits wherever it sits in a handle.  A thread reads
 // four pixels at a time with 16-byte loads (x: one float4; z, u: two each; the same again from the previous planes when DELTA), forms every
 // difference in float32 (one rounding), squares and accumulates it in float64, and the workgroup reduces by wave shuffles, then through
@@ -14,35 +14,15 @@
 // writes the six float32 columns; columns that were not asked for are written as 0.
 // No atomics anywhere: the result is bitwise reproducible.  40 B per pixel for the delta pass (12 without `prev`), 17 for the misfit pass.
 #include "pnp_internal.h"
+#include "block_reduce.h"
 
 namespace pnp {
 
 namespace {
 
 constexpr int kResThreads = 256;
-constexpr int kResIters = kResChunk / (4 * kResThreads);   // four-pixel groups per thread
-static_assert(kResChunk % (4 * kResThreads) == 0, "whole batches of four-pixel groups");
-
-// fixed-order tree: the same sum bit for bit on every call.  `red` holds Q * (kResThreads / 64) doubles; thread 0 returns the totals in v[].
-template <int Q>
-__device__ __forceinline__ void block_sums_fixed(double (&v)[Q], double* red) {
-#pragma unroll
-    for (int q = 0; q < Q; ++q)
-        for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_down(v[q], o);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) red[q * (kResThreads / 64) + (threadIdx.x >> 6)] = v[q];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            double t = 0.0;
-            for (int i = 0; i < kResThreads / 64; ++i) t += red[q * (kResThreads / 64) + i];
-            v[q] = t;
-        }
-    }
-}
+constexpr int kResIters = kPixelChunk / (4 * kResThreads);   // four-pixel groups per thread
+static_assert(kPixelChunk % (4 * kResThreads) == 0, "whole batches of four-pixel groups");
 
 __device__ __forceinline__ double sq(float d) { return (double)d * (double)d; }
 // |a - b|^2 of two complex pairs held in one float4 (re0, im0, re1, im1): four float32 differences, squared and summed in float64
@@ -58,7 +38,7 @@ __global__ __launch_bounds__(kResThreads) void residual_tile_kernel(const float*
     __shared__ double red[4 * (kResThreads / 64)];
     const int n = blockIdx.y;
     const size_t base = (size_t)n * HW;
-    const int p0 = blockIdx.x * kResChunk;
+    const int p0 = blockIdx.x * kPixelChunk;
     float4 vx[kResIters], vz[kResIters][2], vu[kResIters][2], wx[kResIters], wz[kResIters][2], wu[kResIters][2];
     bool on[kResIters];
     // every load of the workgroup's range is issued before the first use (HW is a multiple of 4: a group of four pixels is in or out whole)
@@ -95,7 +75,7 @@ __global__ __launch_bounds__(kResThreads) void residual_tile_kernel(const float*
             acc[3] += diff2(vu[it][0], wu[it][0]) + diff2(vu[it][1], wu[it][1]);
         }
     }
-    block_sums_fixed<4>(acc, red);
+    block_sums_fixed<kResThreads, 4>(acc, red);
     if (threadIdx.x == 0) {
         double* o = partial + ((size_t)n * gridDim.x + blockIdx.x) * 4;
         o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2]; o[3] = acc[3];
@@ -108,7 +88,7 @@ __global__ __launch_bounds__(kResThreads) void misfit_tile_kernel(const float2* 
     __shared__ double red[kResThreads / 64];
     const int n = blockIdx.y;
     const size_t base = (size_t)n * HW, mbase = mask_n > 1 ? base : 0;
-    const int p0 = blockIdx.x * kResChunk;
+    const int p0 = blockIdx.x * kPixelChunk;
     float4 a[kResIters][2], b[kResIters][2];
     unsigned m[kResIters];
     bool on[kResIters];
@@ -134,7 +114,7 @@ __global__ __launch_bounds__(kResThreads) void misfit_tile_kernel(const float2* 
         if (m[it] & 0x00ff0000u) acc[0] += sq(a[it][1].x - b[it][1].x) + sq(a[it][1].y - b[it][1].y);
         if (m[it] & 0xff000000u) acc[0] += sq(a[it][1].z - b[it][1].z) + sq(a[it][1].w - b[it][1].w);
     }
-    block_sums_fixed<1>(acc, red);
+    block_sums_fixed<kResThreads, 1>(acc, red);
     if (threadIdx.x == 0) partial[(size_t)n * gridDim.x + blockIdx.x] = acc[0];
 }
 
@@ -150,7 +130,7 @@ __global__ __launch_bounds__(kResThreads) void residual_reduce_kernel(const doub
         if (has_delta) { acc[1] += p[1]; acc[2] += p[2]; acc[3] += p[3]; }
         if (has_dc) acc[4] += dcpartial[(size_t)n * chunks + i];
     }
-    block_sums_fixed<5>(acc, red);
+    block_sums_fixed<kResThreads, 5>(acc, red);
     if (threadIdx.x == 0) {
         const double dx = sqrt(acc[1]), dz = sqrt(acc[2]), du = sqrt(acc[3]);
         float* o = out + (size_t)n * 6;
@@ -163,11 +143,9 @@ __global__ __launch_bounds__(kResThreads) void residual_reduce_kernel(const doub
 
 }  // namespace
 
-int residual_chunks(int H, int W) { return (H * W + kResChunk - 1) / kResChunk; }
-
 hipError_t launch_residual_tiles(const float* x, const float2* z, const float2* u, const float* xp, const float2* zp, const float2* up,
                                  double* partial, int N, int H, int W, hipStream_t s) {
-    const dim3 grid(residual_chunks(H, W), N);
+    const dim3 grid(pixel_chunks(H, W), N);
     if (xp != nullptr) hipLaunchKernelGGL(residual_tile_kernel<true>, grid, dim3(kResThreads), 0, s, x, z, u, xp, zp, up, partial, H * W);
     else hipLaunchKernelGGL(residual_tile_kernel<false>, grid, dim3(kResThreads), 0, s, x, z, u, xp, zp, up, partial, H * W);
     return hipGetLastError();
@@ -175,13 +153,13 @@ hipError_t launch_residual_tiles(const float* x, const float2* z, const float2* 
 
 hipError_t launch_misfit_tiles(const float2* fx, const float2* y0s, const uint8_t* masks, int mask_n, double* dcpartial, int N, int H, int W,
                                hipStream_t s) {
-    hipLaunchKernelGGL(misfit_tile_kernel, dim3(residual_chunks(H, W), N), dim3(kResThreads), 0, s, fx, y0s, masks, mask_n, dcpartial, H * W);
+    hipLaunchKernelGGL(misfit_tile_kernel, dim3(pixel_chunks(H, W), N), dim3(kResThreads), 0, s, fx, y0s, masks, mask_n, dcpartial, H * W);
     return hipGetLastError();
 }
 
 hipError_t launch_residual_reduce(const double* partial, const double* dcpartial, int has_delta, int has_dc, float* out, int N, int H, int W,
                                   hipStream_t s) {
-    hipLaunchKernelGGL(residual_reduce_kernel, dim3(N), dim3(kResThreads), 0, s, partial, dcpartial, residual_chunks(H, W), has_delta, has_dc,
+    hipLaunchKernelGGL(residual_reduce_kernel, dim3(N), dim3(kResThreads), 0, s, partial, dcpartial, pixel_chunks(H, W), has_delta, has_dc,
                        1.0 / sqrt((double)H * (double)W), out);
     return hipGetLastError();
 }

@@ -9,41 +9,20 @@
 // One Nop in this (unfused) form:  sense_expand_kernel  p -> work[n, c] = S_c . p      | rows forward | cols forward |
 //                                  sense_mask_kernel    work = mask ? work : 0         | cols inverse | rows inverse |
 //                                  sense_combine_kernel q = sum_c conj(S_c) . work[n, c] + mu p,  partial sums of Re<p, q>
-// CG scalars: every inner product is per slice; its terms are float32 values multiplied and summed in float64 by ONE workgroup per kSenseChunk
+// CG scalars: every inner product is per slice; its terms are float32 values multiplied and summed in float64 by ONE workgroup per kPixelChunk
 // pixels of one slice (fixed tree: block_sums_fixed), then by sense_scalar_kernel over the slice's partials in a fixed order.  No atomics:
 // bitwise reproducible, and a slice's bits do not depend on N or on its place in the batch.  alpha / beta are float64 in device memory and
 // applied as float32.  Slices with t_action > 0.5 are skipped by every kernel that writes z, u, a CG vector or a scalar.
 #include "pnp_internal.h"
+#include "block_reduce.h"
 
 namespace pnp {
 
 namespace {
 
 constexpr int kSenseThreads = 256;
-constexpr int kSensePer = kSenseChunk / kSenseThreads;     // pixels per thread
-static_assert(kSenseChunk % kSenseThreads == 0, "whole pixels per thread");
-
-// fixed-order tree: the same sum bit for bit on every call (residual_kernels.hip's scheme).  `red` holds Q * (kSenseThreads / 64) doubles;
-// thread 0 returns the totals in v[].
-template <int Q>
-__device__ __forceinline__ void block_sums_fixed(double (&v)[Q], double* red) {
-#pragma unroll
-    for (int q = 0; q < Q; ++q)
-        for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_down(v[q], o);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) red[q * (kSenseThreads / 64) + (threadIdx.x >> 6)] = v[q];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            double t = 0.0;
-            for (int i = 0; i < kSenseThreads / 64; ++i) t += red[q * (kSenseThreads / 64) + i];
-            v[q] = t;
-        }
-    }
-}
+constexpr int kSensePer = kPixelChunk / kSenseThreads;     // pixels per thread
+static_assert(kPixelChunk % kSenseThreads == 0, "whole pixels per thread");
 
 __device__ __forceinline__ bool stopped(const float* tact, int n) { return tact != nullptr && tact[n] > 0.5f; }
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
@@ -55,7 +34,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_expand_kernel(const void*
                                                                      int C, const float* __restrict__ tact, float2* __restrict__ work, int HW) {
     const int n = blockIdx.y;
     if (stopped(tact, n)) return;
-    const int p0 = blockIdx.x * kSenseChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const size_t base = (size_t)n * HW;
     float2 v[kSensePer];
 #pragma unroll
@@ -84,7 +63,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_expand_kernel(const void*
 __global__ __launch_bounds__(kSenseThreads) void sense_mask_kernel(float2* __restrict__ work, const uint8_t* __restrict__ masks, int mask_n, int C,
                                                                    int HW) {
     const int nc = blockIdx.y, n = nc / C;
-    const int p0 = blockIdx.x * kSenseChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const uint8_t* mk = masks + (mask_n > 1 ? (size_t)n * HW : 0);
     float2* w = work + (size_t)nc * HW;
 #pragma unroll
@@ -102,7 +81,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_combine_kernel(const floa
     __shared__ double red[kSenseThreads / 64];
     const int n = blockIdx.y;
     if (stopped(tact, n)) return;
-    const int p0 = blockIdx.x * kSenseChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const size_t base = (size_t)n * HW;
     float2 acc[kSensePer];
     for (int c = 0; c < C; ++c) {
@@ -139,7 +118,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_combine_kernel(const floa
         }
     }
     if (partial == nullptr) return;                        // (uniform)
-    block_sums_fixed<1>(dot, red);
+    block_sums_fixed<kSenseThreads, 1>(dot, red);
     if (threadIdx.x == 0) partial[((size_t)n * gridDim.x + blockIdx.x) * 2] = dot[0];
 }
 
@@ -152,7 +131,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_cg_init_kernel(const floa
     __shared__ double red[2 * (kSenseThreads / 64)];
     const int n = blockIdx.y;
     if (stopped(tact, n)) return;
-    const int p0 = blockIdx.x * kSenseChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const size_t base = (size_t)n * HW;
     const float m = mu[n];
     double acc[2] = {0.0, 0.0};
@@ -171,7 +150,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_cg_init_kernel(const floa
             acc[1] += (double)b.x * (double)b.x + (double)b.y * (double)b.y;
         }
     }
-    block_sums_fixed<2>(acc, red);
+    block_sums_fixed<kSenseThreads, 2>(acc, red);
     if (threadIdx.x == 0) {
         double* o = partial + ((size_t)n * gridDim.x + blockIdx.x) * 2;
         o[0] = acc[0]; o[1] = acc[1];
@@ -193,7 +172,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_scalar_kernel(const doubl
         acc[0] += p[0];
         if (mode == 0) acc[1] += p[1];
     }
-    block_sums_fixed<2>(acc, red);
+    block_sums_fixed<kSenseThreads, 2>(acc, red);
     if (threadIdx.x != 0) return;
     double* s = sc + (size_t)n * 8;
     if (mode == 0) {
@@ -217,7 +196,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_cg_update_kernel(float2* 
     __shared__ double red[kSenseThreads / 64];
     const int n = blockIdx.y;
     if (stopped(tact, n)) return;
-    const int p0 = blockIdx.x * kSenseChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const size_t base = (size_t)n * HW;
     const float alpha = (float)sc[(size_t)n * 8 + 2];
     double acc[1] = {0.0};
@@ -235,7 +214,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_cg_update_kernel(float2* 
             acc[0] += (double)rr.x * (double)rr.x + (double)rr.y * (double)rr.y;
         }
     }
-    block_sums_fixed<1>(acc, red);
+    block_sums_fixed<kSenseThreads, 1>(acc, red);
     if (threadIdx.x == 0) partial[((size_t)n * gridDim.x + blockIdx.x) * 2] = acc[0];
 }
 
@@ -244,7 +223,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_cg_dir_kernel(const float
                                                                      const float* __restrict__ tact, int HW) {
     const int n = blockIdx.y;
     if (stopped(tact, n)) return;
-    const int p0 = blockIdx.x * kSenseChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const size_t base = (size_t)n * HW;
     const float beta = (float)sc[(size_t)n * 8 + 3];
 #pragma unroll
@@ -263,7 +242,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_dual_kernel(const float* 
                                                                    const float* __restrict__ tact, int HW) {
     const int n = blockIdx.y;
     if (stopped(tact, n)) return;
-    const int p0 = blockIdx.x * kSenseChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const size_t base = (size_t)n * HW;
 #pragma unroll
     for (int j = 0; j < kSensePer; ++j) {
@@ -289,7 +268,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_misfit_kernel(const float
                                                                      double* __restrict__ partial, int HW) {
     __shared__ double red[kSenseThreads / 64];
     const int n = blockIdx.y;
-    const int p0 = blockIdx.x * kSenseChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const uint8_t* mk = masks + (mask_n > 1 ? (size_t)n * HW : 0);
     uint8_t mm[kSensePer];
 #pragma unroll
@@ -310,7 +289,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_misfit_kernel(const float
             }
         }
     }
-    block_sums_fixed<1>(acc, red);
+    block_sums_fixed<kSenseThreads, 1>(acc, red);
     if (threadIdx.x == 0) partial[(size_t)n * gridDim.x + blockIdx.x] = acc[0];
 }
 
@@ -321,7 +300,7 @@ __global__ __launch_bounds__(kSenseThreads) void sense_install_kernel(const floa
                                                                       uint8_t* __restrict__ masks, int H, int W) {
     const int nc = blockIdx.y, n = nc / C, c = nc - n * C;
     const int HW = H * W, hh = H >> 1, hw = W >> 1;
-    const int p0 = blockIdx.x * kSenseChunk + threadIdx.x;
+    const int p0 = blockIdx.x * kPixelChunk + threadIdx.x;
     const size_t mb = mask_n > 1 ? (size_t)n * HW : 0;
     const bool store_mask = c == 0 && (mask_n > 1 || n == 0);
 #pragma unroll
@@ -351,11 +330,9 @@ __global__ __launch_bounds__(kSenseThreads) void sense_iterate_kernel(const floa
     }
 }
 
-inline dim3 tile_grid(int H, int W, int batch) { return dim3((unsigned)sense_chunks(H, W), (unsigned)batch); }
+inline dim3 tile_grid(int H, int W, int batch) { return dim3((unsigned)pixel_chunks(H, W), (unsigned)batch); }
 
 }  // namespace
-
-int sense_chunks(int H, int W) { return (H * W + kSenseChunk - 1) / kSenseChunk; }
 
 hipError_t launch_sense_expand(const float2* src, const float* src_real, const float2* sens, int sens_n, int C, const float* tact, float2* work,
                                int N, int H, int W, hipStream_t s) {
@@ -384,7 +361,7 @@ hipError_t launch_sense_cg_init(const float2* aty, const float* x, const float2*
 }
 
 hipError_t launch_sense_scalar(const double* partial, int mode, const float* tact, double* sc, int N, int H, int W, hipStream_t s) {
-    hipLaunchKernelGGL(sense_scalar_kernel, dim3(N), dim3(kSenseThreads), 0, s, partial, sense_chunks(H, W), mode, tact, sc);
+    hipLaunchKernelGGL(sense_scalar_kernel, dim3(N), dim3(kSenseThreads), 0, s, partial, pixel_chunks(H, W), mode, tact, sc);
     return hipGetLastError();
 }
 
