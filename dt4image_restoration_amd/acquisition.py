@@ -134,6 +134,71 @@ def estimate_sens(engine_or_env, y0, mask=None, acs=None, window: str = "hann", 
     return eng.estimate_sens(y.to(eng.device, torch.complex64).contiguous(), acs, window=window, thresh=thresh)
 
 
+def coils_for_energy(eig, energy: float) -> int:
+    """The virtual coils a batch keeps for an energy target: per slice the smallest V whose leading eigenvalues (eig [N,C], descending)
+    reach `energy` of their sum, and the largest of those over the slices.  A slice without energy counts 1."""
+    e = np.asarray(eig, dtype=np.float64)
+    if e.ndim != 2 or e.shape[1] < 1:
+        raise ValueError(f"eig: expected [N,C], got {e.shape}")
+    if not 0.0 < energy <= 1.0:
+        raise ValueError(f"energy must be in (0, 1], got {energy}")
+    total = e.sum(axis=1)
+    reached = np.cumsum(e, axis=1) >= energy * total[:, None]
+    v = np.where(reached.any(axis=1), reached.argmax(axis=1) + 1, e.shape[1])
+    return int(np.where(total > 0, v, 1).max())
+
+
+def compress_coils(engine_or_env, y0, mask=None, acs=None, out_coils=None, energy=None, sens=None) -> Dict[str, torch.Tensor]:
+    """Coil compression on the device (pnp_coil_compress_matrix, pnp_coil_compress_apply): the C channels of y0 mixed down to V virtual
+    coils by the leading eigenvectors of the calibration block's channel covariance, per slice.  y0: [N,C,H,W] complex, or [N,C,H,W,2]
+    real (array or tensor), centred layout, C <= 64.  acs = (acs_h, acs_w), or None for `acs_block(mask)`.  Exactly one of out_coils (V
+    itself, 1..min(C, 32)) and energy (in (0, 1]: `coils_for_energy` of the eigenvalues - each slice's smallest V that reaches this
+    share of the trace, the batch takes the largest; this costs ONE host read of the [N,C] eigenvalues at setup) must be given.  sens:
+    the coil maps, complex [C,H,W] (shared: broadcast to the batch first, since every slice has its own matrix) or [N,C,H,W], mixed by
+    the same matrices.  Returns a dict: y0 complex64 [N,V,H,W], cmat complex64 [N,C,C], eig float32 [N,C], out_coils, and sens
+    complex64 [N,V,H,W] when maps were given; every tensor on the GPU."""
+    if (out_coils is None) == (energy is None):
+        raise ValueError("compress_coils: give exactly one of out_coils and energy")
+    if energy is not None and not 0.0 < energy <= 1.0:
+        raise ValueError(f"compress_coils: energy must be in (0, 1], got {energy}")
+    y = torch.as_tensor(y0)
+    if not y.is_complex():
+        if y.dim() != 5 or y.shape[-1] != 2:
+            raise ValueError(f"y0: expected complex [N,C,H,W] or real [N,C,H,W,2], got {tuple(y.shape)}")
+        y = torch.view_as_complex(y.float().contiguous())
+    if y.dim() != 4:
+        raise ValueError(f"y0: expected [N,C,H,W], got {tuple(y.shape)}")
+    n, c, h, w = (int(v) for v in y.shape)
+    if out_coils is not None and not 1 <= int(out_coils) <= min(c, 32):
+        raise ValueError(f"compress_coils: out_coils must be 1..{min(c, 32)}, got {out_coils}")
+    if acs is None:
+        if mask is None:
+            raise ValueError("compress_coils: give acs=(acs_h, acs_w) or the sampling mask")
+        acs = acs_block(torch.as_tensor(mask).cpu().numpy())
+    s = None
+    if sens is not None:
+        s = torch.as_tensor(sens)
+        if not s.is_complex() or s.dim() not in (3, 4) or tuple(s.shape[-3:]) != (c, h, w) or (s.dim() == 4 and s.shape[0] != n):
+            raise ValueError(f"sens: expected complex [{c},{h},{w}] or [{n},{c},{h},{w}], got {tuple(s.shape)}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("compress_coils needs a ROCm GPU")
+    eng = engine_or_env if hasattr(engine_or_env, "coil_compress_matrix") else None
+    device = eng.device if eng is not None else torch.device("cuda", torch.cuda.current_device())
+    if eng is None:
+        eng = _engine(engine_or_env, n, h, w, device)
+    if (eng.n, eng.h, eng.w) != (n, h, w):
+        raise ValueError(f"y0 {tuple(y.shape)} does not fit the engine [{eng.n},{eng.h},{eng.w}]")
+    y = y.to(eng.device, torch.complex64).contiguous()
+    cmat, eig = eng.coil_compress_matrix(y, acs)
+    v = int(out_coils) if out_coils is not None else min(coils_for_energy(eig.cpu().numpy(), energy), 32)
+    out = {"y0": eng.coil_compress_apply(y, cmat, v), "cmat": cmat, "eig": eig, "out_coils": v}
+    if s is not None:
+        s = s.to(eng.device, torch.complex64)
+        s = (s[None].expand(n, c, h, w) if s.dim() == 3 else s).contiguous()
+        out["sens"] = eng.coil_compress_apply(s, cmat, v)
+    return out
+
+
 def _centre_block(w: int, center_fraction: float) -> np.ndarray:
     nc = int(round(w * center_fraction))
     lo = (w - nc) // 2

@@ -26,6 +26,14 @@ layout has none):
     ... --coils 4 --cg-iters 8 eval|flex|mcts|fixed ...
     ... --coils 4 --sens estimate [--sens-window hann|box] [--sens-thresh 0.05] [--acs H W] --mask cartesian fixed ...
 
+    ... --coils 16 --compress 8 [--sens true|estimate] [--acs H W] eval|flex|mcts|fixed ...
+
+`--compress V` mixes each set's C coils down to V virtual coils before the solver sees them (coil compression: the leading eigenvectors
+of the channel covariance of the calibration block, per slice, pnp_coil_compress_matrix / pnp_coil_compress_apply); every cost of the
+multi-coil stage is linear in the coils it is handed.  With `--sens true` the analytic maps are mixed by the same matrices; with
+`--sens estimate` the maps are estimated from the compressed k-space.  With --residuals each line carries `compress_energy`, the share of
+the block's energy the kept virtual coils hold (mean over the set).
+
 `--sens estimate` does not hand the solver the maps that generated the measurements: the maps are estimated on the device from the
 fully sampled centre of each set's own y0 (pnp_estimate_sens; the block is the largest one the set's mask samples completely, or
 --acs).  The initial iterate x0 stays the one the set brings.
@@ -81,8 +89,29 @@ def _tasks(args):
     return tasks
 
 
+def _compressed(args, env, batch):
+    """--compress V: the batch with its y0 (and, under --sens true, its maps) mixed down to V virtual coils on the device."""
+    if not args.compress:
+        return batch
+    from . import acquisition
+    batch = dict(batch)
+    try:
+        r = acquisition.compress_coils(env, batch["y0"], mask=batch["mask"], acs=args.acs, out_coils=args.compress,
+                                       sens=batch.get("sens") if args.sens == "true" else None)
+    except ValueError as e:                                    # a mask without a sampled centre, a block that does not fit
+        raise SystemExit(f"--compress: {e}")
+    batch["y0"] = torch.view_as_real(r["y0"])
+    if "sens" in r:
+        batch["sens"] = r["sens"]
+    if getattr(args, "residuals", False):                      # reporting only: one host read per set
+        eig = r["eig"].double()
+        args.compress_energy.append(float((eig[:, :args.compress].sum(dim=1) / eig.sum(dim=1).clamp_min(1e-300)).mean()))
+    return batch
+
+
 def _with_sens(args, env, batch):
-    """--sens estimate: the batch with its coil maps replaced by the estimate from its own y0 and mask (on the device)."""
+    """--compress, then --sens estimate: the batch with its coil maps replaced by the estimate from its own y0 and mask (on the device)."""
+    batch = _compressed(args, env, batch)
     if args.sens != "estimate":
         return batch
     from . import acquisition
@@ -201,7 +230,9 @@ def main(argv=None):
     ap.add_argument("--sens-window", choices=("hann", "box"), default="hann", help="window of the calibration block (--sens estimate)")
     ap.add_argument("--sens-thresh", type=float, default=0.05, help="--sens estimate: pixels whose root-sum-of-squares is not above this "
                     "fraction of the slice's largest get zero maps (in [0, 1))")
-    ap.add_argument("--acs", type=int, nargs=2, default=None, metavar=("H", "W"), help="--sens estimate: even sides of the centred "
+    ap.add_argument("--compress", type=int, default=0, metavar="V", help="coil compression of a --coils run: the solver gets the V "
+                    "strongest virtual coils of each set (1..--coils; default 0: no compression)")
+    ap.add_argument("--acs", type=int, nargs=2, default=None, metavar=("H", "W"), help="--sens estimate / --compress: even sides of the centred "
                     "calibration block (default: the largest block the mask samples completely)")
     ap.add_argument("--seed", type=int, default=0)
     sub = ap.add_subparsers(dest="mode", required=True)
@@ -236,6 +267,14 @@ def main(argv=None):
         raise SystemExit(f"--coils must be 1..32, got {args.coils}")
     if not 1 <= args.cg_iters <= 64:
         raise SystemExit(f"--cg-iters must be 1..64, got {args.cg_iters}")
+    args.compress_energy = []
+    if args.compress:
+        if not args.coils:
+            raise SystemExit("--compress needs --coils: there are no coils to compress on a single-coil problem")
+        if not 1 <= args.compress <= args.coils:
+            raise SystemExit(f"--compress must be 1..--coils = {args.coils}, got {args.compress}")
+        if args.acs is not None and any(v < 2 or v % 2 for v in args.acs):
+            raise SystemExit(f"--acs: sides must be even and >= 2, got {args.acs}")
     if args.sens == "estimate":
         if not args.coils:
             raise SystemExit("--sens estimate needs --coils: there are no coil maps to estimate on a single-coil problem")
@@ -303,6 +342,9 @@ def main(argv=None):
                         "ssim": float(r.ssim.mean()), "ssim_increment": float((r.ssim - r.initial_ssim).mean())})
             if args.residuals:
                 out[-1].update(primal=float(r.residuals[:, 0].mean()), dc=float(r.residuals[:, 5].mean()))
+                if args.compress_energy:
+                    out[-1]["compress_energy"] = float(np.mean(args.compress_energy))
+                    args.compress_energy.clear()
             if rank == 0:
                 print(json.dumps(out[-1]), flush=True)
         if dist is not None:
@@ -352,6 +394,9 @@ def main(argv=None):
                         "ssim": float(np.mean(ssims)), "ssim_increment": float(np.mean(ssim_incs))})
             if args.residuals:
                 out[-1].update(primal=float(np.mean(primals)), dc=float(np.mean(dcs)))
+                if args.compress_energy:
+                    out[-1]["compress_energy"] = float(np.mean(args.compress_energy))
+                    args.compress_energy.clear()
             if rank == 0:
                 print(json.dumps(out[-1]), flush=True)
         if dist is not None:

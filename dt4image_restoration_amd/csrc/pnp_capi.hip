@@ -126,6 +126,10 @@ struct pnp_engine {
     // coil map estimate (pnp_estimate_sens): allocated inside its first call
     float* cm_max = nullptr;     // [N, pixel_chunks] per-workgroup maxima of rss, then smax [N]
     float* cm_rss = nullptr;     // [N,H,W] rss for callers that pass none
+    // coil compression (pnp_coil_compress_matrix): allocated inside its first call, grown by a call that needs more
+    double2* cc_part = nullptr;  // [N, gram_chunks, C, C] per-workgroup Gram partials
+    double2* cc_gram = nullptr;  // [N, C, C] Gram for callers that pass none
+    size_t cc_part_cap = 0, cc_gram_cap = 0;   // capacities in complex128 elements
     // profiling
     std::vector<EventPair> events;
     size_t ev_used = 0;
@@ -499,6 +503,34 @@ int cm_ensure(pnp_engine* e, bool own_rss) {
     return PNP_OK;
 }
 
+// The workspace of pnp_coil_compress_matrix: `part_need` complex128 Gram partials and, for callers that pass no Gram, `gram_need` more.
+// All-or-nothing, as mc_ensure: every new buffer is allocated before an old one is released.
+int cc_ensure(pnp_engine* e, size_t part_need, size_t gram_need) {
+    void* fresh_part = nullptr;
+    void* fresh_gram = nullptr;
+    if (part_need > e->cc_part_cap && hipMalloc(&fresh_part, part_need * sizeof(double2)) != hipSuccess)
+        return fail(PNP_ERR_NOMEM, "coil compression workspace: %zu bytes (the handle keeps the workspace it had)", part_need * sizeof(double2));
+    if (gram_need > e->cc_gram_cap && hipMalloc(&fresh_gram, gram_need * sizeof(double2)) != hipSuccess) {
+        (void)hipFree(fresh_part);
+        return fail(PNP_ERR_NOMEM, "coil compression workspace: %zu bytes (the handle keeps the workspace it had)", gram_need * sizeof(double2));
+    }
+    if (!fresh_part && !fresh_gram) return PNP_OK;
+    if (e->cc_part || e->cc_gram) (void)hipDeviceSynchronize();   // no launch still reads a buffer being replaced
+    if (fresh_part) {
+        (void)hipFree(e->cc_part);
+        e->cc_part = (double2*)fresh_part;
+        e->ws_bytes += (part_need - e->cc_part_cap) * sizeof(double2);
+        e->cc_part_cap = part_need;
+    }
+    if (fresh_gram) {
+        (void)hipFree(e->cc_gram);
+        e->cc_gram = (double2*)fresh_gram;
+        e->ws_bytes += (gram_need - e->cc_gram_cap) * sizeof(double2);
+        e->cc_gram_cap = gram_need;
+    }
+    return PNP_OK;
+}
+
 int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                   hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
@@ -728,6 +760,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->d_work); (void)hipFree(e->d_fftq); (void)hipFree(e->d_y0s); (void)hipFree(e->d_masks); (void)hipFree(e->d_ssim_part); (void)hipFree(e->d_res_part); (void)hipFree(e->d_partial); (void)hipFree(e->d_arrive);
     (void)hipFree(e->mc_y); (void)hipFree(e->mc_work); (void)hipFree(e->mc_sens); (void)hipFree(e->mc_vec); (void)hipFree(e->mc_part); (void)hipFree(e->mc_sc);
     (void)hipFree(e->cm_max); (void)hipFree(e->cm_rss);
+    (void)hipFree(e->cc_part); (void)hipFree(e->cc_gram);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     delete e;
@@ -1161,6 +1194,62 @@ int pnp_estimate_sens(pnp_handle e, const float* y0, int coils, int acs_h, int a
     p.end(3);
     return PNP_OK;
     PNP_API_END("pnp_estimate_sens")
+}
+
+int pnp_coil_compress_matrix(pnp_handle e, const float* y0, int coils, int acs_h, int acs_w, int flags, float* cmat, float* eig, double* gram,
+                             void* stream) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call, and leaves the outputs untouched; scalar ranges first
+    const char* fn = "pnp_coil_compress_matrix";
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (coils < 1 || coils > PNP_CC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_CC_MAX_COILS, coils);
+    if (acs_h < 2 || (acs_h & 1)) return fail(PNP_ERR_INVALID, "%s: acs_h must be even and >= 2 (got %d)", fn, acs_h);
+    if (acs_w < 2 || (acs_w & 1)) return fail(PNP_ERR_INVALID, "%s: acs_w must be even and >= 2 (got %d)", fn, acs_w);
+    if (!y0) return fail(PNP_ERR_INVALID, "%s: null y0", fn);
+    if (!cmat) return fail(PNP_ERR_INVALID, "%s: null cmat", fn);
+    if (!eig) return fail(PNP_ERR_INVALID, "%s: null eig", fn);
+    if ((const void*)cmat == (const void*)y0 || (const void*)eig == (const void*)y0 || (const void*)gram == (const void*)y0 ||
+        (const void*)cmat == (const void*)eig || (const void*)gram == (const void*)cmat || (const void*)gram == (const void*)eig)
+        return fail(PNP_ERR_INVALID, "%s: y0, cmat, eig and gram must not alias", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (acs_h > H) return fail(PNP_ERR_INVALID, "%s: acs_h must be <= h=%d (got %d)", fn, H, acs_h);
+    if (acs_w > W) return fail(PNP_ERR_INVALID, "%s: acs_w must be <= w=%d (got %d)", fn, W, acs_w);
+    if (N > 65535) return fail(PNP_ERR_INVALID, "%s: n must be <= 65535 (got %d)", fn, N);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cc = (size_t)coils * coils;
+    if (int rc = cc_ensure(e, (size_t)N * gram_chunks(acs_h, acs_w) * cc, gram ? 0 : (size_t)N * cc)) return rc;
+    double2* const g = gram ? (double2*)gram : e->cc_gram;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_coilcomp_gram((const float2*)y0, coils, acs_h, acs_w, e->cc_part, g, N, H, W, s));
+    HIP_TRY(launch_coilcomp_eig(g, coils, (float2*)cmat, eig, N, s));
+    p.end(3);
+    return PNP_OK;
+    PNP_API_END("pnp_coil_compress_matrix")
+}
+
+int pnp_coil_compress_apply(pnp_handle e, const float* in, int coils, const float* cmat, int cmat_n, int out_coils, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_coil_compress_apply";
+    if (coils < 1 || coils > PNP_CC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_CC_MAX_COILS, coils);
+    const int vmax = coils < PNP_MC_MAX_COILS ? coils : PNP_MC_MAX_COILS;
+    if (out_coils < 1 || out_coils > vmax) return fail(PNP_ERR_INVALID, "%s: out_coils must be 1..min(coils, %d) = %d (got %d)", fn, PNP_MC_MAX_COILS, vmax, out_coils);
+    if (cmat_n < 1) return fail(PNP_ERR_INVALID, "%s: cmat_n must be 1 or the handle's n (got %d)", fn, cmat_n);
+    if (!in) return fail(PNP_ERR_INVALID, "%s: null in", fn);
+    if (!cmat) return fail(PNP_ERR_INVALID, "%s: null cmat", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (out == in || out == cmat) return fail(PNP_ERR_INVALID, "%s: out must not alias in or cmat", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (cmat_n != 1 && cmat_n != N) return fail(PNP_ERR_INVALID, "%s: cmat_n must be 1 or the handle's n=%d (got %d)", fn, N, cmat_n);
+    if (N > 65535) return fail(PNP_ERR_INVALID, "%s: n must be <= 65535 (got %d)", fn, N);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_coilcomp_apply((const float2*)in, (const float2*)cmat, cmat_n, coils, out_coils, (float2*)out, N, H, W, s));
+    return PNP_OK;
+    PNP_API_END("pnp_coil_compress_apply")
 }
 
 size_t pnp_snapshot_bytes(pnp_handle e) {

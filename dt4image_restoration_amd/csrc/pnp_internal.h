@@ -269,4 +269,17 @@ hipError_t launch_coilmap_max(const float* partial, float* smax, int N, int H, i
 // l <- (rss > 0 and rss > thresh * smax[n]) ? l / rss : 0
 hipError_t launch_coilmap_normalise(float2* l, int C, const float* rss, const float* smax, float thresh, int N, int H, int W, hipStream_t s);
 
+// ---- coil compression (coilcomp_kernels.hip) --------------------------------------------------------
+// The block's bins are dealt to gram_chunks(acs_h, acs_w) workgroups per slice, gram_chunk_bins(bins) consecutive bins each: kGramMinBins, or
+// for blocks above kGramMinBins * kGramMaxChunks bins the 32-multiple that gives at most kGramMaxChunks workgroups.
+static constexpr int kGramMinBins = 1024, kGramMaxChunks = 64;
+int gram_chunk_bins(int bins);
+int gram_chunks(int acs_h, int acs_w);
+// gram: [N, C, C] complex128 = sum over the centred acs_h x acs_w block of y_a conj(y_b); partial: [N, gram_chunks, C, C] complex128.  Two launches.
+hipError_t launch_coilcomp_gram(const float2* y, int C, int acs_h, int acs_w, double2* partial, double2* gram, int N, int H, int W, hipStream_t s);
+// cmat: [N, C, C] complex64, eig: [N, C] float32 from gram: one workgroup per slice
+hipError_t launch_coilcomp_eig(const double2* gram, int C, float2* cmat, float* eig, int N, hipStream_t s);
+// out[n, v] = sum_c cmat[n or 0][v][c] in[n, c], v < V; in: [N, C, H, W], out: [N, V, H, W]
+hipError_t launch_coilcomp_apply(const float2* in, const float2* cmat, int cmat_n, int C, int V, float2* out, int N, int H, int W, hipStream_t s);
+
 }  // namespace pnp

@@ -312,6 +312,44 @@ class PnPEngine:
                                               sens.data_ptr(), _ptr(rss), self._stream()), "pnp_estimate_sens")
         return (sens, rss) if return_rss else sens
 
+    def coil_compress_matrix(self, y0: torch.Tensor, acs: Tuple[int, int], return_gram: bool = False):
+        """Coil compression matrices from the calibration block of multi-coil k-space (pnp_coil_compress_matrix): y0 complex64
+        [N,C,H,W] in the centred layout, C <= 64, acs = (acs_h, acs_w) the even sides of the centred block.  Per slice the C x C channel
+        covariance of the block is diagonalised on the device; row v of cmat is virtual coil v, in order of descending eigenvalue.
+        Returns (cmat complex64 [N,C,C], eig float32 [N,C]) and with return_gram also the covariance, complex128 [N,C,C].  Does not
+        change the engine's mode or its installed constants."""
+        if y0.dim() != 4 or y0.shape[0] != self.n or tuple(y0.shape[-2:]) != (self.h, self.w):
+            raise ValueError(f"y0: expected [{self.n},C,{self.h},{self.w}], got {tuple(y0.shape)}")
+        coils = int(y0.shape[1])
+        y0 = self._chk(y0, torch.complex64, self.n * coils * self.h * self.w, "y0")
+        acs_h, acs_w = (int(v) for v in acs)
+        cmat = torch.empty((self.n, coils, coils), dtype=torch.complex64, device=self.device)
+        eig = torch.empty((self.n, coils), dtype=torch.float32, device=self.device)
+        gram = torch.empty((self.n, coils, coils), dtype=torch.complex128, device=self.device) if return_gram else None
+        _lib.check(self.lib.pnp_coil_compress_matrix(self._h, y0.data_ptr(), coils, acs_h, acs_w, 0, cmat.data_ptr(), eig.data_ptr(),
+                                                     _ptr(gram), self._stream()), "pnp_coil_compress_matrix")
+        return (cmat, eig, gram) if return_gram else (cmat, eig)
+
+    def coil_compress_apply(self, planes: torch.Tensor, cmat: torch.Tensor, out_coils: int) -> torch.Tensor:
+        """The leading `out_coils` virtual coils of `planes` (pnp_coil_compress_apply): planes complex64 [N,C,H,W] - k-space or coil
+        maps, the mix is pointwise -, cmat complex64 [C,C] (one matrix for all slices) or [N,C,C].  Returns complex64 [N,out_coils,H,W],
+        out[n,v] = sum_c cmat[n,v,c] planes[n,c]."""
+        if planes.dim() != 4 or planes.shape[0] != self.n or tuple(planes.shape[-2:]) != (self.h, self.w):
+            raise ValueError(f"planes: expected [{self.n},C,{self.h},{self.w}], got {tuple(planes.shape)}")
+        coils = int(planes.shape[1])
+        planes = self._chk(planes, torch.complex64, self.n * coils * self.h * self.w, "planes")
+        if tuple(cmat.shape) not in ((coils, coils), (1, coils, coils), (self.n, coils, coils)):
+            raise ValueError(f"cmat: expected [{coils},{coils}] or [{self.n},{coils},{coils}], got {tuple(cmat.shape)}")
+        cmat_n = 1 if cmat.numel() == coils * coils else self.n
+        cmat = self._chk(cmat, torch.complex64, cmat_n * coils * coils, "cmat")
+        out_coils = int(out_coils)
+        if not 1 <= out_coils <= min(coils, _lib.PNP_MC_MAX_COILS):
+            raise ValueError(f"out_coils must be 1..{min(coils, _lib.PNP_MC_MAX_COILS)}, got {out_coils}")
+        out = torch.empty((self.n, out_coils, self.h, self.w), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_coil_compress_apply(self._h, planes.data_ptr(), coils, cmat.data_ptr(), cmat_n, out_coils, out.data_ptr(),
+                                                    self._stream()), "pnp_coil_compress_apply")
+        return out
+
     def snapshot(self, x: torch.Tensor, z: torch.Tensor, u: torch.Tensor, t_state: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One packed device buffer [x | z | u | T] (pnp_snapshot): a tree-search node's copy of the iterate."""

@@ -291,6 +291,53 @@ int pnp_acquire_mc(pnp_handle h, const float* gt, const float* sens, int coils, 
 int pnp_estimate_sens(pnp_handle h, const float* y0, int coils, int acs_h, int acs_w, int window, double thresh, int flags,
                       float* sens, float* rss /* may be NULL */, void* stream);
 
+/* Coil compression: SVD virtual coils.  Every cost of the multi-coil stage is linear in the coil count, so an acquisition with C channels is
+ * first mixed down to V <= PNP_MC_MAX_COILS virtual coils by the leading eigenvectors of the calibration block's channel covariance; a unitary
+ * mix keeps white noise white, so the SENSE model is unchanged with the maps mixed by the same matrix (the reference has no counterpart).
+ *
+ * pnp_coil_compress_matrix, per slice n, with the centred block of pnp_estimate_sens (-acs_h/2 <= ky - H/2 < acs_h/2, likewise in x):
+ *     G[a][b]    = sum over the block's bins of y0[n,a] conj(y0[n,b])                                   (C x C Hermitian)
+ *     G          = U diag(lambda) U^H,  lambda descending
+ *     cmat[v][c] = conj(U[c][v]),  eig[v] = lambda_v        row v = virtual coil v:  y'_v = sum_c cmat[v][c] y_c
+ *   Gram: the terms are the float32 components of y0, multiplied and summed in float64 (the products are exact).  The block's bins, in row-major
+ *     block order, are dealt to ceil(B / per) workgroups of `per` consecutive bins, B = acs_h acs_w, per = max(1024, ceil(B / 64) rounded up
+ *     to a multiple of 32); each sums its bins in order (re += ar br; re += ai bi; im += ai br; im -= ar bi) and a second launch adds the
+ *     workgroups' partials in index order.  No atomics: the order depends on (H, W, acs_h, acs_w) only.  G is stored exactly Hermitian, its
+ *     diagonal real.
+ *   Eigen-decomposition: one workgroup per slice, float64, G and the vectors on chip: cyclic Jacobi in round-robin order (C padded to even, C - 1
+ *     rounds of C / 2 disjoint rotations per sweep).  Before every sweep the workgroup tests off(G)_F <= 1e-14 * trace(G) and stops on it; at most
+ *     24 sweeps (noisy 8- to 64-coil blocks stop after 5 to 8; an input that runs into the cap still has eigenvalues good to the off-diagonal that is left).  No
+ *     host read.  A pair whose off-diagonal entry beta is exactly zero is skipped; otherwise tau = (G[q][q] - G[p][p]) / (2 |beta|),
+ *     t = sgn(tau) / (|tau| + hypot(1, tau)) - no square of tau is formed, a vanishing beta gives t = 0.
+ *   Order and phase: a stable descending sort of the diagonal; each eigenvector is multiplied by the unit complex number that makes its entry of
+ *     largest modulus (squared moduli compared in float64, the lowest index wins a tie) real and positive, in float64; cmat is rounded to
+ *     complex64 once and eig to float32 once.  An all-zero block gives cmat = identity and eig = 0; no finite input gives NaN.
+ *   y0    : DEVICE complex64 [N,C,H,W], centred layout; read inside the block only
+ *   coils : 1..PNP_CC_MAX_COILS;   acs_h, acs_w : even, 2 <= acs_h <= H, 2 <= acs_w <= W;   flags : reserved, must be 0
+ *   cmat  : DEVICE complex64 [N,C,C] out;   eig : DEVICE float32 [N,C] out, descending;   gram : DEVICE complex128 [N,C,C] out, or NULL
+ * A slice's bits depend on (y0[n], acs_h, acs_w) only: not on N, its place in the batch, the stream or the handle kind.
+ * SETUP-TIME SEMANTICS, as pnp_estimate_sens: the first call allocates 16 n C^2 ceil(B / per) bytes (the Gram partials) and, when gram is NULL,
+ * 16 n C^2 bytes more (the Gram), inside the call, all-or-nothing (on PNP_ERR_NOMEM the handle keeps the workspace it had), counted by
+ * pnp_workspace_bytes.  A later call allocates only if it needs more than any call before it (more coils, a block of more workgroups), and then
+ * waits for the device; every other call allocates nothing and is asynchronous.  Calls on one handle are stream-ordered.
+ *
+ * pnp_coil_compress_apply:  out[n,v,p] = sum_{c = 0 .. C-1} cmat[n or 0][v][c] * in[n,c,p],  v < out_coils, over all H W bins - k-space or coil
+ * maps: the kernel is pointwise, and no map enters it specially.  float32, from re = im = +0, c ascending, every product contracted:
+ *     re = fma(a.re, x.re, re);  re = fma(-a.im, x.im, re);  im = fma(a.re, x.im, im);  im = fma(a.im, x.re, im)        (a = cmat[v][c], x = in[c])
+ * so an identity or permutation matrix copies the planes exactly (a -0 component comes out as +0), and a bin that is zero in every coil stays zero.
+ *   in        : DEVICE complex64 [N,C,H,W];   coils : 1..PNP_CC_MAX_COILS
+ *   cmat      : DEVICE complex64 [cmat_n,C,C];   cmat_n : 1 (one matrix for all slices) or N
+ *   out_coils : 1..min(coils, PNP_MC_MAX_COILS);   out : DEVICE complex64 [N,out_coils,H,W], must not alias in or cmat
+ * It moves 8 C + 8 V bytes per pixel (each input value is read once), allocates nothing and is asynchronous.
+ *
+ * Both calls take any handle kind and change neither the handle's mode nor its installed constants; n <= 65535.  Every argument error (null
+ * handle or pointer, aliased buffers, coils outside 1..64, out_coils outside 1..min(coils, 32), cmat_n not 1 or n, acs_h / acs_w odd, below 2
+ * or above the handle's H / W, flags != 0) is reported before any HIP call and leaves the outputs untouched. */
+#define PNP_CC_MAX_COILS 64
+int pnp_coil_compress_matrix(pnp_handle h, const float* y0, int coils, int acs_h, int acs_w, int flags, float* cmat, float* eig,
+                             double* gram /* may be NULL */, void* stream);
+int pnp_coil_compress_apply(pnp_handle h, const float* in, int coils, const float* cmat, int cmat_n, int out_coils, float* out, void* stream);
+
 /* ---- tree search support --------------------------------------------------------------------- */
 
 /* Replaces: the per-child copy of `states` in expand_tree (evaluation/mcts.py:118-128), which the reference gets for
