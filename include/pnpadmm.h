@@ -11,6 +11,8 @@
  * Conventions
  *   - every pointer marked DEVICE is HIP device memory owned by the caller (e.g. a torch-ROCm
  *     tensor's data_ptr()); HOST pointers are ordinary memory.  No torch types cross this ABI.
+ *     DEVICE pointers are expected 16-byte aligned, as any hipMalloc or torch allocation and any whole-plane
+ *     view of one is.
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*; NULL = default stream) of the
  *     handle's device; no entry point synchronises the device except pnp_create /
  *     pnp_load_unet_weights / pnp_destroy (setup-time).  Entry points switch to the handle's device
