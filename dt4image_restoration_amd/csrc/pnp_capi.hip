@@ -2,6 +2,7 @@
 // sequencing of one PnP-ADMM iteration, kernel-level event timing.
 #include "../../include/pnpadmm.h"
 #include "pnp_internal.h"
+#include "denoiser_plan.h"
 #include "block_reduce.h"
 
 #include <cmath>
@@ -71,14 +72,6 @@ struct EventPair {
     int count;      // kernel launches between the two events (a run of same-class kernels shares one pair)
 };
 
-struct LevelBufs {
-    float* p;  // ping
-    float* q;  // pong
-    float* s;  // skip / stage output kept for the up path
-    float* pool;  // MaxPool2d(2) of s, written by the kernel that writes s (null if that kernel cannot)
-    int c, h, w;
-};
-
 }  // namespace
 
 struct pnp_engine {
@@ -86,21 +79,14 @@ struct pnp_engine {
     bool weights_loaded = false;
     bool reset_done = false;
     // denoiser
-    float* d_wpack[N_LAYERS] = {};   // packed conv3x3 weights (layers 1..26), raw for 0 and 27
+    float* d_wpack[N_LAYERS] = {};   // packed conv3x3 weights, raw for the first and the last layer
     float* d_bias[N_LAYERS] = {};
-    LevelBufs lv[5] = {};
+    float* plane[N_LEVELS][N_SLOTS] = {};   // activation planes by (level, slot); sized by the plan, [.][SLOT_NONE] stays null
     float* d_partial = nullptr;      // split-K workspace (small problems)
     unsigned* d_arrive = nullptr;    // split-K arrival counters (PNP_SPLITK_INLAUNCH), zero between launches
     Tuning tune;                      // environment overrides, read once in pnp_create
-    WinoPlan wplan[N_LAYERS] = {};    // per-layer launch plans, fixed at pnp_create: the weight pack and every launch use
-    ConvPlan cplan[N_LAYERS] = {};    // the same plan
-    bool wino[N_LAYERS] = {};         // layer runs on the Winograd kernel (weights packed for it)
-    bool fuse_last = false;           // last 1x1 layer rides in the epilogue of up4.conv-2
-    bool fuse_first = false;          // first layer (2 -> 32) is computed in the staging of inc.conv-1 (F(4x4) 32-channel variant)
-    bool pool_ok[4] = {};             // level k's stage output also gets a pooled copy (its producing kernel supports it)
-    int bf16_terms = 0;               // bf16 mode: bf16 terms per conv weight (2: hi + lo, the default; 1: PNP_BF16_W1); 0 = f32 mode
-    bool act16 = false;               // bf16 mode: the 32-channel level-0 activations (lv[0].p/q/s) are stored as bf16 (ConvArgs.act16)
-    uint8_t abits[N_LAYERS] = {};     // bf16 mode, per conv layer: ConvArgs.act16 (bit 0: src0 holds bf16, bit 1: dst holds bf16)
+    DenoiserPlan dplan;               // fixed at pnp_create (plan_denoiser): the allocations, the weight pack and every launch read it
+    ConvArgs largs[N_LAYERS] = {};    // per launch of the plan: the ConvArgs fields that never change (planes, sizes, format bits)
     // data-fidelity stage
     FftPlan plan = {};
     float2* d_work = nullptr;   // [N,H,W] complex scratch
@@ -149,7 +135,7 @@ int check_kspace_sizes(const char* fn, const pnp_engine* e, const char* what = "
 }
 
 // One HIP event pair around a kernel launch - or, with `defer_end`, around a RUN of same-class launches that follow each
-// other on the stream (the 26 conv3x3 launches of a denoiser forward): `count` launches, closed by end().  Event records
+// other on the stream (the conv3x3 launches of a denoiser forward): `count` launches, closed by end().  Event records
 // cost ~3 us of stream time each, so the default profile mode brackets the conv run once; PNP_FLAG_PROFILE_LAYERS keeps
 // a pair per launch for the per-layer table.
 struct Prof {
@@ -203,22 +189,70 @@ int make_twiddles(int L, float2** out) {
     return PNP_OK;
 }
 
-// conv3x3 layer `li` on the kernel family its weights were packed for (create_impl): F(4x4) Winograd, F(2x2) Winograd or the direct kernel
-hipError_t launch_conv_layer(const pnp_engine* e, int li, const ConvArgs& a, int src_mode, hipStream_t s) {
-    if (e->wino[li] && e->wplan[li].algo == 4) return launch_conv3x3_winograd4(a, e->wplan[li], src_mode, s);
-    if (e->wino[li]) return launch_conv3x3_winograd(a, e->wplan[li], src_mode, s);
-    return launch_conv3x3(a, e->cplan[li], src_mode, s);
+// a conv3x3 launch on the kernel family of its plan record - the family its weights were packed for
+hipError_t launch_conv_layer(const ConvLaunch& l, const ConvArgs& a, hipStream_t s) {
+    switch (l.family) {
+    case FAM_WINO4: return launch_conv3x3_winograd4(a, l.wino, l.src_mode, s);
+    case FAM_WINO2: return launch_conv3x3_winograd(a, l.wino, l.src_mode, s);
+    case FAM_DIRECT: case FAM_WS: return launch_conv3x3(a, l.conv, l.src_mode, s);
+    default: return hipErrorInvalidValue;
+    }
 }
 
-// The 27 MFMA convs + first/last layer of one denoiser forward.  Image channel = ximg, or Re(z-u).
+// The part of every launch's ConvArgs that is fixed with the plan: plane names resolved to the handle's buffers, sizes, format bits.
+void resolve_launches(pnp_engine* e) {
+    const DenoiserPlan& P = e->dplan;
+    auto at = [&](PlaneRef r) { return e->plane[r.level][r.slot]; };
+    for (int i = 0; i < P.n_launches; ++i) {
+        const ConvLaunch& l = P.launch[i];
+        const LayerSpec& L = kLayers[l.layer];
+        ConvArgs a{};
+        a.src0 = at(l.src0); a.src1 = at(l.src1); a.dst = at(l.dst); a.pooled = at(l.pooled);
+        a.partial = e->d_partial; a.arrive = e->d_arrive;
+        a.bf16 = P.bf16_terms;
+        a.act16 = l.act16;
+        a.N = e->cfg.n; a.H = e->cfg.h >> L.level; a.W = e->cfg.w >> L.level; a.Cin = L.cin; a.Cskip = L.cskip; a.Cout = L.cout;
+        if (L.src == SRC_UPCAT) {
+            const int hs = a.H / 2, ws = a.W / 2;
+            a.rh = a.H > 1 ? (float)(hs - 1) / (float)(a.H - 1) : 0.f;
+            a.rw = a.W > 1 ? (float)(ws - 1) / (float)(a.W - 1) : 0.f;
+        }
+        e->largs[i] = a;
+    }
+}
+
+// ConvArgs of launch `i` of the plan for one forward: the resolved part plus the weights and the caller's pointers
+ConvArgs conv_args(const pnp_engine* e, int i, const float* ximg, const float2* z, const float2* u, const float* sigma, const float* tact, float* out) {
+    const ConvLaunch& l = e->dplan.launch[i];
+    ConvArgs a = e->largs[i];
+    a.wpack = e->d_wpack[l.layer]; a.bias = e->d_bias[l.layer]; a.tact = tact;
+    if (l.fused_first) {                               // inc.conv-1 evaluates the first layer while staging its patch
+        a.first_w = e->d_wpack[0]; a.first_b = e->d_bias[0]; a.first_sigma = sigma;
+        a.last_ximg = ximg; a.last_z = z; a.last_u = u;
+    }
+    if (l.fused_last) {                                // up4.conv-2 with the last layer (1x1 + residual + clamp) in its epilogue: writes `out` directly
+        a.last_w = e->d_wpack[N_LAYERS - 1]; a.last_b = e->d_bias[N_LAYERS - 1]; a.last_ximg = ximg; a.last_z = z; a.last_u = u; a.last_out = out;
+    }
+#ifdef PNP_DIAG
+    if (const char* dv = getenv("PNP_DIAG_L0")) a.diag = kLayers[l.layer].level == 0 ? atoi(dv) : 0;
+    if (const char* dv = getenv("PNP_DIAG_ALL")) a.diag = atoi(dv);
+#endif
+    return a;
+}
+
+// One denoiser forward: the launches of the handle's plan in order - the first layer (unless fused), the run of conv3x3 MFMA launches,
+// the last layer (unless fused).  Image channel = ximg, or Re(z-u).
 int run_unet(pnp_engine* e, const float* ximg, const float2* z, const float2* u, const float* sigma,
              const float* tact, float* out, hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
     if (e->cfg.flags & PNP_FLAG_NO_DENOISER)
         return fail(PNP_ERR_STATE, "this handle was created with PNP_FLAG_NO_DENOISER");
-    if (!e->fuse_first) {
-        Prof p(e, s, PROF_CONV_FIRST, 0);
-        HIP_TRY(launch_conv_first(ximg, z, u, sigma, tact, e->d_wpack[0], e->d_bias[0], e->lv[0].p, N, H, W, s, e->act16));
+    const DenoiserPlan& P = e->dplan;
+    int i = 0;
+    if (P.launch[i].family == FAM_FIRST) {
+        Prof p(e, s, PROF_CONV_FIRST, P.launch[i].layer);
+        HIP_TRY(launch_conv_first(ximg, z, u, sigma, tact, e->d_wpack[0], e->d_bias[0], e->largs[i].dst, N, H, W, s, (P.launch[i].act16 & 2) != 0));
+        ++i;
     }
     const bool per_layer = (e->cfg.flags & PNP_FLAG_PROFILE_LAYERS) != 0;
 #ifdef PNP_DIAG
@@ -242,87 +276,23 @@ int run_unet(pnp_engine* e, const float* ximg, const float2* z, const float2* u,
 #endif
     Prof run(e, s, PROF_CONV3X3, -1, !per_layer, true);   // one event pair around the whole conv3x3 run
     int run_launches = 0;
-    auto conv = [&](int li, const float* src0, const float* src1, float* dst, int lvl, float* pooled = nullptr,
-                    bool src_is_pooled = false) -> int {
-        const LayerSpec& L = kLayers[li];
-        ConvArgs a{};
-        a.pooled = pooled;
-        a.src0 = src0; a.src1 = src1; a.wpack = e->d_wpack[li]; a.bias = e->d_bias[li]; a.dst = dst; a.partial = e->d_partial; a.arrive = e->d_arrive; a.tact = tact;
-        a.bf16 = e->bf16_terms;
-        a.act16 = e->abits[li];
-        a.N = N; a.H = H >> lvl; a.W = W >> lvl; a.Cin = L.cin; a.Cskip = L.cskip; a.Cout = L.cout;
-        if (L.src == SRC_UPCAT) {
-            const int hs = a.H / 2, ws = a.W / 2;
-            a.rh = a.H > 1 ? (float)(hs - 1) / (float)(a.H - 1) : 0.f;
-            a.rw = a.W > 1 ? (float)(ws - 1) / (float)(a.W - 1) : 0.f;
-        }
-        int src_mode = (L.src == SRC_POOL && src_is_pooled) ? (int)SRC_PLAIN : L.src;   // pooled copy already exists
-        if (li == 1 && e->fuse_first) {                    // inc.conv-1 evaluates the first layer while staging its patch
-            src_mode = SRC_FIRST;
-            a.first_w = e->d_wpack[0]; a.first_b = e->d_bias[0]; a.first_sigma = sigma;
-            a.last_ximg = ximg; a.last_z = z; a.last_u = u;
-        }
-#ifdef PNP_DIAG
-        if (const char* dv = getenv("PNP_DIAG_L0")) a.diag = L.level == 0 ? atoi(dv) : 0;
-        if (const char* dv = getenv("PNP_DIAG_ALL")) a.diag = atoi(dv);
-#endif
-        Prof p(e, s, PROF_CONV3X3, li, per_layer);
+    for (; i < P.n_launches && P.launch[i].family != FAM_LAST; ++i) {
+        const ConvLaunch& l = P.launch[i];
+        const ConvArgs a = conv_args(e, i, ximg, z, u, sigma, tact, out);
+        Prof p(e, s, PROF_CONV3X3, l.layer, per_layer);
         ++run_launches;
         hipStream_t ls = s;
 #ifdef PNP_DIAG
         // PNP_DIAG_STREAMS=K (timing only, results wrong): conv launch i goes to side stream i % K, so consecutive layers do NOT wait for
         // each other - the ceiling of any scheme that overlaps a layer's tail with its successor's head (profiles/r05_ablation.md)
-        if (diag_k > 1) ls = diag_pool[li % diag_k];
+        if (diag_k > 1) ls = diag_pool[l.layer % diag_k];
 #endif
-        HIP_TRY(launch_conv_layer(e, li, a, src_mode, ls));
-        return PNP_OK;
-    };
-    int rc;
-    // inc; a stage's last conv also writes the 2x2 max-pooled copy the next stage starts from, when its kernel can
-    if ((rc = conv(1, e->lv[0].p, nullptr, e->lv[0].q, 0))) return rc;
-    if ((rc = conv(2, e->lv[0].q, nullptr, e->lv[0].s, 0, e->pool_ok[0] ? e->lv[0].pool : nullptr))) return rc;
-    // down1..4: conv-0 reads the pooled copy (or pools the previous stage output while staging)
-    for (int k = 1; k <= 4; ++k) {
-        const int b = 3 * k;
-        const bool pooled_in = e->pool_ok[k - 1];
-        if ((rc = conv(b, pooled_in ? e->lv[k - 1].pool : e->lv[k - 1].s, nullptr, e->lv[k].p, k, nullptr, pooled_in))) return rc;
-        if ((rc = conv(b + 1, e->lv[k].p, nullptr, e->lv[k].q, k))) return rc;
-        if ((rc = conv(b + 2, e->lv[k].q, nullptr, e->lv[k].s, k, (k < 4 && e->pool_ok[k]) ? e->lv[k].pool : nullptr))) return rc;
+        HIP_TRY(launch_conv_layer(l, a, ls));
     }
-    // up1..4: conv-0 reads cat([skip, bilinear_up(low)]) while staging
-    const float* low = e->lv[4].s;
-    for (int k = 3; k >= 1; --k) {
-        const int b = 15 + 3 * (3 - k);
-        if ((rc = conv(b, e->lv[k].s, low, e->lv[k].p, k))) return rc;
-        if ((rc = conv(b + 1, e->lv[k].p, nullptr, e->lv[k].q, k))) return rc;
-        if ((rc = conv(b + 2, e->lv[k].q, nullptr, e->lv[k].p, k))) return rc;
-        low = e->lv[k].p;
-    }
-    if ((rc = conv(24, e->lv[0].s, low, e->lv[0].p, 0))) return rc;
-    if ((rc = conv(25, e->lv[0].p, nullptr, e->lv[0].q, 0))) return rc;
-    if (e->fuse_last) {
-        // up4.conv-2 with the last layer (1x1 + residual + clamp) fused into its epilogue: writes `out` directly
-        const LayerSpec& L = kLayers[26];
-        ConvArgs a{};
-        a.src0 = e->lv[0].q; a.wpack = e->d_wpack[26]; a.bias = e->d_bias[26]; a.dst = e->lv[0].p; a.partial = e->d_partial; a.arrive = e->d_arrive;
-        a.bf16 = e->bf16_terms;
-        a.act16 = e->abits[26] & 1;
-        a.tact = tact; a.N = N; a.H = H; a.W = W; a.Cin = L.cin; a.Cskip = 0; a.Cout = L.cout;
-        a.last_w = e->d_wpack[27]; a.last_b = e->d_bias[27]; a.last_ximg = ximg; a.last_z = z; a.last_u = u; a.last_out = out;
-#ifdef PNP_DIAG
-        if (const char* dv = getenv("PNP_DIAG_L0")) a.diag = atoi(dv);
-#endif
-        {
-            Prof p(e, s, PROF_CONV3X3, 26, per_layer);
-            ++run_launches;
-            HIP_TRY(launch_conv_layer(e, 26, a, SRC_PLAIN, s));
-        }
-        run.end(run_launches);
-    } else {
-        if ((rc = conv(26, e->lv[0].q, nullptr, e->lv[0].p, 0))) return rc;
-        run.end(run_launches);
-        Prof p(e, s, PROF_CONV_LAST, 27);
-        HIP_TRY(launch_conv_last(e->lv[0].p, ximg, z, u, tact, e->d_wpack[27], e->d_bias[27], out, N, H, W, s));
+    run.end(run_launches);
+    if (i < P.n_launches) {
+        Prof p(e, s, PROF_CONV_LAST, P.launch[i].layer);
+        HIP_TRY(launch_conv_last(e->largs[i].src0, ximg, z, u, tact, e->d_wpack[N_LAYERS - 1], e->d_bias[N_LAYERS - 1], out, N, H, W, s));
     }
     return PNP_OK;
 }
@@ -568,132 +538,27 @@ extern "C" {
 const char* pnp_last_error(void) { return g_err.c_str(); }
 const char* pnp_version(void) { return "pnpadmm 0.4 (gfx950, f32 MFMA; optional bf16-operand convs with two-term weights)"; }
 
-// Does layer `li` (a stage's last conv, planned already) also write the 2x2 max-pooled copy of its output?  Its output must have
-// even sides and its kernel must support it (a Winograd kernel, or the direct kernel's LDS-epilogue plan).  ONE predicate for the
-// consumer's planned source mode and for the launch-time pool_ok[] flags.
-static bool pooled_copy_ok(const pnp_engine* e, int li) {
-    const LayerSpec& L = kLayers[li];
-    const int lh = e->cfg.h >> L.level, lw = e->cfg.w >> L.level;
-    return lh % 2 == 0 && lw % 2 == 0 && (e->wino[li] || conv3x3_pooled_output_ok(e->cplan[li]));
-}
-
+// Allocates what the handle's plan (e->dplan, e->tune: set by pnp_create) asks for, and the k-space side
 static int create_impl(const pnp_config* cfg, pnp_engine* e) {
-    e->cfg = *cfg;
-    e->tune = tuning_from_env();
     const size_t N = cfg->n, H = cfg->h, W = cfg->w;
-    const bool bf16 = (cfg->flags & PNP_FLAG_BF16_CONVS) != 0;
-    e->bf16_terms = bf16 ? (e->tune.bf16_w1 ? 1 : 2) : 0;
-    static const int chan[5] = {32, 64, 128, 256, 512};
-    for (int k = 0; k < 5; ++k) {
-        LevelBufs& L = e->lv[k];
-        L.c = chan[k]; L.h = (int)(H >> k); L.w = (int)(W >> k);
-        if (cfg->flags & PNP_FLAG_NO_DENOISER) continue;   // k-space-only handle: no activation planes
-        const size_t bytes_full = N * L.h * L.w * L.c * sizeof(float);
-        float** bufs[4] = {&L.p, &L.q, &L.s, &L.pool};
-        for (auto b : bufs) {
-            const size_t bytes = (b == &L.pool) ? (k < 4 ? bytes_full / 4 : 0) : bytes_full;
+    const DenoiserPlan& P = e->dplan;
+    for (int k = 0; k < N_LEVELS; ++k)
+        for (int slot = 0; slot < N_SLOTS; ++slot) {
+            const size_t bytes = P.plane_bytes[k][slot];
             if (bytes == 0) continue;
-            hipError_t er = hipMalloc((void**)b, bytes);
+            hipError_t er = hipMalloc((void**)&e->plane[k][slot], bytes);
             if (er != hipSuccess) return fail(PNP_ERR_NOMEM, "activation planes: %s", hipGetErrorString(er));
             e->ws_bytes += bytes;
         }
-    }
-    if (!(cfg->flags & PNP_FLAG_NO_DENOISER)) {
-        // launch plans of the 26 conv3x3 layers: fixed here, used by the weight pack and by every launch
-        size_t pf = 0;
-        for (int li = 1; li < N_LAYERS - 1; ++li) {
-            const LayerSpec& L = kLayers[li];
-            const int lh = cfg->h >> L.level, lw = cfg->w >> L.level;
-            // the source mode the launch will use: a pooled stage input is read PLAIN from the producer's pooled copy, which
-            // exists iff the producing layer (li - 1, planned just before) runs a Winograd kernel or the direct LDS-epilogue plan
-            // (the same predicate as pool_ok[] below: the producer's output size - twice this layer's - must be even, which it
-            // always is, and its kernel must be one that writes the pooled copy)
-            int src_mode = L.src;
-            if (L.src == SRC_POOL && pooled_copy_ok(e, li - 1)) src_mode = SRC_PLAIN;
-            e->wplan[li] = winograd_plan(cfg->n, lh, lw, L.cin, L.cout, src_mode, e->tune);
-            if (li == 26 && e->wplan[li].algo == 4 && !(cfg->flags & PNP_FLAG_KEEP_STAGES) &&
-                (e->tune.no_f4_fused_last || e->wplan[li].bn != 32 || e->wplan[li].mt != 32)) {
-                // up4.conv-2 carries the fused last layer (1x1 conv + residual + clamp) in its epilogue: the F(4x4) kernel's
-                // 32-channel variant has it (DPP reduce-scatter over a pixel's channels); PNP_NO_F4_FUSED_LAST puts the layer
-                // back on the F(2x2) kernel, which walks whole pixels there
-                Tuning t2 = e->tune;
-                t2.no_f4 = true;
-                e->wplan[li] = winograd_plan(cfg->n, lh, lw, L.cin, L.cout, src_mode, t2);
-            }
-            // (the producer / consumer kernel's upsample is the separable form: only on heights with the regular line structure)
-            const bool ws_ok = !e->tune.bf16_no_ws && (src_mode != SRC_UPCAT || upsample_lines_regular(lh));
-            e->cplan[li] = conv3x3_plan(cfg->n, lh, lw, L.cin, L.cout, bf16, src_mode, ws_ok);
-            // up4.conv-2 (fused last layer): on the producer / consumer kernel only in the two-term mode, where its producers evaluate the last
-            // layer (OFFLOAD); the one-term form of that tile measured slower than conv_kernels.hip (conv3x3_plan)
-            e->cplan[li].holdhi = e->tune.bf16_no_holdhi ? 0 : 1;
-            if (li == 26 && e->cplan[li].nt == 1 && (e->bf16_terms != 2 || e->tune.bf16_no_holdhi)) e->cplan[li].ws = 0;
-            e->wino[li] = e->wplan[li].use && !bf16;
-            if (e->wino[li] && e->wplan[li].algo == 4) continue;          // (per-slice descriptors)
-            if (!conv3x3_tensor_fits(cfg->n, lh, lw, L.cin, L.cout))
-                return fail(PNP_ERR_INVALID, "pnp_create: layer %d's output tensor (%d x %d x %d x %d floats) reaches 2 GiB, past this "
-                            "kernel's buffer descriptor: use a smaller batch per handle", li, cfg->n, lh, lw, L.cout);
-            if (e->wino[li]) continue;
-            const size_t f = conv3x3_partial_floats(e->cplan[li], cfg->n, lh, lw, L.cout);
-            if (f > pf) pf = f;
-        }
-        if (pf > 0) {
-            if (hipMalloc((void**)&e->d_partial, pf * sizeof(float)) != hipSuccess) return fail(PNP_ERR_NOMEM, "split-K workspace");
-            e->ws_bytes += pf * sizeof(float);
-            if (e->tune.splitk_inlaunch) {                 // one counter per output tile of a split-K launch
-                if (hipMalloc((void**)&e->d_arrive, kSplitKCounters * sizeof(unsigned)) != hipSuccess ||
-                    hipMemset(e->d_arrive, 0, kSplitKCounters * sizeof(unsigned)) != hipSuccess) return fail(PNP_ERR_NOMEM, "split-K counters");
-            }
-        }
-        // which stage outputs get a pooled copy: the producing conv (layers 2, 5, 8, 11) must run a kernel whose epilogue
-        // goes through LDS - the Winograd kernel, or the direct kernel's Cout = 32 configuration on a large problem
-        for (int k = 0; k < 4; ++k) {
-            const int li = 3 * k + 2;
-            const LayerSpec& L = kLayers[li];
-            const int lh = cfg->h >> L.level, lw = cfg->w >> L.level;
-            (void)lh; (void)lw;
-            e->pool_ok[k] = pooled_copy_ok(e, li);
-        }
-        e->fuse_last = !(cfg->flags & PNP_FLAG_KEEP_STAGES) && (e->wino[26] || conv3x3_pooled_output_ok(e->cplan[26]));
-        e->fuse_first = e->wino[1] && e->wplan[1].algo == 4 && e->wplan[1].bn == 32 && e->wplan[1].mt == 32 && !e->tune.no_f4_fused_first;
-        // bf16 mode: the five 32-channel level-0 layers exchange bf16 tensors (same bits the staging would round to; half the
-        // bytes of the HBM-bound level).  Needs the plan that has the variant on all five and the pooled copy for down1
-        // (always so today); a KEEP_STAGES handle keeps f32 stages for pnp_unet_read_stage.
-        e->act16 = bf16 && !(cfg->flags & PNP_FLAG_KEEP_STAGES) && !e->tune.bf16_f32_acts && e->pool_ok[0];
-        for (int li : {1, 2, 24, 25, 26}) e->act16 = e->act16 && conv3x3_pooled_output_ok(e->cplan[li]);
-        if (e->act16) {
-            // ... and so do the layers of the producer / consumer kernel among themselves: a tensor is bf16 when the launch that
-            // writes it and every launch that reads it as src0 (next layer, PLAIN or POOL; the decoder layer taking it as its
-            // skip tensor) can; the low-res input of an upsample (outputs of layers 14, 17, 20, 23) stays f32 - its consumer
-            // rounds after interpolating - and so do the pooled copy of level 0 and the input of the unfused 1x1 conv
-            auto can = [&](int li) { return li >= 1 && li <= 26 && ((li < 3 || li > 23) || e->cplan[li].ws != 0); };
-            bool out16[N_LAYERS] = {};
-            out16[0] = true;                                       // conv_first -> inc.conv-1
-            for (int li = 1; li <= 25; ++li) {
-                if (li == 14 || li == 17 || li == 20 || li == 23) continue;
-                const int skip_reader = li == 2 ? 24 : (li == 5 ? 21 : (li == 8 ? 18 : (li == 11 ? 15 : 0)));
-                // (a stage's last layer: the next stage reads the f32 pooled copy instead when there is one)
-                const bool next_reads = !(skip_reader != 0 && e->pool_ok[kLayers[li].level]);
-                out16[li] = can(li) && (!next_reads || can(li + 1)) && (skip_reader == 0 || can(skip_reader));
-            }
-            for (int li = 1; li <= 26; ++li) {
-                bool in16;
-                if (kLayers[li].src == SRC_POOL && e->pool_ok[kLayers[li].level - 1]) in16 = false;   // reads the producer's f32 pooled copy (today: li = 3)
-                else if (li == 15 || li == 18 || li == 21 || li == 24) in16 = out16[li == 15 ? 11 : (li == 18 ? 8 : (li == 21 ? 5 : 2))];
-                else in16 = out16[li - 1];
-                // the level-0 kernel writes bf16 only from its bf16-source variant
-                if ((li < 3 || li > 23) && !in16) out16[li] = false;
-                e->abits[li] = (uint8_t)((in16 ? 1 : 0) | (out16[li] ? 2 : 0));
-            }
-            // round 5: level 0's pooled copy (inc.conv-2 -> down1.conv-0) as bf16 too when both layers run the producer / consumer kernel:
-            // rounding to nearest even is monotonic, so bf16(max(a, b, c, d)) == max(bf16(a), ...) - the bits down1.conv-0 stages are the
-            // ones it rounded the f32 copy to, at half the bytes written and read (bit 2 of the writer's act16, bit 0 of the reader's)
-            if ((e->abits[2] & 2) && e->cplan[2].ws && e->cplan[3].ws && e->cplan[2].holdhi && e->bf16_terms == 2 && e->pool_ok[0] &&
-                kLayers[3].src == SRC_POOL) {
-                e->abits[2] |= 4;
-                e->abits[3] |= 1;
-            }
+    if (P.partial_floats > 0) {
+        if (hipMalloc((void**)&e->d_partial, P.partial_floats * sizeof(float)) != hipSuccess) return fail(PNP_ERR_NOMEM, "split-K workspace");
+        e->ws_bytes += P.partial_floats * sizeof(float);
+        if (P.want_arrive) {
+            if (hipMalloc((void**)&e->d_arrive, kSplitKCounters * sizeof(unsigned)) != hipSuccess ||
+                hipMemset(e->d_arrive, 0, kSplitKCounters * sizeof(unsigned)) != hipSuccess) return fail(PNP_ERR_NOMEM, "split-K counters");
         }
     }
+    resolve_launches(e);
     const size_t cbytes = N * H * W * sizeof(float2);
     if (hipMalloc((void**)&e->d_work, cbytes) != hipSuccess || hipMalloc((void**)&e->d_y0s, cbytes) != hipSuccess ||
         hipMalloc((void**)&e->d_masks, N * H * W) != hipSuccess)
@@ -730,6 +595,11 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     for (int k = 0; k < 4; ++k)
         if (!(cfg->flags & PNP_FLAG_NO_DENOISER) && !upsample_lines_regular(cfg->h >> k))
             return fail(PNP_ERR_INVALID, "pnp_create: upsample to %d rows is not line-regular in float32", cfg->h >> k);
+    // the whole denoiser plan before any device call or allocation: a handle it refuses costs nothing
+    const Tuning tune = tuning_from_env();
+    DenoiserPlan plan;
+    std::string why;
+    if (!plan_denoiser(*cfg, tune, &plan, &why)) return fail(PNP_ERR_INVALID, "%s", why.c_str());
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev)
@@ -737,6 +607,8 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     pnp_engine* e = new (std::nothrow) pnp_engine();
     if (!e) return fail(PNP_ERR_NOMEM, "pnp_create: out of host memory");
     e->cfg = *cfg;
+    e->tune = tune;
+    e->dplan = plan;
     int rc;
     {
         DeviceGuard g(cfg->device);
@@ -756,7 +628,7 @@ int pnp_destroy(pnp_handle e) {
     DeviceGuard g(e->cfg.device);
     (void)hipDeviceSynchronize();
     for (int i = 0; i < N_LAYERS; ++i) { (void)hipFree(e->d_wpack[i]); (void)hipFree(e->d_bias[i]); }
-    for (auto& L : e->lv) { (void)hipFree(L.p); (void)hipFree(L.q); (void)hipFree(L.s); (void)hipFree(L.pool); }
+    for (auto& level : e->plane) for (float* b : level) (void)hipFree(b);
     (void)hipFree(e->d_work); (void)hipFree(e->d_fftq); (void)hipFree(e->d_y0s); (void)hipFree(e->d_masks); (void)hipFree(e->d_ssim_part); (void)hipFree(e->d_res_part); (void)hipFree(e->d_partial); (void)hipFree(e->d_arrive);
     (void)hipFree(e->mc_y); (void)hipFree(e->mc_work); (void)hipFree(e->mc_sens); (void)hipFree(e->mc_vec); (void)hipFree(e->mc_part); (void)hipFree(e->mc_sc);
     (void)hipFree(e->cm_max); (void)hipFree(e->cm_rss);
@@ -769,7 +641,7 @@ int pnp_destroy(pnp_handle e) {
 }
 
 size_t pnp_workspace_bytes(pnp_handle e) { return e ? e->ws_bytes : 0; }
-int pnp_bf16_weight_terms(pnp_handle e) { return e ? e->bf16_terms : 0; }
+int pnp_bf16_weight_terms(pnp_handle e) { return e ? e->dplan.bf16_terms : 0; }
 
 // All-or-nothing: every layer is packed on the host and uploaded into NEW device buffers first; the handle's buffers are
 // replaced only when all 56 uploads succeeded, so a failure leaves the handle exactly as it was (an earlier successful
@@ -798,23 +670,28 @@ int pnp_load_unet_weights(pnp_handle e, const float* blob, size_t n_floats) {
             off += nw + L.cout;
             size_t pf;
             const float* src;
-            if (li == 0 || li == N_LAYERS - 1) {   // first (2->32, OIHW as is) and last (1x1) layers
+            const int at = e->dplan.launch_of[li];           // (-1: a layer fused into its neighbour; only the two raw ones can be)
+            switch (e->dplan.family[li]) {
+            case FAM_FIRST: case FAM_LAST:                   // first (2->32, OIHW as is) and last (1x1) layers
                 pf = nw; src = w;
-            } else if (e->wino[li] && e->wplan[li].algo == 4) {
+                break;
+            case FAM_WINO4:
                 pf = winograd4_pack_floats(L.cin, L.cout);
                 tmp.assign(pf, 0.f);
-                pack_winograd4_weights(w, L.cin, L.cout, e->wplan[li].ck, tmp.data());
+                pack_winograd4_weights(w, L.cin, L.cout, e->dplan.launch[at].wino.ck, tmp.data());
                 src = tmp.data();
-            } else if (e->wino[li]) {
+                break;
+            case FAM_WINO2:
                 pf = winograd_pack_floats(L.cin, L.cout);
                 tmp.assign(pf, 0.f);
-                pack_winograd_weights(w, L.cin, L.cout, e->wplan[li].ck, tmp.data());
+                pack_winograd_weights(w, L.cin, L.cout, e->dplan.launch[at].wino.ck, tmp.data());
                 src = tmp.data();
-            } else {
-                pf = bf16 ? conv3x3_pack_floats_bf16(L.cin, L.cout, e->bf16_terms) : conv3x3_pack_floats(L.cin, L.cout);
+                break;
+            default:                                         // FAM_DIRECT, FAM_WS
+                pf = bf16 ? conv3x3_pack_floats_bf16(L.cin, L.cout, e->dplan.bf16_terms) : conv3x3_pack_floats(L.cin, L.cout);
                 tmp.assign(pf, 0.f);
-                if (bf16) pack_conv3x3_weights_bf16(w, L.cin, L.cout, e->cplan[li].ck, e->bf16_terms, tmp.data());
-                else pack_conv3x3_weights(w, L.cin, L.cout, e->cplan[li].ck, tmp.data());
+                if (bf16) pack_conv3x3_weights_bf16(w, L.cin, L.cout, e->dplan.launch[at].conv.ck, e->dplan.bf16_terms, tmp.data());
+                else pack_conv3x3_weights(w, L.cin, L.cout, e->dplan.launch[at].conv.ck, tmp.data());
                 src = tmp.data();
             }
             if ((er = hipMalloc((void**)&nw_pack[li], pf * sizeof(float))) != hipSuccess) break;
@@ -1291,18 +1168,16 @@ int pnp_restore(pnp_handle e, const void* src, float* x, float* z, float* u, flo
 int pnp_unet_read_stage(pnp_handle e, int which, float* dst, int* c, int* hh, int* ww, void* stream) {
     PNP_API_BEGIN
     if (!e || which < 0 || which > 8) return fail(PNP_ERR_INVALID, "pnp_unet_read_stage: which must be 0..8");
-    if (which == 8 && e->fuse_last) return fail(PNP_ERR_STATE, "pnp_unet_read_stage: stage 8 is fused away; create the handle with PNP_FLAG_KEEP_STAGES");
-    if (which <= 3 && (e->abits[3 * which + 2] & 2))
-        return fail(PNP_ERR_STATE, "pnp_unet_read_stage: this stage is held as bf16 on this handle; create it with PNP_FLAG_KEEP_STAGES");
+    if (e->cfg.flags & PNP_FLAG_NO_DENOISER) return fail(PNP_ERR_STATE, "pnp_unet_read_stage: handle has no denoiser");
+    const StagePlan& st = e->dplan.stage[which];
+    if (st.fused_away) return fail(PNP_ERR_STATE, "pnp_unet_read_stage: stage 8 is fused away; create the handle with PNP_FLAG_KEEP_STAGES");
+    if (st.bf16) return fail(PNP_ERR_STATE, "pnp_unet_read_stage: this stage is held as bf16 on this handle; create it with PNP_FLAG_KEEP_STAGES");
     PNP_ON_DEVICE(e);
-    // stage outputs: inc, down1..4 live in lv[k].s; up1..4 in lv[3..0].p
-    const int lvl = which <= 4 ? which : 8 - which;
-    const LevelBufs& L = e->lv[lvl];
-    const float* src = which <= 4 ? L.s : L.p;
-    if (c) *c = L.c;
-    if (hh) *hh = L.h;
-    if (ww) *ww = L.w;
-    if (dst) HIP_TRY(launch_nhwc_to_nchw(src, dst, e->cfg.n, L.c, L.h, L.w, (hipStream_t)stream));
+    const float* src = e->plane[st.plane.level][st.plane.slot];
+    if (c) *c = st.c;
+    if (hh) *hh = st.h;
+    if (ww) *ww = st.w;
+    if (dst) HIP_TRY(launch_nhwc_to_nchw(src, dst, e->cfg.n, st.c, st.h, st.w, (hipStream_t)stream));
     return PNP_OK;
     PNP_API_END("pnp_unet_read_stage")
 }
@@ -1311,7 +1186,7 @@ int pnp_conv_algorithms(pnp_handle e, int32_t* algo28) {
     PNP_API_BEGIN
     if (!e || !algo28) return fail(PNP_ERR_INVALID, "pnp_conv_algorithms: null argument");
     if (e->cfg.flags & PNP_FLAG_NO_DENOISER) return fail(PNP_ERR_STATE, "pnp_conv_algorithms: handle has no denoiser");
-    for (int i = 0; i < N_LAYERS; ++i) algo28[i] = i == 0 ? 2 : (i == N_LAYERS - 1 ? 3 : (e->wino[i] ? e->wplan[i].algo : (e->cplan[i].ws ? 5 : 0)));
+    for (int i = 0; i < N_LAYERS; ++i) algo28[i] = e->dplan.family[i];
     return PNP_OK;
     PNP_API_END("pnp_conv_algorithms")
 }

@@ -67,6 +67,17 @@ def test_create_rejects_bad_config_without_touching_a_gpu():
     assert lib.pnp_create(None, C.byref(h)) == -1
 
 
+def test_create_rejects_a_plan_past_2gib_before_any_device_call():
+    """The denoiser's plan is made before the first device call: in bf16 mode (no F(4x4) layers) layer 1's output of a 256 x 256 x 256 handle
+    is exactly 2^31 bytes, which the planner refuses - with or without a GPU, and without allocating anything."""
+    import ctypes as C
+    lib = _lib.load()
+    h = C.c_void_p()
+    cfg = _lib.pnp_config(256, 256, 256, 0, _lib.PNP_FLAG_BF16_CONVS)
+    assert lib.pnp_create(C.byref(cfg), C.byref(h)) == -1            # PNP_ERR_INVALID
+    assert b"2 GiB" in lib.pnp_last_error() and not h.value
+
+
 def test_product_path_never_touches_the_oracle():
     """Nothing under the package (sub-packages and the C sources included) imports, names or links the oracle; only tests/,
     __graft_entry__.smoke() and bench.py's cpu_baseline leg may."""
