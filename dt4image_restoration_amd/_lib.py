@@ -21,6 +21,9 @@ RESIDUAL_COLUMNS = ("primal", "dx", "dz", "du", "delta", "dc")      # columns of
 PNP_MC_MAX_COILS = 32
 PNP_MC_MAX_CG = 64
 PNP_CC_MAX_COILS = 64
+PNP_ESPIRIT_MAX_COILS = 16
+PNP_ESPIRIT_MAX_KSIZE = 8
+PNP_ESPIRIT_MAX_N = 512
 PNP_SENS_BOX = 0
 PNP_SENS_HANN = 1
 SENS_WINDOWS = {"box": PNP_SENS_BOX, "hann": PNP_SENS_HANN}      # window names of pnp_estimate_sens
@@ -61,6 +64,8 @@ SIGNATURES = {
     "pnp_estimate_sens": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp, _fp, _vp]),
     "pnp_coil_compress_matrix": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _vp]),
     "pnp_coil_compress_apply": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_espirit_sens": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double,
+                                  C.c_int, _fp, _fp, _fp, _vp, _vp]),
     "pnp_snapshot_bytes": (C.c_size_t, [C.c_void_p]),
     "pnp_snapshot": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _vp, _vp]),
     "pnp_restore": (C.c_int, [C.c_void_p, _vp, _fp, _fp, _fp, _fp, _vp]),

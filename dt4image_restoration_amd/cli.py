@@ -26,7 +26,9 @@ layout has none):
     ... --coils 4 --cg-iters 8 eval|flex|mcts|fixed ...
     ... --coils 4 --sens estimate [--sens-window hann|box] [--sens-thresh 0.05] [--acs H W] --mask cartesian fixed ...
 
-    ... --coils 16 --compress 8 [--sens true|estimate] [--acs H W] eval|flex|mcts|fixed ...
+    ... --coils 8 --sens espirit [--espirit-kernel 6] [--espirit-sv 0.02] [--espirit-crop 0.9] [--espirit-iters 16] --mask cartesian fixed ...
+
+    ... --coils 16 --compress 8 [--sens true|estimate|espirit] [--acs H W] eval|flex|mcts|fixed ...
 
 `--compress V` mixes each set's C coils down to V virtual coils before the solver sees them (coil compression: the leading eigenvectors
 of the channel covariance of the calibration block, per slice, pnp_coil_compress_matrix / pnp_coil_compress_apply); every cost of the
@@ -36,7 +38,8 @@ the block's energy the kept virtual coils hold (mean over the set).
 
 `--sens estimate` does not hand the solver the maps that generated the measurements: the maps are estimated on the device from the
 fully sampled centre of each set's own y0 (pnp_estimate_sens; the block is the largest one the set's mask samples completely, or
---acs).  The initial iterate x0 stays the one the set brings.
+--acs).  `--sens espirit` estimates them by ESPIRiT instead (pnp_espirit_sens: at most 16 coils after --compress; the block is cropped to
+24 x 24; --sens-window and --sens-thresh apply as well).  The initial iterate x0 stays the one the set brings.
 
 Multi-GPU (BASELINE configs[2]): launch the same command under `python -m torch.distributed.run --nproc-per-node N
 --master-addr 127.0.0.1 -m dt4image_restoration_amd.cli ... eval|mcts|flex ...`: every rank takes a contiguous shard of each
@@ -110,17 +113,20 @@ def _compressed(args, env, batch):
 
 
 def _with_sens(args, env, batch):
-    """--compress, then --sens estimate: the batch with its coil maps replaced by the estimate from its own y0 and mask (on the device)."""
+    """--compress, then --sens estimate / espirit: the batch with its coil maps replaced by the estimate from its own y0 and mask (on the
+    device)."""
     batch = _compressed(args, env, batch)
-    if args.sens != "estimate":
+    if args.sens == "true":
         return batch
     from . import acquisition
     batch = dict(batch)
     try:
         batch["sens"] = acquisition.estimate_sens(env, batch["y0"], mask=batch["mask"], acs=args.acs, window=args.sens_window,
-                                                  thresh=args.sens_thresh)
+                                                  thresh=args.sens_thresh, method="espirit" if args.sens == "espirit" else "lowres",
+                                                  ksize=args.espirit_kernel, sv_thresh=args.espirit_sv, crop=args.espirit_crop,
+                                                  iters=args.espirit_iters)
     except ValueError as e:                                    # a mask without a sampled centre, a block that does not fit
-        raise SystemExit(f"--sens estimate: {e}")
+        raise SystemExit(f"--sens {args.sens}: {e}")
     return batch
 
 
@@ -149,7 +155,7 @@ def _sets(args, flex_target=None, env=None):
                 # the synthetic sets are radial; a --sens estimate run may ask for --mask cartesian, whose calibration block is H x the
                 # centre columns (None: the radial mask of make_problem, as every other run gets)
                 mask = acquisition.make_mask(args.size, args.size, accel, args.mask, args.seed) \
-                    if args.sens == "estimate" and args.mask != "radial" else None
+                    if args.sens != "true" and args.mask != "radial" else None
                 if args.acquire == "device":                   # make_problem's phantoms, mask and noise; the transforms on the GPU
                     gt = np.stack([synthetic.phantom(args.size, args.size, args.seed + accel + i) for i in range(a, b)])
                     sens = synthetic.coil_maps(args.coils, args.size, args.size).astype(np.complex64) if args.coils else None
@@ -225,8 +231,16 @@ def main(argv=None):
     ap.add_argument("--coils", type=int, default=0, help="multi-coil (SENSE) problems with this many analytic coil maps (1..32; "
                     "default 0: single-coil)")
     ap.add_argument("--cg-iters", type=int, default=8, help="conjugate-gradient iterations per step of a multi-coil problem (1..64)")
-    ap.add_argument("--sens", choices=("true", "estimate"), default="true", help="coil maps of a --coils run: the analytic maps that "
-                    "generated the measurements, or maps estimated on the device from the calibration block of each set's own y0")
+    ap.add_argument("--sens", choices=("true", "estimate", "espirit"), default="true", help="coil maps of a --coils run: the analytic maps that "
+                    "generated the measurements, or maps estimated on the device from the calibration block of each set's own y0 (estimate: "
+                    "the low-resolution estimate; espirit: ESPIRiT, at most 16 coils)")
+    ap.add_argument("--espirit-kernel", type=int, default=6, metavar="K", help="--sens espirit: side of the calibration kernels (2..8, coils * "
+                    "K^2 <= 512)")
+    ap.add_argument("--espirit-sv", type=float, default=0.02, help="--sens espirit: singular values above this fraction of the largest span "
+                    "the signal space (in (0, 1))")
+    ap.add_argument("--espirit-crop", type=float, default=0.9, help="--sens espirit: pixels whose eigenvalue is not above this get zero maps "
+                    "(in [0, 1))")
+    ap.add_argument("--espirit-iters", type=int, default=16, help="--sens espirit: power iterations per pixel (1..64)")
     ap.add_argument("--sens-window", choices=("hann", "box"), default="hann", help="window of the calibration block (--sens estimate)")
     ap.add_argument("--sens-thresh", type=float, default=0.05, help="--sens estimate: pixels whose root-sum-of-squares is not above this "
                     "fraction of the slice's largest get zero maps (in [0, 1))")
@@ -275,13 +289,25 @@ def main(argv=None):
             raise SystemExit(f"--compress must be 1..--coils = {args.coils}, got {args.compress}")
         if args.acs is not None and any(v < 2 or v % 2 for v in args.acs):
             raise SystemExit(f"--acs: sides must be even and >= 2, got {args.acs}")
-    if args.sens == "estimate":
+    if args.sens != "true":
         if not args.coils:
-            raise SystemExit("--sens estimate needs --coils: there are no coil maps to estimate on a single-coil problem")
+            raise SystemExit(f"--sens {args.sens} needs --coils: there are no coil maps to estimate on a single-coil problem")
         if not 0.0 <= args.sens_thresh < 1.0:
             raise SystemExit(f"--sens-thresh must be in [0, 1), got {args.sens_thresh}")
         if args.acs is not None and any(v < 2 or v % 2 for v in args.acs):
             raise SystemExit(f"--acs: sides must be even and >= 2, got {args.acs}")
+    if args.sens == "espirit":
+        c = args.compress or args.coils
+        if c > 16:
+            raise SystemExit(f"--sens espirit takes at most 16 coils, got {c}: add --compress V with V <= 16")
+        if not 2 <= args.espirit_kernel <= 8 or c * args.espirit_kernel ** 2 > 512:
+            raise SystemExit(f"--espirit-kernel must be 2..8 with coils * K^2 <= 512, got {args.espirit_kernel} at {c} coils")
+        if not 0.0 < args.espirit_sv < 1.0:
+            raise SystemExit(f"--espirit-sv must be in (0, 1), got {args.espirit_sv}")
+        if not 0.0 <= args.espirit_crop < 1.0:
+            raise SystemExit(f"--espirit-crop must be in [0, 1), got {args.espirit_crop}")
+        if not 1 <= args.espirit_iters <= 64:
+            raise SystemExit(f"--espirit-iters must be 1..64, got {args.espirit_iters}")
     if args.mode == "acquire":
         if args.coils:
             raise SystemExit("acquire --coils: refused - the reference's .mat layout this command writes has no coil axis")

@@ -116,6 +116,9 @@ struct pnp_engine {
     double2* cc_part = nullptr;  // [N, gram_chunks, C, C] per-workgroup Gram partials
     double2* cc_gram = nullptr;  // [N, C, C] Gram for callers that pass none
     size_t cc_part_cap = 0, cc_gram_cap = 0;   // capacities in complex128 elements
+    // ESPIRiT maps (pnp_espirit_sens): allocated inside its first call, grown by a call that needs more
+    void* es_ws = nullptr;       // per slice G and the vectors [2, np, np] complex128, then R [N, C, C, D, D] complex64, then nkept [N]
+    size_t es_cap = 0;           // capacity in bytes
     // profiling
     std::vector<EventPair> events;
     size_t ev_used = 0;
@@ -501,6 +504,20 @@ int cc_ensure(pnp_engine* e, size_t part_need, size_t gram_need) {
     return PNP_OK;
 }
 
+// The workspace of pnp_espirit_sens beyond cm_ensure's: one buffer of `need` bytes, replaced by a larger one when a call needs more.
+int es_ensure(pnp_engine* e, size_t need) {
+    if (need <= e->es_cap) return PNP_OK;
+    void* fresh = nullptr;
+    if (hipMalloc(&fresh, need) != hipSuccess)
+        return fail(PNP_ERR_NOMEM, "ESPIRiT workspace: %zu bytes (the handle keeps the workspace it had)", need);
+    if (e->es_ws) (void)hipDeviceSynchronize();   // no launch still reads the buffer being replaced
+    (void)hipFree(e->es_ws);
+    e->es_ws = fresh;
+    e->ws_bytes += need - e->es_cap;
+    e->es_cap = need;
+    return PNP_OK;
+}
+
 int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                   hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
@@ -633,6 +650,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->mc_y); (void)hipFree(e->mc_work); (void)hipFree(e->mc_sens); (void)hipFree(e->mc_vec); (void)hipFree(e->mc_part); (void)hipFree(e->mc_sc);
     (void)hipFree(e->cm_max); (void)hipFree(e->cm_rss);
     (void)hipFree(e->cc_part); (void)hipFree(e->cc_gram);
+    (void)hipFree(e->es_ws);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     delete e;
@@ -1127,6 +1145,66 @@ int pnp_coil_compress_apply(pnp_handle e, const float* in, int coils, const floa
     HIP_TRY(launch_coilcomp_apply((const float2*)in, (const float2*)cmat, cmat_n, coils, out_coils, (float2*)out, N, H, W, s));
     return PNP_OK;
     PNP_API_END("pnp_coil_compress_apply")
+}
+
+int pnp_espirit_sens(pnp_handle e, const float* y0, int coils, int acs_h, int acs_w, int ksize, double sv_thresh, double crop, int iters,
+                     int window, double thresh, int flags, float* sens, float* eval, float* kern, int32_t* nkept, void* stream) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call, and leaves the outputs untouched; scalar ranges first
+    const char* fn = "pnp_espirit_sens";
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (!(thresh >= 0.0) || !(thresh < 1.0)) return fail(PNP_ERR_INVALID, "%s: thresh must be finite and in [0, 1) (got %g)", fn, thresh);
+    if (!(crop >= 0.0) || !(crop < 1.0)) return fail(PNP_ERR_INVALID, "%s: crop must be finite and in [0, 1) (got %g)", fn, crop);
+    if (!(sv_thresh > 0.0) || !(sv_thresh < 1.0)) return fail(PNP_ERR_INVALID, "%s: sv_thresh must be in (0, 1) (got %g)", fn, sv_thresh);
+    if (iters < 1 || iters > 64) return fail(PNP_ERR_INVALID, "%s: iters must be 1..64 (got %d)", fn, iters);
+    if (window != PNP_SENS_BOX && window != PNP_SENS_HANN)
+        return fail(PNP_ERR_INVALID, "%s: window must be PNP_SENS_BOX or PNP_SENS_HANN (got %d)", fn, window);
+    if (coils < 1 || coils > PNP_ESPIRIT_MAX_COILS)
+        return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d); compress more channels first", fn, PNP_ESPIRIT_MAX_COILS, coils);
+    if (ksize < 2 || ksize > PNP_ESPIRIT_MAX_KSIZE) return fail(PNP_ERR_INVALID, "%s: ksize must be 2..%d (got %d)", fn, PNP_ESPIRIT_MAX_KSIZE, ksize);
+    if (coils * ksize * ksize > PNP_ESPIRIT_MAX_N)
+        return fail(PNP_ERR_INVALID, "%s: coils * ksize^2 must be <= %d (got %d * %d^2)", fn, PNP_ESPIRIT_MAX_N, coils, ksize);
+    if (acs_h < ksize || (acs_h & 1)) return fail(PNP_ERR_INVALID, "%s: acs_h must be even and >= ksize=%d (got %d)", fn, ksize, acs_h);
+    if (acs_w < ksize || (acs_w & 1)) return fail(PNP_ERR_INVALID, "%s: acs_w must be even and >= ksize=%d (got %d)", fn, ksize, acs_w);
+    if (!y0) return fail(PNP_ERR_INVALID, "%s: null y0", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (sens == y0) return fail(PNP_ERR_INVALID, "%s: sens must not alias y0", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (acs_h > H) return fail(PNP_ERR_INVALID, "%s: acs_h must be <= h=%d (got %d)", fn, H, acs_h);
+    if (acs_w > W) return fail(PNP_ERR_INVALID, "%s: acs_w must be <= w=%d (got %d)", fn, W, acs_w);
+    if (int rc = check_kspace_sizes(fn, e)) return rc;
+    if ((long long)N * coils > 65535) return fail(PNP_ERR_INVALID, "%s: n * coils must be <= 65535 (got %d * %d)", fn, N, coils);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    const size_t np = (size_t)espirit_padded(coils, ksize), D = (size_t)(2 * ksize - 1);
+    const size_t mat_bytes = (size_t)N * 2 * np * np * sizeof(double2), kern_bytes = (size_t)N * coils * coils * D * D * sizeof(float2);
+    if ((rc = cm_ensure(e, true))) return rc;
+    if ((rc = es_ensure(e, mat_bytes + kern_bytes + (size_t)N * 8))) return rc;
+    double2* const ws = (double2*)e->es_ws;
+    float2* const R = kern ? (float2*)kern : (float2*)((char*)e->es_ws + mat_bytes);
+    int* const nk = nkept ? (int*)nkept : (int*)((char*)e->es_ws + mat_bytes + kern_bytes);
+    float* const smax = e->cm_max + (size_t)N * pixel_chunks(H, W);
+    {   // the calibration part: Gram matrix, eigen-decomposition, kernel auto-correlation
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_espirit_gram((const float2*)y0, coils, acs_h, acs_w, ksize, ws, N, H, W, s));
+        HIP_TRY(launch_espirit_eig(ws, coils, ksize, N, s));
+        HIP_TRY(launch_espirit_kern(ws, coils, ksize, sv_thresh, R, nk, N, s));
+        p.end(3);
+    }
+    {   // l_c, rss and smax exactly as pnp_estimate_sens forms them
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_coilmap_window((const float2*)y0, (float2*)sens, acs_h, acs_w, window == PNP_SENS_HANN, N, coils, H, W, s));
+    }
+    if ((rc = plain_fft2(e, (float2*)sens, (float2*)sens, N * coils, 1, s))) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_coilmap_rss((const float2*)sens, coils, e->cm_rss, e->cm_max, N, H, W, s));
+    HIP_TRY(launch_coilmap_max(e->cm_max, smax, N, H, W, s));
+    HIP_TRY(launch_espirit_pixels((float2*)sens, R, e->cm_rss, smax, coils, ksize, iters, (float)crop, (float)thresh, eval, N, H, W, s));
+    p.end(3);
+    return PNP_OK;
+    PNP_API_END("pnp_espirit_sens")
 }
 
 size_t pnp_snapshot_bytes(pnp_handle e) {

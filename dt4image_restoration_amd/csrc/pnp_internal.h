@@ -282,4 +282,15 @@ hipError_t launch_coilcomp_eig(const double2* gram, int C, float2* cmat, float* 
 // out[n, v] = sum_c cmat[n or 0][v][c] in[n, c], v < V; in: [N, C, H, W], out: [N, V, H, W]
 hipError_t launch_coilcomp_apply(const float2* in, const float2* cmat, int cmat_n, int C, int V, float2* out, int N, int H, int W, hipStream_t s);
 
+// ---- ESPIRiT coil maps (espirit_kernels.hip) --------------------------------------------------------
+// np: the side of the calibration Gram matrix, n = C k^2 rounded up to even.  ws: per slice G [np][np] then the transposed vectors [np][np], complex128
+inline int espirit_padded(int C, int k) { return (C * k * k + 1) & ~1; }
+hipError_t launch_espirit_gram(const float2* y, int C, int acs_h, int acs_w, int k, double2* ws, int N, int H, int W, hipStream_t s);
+hipError_t launch_espirit_eig(double2* ws, int C, int k, int N, hipStream_t s);              // one workgroup per slice; eigenvalues on G's diagonal
+// kern: [N, C, C, 2k-1, 2k-1] complex64, nkept: [N]
+hipError_t launch_espirit_kern(const double2* ws, int C, int k, double sv_thresh, float2* kern, int* nkept, int N, hipStream_t s);
+// sens: [N, C, H, W], in the low-resolution coil images, out the maps; rss [N, H, W], smax [N] of the coil map kernels; eval [N, H, W] or nullptr
+hipError_t launch_espirit_pixels(float2* sens, const float2* kern, const float* rss, const float* smax, int C, int k, int iters, float crop,
+                                 float thresh, float* eval, int N, int H, int W, hipStream_t s);
+
 }  // namespace pnp

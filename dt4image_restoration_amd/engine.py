@@ -312,6 +312,41 @@ class PnPEngine:
                                               sens.data_ptr(), _ptr(rss), self._stream()), "pnp_estimate_sens")
         return (sens, rss) if return_rss else sens
 
+    def espirit_sens(self, y0: torch.Tensor, acs: Tuple[int, int], ksize: int = 6, sv_thresh: float = 0.02, crop: float = 0.9, iters: int = 16,
+                     window: str = "hann", thresh: float = 0.0, return_eval: bool = False, return_kernels: bool = False):
+        """ESPIRiT coil sensitivity maps from the fully sampled calibration block of multi-coil k-space (pnp_espirit_sens): y0 complex64
+        [N,C,H,W] in the centred layout, C <= 16 (compress more channels first), acs = (acs_h, acs_w) the even sides of the centred block,
+        ksize the side of the calibration kernels (C ksize^2 <= 512; a block with fewer (acs_h - ksize + 1)(acs_w - ksize + 1) windows than
+        C ksize^2 calibrates badly).  The signal space of the calibration matrix keeps the singular values above sv_thresh times the
+        largest; per pixel the dominant eigenvector comes from `iters` power steps started at the low-resolution estimate of
+        `estimate_sens` (same window), its phase is set so that the image stays real, and pixels whose eigenvalue is not above crop - or
+        whose low-resolution rss is not above thresh * (the slice's largest) - get zero maps.  Returns complex64 [N,C,H,W] per-slice maps
+        for `reset(..., sens=)`; with return_eval also the eigenvalue map float32 [N,H,W]; with return_kernels also (kern complex64
+        [N,C,C,2 ksize - 1,2 ksize - 1], nkept int32 [N]).  Does not change the engine's mode or its installed constants."""
+        if y0.dim() != 4 or y0.shape[0] != self.n or tuple(y0.shape[-2:]) != (self.h, self.w):
+            raise ValueError(f"y0: expected [{self.n},C,{self.h},{self.w}], got {tuple(y0.shape)}")
+        coils = int(y0.shape[1])
+        y0 = self._chk(y0, torch.complex64, self.n * coils * self.h * self.w, "y0")
+        if window not in _lib.SENS_WINDOWS:
+            raise ValueError(f"window must be one of {tuple(_lib.SENS_WINDOWS)}, got {window!r}")
+        if not 1 <= coils <= _lib.PNP_ESPIRIT_MAX_COILS:
+            raise ValueError(f"espirit_sens takes 1..{_lib.PNP_ESPIRIT_MAX_COILS} coils, got {coils}: compress the channels first")
+        ksize, iters = int(ksize), int(iters)
+        if not 2 <= ksize <= _lib.PNP_ESPIRIT_MAX_KSIZE or coils * ksize * ksize > _lib.PNP_ESPIRIT_MAX_N:
+            raise ValueError(f"ksize must be 2..{_lib.PNP_ESPIRIT_MAX_KSIZE} with coils * ksize^2 <= {_lib.PNP_ESPIRIT_MAX_N}, got {ksize} at "
+                             f"{coils} coils")
+        acs_h, acs_w = (int(v) for v in acs)
+        sens = torch.empty_like(y0)
+        ev = torch.empty((self.n, self.h, self.w), dtype=torch.float32, device=self.device) if return_eval else None
+        d = 2 * ksize - 1
+        kern = torch.empty((self.n, coils, coils, d, d), dtype=torch.complex64, device=self.device) if return_kernels else None
+        nkept = torch.empty((self.n,), dtype=torch.int32, device=self.device) if return_kernels else None
+        _lib.check(self.lib.pnp_espirit_sens(self._h, y0.data_ptr(), coils, acs_h, acs_w, ksize, float(sv_thresh), float(crop), iters,
+                                             _lib.SENS_WINDOWS[window], float(thresh), 0, sens.data_ptr(), _ptr(ev), _ptr(kern), _ptr(nkept),
+                                             self._stream()), "pnp_espirit_sens")
+        out = (sens,) + ((ev,) if return_eval else ()) + ((kern, nkept) if return_kernels else ())
+        return out if len(out) > 1 else sens
+
     def coil_compress_matrix(self, y0: torch.Tensor, acs: Tuple[int, int], return_gram: bool = False):
         """Coil compression matrices from the calibration block of multi-coil k-space (pnp_coil_compress_matrix): y0 complex64
         [N,C,H,W] in the centred layout, C <= 64, acs = (acs_h, acs_w) the even sides of the centred block.  Per slice the C x C channel

@@ -273,7 +273,7 @@ int pnp_acquire_mc(pnp_handle h, const float* gt, const float* sens, int coils, 
  * squared and summed in float64 in coil order; the square root is taken in float64 and rounded to float32 once.  The threshold product and the
  * division are float32 (an IEEE divide).  On the kept set the maps have unit root-sum-of-squares, so they absorb the object's slowly varying
  * phase and the image left to restore is close to real - the iterate this engine keeps.  ESPIRiT (calibration-matrix SVD, per-pixel
- * eigen-decomposition) is not built.
+ * eigen-decomposition) is pnp_espirit_sens below; it starts from these low-resolution coil images.
  *   y0     : DEVICE complex64 [N,C,H,W], centred layout (what pnp_reset_mc takes); read inside the block only: the block must be fully sampled
  *   coils  : 1..PNP_MC_MAX_COILS;   acs_h, acs_w : even, 2 <= acs_h <= H, 2 <= acs_w <= W;   window : PNP_SENS_BOX or PNP_SENS_HANN
  *   thresh : in [0, 1);   flags : reserved, must be 0
@@ -339,6 +339,60 @@ int pnp_estimate_sens(pnp_handle h, const float* y0, int coils, int acs_h, int a
 int pnp_coil_compress_matrix(pnp_handle h, const float* y0, int coils, int acs_h, int acs_w, int flags, float* cmat, float* eig,
                              double* gram /* may be NULL */, void* stream);
 int pnp_coil_compress_apply(pnp_handle h, const float* in, int coils, const float* cmat, int cmat_n, int out_coils, float* out, void* stream);
+
+/* ESPIRiT coil sensitivity maps: the maps as the dominant eigenvector, per pixel, of an operator built from the null space of the calibration
+ * matrix, instead of the band-limited low-resolution estimate of pnp_estimate_sens (the reference has no counterpart).  Per slice, with the
+ * centred acs_h x acs_w block B of pnp_estimate_sens, kernel side k = ksize, C = coils, n = C k^2, D = 2 k - 1:
+ *   Calibration Gram matrix.  The rows of A are all (acs_h - k + 1)(acs_w - k + 1) sliding k x k x C windows of the block,
+ *     A[(wy, wx)][(a, iy, ix)] = B[a][wy + iy][wx + ix], column index a k^2 + iy k + ix;  G = A^H A (n x n Hermitian).  The terms are the float32
+ *     components of y0, their products are exact in float64, and every entry of the lower triangle is summed in float64 over the windows in
+ *     row-major window order (re += xr yr; re += xi yi; im += xr yi; im -= xi yr for conj(x) y), one thread per entry, then mirrored; the diagonal
+ *     is real.  No atomics.
+ *   Eigen-decomposition.  G = V diag(lambda) V^H by the cyclic Jacobi method of pnp_coil_compress_matrix in float64: the same rotation formula,
+ *     round-robin order and two-phase round, the same stop rule off(G)_F <= 1e-14 trace(G) before every sweep, at most 40 sweeps (the 64- to
+ *     288-column matrices of the tests stop after 11 to 13).  One workgroup per slice; G and the vectors live in the slice's workspace in device
+ *     memory (n is padded to even).  The signal space is {j : lambda_j > sv_thresh^2 lambda_0}, lambda_0 the largest eigenvalue; its size nkept is
+ *     found on the device, no host read.  Only the projector P = V_kept V_kept^H enters what follows, so neither the order nor the phase of the
+ *     vectors matters (no sort or phase step is run) and clustered eigenvalues leave the result well defined.
+ *   Kernel auto-correlation.  R[a][b][d] = (1 / k^2) sum over {i - j = d} of conj(P[(a, i), (b, j)]), d over the D x D offsets: summed in float64
+ *     (kept vectors in index order, inside them the pairs in (iy, ix) order), divided by k^2 and rounded to complex64 ONCE: kern.
+ *   Per-pixel matrix.  With the centred pixel q = (py - H/2, px - W/2):  G_q[a][b] = sum_d R[a][b][d] exp(+2 pi i (dy qy / H + dx qx / W)), C x C
+ *     Hermitian; with this sign and normalisation the true map vector S(q) is an eigenvector of G_q with eigenvalue 1.  float32 from here on: the
+ *     twiddles are the float64 values of exactly reduced arguments (dy qy mod H, dx qx mod W in integers) rounded to float32 once; d_y is contracted
+ *     first (dy ascending), then d_x (dx ascending), every complex product-sum as four fused multiply-adds from +0; only b <= a is formed, the
+ *     upper triangle is its conjugate and the diagonal's imaginary part is dropped.
+ *   Dominant eigenpair.  iters power steps v <- G_q v / ||G_q v|| (the squared norm by fused multiply-adds in coil order, one square root, one
+ *     IEEE reciprocal, a product per component; a zero G_q v gives v = 0) from v = l / rss, where l_c = ifft_c(win * block) and rss are the
+ *     low-resolution coil images and their root-sum-of-squares exactly as in pnp_estimate_sens (same window argument; rss = 0 gives v = 0 and
+ *     zero maps).  eval = lambda(q) = Re(v^H G_q v) after the last step.  A fixed count: no data-dependent branch.
+ *   Phase.  This engine keeps a real iterate, so the maps absorb the object's phase as the low-resolution maps do:  p = sum_c conj(v_c) l_c,
+ *     phi = p / |p| (1 when p is exactly 0), S_c = v_c phi.  (Not the usual "coil 0 real" convention, which would leave a complex image.)
+ *   Kept set.  sens_c = S_c where lambda(q) > float32(crop) and rss > 0 and rss > float32(thresh) * smax_n (rss, smax_n of pnp_estimate_sens), else
+ *     0; thresh = 0 leaves only the crop rule.  On the kept set sum_c |S_c|^2 = 1 to float32 rounding.
+ *   y0     : DEVICE complex64 [N,C,H,W], centred layout; read inside the block only: the block must be fully sampled
+ *   coils  : 1..PNP_ESPIRIT_MAX_COILS (acquisitions with more channels compress first: pnp_coil_compress_*);   ksize : 2..PNP_ESPIRIT_MAX_KSIZE;
+ *            coils * ksize^2 <= PNP_ESPIRIT_MAX_N;   acs_h, acs_w : even, ksize <= acs_h <= H, ksize <= acs_w <= W.  A block with fewer windows
+ *            than n calibrates badly (the Gram matrix is rank deficient and the signal space is not separated)
+ *   sv_thresh : in (0, 1);   crop : in [0, 1);   iters : 1..64;   window, thresh : as pnp_estimate_sens;   flags : reserved, must be 0
+ *   sens   : DEVICE complex64 [N,C,H,W] out, must not alias y0.  The window and inverse-transform launches of pnp_estimate_sens run in it first and
+ *            the pixel kernel reads l_c from it and writes S_c to it in place: there is no [N,C,H,W] workspace
+ *   eval   : DEVICE float32 [N,H,W] out, or NULL;   kern : DEVICE complex64 [N,C,C,D,D] out, or NULL;   nkept : DEVICE int32 [N] out, or NULL
+ * Any handle kind; the call changes neither the handle's mode nor its installed constants.  Sizes the k-space stage accepts, n * coils <= 65535.
+ * A slice's bits depend on its own y0 and the arguments only: not on N, its place in the batch, the stream or the handle kind; no atomics.
+ * SETUP-TIME SEMANTICS, as pnp_coil_compress_matrix: the first call allocates the workspace of pnp_estimate_sens with a NULL rss
+ * (4 n ceil(H W / 2048) + 4 n + 4 n H W bytes, unless an earlier call did) and n (32 np^2 + 8 C^2 D^2 + 8) bytes (np = C k^2 rounded up to even: G
+ * and the vectors, R, nkept), inside the call, all-or-nothing (on PNP_ERR_NOMEM the handle keeps the workspace it had), counted by
+ * pnp_workspace_bytes.  A later call allocates only if it needs more than any call before it, and then waits for the device; every other call
+ * allocates nothing and is asynchronous.  Calls on one handle are stream-ordered.
+ * Every argument error (null handle, y0 or sens, sens == y0, coils outside 1..16, ksize outside 2..8, coils * ksize^2 > 512, acs_h / acs_w odd,
+ * below ksize or above the handle's H / W, sv_thresh outside (0, 1), crop or thresh outside [0, 1), iters outside 1..64, an unknown window,
+ * flags != 0, n * coils > 65535) is reported before any HIP call and leaves the outputs untouched. */
+#define PNP_ESPIRIT_MAX_COILS 16
+#define PNP_ESPIRIT_MAX_KSIZE 8
+#define PNP_ESPIRIT_MAX_N     512
+int pnp_espirit_sens(pnp_handle h, const float* y0, int coils, int acs_h, int acs_w, int ksize, double sv_thresh, double crop, int iters,
+                     int window, double thresh, int flags, float* sens, float* eval /* [N,H,W], may be NULL */,
+                     float* kern /* complex64 [N,C,C,2k-1,2k-1], may be NULL */, int32_t* nkept /* [N], may be NULL */, void* stream);
 
 /* ---- tree search support --------------------------------------------------------------------- */
 
