@@ -24,6 +24,10 @@ PNP_CC_MAX_COILS = 64
 PNP_ESPIRIT_MAX_COILS = 16
 PNP_ESPIRIT_MAX_KSIZE = 8
 PNP_ESPIRIT_MAX_N = 512
+PNP_TV_MAX_ITERS = 64
+PNP_PRIOR_UNET = 0
+PNP_PRIOR_TV = 1
+PRIORS = {"unet": PNP_PRIOR_UNET, "tv": PNP_PRIOR_TV}      # prior names of pnp_set_prior
 PNP_SENS_BOX = 0
 PNP_SENS_HANN = 1
 SENS_WINDOWS = {"box": PNP_SENS_BOX, "hann": PNP_SENS_HANN}      # window names of pnp_estimate_sens
@@ -49,6 +53,9 @@ SIGNATURES = {
     "pnp_set_kspace": (C.c_int, [C.c_void_p, _fp, _u8p, C.c_int, _vp]),
     "pnp_step": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _u8p, _vp]),
     "pnp_denoise": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),
+    "pnp_tv_denoise": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, _vp]),
+    "pnp_set_prior": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int]),
+    "pnp_get_prior": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "pnp_fft2c": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "pnp_prox_dual": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _fp, _vp]),
     "pnp_psnr": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),

@@ -119,6 +119,12 @@ struct pnp_engine {
     // ESPIRiT maps (pnp_espirit_sens): allocated inside its first call, grown by a call that needs more
     void* es_ws = nullptr;       // per slice G and the vectors [2, np, np] complex128, then R [N, C, C, D, D] complex64, then nkept [N]
     size_t es_cap = 0;           // capacity in bytes
+    // the prior of pnp_step (pnp_set_prior) and the total-variation denoiser's workspace (allocated inside the first call that runs it)
+    int prior = PNP_PRIOR_UNET;
+    double tv_scale = 1.0;       // as given; applied as float32
+    int tv_iters = 20;
+    bool tv_naive = false;       // PNP_TV_NAIVE=1 at pnp_create: one launch per iteration (the fused kernel's check and timing baseline)
+    float2* tv_p = nullptr;      // [N,H,W] (py, px): the hand-over plane between launches; the other plane of the ping-pong is d_work
     // profiling
     std::vector<EventPair> events;
     size_t ev_used = 0;
@@ -518,6 +524,51 @@ int es_ensure(pnp_engine* e, size_t need) {
     return PNP_OK;
 }
 
+// The workspace of the total-variation denoiser: one (py, px) plane, never replaced.
+int tv_ensure(pnp_engine* e) {
+    if (e->tv_p) return PNP_OK;
+    const size_t bytes = (size_t)e->cfg.n * e->cfg.h * e->cfg.w * sizeof(float2);
+    void* fresh = nullptr;
+    if (hipMalloc(&fresh, bytes) != hipSuccess)
+        return fail(PNP_ERR_NOMEM, "total-variation workspace: %zu bytes (the handle keeps the workspace it had)", bytes);
+    e->tv_p = (float2*)fresh;
+    e->ws_bytes += bytes;
+    return PNP_OK;
+}
+
+// out = TV(v, scale * lam, iters), v = the plane `v` or Re z - Re u.  p travels between launches through two planes in turn: the
+// data-fidelity stage's scratch plane (free while the x-update runs; calls on one handle are stream-ordered) and tv_p.  No launch writes
+// a plane that another workgroup of it reads: when out aliases v the last fused launch stores p and tv_close_kernel ends the call.
+int run_tv(pnp_engine* e, const float* v, const float2* z, const float2* u, const float* lam, float scale, const float* tact, int iters,
+           float* out, hipStream_t s) {
+    const int N = e->cfg.n;
+    if (int rc = tv_ensure(e)) return rc;
+    float2* const buf[2] = {e->d_work, e->tv_p};
+    TvArgs a{};
+    a.v = v; a.z = z; a.u = u; a.lam = lam; a.scale = scale; a.tact = tact; a.H = e->cfg.h; a.W = e->cfg.w;
+    Prof p(e, s, PROF_OTHER, -1, true, true);
+    int launches = 0;
+    const bool alias = v != nullptr && v == out;
+    const int L = e->tv_naive ? iters : (iters + kTvT - 1) / kTvT;
+    for (int l = 0; l < L; ++l) {
+        a.p_in = l == 0 ? nullptr : buf[l & 1];
+        a.p_out = buf[(l + 1) & 1];
+        a.out = nullptr;
+        ++launches;
+        if (e->tv_naive) { HIP_TRY(launch_tv_iter(a, N, s)); continue; }
+        a.iters = iters - l * kTvT < kTvT ? iters - l * kTvT : kTvT;
+        if (l == L - 1 && !alias) { a.p_out = nullptr; a.out = out; }
+        HIP_TRY(launch_tv_fused(a, N, s));
+    }
+    if (e->tv_naive || alias) {
+        a.p_in = buf[L & 1]; a.p_out = nullptr; a.out = out;
+        ++launches;
+        HIP_TRY(launch_tv_close(a, N, s));
+    }
+    p.end(launches);
+    return PNP_OK;
+}
+
 int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                   hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
@@ -626,6 +677,7 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     e->cfg = *cfg;
     e->tune = tune;
     e->dplan = plan;
+    if (const char* v = getenv("PNP_TV_NAIVE")) e->tv_naive = atoi(v) != 0;
     int rc;
     {
         DeviceGuard g(cfg->device);
@@ -651,6 +703,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->cm_max); (void)hipFree(e->cm_rss);
     (void)hipFree(e->cc_part); (void)hipFree(e->cc_gram);
     (void)hipFree(e->es_ws);
+    (void)hipFree(e->tv_p);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     delete e;
@@ -769,12 +822,15 @@ int pnp_step(pnp_handle e, const float* mu, const float* sigma_d, const float* t
              float* t_state, uint8_t* done, void* stream) {
     PNP_API_BEGIN
     if (!e || !mu || !sigma_d || !x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_step: null argument");
-    if (!e->weights_loaded) return fail(PNP_ERR_STATE, "pnp_step: denoiser weights not loaded (pnp_load_unet_weights)");
+    const bool tv = e->prior == PNP_PRIOR_TV;
+    if (!tv && !e->weights_loaded) return fail(PNP_ERR_STATE, "pnp_step: denoiser weights not loaded (pnp_load_unet_weights)");
     if (!e->reset_done) return fail(PNP_ERR_STATE, "pnp_step: pnp_reset has not been called");
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    if ((rc = run_unet(e, nullptr, (const float2*)z, (const float2*)u, sigma_d, t_action, x, s))) return rc;
+    if (tv) {
+        if ((rc = run_tv(e, nullptr, (const float2*)z, (const float2*)u, sigma_d, (float)e->tv_scale, t_action, e->tv_iters, x, s))) return rc;
+    } else if ((rc = run_unet(e, nullptr, (const float2*)z, (const float2*)u, sigma_d, t_action, x, s))) return rc;
     if ((rc = run_prox_dual(e, mu, t_action, x, (float2*)z, (float2*)u, s))) return rc;
     if (t_state || done) {
         Prof p(e, s, PROF_OTHER, -1);
@@ -791,6 +847,55 @@ int pnp_denoise(pnp_handle e, const float* x_in, const float* sigma, float* out,
     PNP_ON_DEVICE(e);
     return run_unet(e, x_in, nullptr, nullptr, sigma, nullptr, out, (hipStream_t)stream);
     PNP_API_END("pnp_denoise")
+}
+
+int pnp_tv_denoise(pnp_handle e, const float* x_in, const float* lam, int iters, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_tv_denoise";
+    if (iters < 1 || iters > PNP_TV_MAX_ITERS) return fail(PNP_ERR_INVALID, "%s: iters must be 1..%d (got %d)", fn, PNP_TV_MAX_ITERS, iters);
+    if (!x_in) return fail(PNP_ERR_INVALID, "%s: null x_in", fn);
+    if (!lam) return fail(PNP_ERR_INVALID, "%s: null lam", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    PNP_ON_DEVICE(e);
+    return run_tv(e, x_in, nullptr, nullptr, lam, 1.0f, nullptr, iters, out, (hipStream_t)stream);
+    PNP_API_END("pnp_tv_denoise")
+}
+
+int pnp_set_prior(pnp_handle e, int prior, double tv_scale, int tv_iters) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_set_prior";
+    if (prior != PNP_PRIOR_UNET && prior != PNP_PRIOR_TV)
+        return fail(PNP_ERR_INVALID, "%s: prior must be PNP_PRIOR_UNET or PNP_PRIOR_TV (got %d)", fn, prior);
+    if (prior == PNP_PRIOR_TV) {
+        if (!(tv_scale >= 0.0) || !std::isfinite(tv_scale)) return fail(PNP_ERR_INVALID, "%s: tv_scale must be finite and >= 0 (got %g)", fn, tv_scale);
+        if (tv_iters < 1 || tv_iters > PNP_TV_MAX_ITERS)
+            return fail(PNP_ERR_INVALID, "%s: tv_iters must be 1..%d (got %d)", fn, PNP_TV_MAX_ITERS, tv_iters);
+    }
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (prior == PNP_PRIOR_UNET) {
+        if (e->cfg.flags & PNP_FLAG_NO_DENOISER)
+            return fail(PNP_ERR_STATE, "%s: PNP_PRIOR_UNET on a handle created with PNP_FLAG_NO_DENOISER", fn);
+        e->prior = PNP_PRIOR_UNET;                             // (the TV parameters stay as they were: they are not read under this prior)
+        return PNP_OK;
+    }
+    e->prior = PNP_PRIOR_TV;
+    e->tv_scale = tv_scale;
+    e->tv_iters = tv_iters;
+    return PNP_OK;
+    PNP_API_END("pnp_set_prior")
+}
+
+int pnp_get_prior(pnp_handle e, int* prior, double* tv_scale, int* tv_iters) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_get_prior";
+    if (!prior || !tv_scale || !tv_iters) return fail(PNP_ERR_INVALID, "%s: null pointer", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    *prior = e->prior;
+    *tv_scale = e->tv_scale;
+    *tv_iters = e->tv_iters;
+    return PNP_OK;
+    PNP_API_END("pnp_get_prior")
 }
 
 int pnp_fft2c(pnp_handle e, const float* in, float* out, int batch, int hh, int ww, int inverse, void* stream) {

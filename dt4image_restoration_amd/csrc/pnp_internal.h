@@ -293,4 +293,25 @@ hipError_t launch_espirit_kern(const double2* ws, int C, int k, double sv_thresh
 hipError_t launch_espirit_pixels(float2* sens, const float2* kern, const float* rss, const float* smax, int C, int k, int iters, float crop,
                                  float thresh, float* eval, int N, int H, int W, hipStream_t s);
 
+// ---- total-variation prior (tv_kernels.hip) ---------------------------------------------------------
+// The fused kernel's plan: kTvT iterations per launch over a kTvRegion^2 region, of which the kTvTile^2 tile is stored
+static constexpr int kTvT = 10, kTvRegion = 128, kTvTile = kTvRegion - 2 * kTvT - 1;
+struct TvArgs {
+    const float* v;        // [N,H,W] input plane, or nullptr: Re z - Re u
+    const float2* z;       // [N,H,W] complex planes of pnp_step, or nullptr
+    const float2* u;
+    const float* lam;      // [N]; the slice's weight is scale * lam[n]
+    float scale;
+    const float* tact;     // [N] stop actions or nullptr; slice skipped when tact[n] > 0.5
+    const float2* p_in;    // [N,H,W] (py, px) of the iteration before, or nullptr: p = 0
+    float2* p_out;         // [N,H,W] or nullptr (fused kernel: p is not stored)
+    float* out;            // [N,H,W] or nullptr (fused kernel: no closing divergence)
+    int H, W;
+    int iters;             // fused kernel: iterations of this launch, 1..kTvT
+    int tiles_x, tiles_y;  // filled by the launchers
+};
+hipError_t launch_tv_fused(TvArgs a, int N, hipStream_t s);   // a.iters iterations from p_in, then p_out and / or out
+hipError_t launch_tv_iter(TvArgs a, int N, hipStream_t s);    // ONE iteration p_in -> p_out, a thread per pixel (p_in must not be p_out)
+hipError_t launch_tv_close(TvArgs a, int N, hipStream_t s);   // out = clamp(v - lam div p_in); out may alias v
+
 }  // namespace pnp

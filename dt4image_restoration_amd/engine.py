@@ -202,6 +202,38 @@ class PnPEngine:
         _lib.check(self.lib.pnp_denoise(self._h, x.data_ptr(), sigma.data_ptr(), out.data_ptr(), self._stream()), "pnp_denoise")
         return out
 
+    def tv_denoise(self, x: torch.Tensor, lam: torch.Tensor, iters: int = 20, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Isotropic total-variation denoiser (pnp_tv_denoise): `iters` steps of Chambolle's dual projection, then clamp(x - lam div p, 0, 1).
+        x float32 [N,1,H,W], lam float32 [N] (0 gives the clamp alone); out may be x.  Any engine kind, any size the engine takes."""
+        nhw = self.n * self.h * self.w
+        self._chk(x, torch.float32, nhw, "x"); self._chk(lam, torch.float32, self.n, "lam")
+        iters = int(iters)
+        if not 1 <= iters <= _lib.PNP_TV_MAX_ITERS:
+            raise ValueError(f"iters must be 1..{_lib.PNP_TV_MAX_ITERS}, got {iters}")
+        if out is None:
+            out = torch.empty_like(x)
+        self._chk(out, torch.float32, nhw, "out")
+        _lib.check(self.lib.pnp_tv_denoise(self._h, x.data_ptr(), lam.data_ptr(), iters, out.data_ptr(), self._stream()), "pnp_tv_denoise")
+        return out
+
+    def set_prior(self, prior: str, tv_scale: float = 1.0, tv_iters: int = 20) -> None:
+        """The x-update of `step` (pnp_set_prior): "unet" (the default) or "tv" - total variation with weight tv_scale * sigma_d and
+        tv_iters dual steps, which needs no weights and also runs on an engine built with denoiser=False."""
+        if prior not in _lib.PRIORS:
+            raise ValueError(f"prior must be one of {tuple(_lib.PRIORS)}, got {prior!r}")
+        _lib.check(self.lib.pnp_set_prior(self._h, _lib.PRIORS[prior], float(tv_scale), int(tv_iters)), "pnp_set_prior")
+
+    @property
+    def prior(self) -> str:
+        """"unet" or "tv" (pnp_get_prior)."""
+        return self.prior_settings()[0]
+
+    def prior_settings(self) -> Tuple[str, float, int]:
+        """(prior, tv_scale, tv_iters) as the handle holds them."""
+        pr, sc, it = C.c_int(), C.c_double(), C.c_int()
+        _lib.check(self.lib.pnp_get_prior(self._h, C.byref(pr), C.byref(sc), C.byref(it)), "pnp_get_prior")
+        return {v: k for k, v in _lib.PRIORS.items()}[pr.value], float(sc.value), int(it.value)
+
     def fft2c(self, img: torch.Tensor, inverse: bool = False) -> torch.Tensor:
         if img.dtype != torch.complex64 or img.shape[-2:] != (self.h, self.w):
             raise ValueError(f"fft2c: expected complex64 [...,{self.h},{self.w}], got {img.dtype} {tuple(img.shape)}")

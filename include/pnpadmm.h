@@ -132,6 +132,59 @@ int pnp_step(pnp_handle h, const float* mu, const float* sigma_d, const float* t
  * (may alias), sigma DEVICE float32 [N]. */
 int pnp_denoise(pnp_handle h, const float* x_in, const float* sigma, float* out, void* stream);
 
+/* A second plug-in regulariser beside the U-Net: isotropic total variation by Chambolle's dual projection (the reference has one prior only,
+ * its U-Net; this is the classical baseline a PnP result is reported against).  Per slice, with v the input image [H, W], lam its weight,
+ * K = iters, tau = 1/8, forward differences with Neumann ends ((Dy a)[i,j] = a[i+1,j] - a[i,j] for i < H-1 and 0 on the last row, Dx likewise)
+ * and div = -D^T:
+ *     not (lam > 0):  out = min(max(v, 0), 1)                                (lam = 0; a negative or NaN weight is treated alike)
+ *     else:  w = v * (1 / lam);  py = px = 0;
+ *            K times (Jacobi: every pixel reads the p of the iteration before):
+ *                d = div(py, px) - w;   gy = Dy d;   gx = Dx d;   r = 1 / (1 + tau sqrt(gy^2 + gx^2));
+ *                py = (py + tau gy) r;  px = (px + tau gx) r
+ *            out = min(max(v - lam div(py, px), 0), 1)
+ * float32 throughout, every operation one IEEE operation in this order (fma = one rounding; p outside the image reads as 0):
+ *     rl  = 1 / lam                                                          (one IEEE reciprocal per slice)
+ *     d(i,j) = ((py[i,j] - py[i-1,j]) + (px[i,j] - px[i,j-1])) - v[i,j] * rl (the product is rounded, then subtracted)
+ *     gy  = i < H-1 ? d(i+1,j) - d(i,j) : 0;     gx = j < W-1 ? d(i,j+1) - d(i,j) : 0
+ *     s   = fma(gx, gx, gy * gy);    den = fma(tau, sqrt(s), 1);    r = 1 / den              (IEEE square root and reciprocal)
+ *     py  = fma(tau, gy, py) * r;    px = fma(tau, gx, px) * r
+ *     out = min(max(fma(-lam, (py[i,j] - py[i-1,j]) + (px[i,j] - px[i,j-1]), v[i,j]), 0), 1)
+ * The result at a pixel is a pure function of its slice's v, lam and K: it depends neither on N, the slice's place in the batch, the stream,
+ * the handle kind, nor on how the kernels cut the image into tiles; no atomics, no reductions.  A constant image comes back bit for bit
+ * (clamped).  The clamp mirrors pnp_denoise.
+ *   x_in, out : DEVICE float32 [N,1,H,W]; they may alias (exactly, not partly), as in pnp_denoise
+ *   lam       : DEVICE float32 [N];   iters : 1..PNP_TV_MAX_ITERS
+ * Any handle kind (PNP_FLAG_NO_DENOISER, bf16 convs, single- or multi-coil mode) and any size pnp_create accepts; the call changes neither the
+ * handle's mode nor its installed constants.
+ * SETUP-TIME SEMANTICS, as pnp_estimate_sens: the first call that runs the operator on a handle (this one, or pnp_step under PNP_PRIOR_TV)
+ * allocates 8 n H W bytes (one plane of (py, px) pairs through which launches hand the dual over; the second plane of the ping-pong is the
+ * data-fidelity stage's scratch) inside the call, all-or-nothing (on PNP_ERR_NOMEM the handle keeps the workspace it had), counted by
+ * pnp_workspace_bytes; later calls allocate nothing and are asynchronous.  Calls on one handle are stream-ordered (they share that workspace).
+ * PNP_TV_NAIVE=1 in the environment at pnp_create selects one launch per iteration instead of the fused kernel (same bits; a check and a
+ * timing baseline, not a mode).
+ * Every argument error (null handle or pointer, iters outside 1..64) is reported before any HIP call and leaves the outputs untouched. */
+#define PNP_TV_MAX_ITERS 64
+int pnp_tv_denoise(pnp_handle h, const float* x_in, const float* lam, int iters, float* out, void* stream);
+
+/* The prior of pnp_step's x-update, per handle.  PNP_PRIOR_UNET (the default: a handle that never calls the setter is what it always was) runs
+ * the U-Net of pnp_denoise.  PNP_PRIOR_TV computes, in place of the U-Net forward,
+ *     x = TV(float32(Re z - Re u), lam_n = float32(tv_scale) * sigma_d[n], tv_iters)           (the operator of pnp_tv_denoise)
+ * read directly from the two complex planes (no real copy is made first); the k-space stage then runs as before, closed form or CG, whichever
+ * constants are installed.  Slices with t_action > 0.5 keep x, z, u, t_state bit for bit; done and t_state behave as before.  Under
+ * PNP_PRIOR_TV pnp_step needs no weights and runs on a PNP_FLAG_NO_DENOISER handle (which otherwise cannot step: PNP_ERR_STATE);
+ * PNP_PRIOR_UNET on such a handle is refused with PNP_ERR_STATE.  Setting the prior back to PNP_PRIOR_UNET gives steps bit-identical to a
+ * handle that never left it.  The prior is stateless - the dual starts from 0 in every call - so snapshots, residuals and every driver work
+ * unchanged.
+ *   prior : PNP_PRIOR_UNET or PNP_PRIOR_TV;   tv_scale : finite, >= 0;   tv_iters : 1..PNP_TV_MAX_ITERS
+ * (tv_scale and tv_iters are checked and stored for PNP_PRIOR_TV only; PNP_PRIOR_UNET leaves the stored pair as it was).  No HIP call is made.
+ * pnp_get_prior returns the current prior and the stored pair (1.0 and 20 on a fresh handle); all three pointers are required.
+ * Every argument error (null handle or pointer, an unknown prior, tv_scale negative or not finite, tv_iters outside 1..64) leaves the handle
+ * and the outputs untouched. */
+#define PNP_PRIOR_UNET 0
+#define PNP_PRIOR_TV   1
+int pnp_set_prior(pnp_handle h, int prior, double tv_scale, int tv_iters);
+int pnp_get_prior(pnp_handle h, int* prior, double* tv_scale, int* tv_iters);
+
 /* Replaces: fft(img) / ifft(img) (evaluation/utils/transformations.py:6-12 / :14-19): centred
  * (ifftshift -> fftn/ifftn norm='ortho' -> fftshift) 2-D transform over the last two dims.
  * in/out DEVICE complex64 [batch,H,W] (may alias); hh, ww are the engine's h, w and batch <= n.
