@@ -21,6 +21,7 @@ RESIDUAL_COLUMNS = ("primal", "dx", "dz", "du", "delta", "dc")      # columns of
 PNP_MC_MAX_COILS = 32
 PNP_MC_MAX_CG = 64
 PNP_CC_MAX_COILS = 64
+PNP_PW_MAX_COILS = 64
 PNP_ESPIRIT_MAX_COILS = 16
 PNP_ESPIRIT_MAX_KSIZE = 8
 PNP_ESPIRIT_MAX_N = 512
@@ -71,6 +72,9 @@ SIGNATURES = {
     "pnp_estimate_sens": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp, _fp, _vp]),
     "pnp_coil_compress_matrix": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _vp]),
     "pnp_coil_compress_apply": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_noise_cov": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_whiten_matrix": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _vp]),
+    "pnp_whiten_apply": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, C.c_int, _fp, _vp]),
     "pnp_espirit_sens": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double,
                                   C.c_int, _fp, _fp, _fp, _vp, _vp]),
     "pnp_snapshot_bytes": (C.c_size_t, [C.c_void_p]),

@@ -18,7 +18,7 @@ from typing import Dict, Tuple
 import numpy as np
 import torch
 
-from . import synthetic
+from . import _lib, synthetic
 from .weights import hash_uniform
 
 MASK_KINDS = ("radial", "cartesian")
@@ -32,13 +32,116 @@ def _engine(engine_or_env, n: int, h: int, w: int, device: torch.device):
     raise TypeError(f"simulate: expected a PnPEngine or a PnPEnv, got {type(engine_or_env).__name__}")
 
 
-def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: int = 0, sens=None) -> Dict[str, torch.Tensor]:
+SCAN_SAMPLES = 4096          # samples per channel of the noise-only scan the command line takes
+SCAN_SEED = 9000             # ... and the offset of its seed from the run's
+
+
+def unit_scan_sigma(noise_cov=None) -> float:
+    """The sigma_n at which `noise_scan(..., noise_cov)` has a mean channel variance of 1 (sigma_n^2 * 2 * mean diag Psi = 1): whitening by
+    that scan's covariance keeps the overall scale of the data, so a penalty mu means the same with and without it."""
+    d = 1.0 if noise_cov is None else float(np.real(np.diagonal(np.asarray(torch.as_tensor(noise_cov).cpu()))).mean())
+    return 1.0 / math.sqrt(2.0 * d)
+
+
+def _factor(eng, noise_cov, coils: int):
+    """(wmat, lmat) complex64 [C,C] of a covariance [C,C] on the engine's device (pnp_whiten_matrix); PnPError when it is not positive
+    definite.  Reads the one int32 `info` back: a setup-time step."""
+    psi = torch.as_tensor(noise_cov)
+    if psi.dim() != 2 or tuple(psi.shape) != (coils, coils):
+        raise ValueError(f"noise_cov: expected [{coils},{coils}], got {tuple(psi.shape)}")
+    wmat, lmat, info = eng.whiten_matrix(psi.to(eng.device, torch.complex128).contiguous())
+    bad = int(info[0])
+    if bad:
+        raise _lib.PnPError(f"noise_cov is not positive definite: the pivot of column {bad - 1} fails (pnp_whiten_matrix info = {bad})")
+    return wmat, lmat
+
+
+def noise_scan(engine_or_env, coils: int, samples: int, noise_cov=None, sigma_n: float = 1.0, seed: int = 0) -> torch.Tensor:
+    """A noise-only scan on the device: complex64 [coils, samples] with covariance sigma_n^2 * 2 * noise_cov (each white sample is
+    sigma_n (g_re + i g_im) with unit-variance parts, as in `simulate`), for `PnPEngine.noise_cov` / `prewhiten`.  The white noise is
+    pnp_acquire_mc's, run with gt = 0 and a full mask (so coils <= 32), mixed by L (noise_cov = L L^H) with pnp_whiten_apply in place;
+    noise_cov None leaves it white.  Sample s of coil c is bin s of the engine's [N,H,W] planes in row-major order, so samples <=
+    N H W.  A PnPEnv is asked for a handle of ceil(samples / 4096) slices of 64 x 64."""
+    coils, samples = int(coils), int(samples)
+    if not 1 <= coils <= 32:
+        raise ValueError(f"noise_scan: coils must be 1..32, got {coils}")
+    if samples < 1:
+        raise ValueError(f"noise_scan: samples must be >= 1, got {samples}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("noise_scan needs a ROCm GPU")
+    eng = engine_or_env if hasattr(engine_or_env, "acquire") else None
+    if eng is None:
+        eng = _engine(engine_or_env, (samples + 4095) // 4096, 64, 64, torch.device("cuda", torch.cuda.current_device()))
+    n, h, w = eng.n, eng.h, eng.w
+    if samples > n * h * w:
+        raise ValueError(f"noise_scan: the engine [{n},{h},{w}] holds {n * h * w} samples per coil, fewer than {samples}")
+    lmat = _factor(eng, noise_cov, coils)[1] if noise_cov is not None else None
+    gt = torch.zeros((n, 1, h, w), dtype=torch.float32, device=eng.device)
+    ones = torch.ones((h, w), dtype=torch.bool, device=eng.device)
+    sens = torch.ones((coils, h, w), dtype=torch.complex64, device=eng.device)
+    y = eng.acquire(gt, ones, float(sigma_n), int(seed), sens=sens)[0]
+    if lmat is not None:
+        eng.whiten_apply(y, lmat, out=y)
+    return y.permute(1, 0, 2, 3).reshape(coils, n * h * w)[:, :samples].contiguous()
+
+
+def prewhiten(engine_or_env, y0, noise, sens=None, inplace: bool = True):
+    """Noise pre-whitening on the device (pnp_noise_cov, pnp_whiten_matrix, pnp_whiten_apply): the head of the chain whiten -> compress
+    -> maps -> SENSE.  y0: multi-coil k-space, complex [N,C,H,W] or real [N,C,H,W,2]; noise: a noise-only scan complex64 [C,S] (e.g.
+    `noise_scan`); sens: the coil maps, complex [C,H,W] or [N,C,H,W], mixed by the same W (the maps of whitened data are W S), or None -
+    estimate them from the whitened k-space afterwards.  inplace: y0 (when it already is a contiguous complex64 tensor on the engine's
+    device) and a per-slice sens are overwritten, no second [N,C,H,W] buffer.  Returns (y0_w, sens_w or None, wmat complex64 [C,C], psi
+    complex128 [C,C]); raises PnPError when the measured covariance is not positive definite (info != 0) - the one host read, made at
+    setup time.  Whitened noise has covariance I: sigma_n^2 * 2 * Psi of `noise_scan` becomes unit variance per complex sample."""
+    y = torch.as_tensor(y0)
+    if not y.is_complex():
+        if y.dim() != 5 or y.shape[-1] != 2:
+            raise ValueError(f"y0: expected complex [N,C,H,W] or real [N,C,H,W,2], got {tuple(y.shape)}")
+        y = torch.view_as_complex(y.float().contiguous())
+    if y.dim() != 4:
+        raise ValueError(f"y0: expected [N,C,H,W], got {tuple(y.shape)}")
+    n, c, h, w = (int(v) for v in y.shape)
+    nz = torch.as_tensor(noise)
+    if not nz.is_complex() or nz.dim() != 2 or nz.shape[0] != c:
+        raise ValueError(f"noise: expected complex [{c},S], got {tuple(nz.shape)}")
+    s = None
+    if sens is not None:
+        s = torch.as_tensor(sens)
+        if not s.is_complex() or s.dim() not in (3, 4) or tuple(s.shape[-3:]) != (c, h, w) or (s.dim() == 4 and s.shape[0] != n):
+            raise ValueError(f"sens: expected complex [{c},{h},{w}] or [{n},{c},{h},{w}], got {tuple(s.shape)}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("prewhiten needs a ROCm GPU")
+    eng = engine_or_env if hasattr(engine_or_env, "whiten_apply") else None
+    if eng is None:
+        eng = _engine(engine_or_env, n, h, w, torch.device("cuda", torch.cuda.current_device()))
+    if (eng.n, eng.h, eng.w) != (n, h, w):
+        raise ValueError(f"y0 {tuple(y.shape)} does not fit the engine [{eng.n},{eng.h},{eng.w}]")
+    psi = eng.noise_cov(nz.to(eng.device, torch.complex64).contiguous())
+    wmat, _ = _factor(eng, psi, c)
+    y = y.to(eng.device, torch.complex64).contiguous()
+    y = eng.whiten_apply(y, wmat, out=y if inplace else None)
+    if s is not None:
+        s = s.to(eng.device, torch.complex64)
+        if s.dim() == 3:
+            s = s[None].expand(n, c, h, w).contiguous()      # one matrix, but whitened maps are stored per slice: [N,C,H,W] for `reset`
+            s = eng.whiten_apply(s, wmat, out=s)
+        else:
+            s = s.contiguous()
+            s = eng.whiten_apply(s, wmat, out=s if inplace else None)
+    return y, s, wmat, psi
+
+
+def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: int = 0, sens=None, noise_cov=None) -> Dict[str, torch.Tensor]:
     """The collated `.mat` dict `PnPEnv.reset` reads, acquired on the device: x0, y0, ATy0 float32 [N,1,H,W,2] (real views of the
     complex outputs), mask bool [H,W] (or [N,H,W]), gt float32 [N,1,H,W], x0_raw = Re ATy0 [N,1,H,W]; every tensor on the GPU.
     gt: [N,H,W] or [N,1,H,W] in [0, 1] (array or tensor), mask: [H,W] or [N,H,W] in the centred layout.  Slice i draws the noise of
     seed + first_slice + i, so shards of one job agree with the unsharded job (as in `synthetic.make_problem`).
     sens: coil sensitivity maps, complex [C,H,W] (shared) or [N,C,H,W] - the multi-coil acquisition (pnp_acquire_mc): y0 is then
-    [N,C,H,W,2], ATy0 = sum_c conj(S_c) ifft_c(y_c), and the dict carries `sens` (complex64, on the GPU) for `PnPEnv.reset`."""
+    [N,C,H,W,2], ATy0 = sum_c conj(S_c) ifft_c(y_c), and the dict carries `sens` (complex64, on the GPU) for `PnPEnv.reset`.
+    noise_cov (with sens): the channel noise covariance Psi, complex [C,C] Hermitian positive definite (e.g. `synthetic.noise_cov_model`):
+    y_c = mask * (fft_c(S_c gt) + sigma_n * sum_k L[c][k] noise_k), Psi = L L^H - the noise-free acquisition plus the masked white noise
+    of the plain call mixed by L on the device (pnp_whiten_apply, in place; an unsampled bin stays exactly zero).  ATy0 is the sum of
+    the two parts' A^H (the noise part through the maps mixed by L^H), x0 its clip at 0; the dict carries `noise_cov` (complex128)."""
     if not torch.cuda.is_available():
         raise RuntimeError("simulate needs a ROCm GPU; the CPU route is synthetic.make_problem")
     g = torch.as_tensor(gt)
@@ -62,11 +165,27 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
     m = (m != 0).to(eng.device).contiguous()
     if sens is not None:
         sens = torch.as_tensor(sens).to(eng.device, torch.complex64).contiguous()
-    y0, aty0, x0 = eng.acquire(g, m, float(sigma_n), int(seed) + int(first_slice), sens=sens)
+    if noise_cov is not None:
+        if sens is None:
+            raise ValueError("simulate: noise_cov needs sens (a multi-coil acquisition)")
+        c = int(sens.shape[-3])
+        _, lmat = _factor(eng, noise_cov, c)
+        y0, aty0, _ = eng.acquire(g, m, 0.0, int(seed) + int(first_slice), sens=sens)
+        sn = (sens[None].expand(n, c, h, w) if sens.dim() == 3 else sens).contiguous()
+        mixed = eng.coil_compress_apply(sn, lmat.conj().transpose(0, 1).resolve_conj().contiguous(), c)      # A^H (L n) = sum_k conj((L^H S)_k) ifft_c(n_k)
+        yn, atn, _ = eng.acquire(torch.zeros_like(g), m, float(sigma_n), int(seed) + int(first_slice), sens=mixed)
+        eng.whiten_apply(yn, lmat, out=yn)
+        y0 = y0 + yn
+        aty0 = aty0 + atn
+        x0 = torch.view_as_complex(torch.view_as_real(aty0).clamp_min(0.0))
+    else:
+        y0, aty0, x0 = eng.acquire(g, m, float(sigma_n), int(seed) + int(first_slice), sens=sens)
     out = {"x0": torch.view_as_real(x0), "y0": torch.view_as_real(y0), "ATy0": torch.view_as_real(aty0), "mask": m, "gt": g,
            "x0_raw": aty0.real.contiguous()}
     if sens is not None:
         out["sens"] = sens
+    if noise_cov is not None:
+        out["noise_cov"] = torch.as_tensor(noise_cov).to(eng.device, torch.complex128)
     return out
 
 
@@ -266,13 +385,13 @@ def make_mask(h: int, w: int, accel: float, kind: str = "radial", seed: int = 0)
 
 
 def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int = 0, mask_kind: str = "radial",
-                 mask=None, coils: int = 0) -> Dict[str, torch.Tensor]:
+                 mask=None, coils: int = 0, noise_cov=None) -> Dict[str, torch.Tensor]:
     """`simulate` for a named task: '4x_10' = acceleration 4, sigma_n = 10 / 255.  mask: a ready mask, or None for
     `make_mask(h, w, accel, mask_kind, seed)` (the same for every shard of a job).  coils > 0: a multi-coil acquisition with the
-    analytic maps `synthetic.coil_maps(coils, h, w)`."""
+    analytic maps `synthetic.coil_maps(coils, h, w)`; noise_cov: their channel noise covariance (`simulate`)."""
     accel, sigma_n = parse_task(task)
     h, w = (int(v) for v in torch.as_tensor(gt).shape[-2:])
     if mask is None:
         mask = make_mask(h, w, accel, mask_kind, seed)
     sens = synthetic.coil_maps(coils, h, w).astype(np.complex64) if coils else None
-    return simulate(engine_or_env, gt, mask, sigma_n, seed, first_slice, sens=sens)
+    return simulate(engine_or_env, gt, mask, sigma_n, seed, first_slice, sens=sens, noise_cov=noise_cov)

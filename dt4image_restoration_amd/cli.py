@@ -105,6 +105,32 @@ def _tasks(args):
     return tasks
 
 
+def _psi(args):
+    """--noise-cov RHO[,GAIN_SPREAD]: the channel noise covariance of the run's --coils problems (synthetic.noise_cov_model), or None."""
+    if not args.noise_cov:
+        return None
+    from . import synthetic
+    return synthetic.noise_cov_model(args.coils, args.noise_cov[0], args.noise_cov[1], args.seed)
+
+
+def _prewhitened(args, env, batch):
+    """--prewhiten: the batch with its y0 (and, under --sens true, its maps) mixed by W = L^-1 of the covariance measured on a noise-only
+    scan (acquisition.prewhiten).  The scan has the run's covariance at the level that makes the mean channel variance 1, so the data
+    keep their overall scale (and --mu its meaning); x0 stays the one the set brings."""
+    if not args.prewhiten:
+        return batch
+    from . import acquisition
+    batch = dict(batch)
+    psi = _psi(args)
+    scan = acquisition.noise_scan(env, args.coils, acquisition.SCAN_SAMPLES, noise_cov=psi, sigma_n=acquisition.unit_scan_sigma(psi),
+                                  seed=args.seed + acquisition.SCAN_SEED)
+    y, sens, _, _ = acquisition.prewhiten(env, batch["y0"], scan, sens=batch.get("sens") if args.sens == "true" else None)
+    batch["y0"] = torch.view_as_real(y)
+    if sens is not None:
+        batch["sens"] = sens
+    return batch
+
+
 def _compressed(args, env, batch):
     """--compress V: the batch with its y0 (and, under --sens true, its maps) mixed down to V virtual coils on the device."""
     if not args.compress:
@@ -126,9 +152,9 @@ def _compressed(args, env, batch):
 
 
 def _with_sens(args, env, batch):
-    """--compress, then --sens estimate / espirit: the batch with its coil maps replaced by the estimate from its own y0 and mask (on the
+    """--prewhiten, then --compress, then --sens estimate / espirit: the batch with its coil maps replaced by the estimate from its own y0 and mask (on the
     device)."""
-    batch = _compressed(args, env, batch)
+    batch = _compressed(args, env, _prewhitened(args, env, batch))
     if args.sens == "true":
         return batch
     from . import acquisition
@@ -151,7 +177,8 @@ def _sets(args, flex_target=None, env=None):
             for task in _tasks(args):
                 def load(a, b, d=d, task=task):
                     gt, _ = D.load_gt_dir(d, limit=args.limit, start=a, stop=b)
-                    batch = acquisition.task_problem(task, gt, env, seed=args.seed, first_slice=a, mask_kind=args.mask, coils=args.coils)
+                    batch = acquisition.task_problem(task, gt, env, seed=args.seed, first_slice=a, mask_kind=args.mask, coils=args.coils,
+                                                    noise_cov=_psi(args))
                     return _with_sens(args, env, batch), D.task_tokens([task] * (b - a), flex_target)
                 yield f"{d} {task}", D.count_gt_dir(d, args.limit), load
     elif args.data:
@@ -169,11 +196,11 @@ def _sets(args, flex_target=None, env=None):
                 # centre columns (None: the radial mask of make_problem, as every other run gets)
                 mask = acquisition.make_mask(args.size, args.size, accel, args.mask, args.seed) \
                     if args.sens != "true" and args.mask != "radial" else None
-                if args.acquire == "device":                   # make_problem's phantoms, mask and noise; the transforms on the GPU
+                if args.acquire == "device" or args.noise_cov:   # (correlated noise is mixed on the device) make_problem's phantoms, mask and noise; the transforms on the GPU
                     gt = np.stack([synthetic.phantom(args.size, args.size, args.seed + accel + i) for i in range(a, b)])
                     sens = synthetic.coil_maps(args.coils, args.size, args.size).astype(np.complex64) if args.coils else None
                     p = acquisition.simulate(env, gt.astype(np.float32), synthetic.radial_mask(args.size, args.size, accel) if mask is None else mask,
-                                             sig / 255.0, args.seed + accel, first_slice=a, sens=sens)
+                                             sig / 255.0, args.seed + accel, first_slice=a, sens=sens, noise_cov=_psi(args))
                     return (_with_sens(args, env, p) if args.coils else p), D.task_tokens([f"{accel}x_{sig}"] * (b - a), flex_target)
                 if args.coils:
                     p = synthetic.make_problem_mc(b - a, args.size, args.size, args.coils, accel=accel, sigma_n=sig / 255.0,
@@ -259,6 +286,11 @@ def main(argv=None):
                     "fraction of the slice's largest get zero maps (in [0, 1))")
     ap.add_argument("--compress", type=int, default=0, metavar="V", help="coil compression of a --coils run: the solver gets the V "
                     "strongest virtual coils of each set (1..--coils; default 0: no compression)")
+    ap.add_argument("--noise-cov", default=None, metavar="RHO[,GAIN_SPREAD]", help="correlated receiver noise for the --coils problems: "
+                    "neighbouring channels correlate by RHO (in [0, 1)) and the channel gains ramp from 1 to GAIN_SPREAD (>= 1, default 1); "
+                    "the synthetic sets are then acquired on the device")
+    ap.add_argument("--prewhiten", action="store_true", help="measure the channel noise covariance on a noise-only scan and whiten y0 (and "
+                    "the maps of --sens true) on the device, before --compress and --sens estimate|espirit")
     ap.add_argument("--acs", type=int, nargs=2, default=None, metavar=("H", "W"), help="--sens estimate / --compress: even sides of the centred "
                     "calibration block (default: the largest block the mask samples completely)")
     ap.add_argument("--prior", choices=("unet", "tv"), default="unet", help="the x-update of eval / flex / mcts / fixed: the U-Net, or total "
@@ -307,6 +339,22 @@ def main(argv=None):
             raise SystemExit("--prior tv loads no weights: drop --denoiser-ckpt")
         if args.mode == "acquire":
             raise SystemExit("acquire has no x-update: drop --prior tv")
+    if args.noise_cov is not None:
+        try:
+            v = [float(t) for t in args.noise_cov.split(",")]
+        except ValueError:
+            v = []
+        if len(v) not in (1, 2) or not 0.0 <= v[0] < 1.0 or (len(v) == 2 and not (v[1] >= 1.0 and np.isfinite(v[1]))):
+            raise SystemExit(f"--noise-cov takes RHO[,GAIN_SPREAD] with 0 <= RHO < 1 and a finite GAIN_SPREAD >= 1, got {args.noise_cov!r}")
+        if not args.coils:
+            raise SystemExit("--noise-cov needs --coils: a single-coil problem has one channel")
+        if args.mode == "acquire" or args.data:
+            raise SystemExit("--noise-cov applies to the synthetic sets and --gt of eval|flex|mcts|fixed")
+        args.noise_cov = (v[0], v[1] if len(v) == 2 else 1.0)
+    if args.prewhiten and args.mode == "acquire":
+        raise SystemExit("--prewhiten applies to eval|flex|mcts|fixed: acquire writes the measurements as they are")
+    if args.prewhiten and not args.coils:
+        raise SystemExit("--prewhiten needs --coils: there are no channels to whiten on a single-coil problem")
     args.compress_energy = []
     if args.compress:
         if not args.coils:

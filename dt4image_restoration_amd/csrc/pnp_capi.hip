@@ -116,6 +116,9 @@ struct pnp_engine {
     double2* cc_part = nullptr;  // [N, gram_chunks, C, C] per-workgroup Gram partials
     double2* cc_gram = nullptr;  // [N, C, C] Gram for callers that pass none
     size_t cc_part_cap = 0, cc_gram_cap = 0;   // capacities in complex128 elements
+    // noise pre-whitening (pnp_noise_cov): allocated inside its first call, grown by a call that needs more
+    double2* pw_part = nullptr;  // [noise_n, whiten_chunks, C, C] per-workgroup covariance partials
+    size_t pw_part_cap = 0;      // capacity in complex128 elements
     // ESPIRiT maps (pnp_espirit_sens): allocated inside its first call, grown by a call that needs more
     void* es_ws = nullptr;       // per slice G and the vectors [2, np, np] complex128, then R [N, C, C, D, D] complex64, then nkept [N]
     size_t es_cap = 0;           // capacity in bytes
@@ -510,6 +513,20 @@ int cc_ensure(pnp_engine* e, size_t part_need, size_t gram_need) {
     return PNP_OK;
 }
 
+// The workspace of pnp_noise_cov: `need` complex128 covariance partials, replaced by a larger buffer when a call needs more.
+int pw_ensure(pnp_engine* e, size_t need) {
+    if (need <= e->pw_part_cap) return PNP_OK;
+    void* fresh = nullptr;
+    if (hipMalloc(&fresh, need * sizeof(double2)) != hipSuccess)
+        return fail(PNP_ERR_NOMEM, "noise covariance workspace: %zu bytes (the handle keeps the workspace it had)", need * sizeof(double2));
+    if (e->pw_part) (void)hipDeviceSynchronize();   // no launch still reads the buffer being replaced
+    (void)hipFree(e->pw_part);
+    e->pw_part = (double2*)fresh;
+    e->ws_bytes += (need - e->pw_part_cap) * sizeof(double2);
+    e->pw_part_cap = need;
+    return PNP_OK;
+}
+
 // The workspace of pnp_espirit_sens beyond cm_ensure's: one buffer of `need` bytes, replaced by a larger one when a call needs more.
 int es_ensure(pnp_engine* e, size_t need) {
     if (need <= e->es_cap) return PNP_OK;
@@ -702,6 +719,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->mc_y); (void)hipFree(e->mc_work); (void)hipFree(e->mc_sens); (void)hipFree(e->mc_vec); (void)hipFree(e->mc_part); (void)hipFree(e->mc_sc);
     (void)hipFree(e->cm_max); (void)hipFree(e->cm_rss);
     (void)hipFree(e->cc_part); (void)hipFree(e->cc_gram);
+    (void)hipFree(e->pw_part);
     (void)hipFree(e->es_ws);
     (void)hipFree(e->tv_p);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
@@ -1250,6 +1268,85 @@ int pnp_coil_compress_apply(pnp_handle e, const float* in, int coils, const floa
     HIP_TRY(launch_coilcomp_apply((const float2*)in, (const float2*)cmat, cmat_n, coils, out_coils, (float2*)out, N, H, W, s));
     return PNP_OK;
     PNP_API_END("pnp_coil_compress_apply")
+}
+
+int pnp_noise_cov(pnp_handle e, const float* noise, int noise_n, int coils, int samples, int flags, double* psi, void* stream) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call, and leaves the outputs untouched; scalar ranges first
+    const char* fn = "pnp_noise_cov";
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (coils < 1 || coils > PNP_PW_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_PW_MAX_COILS, coils);
+    if (samples < 1) return fail(PNP_ERR_INVALID, "%s: samples must be >= 1 (got %d)", fn, samples);
+    if (noise_n < 1 || noise_n > 65535) return fail(PNP_ERR_INVALID, "%s: noise_n must be 1..65535 (got %d)", fn, noise_n);
+    if (!noise) return fail(PNP_ERR_INVALID, "%s: null noise", fn);
+    if (!psi) return fail(PNP_ERR_INVALID, "%s: null psi", fn);
+    if ((const void*)psi == (const void*)noise) return fail(PNP_ERR_INVALID, "%s: psi must not alias noise", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = pw_ensure(e, (size_t)noise_n * whiten_chunks(samples) * coils * coils)) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_prewhiten_cov((const float2*)noise, noise_n, coils, samples, e->pw_part, (double2*)psi, s));
+    p.end(2);
+    return PNP_OK;
+    PNP_API_END("pnp_noise_cov")
+}
+
+int pnp_whiten_matrix(pnp_handle e, const double* psi, int psi_n, int coils, int flags, float* wmat, float* lmat, int32_t* info, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_whiten_matrix";
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (coils < 1 || coils > PNP_PW_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_PW_MAX_COILS, coils);
+    if (psi_n < 1 || psi_n > 65535) return fail(PNP_ERR_INVALID, "%s: psi_n must be 1..65535 (got %d)", fn, psi_n);
+    if (!psi) return fail(PNP_ERR_INVALID, "%s: null psi", fn);
+    if (!wmat) return fail(PNP_ERR_INVALID, "%s: null wmat", fn);
+    if (!info) return fail(PNP_ERR_INVALID, "%s: null info", fn);
+    {
+        const void* q[4] = {psi, wmat, info, lmat};
+        for (int i = 0; i < 4; ++i)
+            for (int j = i + 1; j < 4; ++j)
+                if (q[j] && q[i] == q[j]) return fail(PNP_ERR_INVALID, "%s: psi, wmat, lmat and info must not alias", fn);
+    }
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_prewhiten_chol((const double2*)psi, psi_n, coils, (float2*)wmat, (float2*)lmat, (int*)info, s));
+    return PNP_OK;
+    PNP_API_END("pnp_whiten_matrix")
+}
+
+int pnp_whiten_apply(pnp_handle e, const float* in, int coils, const float* wmat, int wmat_n, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_whiten_apply";
+    if (coils < 1 || coils > PNP_PW_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_PW_MAX_COILS, coils);
+    if (wmat_n < 1) return fail(PNP_ERR_INVALID, "%s: wmat_n must be 1 or the handle's n (got %d)", fn, wmat_n);
+    if (!in) return fail(PNP_ERR_INVALID, "%s: null in", fn);
+    if (!wmat) return fail(PNP_ERR_INVALID, "%s: null wmat", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (out == wmat || in == wmat) return fail(PNP_ERR_INVALID, "%s: wmat must not alias in or out", fn);
+    // out == in is the in-place call; any other overlap is refused.  The planes of the smallest handle (16 x 16) already span 2048 coils bytes,
+    // so an offset below that overlaps whatever the handle is: refused before the handle is looked at
+    const uintptr_t pi = (uintptr_t)in, po = (uintptr_t)out;
+    const uintptr_t gap = pi < po ? po - pi : pi - po;
+    if (gap != 0 && gap < (uintptr_t)2048 * (uintptr_t)coils)
+        return fail(PNP_ERR_INVALID, "%s: out must be in exactly (in place) or must not overlap it (the buffers lie %zu bytes apart)", fn, (size_t)gap);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (wmat_n != 1 && wmat_n != N) return fail(PNP_ERR_INVALID, "%s: wmat_n must be 1 or the handle's n=%d (got %d)", fn, N, wmat_n);
+    if (N > 65535) return fail(PNP_ERR_INVALID, "%s: n must be <= 65535 (got %d)", fn, N);
+    const uintptr_t bytes = (uintptr_t)N * coils * H * W * sizeof(float2), wbytes = (uintptr_t)wmat_n * coils * coils * sizeof(float2);
+    if (gap != 0 && gap < bytes)
+        return fail(PNP_ERR_INVALID, "%s: out must be in exactly (in place) or must not overlap it (the buffers lie %zu bytes apart)", fn, (size_t)gap);
+    const uintptr_t pw = (uintptr_t)wmat;
+    if ((pw < po + bytes && po < pw + wbytes) || (pw < pi + bytes && pi < pw + wbytes))
+        return fail(PNP_ERR_INVALID, "%s: wmat must not alias in or out", fn);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_prewhiten_apply((const float2*)in, (const float2*)wmat, wmat_n, coils, (float2*)out, N, H, W, s));
+    return PNP_OK;
+    PNP_API_END("pnp_whiten_apply")
 }
 
 int pnp_espirit_sens(pnp_handle e, const float* y0, int coils, int acs_h, int acs_w, int ksize, double sv_thresh, double crop, int iters,

@@ -282,6 +282,17 @@ hipError_t launch_coilcomp_eig(const double2* gram, int C, float2* cmat, float* 
 // out[n, v] = sum_c cmat[n or 0][v][c] in[n, c], v < V; in: [N, C, H, W], out: [N, V, H, W]
 hipError_t launch_coilcomp_apply(const float2* in, const float2* cmat, int cmat_n, int C, int V, float2* out, int N, int H, int W, hipStream_t s);
 
+// ---- coil noise pre-whitening (prewhiten_kernels.hip) -----------------------------------------------
+// A scan's samples are dealt to whiten_chunks(S) workgroups of whiten_chunk_samples(S) consecutive samples each, by the rule of gram_chunk_bins.
+int whiten_chunk_samples(int samples);
+int whiten_chunks(int samples);
+// psi: [noise_n, C, C] complex128 = (1 / S) sum_s n_a conj(n_b); noise: [noise_n, C, S]; partial: [noise_n, whiten_chunks, C, C] complex128.  Two launches.
+hipError_t launch_prewhiten_cov(const float2* noise, int noise_n, int C, int S, double2* partial, double2* psi, hipStream_t s);
+// wmat, lmat (or nullptr): [psi_n, C, C] complex64 lower-triangular, info: [psi_n]; one workgroup per matrix
+hipError_t launch_prewhiten_chol(const double2* psi, int psi_n, int C, float2* wmat, float2* lmat, int* info, hipStream_t s);
+// out[n, v] = sum_{c <= v} wmat[n or 0][v][c] in[n, c]; in, out: [N, C, H, W]; out may be in
+hipError_t launch_prewhiten_apply(const float2* in, const float2* wmat, int wmat_n, int C, float2* out, int N, int H, int W, hipStream_t s);
+
 // ---- ESPIRiT coil maps (espirit_kernels.hip) --------------------------------------------------------
 // np: the side of the calibration Gram matrix, n = C k^2 rounded up to even.  ws: per slice G [np][np] then the transposed vectors [np][np], complex128
 inline int espirit_padded(int C, int k) { return (C * k * k + 1) & ~1; }

@@ -417,6 +417,56 @@ class PnPEngine:
                                                     self._stream()), "pnp_coil_compress_apply")
         return out
 
+    def noise_cov(self, noise: torch.Tensor) -> torch.Tensor:
+        """Channel noise covariance of noise-only scans (pnp_noise_cov): noise complex64 [C,S] or [M,C,S], C <= 64, any M (not tied to the
+        engine's N).  Returns Psi complex128 [M,C,C] ([C,C] for a 2-d input), Psi[a][b] = mean_s n_a[s] conj(n_b[s]), summed in float64 in
+        a fixed order, exactly Hermitian.  Does not change the engine's mode or its installed constants."""
+        if noise.dim() not in (2, 3):
+            raise ValueError(f"noise: expected [C,S] or [M,C,S], got {tuple(noise.shape)}")
+        m = 1 if noise.dim() == 2 else int(noise.shape[0])
+        coils, samples = int(noise.shape[-2]), int(noise.shape[-1])
+        noise = self._chk(noise, torch.complex64, m * coils * samples, "noise")
+        psi = torch.empty((m, coils, coils), dtype=torch.complex128, device=self.device)
+        _lib.check(self.lib.pnp_noise_cov(self._h, noise.data_ptr(), m, coils, samples, 0, psi.data_ptr(), self._stream()), "pnp_noise_cov")
+        return psi[0] if noise.dim() == 2 else psi
+
+    def whiten_matrix(self, psi: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Whitening matrices of Hermitian positive-definite covariances (pnp_whiten_matrix): psi complex128 [C,C] or [M,C,C].  Returns
+        (wmat, lmat, info): Psi = L L^H, W = L^-1, both complex64 lower-triangular in psi's shape, and info int32 [M] - 0, or j + 1 when
+        column j's pivot fails (that matrix's wmat and lmat are then the identity).  Nothing is read back: check info where it matters."""
+        if psi.dim() not in (2, 3) or psi.shape[-1] != psi.shape[-2]:
+            raise ValueError(f"psi: expected [C,C] or [M,C,C], got {tuple(psi.shape)}")
+        m = 1 if psi.dim() == 2 else int(psi.shape[0])
+        coils = int(psi.shape[-1])
+        psi = self._chk(psi, torch.complex128, m * coils * coils, "psi")
+        wmat = torch.empty(tuple(psi.shape), dtype=torch.complex64, device=self.device)
+        lmat = torch.empty_like(wmat)
+        info = torch.empty((m,), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.pnp_whiten_matrix(self._h, psi.data_ptr(), m, coils, 0, wmat.data_ptr(), lmat.data_ptr(), info.data_ptr(),
+                                              self._stream()), "pnp_whiten_matrix")
+        return wmat, lmat, info
+
+    def whiten_apply(self, planes: torch.Tensor, wmat: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The lower-triangular channel mix out[n,v] = sum_{c <= v} wmat[n,v,c] planes[n,c] (pnp_whiten_apply): planes complex64 [N,C,H,W]
+        - k-space or coil maps -, wmat complex64 [C,C] (one matrix for all slices) or [N,C,C], only its lower triangle is read.
+        out=planes runs in place (no second buffer); out=None allocates the result."""
+        if planes.dim() != 4 or planes.shape[0] != self.n or tuple(planes.shape[-2:]) != (self.h, self.w):
+            raise ValueError(f"planes: expected [{self.n},C,{self.h},{self.w}], got {tuple(planes.shape)}")
+        coils = int(planes.shape[1])
+        planes = self._chk(planes, torch.complex64, self.n * coils * self.h * self.w, "planes")
+        if tuple(wmat.shape) not in ((coils, coils), (1, coils, coils), (self.n, coils, coils)):
+            raise ValueError(f"wmat: expected [{coils},{coils}] or [{self.n},{coils},{coils}], got {tuple(wmat.shape)}")
+        wmat_n = 1 if wmat.numel() == coils * coils else self.n
+        wmat = self._chk(wmat, torch.complex64, wmat_n * coils * coils, "wmat")
+        if out is None:
+            out = torch.empty_like(planes)
+        elif tuple(out.shape) != tuple(planes.shape):
+            raise ValueError(f"out: expected {tuple(planes.shape)}, got {tuple(out.shape)}")
+        out = self._chk(out, torch.complex64, planes.numel(), "out")
+        _lib.check(self.lib.pnp_whiten_apply(self._h, planes.data_ptr(), coils, wmat.data_ptr(), wmat_n, out.data_ptr(), self._stream()),
+                   "pnp_whiten_apply")
+        return out
+
     def snapshot(self, x: torch.Tensor, z: torch.Tensor, u: torch.Tensor, t_state: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One packed device buffer [x | z | u | T] (pnp_snapshot): a tree-search node's copy of the iterate."""

@@ -144,6 +144,32 @@ def coil_maps(c: int, h: int, w: int, radius: float = 1.3, width: float = 1.1) -
     return out / np.sqrt((np.abs(out) ** 2).sum(axis=0, keepdims=True))
 
 
+def noise_cov_model(c: int, rho: float = 0.4, gains=1.0, seed: int = 0) -> np.ndarray:
+    """complex128 [c,c]: a channel noise covariance with unequal gains and correlated neighbours,
+        Psi[a][b] = g_a g_b rho^|a-b| e^{i phi_(a-b)},   phi_d = d theta,  theta = pi hash_uniform(seed, 9201, 1)   (phi_-d = -phi_d: Hermitian).
+    gains: the c gains g_a > 0, or one number s >= 1, the gain spread: g_a = s^(a / (c - 1)), a geometric ramp from 1 to s.  0 <= rho < 1.
+    Psi = D R D^H with D = diag(g_a e^{i a theta}) and R the real AR(1) matrix rho^|a-b|, which is positive definite for every rho in
+    [0, 1): so is Psi, with a condition number of at most (g_max / g_min)^2 (1 + rho) / (1 - rho).  Plain float64 arithmetic on a
+    counter hash: the same bits on every machine."""
+    if c < 1:
+        raise ValueError(f"noise_cov_model: need c >= 1, got {c}")
+    if not 0.0 <= rho < 1.0:
+        raise ValueError(f"noise_cov_model: rho must be in [0, 1), got {rho}")
+    if np.ndim(gains) == 0:
+        if not float(gains) >= 1.0 or not math.isfinite(float(gains)):
+            raise ValueError(f"noise_cov_model: a gain spread must be finite and >= 1, got {gains}")
+        g = float(gains) ** (np.arange(c) / max(c - 1, 1))
+    else:
+        g = np.asarray(gains, dtype=np.float64)
+        if g.shape != (c,) or not (g > 0).all() or not np.isfinite(g).all():
+            raise ValueError(f"noise_cov_model: gains must be {c} finite positive numbers, got {gains!r}")
+    theta = math.pi * float(hash_uniform(seed, 9201, 1)[0])
+    d = np.arange(c)[:, None] - np.arange(c)[None, :]
+    psi = (g[:, None] * g[None, :]) * float(rho) ** np.abs(d) * np.exp(1j * theta * d)
+    psi[np.arange(c), np.arange(c)] = g * g                  # an exactly real diagonal
+    return np.tril(psi) + np.tril(psi, -1).conj().T          # exactly Hermitian
+
+
 def make_problem_mc(n: int, h: int, w: int, coils: int, accel: float = 4.0, sigma_n: float = 10.0 / 255.0, seed: int = 1234,
                     first_slice: int = 0, mask: np.ndarray = None) -> Dict[str, np.ndarray]:
     """`make_problem` for `coils` coils with the maps of `coil_maps`: y0 float32 [n,coils,h,w,2] with

@@ -393,6 +393,60 @@ int pnp_coil_compress_matrix(pnp_handle h, const float* y0, int coils, int acs_h
                              double* gram /* may be NULL */, void* stream);
 int pnp_coil_compress_apply(pnp_handle h, const float* in, int coils, const float* cmat, int cmat_n, int out_coils, float* out, void* stream);
 
+/* Coil noise pre-whitening: the head of the chain whiten -> compress -> maps -> SENSE.  Every later stage takes the receiver noise as white and
+ * equal across channels; a real array has unequal gains and correlated channels, so the channel noise covariance Psi is measured from a
+ * noise-only scan and the channels are mixed by W = L^-1, Psi = L L^H, after which W Psi W^H = I (the reference has no counterpart).  The maps of
+ * a whitened acquisition are mixed by the same W (S' = W S), or estimated from the whitened k-space.
+ *
+ * pnp_noise_cov, per scan n:   Psi[a][b] = (1 / S) sum_{s < S} noise[n,a,s] conj(noise[n,b,s])        (C x C Hermitian, the Gram convention of
+ *   pnp_coil_compress_matrix).  The terms are the float32 components of the samples, multiplied and summed in float64 (the products are exact).
+ *   The samples are dealt to ceil(S / per) workgroups of `per` consecutive samples, per = max(1024, ceil(S / 64) rounded up to a multiple of 32)
+ *   (the Gram's rule); each sums its samples in order (re += ar br; re += ai bi; im += ai br; im -= ar bi) and a second launch adds the
+ *   workgroups' partials in index order from 0.0, then divides once by S in float64.  No atomics: the order depends on (C, S) only.  Psi is
+ *   stored exactly Hermitian, its diagonal real.
+ *   noise : DEVICE complex64 [noise_n,C,S];   noise_n : 1..65535 (independent of the handle's n);   coils : 1..PNP_PW_MAX_COILS;   samples >= 1
+ *   flags : reserved, must be 0;   psi : DEVICE complex128 [noise_n,C,C] out, must not alias noise
+ *   SETUP-TIME SEMANTICS, as pnp_coil_compress_matrix: the first call allocates 16 noise_n C^2 ceil(S / per) bytes (the partials) inside the call,
+ *   all-or-nothing (on PNP_ERR_NOMEM the handle keeps the workspace it had), counted by pnp_workspace_bytes.  A later call allocates only if it
+ *   needs more than any call before it, and then waits for the device; every other call allocates nothing and is asynchronous.  Calls on one
+ *   handle are stream-ordered.
+ *
+ * pnp_whiten_matrix, per matrix n, one workgroup, float64, the matrix on chip.  Only the lower triangle of Psi and the real part of its diagonal
+ * are read.  Cholesky, column j = 0 .. C-1, every sum from 0.0 with k ascending and a conj(b) accumulated as
+ * (re += ar br; re += ai bi; im += ai br; im -= ar bi):
+ *     d       = Re Psi[j][j] - sum_{k<j} |L[j][k]|^2                      L[j][j] = sqrt(d)
+ *     L[i][j] = (Psi[i][j] - sum_{k<j} L[i][k] conj(L[j][k])) / L[j][j]   (i > j; real and imaginary part each divided by the real L[j][j])
+ *   W = L^-1 by forward substitution, column by column, i and k ascending, a b accumulated as (re += ar br; re -= ai bi; im += ar bi; im += ai br):
+ *     W[j][j] = 1 / L[j][j]            W[i][j] = -(sum_{k=j}^{i-1} L[i][k] W[k][j]) / L[i][i]
+ *   wmat and lmat are rounded to complex64 once, lower-triangular with exact +0 above the diagonal (and a zero below it stored as +0).
+ *   info[n] = 0, or j + 1 for the first column whose pivot d is not finite, not positive or not greater than 1e-12 * max_i Re Psi[i][i]; that
+ *   matrix's wmat and lmat are then the identity: a matrix that is not positive definite never produces NaN and needs no host read to be
+ *   survived.  Psi = I gives W = L = I bit for bit.
+ *   psi   : DEVICE complex128 [psi_n,C,C];   psi_n : 1..65535;   coils : 1..PNP_PW_MAX_COILS;   flags : reserved, must be 0
+ *   wmat  : DEVICE complex64 [psi_n,C,C] out;   lmat : the same layout, L, or NULL;   info : DEVICE int32 [psi_n] out; none may alias another
+ *   It allocates nothing and is asynchronous.
+ *
+ * pnp_whiten_apply:  out[n,v,p] = sum_{c = 0 .. v} wmat[n or 0][v][c] * in[n,c,p]  over all H W bins.  Only the lower triangle of wmat is read
+ * (whatever lies above the diagonal is ignored, and coil c > v never enters row v).  The float32 arithmetic is that of pnp_coil_compress_apply:
+ * from re = im = +0, c ascending, every product contracted:
+ *     re = fma(a.re, x.re, re);  re = fma(-a.im, x.im, re);  im = fma(a.re, x.im, im);  im = fma(a.im, x.re, im)        (a = wmat[v][c], x = in[c])
+ * so for coils <= 32 the result equals pnp_coil_compress_apply(in, wmat, out_coils = coils) bit for bit when wmat is zero above the diagonal,
+ * the identity copies the planes, and a bin that is zero in every coil stays zero.  The bits do not depend on which kernel variant runs.
+ *   in     : DEVICE complex64 [N,C,H,W];   coils : 1..PNP_PW_MAX_COILS
+ *   wmat   : DEVICE complex64 [wmat_n,C,C];   wmat_n : 1 (one matrix for all slices) or N;   must not overlap in or out
+ *   out    : DEVICE complex64 [N,C,H,W]; out == in (exactly) runs IN PLACE: row v needs coils 0..v only, and a thread reads all coils of its
+ *            pixels before it stores any row.  Any other overlap of in and out is refused.
+ * Each input value comes from memory once: 16 coils bytes per pixel (8 read, 8 written), in place or not, no workspace, asynchronous.
+ *
+ * All three take any handle kind and change neither the handle's mode nor its installed constants; pnp_whiten_apply needs n <= 65535.  Every
+ * argument error (null handle or pointer, a count out of range, flags != 0, forbidden aliasing) is reported with PNP_ERR_INVALID and a message
+ * naming the argument, before any HIP call, and leaves the outputs untouched. */
+#define PNP_PW_MAX_COILS 64
+int pnp_noise_cov(pnp_handle h, const float* noise, int noise_n, int coils, int samples, int flags, double* psi, void* stream);
+int pnp_whiten_matrix(pnp_handle h, const double* psi, int psi_n, int coils, int flags, float* wmat, float* lmat /* may be NULL */,
+                      int32_t* info, void* stream);
+int pnp_whiten_apply(pnp_handle h, const float* in, int coils, const float* wmat, int wmat_n, float* out, void* stream);
+
 /* ESPIRiT coil sensitivity maps: the maps as the dominant eigenvector, per pixel, of an operator built from the null space of the calibration
  * matrix, instead of the band-limited low-resolution estimate of pnp_estimate_sens (the reference has no counterpart).  Per slice, with the
  * centred acs_h x acs_w block B of pnp_estimate_sens, kernel side k = ksize, C = coils, n = C k^2, D = 2 k - 1:
