@@ -10,9 +10,7 @@
 //                            float32 values are exact), and stores the entry and its mirror; the diagonal's imaginary part is 0, the padding 0.
 //   espirit_eig_kernel       grid (N), one workgroup of 1024 threads per slice; G and the TRANSPOSED vectors (Vt[col][row]: a rotation's two
 //                            columns are two contiguous runs) live in the slice's global workspace, 2 x 16 np^2 bytes, and the workgroup's
-//                            barriers order its accesses.  The cyclic Jacobi method of coilcomp_eig_kernel: the same rotation, the same round-robin
-//                            order, the same two-phase round (np / 2 rotations from the diagonal blocks, then the blocks (pair k, pair l), k > l,
-//                            mirrored, and the vectors), the same stop rule off(G)_F <= 1e-14 trace before every sweep; at most kEsSweeps sweeps.
+//                            barriers order its accesses.  The cyclic Jacobi method of hermitian.h (jacobi_sweeps), at most kEsSweeps sweeps.
 //                            The eigenvalues stay on G's diagonal.  No sort and no phase step: only the projector on the kept vectors is used.
 //   espirit_kern_kernel      grid (ceil(C^2 D^2 / 256), N): every workgroup finds lambda_0 = max lambda and the kept flags lambda_j >
 //                            sv_thresh^2 lambda_0 (the first one of a slice writes nkept); one thread per R[a][b][dy][dx]: the kept vectors j in index
@@ -27,6 +25,7 @@
 // No atomics anywhere: a slice's bits depend on its own inputs and the arguments only.
 #include "pnp_internal.h"
 #include "block_reduce.h"
+#include "hermitian.h"
 #include "../../include/pnpadmm.h"
 
 namespace pnp {
@@ -36,7 +35,6 @@ namespace {
 constexpr int kEsThreads = 256;
 constexpr int kEsEigThreads = 1024;
 constexpr int kEsSweeps = 40;           // cap; the stop test ends the cases of the test suite (n = 64 .. 288) after 11 to 13 sweeps
-constexpr double kEsEps = 1e-14;        // off(G)_F <= kEsEps * trace
 constexpr int kEsMaxD = 2 * PNP_ESPIRIT_MAX_KSIZE - 1;
 constexpr int kEsMaxW = 1024;           // pnp_create's largest side
 
@@ -77,107 +75,16 @@ __global__ __launch_bounds__(kEsThreads) void espirit_gram_kernel(const float2* 
     }
 }
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 cmulc(double2 a, double2 b) { return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a conj(b)
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 cscale(double s, double2 a) { return make_double2(s * a.x, s * a.y); }
-__device__ __forceinline__ double2 cconj(double2 a) { return make_double2(a.x, -a.y); }
-
-// pair k of round r among m + 1 = np indices, p < q (coilcomp_kernels.hip's order)
-__device__ __forceinline__ void rr_pair(int k, int r, int m, int& p, int& q) {
-    int a = r, b = m;
-    if (k) {
-        a = (r + k) % m;
-        b = (r - k + m) % m;
-    }
-    p = min(a, b);
-    q = max(a, b);
-}
-
-struct Rot { double c; double2 s; };       // J = [[c, s], [-conj(s), c]]
-
 // grid (N); ws: per slice G [np][np] (in: the Gram matrix; out: the eigenvalues on its diagonal) then Vt [np][np] (out: Vt[j][row] = V[row][j])
 __global__ __launch_bounds__(kEsEigThreads) void espirit_eig_kernel(double2* __restrict__ ws, int np) {
-    __shared__ double red[kEsEigThreads / 64];
     __shared__ Rot rot[PNP_ESPIRIT_MAX_N / 2];
-    __shared__ double trace;
-    __shared__ int stop;
-    const int m = np - 1, half = np >> 1, tid = threadIdx.x;
     double2* G = ws + (size_t)blockIdx.x * 2 * np * np;
     double2* Vt = G + (size_t)np * np;
-    for (int idx = tid; idx < np * np; idx += kEsEigThreads) {
+    for (int idx = threadIdx.x; idx < np * np; idx += kEsEigThreads) {
         const int r = idx / np, c = idx - r * np;
         Vt[idx] = make_double2(r == c ? 1.0 : 0.0, 0.0);
     }
-    if (tid == 0) {
-        double t = 0.0;
-        for (int i = 0; i < np; ++i) t += G[i * np + i].x;
-        trace = t;
-    }
-    __syncthreads();
-    for (int sweep = 0; sweep < kEsSweeps; ++sweep) {
-        double off = 0.0;
-        for (int idx = tid; idx < np * np; idx += kEsEigThreads) {
-            const int r = idx / np, c = idx - r * np;
-            const double2 v = G[idx];
-            if (r != c) off += v.x * v.x + v.y * v.y;
-        }
-        off = block_sum_fixed<kEsEigThreads>(off, red);
-        if (tid == 0) stop = off <= (kEsEps * trace) * (kEsEps * trace);
-        __syncthreads();
-        if (stop) break;
-        for (int r = 0; r < m; ++r) {
-            if (tid < half) {
-                int p, q;
-                rr_pair(tid, r, m, p, q);
-                const double2 beta = G[p * np + q];
-                Rot j{1.0, make_double2(0.0, 0.0)};
-                if (beta.x != 0.0 || beta.y != 0.0) {
-                    const double ab = hypot(beta.x, beta.y), alpha = G[p * np + p].x, gamma = G[q * np + q].x;
-                    const double tau = (gamma - alpha) / (2.0 * ab);
-                    const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + hypot(1.0, tau));
-                    j.c = 1.0 / sqrt(1.0 + t * t);
-                    const double s = t * j.c;
-                    j.s = make_double2(s * (beta.x / ab), s * (beta.y / ab));
-                    G[p * np + p] = make_double2(alpha - t * ab, 0.0);
-                    G[q * np + q] = make_double2(gamma + t * ab, 0.0);
-                    G[p * np + q] = make_double2(0.0, 0.0);
-                    G[q * np + p] = make_double2(0.0, 0.0);
-                }
-                rot[tid] = j;
-            }
-            __syncthreads();
-            // blocks (pair k, pair l), k > l: B <- Jk^H B Jl, mirrored; then the vectors' columns
-            for (int task = tid; task < half * half; task += kEsEigThreads) {
-                const int k = task / half, l = task - k * half;
-                if (l >= k) continue;
-                int p, q, pl, ql;
-                rr_pair(k, r, m, p, q);
-                rr_pair(l, r, m, pl, ql);
-                const Rot jk = rot[k], jl = rot[l];
-                const double2 b00 = G[p * np + pl], b01 = G[p * np + ql], b10 = G[q * np + pl], b11 = G[q * np + ql];
-                // T = B Jl
-                const double2 t00 = csub(cscale(jl.c, b00), cmulc(b01, jl.s)), t01 = cadd(cmul(b00, jl.s), cscale(jl.c, b01));
-                const double2 t10 = csub(cscale(jl.c, b10), cmulc(b11, jl.s)), t11 = cadd(cmul(b10, jl.s), cscale(jl.c, b11));
-                // N = Jk^H T,  Jk^H = [[c, -s], [conj(s), c]]
-                const double2 n00 = csub(cscale(jk.c, t00), cmul(jk.s, t10)), n01 = csub(cscale(jk.c, t01), cmul(jk.s, t11));
-                const double2 n10 = cadd(cmulc(t00, jk.s), cscale(jk.c, t10)), n11 = cadd(cmulc(t01, jk.s), cscale(jk.c, t11));
-                G[p * np + pl] = n00; G[p * np + ql] = n01; G[q * np + pl] = n10; G[q * np + ql] = n11;
-                G[pl * np + p] = cconj(n00); G[ql * np + p] = cconj(n01); G[pl * np + q] = cconj(n10); G[ql * np + q] = cconj(n11);
-            }
-            for (int task = tid; task < np * half; task += kEsEigThreads) {
-                const int k = task / np, row = task - k * np;
-                int p, q;
-                rr_pair(k, r, m, p, q);
-                const Rot j = rot[k];
-                const double2 up = Vt[p * np + row], uq = Vt[q * np + row];
-                Vt[p * np + row] = csub(cscale(j.c, up), cmulc(uq, j.s));
-                Vt[q * np + row] = cadd(cmul(up, j.s), cscale(j.c, uq));
-            }
-            __syncthreads();
-        }
-    }
+    jacobi_sweeps<kEsEigThreads, kEsSweeps, true>(G, Vt, np, rot);
 }
 
 // grid (ceil(C^2 D^2 / 256), N); kern[n][a][b][dy][dx], nkept[n]

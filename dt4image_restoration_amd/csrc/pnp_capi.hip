@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -105,7 +106,7 @@ struct pnp_engine {
     float2* mc_y = nullptr;      // [N,C,H,W] sgn * S y per coil (reset_kernel's y0s convention)
     float2* mc_work = nullptr;   // [N,C,H,W] coil-image scratch
     float2* mc_sens = nullptr;   // [sens_n,C,H,W]
-    size_t mc_y_cap = 0, mc_work_cap = 0, mc_sens_cap = 0;   // capacities in complex elements
+    size_t mc_y_cap = 0, mc_work_cap = 0, mc_sens_cap = 0;   // capacities in bytes, as every *_cap below
     float2* mc_vec = nullptr;    // [4,N,H,W]: A^H y and the CG vectors r, p, q
     double* mc_part = nullptr;   // [N, pixel_chunks, 2] per-workgroup sums
     double* mc_sc = nullptr;     // [N, 8] CG scalars (rs, bb, alpha, beta, frozen)
@@ -115,13 +116,13 @@ struct pnp_engine {
     // coil compression (pnp_coil_compress_matrix): allocated inside its first call, grown by a call that needs more
     double2* cc_part = nullptr;  // [N, gram_chunks, C, C] per-workgroup Gram partials
     double2* cc_gram = nullptr;  // [N, C, C] Gram for callers that pass none
-    size_t cc_part_cap = 0, cc_gram_cap = 0;   // capacities in complex128 elements
+    size_t cc_part_cap = 0, cc_gram_cap = 0;
     // noise pre-whitening (pnp_noise_cov): allocated inside its first call, grown by a call that needs more
-    double2* pw_part = nullptr;  // [noise_n, whiten_chunks, C, C] per-workgroup covariance partials
-    size_t pw_part_cap = 0;      // capacity in complex128 elements
+    double2* pw_part = nullptr;  // [noise_n, gram_chunks, C, C] per-workgroup covariance partials
+    size_t pw_part_cap = 0;
     // ESPIRiT maps (pnp_espirit_sens): allocated inside its first call, grown by a call that needs more
     void* es_ws = nullptr;       // per slice G and the vectors [2, np, np] complex128, then R [N, C, C, D, D] complex64, then nkept [N]
-    size_t es_cap = 0;           // capacity in bytes
+    size_t es_cap = 0;
     // the prior of pnp_step (pnp_set_prior) and the total-variation denoiser's workspace (allocated inside the first call that runs it)
     int prior = PNP_PRIOR_UNET;
     double tv_scale = 1.0;       // as given; applied as float32
@@ -383,43 +384,61 @@ int run_prox_dual_mc(pnp_engine* e, const float* mu, const float* tact, const fl
     return PNP_OK;
 }
 
-// Grow the coil workspace to hold `y_need`, `work_need`, `sens_need` complex elements (0: leave that buffer alone) and the per-slice vectors.
-// All-or-nothing: every new buffer is allocated before any old one is released; buffers that grow lose their contents (their callers rewrite them).
-int mc_ensure(pnp_engine* e, size_t y_need, size_t work_need, size_t sens_need) {
-    const size_t px = (size_t)e->cfg.n * e->cfg.h * e->cfg.w;
-    const size_t part_bytes = (size_t)e->cfg.n * pixel_chunks(e->cfg.h, e->cfg.w) * 2 * sizeof(double), sc_bytes = (size_t)e->cfg.n * 8 * sizeof(double);
-    struct Want { void** slot; size_t bytes, old_bytes; void* fresh; size_t* cap; size_t new_cap; };
-    Want w[6] = {
-        {(void**)&e->mc_y, y_need > e->mc_y_cap ? y_need * sizeof(float2) : 0, e->mc_y_cap * sizeof(float2), nullptr, &e->mc_y_cap, y_need},
-        {(void**)&e->mc_work, work_need > e->mc_work_cap ? work_need * sizeof(float2) : 0, e->mc_work_cap * sizeof(float2), nullptr, &e->mc_work_cap, work_need},
-        {(void**)&e->mc_sens, sens_need > e->mc_sens_cap ? sens_need * sizeof(float2) : 0, e->mc_sens_cap * sizeof(float2), nullptr, &e->mc_sens_cap, sens_need},
-        {(void**)&e->mc_vec, e->mc_vec ? 0 : 4 * px * sizeof(float2), 0, nullptr, nullptr, 0},
-        {(void**)&e->mc_part, e->mc_part ? 0 : part_bytes, 0, nullptr, nullptr, 0},
-        {(void**)&e->mc_sc, e->mc_sc ? 0 : sc_bytes, 0, nullptr, nullptr, 0},
-    };
-    bool any = false;
-    for (auto& q : w) {
-        if (q.bytes == 0) continue;
+// Grow buffers of the handle's workspace: the one contract of every entry point that allocates inside the call (include/pnpadmm.h).  A slot
+// grows when it needs more bytes than it holds (cap == nullptr: a buffer that is never replaced; its caller asks for its fixed size while the
+// slot is null and for 0 afterwards).  Nothing to grow: PNP_OK without a HIP call.  All-or-nothing: every new buffer is allocated, and
+// zero-filled where asked, before any old one is released, and on failure the new ones are freed and the handle keeps the workspace it had.
+// Buffers that grow lose their contents (their callers rewrite them).
+struct WsSlot { void** ptr; size_t* cap; size_t need; bool zero; };
+int ws_grow(pnp_engine* e, const char* label, std::initializer_list<WsSlot> slots) {
+    void* fresh[6] = {};                                   // mc_ensure's six slots are the most
+    const auto held = [](const WsSlot& q) { return q.cap ? *q.cap : 0; };
+    const auto undo = [&] { for (void* f : fresh) (void)hipFree(f); };   // hipFree(nullptr) is a no-op
+    bool any = false, replaces = false;
+    size_t i = 0;
+    for (const WsSlot& q : slots) {
+        void*& f = fresh[i++];
+        if (q.need <= held(q)) continue;
         any = true;
-        if (hipMalloc(&q.fresh, q.bytes) != hipSuccess) {
-            for (auto& r : w) (void)hipFree(r.fresh);
-            return fail(PNP_ERR_NOMEM, "coil workspace: %zu bytes (the handle keeps the workspace it had)", q.bytes);
+        replaces |= *q.ptr != nullptr;
+        if (hipMalloc(&f, q.need) != hipSuccess) {
+            f = nullptr;
+            undo();
+            return fail(PNP_ERR_NOMEM, "%s: %zu bytes (the handle keeps the workspace it had)", label, q.need);
         }
     }
     if (!any) return PNP_OK;
-    if (w[5].fresh && hipMemset(w[5].fresh, 0, sc_bytes) != hipSuccess) {
-        for (auto& r : w) (void)hipFree(r.fresh);
-        return fail(PNP_ERR_HIP, "coil workspace: hipMemset failed");
+    i = 0;
+    for (const WsSlot& q : slots) {
+        void* f = fresh[i++];
+        if (f && q.zero && hipMemset(f, 0, q.need) != hipSuccess) {
+            undo();
+            return fail(PNP_ERR_HIP, "%s: hipMemset failed", label);
+        }
     }
-    (void)hipDeviceSynchronize();                          // no launch still reads a buffer being replaced
-    for (auto& q : w) {
-        if (!q.fresh) continue;
-        (void)hipFree(*q.slot);
-        *q.slot = q.fresh;
-        e->ws_bytes += q.bytes - q.old_bytes;
-        if (q.cap) *q.cap = q.new_cap;
+    if (replaces) (void)hipDeviceSynchronize();            // no launch still reads a buffer being replaced
+    i = 0;
+    for (const WsSlot& q : slots) {
+        void* f = fresh[i++];
+        if (!f) continue;
+        (void)hipFree(*q.ptr);
+        *q.ptr = f;
+        e->ws_bytes += q.need - held(q);
+        if (q.cap) *q.cap = q.need;
     }
     return PNP_OK;
+}
+
+// The coil workspace: `y_need`, `work_need`, `sens_need` complex elements (0: leave that buffer alone) and the per-slice vectors
+int mc_ensure(pnp_engine* e, size_t y_need, size_t work_need, size_t sens_need) {
+    const size_t px = (size_t)e->cfg.n * e->cfg.h * e->cfg.w;
+    const size_t part_bytes = (size_t)e->cfg.n * pixel_chunks(e->cfg.h, e->cfg.w) * 2 * sizeof(double), sc_bytes = (size_t)e->cfg.n * 8 * sizeof(double);
+    return ws_grow(e, "coil workspace", {{(void**)&e->mc_y, &e->mc_y_cap, y_need * sizeof(float2), false},
+                                        {(void**)&e->mc_work, &e->mc_work_cap, work_need * sizeof(float2), false},
+                                        {(void**)&e->mc_sens, &e->mc_sens_cap, sens_need * sizeof(float2), false},
+                                        {(void**)&e->mc_vec, nullptr, e->mc_vec ? 0 : 4 * px * sizeof(float2), false},
+                                        {(void**)&e->mc_part, nullptr, e->mc_part ? 0 : part_bytes, false},
+                                        {(void**)&e->mc_sc, nullptr, e->mc_sc ? 0 : sc_bytes, true}});
 }
 
 // argument errors shared by the three multi-coil entry points that take maps and a mask: before any HIP call
@@ -467,90 +486,32 @@ int mc_install(pnp_engine* e, const float2* x0, const float2* y0, const float2* 
     return PNP_OK;
 }
 
-// The workspace of pnp_estimate_sens: the maxima / smax buffer and, with `own_rss`, the rss plane.  Neither is ever replaced, so nothing in flight
-// reads a buffer that goes away; all-or-nothing: both allocations are made before either is installed.
+// The workspace of pnp_estimate_sens: the maxima / smax buffer and, with `own_rss`, the rss plane
 int cm_ensure(pnp_engine* e, bool own_rss) {
     const size_t max_bytes = (size_t)e->cfg.n * (pixel_chunks(e->cfg.h, e->cfg.w) + 1) * sizeof(float);
     const size_t rss_bytes = (size_t)e->cfg.n * e->cfg.h * e->cfg.w * sizeof(float);
-    void* fresh_max = nullptr;
-    void* fresh_rss = nullptr;
-    if (!e->cm_max && hipMalloc(&fresh_max, max_bytes) != hipSuccess)
-        return fail(PNP_ERR_NOMEM, "coil map workspace: %zu bytes (the handle keeps the workspace it had)", max_bytes);
-    if (own_rss && !e->cm_rss && hipMalloc(&fresh_rss, rss_bytes) != hipSuccess) {
-        (void)hipFree(fresh_max);
-        return fail(PNP_ERR_NOMEM, "coil map workspace: %zu bytes (the handle keeps the workspace it had)", rss_bytes);
-    }
-    if (fresh_max) { e->cm_max = (float*)fresh_max; e->ws_bytes += max_bytes; }
-    if (fresh_rss) { e->cm_rss = (float*)fresh_rss; e->ws_bytes += rss_bytes; }
-    return PNP_OK;
+    return ws_grow(e, "coil map workspace", {{(void**)&e->cm_max, nullptr, e->cm_max ? 0 : max_bytes, false},
+                                            {(void**)&e->cm_rss, nullptr, own_rss && !e->cm_rss ? rss_bytes : 0, false}});
 }
 
-// The workspace of pnp_coil_compress_matrix: `part_need` complex128 Gram partials and, for callers that pass no Gram, `gram_need` more.
-// All-or-nothing, as mc_ensure: every new buffer is allocated before an old one is released.
+// The workspace of pnp_coil_compress_matrix: `part_need` complex128 Gram partials and, for callers that pass no Gram, `gram_need` more
 int cc_ensure(pnp_engine* e, size_t part_need, size_t gram_need) {
-    void* fresh_part = nullptr;
-    void* fresh_gram = nullptr;
-    if (part_need > e->cc_part_cap && hipMalloc(&fresh_part, part_need * sizeof(double2)) != hipSuccess)
-        return fail(PNP_ERR_NOMEM, "coil compression workspace: %zu bytes (the handle keeps the workspace it had)", part_need * sizeof(double2));
-    if (gram_need > e->cc_gram_cap && hipMalloc(&fresh_gram, gram_need * sizeof(double2)) != hipSuccess) {
-        (void)hipFree(fresh_part);
-        return fail(PNP_ERR_NOMEM, "coil compression workspace: %zu bytes (the handle keeps the workspace it had)", gram_need * sizeof(double2));
-    }
-    if (!fresh_part && !fresh_gram) return PNP_OK;
-    if (e->cc_part || e->cc_gram) (void)hipDeviceSynchronize();   // no launch still reads a buffer being replaced
-    if (fresh_part) {
-        (void)hipFree(e->cc_part);
-        e->cc_part = (double2*)fresh_part;
-        e->ws_bytes += (part_need - e->cc_part_cap) * sizeof(double2);
-        e->cc_part_cap = part_need;
-    }
-    if (fresh_gram) {
-        (void)hipFree(e->cc_gram);
-        e->cc_gram = (double2*)fresh_gram;
-        e->ws_bytes += (gram_need - e->cc_gram_cap) * sizeof(double2);
-        e->cc_gram_cap = gram_need;
-    }
-    return PNP_OK;
+    return ws_grow(e, "coil compression workspace", {{(void**)&e->cc_part, &e->cc_part_cap, part_need * sizeof(double2), false},
+                                                    {(void**)&e->cc_gram, &e->cc_gram_cap, gram_need * sizeof(double2), false}});
 }
 
-// The workspace of pnp_noise_cov: `need` complex128 covariance partials, replaced by a larger buffer when a call needs more.
+// The workspace of pnp_noise_cov: `need` complex128 covariance partials
 int pw_ensure(pnp_engine* e, size_t need) {
-    if (need <= e->pw_part_cap) return PNP_OK;
-    void* fresh = nullptr;
-    if (hipMalloc(&fresh, need * sizeof(double2)) != hipSuccess)
-        return fail(PNP_ERR_NOMEM, "noise covariance workspace: %zu bytes (the handle keeps the workspace it had)", need * sizeof(double2));
-    if (e->pw_part) (void)hipDeviceSynchronize();   // no launch still reads the buffer being replaced
-    (void)hipFree(e->pw_part);
-    e->pw_part = (double2*)fresh;
-    e->ws_bytes += (need - e->pw_part_cap) * sizeof(double2);
-    e->pw_part_cap = need;
-    return PNP_OK;
+    return ws_grow(e, "noise covariance workspace", {{(void**)&e->pw_part, &e->pw_part_cap, need * sizeof(double2), false}});
 }
 
-// The workspace of pnp_espirit_sens beyond cm_ensure's: one buffer of `need` bytes, replaced by a larger one when a call needs more.
-int es_ensure(pnp_engine* e, size_t need) {
-    if (need <= e->es_cap) return PNP_OK;
-    void* fresh = nullptr;
-    if (hipMalloc(&fresh, need) != hipSuccess)
-        return fail(PNP_ERR_NOMEM, "ESPIRiT workspace: %zu bytes (the handle keeps the workspace it had)", need);
-    if (e->es_ws) (void)hipDeviceSynchronize();   // no launch still reads the buffer being replaced
-    (void)hipFree(e->es_ws);
-    e->es_ws = fresh;
-    e->ws_bytes += need - e->es_cap;
-    e->es_cap = need;
-    return PNP_OK;
-}
+// The workspace of pnp_espirit_sens beyond cm_ensure's: one buffer of `need` bytes
+int es_ensure(pnp_engine* e, size_t need) { return ws_grow(e, "ESPIRiT workspace", {{&e->es_ws, &e->es_cap, need, false}}); }
 
-// The workspace of the total-variation denoiser: one (py, px) plane, never replaced.
+// The workspace of the total-variation denoiser: one (py, px) plane
 int tv_ensure(pnp_engine* e) {
-    if (e->tv_p) return PNP_OK;
     const size_t bytes = (size_t)e->cfg.n * e->cfg.h * e->cfg.w * sizeof(float2);
-    void* fresh = nullptr;
-    if (hipMalloc(&fresh, bytes) != hipSuccess)
-        return fail(PNP_ERR_NOMEM, "total-variation workspace: %zu bytes (the handle keeps the workspace it had)", bytes);
-    e->tv_p = (float2*)fresh;
-    e->ws_bytes += bytes;
-    return PNP_OK;
+    return ws_grow(e, "total-variation workspace", {{(void**)&e->tv_p, nullptr, e->tv_p ? 0 : bytes, false}});
 }
 
 // out = TV(v, scale * lam, iters), v = the plane `v` or Re z - Re u.  p travels between launches through two planes in turn: the
@@ -1237,7 +1198,7 @@ int pnp_coil_compress_matrix(pnp_handle e, const float* y0, int coils, int acs_h
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     const size_t cc = (size_t)coils * coils;
-    if (int rc = cc_ensure(e, (size_t)N * gram_chunks(acs_h, acs_w) * cc, gram ? 0 : (size_t)N * cc)) return rc;
+    if (int rc = cc_ensure(e, (size_t)N * gram_chunks(acs_h * acs_w) * cc, gram ? 0 : (size_t)N * cc)) return rc;
     double2* const g = gram ? (double2*)gram : e->cc_gram;
     Prof p(e, s, PROF_OTHER, -1);
     HIP_TRY(launch_coilcomp_gram((const float2*)y0, coils, acs_h, acs_w, e->cc_part, g, N, H, W, s));
@@ -1284,7 +1245,7 @@ int pnp_noise_cov(pnp_handle e, const float* noise, int noise_n, int coils, int 
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = pw_ensure(e, (size_t)noise_n * whiten_chunks(samples) * coils * coils)) return rc;
+    if (int rc = pw_ensure(e, (size_t)noise_n * gram_chunks(samples) * coils * coils)) return rc;
     Prof p(e, s, PROF_OTHER, -1);
     HIP_TRY(launch_prewhiten_cov((const float2*)noise, noise_n, coils, samples, e->pw_part, (double2*)psi, s));
     p.end(2);

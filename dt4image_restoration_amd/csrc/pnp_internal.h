@@ -270,11 +270,15 @@ hipError_t launch_coilmap_max(const float* partial, float* smax, int N, int H, i
 hipError_t launch_coilmap_normalise(float2* l, int C, const float* rss, const float* smax, float thresh, int N, int H, int W, hipStream_t s);
 
 // ---- coil compression (coilcomp_kernels.hip) --------------------------------------------------------
-// The block's bins are dealt to gram_chunks(acs_h, acs_w) workgroups per slice, gram_chunk_bins(bins) consecutive bins each: kGramMinBins, or
-// for blocks above kGramMinBins * kGramMaxChunks bins the 32-multiple that gives at most kGramMaxChunks workgroups.
+// The chunk rule of a Gram accumulation (hermitian.h), shared with the noise covariance: `count` samples (the block's bins, a scan's samples)
+// are dealt to gram_chunks(count) workgroups, gram_chunk_len(count) consecutive samples each: kGramMinBins, or for counts above
+// kGramMinBins * kGramMaxChunks the 32-multiple that gives at most kGramMaxChunks workgroups.
 static constexpr int kGramMinBins = 1024, kGramMaxChunks = 64;
-int gram_chunk_bins(int bins);
-int gram_chunks(int acs_h, int acs_w);
+inline int gram_chunk_len(long long count) {
+    const long long per = ((count + kGramMaxChunks - 1) / kGramMaxChunks + 31) / 32 * 32;
+    return per < kGramMinBins ? kGramMinBins : (int)per;
+}
+inline int gram_chunks(long long count) { return (int)((count + gram_chunk_len(count) - 1) / gram_chunk_len(count)); }
 // gram: [N, C, C] complex128 = sum over the centred acs_h x acs_w block of y_a conj(y_b); partial: [N, gram_chunks, C, C] complex128.  Two launches.
 hipError_t launch_coilcomp_gram(const float2* y, int C, int acs_h, int acs_w, double2* partial, double2* gram, int N, int H, int W, hipStream_t s);
 // cmat: [N, C, C] complex64, eig: [N, C] float32 from gram: one workgroup per slice
@@ -283,10 +287,7 @@ hipError_t launch_coilcomp_eig(const double2* gram, int C, float2* cmat, float* 
 hipError_t launch_coilcomp_apply(const float2* in, const float2* cmat, int cmat_n, int C, int V, float2* out, int N, int H, int W, hipStream_t s);
 
 // ---- coil noise pre-whitening (prewhiten_kernels.hip) -----------------------------------------------
-// A scan's samples are dealt to whiten_chunks(S) workgroups of whiten_chunk_samples(S) consecutive samples each, by the rule of gram_chunk_bins.
-int whiten_chunk_samples(int samples);
-int whiten_chunks(int samples);
-// psi: [noise_n, C, C] complex128 = (1 / S) sum_s n_a conj(n_b); noise: [noise_n, C, S]; partial: [noise_n, whiten_chunks, C, C] complex128.  Two launches.
+// psi: [noise_n, C, C] complex128 = (1 / S) sum_s n_a conj(n_b); noise: [noise_n, C, S]; partial: [noise_n, gram_chunks(S), C, C] complex128.  Two launches.
 hipError_t launch_prewhiten_cov(const float2* noise, int noise_n, int C, int S, double2* partial, double2* psi, hipStream_t s);
 // wmat, lmat (or nullptr): [psi_n, C, C] complex64 lower-triangular, info: [psi_n]; one workgroup per matrix
 hipError_t launch_prewhiten_chol(const double2* psi, int psi_n, int C, float2* wmat, float2* lmat, int* info, hipStream_t s);

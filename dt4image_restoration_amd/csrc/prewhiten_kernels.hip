@@ -2,11 +2,9 @@
 // Cholesky factor and the inverse of that factor, and the triangular channel mix that makes the noise white and equal across channels
 //     Psi[a][b] = (1 / S) sum_s n_a[s] conj(n_b[s])        Psi = L L^H        W = L^-1        out[v] = sum_{c <= v} W[v][c] in[c]
 //
-//   prewhiten_cov_kernel     grid (chunks, noise_n): samples [g * per, (g + 1) * per) of one scan, per = whiten_chunk_samples(S) (the rule of
-//                            coilcomp_gram_kernel); every thread owns entries (a, b), b <= a, and walks the samples IN ORDER:
-//                            re += ar br; re += ai bi; im += ai br; im -= ar bi, float64 (the products of float32 values are exact in float64)
-//   prewhiten_cov_sum_kernel Psi[a][b] = (partial[0] + partial[1] + ...) / S in chunk order from 0.0, one division; Psi[b][a] = conj, the
-//                            diagonal's imaginary part 0
+//   prewhiten_cov_kernel     grid (chunks, noise_n): samples [g * per, (g + 1) * per) of one scan, per = gram_chunk_len(S), walked IN ORDER by
+//                            gram_partial (hermitian.h)
+//   prewhiten_cov_sum_kernel Psi = (the chunks' partials summed in chunk order) / S, one division, mirrored (gram_chunk_sum, hermitian.h)
 //   prewhiten_chol_kernel    grid (psi_n), one workgroup per matrix, L and W in LDS (2 * 16 C (C | 1) bytes: the row stride is odd, so a column
 //                            walk does not stay on one bank), float64.  Column j of L, left-looking: thread i >= j sums
 //                            s = sum_{k < j} L[i][k] conj(L[j][k]), k ascending from 0.0; thread j tests the pivot d = Re Psi[j][j] - Re s and stores
@@ -23,96 +21,34 @@
 // No atomics anywhere: a matrix's or slice's bits depend on its own input only.
 #include "pnp_internal.h"
 #include "block_reduce.h"
+#include "hermitian.h"
 #include "../../include/pnpadmm.h"
 
 namespace pnp {
-
-int whiten_chunk_samples(int samples) {
-    long long per = ((long long)samples + kGramMaxChunks - 1) / kGramMaxChunks;
-    per = (per + 31) / 32 * 32;
-    return per < kGramMinBins ? kGramMinBins : (int)per;
-}
-int whiten_chunks(int samples) {
-    const long long per = whiten_chunk_samples(samples);
-    return (int)(((long long)samples + per - 1) / per);
-}
 
 namespace {
 
 constexpr int kPwThreads = 256;
 constexpr int kPwMax = PNP_PW_MAX_COILS;
 constexpr int kCovTile = 32;                                    // samples staged at a time
-constexpr int kCovEnt = kPwMax * kPwMax / kPwThreads;           // covariance entries per thread at the most
-static_assert(kPwMax * kPwMax % kPwThreads == 0, "whole entries per thread");
 static_assert(kPwMax <= kPwThreads, "a thread per row of the factorisation");
 constexpr double kPivotEps = 1e-12;
 
 // grid (chunks, noise_n); partial[n][g][a * C + b], b <= a
 __global__ __launch_bounds__(kPwThreads) void prewhiten_cov_kernel(const float2* __restrict__ noise, int C, int S, int per,
                                                                    double2* __restrict__ partial) {
-    __shared__ float2 tile[kCovTile * kPwMax];                   // [sample][coil]
     const int n = blockIdx.y, g = blockIdx.x;
     const long long first = (long long)g * per;
     const int last = (int)min((long long)S, first + per);
-    int ea[kCovEnt], eb[kCovEnt];
-    bool on[kCovEnt];
-    double re[kCovEnt], im[kCovEnt];
-#pragma unroll
-    for (int e = 0; e < kCovEnt; ++e) {
-        const int idx = e * kPwThreads + threadIdx.x;
-        ea[e] = idx / C;
-        eb[e] = idx - ea[e] * C;
-        on[e] = idx < C * C && eb[e] <= ea[e];
-        re[e] = 0.0;
-        im[e] = 0.0;
-    }
-    for (int t0 = (int)first; t0 < last; t0 += kCovTile) {
-        const int nb = min(kCovTile, last - t0);
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < kCovTile * C; idx += kPwThreads) {
-            const int c = idx / kCovTile, b = idx - c * kCovTile;
-            if (b < nb) tile[b * C + c] = noise[((size_t)n * C + c) * (size_t)S + (size_t)(t0 + b)];
-        }
-        __syncthreads();
-        for (int b = 0; b < nb; ++b) {
-#pragma unroll
-            for (int e = 0; e < kCovEnt; ++e) {
-                if (!on[e]) continue;
-                const float2 p = tile[b * C + ea[e]], q = tile[b * C + eb[e]];
-                re[e] += (double)p.x * (double)q.x;
-                re[e] += (double)p.y * (double)q.y;
-                im[e] += (double)p.y * (double)q.x;
-                im[e] -= (double)p.x * (double)q.y;
-            }
-        }
-    }
-    double2* out = partial + ((size_t)n * gridDim.x + g) * C * C;
-#pragma unroll
-    for (int e = 0; e < kCovEnt; ++e)
-        if (on[e]) out[e * kPwThreads + threadIdx.x] = make_double2(re[e], im[e]);
+    const auto load = [&](int c, int i) { return noise[((size_t)n * C + c) * (size_t)S + (size_t)i]; };
+    gram_partial<kPwThreads, kPwMax, kCovTile>(C, (int)first, last, load, partial + ((size_t)n * gridDim.x + g) * C * C);
 }
 
 // grid (ceil(C * C / threads), noise_n); psi[n][a][b] = (sum of the chunks' partials in chunk order) / S
 __global__ __launch_bounds__(kPwThreads) void prewhiten_cov_sum_kernel(const double2* __restrict__ partial, int chunks, int C, int S,
                                                                        double2* __restrict__ psi) {
-    const int n = blockIdx.y, idx = blockIdx.x * kPwThreads + threadIdx.x;
-    const int a = idx / C, b = idx - a * C;
-    if (idx >= C * C || b > a) return;
-    double re = 0.0, im = 0.0;
-    for (int g = 0; g < chunks; ++g) {
-        const double2 v = partial[((size_t)n * chunks + g) * C * C + idx];
-        re += v.x;
-        im += v.y;
-    }
-    re /= (double)S;
-    im /= (double)S;
-    double2* P = psi + (size_t)n * C * C;
-    if (a == b) {
-        P[idx] = make_double2(re, 0.0);
-    } else {
-        P[idx] = make_double2(re, im);
-        P[b * C + a] = make_double2(re, -im);
-    }
+    const int n = blockIdx.y;
+    gram_chunk_sum<kPwThreads, true>(partial + (size_t)n * chunks * C * C, chunks, C, (double)S, psi + (size_t)n * C * C);
 }
 
 // grid (psi_n); LDS: L [C][ld] double2, W [C][ld] double2, ld = C | 1
@@ -279,8 +215,8 @@ __global__ __launch_bounds__(kPwThreads) void prewhiten_apply_kernel(const float
 }  // namespace
 
 hipError_t launch_prewhiten_cov(const float2* noise, int noise_n, int C, int S, double2* partial, double2* psi, hipStream_t s) {
-    const int chunks = whiten_chunks(S);
-    hipLaunchKernelGGL(prewhiten_cov_kernel, dim3(chunks, noise_n), dim3(kPwThreads), 0, s, noise, C, S, whiten_chunk_samples(S), partial);
+    const int chunks = gram_chunks(S);
+    hipLaunchKernelGGL(prewhiten_cov_kernel, dim3(chunks, noise_n), dim3(kPwThreads), 0, s, noise, C, S, gram_chunk_len(S), partial);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     hipLaunchKernelGGL(prewhiten_cov_sum_kernel, dim3((C * C + kPwThreads - 1) / kPwThreads, noise_n), dim3(kPwThreads), 0, s, partial, chunks, C,
                        S, psi);
