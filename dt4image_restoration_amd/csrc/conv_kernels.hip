@@ -853,6 +853,7 @@ Tuning tuning_from_env() {
     t.no_f4_fused_last = getenv("PNP_NO_F4_FUSED_LAST") != nullptr;
     t.no_f4_fused_first = getenv("PNP_NO_F4_FUSED_FIRST") != nullptr;
     if (const char* v = getenv("PNP_WINO_F4_MT16")) t.f4_mt16 = atoi(v);
+    if (const char* v = getenv("PNP_WINO_F4_CS")) t.f4_cs = atoi(v);
     if (const char* v = getenv("PNP_WINO_F4_ORDER")) t.f4_order = atoi(v) != 0;
     t.bf16_f32_acts = getenv("PNP_BF16_F32_ACTS") != nullptr;
     t.bf16_no_ws = getenv("PNP_BF16_NO_WS") != nullptr;

@@ -68,14 +68,14 @@ bool plan_denoiser(const pnp_config& cfg, const Tuning& tune, DenoiserPlan* out,
             rec[li - 1].pooled = r.src0 = {kLayers[li - 1].level, SLOT_POOL};
             P.pool_ok[kLayers[li - 1].level] = true;
         }
-        r.wino = winograd_plan(cfg.n, lh, lw, L.cin, L.cout, r.src_mode, tune);
+        r.wino = winograd_plan(cfg.n, lh, lw, L.cin, L.cout, r.src_mode, tune, L.cskip);
         if (li == kTail && r.wino.algo == 4 && !keep_stages && (tune.no_f4_fused_last || r.wino.bn != 32 || r.wino.mt != 32)) {
             // up4.conv-2 carries the fused last layer (1x1 conv + residual + clamp) in its epilogue: the F(4x4) kernel's
             // 32-channel variant has it (DPP reduce-scatter over a pixel's channels); PNP_NO_F4_FUSED_LAST puts the layer
             // back on the F(2x2) kernel, which walks whole pixels there
             Tuning t2 = tune;
             t2.no_f4 = true;
-            r.wino = winograd_plan(cfg.n, lh, lw, L.cin, L.cout, r.src_mode, t2);
+            r.wino = winograd_plan(cfg.n, lh, lw, L.cin, L.cout, r.src_mode, t2, L.cskip);
         }
         // (the producer / consumer kernel's upsample is the separable form: only on heights with the regular line structure)
         const bool ws_ok = !tune.bf16_no_ws && (r.src_mode != SRC_UPCAT || upsample_lines_regular(lh));

@@ -1432,6 +1432,21 @@ int pnp_conv_algorithms(pnp_handle e, int32_t* algo28) {
     PNP_API_END("pnp_conv_algorithms")
 }
 
+int pnp_conv_schedules(pnp_handle e, int32_t* sched28) {
+    PNP_API_BEGIN
+    if (!e || !sched28) return fail(PNP_ERR_INVALID, "pnp_conv_schedules: null argument");
+    if (e->cfg.flags & PNP_FLAG_NO_DENOISER) return fail(PNP_ERR_STATE, "pnp_conv_schedules: handle has no denoiser");
+    for (int i = 0; i < N_LAYERS; ++i) {
+        const int at = e->dplan.launch_of[i];
+        sched28[i] = 0;
+        if (at < 0 || e->dplan.family[i] != FAM_WINO4) continue;
+        const WinoPlan& w = e->dplan.launch[at].wino;
+        sched28[i] = w.cs ? 4 : (w.mt == 16 ? 3 : (w.phased ? 2 : 1));
+    }
+    return PNP_OK;
+    PNP_API_END("pnp_conv_schedules")
+}
+
 int pnp_profile_reset(pnp_handle e) {
     PNP_API_BEGIN
     if (!e) return fail(PNP_ERR_INVALID, "null handle");

@@ -28,6 +28,8 @@ struct Tuning {
     bool bf16_no_holdhi = false;  // PNP_BF16_NO_HOLDHI (ablation): the 32 -> 32 layers of the bf16 mode stream their weights instead of holding them
     bool bf16_w1 = false;         // PNP_BF16_W1 (ablation): bf16 mode with ONE bf16 term per weight (the round-3 arithmetic: 0.015 dB of
                                   // PSNR drift against the f32 reference over configs[4]'s 50 iterations) instead of hi + lo
+    int f4_cs = 1;                // PNP_WINO_F4_CS: the cout-split F(4x4) schedule (16 tiles x 128 channels per workgroup, conv3x3_wino4c_kernel):
+                                  // 0 = never, 1 = the default rule (winograd_plan), 2 = every layer the schedule can take
     int f4_order = 1;             // PNP_WINO_F4_ORDER (experiments): 0 = spatial tiles dealt round-robin over the XCDs (rounds 1-2)
     int splitk_inlaunch = 0;      // PNP_SPLITK_INLAUNCH (experiments): 1 = split-K planes combined inside the conv launch (agent-scope accesses,
                                   // no fence) instead of by splitk_reduce_kernel
@@ -125,10 +127,12 @@ struct WinoPlan {
     int stack;         // F(4x4) on 16 x 16 images: two slices stacked into one 32-tile workgroup
     int mt;            // F(4x4): tiles per workgroup (32, or 16 = two independent 4-wave workgroups per CU)
     int phased;        // F(4x4), 64-channel blocks, plain source: the two tile halves run half a chunk apart (conv3x3_wino4p_kernel)
+    int cs;            // F(4x4), Cout % 128 == 0: one 16-tile M-block x 128 channels per workgroup (conv3x3_wino4c_kernel); bn = 128, mt = 16
     int order;         // F(4x4): 1 = every XCD walks a contiguous range of spatial tiles (halo pixels shared through its L2), 0 = tiles dealt round-robin
 };
 // `src_mode` = the source mode the layer will be LAUNCHED with (a POOL layer whose producer writes the pooled copy runs PLAIN)
-WinoPlan winograd_plan(int N, int H, int W, int Cin, int Cout, int src_mode, const Tuning& t);
+// `Cskip`: channels an upsample + concat layer takes from its skip tensor (0: unknown - such a layer is then not planned on the cout-split schedule)
+WinoPlan winograd_plan(int N, int H, int W, int Cin, int Cout, int src_mode, const Tuning& t, int Cskip = 0);
 bool upsample_lines_regular(int H);   // winograd4_kernels.hip: the x2 upsample to H rows reads lines floor((g - 1) / 2), + 1 in float32 too
 size_t winograd4_pack_floats(int cin, int cout);
 void pack_winograd4_weights(const float* oihw, int cin, int cout, int ck, float* dst);

@@ -27,12 +27,15 @@
 // profiles/r02_wino4_stamps.md).  + bias, LeakyReLU, NHWC stores (16 consecutive channels = 64 bytes per pixel and wave, the
 // neighbouring wave writes the other half of the line) and the 2x2 max-pooled copy for the next stage from the same registers.
 //
-// Three schedules of the same arithmetic (winograd_plan picks per layer):
+// Four schedules of the same arithmetic (winograd_plan picks per layer):
 //   conv3x3_wino4_kernel<.., WN = 2, MT = 32>  8 waves in step (barrier - transform - barrier - MFMAs), one workgroup per CU
 //   conv3x3_wino4p_kernel                      8 waves, the two tile halves half a chunk apart: one wave of every SIMD is in its
 //                                              MFMA phase while the other transforms (plain layers with Cin >= 128)
 //   conv3x3_wino4_kernel<.., MT = 16 / WN = 1> 4-wave workgroups (16 tiles x 64 channels / 32 tiles x 32 channels), two
 //                                              independent ones per CU (upsample + concat layers, Cin <= 64, Cout = 32)
+//   conv3x3_wino4c_kernel                      8 waves on 16 tiles x 128 channels: one patch, one input transform and one interpolation
+//                                              per 128 output channels, a chunk ahead (PNP_WINO_F4_CS; plain and upsample + concat layers
+//                                              with Cout % 128 == 0; the default rule takes up1.conv-0 and up2.conv-0)
 #include "pnp_internal.h"
 #include "conv_staging.h"
 #include <type_traits>
@@ -195,6 +198,94 @@ __device__ __forceinline__ void wino4_decode(int bid, int ny, int ntiles, int or
         cby = slot - lt * ny;
         bt = lt < tpx ? xcd * tpx + lt : ntiles;           // (grid padding)
     }
+}
+
+// ---- upsampled chunks (SRC_UPCAT): the patch is interpolated from the tile's low-res source region parked in LDS (ATen
+// upsample_bilinear2d, align_corners=True: src = dst * (in-1)/(out-1), weights (1-l, l), noise.py:39,46):
+// out = wy0 (wx0 p[i0][c0] + wx1 p[i0][c1]) + wy1 (... p[i1] ...).
+// SEPARABLE (round 4): a lane owns one (patch column, 4-channel piece) and the rows of its row group.  It first forms
+// t[k] = wx0 p[k][c0] + wx1 p[k][c1] for the low-res lines its rows touch - every read at a compile-time offset from one
+// address, all in flight together - and then each patch row as a weighted sum of two of them: for an exact x2 upsample the
+// source lines of output row g >= 1 are floor((g - 1) / 2) and the next (winograd_plan checks that the float product
+// rh * g ATen evaluates agrees for every row of this image height - it does for every even height up to 1024), so patch row y
+// of a tile whose first row is even touches lines s, s + 1 with s = ty0 / 2 - 1 + (y >> 1): two compile-time registers; the
+// per-row table holds their weights, filled from the float formula.  Same products and sums per output value as
+// interpolating each piece from its four source pixels, ~7 packed vector instructions per output piece instead of 27 and
+// three LDS round trips per chunk instead of two per piece (the f32 MFMAs share the vector issue port: interpolation was
+// 0.20-0.25 of these kernels' lifetime, profiles/r03_wino4_stamps.md).  PW x PPP lanes of IWPG waves work per row group, ING
+// groups split the rows among the NW waves that interpolate.
+template <int PH, int PW, int PPP, int NW>
+struct Wino4Interp {
+    static constexpr int IPAIRS = PW * PPP, IWPG = (IPAIRS + 63) / 64, ING = NW / IWPG;
+    static constexpr int IRG = (((PH + (ING > 0 ? ING : 1) - 1) / (ING > 0 ? ING : 1)) + 1) & ~1;   // rows per group, even: (y >> 1) splits into group and row part
+    static constexpr int IK = IRG / 2 + 1;                                // low-res lines a row group touches
+};
+// `w` / `t`: this wave's / thread's index among the NW waves that interpolate (w wave-uniform).  The patch layout is the kernel's:
+// slot(y, x, part) = offset of channels 4 part .. 4 part + 3 of patch pixel (y, x), ROWSTEP = floats from one patch row to the next,
+// put(offset, v) stores four channels there.
+template <int PH, int PW, int PPP, int LH, int LW, int LP, int NW, int ROWSTEP, class Slot, class Put>
+__device__ __forceinline__ void wino4_interpolate(const float* lowres, const float* rowT, const float* colT, int w, int t, Slot slot, Put put) {
+    typedef Wino4Interp<PH, PW, PPP, NW> G;
+    constexpr int IPAIRS = G::IPAIRS, IWPG = G::IWPG, ING = G::ING, IRG = G::IRG, IK = G::IK;
+    const int ig = w / IWPG;                               // this wave's row group (wave-uniform)
+    const int it = t - ig * (IWPG * 64);
+    if (ig >= ING || it >= IPAIRS) return;
+    const int x = it / PPP, part = it % PPP;
+    const int yb = ig * IRG;
+    const float4 ct = *reinterpret_cast<const float4*>(&colT[4 * x]);
+    const float* const l0 = &lowres[__float_as_int(ct.x) + part * 4 + (yb / 2) * (LW * LP)];
+    const float* const l1 = &lowres[__float_as_int(ct.y) + part * 4 + (yb / 2) * (LW * LP)];
+    const v2f wx0 = v2f{ct.z, ct.z}, wx1 = v2f{ct.w, ct.w};
+    v2f tl[IK], th_[IK];
+#pragma unroll
+    for (int k = 0; k < IK; ++k) {                         // wx0 * p[line][c0] + wx1 * p[line][c1], 4 channels
+        if ((yb / 2 + k) < LH) {                           // (wave-uniform; lines past the region belong to rows past the patch)
+            const float4 pa = *reinterpret_cast<const float4*>(l0 + k * (LW * LP)), pb = *reinterpret_cast<const float4*>(l1 + k * (LW * LP));
+            tl[k] = __builtin_elementwise_fma(wx0, v2f{pa.x, pa.y}, wx1 * v2f{pb.x, pb.y});
+            th_[k] = __builtin_elementwise_fma(wx0, v2f{pa.z, pa.w}, wx1 * v2f{pb.z, pb.w});
+        } else { tl[k] = v2f{0.f, 0.f}; th_[k] = v2f{0.f, 0.f}; }
+    }
+    const int pdst = slot(yb, x, part);
+#pragma unroll
+    for (int j = 0; j < IRG; ++j) {
+        if (yb + j < PH) {                                 // (wave-uniform)
+            const float4 rw = *reinterpret_cast<const float4*>(&rowT[4 * (yb + j)]);
+            const v2f wa = v2f{rw.x, rw.x}, wb = v2f{rw.y, rw.y};
+            const int k = j >> 1;
+            const v2f olo = __builtin_elementwise_fma(wa, tl[k], wb * tl[k + 1]);
+            const v2f ohi = __builtin_elementwise_fma(wa, th_[k], wb * th_[k + 1]);
+            put(pdst + j * ROWSTEP, make_float4(olo.x, olo.y, ohi.x, ohi.y));
+        }
+    }
+}
+// The interpolation's coordinates are the same for every chunk: one table entry per patch row and column, built once by the
+// first PH + PW threads.  Pixels outside the image (the conv's zero padding) get zero weights.  Row entry: the weights of the row's
+// two candidate source lines s, s + 1 (see above); column entry: {offsets of the two source columns in the region, their weights}.
+template <int PH, int PW, int LP>
+__device__ __forceinline__ void wino4_upsample_tables(const ConvArgs& a, int tid, int ty0, int tx0, int ylo, int xlo, float* rowT, float* colT) {
+    if (tid >= PH + PW) return;
+    const int Hs = a.H >> 1, Ws = a.W >> 1;
+    const bool isrow = tid < PH;
+    const int pq = isrow ? tid : tid - PH;
+    const int g = (isrow ? ty0 : tx0) + pq - 1;
+    float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g >= 0 && g < (isrow ? a.H : a.W)) {
+        const float sc = (isrow ? a.rh : a.rw) * (float)g;
+        const int i0 = (int)sc;
+        const int i1 = i0 + (i0 < (isrow ? Hs : Ws) - 1 ? 1 : 0);
+        const float l = fminf(fmaxf(sc - (float)i0, 0.f), 1.f);
+        if (isrow) {
+            const int s0 = ylo + (pq >> 1);                // the row's first candidate line
+            const float w0 = 1.f - l, w1 = l;
+            e.x = (i0 == s0 ? w0 : 0.f) + (i1 == s0 ? w1 : 0.f);
+            e.y = (i0 == s0 + 1 ? w0 : 0.f) + (i1 == s0 + 1 ? w1 : 0.f);
+            // (a line outside the two candidates can only carry the weight l = 0 of image row 0, where sc = 0:
+            // upsample_lines_regular(), checked by winograd_plan)
+        } else {
+            e = make_float4(__int_as_float((i0 - xlo) * LP), __int_as_float((i1 - xlo) * LP), 1.f - l, l);
+        }
+    }
+    *reinterpret_cast<float4*>(&(isrow ? rowT : colT)[4 * pq]) = e;
 }
 
 // ---- output transform Y = A^T M A,  A^T = [1 1 1 1 1 0; 0 a -a b -b 0; 0 a^2 a^2 b^2 b^2 0; 0 a^3 -a^3 b^3 -b^3 1],
@@ -535,55 +626,13 @@ __global__ __launch_bounds__(8 * MT * WN, 2) void conv3x3_wino4_kernel(const Con
             }
         }
     };
-    // upsampled chunk: interpolate the patch from the parked low-res region (ATen upsample_bilinear2d, align_corners=True:
-    // src = dst * (in-1)/(out-1), weights (1-l, l), noise.py:39,46): out = wy0 (wx0 p[i0][c0] + wx1 p[i0][c1]) + wy1 (... p[i1] ...).
-    // SEPARABLE (round 4): a lane owns one (patch column, 4-channel piece) and the rows of its row group.  It first forms
-    // t[k] = wx0 p[k][c0] + wx1 p[k][c1] for the low-res lines its rows touch - every read at a compile-time offset from one
-    // address, all in flight together - and then each patch row as a weighted sum of two of them: for an exact x2 upsample the
-    // source lines of output row g >= 1 are floor((g - 1) / 2) and the next (winograd_plan checks that the float product
-    // rh * g ATen evaluates agrees for every row of this image height - it does for every even height up to 1024), so patch row y
-    // of a tile whose first row is even touches lines s, s + 1 with s = ty0 / 2 - 1 + (y >> 1): two compile-time registers; the
-    // per-row table holds their weights, filled from the float formula.  Same products and sums per output value as
-    // interpolating each piece from its four source pixels, ~7 packed vector instructions per output piece instead of 27 and
-    // three LDS round trips per chunk instead of two per piece (the f32 MFMAs share the vector issue port: interpolation was
-    // 0.20-0.25 of these kernels' lifetime, profiles/r03_wino4_stamps.md).  PW x PPP lanes of IWPG waves work per row group, ING
-    // groups split the rows.
-    constexpr int IPAIRS = PW * PPP, IWPG = (IPAIRS + 63) / 64, ING = (NT_ / 64) / IWPG;
-    constexpr int IRG = (((PH + ING - 1) / ING) + 1) & ~1;                // rows per group, even: (y >> 1) splits into group and row part
-    constexpr int IK = IRG / 2 + 1;                                        // low-res lines a row group touches
-    static_assert(!UP2 || (ING >= 1 && (PPP & (PPP - 1)) == 0 && TH % 2 == 0), "row groups of whole waves; even tile origin");
+    // upsampled chunk: the patch is interpolated from the parked low-res region by all the workgroup's waves (wino4_interpolate)
+    typedef Wino4Interp<PH, PW, PPP, NT_ / 64> IG;
+    static_assert(!UP2 || (IG::ING >= 1 && (PPP & (PPP - 1)) == 0 && TH % 2 == 0), "row groups of whole waves; even tile origin");
     static_assert(!UP2 || ((PH - 1) / 2 + 1 < LH), "the parked region holds every candidate line");
     auto interpolate = [&]() {
-        const int ig = wid / IWPG;                         // this wave's row group (wave-uniform)
-        const int it = tid - ig * (IWPG * 64);
-        if (ig >= ING || it >= IPAIRS) return;
-        const int x = it / PPP, part = it % PPP;
-        const int yb = ig * IRG;
-        const float4 ct = *reinterpret_cast<const float4*>(&colT[4 * x]);
-        const float* const l0 = &lowres[__float_as_int(ct.x) + part * 4 + (yb / 2) * (LW * LP)];
-        const float* const l1 = &lowres[__float_as_int(ct.y) + part * 4 + (yb / 2) * (LW * LP)];
-        const v2f wx0 = v2f{ct.z, ct.z}, wx1 = v2f{ct.w, ct.w};
-        v2f tl[IK], th_[IK];
-#pragma unroll
-        for (int k = 0; k < IK; ++k) {                     // wx0 * p[line][c0] + wx1 * p[line][c1], 4 channels
-            if ((yb / 2 + k) < LH) {                       // (wave-uniform; lines past the region belong to rows past the patch)
-                const float4 pa = *reinterpret_cast<const float4*>(l0 + k * (LW * LP)), pb = *reinterpret_cast<const float4*>(l1 + k * (LW * LP));
-                tl[k] = __builtin_elementwise_fma(wx0, v2f{pa.x, pa.y}, wx1 * v2f{pb.x, pb.y});
-                th_[k] = __builtin_elementwise_fma(wx0, v2f{pa.z, pa.w}, wx1 * v2f{pb.z, pb.w});
-            } else { tl[k] = v2f{0.f, 0.f}; th_[k] = v2f{0.f, 0.f}; }
-        }
-        const int pdst = ((yb * PW + x) * CKQ) + part * 4;
-#pragma unroll
-        for (int j = 0; j < IRG; ++j) {
-            if (yb + j < PH) {                             // (wave-uniform)
-                const float4 rw = *reinterpret_cast<const float4*>(&rowT[4 * (yb + j)]);
-                const v2f wa = v2f{rw.x, rw.x}, wb = v2f{rw.y, rw.y};
-                const int k = j >> 1;
-                const v2f olo = __builtin_elementwise_fma(wa, tl[k], wb * tl[k + 1]);
-                const v2f ohi = __builtin_elementwise_fma(wa, th_[k], wb * th_[k + 1]);
-                put_patch(pdst + j * (PW * CKQ), make_float4(olo.x, olo.y, ohi.x, ohi.y));
-            }
-        }
+        wino4_interpolate<PH, PW, PPP, LH, LW, LP, NT_ / 64, PW * CKQ>(lowres, rowT, colT, wid, tid,
+            [](int y, int x, int part) { return ((y * PW + x) * CKQ) + part * 4; }, [&](int off, float4 v) { put_patch(off, v); });
     };
     // ---- FIRST: the denoiser's first layer (sigma-plane cat + conv 2 -> 32 + LeakyReLU, noise.py:157-162,104; conv_first_kernel)
     // evaluated for the patch pixels of chunk c's 8 channels straight into the patch: its 537 MB output is neither written nor
@@ -664,29 +713,7 @@ __global__ __launch_bounds__(8 * MT * WN, 2) void conv3x3_wino4_kernel(const Con
         // (first read behind the loop-top barrier).  Pixels outside the image (the conv's zero padding) get zero weights.
         // Row entry: the weights of the row's two candidate source lines s, s + 1 (see interpolate()); column entry:
         // {offsets of the two source columns in the region, their weights}.
-        if (tid < PH + PW) {
-            const bool isrow = tid < PH;
-            const int pq = isrow ? tid : tid - PH;
-            const int g = (isrow ? ty0 : tx0) + pq - 1;
-            float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (g >= 0 && g < (isrow ? a.H : a.W)) {
-                const float sc = (isrow ? a.rh : a.rw) * (float)g;
-                const int i0 = (int)sc;
-                const int i1 = i0 + (i0 < (isrow ? Hs : Ws) - 1 ? 1 : 0);
-                const float l = fminf(fmaxf(sc - (float)i0, 0.f), 1.f);
-                if (isrow) {
-                    const int s0 = ylo + (pq >> 1);        // the row's first candidate line
-                    const float w0 = 1.f - l, w1 = l;
-                    e.x = (i0 == s0 ? w0 : 0.f) + (i1 == s0 ? w1 : 0.f);
-                    e.y = (i0 == s0 + 1 ? w0 : 0.f) + (i1 == s0 + 1 ? w1 : 0.f);
-                    // (a line outside the two candidates can only carry the weight l = 0 of image row 0, where sc = 0:
-                    // upsample_lines_regular(), checked by winograd_plan)
-                } else {
-                    e = make_float4(__int_as_float((i0 - xlo) * LP), __int_as_float((i1 - xlo) * LP), 1.f - l, l);
-                }
-            }
-            *reinterpret_cast<float4*>(&(isrow ? rowT : colT)[4 * pq]) = e;
-        }
+        wino4_upsample_tables<PH, PW, LP>(a, tid, ty0, tx0, ylo, xlo, rowT, colT);
     }
     if constexpr (FIRST) first_patch(0);
     else {
@@ -1036,6 +1063,293 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino4p_kernel(const ConvArgs a
 #endif
 }
 
+// ---- COUT-SPLIT variant (plain or upsample + concat source, Cout a multiple of 128) ----------------------------------------------------------------
+// Same arithmetic again, the workgroup cut the other way: ONE 16-tile M-block (the MT = 16 geometries: 16 x 16 pixels for TW = 16,
+// 8 x 32 for TW = 32) x 128 output channels.  Wave w owns the 16 tiles x channels [16 w, 16 w + 16) of the block for all 36
+// frequencies - accumulator layout, A fragment read and B ring of the kernels above - so ONE staged patch and ONE input transform of
+// 16 tiles (256 items: half the workgroup) feed eight waves' MFMAs instead of four: a layer with Cout = 128 / 256 / 512 evaluates
+// V = B^T d B 1 / 2 / 4 times per tile instead of 2 / 4 / 8.  V is double-buffered and the transform runs a chunk ahead, its duty
+// alternating between the two halves of the workgroup (waves 0-3 / 4-7 = one wave of every SIMD), one workgroup barrier per chunk:
+//     barrier | half c & 1: T(c+1) -> V[(c+1) & 1], then M(c)    other half: M(c) | barrier | ...
+// so for most of a chunk both waves of a SIMD are in their MFMA phase and fill each other's fragment latencies.  The patch lives
+// twice (chunk c + 2 is parked while chunk c + 1 is being transformed) in conv3x3_wino4p_kernel's channel-granule planes; its loads
+// go out a chunk ahead from all 512 threads, three float4 each.  Summation order per output: chunks ascending, the four MFMAs of a
+// frequency in the order above - bit-identical results.  A 16 x 16 image is one M-block: no slice stacking.
+// SRC_UPCAT (up1.conv-0, up2.conv-0): the skip chunks are staged as above; an upsampled chunk k travels one step longer - its
+// low-res source region (conv3x3_wino4_kernel's, two copies here) is fetched in chunk k - 3, interpolated into the patch in chunk
+// k - 2 by the half that has NO transform duty there (the same separable interpolation, once per 128 output channels), transformed
+// in chunk k - 1 and multiplied in chunk k: in the upsampled part of the K loop every half has one VALU job per chunk.
+template <int TW, int SRC>
+__global__ __launch_bounds__(512, 2) void conv3x3_wino4c_kernel(const ConvArgs a) {
+    constexpr int CK = 16, CKP = 16, PPP = 4, NT_ = 512, S = 4, MT = 16;
+    constexpr bool UP2 = SRC == SRC_UPCAT;
+    static_assert(SRC == SRC_PLAIN || SRC == SRC_UPCAT, "plain or upsample + concat source");
+    constexpr int TC = TW / 4, TR = MT / TC;           // tiles per row / rows of tiles in the 16-tile M-block
+    constexpr int TH = 4 * TR;
+    constexpr int PH = TH + 2, PW = TW + 2;
+    constexpr int NPIX = PH * PW, ITEMS = NPIX * PPP;
+    constexpr int NIT = (ITEMS + NT_ - 1) / NT_;
+    constexpr int PLSZ = ((NPIX * 4 + 15) / 16) * 16 + 4;  // floats per channel-granule plane, = 4 (mod 16) (conv3x3_wino4p_kernel)
+    constexpr int PATCH = 4 * PLSZ;                    // floats per copy of the patch
+    constexpr int PF = 12, KEEP = 3;                   // B fragment ring (conv3x3_wino4p_kernel)
+    constexpr int PLANE = MT * CKP;                    // floats per frequency plane of V
+    constexpr int VSZ = 36 * PLANE;                    // floats per copy of V
+    constexpr unsigned OOB = 0x80000000u;
+    static_assert(NIT == 3 && ITEMS <= NIT * NT_, "three staging items per thread");
+    constexpr int LP = CK;                             // UPCAT: pixel stride of the low-res region (conv3x3_wino4_kernel)
+    constexpr int LH = TH / 2 + 3, LW = TW / 2 + 3;    // its rows [ty0 / 2 - 1, ...) and columns from xlo
+    constexpr int LITEMS = LH * LW * PPP, NITL = (LITEMS + NT_ - 1) / NT_;
+    constexpr int LOWRES = LH * LW * LP;               // floats per copy of the region
+    static_assert((2 * PATCH + 2 * VSZ + (UP2 ? 2 * LOWRES + 4 * (PH + PW) : 0)) * 4 <= 160 * 1024, "everything in one CU's LDS");
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const patch = smem;                             // [2][4 granules][PLSZ]
+    float* const V = smem + 2 * PATCH;                     // [2][36][16 tiles][16], granules swizzled (see swz)
+    float* const lowres = V + 2 * VSZ;                     // UPCAT: [2][LH][LW][LP]
+    float* const rowT = lowres + 2 * LOWRES;               // UPCAT: the interpolation tables of conv3x3_wino4_kernel
+    float* const colT = rowT + 4 * PH;
+#ifdef PNP_STAMPS
+    unsigned long long st_t0 = W4T(), st_setup = 0, st_loop0 = 0, st_commit = 0, st_trans = 0, st_mfma = 0, st_loop1 = 0, st_tmp = 0;
+#endif
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int half = wid >> 2;                             // transforms the chunks c + 1 with (c & 1) == half
+    const int tg = lane >> 4, cl = lane & 15;              // MFMA lane = (k / row group tg, column / row cl)
+
+    const int ny = a.Cout / 128;
+    const int bid = blockIdx.x;
+    const int ntl = a.tilesX * a.tilesY * a.N;
+    int cby, bt;                                           // this workgroup's block of 128 channels, its spatial tile index (XCD-aware
+    wino4_decode(bid, ny, ntl, a.order, cby, bt);          // order, see conv3x3_wino4_kernel)
+    if (bt >= ntl) return;
+    const int tx0 = (bt % a.tilesX) * TW;
+    bt /= a.tilesX;
+    const int ty0 = (bt % a.tilesY) * TH;
+    const int n = bt / a.tilesY;
+    if (a.tact != nullptr && a.tact[n] > 0.5f) return;
+    const int cb = cby * 8 + wid;                          // this wave's 16-channel block
+    const int nchunks = a.Cin / CK;
+    const int cs = UP2 ? a.Cskip : a.Cin;                  // channels of src0
+    const int nskip = UP2 ? a.Cskip / CK : nchunks;        // leading chunks that come straight from src0 (>= 3: the launcher checks)
+    const int Hs = a.H >> 1, Ws = a.W >> 1;
+    const int ylo = UP2 ? ty0 / 2 - 1 : 0;                 // first low-res row of the parked region (-1 at the top of the image: a zero row)
+    const int xlo = UP2 ? (int)(a.rw * (float)(tx0 > 0 ? tx0 - 1 : 0)) : 0;
+
+    // staging addresses, once (see conv3x3_wino4_kernel): item idx = (pixel, channel granule), granule fastest
+    const __amdgpu_buffer_rsrc_t rsrc0 = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(a.src0 + (size_t)n * a.H * a.W * cs), 0, a.H * a.W * cs * 4, 0x00020000);
+    unsigned voff[NIT];
+#pragma unroll
+    for (int k = 0; k < NIT; ++k) {
+        const int idx = tid + k * NT_;
+        const int part = idx % PPP, pp = idx / PPP;
+        const int gy = ty0 + pp / PW - 1, gx = tx0 + pp % PW - 1;
+        voff[k] = (idx < ITEMS && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? (unsigned)(((gy * a.W + gx) * cs + part * 4) * 4) : OOB;
+    }
+    const int ldst = (tid & 3) * PLSZ + (tid >> 2) * 4;    // LDS slot of item 0; item k is 128 pixels (512 floats) further
+    float4 raw[NIT];
+    // UPCAT: the low-res region of an upsampled chunk, its own registers (at the seam the last skip chunk and the first region fly together)
+    const int Cup = a.Cin - a.Cskip;
+    const __amdgpu_buffer_rsrc_t rsrc1 = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(UP2 ? a.src1 + (size_t)n * Hs * Ws * Cup : a.src0), 0, UP2 ? Hs * Ws * Cup * 4 : 0, 0x00020000);
+    unsigned voffL[UP2 ? NITL : 1];
+    float4 rawL[UP2 ? NITL : 1];
+    if constexpr (UP2) {
+#pragma unroll
+        for (int k = 0; k < NITL; ++k) {
+            const int idx = tid + k * NT_;
+            const int part = idx % PPP, pp = idx / PPP;
+            const int sy = ylo + pp / LW, sx = xlo + pp % LW;
+            voffL[k] = (idx < LITEMS && sy >= 0 && sy < Hs && sx < Ws) ? (unsigned)(((sy * Ws + sx) * Cup + part * 4) * 4) : OOB;
+        }
+    }
+    const int ldstL = (tid >> 2) * LP + (tid & 3) * 4;     // slot of item 0 in the region; item k is 128 pixels further
+    auto issueL = [&](int c) {
+        if constexpr (UP2) {
+            const int soff = (c * CK - a.Cskip) * 4;
+#pragma unroll
+            for (int k = 0; k < NITL; ++k)
+                rawL[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc1, voffL[k], soff, 0));
+        }
+    };
+    auto parkL = [&](int c) {                              // registers -> copy (c & 1) of the region
+        if constexpr (UP2) {
+            float* const dst = lowres + (c & 1) * LOWRES + ldstL;
+#pragma unroll
+            for (int k = 0; k < NITL; ++k)
+                if (tid + k * NT_ < LITEMS) *reinterpret_cast<float4*>(&dst[k * (NT_ / PPP) * LP]) = rawL[k];
+        }
+    };
+    // upsampled chunk c: region copy c & 1 -> patch copy c & 1, by the four waves of one half: conv3x3_wino4_kernel's separable
+    // interpolate() (see there: a lane owns one (patch column, 4-channel piece) and the rows of its row group; the same products
+    // and sums per output value), writing the patch's channel-granule planes
+    static_assert(Wino4Interp<PH, PW, PPP, 4>::ING >= 1 && TH % 2 == 0 && (PH - 1) / 2 + 1 < LH, "row groups of whole waves; even tile origin; every candidate line parked");
+    auto interpolate = [&](int c) {
+        if constexpr (UP2) {
+            float* const pdst = patch + (c & 1) * PATCH;
+            wino4_interpolate<PH, PW, PPP, LH, LW, LP, 4, PW * 4>(lowres + (c & 1) * LOWRES, rowT, colT, wid & 3, tid & 255,
+                [](int y, int x, int part) { return part * PLSZ + (y * PW + x) * 4; }, [&](int off, float4 v) { *reinterpret_cast<float4*>(&pdst[off]) = v; });
+        }
+    };
+    if constexpr (UP2) {
+        // the interpolation's tables, built once (conv3x3_wino4_kernel: row entry = the weights of the row's two candidate source
+        // lines, column entry = {offsets of the two source columns in the region, their weights}); first read barriers later
+        wino4_upsample_tables<PH, PW, LP>(a, tid, ty0, tx0, ylo, xlo, rowT, colT);
+    }
+    auto issue = [&](int c) {
+        const int soff = c * CK * 4;
+#pragma unroll
+        for (int k = 0; k < NIT; ++k)
+            raw[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc0, voff[k], soff, 0));
+    };
+    auto park = [&](int c) {                               // registers -> copy (c & 1) of the patch
+        float* const dst = patch + (c & 1) * PATCH + ldst;
+#pragma unroll
+        for (int k = 0; k < NIT; ++k)
+            if (tid + k * NT_ < ITEMS) *reinterpret_cast<float4*>(&dst[k * (NT_ / PPP) * 4]) = raw[k];
+    };
+
+    // this thread's transform item when its half has the duty: tile t16, channels [2*hc, 2*hc+2), frequency column group tj
+    // (waves 0-1 of the half: columns 0..2, waves 2-3: columns 3..5; all six rows)
+    auto swz = [](int t16, int g) { return g ^ ((4 - (t16 >> 2)) & 3); };
+    const int tgi = tid & 255;
+    const int hc = tgi & 7, t16 = (tgi >> 3) & 15;
+    const int tj = (wid >> 1) & 1;
+    const int win = (hc >> 1) * PLSZ + (4 * (t16 / TC) * PW + 4 * (t16 % TC)) * 4 + 2 * (hc & 1);   // top-left of the 6x6 window, copy 0
+    const int vout = t16 * CKP + 4 * swz(t16, hc >> 1) + 2 * (hc & 1);         // this item's slot in every frequency plane, copy 0
+    auto transform = [&](int c) {                          // patch copy c & 1 -> V copy c & 1
+        const float* const w = patch + (c & 1) * PATCH + win;
+        float* const v = V + (c & 1) * VSZ + vout;
+        if (tj == 0) wino4_input_transform<0, PW, 4, PLANE>(w, v);
+        else wino4_input_transform<1, PW, 4, PLANE>(w, v);
+    };
+
+    f32x4 acc[36];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const size_t stream = (size_t)nchunks * 36 * 64 + kW4Tail / S;                // fragments per 16-channel block's stream
+    // B fragments: global loads (plain) or buffer loads with a scalar fragment offset (upsample + concat), as conv3x3_wino4_kernel
+    const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(reinterpret_cast<const float4*>(a.wpack) + (size_t)cb * stream), 0, (int)(stream * sizeof(float4)), 0x00020000);
+    const int boff = lane * (int)sizeof(float4);
+    const float4* const bptr = reinterpret_cast<const float4*>(a.wpack) + (size_t)cb * stream + lane;
+    auto bfrag = [&](const float4* bp, int f0, int i) -> float4 {
+        if constexpr (!UP2) return bp[i * 64];
+        else return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rB, boff, (f0 + i) * (64 * 16), 0));
+    };
+    float4 bq[PF];
+#pragma unroll
+    for (int p = 0; p < KEEP; ++p) bq[p] = bfrag(bptr, 0, p);
+    const int aoff = cl * CKP + 4 * swz(cl, tg);                                  // this lane's fragment of V[0], copy 0
+
+    // prologue: chunk 0 parked and transformed (by the half that has no duty in chunk 0), chunk 1 parked (both skip chunks)
+    issue(0);
+    park(0);
+    if (nchunks > 1) issue(1);
+    __syncthreads();
+    if (half == 1) transform(0);
+    if (nchunks > 1) park(1);
+#ifdef PNP_STAMPS
+    st_setup = W4T();
+    st_loop0 = st_setup;
+#endif
+    for (int c = 0; c < nchunks; ++c) {
+#ifdef PNP_STAMPS
+        st_tmp = W4T();
+#endif
+        __syncthreads();                                   // V[c & 1] is written, chunk c + 1 is parked; everybody's MFMAs of chunk c - 1 are done
+#ifdef PNP_STAMPS
+        { const unsigned long long t = W4T(); st_commit += t - st_tmp; st_tmp = t; }
+#endif
+        // ---- the duty half transforms chunk c + 1 (its partner waves on the SIMDs are in their MFMA phase: the few VALU
+        // instructions of the transform go first); V copy (c + 1) & 1 was last read by the MFMAs of chunk c - 1
+        if (half == (c & 1)) {
+            if (c + 1 < nchunks) {
+                __builtin_amdgcn_s_setprio(3);
+                transform(c + 1);
+                __builtin_amdgcn_s_setprio(0);
+            }
+        } else if (UP2 && c + 2 >= nskip && c + 2 < nchunks) {     // the other half: upsampled chunk c + 2 into the patch copy chunk c held
+            __builtin_amdgcn_s_setprio(3);
+            interpolate(c + 2);
+            __builtin_amdgcn_s_setprio(0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const float4* bp = bptr + (size_t)c * 36 * 64;
+        const int bf0 = c * 36;
+#pragma unroll
+        for (int p = KEEP; p < PF; ++p) bq[p] = bfrag(bp, bf0, p);
+        // skip / plain chunk c + 2 flies under this chunk's MFMAs and is parked behind them, in the copy chunk c held (last read by
+        // the transform of chunk c, one barrier back; first read by the transform of chunk c + 2, behind the next barrier); the
+        // region of upsampled chunk c + 3 likewise, in the copy chunk c + 1's held (last read by its interpolation, one barrier back)
+        if (c + 2 < nskip) issue(c + 2);
+        if (UP2 && c + 3 >= nskip && c + 3 < nchunks) issueL(c + 3);
+#ifdef PNP_STAMPS
+        { const unsigned long long t = W4T(); st_trans += t - st_tmp; st_tmp = t; }
+#endif
+
+        // ---- 36 GEMMs per wave: A from V (LDS), B from the packed U stream (L2), 4 MFMAs per frequency -----------------------
+        const float* const Vc = V + (c & 1) * VSZ + aoff;
+        float4 ar[3];
+        ar[0] = *reinterpret_cast<const float4*>(&Vc[0]);
+        ar[1] = *reinterpret_cast<const float4*>(&Vc[PLANE]);
+#pragma unroll
+        for (int xi = 0; xi < 36; ++xi) {
+            if (xi + 2 < 36) ar[(xi + 2) % 3] = *reinterpret_cast<const float4*>(&Vc[(xi + 2) * PLANE]);
+            __builtin_amdgcn_sched_barrier(0);
+            const float4 a0 = ar[xi % 3], b0 = bq[xi % PF];
+            acc[xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b0.x, acc[xi], 0, 0, 0);
+            acc[xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b0.y, acc[xi], 0, 0, 0);
+            acc[xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b0.z, acc[xi], 0, 0, 0);
+            acc[xi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b0.w, acc[xi], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (xi + PF < 36 + KEEP) bq[xi % PF] = bfrag(bp, bf0, xi + PF);
+        }
+#ifdef PNP_STAMPS
+        { const unsigned long long t = W4T(); st_mfma += t - st_tmp; }
+#endif
+        if (c + 2 < nskip) park(c + 2);
+        if (UP2 && c + 3 >= nskip && c + 3 < nchunks) parkL(c + 3);
+    }
+#ifdef PNP_STAMPS
+    st_loop1 = W4T();
+    st_tmp = st_loop1;
+#endif
+
+    // ---- output transform, lane-local (as conv3x3_wino4_kernel, MT = 16: one 16-tile part) ------------------------------------
+    wino4_epilogue<TW, false, 16>(a, acc, n, 0, tg, cl, cb, tx0, ty0, true);
+#ifdef PNP_STAMPS
+    {
+        const int w = (int)blockIdx.x - (int)(gridDim.x / 2);
+        if (tid == 0 && w >= 0 && w < W4_WGS && a.stamp_slot < W4_SLOTS) {
+            unsigned long long* o = g_w4_stamps + ((size_t)a.stamp_slot * W4_WGS + w) * W4_N;
+            const unsigned long long te = W4T();
+            o[0] = 1; o[1] = st_setup - st_t0; o[2] = st_commit; o[3] = st_trans; o[4] = st_mfma; o[5] = st_loop1 - st_loop0;
+            o[6] = te - st_tmp; o[7] = 0; o[8] = te - st_loop1; o[9] = te - st_t0; o[10] = (unsigned long long)nchunks;
+        }
+    }
+#endif
+}
+
+template <int TW, int SRC>
+static hipError_t launch_wino4c_inst(const ConvArgs& a, const WinoPlan& p, hipStream_t s) {
+    constexpr int TC = TW / 4, TR = 16 / TC, TH = 4 * TR;
+    constexpr int NPIX = (TH + 2) * (TW + 2);
+    constexpr int PLSZ = ((NPIX * 4 + 15) / 16) * 16 + 4;
+    constexpr size_t lowres_f = SRC == SRC_UPCAT ? (size_t)2 * (TH / 2 + 3) * (TW / 2 + 3) * 16 + 4 * (TH + 2 + TW + 2) : 0;   // two regions + tables
+    constexpr size_t lds = ((size_t)2 * 4 * PLSZ + (size_t)2 * 36 * 16 * 16 + lowres_f) * sizeof(float);
+    if (p.th != TH || p.tw != TW) return hipErrorInvalidValue;
+    if (SRC == SRC_UPCAT && a.Cskip < 3 * 16) return hipErrorInvalidValue;      // (the prologue stages skip chunks only)
+    auto kern = conv3x3_wino4c_kernel<TW, SRC>;
+    static DeviceOnce cap;
+    if (hipError_t e = raise_lds_cap((const void*)kern, (int)lds, cap); e != hipSuccess) return e;
+    const int ntiles = p.tiles_x * p.tiles_y * a.N, ny = a.Cout / 128;
+    dim3 grid((unsigned)(((ntiles + 7) / 8) * 8 * ny));
+    hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, a);
+    return hipGetLastError();
+}
+
 template <int TW, bool STK>
 static hipError_t launch_wino4p_inst(const ConvArgs& a, const WinoPlan& p, hipStream_t s) {
     constexpr int TC = TW / 4, TR = 32 / TC, TH = 4 * TR;
@@ -1091,6 +1405,14 @@ hipError_t launch_conv3x3_winograd4(const ConvArgs& a0, const WinoPlan& p, int s
         return hipErrorInvalidValue;
     }
     if (p.ck != 16) return hipErrorInvalidValue;
+    if (p.cs) {                                            // one 16-tile M-block x 128 channels (conv3x3_wino4c_kernel)
+        if (p.bn != 128 || p.mt != 16 || p.stack) return hipErrorInvalidValue;
+        if (p.tw == 32 && src_mode == SRC_PLAIN) return launch_wino4c_inst<32, SRC_PLAIN>(a, p, s);
+        if (p.tw == 32 && src_mode == SRC_UPCAT) return launch_wino4c_inst<32, SRC_UPCAT>(a, p, s);
+        if (p.tw == 16 && src_mode == SRC_PLAIN) return launch_wino4c_inst<16, SRC_PLAIN>(a, p, s);
+        if (p.tw == 16 && src_mode == SRC_UPCAT) return launch_wino4c_inst<16, SRC_UPCAT>(a, p, s);
+        return hipErrorInvalidValue;
+    }
     if (p.mt == 16) {                                      // 16-tile M-blocks: two independent 4-wave workgroups per CU
         if (p.stack) return hipErrorInvalidValue;
         if (p.tw == 32 && src_mode == SRC_PLAIN) return launch_wino4_inst<32, SRC_PLAIN, false, 2, 16>(a, p, s);

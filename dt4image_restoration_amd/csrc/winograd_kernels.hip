@@ -70,7 +70,11 @@ void pack_winograd_weights(const float* oihw, int cin, int cout, int ck, float* 
 // Eligibility + tile plan.  The transforms and the 16-accumulator epilogue are per-item overhead that long K amortises
 // best (1.65x over the direct kernel at Cin >= 128), but even the K = 288 layers gain ~9 %; small problems (too few
 // workgroups) stay on the direct kernel with split-K.
-WinoPlan winograd_plan(int N, int H, int W, int Cin, int Cout, int src_mode, const Tuning& t) {
+WinoPlan winograd_plan(int N, int H, int W, int Cin, int Cout, int src_mode, const Tuning& t, int Cskip) {
+    // default cout-split rule: from one workgroup per CU on.  Measured against the parent build, two interleaved passes, ms per launch at 256 x 256:
+    // 1024 / 512 workgroups (64 slices) -8 %; 512 (up2.conv-0, 32 slices) 0.302 -> 0.284 (-6 %); 256 (up1.conv-0, 32 slices) 0.298 -> 0.291
+    // (-2.5 / -2.5 %); 256 (up2.conv-0, 16 slices) 0.155 -> 0.150 (-3.6 / -3.7 %).  Fewer workgroups than CUs: not measured, not taken.
+    constexpr long kCsMinBlocks = 256;
     WinoPlan p{};
     p.use = false;
     p.algo = 1;
@@ -107,6 +111,31 @@ WinoPlan winograd_plan(int N, int H, int W, int Cin, int Cout, int src_mode, con
                 f.stack = 0;
             }
             f.phased = (f.mt == 32 && f.bn == 64 && src_mode == SRC_PLAIN && !t.no_f4_phased) ? 1 : 0;
+            // cout-split (one 16-tile M-block x 128 channels per workgroup: one patch and one input transform per 128 output channels
+            // instead of per 64).  PNP_WINO_F4_CS=2 takes every layer the schedule can run; the default rule holds the layer shapes
+            // whose per-layer A/B showed a gain in both passes (profiles/wino4_coutsplit.md) and applies only where the switches of
+            // the other schedules are at their defaults, so those keep their meaning.
+            // An upsample + concat layer needs whole skip chunks and at least three of them (the kernel's prologue stages skip chunks only).
+            const bool cs_can = f.bn == 64 && Cout % 128 == 0 && (src_mode == SRC_PLAIN || (Cskip % 16 == 0 && Cskip >= 48));
+            // Its workgroups are half as many and must pass the workgroup-count gate themselves; where they do not, the plan built
+            // above stands (a layer never leaves F(4x4) because of this schedule).
+            const int cs_th = f.tw == 32 ? 8 : 16;
+            const long cs_blocks = (long)f.tiles_x * ((H + cs_th - 1) / cs_th) * N * (Cout / 128);
+            // Measured (64 slices of 256 x 256, two interleaved passes against the parent build, ms per launch): up1.conv-0 0.588 -> 0.542
+            // (-7.6 / -8.1 %), up2.conv-0 0.597 -> 0.548 (-8.2 / -8.3 %): the interpolation runs once per 128 channels and on the half
+            // that has no transform in that chunk.  The plain layers are SLOWER than on the phased kernel (+1.2...2.1 % at 128 channels,
+            // +2.8...3.9 % at 256, +5 % on down2.conv-0) - its transforms already ran under the partner half's MFMAs, and here every
+            // chunk's barrier waits for the duty half's transform + MFMAs - and the 16 x 16 level is equal within its noise (-0.1...1.2 %).
+            const bool cs_rule = src_mode == SRC_UPCAT && cs_blocks >= kCsMinBlocks;
+            if (cs_can && cs_blocks >= t.wino_min_blocks && (t.f4_cs == 2 || (t.f4_cs == 1 && t.f4_mt16 == 0 && !t.no_f4_phased && cs_rule))) {
+                f.cs = 1;
+                f.bn = 128;
+                f.mt = 16;
+                f.th = cs_th;
+                f.tiles_y = (H + f.th - 1) / f.th;
+                f.stack = 0;
+                f.phased = 0;
+            }
             const long blocks = (long)f.tiles_x * f.tiles_y * (f.stack ? (N + 1) / 2 : N) * (Cout / f.bn);
             f.use = blocks >= t.wino_min_blocks;
             if (f.use) return f;

@@ -510,6 +510,13 @@ class PnPEngine:
         _lib.check(self.lib.pnp_conv_algorithms(self._h, out), "pnp_conv_algorithms")
         return list(out)
 
+    def conv_schedules(self):
+        """Per conv layer, the schedule of the F(4x4) arithmetic it runs: 0 not on F(4x4), 1 all waves in step, 2 the tile halves half
+        a chunk apart, 3 16-tile M-blocks in independent workgroups, 4 cout-split (16 tiles x 128 channels per workgroup)."""
+        out = (C.c_int32 * _lib.N_LAYERS)()
+        _lib.check(self.lib.pnp_conv_schedules(self._h, out), "pnp_conv_schedules")
+        return list(out)
+
     def bf16_weight_terms(self) -> int:
         """bf16 terms per conv weight: 0 on an f32 handle, 2 in bf16 mode (hi + lo), 1 with PNP_BF16_W1 (ablation)."""
         return int(self.lib.pnp_bf16_weight_terms(self._h))

@@ -537,6 +537,11 @@ int pnp_profile_layers(pnp_handle h, double* layer_ms, int64_t* layer_launches);
  * MFMA conv in producer / consumer form (PNP_FLAG_BF16_CONVS handles on chip-filling problems). */
 int pnp_conv_algorithms(pnp_handle h, int32_t* algo28);
 
+/* Which schedule of the F(4x4,3x3) arithmetic each of the 28 conv layers runs (fixed at pnp_create; dt4image_restoration_amd/csrc/
+ * winograd4_kernels.hip): 0 the layer is not on F(4x4), 1 all waves in step (32 tiles; the 32-channel variant too), 2 the two tile
+ * halves half a chunk apart, 3 16-tile M-blocks in two independent workgroups per CU, 4 cout-split (16 tiles x 128 channels). */
+int pnp_conv_schedules(pnp_handle h, int32_t* sched28);
+
 /* bf16 terms per conv weight on this handle: 0 (f32 handle), 2 (PNP_FLAG_BF16_CONVS), 1 (... with PNP_BF16_W1). */
 int pnp_bf16_weight_terms(pnp_handle h);
 
