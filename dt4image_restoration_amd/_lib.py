@@ -25,6 +25,9 @@ PNP_PW_MAX_COILS = 64
 PNP_ESPIRIT_MAX_COILS = 16
 PNP_ESPIRIT_MAX_KSIZE = 8
 PNP_ESPIRIT_MAX_N = 512
+PNP_GRAPPA_MAX_COILS = 32
+PNP_GRAPPA_MAX_ACCEL = 8
+PNP_GRAPPA_MAX_SRC = 512
 PNP_TV_MAX_ITERS = 64
 PNP_PRIOR_UNET = 0
 PNP_PRIOR_TV = 1
@@ -77,6 +80,9 @@ SIGNATURES = {
     "pnp_whiten_apply": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, C.c_int, _fp, _vp]),
     "pnp_espirit_sens": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double,
                                   C.c_int, _fp, _fp, _fp, _vp, _vp]),
+    "pnp_grappa_weights": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp, _vp, _fp,
+                                    _vp]),
+    "pnp_grappa_apply": (C.c_int, [C.c_void_p, _fp, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _vp]),
     "pnp_snapshot_bytes": (C.c_size_t, [C.c_void_p]),
     "pnp_snapshot": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _vp, _vp]),
     "pnp_restore": (C.c_int, [C.c_void_p, _vp, _fp, _fp, _fp, _fp, _vp]),

@@ -21,7 +21,7 @@ import torch
 from . import _lib, synthetic
 from .weights import hash_uniform
 
-MASK_KINDS = ("radial", "cartesian")
+MASK_KINDS = ("radial", "cartesian", "uniform")
 
 
 def _engine(engine_or_env, n: int, h: int, w: int, device: torch.device):
@@ -368,6 +368,129 @@ def cartesian_mask(h: int, w: int, accel: float, center_fraction: float = 0.08, 
     return np.broadcast_to(cols[None, :], (h, w)).copy()
 
 
+def uniform_mask(h: int, w: int, accel: int, offset: int = None, center_fraction: float = 0.08) -> np.ndarray:
+    """Bool [h,w] of whole columns, centred layout: the integer comb offset + k accel (offset: accel // 2 by default) laid under the
+    centred block of round(w * center_fraction) columns of `cartesian_mask` (at least the two centre columns, so that there always is a
+    calibration block) - the sampling GRAPPA works on (`grappa_geometry` reads it back).  ValueError unless accel is a whole number that
+    divides w."""
+    if accel != int(accel) or int(accel) < 1 or w % int(accel):
+        raise ValueError(f"uniform_mask: accel must be a whole number that divides w={w}, got {accel}")
+    accel = int(accel)
+    offset = accel // 2 if offset is None else int(offset)
+    if not 0 <= offset < accel:
+        raise ValueError(f"uniform_mask: offset must be 0..{accel - 1}, got {offset}")
+    cols = _centre_block(w, max(center_fraction, 2.0 / w))
+    cols[offset::accel] = True
+    return np.broadcast_to(cols[None, :], (h, w)).copy()
+
+
+def _comb_of(cols: np.ndarray) -> Tuple[int, int, int]:
+    """(accel, offset, acs_w) of one row of a whole-column mask (bool [W], W even), or ValueError"""
+    w = len(cols)
+    acs_w = _centred_run(cols)
+    if acs_w < 2:
+        raise ValueError("the mask does not sample the centre columns of k-space: no calibration block")
+    lo, hi = w // 2, w // 2                                  # the whole run of sampled columns around the centre
+    while lo > 0 and cols[lo - 1]:
+        lo -= 1
+    while hi < w and cols[hi]:
+        hi += 1
+    outer = cols.copy()
+    outer[lo:hi] = False
+    teeth = np.flatnonzero(outer)
+    if len(teeth) == 0:
+        raise ValueError("the mask has no comb of columns outside its centre block")
+    for accel in range(2, w // 2 + 1):
+        if w % accel:
+            continue
+        comb = np.zeros(w, dtype=bool)
+        comb[int(teeth[0]) % accel::accel] = True
+        comb[lo:hi] = False
+        if np.array_equal(comb, outer):
+            return accel, int(teeth[0]) % accel, acs_w
+    raise ValueError("the columns outside the centre block are not one integer comb x = offset (mod accel) with accel dividing the width")
+
+
+def grappa_geometry(mask) -> Tuple[int, int, int, int]:
+    """(accel, offset, acs_h, acs_w) of a mask GRAPPA can work on: whole columns (bool [H,W]; or [N,H,W], every slice on the same comb -
+    acs_w is then the narrowest centre), the integer comb x = offset (mod accel) with accel dividing W, plus a fully sampled centre
+    (acs_h = H, acs_w = its largest centred even run, as `acs_block`).  ValueError for every other mask: radial, random columns, an
+    `equispaced` comb whose spacing is not a whole number, a comb without a centre."""
+    m = np.asarray(torch.as_tensor(mask).cpu()) != 0
+    if m.ndim == 2:
+        m = m[None]
+    if m.ndim != 3 or m.shape[1] % 2 or m.shape[2] % 2:
+        raise ValueError(f"grappa_geometry: expected a mask [H,W] or [N,H,W] with even H, W, got {tuple(np.asarray(mask).shape)}")
+    if not (m == m[:, :1, :]).all():
+        raise ValueError("grappa_geometry: the mask is not made of whole columns")
+    found = []
+    for cols in m[:, 0, :]:
+        try:
+            found.append(_comb_of(cols))
+        except ValueError as e:
+            raise ValueError(f"grappa_geometry: {e}") from None
+    if any(f[:2] != found[0][:2] for f in found):
+        raise ValueError("grappa_geometry: the slices' masks are not on one comb")
+    return found[0][0], found[0][1], int(m.shape[1]), min(f[2] for f in found)
+
+
+def coil_images(eng, kspace: torch.Tensor) -> torch.Tensor:
+    """ifft_c of every coil of kspace complex64 [N,C,H,W] with the engine's transform, coil by coil (the engine transforms N planes per
+    call): setup-time plumbing."""
+    return torch.stack([eng.fft2c(kspace[:, c].contiguous(), inverse=True) for c in range(kspace.shape[1])], dim=1)
+
+
+def grappa(engine_or_env, y0, mask, kernel: Tuple[int, int] = (5, 4), lam: float = 1e-2, sens=None) -> Dict[str, torch.Tensor]:
+    """GRAPPA on the device (pnp_grappa_weights, pnp_grappa_apply): the missing columns of multi-coil k-space synthesised from their
+    acquired neighbours with weights calibrated, per slice, on the fully sampled centre of its own y0.  y0: [N,C,H,W] complex, or
+    [N,C,H,W,2] real (array or tensor), centred layout, C <= 32; mask: what `grappa_geometry` accepts (`uniform_mask`); kernel = (by, bx)
+    rows by acquired columns; lam: the Tikhonov weight relative to the mean diagonal of the normal matrix (1e-2: a default from a scan on
+    the analytic coils, not a tuned value).  Returns a dict, every tensor on the GPU: y0 complex64 [N,C,H,W] filled k-space (measured bins
+    are copies), wts complex64 [N,nt,ns], info int32 [N] (non-zero: that slice's calibration failed and its missing bins stay zero; it is
+    not read here), rss float32 [N,H,W] the root-sum-of-squares image of the filled k-space, and with sens (complex [C,H,W] or
+    [N,C,H,W]) also x0 float32 [N,1,H,W] = max(Re sum_c conj(S_c) ifft_c(filled_c), 0), the map-combined image - an initial iterate.  The
+    two images are setup-time torch arithmetic over the engine's inverse transform."""
+    y = torch.as_tensor(y0)
+    if not y.is_complex():
+        if y.dim() != 5 or y.shape[-1] != 2:
+            raise ValueError(f"y0: expected complex [N,C,H,W] or real [N,C,H,W,2], got {tuple(y.shape)}")
+        y = torch.view_as_complex(y.float().contiguous())
+    if y.dim() != 4:
+        raise ValueError(f"y0: expected [N,C,H,W], got {tuple(y.shape)}")
+    n, c, h, w = (int(v) for v in y.shape)
+    m = torch.as_tensor(mask)
+    if m.numel() not in (h * w, n * h * w):
+        raise ValueError(f"mask: expected [{h},{w}] or [{n},{h},{w}], got {tuple(m.shape)}")
+    m = m.reshape((h, w) if m.numel() == h * w else (n, h, w))
+    accel, offset, acs_h, acs_w = grappa_geometry(m)
+    by, bx = (int(v) for v in kernel)
+    if acs_h < by or acs_w < (bx - 1) * accel + 1:
+        raise ValueError(f"grappa: the {acs_h} x {acs_w} calibration block holds no {by} x {bx} kernel at acceleration {accel} "
+                         f"(it spans {(bx - 1) * accel + 1} columns)")
+    s = None
+    if sens is not None:
+        s = torch.as_tensor(sens)
+        if not s.is_complex() or s.dim() not in (3, 4) or tuple(s.shape[-3:]) != (c, h, w) or (s.dim() == 4 and s.shape[0] != n):
+            raise ValueError(f"sens: expected complex [{c},{h},{w}] or [{n},{c},{h},{w}], got {tuple(s.shape)}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("grappa needs a ROCm GPU")
+    eng = engine_or_env if hasattr(engine_or_env, "grappa_apply") else None
+    if eng is None:
+        eng = _engine(engine_or_env, n, h, w, torch.device("cuda", torch.cuda.current_device()))
+    if (eng.n, eng.h, eng.w) != (n, h, w):
+        raise ValueError(f"y0 {tuple(y.shape)} does not fit the engine [{eng.n},{eng.h},{eng.w}]")
+    y = y.to(eng.device, torch.complex64).contiguous()
+    m = (m != 0).to(eng.device).contiguous()
+    wts, info = eng.grappa_weights(y, (acs_h, acs_w), accel, kernel=(by, bx), lam=lam)
+    filled = eng.grappa_apply(y, wts, m, accel, offset, kernel=(by, bx))
+    img = coil_images(eng, filled)
+    out = {"y0": filled, "wts": wts, "info": info, "rss": (img.real ** 2 + img.imag ** 2).sum(dim=1).sqrt()}
+    if s is not None:
+        s = s.to(eng.device, torch.complex64)
+        out["x0"] = (s.conj() * img).sum(dim=1, keepdim=True).real.clamp_min(0.0).contiguous()
+    return out
+
+
 def parse_task(task: str) -> Tuple[int, float]:
     """'4x_10' -> (4, 10 / 255): the task names `data.task_from_filename` produces."""
     m = re.fullmatch(r"(\d+)x_(\d+)", task)
@@ -381,6 +504,8 @@ def make_mask(h: int, w: int, accel: float, kind: str = "radial", seed: int = 0)
         return synthetic.radial_mask(h, w, accel)
     if kind == "cartesian":
         return cartesian_mask(h, w, accel, seed=seed)
+    if kind == "uniform":                                    # a centre of 3 accel + 4 columns: room for four window columns of a 4-column GRAPPA kernel
+        return uniform_mask(h, w, accel, center_fraction=max(0.08, (3 * int(accel) + 4) / w))
     raise ValueError(f"mask kind must be one of {MASK_KINDS}, got {kind!r}")
 
 

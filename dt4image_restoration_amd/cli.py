@@ -29,6 +29,13 @@ layout has none):
     ... --coils 8 --sens espirit [--espirit-kernel 6] [--espirit-sv 0.02] [--espirit-crop 0.9] [--espirit-iters 16] --mask cartesian fixed ...
 
     ... --coils 16 --compress 8 [--sens true|estimate|espirit] [--acs H W] eval|flex|mcts|fixed ...
+    ... --coils 8 --mask uniform --grappa [--grappa-kernel 5 4] [--grappa-lambda 0.01] eval|flex|mcts|fixed ...
+
+`--mask uniform` samples an integer comb of columns (every accel-th, under the centre block) instead of `cartesian`'s random ones.
+`--grappa` starts every set from the map-combined image of its GRAPPA-filled k-space (pnp_grappa_weights / pnp_grappa_apply: the missing
+columns synthesised from their acquired neighbours with weights calibrated on the set's own centre) instead of the zero-filled ATy0;
+the data fidelity keeps the measured y0 and the mask.  It runs after --prewhiten and --compress, before the maps are estimated, and
+takes a comb (--mask uniform).
 
 `--compress V` mixes each set's C coils down to V virtual coils before the solver sees them (coil compression: the leading eigenvectors
 of the channel covariance of the calibration block, per slice, pnp_coil_compress_matrix / pnp_coil_compress_apply); every cost of the
@@ -155,8 +162,15 @@ def _with_sens(args, env, batch):
     """--prewhiten, then --compress, then --sens estimate / espirit: the batch with its coil maps replaced by the estimate from its own y0 and mask (on the
     device)."""
     batch = _compressed(args, env, _prewhitened(args, env, batch))
+    filled = None
+    if args.grappa:
+        from . import acquisition
+        try:
+            filled = acquisition.grappa(env, batch["y0"], batch["mask"], kernel=tuple(args.grappa_kernel), lam=args.grappa_lambda)["y0"]
+        except ValueError as e:                                # a mask that is no comb, a block that holds no kernel
+            raise SystemExit(f"--grappa: {e}")
     if args.sens == "true":
-        return batch
+        return _grappa_start(env, batch, filled)
     from . import acquisition
     batch = dict(batch)
     try:
@@ -166,6 +180,21 @@ def _with_sens(args, env, batch):
                                                   iters=args.espirit_iters)
     except ValueError as e:                                    # a mask without a sampled centre, a block that does not fit
         raise SystemExit(f"--sens {args.sens}: {e}")
+    return _grappa_start(env, batch, filled)
+
+
+def _grappa_start(env, batch, filled):
+    """--grappa: the batch with x0 replaced by max(Re sum_c conj(S_c) ifft_c(filled_c), 0), the map-combined image of its GRAPPA-filled
+    k-space `filled`, with the maps the run uses; y0, ATy0 and the mask stay what was measured."""
+    if filled is None:
+        return batch
+    batch = dict(batch)
+    n, c, h, w = (int(v) for v in filled.shape)
+    eng = env._engine_for(n, h, w, filled.device)
+    sens = torch.as_tensor(batch["sens"]).to(filled.device, torch.complex64)
+    from . import acquisition
+    x = (sens.conj() * acquisition.coil_images(eng, filled)).sum(dim=1, keepdim=True).real.clamp_min(0.0)
+    batch["x0"] = torch.stack([x, torch.zeros_like(x)], dim=-1)
     return batch
 
 
@@ -177,8 +206,14 @@ def _sets(args, flex_target=None, env=None):
             for task in _tasks(args):
                 def load(a, b, d=d, task=task):
                     gt, _ = D.load_gt_dir(d, limit=args.limit, start=a, stop=b)
-                    batch = acquisition.task_problem(task, gt, env, seed=args.seed, first_slice=a, mask_kind=args.mask, coils=args.coils,
-                                                    noise_cov=_psi(args))
+                    mask = None
+                    if args.mask == "uniform":                     # a task whose acceleration does not divide the width has no comb
+                        try:
+                            mask = acquisition.make_mask(gt.shape[-2], gt.shape[-1], acquisition.parse_task(task)[0], "uniform", args.seed)
+                        except ValueError as e:
+                            raise SystemExit(f"--mask uniform: task {task}: {e}")
+                    batch = acquisition.task_problem(task, gt, env, seed=args.seed, first_slice=a, mask_kind=args.mask, mask=mask,
+                                                    coils=args.coils, noise_cov=_psi(args))
                     return _with_sens(args, env, batch), D.task_tokens([task] * (b - a), flex_target)
                 yield f"{d} {task}", D.count_gt_dir(d, args.limit), load
     elif args.data:
@@ -193,9 +228,13 @@ def _sets(args, flex_target=None, env=None):
         for accel, sig in ((4, 10), (8, 10)):
             def load(a, b, accel=accel, sig=sig):
                 # the synthetic sets are radial; a --sens estimate run may ask for --mask cartesian, whose calibration block is H x the
-                # centre columns (None: the radial mask of make_problem, as every other run gets)
-                mask = acquisition.make_mask(args.size, args.size, accel, args.mask, args.seed) \
-                    if args.sens != "true" and args.mask != "radial" else None
+                # centre columns, and --mask uniform (the comb --grappa works on) always applies (None: the radial mask of make_problem, as
+                # every other run gets)
+                try:
+                    mask = acquisition.make_mask(args.size, args.size, accel, args.mask, args.seed) \
+                        if args.mask == "uniform" or (args.sens != "true" and args.mask != "radial") else None
+                except ValueError as e:                        # --mask uniform at a size the acceleration does not divide
+                    raise SystemExit(f"--mask {args.mask}: {e}")
                 if args.acquire == "device" or args.noise_cov:   # (correlated noise is mixed on the device) make_problem's phantoms, mask and noise; the transforms on the GPU
                     gt = np.stack([synthetic.phantom(args.size, args.size, args.seed + accel + i) for i in range(a, b)])
                     sens = synthetic.coil_maps(args.coils, args.size, args.size).astype(np.complex64) if args.coils else None
@@ -241,7 +280,12 @@ def _acquire(args):
             if key not in engines:
                 engines[key] = PnPEngine(*key, denoiser=False)
             for task in tasks:
-                p = acquisition.task_problem(task, gt, engines[key], seed=args.seed, first_slice=a, mask_kind=args.mask)
+                try:
+                    p = acquisition.task_problem(task, gt, engines[key], seed=args.seed, first_slice=a, mask_kind=args.mask)
+                except ValueError as e:
+                    if args.mask != "uniform":
+                        raise
+                    raise SystemExit(f"--mask uniform: task {task}: {e}")
                 host = {k: v.cpu().numpy() for k, v in p.items()}
                 for i, name in enumerate(names):
                     D.save_mat(os.path.join(dsts[task], acquired_name(task, name)), host, i)
@@ -261,8 +305,15 @@ def main(argv=None):
     ap.add_argument("--gt", nargs="+", default=None, help="directories of ground-truth images (.npy / .mat with a `gt` key), "
                     "acquired on the device: one set per (directory, task)")
     ap.add_argument("--tasks", default=None, help="comma-separated tasks for --gt, e.g. 4x_10,8x_15 (default: the reference's nine)")
-    ap.add_argument("--mask", choices=("radial", "cartesian"), default="radial", help="sampling mask of the --gt sets "
-                    "(and of the synthetic sets of a --sens estimate run)")
+    ap.add_argument("--mask", choices=("radial", "cartesian", "uniform"), default="radial", help="sampling mask of the --gt sets "
+                    "(cartesian: and of the synthetic sets of a --sens estimate run; uniform: of the synthetic sets too); uniform: every accel-th "
+                    "column under a centre block of at least 3 accel + 4 columns")
+    ap.add_argument("--grappa", action="store_true", help="start a --coils run from the map-combined image of the GRAPPA-filled k-space "
+                    "(needs a comb: --mask uniform)")
+    ap.add_argument("--grappa-kernel", type=int, nargs=2, default=(5, 4), metavar=("BY", "BX"), help="--grappa: rows (1, 3, 5 or 7) by "
+                    "acquired columns (2 or 4) of the interpolation kernel, coils * BY * BX <= 512")
+    ap.add_argument("--grappa-lambda", type=float, default=1e-2, metavar="L", help="--grappa: Tikhonov weight of the calibration, relative "
+                    "to the mean diagonal of its normal matrix (in [0, 1])")
     ap.add_argument("--acquire", choices=("cpu", "device"), default="cpu",
                     help="where the synthetic sets are acquired: synthetic.make_problem on the CPU, or pnp_acquire on the GPU")
     ap.add_argument("--limit", type=int, default=None, help="images per directory (default 7: the reference averages the first 7; "
@@ -355,6 +406,19 @@ def main(argv=None):
         raise SystemExit("--prewhiten applies to eval|flex|mcts|fixed: acquire writes the measurements as they are")
     if args.prewhiten and not args.coils:
         raise SystemExit("--prewhiten needs --coils: there are no channels to whiten on a single-coil problem")
+    if args.grappa:
+        if args.mode == "acquire":
+            raise SystemExit("--grappa applies to eval|flex|mcts|fixed: acquire writes the measurements as they are")
+        if not args.coils:
+            raise SystemExit("--grappa needs --coils: GRAPPA interpolates across the channels of a multi-coil problem")
+        if args.mask != "uniform":
+            raise SystemExit(f"--grappa needs a comb of acquired columns: --mask uniform (got --mask {args.mask})")
+        by, bx = args.grappa_kernel
+        c = args.compress or args.coils
+        if by not in (1, 3, 5, 7) or bx not in (2, 4) or c * by * bx > 512:
+            raise SystemExit(f"--grappa-kernel takes BY in 1, 3, 5, 7 and BX in 2, 4 with coils * BY * BX <= 512, got {by} {bx} at {c} coils")
+        if not 0.0 <= args.grappa_lambda <= 1.0:
+            raise SystemExit(f"--grappa-lambda must be in [0, 1], got {args.grappa_lambda}")
     args.compress_energy = []
     if args.compress:
         if not args.coils:

@@ -123,6 +123,9 @@ struct pnp_engine {
     // ESPIRiT maps (pnp_espirit_sens): allocated inside its first call, grown by a call that needs more
     void* es_ws = nullptr;       // per slice G and the vectors [2, np, np] complex128, then R [N, C, C, D, D] complex64, then nkept [N]
     size_t es_cap = 0;
+    // GRAPPA weights (pnp_grappa_weights): allocated inside its first call, grown by a call that needs more
+    double2* gr_ws = nullptr;    // per slice M = A^H [A | T], [ns, ns + nt] complex128; the solve factors it in place
+    size_t gr_cap = 0;
     // the prior of pnp_step (pnp_set_prior) and the total-variation denoiser's workspace (allocated inside the first call that runs it)
     int prior = PNP_PRIOR_UNET;
     double tv_scale = 1.0;       // as given; applied as float32
@@ -508,6 +511,11 @@ int pw_ensure(pnp_engine* e, size_t need) {
 // The workspace of pnp_espirit_sens beyond cm_ensure's: one buffer of `need` bytes
 int es_ensure(pnp_engine* e, size_t need) { return ws_grow(e, "ESPIRiT workspace", {{&e->es_ws, &e->es_cap, need, false}}); }
 
+// The workspace of pnp_grappa_weights: `need` complex128 entries
+int gr_ensure(pnp_engine* e, size_t need) {
+    return ws_grow(e, "GRAPPA workspace", {{(void**)&e->gr_ws, &e->gr_cap, need * sizeof(double2), false}});
+}
+
 // The workspace of the total-variation denoiser: one (py, px) plane
 int tv_ensure(pnp_engine* e) {
     const size_t bytes = (size_t)e->cfg.n * e->cfg.h * e->cfg.w * sizeof(float2);
@@ -682,6 +690,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->cc_part); (void)hipFree(e->cc_gram);
     (void)hipFree(e->pw_part);
     (void)hipFree(e->es_ws);
+    (void)hipFree(e->gr_ws);
     (void)hipFree(e->tv_p);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -1368,6 +1377,103 @@ int pnp_espirit_sens(pnp_handle e, const float* y0, int coils, int acs_h, int ac
     p.end(3);
     return PNP_OK;
     PNP_API_END("pnp_espirit_sens")
+}
+
+namespace {
+// the kernel geometry shared by the two GRAPPA entry points; scalar ranges only, no handle
+int grappa_check_kernel(const char* fn, int coils, int accel, int by, int bx) {
+    if (coils < 1 || coils > PNP_GRAPPA_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_GRAPPA_MAX_COILS, coils);
+    if (accel < 2 || accel > PNP_GRAPPA_MAX_ACCEL) return fail(PNP_ERR_INVALID, "%s: accel must be 2..%d (got %d)", fn, PNP_GRAPPA_MAX_ACCEL, accel);
+    if (by != 1 && by != 3 && by != 5 && by != 7) return fail(PNP_ERR_INVALID, "%s: by must be 1, 3, 5 or 7 (got %d)", fn, by);
+    if (bx != 2 && bx != 4) return fail(PNP_ERR_INVALID, "%s: bx must be 2 or 4 (got %d)", fn, bx);
+    if (coils * by * bx > PNP_GRAPPA_MAX_SRC)
+        return fail(PNP_ERR_INVALID, "%s: coils * by * bx must be <= %d (got %d * %d * %d)", fn, PNP_GRAPPA_MAX_SRC, coils, by, bx);
+    return PNP_OK;
+}
+// [a, a + an) and [b, b + bn) share a byte
+bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + bn && pb < pa + an;
+}
+}  // namespace
+
+int pnp_grappa_weights(pnp_handle e, const float* y0, int coils, int acs_h, int acs_w, int accel, int by, int bx, double lam, int flags,
+                       float* wts, int32_t* info, double* gram, void* stream) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call, and leaves the outputs untouched; scalar ranges first
+    const char* fn = "pnp_grappa_weights";
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (!(lam >= 0.0) || !(lam <= 1.0)) return fail(PNP_ERR_INVALID, "%s: lam must be finite and in [0, 1] (got %g)", fn, lam);
+    if (int rc = grappa_check_kernel(fn, coils, accel, by, bx)) return rc;
+    const int span = (bx - 1) * accel + 1;
+    if (acs_h < by || (acs_h & 1)) return fail(PNP_ERR_INVALID, "%s: acs_h must be even and >= by=%d (got %d)", fn, by, acs_h);
+    if (acs_w < span || (acs_w & 1)) return fail(PNP_ERR_INVALID, "%s: acs_w must be even and >= (bx - 1) accel + 1 = %d (got %d)", fn, span, acs_w);
+    if (!y0) return fail(PNP_ERR_INVALID, "%s: null y0", fn);
+    if (!wts) return fail(PNP_ERR_INVALID, "%s: null wts", fn);
+    if (!info) return fail(PNP_ERR_INVALID, "%s: null info", fn);
+    {
+        const void* q[4] = {y0, wts, info, gram};
+        for (int i = 0; i < 4; ++i)
+            for (int j = i + 1; j < 4; ++j)
+                if (q[j] && q[i] == q[j]) return fail(PNP_ERR_INVALID, "%s: y0, wts, info and gram must not alias", fn);
+    }
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (W % accel) return fail(PNP_ERR_INVALID, "%s: accel must divide w=%d (got %d)", fn, W, accel);
+    if (acs_h > H) return fail(PNP_ERR_INVALID, "%s: acs_h must be <= h=%d (got %d)", fn, H, acs_h);
+    if (acs_w > W) return fail(PNP_ERR_INVALID, "%s: acs_w must be <= w=%d (got %d)", fn, W, acs_w);
+    if ((long long)N * coils > 65535) return fail(PNP_ERR_INVALID, "%s: n * coils must be <= 65535 (got %d * %d)", fn, N, coils);
+    const int ns = coils * by * bx, nt = coils * (accel - 1);
+    {   // with the sizes known: no two of the four buffers may share a byte
+        const void* q[4] = {y0, wts, info, gram};
+        const size_t len[4] = {(size_t)N * coils * H * W * sizeof(float2), (size_t)N * nt * ns * sizeof(float2), (size_t)N * sizeof(int32_t),
+                               (size_t)N * ns * (ns + nt) * sizeof(double2)};
+        for (int i = 0; i < 4; ++i)
+            for (int j = i + 1; j < 4; ++j)
+                if (q[j] && ranges_overlap(q[i], len[i], q[j], len[j])) return fail(PNP_ERR_INVALID, "%s: y0, wts, info and gram must not alias", fn);
+    }
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = gr_ensure(e, (size_t)N * ns * (ns + nt))) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_grappa_gram((const float2*)y0, coils, acs_h, acs_w, accel, by, bx, e->gr_ws, (double2*)gram, N, H, W, s));
+    HIP_TRY(launch_grappa_solve(e->gr_ws, ns, nt, lam, (float2*)wts, (int*)info, N, s));
+    p.end(2);
+    return PNP_OK;
+    PNP_API_END("pnp_grappa_weights")
+}
+
+int pnp_grappa_apply(pnp_handle e, const float* y0, int coils, const uint8_t* mask, int mask_n, int accel, int offset, int by, int bx,
+                     const float* wts, int wts_n, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_grappa_apply";
+    if (int rc = grappa_check_kernel(fn, coils, accel, by, bx)) return rc;
+    if (offset < 0 || offset >= accel) return fail(PNP_ERR_INVALID, "%s: offset must be 0..accel-1 = %d (got %d)", fn, accel - 1, offset);
+    if (mask_n < 1) return fail(PNP_ERR_INVALID, "%s: mask_n must be 1 or the handle's n (got %d)", fn, mask_n);
+    if (wts_n < 1) return fail(PNP_ERR_INVALID, "%s: wts_n must be 1 or the handle's n (got %d)", fn, wts_n);
+    if (!y0) return fail(PNP_ERR_INVALID, "%s: null y0", fn);
+    if (!mask) return fail(PNP_ERR_INVALID, "%s: null mask", fn);
+    if (!wts) return fail(PNP_ERR_INVALID, "%s: null wts", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    // the planes of the smallest handle (16 x 16) already span 2048 coils bytes: a y0 and an out closer than that overlap whatever the handle is
+    if (out == wts || (const void*)out == (const void*)mask || ranges_overlap(out, (size_t)2048 * coils, y0, (size_t)2048 * coils))
+        return fail(PNP_ERR_INVALID, "%s: out must not overlap y0, wts or mask", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (W % accel) return fail(PNP_ERR_INVALID, "%s: accel must divide w=%d (got %d)", fn, W, accel);
+    if (mask_n != 1 && mask_n != N) return fail(PNP_ERR_INVALID, "%s: mask_n must be 1 or the handle's n=%d (got %d)", fn, N, mask_n);
+    if (wts_n != 1 && wts_n != N) return fail(PNP_ERR_INVALID, "%s: wts_n must be 1 or the handle's n=%d (got %d)", fn, N, wts_n);
+    if ((long long)N * coils > 65535) return fail(PNP_ERR_INVALID, "%s: n * coils must be <= 65535 (got %d * %d)", fn, N, coils);
+    const size_t ns = (size_t)coils * by * bx, nt = (size_t)coils * (accel - 1);
+    const size_t bytes = (size_t)N * coils * H * W * sizeof(float2), wbytes = (size_t)wts_n * nt * ns * sizeof(float2), mbytes = (size_t)mask_n * H * W;
+    if (ranges_overlap(out, bytes, y0, bytes) || ranges_overlap(out, bytes, wts, wbytes) || ranges_overlap(out, bytes, mask, mbytes))
+        return fail(PNP_ERR_INVALID, "%s: out must not overlap y0, wts or mask", fn);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_grappa_apply((const float2*)y0, mask, mask_n, (const float2*)wts, wts_n, (float2*)out, coils, accel, offset, by, bx, N, H, W, s));
+    return PNP_OK;
+    PNP_API_END("pnp_grappa_apply")
 }
 
 size_t pnp_snapshot_bytes(pnp_handle e) {

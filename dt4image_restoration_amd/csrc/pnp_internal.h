@@ -298,6 +298,16 @@ hipError_t launch_prewhiten_chol(const double2* psi, int psi_n, int C, float2* w
 // out[n, v] = sum_{c <= v} wmat[n or 0][v][c] in[n, c]; in, out: [N, C, H, W]; out may be in
 hipError_t launch_prewhiten_apply(const float2* in, const float2* wmat, int wmat_n, int C, float2* out, int N, int H, int W, hipStream_t s);
 
+// ---- GRAPPA (grappa_kernels.hip) ---------------------------------------------------------------------
+// ns = C by bx sources, nt = C (R - 1) targets.  ws: per slice M [ns][ns + nt] complex128 (the solve destroys it); gram: the same layout or nullptr
+hipError_t launch_grappa_gram(const float2* y, int C, int acs_h, int acs_w, int R, int by, int bx, double2* ws, double2* gram, int N, int H, int W,
+                              hipStream_t s);
+// wts: [N, nt, ns] complex64, info: [N]; one workgroup per slice
+hipError_t launch_grappa_solve(double2* ws, int ns, int nt, double lam, float2* wts, int* info, int N, hipStream_t s);
+// out: [N, C, H, W]; the comb x = offset (mod R) and the bins of mask are copies of y0, the others are synthesised; out overlaps nothing
+hipError_t launch_grappa_apply(const float2* y0, const uint8_t* mask, int mask_n, const float2* wts, int wts_n, float2* out, int C, int R,
+                               int offset, int by, int bx, int N, int H, int W, hipStream_t s);
+
 // ---- ESPIRiT coil maps (espirit_kernels.hip) --------------------------------------------------------
 // np: the side of the calibration Gram matrix, n = C k^2 rounded up to even.  ws: per slice G [np][np] then the transposed vectors [np][np], complex128
 inline int espirit_padded(int C, int k) { return (C * k * k + 1) & ~1; }

@@ -467,6 +467,69 @@ class PnPEngine:
                    "pnp_whiten_apply")
         return out
 
+    @staticmethod
+    def _grappa_kernel(coils: int, accel: int, kernel) -> Tuple[int, int, int, int]:
+        """(by, bx, ns, nt) of a GRAPPA kernel, or ValueError for what pnp_grappa_* would refuse"""
+        by, bx = (int(v) for v in kernel)
+        if not 1 <= coils <= _lib.PNP_GRAPPA_MAX_COILS:
+            raise ValueError(f"grappa takes 1..{_lib.PNP_GRAPPA_MAX_COILS} coils, got {coils}: compress the channels first")
+        if not 2 <= accel <= _lib.PNP_GRAPPA_MAX_ACCEL:
+            raise ValueError(f"accel must be 2..{_lib.PNP_GRAPPA_MAX_ACCEL}, got {accel}")
+        if by not in (1, 3, 5, 7) or bx not in (2, 4) or coils * by * bx > _lib.PNP_GRAPPA_MAX_SRC:
+            raise ValueError(f"kernel must be (1|3|5|7, 2|4) with coils * by * bx <= {_lib.PNP_GRAPPA_MAX_SRC}, got {(by, bx)} at {coils} coils")
+        return by, bx, coils * by * bx, coils * (accel - 1)
+
+    def grappa_weights(self, y0: torch.Tensor, acs: Tuple[int, int], accel: int, kernel: Tuple[int, int] = (5, 4), lam: float = 1e-2,
+                       return_gram: bool = False):
+        """GRAPPA interpolation weights from the fully sampled calibration block of multi-coil k-space (pnp_grappa_weights): y0 complex64
+        [N,C,H,W] in the centred layout, C <= 32, acs = (acs_h, acs_w) the even sides of the centred block, accel = R the spacing of the
+        comb of acquired columns (it divides W), kernel = (by, bx): by rows (1, 3, 5 or 7) by bx acquired columns (2 or 4).  Per slice the
+        normal equations of all windows of the block, regularised by lam * trace / ns, are solved in float64 on the device.  Returns
+        (wts complex64 [N,nt,ns], info int32 [N]) with ns = C by bx sources and nt = C (R - 1) targets - info is 0, or j + 1 when pivot j
+        fails (that slice's weights are then zero; nothing is read back: check info where it matters) - and with return_gram also the
+        normal matrix A^H [A | T], complex128 [N,ns,ns+nt].  lam = 1e-2 is a default from a scan on the analytic coils, not a tuned value.
+        Does not change the engine's mode or its installed constants."""
+        if y0.dim() != 4 or y0.shape[0] != self.n or tuple(y0.shape[-2:]) != (self.h, self.w):
+            raise ValueError(f"y0: expected [{self.n},C,{self.h},{self.w}], got {tuple(y0.shape)}")
+        coils, accel = int(y0.shape[1]), int(accel)
+        y0 = self._chk(y0, torch.complex64, self.n * coils * self.h * self.w, "y0")
+        by, bx, ns, nt = self._grappa_kernel(coils, accel, kernel)
+        acs_h, acs_w = (int(v) for v in acs)
+        wts = torch.empty((self.n, nt, ns), dtype=torch.complex64, device=self.device)
+        info = torch.empty((self.n,), dtype=torch.int32, device=self.device)
+        gram = torch.empty((self.n, ns, ns + nt), dtype=torch.complex128, device=self.device) if return_gram else None
+        _lib.check(self.lib.pnp_grappa_weights(self._h, y0.data_ptr(), coils, acs_h, acs_w, accel, by, bx, float(lam), 0, wts.data_ptr(),
+                                               info.data_ptr(), _ptr(gram), self._stream()), "pnp_grappa_weights")
+        return (wts, info, gram) if return_gram else (wts, info)
+
+    def grappa_apply(self, y0: torch.Tensor, wts: torch.Tensor, mask: torch.Tensor, accel: int, offset: int, kernel: Tuple[int, int] = (5, 4),
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """K-space with its missing columns synthesised from their acquired neighbours (pnp_grappa_apply): y0 complex64 [N,C,H,W], wts
+        complex64 [nt,ns] (one set for all slices) or [N,nt,ns] from `grappa_weights`, mask bool/uint8 [H,W] or [N,H,W] in the centred
+        layout, the acquired comb x = offset (mod accel).  Bins of the mask and of the comb are copies of y0; every other bin is the
+        weighted sum of its by x bx x C neighbours on the comb, indices periodic.  out must not overlap y0; None allocates it."""
+        if y0.dim() != 4 or y0.shape[0] != self.n or tuple(y0.shape[-2:]) != (self.h, self.w):
+            raise ValueError(f"y0: expected [{self.n},C,{self.h},{self.w}], got {tuple(y0.shape)}")
+        coils, accel, offset = int(y0.shape[1]), int(accel), int(offset)
+        y0 = self._chk(y0, torch.complex64, self.n * coils * self.h * self.w, "y0")
+        by, bx, ns, nt = self._grappa_kernel(coils, accel, kernel)
+        if tuple(wts.shape) not in ((nt, ns), (1, nt, ns), (self.n, nt, ns)):
+            raise ValueError(f"wts: expected [{nt},{ns}] or [{self.n},{nt},{ns}], got {tuple(wts.shape)}")
+        wts_n = 1 if wts.numel() == nt * ns else self.n
+        wts = self._chk(wts, torch.complex64, wts_n * nt * ns, "wts")
+        m = mask.to(torch.uint8).contiguous()
+        if m.numel() not in (self.h * self.w, self.n * self.h * self.w):
+            raise ValueError(f"mask: expected {self.h * self.w} or {self.n * self.h * self.w} elements, got {tuple(mask.shape)}")
+        self._chk(m, torch.uint8, m.numel(), "mask")
+        if out is None:
+            out = torch.empty_like(y0)
+        elif tuple(out.shape) != tuple(y0.shape):
+            raise ValueError(f"out: expected {tuple(y0.shape)}, got {tuple(out.shape)}")
+        out = self._chk(out, torch.complex64, y0.numel(), "out")
+        _lib.check(self.lib.pnp_grappa_apply(self._h, y0.data_ptr(), coils, m.data_ptr(), 1 if m.numel() == self.h * self.w else self.n, accel,
+                                             offset, by, bx, wts.data_ptr(), wts_n, out.data_ptr(), self._stream()), "pnp_grappa_apply")
+        return out
+
     def snapshot(self, x: torch.Tensor, z: torch.Tensor, u: torch.Tensor, t_state: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One packed device buffer [x | z | u | T] (pnp_snapshot): a tree-search node's copy of the iterate."""

@@ -501,6 +501,64 @@ int pnp_espirit_sens(pnp_handle h, const float* y0, int coils, int acs_h, int ac
                      int window, double thresh, int flags, float* sens, float* eval /* [N,H,W], may be NULL */,
                      float* kern /* complex64 [N,C,C,2k-1,2k-1], may be NULL */, int32_t* nkept /* [N], may be NULL */, void* stream);
 
+/* GRAPPA: autocalibrated k-space interpolation, the k-space counterpart of the map-based stages above (the reference has no counterpart).  The
+ * undersampled axis is W (whole columns, as cartesian_mask); the acquired columns are the integer comb x = offset (mod R), R = accel, W % R == 0,
+ * plus a fully sampled centre.  A kernel of `by` rows (odd) by `bx` comb columns (2 or 4) synthesises the R - 1 missing columns to the right of a
+ * comb column xa from their acquired neighbours in every coil.  Per slice, centred layout, C = coils:
+ *     sources of (y, xa):  (c, y + i - by/2, xa + (j - (bx/2 - 1)) R),  i < by, j < bx;    index s = (c by + i) bx + j,    ns = C by bx
+ *     targets of (y, xa):  (c', y, xa + r),  r = 1 .. R-1;                                 index t = c' (R-1) + (r-1),     nt = C (R-1)
+ *   All targets of a comb column share its sources.
+ *
+ * pnp_grappa_weights, per slice n, with the centred acs_h x acs_w block B of pnp_estimate_sens (it must be fully sampled; y0 is read inside it only):
+ *   Windows.  All (acs_h - by + 1)(acs_w - span + 1) window positions (wy, wx) of the block, span = (bx-1) R + 1, in row-major order; windows do
+ *     not wrap.  A[w][s] = B[c][wy+i][wx+jR],  T[w][t] = B[c'][wy+by/2][wx+(bx/2-1)R+r],  Z = [A | T].
+ *   Gram.  M[s][j] = sum_w conj(A[w][s]) Z[w][j], j < ns + nt: the float32 components multiplied and summed in float64 (the products are exact), one
+ *     thread per entry walking the windows in order (re += xr yr; re += xi yi; im += xr yi; im -= xi yr for conj(x) y, the convention of
+ *     pnp_espirit_sens).  For j < ns only j <= s is formed and mirrored: the left block G is exactly Hermitian, its diagonal real.  No atomics.
+ *     gram, when not NULL, receives M before regularisation.
+ *   Regularisation.  lam * trace(G) / ns is added to G's diagonal; the trace is summed in float64 with s ascending.
+ *   Solve.  G X = Rh (Rh = the right block of M) by Cholesky and forward and back substitution, one workgroup per slice, float64, the matrix in the
+ *     slice's workspace in device memory.  The factor by the column formulas of pnp_whiten_matrix (every sum from 0.0, k ascending); then per
+ *     right-hand side  Y[i] = (Rh[i] - sum_{k<i} L[i][k] Y[k]) / L[i][i], i ascending, and  X[i] = (Y[i] - sum_{k>i} conj(L[k][i]) X[k]) / L[i][i],
+ *     i descending, k ascending.
+ *   info[n] = 0, or j + 1 for the first column whose pivot is not finite, not positive or not greater than 1e-12 * max_i (regularised) G[i][i] -
+ *     the rule of pnp_whiten_matrix; that slice's wts are then all +0 (pnp_grappa_apply leaves its missing bins zero): no finite input gives
+ *     NaN and no host read is needed.  An all-zero block gives info = 1.
+ *   wts[n][t][s] = X[s][t], rounded to complex64 once.
+ *   y0    : DEVICE complex64 [N,C,H,W];   coils : 1..PNP_GRAPPA_MAX_COILS;   accel : 2..PNP_GRAPPA_MAX_ACCEL, W % accel == 0
+ *   by    : 1, 3, 5 or 7;   bx : 2 or 4;   coils * by * bx <= PNP_GRAPPA_MAX_SRC
+ *   acs_h : even, by <= acs_h <= H;   acs_w : even, span <= acs_w <= W.  A block with fewer windows than ns is rank deficient before lam is added
+ *   lam   : finite, in [0, 1];   flags : reserved, must be 0;   n * coils <= 65535
+ *   wts   : DEVICE complex64 [N,nt,ns] out;   info : DEVICE int32 [N] out;   gram : DEVICE complex128 [N,ns,ns+nt] out, or NULL; none may alias another
+ *   SETUP-TIME SEMANTICS, as pnp_coil_compress_matrix: the first call allocates 16 n ns (ns + nt) bytes (M) inside the call, all-or-nothing (on
+ *   PNP_ERR_NOMEM the handle keeps the workspace it had), counted by pnp_workspace_bytes.  A later call allocates only if it needs more than any
+ *   call before it, and then waits for the device; every other call allocates nothing and is asynchronous.  Calls on one handle are stream-ordered.
+ *
+ * pnp_grappa_apply, for every bin (y, x) of every coil c':
+ *     out = y0 (the bits)                                   where mask[n or 0][y][x] != 0
+ *         = y0 (the bits)                                   where x mod R == offset: the caller promises that the comb is sampled
+ *         = sum over s ascending of wts[n or 0][t][s] * src_s   otherwise, with xa the comb column at or below x (periodically), r = x - xa
+ *   Source indices are periodic, mod H in y and mod W in x: the comb of a width divisible by R is periodic, so every missing bin has full support.
+ *   float32 from re = im = +0 with the fused multiply-add chain of pnp_coil_compress_apply:
+ *     re = fma(a.re, x.re, re);  re = fma(-a.im, x.im, re);  im = fma(a.re, x.im, im);  im = fma(a.im, x.re, im)        (a = wts[t][s], x = src_s)
+ *   so a one-hot weight copies its source plane, shifted.  The bits do not depend on which kernel variant runs.
+ *   mask  : DEVICE u8 [mask_n,H,W], centred;   mask_n : 1 or N;   wts : DEVICE complex64 [wts_n,nt,ns];   wts_n : 1 or N;   0 <= offset < accel
+ *   out   : DEVICE complex64 [N,C,H,W]; must not overlap y0, wts or mask (neighbouring bins read y0)
+ *   It does 8 ns real operations per synthesised value, allocates nothing and is asynchronous; n * coils <= 65535.
+ *
+ * Both calls take any handle kind and change neither the handle's mode nor its installed constants.  A slice's bits depend on its own input and
+ * the arguments only: not on N, its place in the batch, the stream or the handle kind; no atomics.  Every argument error (null handle or pointer,
+ * a count or size out of range, flags != 0, forbidden aliasing) is reported with PNP_ERR_INVALID and a message naming the argument, before any
+ * HIP call, and leaves the outputs untouched. */
+#define PNP_GRAPPA_MAX_COILS 32
+#define PNP_GRAPPA_MAX_ACCEL 8
+#define PNP_GRAPPA_MAX_SRC   512
+int pnp_grappa_weights(pnp_handle h, const float* y0, int coils, int acs_h, int acs_w, int accel, int by, int bx, double lam, int flags,
+                       float* wts /* complex64 [N,nt,ns] */, int32_t* info /* [N] */,
+                       double* gram /* complex128 [N,ns,ns+nt], may be NULL */, void* stream);
+int pnp_grappa_apply(pnp_handle h, const float* y0, int coils, const uint8_t* mask, int mask_n, int accel, int offset, int by, int bx,
+                     const float* wts, int wts_n, float* out /* complex64 [N,C,H,W] */, void* stream);
+
 /* ---- tree search support --------------------------------------------------------------------- */
 
 /* Replaces: the per-child copy of `states` in expand_tree (evaluation/mcts.py:118-128), which the reference gets for
