@@ -32,6 +32,12 @@ PNP_TV_MAX_ITERS = 64
 PNP_PRIOR_UNET = 0
 PNP_PRIOR_TV = 1
 PRIORS = {"unet": PNP_PRIOR_UNET, "tv": PNP_PRIOR_TV}      # prior names of pnp_set_prior
+PNP_PRIOR_HAAR = 2                                         # set by pnp_set_prior_haar, never by pnp_set_prior
+PRIOR_NAMES = {PNP_PRIOR_UNET: "unet", PNP_PRIOR_TV: "tv", PNP_PRIOR_HAAR: "haar"}      # what pnp_get_prior can report
+PNP_HAAR_TI = 0
+PNP_HAAR_ORTHO = 1
+PNP_HAAR_MAX_LEVELS = 4
+HAAR_MODES = {"ti": PNP_HAAR_TI, "ortho": PNP_HAAR_ORTHO}      # mode names of pnp_haar_denoise / pnp_set_prior_haar
 PNP_SENS_BOX = 0
 PNP_SENS_HANN = 1
 SENS_WINDOWS = {"box": PNP_SENS_BOX, "hann": PNP_SENS_HANN}      # window names of pnp_estimate_sens
@@ -60,6 +66,9 @@ SIGNATURES = {
     "pnp_tv_denoise": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, _vp]),
     "pnp_set_prior": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int]),
     "pnp_get_prior": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "pnp_haar_denoise": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_set_prior_haar": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int]),
+    "pnp_get_prior_haar": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pnp_fft2c": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "pnp_prox_dual": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _fp, _fp, _vp]),
     "pnp_psnr": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),

@@ -53,6 +53,12 @@ The classical baseline beside the U-Net: `--prior tv [--tv-scale 1.0] [--tv-iter
 
     ... --prior tv fixed --mu 0.3 --sigma-start 50 --sigma-end 5 --max_iter 30
 
+The other classical baseline: `--prior haar [--haar-scale 1.0] [--haar-levels 3] [--haar-mode ti|ortho]` runs the x-update as Haar wavelet
+shrinkage with threshold haar-scale * sigma_d (pnp_set_prior_haar; ti = translation-invariant, fully cycle-spun; ortho = the decimated
+transform), again on k-space-only handles without weights:
+
+    ... --prior haar fixed --mu 0.3 --sigma-start 50 --sigma-end 5 --max_iter 30
+
 Multi-GPU (BASELINE configs[2]): launch the same command under `python -m torch.distributed.run --nproc-per-node N
 --master-addr 127.0.0.1 -m dt4image_restoration_amd.cli ... eval|mcts|flex ...`: every rank takes a contiguous shard of each
 set's images (drivers/sharded.py), the per-image PSNR / stop iteration are gathered over RCCL, rank 0 prints.
@@ -74,7 +80,11 @@ import torch
 
 
 def _denoiser(args):
-    """The regulariser object of the run: the U-Net (checkpoint or seeded stand-in), or under --prior tv the weightless TV denoiser."""
+    """The regulariser object of the run: the U-Net (checkpoint or seeded stand-in), or under --prior tv / haar the weightless TV / Haar
+    denoiser."""
+    if args.prior == "haar":
+        from .denoiser import HaarDenoiser2D
+        return HaarDenoiser2D(scale=args.haar_scale, levels=args.haar_levels, mode=args.haar_mode)
     if args.prior == "tv":
         from .denoiser import TVDenoiser2D
         return TVDenoiser2D(scale=args.tv_scale, iters=args.tv_iters)
@@ -344,10 +354,13 @@ def main(argv=None):
                     "the maps of --sens true) on the device, before --compress and --sens estimate|espirit")
     ap.add_argument("--acs", type=int, nargs=2, default=None, metavar=("H", "W"), help="--sens estimate / --compress: even sides of the centred "
                     "calibration block (default: the largest block the mask samples completely)")
-    ap.add_argument("--prior", choices=("unet", "tv"), default="unet", help="the x-update of eval / flex / mcts / fixed: the U-Net, or total "
-                    "variation (needs no --denoiser-ckpt and loads no weights)")
+    ap.add_argument("--prior", choices=("unet", "tv", "haar"), default="unet", help="the x-update of eval / flex / mcts / fixed: the U-Net, total "
+                    "variation or Haar wavelet shrinkage (the last two need no --denoiser-ckpt and load no weights)")
     ap.add_argument("--tv-scale", type=float, default=1.0, help="--prior tv: the TV weight is this times sigma_d (finite, >= 0)")
     ap.add_argument("--tv-iters", type=int, default=20, help="--prior tv: dual projection steps per x-update (1..64)")
+    ap.add_argument("--haar-scale", type=float, default=1.0, help="--prior haar: the threshold is this times sigma_d (finite, >= 0)")
+    ap.add_argument("--haar-levels", type=int, default=3, help="--prior haar: levels of the transform (1..4)")
+    ap.add_argument("--haar-mode", default="ti", help="--prior haar: ti (translation-invariant, the default) or ortho (decimated)")
     ap.add_argument("--seed", type=int, default=0)
     sub = ap.add_subparsers(dest="mode", required=True)
     for name in ("eval", "mcts"):
@@ -390,6 +403,17 @@ def main(argv=None):
             raise SystemExit("--prior tv loads no weights: drop --denoiser-ckpt")
         if args.mode == "acquire":
             raise SystemExit("acquire has no x-update: drop --prior tv")
+    if args.prior == "haar":
+        if not (args.haar_scale >= 0.0 and np.isfinite(args.haar_scale)):
+            raise SystemExit(f"--haar-scale must be finite and >= 0, got {args.haar_scale}")
+        if not 1 <= args.haar_levels <= 4:
+            raise SystemExit(f"--haar-levels must be 1..4, got {args.haar_levels}")
+        if args.haar_mode not in ("ti", "ortho"):
+            raise SystemExit(f"--haar-mode must be ti or ortho, got {args.haar_mode!r}")
+        if args.denoiser_ckpt:
+            raise SystemExit("--prior haar loads no weights: drop --denoiser-ckpt")
+        if args.mode == "acquire":
+            raise SystemExit("acquire has no x-update: drop --prior haar")
     if args.noise_cov is not None:
         try:
             v = [float(t) for t in args.noise_cov.split(",")]

@@ -132,6 +132,12 @@ struct pnp_engine {
     int tv_iters = 20;
     bool tv_naive = false;       // PNP_TV_NAIVE=1 at pnp_create: one launch per iteration (the fused kernel's check and timing baseline)
     float2* tv_p = nullptr;      // [N,H,W] (py, px): the hand-over plane between launches; the other plane of the ping-pong is d_work
+    // the Haar wavelet prior (pnp_set_prior_haar): prior == PNP_PRIOR_HAAR while it is the x-update
+    double haar_scale = 1.0;     // as given; applied as float32
+    int haar_levels = 3;
+    int haar_mode = PNP_HAAR_TI;
+    bool haar_naive = false;     // PNP_HAAR_NAIVE=1 at pnp_create: TI as one launch per level (the fused kernel's check and timing baseline)
+    float* haar_ws = nullptr;    // naive form only, allocated inside its first TI call: kHaarNaivePlanes planes [N,H,W] (a_1 .. a_3, two of r_j)
     // profiling
     std::vector<EventPair> events;
     size_t ev_used = 0;
@@ -555,6 +561,56 @@ int run_tv(pnp_engine* e, const float* v, const float2* z, const float2* u, cons
     return PNP_OK;
 }
 
+// The planes of the naive Haar form: a_1 .. a_(J-1) and the residual's ping-pong pair, never replaced
+constexpr int kHaarNaivePlanes = PNP_HAAR_MAX_LEVELS - 1 + 2;
+static_assert(PNP_HAAR_MAX_LEVELS == kHaarMaxLevels, "the header's limit is the kernels'");
+int haar_ensure(pnp_engine* e) {
+    const size_t bytes = (size_t)e->cfg.n * e->cfg.h * e->cfg.w * sizeof(float) * kHaarNaivePlanes;
+    return ws_grow(e, "Haar workspace", {{(void**)&e->haar_ws, nullptr, e->haar_ws ? 0 : bytes, false}});
+}
+
+// out = Haar(v, scale * lam, levels, mode), v = the plane `v` or Re z - Re u.  ORTHO is one launch whose threads read and write their own
+// pixel.  A TI launch reads the halo of its neighbours' tiles, so it never writes the plane it reads: when out aliases v it writes the
+// data-fidelity stage's scratch plane (free while the x-update runs; calls on one handle are stream-ordered) and a copy ends the call.
+int run_haar(pnp_engine* e, const float* v, const float2* z, const float2* u, const float* lam, float scale, const float* tact, int levels,
+             int mode, float* out, hipStream_t s) {
+    const int N = e->cfg.n;
+    const size_t px = (size_t)N * e->cfg.h * e->cfg.w;
+    const bool ti = mode == PNP_HAAR_TI, naive = ti && e->haar_naive;
+    if (naive)
+        if (int rc = haar_ensure(e)) return rc;
+    HaarArgs a{};
+    a.v = v; a.z = z; a.u = u; a.lam = lam; a.scale = scale; a.tact = tact; a.H = e->cfg.h; a.W = e->cfg.w; a.levels = levels;
+    const bool alias = ti && v != nullptr && v == out;
+    a.out = alias ? (float*)e->d_work : out;
+    Prof p(e, s, PROF_OTHER, -1, true, true);
+    int launches = 1;
+    if (!ti) {
+        HIP_TRY(launch_haar_ortho(a, N, s));
+    } else if (!naive) {
+        HIP_TRY(launch_haar_ti_fused(a, N, s));
+    } else {
+        const auto plane = [&](int i) { return e->haar_ws + (size_t)i * px; };
+        launches = 0;
+        for (int j = 1; j < levels; ++j, ++launches) {             // a_j into plane j - 1
+            a.level = j; a.a_src = j > 1 ? plane(j - 2) : nullptr; a.a_dst = plane(j - 1);
+            HIP_TRY(launch_haar_ti_down(a, N, s));
+        }
+        for (int j = levels; j >= 1; --j, ++launches) {            // r_(j-1) from r_j, through the last two planes in turn
+            a.level = j; a.a_src = j > 1 ? plane(j - 2) : nullptr; a.a_dst = nullptr;
+            a.r_src = j < levels ? plane(kHaarNaivePlanes - 2 + (j & 1)) : nullptr;
+            a.r_dst = plane(kHaarNaivePlanes - 2 + ((j - 1) & 1));
+            HIP_TRY(launch_haar_ti_up(a, N, s));
+        }
+    }
+    if (alias) {
+        HIP_TRY(hipMemcpyAsync(out, e->d_work, px * sizeof(float), hipMemcpyDeviceToDevice, s));
+        ++launches;
+    }
+    p.end(launches);
+    return PNP_OK;
+}
+
 int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                   hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
@@ -664,6 +720,7 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     e->tune = tune;
     e->dplan = plan;
     if (const char* v = getenv("PNP_TV_NAIVE")) e->tv_naive = atoi(v) != 0;
+    if (const char* v = getenv("PNP_HAAR_NAIVE")) e->haar_naive = atoi(v) != 0;
     int rc;
     {
         DeviceGuard g(cfg->device);
@@ -692,6 +749,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->es_ws);
     (void)hipFree(e->gr_ws);
     (void)hipFree(e->tv_p);
+    (void)hipFree(e->haar_ws);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     delete e;
@@ -810,14 +868,17 @@ int pnp_step(pnp_handle e, const float* mu, const float* sigma_d, const float* t
              float* t_state, uint8_t* done, void* stream) {
     PNP_API_BEGIN
     if (!e || !mu || !sigma_d || !x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_step: null argument");
-    const bool tv = e->prior == PNP_PRIOR_TV;
-    if (!tv && !e->weights_loaded) return fail(PNP_ERR_STATE, "pnp_step: denoiser weights not loaded (pnp_load_unet_weights)");
+    const bool tv = e->prior == PNP_PRIOR_TV, haar = e->prior == PNP_PRIOR_HAAR;
+    if (!tv && !haar && !e->weights_loaded) return fail(PNP_ERR_STATE, "pnp_step: denoiser weights not loaded (pnp_load_unet_weights)");
     if (!e->reset_done) return fail(PNP_ERR_STATE, "pnp_step: pnp_reset has not been called");
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if (tv) {
         if ((rc = run_tv(e, nullptr, (const float2*)z, (const float2*)u, sigma_d, (float)e->tv_scale, t_action, e->tv_iters, x, s))) return rc;
+    } else if (haar) {
+        if ((rc = run_haar(e, nullptr, (const float2*)z, (const float2*)u, sigma_d, (float)e->haar_scale, t_action, e->haar_levels, e->haar_mode, x, s)))
+            return rc;
     } else if ((rc = run_unet(e, nullptr, (const float2*)z, (const float2*)u, sigma_d, t_action, x, s))) return rc;
     if ((rc = run_prox_dual(e, mu, t_action, x, (float2*)z, (float2*)u, s))) return rc;
     if (t_state || done) {
@@ -884,6 +945,50 @@ int pnp_get_prior(pnp_handle e, int* prior, double* tv_scale, int* tv_iters) {
     *tv_iters = e->tv_iters;
     return PNP_OK;
     PNP_API_END("pnp_get_prior")
+}
+
+int pnp_haar_denoise(pnp_handle e, const float* x_in, const float* lam, int levels, int mode, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_haar_denoise";
+    if (levels < 1 || levels > PNP_HAAR_MAX_LEVELS)
+        return fail(PNP_ERR_INVALID, "%s: levels must be 1..%d (got %d)", fn, PNP_HAAR_MAX_LEVELS, levels);
+    if (mode != PNP_HAAR_TI && mode != PNP_HAAR_ORTHO) return fail(PNP_ERR_INVALID, "%s: mode must be PNP_HAAR_TI or PNP_HAAR_ORTHO (got %d)", fn, mode);
+    if (!x_in) return fail(PNP_ERR_INVALID, "%s: null x_in", fn);
+    if (!lam) return fail(PNP_ERR_INVALID, "%s: null lam", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    PNP_ON_DEVICE(e);
+    return run_haar(e, x_in, nullptr, nullptr, lam, 1.0f, nullptr, levels, mode, out, (hipStream_t)stream);
+    PNP_API_END("pnp_haar_denoise")
+}
+
+int pnp_set_prior_haar(pnp_handle e, double haar_scale, int levels, int mode) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_set_prior_haar";
+    if (!(haar_scale >= 0.0) || !std::isfinite(haar_scale))
+        return fail(PNP_ERR_INVALID, "%s: haar_scale must be finite and >= 0 (got %g)", fn, haar_scale);
+    if (levels < 1 || levels > PNP_HAAR_MAX_LEVELS)
+        return fail(PNP_ERR_INVALID, "%s: levels must be 1..%d (got %d)", fn, PNP_HAAR_MAX_LEVELS, levels);
+    if (mode != PNP_HAAR_TI && mode != PNP_HAAR_ORTHO) return fail(PNP_ERR_INVALID, "%s: mode must be PNP_HAAR_TI or PNP_HAAR_ORTHO (got %d)", fn, mode);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    e->prior = PNP_PRIOR_HAAR;
+    e->haar_scale = haar_scale;
+    e->haar_levels = levels;
+    e->haar_mode = mode;
+    return PNP_OK;
+    PNP_API_END("pnp_set_prior_haar")
+}
+
+int pnp_get_prior_haar(pnp_handle e, double* haar_scale, int* levels, int* mode) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_get_prior_haar";
+    if (!haar_scale || !levels || !mode) return fail(PNP_ERR_INVALID, "%s: null pointer", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    *haar_scale = e->haar_scale;
+    *levels = e->haar_levels;
+    *mode = e->haar_mode;
+    return PNP_OK;
+    PNP_API_END("pnp_get_prior_haar")
 }
 
 int pnp_fft2c(pnp_handle e, const float* in, float* out, int batch, int hh, int ww, int inverse, void* stream) {

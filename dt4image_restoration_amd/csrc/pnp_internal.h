@@ -340,4 +340,30 @@ hipError_t launch_tv_fused(TvArgs a, int N, hipStream_t s);   // a.iters iterati
 hipError_t launch_tv_iter(TvArgs a, int N, hipStream_t s);    // ONE iteration p_in -> p_out, a thread per pixel (p_in must not be p_out)
 hipError_t launch_tv_close(TvArgs a, int N, hipStream_t s);   // out = clamp(v - lam div p_in); out may alias v
 
+// ---- Haar wavelet prior (haar_kernels.hip) ----------------------------------------------------------
+// The fused TI kernel's plan: a kHaarRegion^2 region per workgroup, of which the tile - the region minus the halo 2^J - 1 all round - is stored
+static constexpr int kHaarRegion = 128, kHaarMaxLevels = 4;   // (PNP_HAAR_MAX_LEVELS: asserted equal in pnp_capi.hip)
+inline int haar_tile(int levels) { return kHaarRegion - 2 * ((1 << levels) - 1); }
+struct HaarArgs {
+    const float* v;        // [N,H,W] input plane, or nullptr: Re z - Re u
+    const float2* z;       // [N,H,W] complex planes of pnp_step, or nullptr
+    const float2* u;
+    const float* lam;      // [N]; the slice's threshold is scale * lam[n]
+    float scale;
+    const float* tact;     // [N] stop actions or nullptr; slice skipped when tact[n] > 0.5
+    float* out;            // [N,H,W]; only the ORTHO kernel may be handed out == v
+    int H, W;
+    int levels;            // J: 1..kHaarMaxLevels
+    int level;             // naive kernels: the level j of this launch
+    const float* a_src;    // naive kernels: a_(j-1) [N,H,W], or nullptr: v (j = 1)
+    float* a_dst;          // naive down: a_j
+    const float* r_src;    // naive up: r_j, or nullptr: 0 (j = J)
+    float* r_dst;          // naive up: r_(j-1) (j > 1; level 1 stores out)
+    int tiles_x, tiles_y;  // filled by the launchers
+};
+hipError_t launch_haar_ti_fused(HaarArgs a, int N, hipStream_t s);   // the whole TI operator in one launch; out must not be v
+hipError_t launch_haar_ti_down(HaarArgs a, int N, hipStream_t s);    // ONE level down, a thread per pixel: a_src -> a_dst
+hipError_t launch_haar_ti_up(HaarArgs a, int N, hipStream_t s);      // ONE level up: (a_src, r_src) -> r_dst, or out at level 1 (out must not be v)
+hipError_t launch_haar_ortho(HaarArgs a, int N, hipStream_t s);      // the whole ORTHO operator; out may alias v
+
 }  // namespace pnp

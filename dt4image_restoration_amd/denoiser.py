@@ -110,3 +110,51 @@ class TVDenoiser2D:
         return eng.tv_denoise(x.contiguous().float(), lam, self.iters)
 
     __call__ = forward
+
+
+class HaarDenoiser2D:
+    """The other classical baseline beside the U-Net: Haar wavelet shrinkage, translation-invariant (mode "ti", fully cycle-spun) or
+    decimated ("ortho"), with the same call shape `denoiser(x[N,1,H,W] f32, sigma[N]) -> [N,1,H,W] in [0,1]`: threshold `scale * sigma`,
+    `levels` levels (pnp_haar_denoise).  Like `TVDenoiser2D` its engines are k-space-only handles whose `step` runs the prior, so `PnPEnv`,
+    the drivers and the sharded runners take it wherever they take a `UNetDenoiser2D`, multi-coil problems included."""
+
+    def __init__(self, scale: float = 1.0, levels: int = 3, mode: str = "ti"):
+        scale, levels = float(scale), int(levels)
+        if not (scale >= 0.0 and np.isfinite(scale)):
+            raise ValueError(f"scale must be finite and >= 0, got {scale}")
+        if not 1 <= levels <= 4:
+            raise ValueError(f"levels must be 1..4, got {levels}")
+        if mode not in ("ti", "ortho"):
+            raise ValueError(f"mode must be 'ti' or 'ortho', got {mode!r}")
+        self.scale, self.levels, self.mode = scale, levels, mode
+        self._engines: Dict[Tuple[int, int, int, int, int], PnPEngine] = {}
+        self.bf16_convs = False
+
+    def to(self, *_a, **_k):
+        return self
+
+    def eval(self):
+        return self
+
+    def engine_for(self, n: int, h: int, w: int, device_index: int, replica: int = 0) -> PnPEngine:
+        key = (n, h, w, device_index, replica)
+        eng = self._engines.get(key)
+        if eng is None:
+            eng = PnPEngine(n, h, w, device=device_index, denoiser=False)
+            eng.set_haar_prior(self.scale, self.levels, self.mode)
+            self._engines[key] = eng
+        return eng
+
+    def forward(self, x: torch.Tensor, sigma: torch.Tensor) -> torch.Tensor:
+        if x.dim() != 4 or x.shape[1] != 1:
+            raise ValueError(f"denoiser expects x of shape [N,1,H,W], got {tuple(x.shape)}")
+        n, _, h, w = x.shape
+        if sigma.numel() != n:
+            raise RuntimeError(f"shape '[{n}, 1, 1, 1]' is invalid for input of size {sigma.numel()}")
+        if not x.is_cuda:
+            raise RuntimeError("the HIP denoiser needs a tensor on the GPU; there is no CPU path")
+        eng = self.engine_for(n, h, w, x.device.index)
+        lam = (sigma.reshape(n).to(x.device, torch.float32) * torch.tensor(self.scale, dtype=torch.float32, device=x.device)).contiguous()
+        return eng.haar_denoise(x.contiguous().float(), lam, self.levels, self.mode)
+
+    __call__ = forward

@@ -223,16 +223,47 @@ class PnPEngine:
             raise ValueError(f"prior must be one of {tuple(_lib.PRIORS)}, got {prior!r}")
         _lib.check(self.lib.pnp_set_prior(self._h, _lib.PRIORS[prior], float(tv_scale), int(tv_iters)), "pnp_set_prior")
 
+    def haar_denoise(self, x: torch.Tensor, lam: torch.Tensor, levels: int = 3, mode: str = "ti", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Haar wavelet shrinkage (pnp_haar_denoise): `levels` levels, threshold lam, periodic boundaries, clamped to [0, 1]; mode "ti" is the
+        translation-invariant (fully cycle-spun) form, "ortho" the decimated orthonormal transform.  x float32 [N,1,H,W], lam float32 [N]
+        (0 gives the clamp alone); out may be x.  Any engine kind, any size the engine takes."""
+        nhw = self.n * self.h * self.w
+        self._chk(x, torch.float32, nhw, "x"); self._chk(lam, torch.float32, self.n, "lam")
+        levels = int(levels)
+        if not 1 <= levels <= _lib.PNP_HAAR_MAX_LEVELS:
+            raise ValueError(f"levels must be 1..{_lib.PNP_HAAR_MAX_LEVELS}, got {levels}")
+        if mode not in _lib.HAAR_MODES:
+            raise ValueError(f"mode must be one of {tuple(_lib.HAAR_MODES)}, got {mode!r}")
+        if out is None:
+            out = torch.empty_like(x)
+        self._chk(out, torch.float32, nhw, "out")
+        _lib.check(self.lib.pnp_haar_denoise(self._h, x.data_ptr(), lam.data_ptr(), levels, _lib.HAAR_MODES[mode], out.data_ptr(), self._stream()),
+                   "pnp_haar_denoise")
+        return out
+
+    def set_haar_prior(self, scale: float = 1.0, levels: int = 3, mode: str = "ti") -> None:
+        """Makes Haar shrinkage the x-update of `step` (pnp_set_prior_haar): threshold scale * sigma_d; like "tv" it needs no weights and
+        also runs on an engine built with denoiser=False.  `set_prior("unet" | "tv")` switches away from it."""
+        if mode not in _lib.HAAR_MODES:
+            raise ValueError(f"mode must be one of {tuple(_lib.HAAR_MODES)}, got {mode!r}")
+        _lib.check(self.lib.pnp_set_prior_haar(self._h, float(scale), int(levels), _lib.HAAR_MODES[mode]), "pnp_set_prior_haar")
+
+    def haar_settings(self) -> Tuple[float, int, str]:
+        """(haar_scale, levels, mode) as the handle holds them (pnp_get_prior_haar), whatever the current prior."""
+        sc, lv, md = C.c_double(), C.c_int(), C.c_int()
+        _lib.check(self.lib.pnp_get_prior_haar(self._h, C.byref(sc), C.byref(lv), C.byref(md)), "pnp_get_prior_haar")
+        return float(sc.value), int(lv.value), {v: k for k, v in _lib.HAAR_MODES.items()}[md.value]
+
     @property
     def prior(self) -> str:
-        """"unet" or "tv" (pnp_get_prior)."""
+        """"unet", "tv" or "haar" (pnp_get_prior)."""
         return self.prior_settings()[0]
 
     def prior_settings(self) -> Tuple[str, float, int]:
-        """(prior, tv_scale, tv_iters) as the handle holds them."""
+        """(prior, tv_scale, tv_iters) as the handle holds them; under "haar" the pair is the stored TV pair (`haar_settings` has Haar's)."""
         pr, sc, it = C.c_int(), C.c_double(), C.c_int()
         _lib.check(self.lib.pnp_get_prior(self._h, C.byref(pr), C.byref(sc), C.byref(it)), "pnp_get_prior")
-        return {v: k for k, v in _lib.PRIORS.items()}[pr.value], float(sc.value), int(it.value)
+        return _lib.PRIOR_NAMES[pr.value], float(sc.value), int(it.value)
 
     def fft2c(self, img: torch.Tensor, inverse: bool = False) -> torch.Tensor:
         if img.dtype != torch.complex64 or img.shape[-2:] != (self.h, self.w):

@@ -185,6 +185,65 @@ int pnp_tv_denoise(pnp_handle h, const float* x_in, const float* lam, int iters,
 int pnp_set_prior(pnp_handle h, int prior, double tv_scale, int tv_iters);
 int pnp_get_prior(pnp_handle h, int* prior, double* tv_scale, int* tv_iters);
 
+/* A third plug-in regulariser: Haar wavelet shrinkage, the l1-wavelet term of Sparse MRI and, in its translation-invariant (cycle-spun) form,
+ * the classical denoiser reported beside total variation.  Per slice, with v the input image [H, W] (H, W multiples of 16), lam >= 0 the
+ * threshold, J = levels, periodic boundaries.  One 2-D Haar step on four samples p00 p01 / p10 p11 of the approximation a_(j-1) (a_0 = v):
+ *     a  = ((p00 + p01) + (p10 + p11)) / 2        dh = ((p00 - p01) + (p10 - p11)) / 2
+ *     dv = ((p00 + p01) - (p10 + p11)) / 2        dd = ((p00 - p01) - (p10 - p11)) / 2
+ * and the synthesis is its transpose.
+ *   PNP_HAAR_ORTHO : the decimated orthonormal transform: J levels on aligned 2 x 2 groups, the three detail bands of every level
+ *                    soft-thresholded by lam, the coarsest approximation untouched, the transform inverted.  Unclamped this is exactly
+ *                    prox_{lam ||detail coefficients||_1}(v).
+ *   PNP_HAAR_TI    : the mean over all 4^J circular shifts (sy, sx), 0 <= sy, sx < 2^J, of shift^-1 . ORTHO . shift (full cycle spinning),
+ *                    computed as the undecimated transform: at level j, with h = 2^(j-1), the block at (i, k) has the samples (i, k), (i, k+h),
+ *                    (i+h, k), (i+h, k+h) of a_(j-1), and the synthesis averages the four reconstructions that reach a pixel.
+ * Both are evaluated in the residual form  out = min(max(v - r, 0), 1),  r the synthesis, with zero approximation, of the clipped details
+ * clip(d, -lam, lam) = d - soft(d, lam): the same function in exact arithmetic; lam = 0 gives the clamp bit for bit and a constant image
+ * comes back bit for bit (its details are exactly 0).  float32 throughout, every operation one IEEE operation in this order (no fma; every
+ * scale factor an exact power of two):
+ *     not (lam > 0):  out = min(max(v, 0), 1)                                (lam = 0; a negative or NaN threshold is treated alike)
+ *     a, dh, dv, dd as written above, "/ 2" a product with 0.5;   ch = min(max(dh, -lam), lam), cv, cd likewise
+ *     with s = r_j of the block (r_J = 0):
+ *         q00 = (s + ch) + (cv + cd)    q01 = (s - ch) + (cv - cd)    q10 = (s + ch) - (cv + cd)    q11 = (s - ch) - (cv - cd)
+ *     ORTHO:  r_(j-1)(2i+a, 2k+b) = q_ab * 0.5                                          (block (i, k) of level j, a, b in {0, 1})
+ *     TI:     r_(j-1)(i, k) = ((q00 of block (i, k) + q01 of block (i, k-h)) + (q10 of block (i-h, k) + q11 of block (i-h, k-h))) * 0.125
+ *     out = min(max(v - r_0, 0), 1)
+ * The result at a pixel is a pure function of its slice's v, lam, J and mode: it depends neither on N, the slice's place in the batch, the
+ * stream, the handle kind, nor on how the kernels cut the image into tiles; no atomics, no reductions.  The clamp mirrors pnp_denoise.
+ *   x_in, out : DEVICE float32 [N,1,H,W]; they may alias (exactly, not partly), as in pnp_tv_denoise
+ *   lam       : DEVICE float32 [N];   levels : 1..PNP_HAAR_MAX_LEVELS;   mode : PNP_HAAR_TI or PNP_HAAR_ORTHO
+ * Any handle kind (PNP_FLAG_NO_DENOISER, bf16 convs, single- or multi-coil mode) and any size pnp_create accepts; the call changes neither the
+ * handle's mode nor its installed constants.  PNP_HAAR_TI is ONE launch (a workgroup keeps a 128 x 128 region on chip and stores the tile
+ * inside it, the region minus 2^J - 1 pixels all round); when out aliases x_in the launch writes the data-fidelity stage's scratch plane and a
+ * device-to-device copy on the stream ends the call (a launch reads its neighbours' halos).  Calls on one handle are stream-ordered.
+ * The shipped forms need no workspace.  PNP_HAAR_NAIVE=1 in the environment at pnp_create selects, for PNP_HAAR_TI, one launch per level
+ * down and per level up with the planes in device memory (same bits; a check and a timing baseline, not a mode); its planes, 20 n H W bytes
+ * (a_1 .. a_3 and two residual planes), follow the SETUP-TIME SEMANTICS of pnp_tv_denoise: allocated inside the first TI call on such a
+ * handle, all-or-nothing (on PNP_ERR_NOMEM the handle keeps the workspace it had), counted by pnp_workspace_bytes; later calls allocate
+ * nothing and are asynchronous.
+ * Every argument error (null handle or pointer, levels outside 1..4, an unknown mode) is reported before any HIP call and leaves the outputs
+ * untouched. */
+#define PNP_HAAR_TI         0
+#define PNP_HAAR_ORTHO      1
+#define PNP_HAAR_MAX_LEVELS 4
+int pnp_haar_denoise(pnp_handle h, const float* x_in, const float* lam, int levels, int mode, float* out, void* stream);
+
+/* Makes the Haar operator the x-update of pnp_step (pnp_get_prior then reports PNP_PRIOR_HAAR; pnp_set_prior itself takes PNP_PRIOR_UNET and
+ * PNP_PRIOR_TV only and switches away from it as from any prior):
+ *     x = Haar(float32(Re z - Re u), lam_n = float32(haar_scale) * sigma_d[n], levels, mode)      (the operator of pnp_haar_denoise)
+ * read directly from the two complex planes (no real copy is made first).  The semantics are those of PNP_PRIOR_TV: pnp_step needs no weights
+ * and runs on a PNP_FLAG_NO_DENOISER handle; slices with t_action > 0.5 keep x, z, u, t_state bit for bit; the prior is stateless, so
+ * snapshots, residuals and every driver work unchanged; pnp_set_prior(h, PNP_PRIOR_UNET, ...) afterwards gives steps bit-identical to a handle
+ * that never left the U-Net, pnp_set_prior(h, PNP_PRIOR_TV, ...) switches to total variation as before.  The TV pair of pnp_get_prior is
+ * untouched.  No HIP call is made.
+ *   haar_scale : finite, >= 0;   levels : 1..PNP_HAAR_MAX_LEVELS;   mode : PNP_HAAR_TI or PNP_HAAR_ORTHO
+ * pnp_get_prior_haar returns the stored triple (1.0, 3, PNP_HAAR_TI on a fresh handle) whatever the current prior; all three pointers are
+ * required.  Every argument error (null handle or pointer, levels outside 1..4, an unknown mode, haar_scale negative or not finite) leaves the
+ * handle and the outputs untouched. */
+#define PNP_PRIOR_HAAR      2
+int pnp_set_prior_haar(pnp_handle h, double haar_scale, int levels, int mode);
+int pnp_get_prior_haar(pnp_handle h, double* haar_scale, int* levels, int* mode);
+
 /* Replaces: fft(img) / ifft(img) (evaluation/utils/transformations.py:6-12 / :14-19): centred
  * (ifftshift -> fftn/ifftn norm='ortho' -> fftshift) 2-D transform over the last two dims.
  * in/out DEVICE complex64 [batch,H,W] (may alias); hh, ww are the engine's h, w and batch <= n.
