@@ -73,8 +73,7 @@ ConvPlan conv3x3_plan(int N, int H, int W, int Cin, int Cout, bool bf16, int src
     // 1 x 128 x 128 (profiles/r04_ablation.md).  (bf16 k-steps are sixteen times shorter; that mode keeps the round-3 tiles.)
     // The upsample + concat layers keep the round-3 tile and its 384-workgroup rule (their chain is the two-stage staging, not the
     // MFMAs: no gain measured).
-    static const bool coarse = getenv("PNP_SPLITK_COARSE") != nullptr;       // (A/B: the round-3 tiles)
-    const bool fine = !coarse && !bf16;
+    const bool fine = !bf16;
     if (blocks < 128 && Cout >= 64) {
         const bool f = fine && src_mode != SRC_UPCAT;
         p.mt = f ? 1 : 2; p.nt = 1; p.ck = f ? 16 : 32;
@@ -631,17 +630,11 @@ __global__ __launch_bounds__(256, WPS) void conv3x3_mfma_kernel(const ConvArgs a
         }
     } else {
         // Two full 128-B lines per store instruction; per-slot address part in the scalar offset of a buffer store,
-        // per-lane part in one VGPR per N-block.  Split-K workgroups store raw partial sums to plane blockIdx.z, combined either by
-        // splitk_reduce_kernel or (a.arrive != nullptr) in this launch by the LAST of the tile's gridDim.z workgroups to arrive.
-        // The hand-over uses no fence: a device-scope fence (`__threadfence()` = L2 write-back + invalidate of the workgroup's XCD)
-        // per workgroup cost more than the 21 launches it saved (round 4: 0.90 against 0.546 ms per step at 1 x 128 x 128,
-        // profiles/r04_ablation.md).  Instead every access to the shared data is itself agent-scope (sc1: stores write through the
-        // XCD's L2, loads do not hit in it): partial sums stored sc1 - vmcnt(0) - workgroup barrier - one relaxed agent-scope
-        // fetch_add on the tile's arrival counter - the last arrival loads all planes sc1, in plane order (bit-identical to the kernel).
+        // per-lane part in one VGPR per N-block.  Split-K workgroups store raw partial sums to plane blockIdx.z, combined by
+        // splitk_reduce_kernel.
         const size_t plane = (size_t)a.N * a.H * a.W * a.Cout;
         float* const obuf = SPLITK ? a.partial + (size_t)blockIdx.z * plane : a.dst;
         const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void*)obuf, 0, (int)(plane * sizeof(float)), 0x00020000);
-        const bool inlaunch = SPLITK && a.arrive != nullptr;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int co = (cbt * (WN * NT) + wn * NT + nt) * 32 + li;
@@ -654,68 +647,8 @@ __global__ __launch_bounds__(256, WPS) void conv3x3_mfma_kernel(const ConvArgs a
                     const int gy = ty0 + qc / TW, gx = tx0 + qc % TW + 4 * hh;
                     const int soff = __builtin_amdgcn_readfirstlane(((qc / TW) * a.W + qc % TW) * a.Cout * 4);
                     const float v = SPLITK ? acc[mt][nt][r] : fmaxf(acc[mt][nt][r], kLeaky * acc[mt][nt][r]);
-                    if (gy < a.H && gx < a.W) {
-                        if (inlaunch) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), orsrc, obase, soff, 16);   // sc1
-                        else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), orsrc, obase, soff, 0);
-                    }
+                    if (gy < a.H && gx < a.W) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), orsrc, obase, soff, 0);
                 }
-        }
-        if constexpr (SPLITK) {
-            if (!inlaunch) return;
-            __shared__ unsigned arrived;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's partial sums have been written through
-            __syncthreads();
-            unsigned* const cnt = a.arrive + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-            if (tid == 0) arrived = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();
-            if (arrived + 1 != gridDim.z) return;           // (uniform)
-            if (tid == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-            const __amdgpu_buffer_rsrc_t prsrc =
-                __builtin_amdgcn_make_buffer_rsrc((void*)a.partial, 0, (int)(plane * gridDim.z * sizeof(float)), 0x00020000);
-            constexpr int V4 = BN_ / 4;
-            const int cbase = cbt * BN_;
-            // four tile positions x four planes in flight per thread: sixteen independent 16-byte loads per round trip (one load
-            // at a time, 8 x gridDim.z dependent round trips of ~0.25 us, this combine cost 2 us per plane)
-            const unsigned nz = gridDim.z, pstride = (unsigned)plane * 4u;
-#pragma unroll 1
-            for (int f0 = tid; f0 < BM * V4; f0 += 4 * 256) {
-                unsigned e[4];
-                bool ok[4];
-                float4 sum[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int f = f0 + 256 * j, p = f / V4, c4 = f % V4;
-                    const int gy = ty0 + p / TW, gx = tx0 + p % TW;
-                    ok[j] = f < BM * V4 && gy < a.H && gx < a.W;
-                    e[j] = ok[j] ? (unsigned)(((size_t)n * a.H + gy) * a.W + gx) * (unsigned)a.Cout + (unsigned)(cbase + 4 * c4) : 0u;
-                    sum[j] = *reinterpret_cast<const float4*>(a.bias + cbase + 4 * c4);
-                }
-#pragma unroll 1
-                for (unsigned z0 = 0; z0 < nz; z0 += 4) {
-                    float4 q[4][4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const unsigned z = z0 + k < nz ? z0 + k : nz - 1;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            q[k][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(prsrc, e[j] * 4u, (int)(z * pstride), 16));
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (z0 + k < nz) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) { sum[j].x += q[k][j].x; sum[j].y += q[k][j].y; sum[j].z += q[k][j].z; sum[j].w += q[k][j].w; }
-                        }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (!ok[j]) continue;
-                    float4 v = sum[j];
-                    v.x = fmaxf(v.x, kLeaky * v.x); v.y = fmaxf(v.y, kLeaky * v.y);
-                    v.z = fmaxf(v.z, kLeaky * v.z); v.w = fmaxf(v.w, kLeaky * v.w);
-                    *reinterpret_cast<float4*>(a.dst + e[j]) = v;
-                }
-            }
         }
     }
 }
@@ -799,7 +732,6 @@ hipError_t launch_conv3x3(const ConvArgs& a0, const ConvPlan& p, int src_mode, h
     a.tilesY = p.tiles_y;
     const bool split = p.mt <= 2 && p.wn >= 2;          // the small-problem configs always go through the workspace
     if (split && a.partial == nullptr) return hipErrorInvalidValue;
-    if (!split || (size_t)p.tiles_x * p.tiles_y * a.N * (a.Cout / p.bn) > 4096) a.arrive = nullptr;   // (the counters the engine allocates)
     hipError_t e;
     if (a.bf16 == 2) {                                    // bf16 operands, two-term weights (the mode's default)
         if (p.tw == 32) e = launch_tw<32, 2>(a, p, src_mode, s);
@@ -814,7 +746,7 @@ hipError_t launch_conv3x3(const ConvArgs& a0, const ConvPlan& p, int src_mode, h
         else if (p.tw == 16) e = launch_tw<16, 0>(a, p, src_mode, s);
         else e = launch_tw<8, 0>(a, p, src_mode, s);
     }
-    if (e != hipSuccess || !split || a.arrive != nullptr) return e;
+    if (e != hipSuccess || !split) return e;
     const size_t plane4 = (size_t)a.N * a.H * a.W * a.Cout / 4;
     unsigned blocks = (unsigned)((plane4 + 255) / 256);
     if (blocks > 2048u) blocks = 2048u;
@@ -859,9 +791,9 @@ Tuning tuning_from_env() {
     t.bf16_no_ws = getenv("PNP_BF16_NO_WS") != nullptr;
     t.bf16_w1 = getenv("PNP_BF16_W1") != nullptr;
     t.bf16_no_holdhi = getenv("PNP_BF16_NO_HOLDHI") != nullptr;
-    t.fft_xcd = getenv("PNP_FFT_XCD") != nullptr && atoi(getenv("PNP_FFT_XCD")) != 0;
-    if (const char* v = getenv("PNP_SPLITK_INLAUNCH")) t.splitk_inlaunch = atoi(v);
     if (const char* v = getenv("PNP_SLICE128_MIN_N")) t.slice128_min_n = atoi(v);
+    if (const char* v = getenv("PNP_TV_NAIVE")) t.tv_naive = atoi(v) != 0;
+    if (const char* v = getenv("PNP_HAAR_NAIVE")) t.haar_naive = atoi(v) != 0;
     return t;
 }
 

@@ -58,7 +58,6 @@ struct DenoiserPlan {
     int bf16_terms = 0;                   // bf16 mode: bf16 terms per conv weight (2: hi + lo, the default; 1: PNP_BF16_W1); 0 = f32 mode
     bool pool_ok[N_LEVELS] = {};          // the level's stage output also gets a pooled copy (its producing kernel supports it)
     size_t partial_floats = 0;            // split-K workspace
-    bool want_arrive = false;             // split-K arrival counters (PNP_SPLITK_INLAUNCH)
     size_t plane_bytes[N_LEVELS][N_SLOTS] = {};
     StagePlan stage[N_STAGES] = {};
 };

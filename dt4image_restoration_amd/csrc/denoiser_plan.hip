@@ -97,7 +97,6 @@ bool plan_denoiser(const pnp_config& cfg, const Tuning& tune, DenoiserPlan* out,
         const size_t f = conv3x3_partial_floats(r.conv, cfg.n, lh, lw, L.cout);
         if (f > P.partial_floats) P.partial_floats = f;
     }
-    P.want_arrive = P.partial_floats > 0 && tune.splitk_inlaunch;    // one counter per output tile of a split-K launch
 
     P.fuse_last = !keep_stages && (is_wino(rec[kTail]) || conv3x3_pooled_output_ok(rec[kTail].conv));
     P.fuse_first = rec[kHead].family == FAM_WINO4 && rec[kHead].wino.bn == 32 && rec[kHead].wino.mt == 32 && !tune.no_f4_fused_first;

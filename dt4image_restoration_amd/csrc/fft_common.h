@@ -4,8 +4,8 @@
 
 namespace pnp {
 
-// (explicit fused form: `a.x * b.x - a.y * b.y` has two legal contractions with different roundings, and hipcc picked different ones for the
-// same pass body inlined into two kernels - the per-XCD persistent kernel and the three-launch path must agree bit for bit)
+// (explicit fused form: `a.x * b.x - a.y * b.y` has two legal contractions with different roundings, and hipcc has picked different ones for the
+// same pass body inlined into two kernels - every kernel that runs a pass must round it the same way, so the form is fixed here)
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
 }

@@ -61,7 +61,6 @@ struct DeviceGuard {
     if (dev_guard_.err != hipSuccess) return fail(PNP_ERR_HIP, "hipSetDevice(%d): %s", (e)->cfg.device, hipGetErrorString(dev_guard_.err))
 
 constexpr size_t kNParams = 11773857;
-constexpr size_t kSplitKCounters = 4096;   // split-K arrival counters (PNP_SPLITK_INLAUNCH): one per output tile of a launch, never more than this many tiles
 
 // the profile classes of pnp_profile_collect, in the order of _lib.PROFILE_CLASS_NAMES
 enum ProfClass : int { PROF_CONV3X3 = 0, PROF_CONV_FIRST = 1, PROF_CONV_LAST = 2, PROF_FFT_ROWS = 3, PROF_FFT_COLS = 4, PROF_OTHER = 5 };
@@ -84,15 +83,12 @@ struct pnp_engine {
     float* d_bias[N_LAYERS] = {};
     float* plane[N_LEVELS][N_SLOTS] = {};   // activation planes by (level, slot); sized by the plan, [.][SLOT_NONE] stays null
     float* d_partial = nullptr;      // split-K workspace (small problems)
-    unsigned* d_arrive = nullptr;    // split-K arrival counters (PNP_SPLITK_INLAUNCH), zero between launches
     Tuning tune;                      // environment overrides, read once in pnp_create
     DenoiserPlan dplan;               // fixed at pnp_create (plan_denoiser): the allocations, the weight pack and every launch read it
     ConvArgs largs[N_LAYERS] = {};    // per launch of the plan: the ConvArgs fields that never change (planes, sizes, format bits)
     // data-fidelity stage
     FftPlan plan = {};
     float2* d_work = nullptr;   // [N,H,W] complex scratch
-    unsigned* d_fftq = nullptr; // per-XCD ticket / completion counters of the persistent data-fidelity kernel (nullptr: three launches)
-    unsigned fftq_epoch = 0;    // launches of that kernel since the counters were zeroed (they are never reset: the kernel subtracts epoch x per-launch advance)
     float2* d_y0s = nullptr;    // [N,H,W] sgn * S y0
     uint8_t* d_masks = nullptr; // [mask_n,H,W] S mask
     double* d_ssim_part = nullptr; // [N, ssim_tiles(H, W)] per-tile SSIM sums (pnp_ssim)
@@ -130,13 +126,11 @@ struct pnp_engine {
     int prior = PNP_PRIOR_UNET;
     double tv_scale = 1.0;       // as given; applied as float32
     int tv_iters = 20;
-    bool tv_naive = false;       // PNP_TV_NAIVE=1 at pnp_create: one launch per iteration (the fused kernel's check and timing baseline)
     float2* tv_p = nullptr;      // [N,H,W] (py, px): the hand-over plane between launches; the other plane of the ping-pong is d_work
     // the Haar wavelet prior (pnp_set_prior_haar): prior == PNP_PRIOR_HAAR while it is the x-update
     double haar_scale = 1.0;     // as given; applied as float32
     int haar_levels = 3;
     int haar_mode = PNP_HAAR_TI;
-    bool haar_naive = false;     // PNP_HAAR_NAIVE=1 at pnp_create: TI as one launch per level (the fused kernel's check and timing baseline)
     float* haar_ws = nullptr;    // naive form only, allocated inside its first TI call: kHaarNaivePlanes planes [N,H,W] (a_1 .. a_3, two of r_j)
     // profiling
     std::vector<EventPair> events;
@@ -230,7 +224,7 @@ void resolve_launches(pnp_engine* e) {
         const LayerSpec& L = kLayers[l.layer];
         ConvArgs a{};
         a.src0 = at(l.src0); a.src1 = at(l.src1); a.dst = at(l.dst); a.pooled = at(l.pooled);
-        a.partial = e->d_partial; a.arrive = e->d_arrive;
+        a.partial = e->d_partial;
         a.bf16 = P.bf16_terms;
         a.act16 = l.act16;
         a.N = e->cfg.n; a.H = e->cfg.h >> L.level; a.W = e->cfg.w >> L.level; a.Cin = L.cin; a.Cskip = L.cskip; a.Cout = L.cout;
@@ -541,18 +535,18 @@ int run_tv(pnp_engine* e, const float* v, const float2* z, const float2* u, cons
     Prof p(e, s, PROF_OTHER, -1, true, true);
     int launches = 0;
     const bool alias = v != nullptr && v == out;
-    const int L = e->tv_naive ? iters : (iters + kTvT - 1) / kTvT;
+    const int L = e->tune.tv_naive ? iters : (iters + kTvT - 1) / kTvT;
     for (int l = 0; l < L; ++l) {
         a.p_in = l == 0 ? nullptr : buf[l & 1];
         a.p_out = buf[(l + 1) & 1];
         a.out = nullptr;
         ++launches;
-        if (e->tv_naive) { HIP_TRY(launch_tv_iter(a, N, s)); continue; }
+        if (e->tune.tv_naive) { HIP_TRY(launch_tv_iter(a, N, s)); continue; }
         a.iters = iters - l * kTvT < kTvT ? iters - l * kTvT : kTvT;
         if (l == L - 1 && !alias) { a.p_out = nullptr; a.out = out; }
         HIP_TRY(launch_tv_fused(a, N, s));
     }
-    if (e->tv_naive || alias) {
+    if (e->tune.tv_naive || alias) {
         a.p_in = buf[L & 1]; a.p_out = nullptr; a.out = out;
         ++launches;
         HIP_TRY(launch_tv_close(a, N, s));
@@ -576,7 +570,7 @@ int run_haar(pnp_engine* e, const float* v, const float2* z, const float2* u, co
              int mode, float* out, hipStream_t s) {
     const int N = e->cfg.n;
     const size_t px = (size_t)N * e->cfg.h * e->cfg.w;
-    const bool ti = mode == PNP_HAAR_TI, naive = ti && e->haar_naive;
+    const bool ti = mode == PNP_HAAR_TI, naive = ti && e->tune.haar_naive;
     if (naive)
         if (int rc = haar_ensure(e)) return rc;
     HaarArgs a{};
@@ -620,12 +614,6 @@ int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float
         HIP_TRY(launch_admm_slice128(x, z, u, e->plan.tw_w, e->d_y0s, e->d_masks, e->mask_n, mu, tact, N, s));
         return PNP_OK;
     }
-    if (e->d_fftq != nullptr) {                           // square 256 / 512 slices, >= 8 of them: one persistent launch, scratch stays in L2
-        Prof p(e, s, PROF_FFT_COLS, -1);
-        HIP_TRY(launch_admm_xcd(x, z, u, e->d_work, e->plan.tw_w, e->d_y0s, e->d_masks, e->mask_n, mu, tact, e->d_fftq, e->fftq_epoch, N, H, s));
-        ++e->fftq_epoch;
-        return PNP_OK;
-    }
     {                                                     // three launches; each picks the kernel family for the handle's sides
         Prof p(e, s, PROF_FFT_ROWS, -1);
         HIP_TRY(launch_fft_rows_fwd_admm(x, u, e->d_work, e->plan.tw_w, tact, N, H, W, s));
@@ -663,10 +651,6 @@ static int create_impl(const pnp_config* cfg, pnp_engine* e) {
     if (P.partial_floats > 0) {
         if (hipMalloc((void**)&e->d_partial, P.partial_floats * sizeof(float)) != hipSuccess) return fail(PNP_ERR_NOMEM, "split-K workspace");
         e->ws_bytes += P.partial_floats * sizeof(float);
-        if (P.want_arrive) {
-            if (hipMalloc((void**)&e->d_arrive, kSplitKCounters * sizeof(unsigned)) != hipSuccess ||
-                hipMemset(e->d_arrive, 0, kSplitKCounters * sizeof(unsigned)) != hipSuccess) return fail(PNP_ERR_NOMEM, "split-K counters");
-        }
     }
     resolve_launches(e);
     const size_t cbytes = N * H * W * sizeof(float2);
@@ -681,11 +665,6 @@ static int create_impl(const pnp_config* cfg, pnp_engine* e) {
     const size_t rbytes = N * (size_t)pixel_chunks(cfg->h, cfg->w) * 5 * sizeof(double);
     if (hipMalloc((void**)&e->d_res_part, rbytes) != hipSuccess) return fail(PNP_ERR_NOMEM, "residual partial sums");
     e->ws_bytes += rbytes;
-    if (e->tune.fft_xcd && admm_xcd_usable(cfg->n, cfg->h, cfg->w)) {
-        if (hipMalloc((void**)&e->d_fftq, admm_xcd_counter_bytes()) != hipSuccess || hipMemset(e->d_fftq, 0, admm_xcd_counter_bytes()) != hipSuccess)
-            return fail(PNP_ERR_NOMEM, "data-fidelity work queues");
-        e->ws_bytes += admm_xcd_counter_bytes();
-    }
     e->plan.h = cfg->h; e->plan.w = cfg->w;
     int rc;
     if ((rc = make_twiddles(cfg->h, &e->plan.tw_h)) || (rc = make_twiddles(cfg->w, &e->plan.tw_w))) return rc;
@@ -719,8 +698,6 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     e->cfg = *cfg;
     e->tune = tune;
     e->dplan = plan;
-    if (const char* v = getenv("PNP_TV_NAIVE")) e->tv_naive = atoi(v) != 0;
-    if (const char* v = getenv("PNP_HAAR_NAIVE")) e->haar_naive = atoi(v) != 0;
     int rc;
     {
         DeviceGuard g(cfg->device);
@@ -741,7 +718,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipDeviceSynchronize();
     for (int i = 0; i < N_LAYERS; ++i) { (void)hipFree(e->d_wpack[i]); (void)hipFree(e->d_bias[i]); }
     for (auto& level : e->plane) for (float* b : level) (void)hipFree(b);
-    (void)hipFree(e->d_work); (void)hipFree(e->d_fftq); (void)hipFree(e->d_y0s); (void)hipFree(e->d_masks); (void)hipFree(e->d_ssim_part); (void)hipFree(e->d_res_part); (void)hipFree(e->d_partial); (void)hipFree(e->d_arrive);
+    (void)hipFree(e->d_work); (void)hipFree(e->d_y0s); (void)hipFree(e->d_masks); (void)hipFree(e->d_ssim_part); (void)hipFree(e->d_res_part); (void)hipFree(e->d_partial);
     (void)hipFree(e->mc_y); (void)hipFree(e->mc_work); (void)hipFree(e->mc_sens); (void)hipFree(e->mc_vec); (void)hipFree(e->mc_part); (void)hipFree(e->mc_sc);
     (void)hipFree(e->cm_max); (void)hipFree(e->cm_rss);
     (void)hipFree(e->cc_part); (void)hipFree(e->cc_gram);
@@ -837,11 +814,6 @@ int pnp_reset(pnp_handle e, const float* x0, const float* y0, const uint8_t* mas
     PNP_ON_DEVICE(e);
     e->mask_n = mask_n;
     e->mc_coils = 0;                                       // back to the single-coil stage
-    // the two experimental in-launch hand-over schemes keep counters between launches (PNP_SPLITK_INLAUNCH: arrival counters that return to zero;
-    // PNP_FFT_XCD: ticket / completion counters read against a launch epoch): a launch that faulted half way would leave them out of step for good,
-    // so an episode starts from zero
-    if (e->d_arrive) HIP_TRY(hipMemsetAsync(e->d_arrive, 0, kSplitKCounters * sizeof(unsigned), (hipStream_t)stream));
-    if (e->d_fftq) { HIP_TRY(hipMemsetAsync(e->d_fftq, 0, admm_xcd_counter_bytes(), (hipStream_t)stream)); e->fftq_epoch = 0; }
     HIP_TRY(launch_reset((const float2*)x0, (const float2*)y0, mask, mask_n, x, (float2*)z, (float2*)u, e->d_y0s,
                          e->d_masks, e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
     e->reset_done = true;
@@ -1176,7 +1148,6 @@ int pnp_reset_mc(pnp_handle e, const float* x0, const float* y0, const float* se
     if (!e) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null handle");
     if (int rc = mc_check("pnp_reset_mc", e, coils, sens_n, mask_n)) return rc;
     PNP_ON_DEVICE(e);
-    if (e->d_arrive) HIP_TRY(hipMemsetAsync(e->d_arrive, 0, kSplitKCounters * sizeof(unsigned), (hipStream_t)stream));   // as pnp_reset: an episode starts from zero
     return mc_install(e, (const float2*)x0, (const float2*)y0, (const float2*)sens, coils, sens_n, mask, mask_n, cg_iters, x, (float2*)z,
                       (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_mc")

@@ -277,7 +277,6 @@ SWEEP = [(1, 16, 48), (5, 32, 16), (2, 80, 48), (3, 96, 112), (1, 144, 64), (4, 
 # row: (budget family, arithmetic of the oracle, engine in bf16 mode, environment, probes, shapes)
 MATRIX = {
     "direct": ("f32", "f32", False, {"PNP_NO_WINOGRAD": "1"}, ("sum", "route"), SWEEP + [(2, 256, 256), (1, 16, 1024), (1, 1024, 16)]),
-    "direct-inlaunch": ("f32", "f32", False, {"PNP_NO_WINOGRAD": "1", "PNP_SPLITK_INLAUNCH": "1"}, ("sum",), [(1, 128, 128), (3, 96, 80)]),
     "wino2": ("wino2", "f32", False, {"PNP_WINO_MIN_BLOCKS": "1", "PNP_NO_WINO_F4": "1"}, ("sum", "route"),
               [(1, 32, 32), (2, 48, 64), (3, 64, 16), (64, 128, 128)]),
     "bf16": ("bf16", "bf16", True, {}, ("sum", "lo"),

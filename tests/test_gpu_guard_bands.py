@@ -56,12 +56,8 @@ single-coil pnp_prox_dual / pnp_step, which write z and u.
     (2,256,512)   rows <0,0> 4 rows/wg, stage rows <1,512,true> / <2,512,true> (radix-8 form, 4 rows/wg); cols <0,0>, cols_prox <1,256> 16 cols/wg
     (2,512,256)   rows <0,0> 8 rows/wg, stage rows <1,256,true> / <2,256,true> (radix-16 form, 16 rows/wg); cols <0,0>, cols_prox <1,512> 8 cols/wg
     (3,128,128) with PNP_SLICE128_MIN_N=1   launch_admm_slice128 (one workgroup per slice, writes z and u)
-    (9,256,256) with PNP_FFT_XCD=1          launch_admm_xcd, admm_xcd_kernel<256> (persistent, per-XCD queues, writes z and u)
-    (9,512,512) with PNP_FFT_XCD=1          launch_admm_xcd, admm_xcd_kernel<512>
     (rows_per_block = min(H, 2048 / W) takes the values 2, 4, 8, 16, 32, 64, 128: W = 1024, 512, 256, 128 / 16 with H = 16, 64, 32, 16 with
-    H >= 128; cols_per_block 16, 8, 4: H <= 256, 512, 1024.  The one-launch cases assert (0, 1, 0) booked launches, i.e. that the form ran.)
-    the stage rows <1|2,256> and <1|2,512> without the radix-16 / radix-8 form run only under PNP_FFT_ROWS_R4, which the library reads once
-    per process: test_stage_rows_r4_in_a_fresh_process runs (2,512,256) and (2,256,512) under it in a child process
+    H >= 128; cols_per_block 16, 8, 4: H <= 256, 512, 1024.  The one-launch case asserts (0, 1, 0) booked launches, i.e. that the form ran.)
   a side that is not a power of two (fft_mixed_kernels.hip, namespace mixed): fft_rows_mixed_kernel<0|1|2>, fft_rows_real_m5_kernel,
   fft_cols_mixed_kernel<0|1>; rows/wg = mixed_rows_per_block(W), cols/wg = mixed_cols_per_block(H)
     (2,80,160)    8 rows/wg, 16 cols/wg            (2,160,80)   16 rows/wg, 16 cols/wg
@@ -79,7 +75,6 @@ single-coil pnp_prox_dual / pnp_step, which write z and u.
     coilcomp_apply_kernel<8> for V <= 8, <16> for V <= 16, <32> above)"""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import pytest
@@ -281,17 +276,14 @@ def _install(pair, g, n, h, w, per_slice=False):
 
 PROX_CASES = [("kspace", s, {}) for s in KS_N + FFT] + [("f32", KS[0], {}), ("bf16", KS[0], {}),
                                                         ("kspace", (3, 128, 128), {"PNP_SLICE128_MIN_N": "1"}),
-                                                        ("f32", (3, 128, 128), {"PNP_SLICE128_MIN_N": "1"}),
-                                                        ("kspace", (9, 256, 256), {"PNP_FFT_XCD": "1"}),
-                                                        ("kspace", (9, 512, 512), {"PNP_FFT_XCD": "1"})]
+                                                        ("f32", (3, 128, 128), {"PNP_SLICE128_MIN_N": "1"})]
 
 
 @pytest.mark.parametrize("kind,shape,env", PROX_CASES, ids=[f"{k}-{'x'.join(map(str, s))}{'-' + '-'.join(e) if e else ''}" for k, s, e in PROX_CASES])
 def test_prox_dual(kind, shape, env, monkeypatch):
-    """The data-fidelity stage writes z and u from its row kernels (or the one-launch forms): every stage variant of table 2.  Both handles
-    profile, and every call is asserted to be the form the case is about: the one-launch forms (launch_admm_slice128, launch_admm_xcd) book
-    (fft_rows, fft_cols_prox, other) = (0, 1, 0) launches, the three-launch path (2, 1, 0) - launch_admm_xcd falls back to three launches
-    silently where its device probe fails, and the case would then cover nothing new."""
+    """The data-fidelity stage writes z and u from its row kernels (or the one-launch form): every stage variant of table 2.  Both handles
+    profile, and every call is asserted to be the form the case is about: the one-launch form (launch_admm_slice128) books
+    (fft_rows, fft_cols_prox, other) = (0, 1, 0) launches, the three-launch path (2, 1, 0)."""
     n, h, w = shape
     g = _gen(2, n, h, w)
     for k, v in env.items():
@@ -448,19 +440,6 @@ def test_positive_control(shape):
         end = g_info.start + g_info.nbytes
         assert torch.equal(g_info.raw[end:end + h * w * 8], gb.as_bytes(want[1]))
         assert torch.equal(gb.as_bytes(gout[0]), gb.as_bytes(want[0]))
-
-
-def test_stage_rows_r4_in_a_fresh_process():
-    """PNP_FFT_ROWS_R4 (the stage's <1|2,256> and <1|2,512> row kernels without the radix-16 / radix-8 form) is read once per process, so
-    this one variant runs test_prox_dual's two shapes in a child process that has it set.  The launch counts cannot tell the two row
-    forms apart (both book (2, 1, 0)), and the library has no other signal; the child inherits the variable before the library is loaded.
-    test_prox_dual asserts there that neither one-launch form took the stage over."""
-    env = dict(os.environ, PNP_FFT_ROWS_R4="1")
-    ids = ["kspace-2x256x512", "kspace-2x512x256"]
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider", os.path.abspath(__file__), "-k",
-                        "test_prox_dual and (" + " or ".join(ids) + ")"], env=env, capture_output=True, text=True, timeout=300,
-                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    assert r.returncode == 0 and "2 passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 # ---- metrics -----------------------------------------------------------------------------------------------------------------------------

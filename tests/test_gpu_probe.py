@@ -35,7 +35,7 @@ def _cases():
 CASES = _cases()
 CASE_IDS = [f"{row}-{probe}-s{seed}-{n}x{h}x{w}" for (_, probe, seed, (n, h, w), row) in CASES]
 # one case per family also runs denoise twice and requires the same bits
-REPEAT = {("direct", "sum", 0, (3, 96, 112)), ("direct-inlaunch", "sum", 0, (3, 96, 80)), ("wino2", "sum", 0, (2, 48, 64)),
+REPEAT = {("direct", "sum", 0, (3, 96, 112)), ("wino2", "sum", 0, (2, 48, 64)),
           ("bf16", "lo", 0, (16, 256, 256)), ("bf16-no-ws", "lo", 0, (3, 48, 80)), ("bf16-w1", "lo", 0, (2, 128, 128)),
           ("f4", "route", 0, (2, 256, 256))}
 

@@ -96,6 +96,54 @@ def test_product_path_never_touches_the_oracle():
     assert bench.count("from oracle") == 1 and "def cpu_baseline" in bench      # one import, inside the baseline leg
 
 
+def test_one_place_reads_the_environment():
+    """Every getenv of the library sits in tuning_from_env, read once per handle at pnp_create - a plan, a launch or an entry point never reads
+    the process environment on its own - except the timing switches of the diagnostic build (`#ifdef PNP_DIAG` regions of pnp_capi.hip).  The four
+    retired experiment switches are named nowhere in the package."""
+    csrc = os.path.join(ROOT, "dt4image_restoration_amd", "csrc")
+    reads = 0
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith((".hip", ".h", ".cpp", ".c")):
+            continue
+        text = open(os.path.join(csrc, fn)).read()
+        allowed = []                                     # [start, end) character ranges that may read the environment
+        m = re.search(r"^Tuning tuning_from_env\(\) \{$.*?^\}$", text, re.S | re.M)
+        if m:
+            allowed.append(m.span())
+        if fn == "pnp_capi.hip":                         # #ifdef PNP_DIAG ... its #endif (conditionals inside it nest)
+            depth, start = 0, None
+            for d in re.finditer(r"^[ \t]*#[ \t]*(ifdef|ifndef|if|endif)\b(.*)$", text, re.M):
+                if d.group(1) != "endif":
+                    if start is None and d.group(1) == "ifdef" and d.group(2).strip() == "PNP_DIAG":
+                        start, depth = d.end(), 0
+                    elif start is not None:
+                        depth += 1
+                elif start is not None:
+                    if depth == 0:
+                        allowed.append((start, d.start()))
+                        start = None
+                    else:
+                        depth -= 1
+            assert start is None, "unterminated #ifdef PNP_DIAG"
+        for g in re.finditer(r"getenv\s*\(", text):
+            reads += 1
+            line = text.count("\n", 0, g.start()) + 1
+            assert any(a <= g.start() < b for a, b in allowed), f"{fn}:{line}: getenv outside tuning_from_env"
+    assert reads >= 20                                   # the scan found tuning_from_env's own reads
+    retired = ("PNP_FFT_XCD", "PNP_SPLITK_INLAUNCH", "PNP_SPLITK_COARSE", "PNP_FFT_ROWS_R4")
+    seen = 0
+    for dirpath, _dirs, files in os.walk(os.path.join(ROOT, "dt4image_restoration_amd")):
+        if "__pycache__" in dirpath or os.path.basename(dirpath) in ("_asan", "_stamps", "_diag", "_isa"):
+            continue
+        for fn in files:
+            if fn.endswith((".py", ".hip", ".h", ".cpp", ".c")) or fn in ("Makefile", "libpnpadmm.so"):   # the sources and what they built
+                seen += 1
+                blob = open(os.path.join(dirpath, fn), "rb").read()
+                for name in retired:
+                    assert name.encode() not in blob, f"{os.path.join(dirpath, fn)} names {name}"
+    assert seen >= 18
+
+
 def test_product_path_fails_loudly_without_a_gpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
