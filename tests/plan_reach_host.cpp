@@ -1,0 +1,311 @@
+// Host-only: the VARIANT KEY of every launch a denoiser handle plans (run by tests/test_variant_reach_host.py against the built library,
+// linked like tests/plan_coutsplit_host.cpp).  For a handle description it calls plan_denoiser and names, per launch record, the code
+// the launch runs: kernel family, the template arguments its dispatcher resolves to, and the runtime switches that pick a code path.
+//
+// The keys restate the dispatchers - launch_conv3x3 / launch_tw / launch_cfg / launch_inst (conv_kernels.hip), launch_conv3x3_bf16ws /
+// launch_src / launch_one (conv_bf16_kernels.hip), launch_conv3x3_winograd (winograd_kernels.hip), launch_conv3x3_winograd4
+// (winograd4_kernels.hip) - and must change with them.  A plan record no dispatcher branch accepts gets the key "INVALID ...".
+//
+//   template level   family<template arguments> src=<source mode of the launch> + the switches: ksplit (more than one K range), pool (the
+//                    pooled copy is written), first / last (fused first / last layer), a16=<act16 bits>, and for F(4x4) which of its four
+//                    kernels (in-step with stack, mt, wn; phased with stack; cout-split) - all of it what selects code
+//   edge level       the template key + rx (level width % tw != 0), ry (level height % th != 0), odd (a stacked F(4x4) launch with odd N)
+//
+// Modes:
+//   plan_reach_host                handle descriptions on stdin, one per line: `n h w flags [PNP_NAME=value ...]` (the environment switches
+//                                  of tuning_from_env; every other PNP_* variable is cleared first).  Prints, per handle k (0-based),
+//                                    plan k families=<28 codes> schedules=<28 codes>       (pnp_conv_algorithms / pnp_conv_schedules)
+//                                    launch k layer=<li> | <template key> | <edge key>     (one per launch record)
+//                                  or `refused k <message>`.
+//   plan_reach_host --reach        enumerates default tuning (no PNP_* variable) over
+//                                    H, W   every multiple of 16 in 16 ... 1024
+//                                    N      1 ... 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256
+//                                    N H W  <= 64 * 256 * 256: the largest workload the suite and the benchmark run - a stated bound, not a measurement
+//                                    flags  0, BF16_CONVS, KEEP_STAGES, both
+//                                  and prints, per key of either level, the reaching handle of smallest N H W and, where one exists, the
+//                                  smallest whose sides both pass kspace_len_ok:
+//                                    reach T|E | <key> | n h w flags | n h w flags   (or `-`)
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <map>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../dt4image_restoration_amd/csrc/denoiser_plan.h"
+
+extern char** environ;
+using namespace pnp;
+
+static const char* src_name(int s) {
+    switch (s) {
+    case SRC_PLAIN: return "PLAIN";
+    case SRC_SIGMA: return "SIGMA";
+    case SRC_POOL: return "POOL";
+    case SRC_UPCAT: return "UPCAT";
+    case SRC_FIRST: return "FIRST";
+    }
+    return "?";
+}
+
+static std::string fmt(const char* f, ...) __attribute__((format(printf, 1, 2)));
+static std::string fmt(const char* f, ...) {
+    char buf[256];
+    va_list ap;
+    va_start(ap, f);
+    vsnprintf(buf, sizeof buf, f, ap);
+    va_end(ap);
+    return buf;
+}
+
+struct Key { std::string tmpl; int tw = 0, th = 0; bool stack = false; };
+
+// launch_conv3x3 -> launch_tw -> launch_cfg -> launch_inst
+static Key direct_key(const ConvLaunch& l, int terms) {
+    const ConvPlan& p = l.conv;
+    Key k;
+    k.tw = p.tw; k.th = p.th;
+    int mt, nt, wm, wn, ck, bf = terms;
+    bool sk;
+    auto cfg = [&](int a, int b, int c, int d, int e, bool s, int f) { mt = a; nt = b; wm = c; wn = d; ck = e; sk = s; bf = f; };
+    if (terms == 0 && p.mt == 1 && p.wn == 4) cfg(1, 1, 1, 4, 16, true, 0);
+    else if (terms == 0 && p.mt == 1 && p.wn == 2) cfg(1, 1, 2, 2, 16, true, 0);
+    else if (p.mt == 2 && p.wn == 4) cfg(2, 1, 1, 4, 32, true, terms);
+    else if (p.mt == 2 && p.wn == 2) cfg(2, 1, 2, 2, 32, true, terms);
+    else if (terms == 0 && p.nt == 1 && p.mt == 1) cfg(1, 1, 4, 1, 32, false, 0);
+    else if (p.nt == 1) cfg(2, 1, 4, 1, 32, false, terms);
+    else if (p.nt == 2 && p.wn == 1) cfg(4, 2, 4, 1, 16, false, terms);
+    else if (p.nt == 2) cfg(4, 2, 2, 2, 32, false, terms);
+    else if (terms == 0) cfg(4, 4, 2, 2, 32, false, 0);
+    else { k.tmpl = "INVALID direct: the bf16 dispatcher has no 256-accumulator tile"; return k; }
+    // the tile the dispatcher instantiates must be the tile the plan computed its grid for
+    if (mt != p.mt || nt != p.nt || wm != p.wm || wn != p.wn || ck != p.ck || (p.tw != 8 && p.tw != 16 && p.tw != 32) ||
+        sk != (p.mt <= 2 && p.wn >= 2) || (!sk && p.splitk != 1)) {
+        k.tmpl = fmt("INVALID direct: plan <tw %d mt %d nt %d wm %d wn %d ck %d splitk %d> dispatched as <%d,%d,%d,%d,%d>", p.tw, p.mt, p.nt, p.wm,
+                     p.wn, p.ck, p.splitk, mt, nt, wm, wn, ck);
+        return k;
+    }
+    if (l.src_mode != SRC_PLAIN && l.src_mode != SRC_POOL && l.src_mode != SRC_UPCAT) { k.tmpl = fmt("INVALID direct: src %d", l.src_mode); return k; }
+    const bool can16 = bf != 0 && !sk && mt == 2 && nt == 1 && wm == 4 && ck == 32 && l.src_mode != SRC_POOL;
+    const bool a16 = can16 && (l.act16 & 1);
+    if (l.act16 != 0 && !a16) { k.tmpl = fmt("INVALID direct: act16 %d on a tile without bf16 activations", l.act16); return k; }
+    k.tmpl = fmt("direct<TW=%d,MT=%d,NT=%d,WM=%d,WN=%d,CK=%d,SPLITK=%d,BF16=%d,A16=%d> src=%s", p.tw, mt, nt, wm, wn, ck, sk ? 1 : 0, bf, a16 ? 1 : 0,
+                 src_name(l.src_mode));
+    if (p.splitk > 1) k.tmpl += " ksplit";
+    return k;
+}
+
+// launch_conv3x3_bf16ws -> launch_src -> launch_one -> launch_k
+static Key ws_key(const ConvLaunch& l, int terms) {
+    const ConvPlan& p = l.conv;
+    const LayerSpec& L = kLayers[l.layer];
+    Key k;
+    k.tw = p.tw; k.th = p.th;
+    int wm = 0, wn = 0, mt = 0, nt = 0;
+    if (p.ck != 32 || terms == 0) { k.tmpl = "INVALID ws: ck / terms"; return k; }
+    if (p.nt == 1) { if (p.tw == 32 && p.mt == 2 && p.wm == 4) { wm = 4; wn = 1; mt = 2; nt = 1; } }
+    else if (p.wn == 2) { if (p.tw == 32 || p.tw == 16) { wm = 2; wn = 2; mt = 4; nt = 2; } }
+    else if (p.tw == 32 || p.tw == 16) { wm = 4; wn = 1; mt = 4; nt = 2; }
+    if (wm == 0 || mt != p.mt || nt != p.nt || wm != p.wm || wn != p.wn) {
+        k.tmpl = fmt("INVALID ws: plan <tw %d mt %d nt %d wm %d wn %d>", p.tw, p.mt, p.nt, p.wm, p.wn);
+        return k;
+    }
+    const bool src_ok = l.src_mode == SRC_PLAIN || (l.src_mode == SRC_POOL && wn == 2) ||
+                        (l.src_mode == SRC_UPCAT && L.cskip % 32 == 0 && L.cskip >= 32 && L.cin - L.cskip >= 32);
+    if (!src_ok) { k.tmpl = fmt("INVALID ws: src %d on wn %d", l.src_mode, wn); return k; }
+    if ((l.pooled.slot != SLOT_NONE || l.fused_last) && p.nt != 1) { k.tmpl = "INVALID ws: pooled copy / fused last on a two-block tile"; return k; }
+    const bool hold = nt == 1 && l.src_mode == SRC_PLAIN && terms == 2 && L.cin == 32 && L.cout == 32 && p.holdhi;
+    k.tmpl = fmt("ws<TW=%d,WM=%d,WN=%d,MT=%d,NT=%d,A16S=%d,NW=%d,HOLDHI=%d> src=%s", p.tw, wm, wn, mt, nt, l.act16 & 1, terms, hold ? 1 : 0,
+                 src_name(l.src_mode));
+    return k;
+}
+
+// launch_conv3x3_winograd -> launch_wino_tw -> launch_wino_cfg
+static Key wino2_key(const ConvLaunch& l) {
+    const WinoPlan& p = l.wino;
+    Key k;
+    k.tw = p.tw; k.th = p.th;
+    int wm, wn, ck;
+    if (p.wm == 1 && p.wn == 4) { wm = 1; wn = 4; ck = 32; }
+    else if (p.wm == 1 && p.wn == 2) { wm = 1; wn = 2; ck = 16; }
+    else if (p.wm == 2 && p.wn == 2) { wm = 2; wn = 2; ck = 16; }
+    else if (p.wm == 2 && p.wn == 1) { wm = 2; wn = 1; ck = 8; }
+    else { wm = 4; wn = 1; ck = 8; }
+    const int tw = p.tw == 32 ? 32 : (p.tw == 16 ? 16 : 8);
+    if (!p.use || wm != p.wm || wn != p.wn || ck != p.ck || tw != p.tw || p.th != wm * 2 * (32 / (tw / 2)) ||
+        (l.src_mode != SRC_PLAIN && l.src_mode != SRC_POOL && l.src_mode != SRC_UPCAT)) {
+        k.tmpl = fmt("INVALID wino2: plan <tw %d th %d wm %d wn %d ck %d> src %d", p.tw, p.th, p.wm, p.wn, p.ck, l.src_mode);
+        return k;
+    }
+    k.tmpl = fmt("wino2<TW=%d,WM=%d,WN=%d,CK=%d> src=%s", tw, wm, wn, ck, src_name(l.src_mode));
+    return k;
+}
+
+// launch_conv3x3_winograd4
+static Key wino4_key(const ConvLaunch& l, int lh, int lw) {
+    const WinoPlan& p = l.wino;
+    const LayerSpec& L = kLayers[l.layer];
+    const int s = l.src_mode;
+    Key k;
+    k.tw = p.tw; k.th = p.th; k.stack = p.stack != 0;
+    auto bad = [&](const char* why) {
+        k.tmpl = fmt("INVALID wino4 (%s): plan <tw %d th %d bn %d ck %d mt %d stack %d phased %d cs %d> src %d", why, p.tw, p.th, p.bn, p.ck, p.mt, p.stack,
+                     p.phased, p.cs, s);
+        return k;
+    };
+    if (!p.use || p.algo != 4 || L.cout % p.bn || L.cin % p.ck || (s == SRC_UPCAT && L.cskip % p.ck) || lw % 4) return bad("entry");
+    if (l.fused_last && !(p.bn == 32 && p.mt == 32 && s == SRC_PLAIN)) return bad("fused last");
+    if (p.tw != 16 && p.tw != 32) return bad("tw");
+    const bool plain_up = s == SRC_PLAIN || s == SRC_UPCAT;
+    if (p.bn == 32) {
+        if (p.ck != 8 || p.stack || !(plain_up || s == SRC_FIRST) || p.th != 4 * (32 / (p.tw / 4))) return bad("32-channel variant");
+        k.tmpl = fmt("wino4<TW=%d,STK=0,WN=1,MT=32> src=%s", p.tw, src_name(s));
+        return k;
+    }
+    if (p.ck != 16) return bad("ck");
+    if (p.cs) {
+        if (p.bn != 128 || p.mt != 16 || p.stack || !plain_up || p.th != 4 * (16 / (p.tw / 4)) || (s == SRC_UPCAT && L.cskip < 48)) return bad("cout-split");
+        k.tmpl = fmt("wino4c<TW=%d> src=%s", p.tw, src_name(s));
+        return k;
+    }
+    if (p.mt == 16) {
+        if (p.stack || !plain_up || p.th != 4 * (16 / (p.tw / 4))) return bad("16-tile");
+        k.tmpl = fmt("wino4<TW=%d,STK=0,WN=2,MT=16> src=%s", p.tw, src_name(s));
+        return k;
+    }
+    if (p.stack && !(p.tw == 16 && s == SRC_PLAIN && lh == 16 && lw == 16)) return bad("stack");
+    if (p.phased && s == SRC_PLAIN) {
+        k.tmpl = fmt("wino4p<TW=%d,STK=%d> src=PLAIN", p.tw, p.stack ? 1 : 0);
+        return k;
+    }
+    if (!plain_up || p.th != 4 * (32 / (p.tw / 4))) return bad("in-step");
+    k.tmpl = fmt("wino4<TW=%d,STK=%d,WN=2,MT=32> src=%s", p.tw, p.stack ? 1 : 0, src_name(s));
+    return k;
+}
+
+static void launch_keys(const pnp_config& cfg, const DenoiserPlan& P, const ConvLaunch& l, std::string* tmpl, std::string* edge) {
+    const LayerSpec& L = kLayers[l.layer];
+    const int lh = cfg.h >> L.level, lw = cfg.w >> L.level;
+    Key k;
+    switch (l.family) {
+    case FAM_FIRST: k.tmpl = fmt("first<dst16=%d>", (l.act16 & 2) ? 1 : 0); k.tw = 32; k.th = 8; break;     // conv_first_kernel: 8 x 32 tiles
+    case FAM_LAST: k.tmpl = "last"; k.tw = 1; k.th = 1; break;                                               // conv_last_kernel: a flat pixel loop
+    case FAM_DIRECT: k = direct_key(l, P.bf16_terms); break;
+    case FAM_WS: k = ws_key(l, P.bf16_terms); break;
+    case FAM_WINO2: k = wino2_key(l); break;
+    case FAM_WINO4: k = wino4_key(l, lh, lw); break;
+    default: k.tmpl = fmt("INVALID family %d", l.family);
+    }
+    if (l.family != FAM_FIRST && l.family != FAM_LAST && k.tmpl.compare(0, 7, "INVALID") != 0) {
+        if (l.pooled.slot != SLOT_NONE) k.tmpl += " pool";
+        if (l.fused_first) k.tmpl += " first";
+        if (l.fused_last) k.tmpl += " last";
+        k.tmpl += fmt(" a16=%d", l.act16);
+    }
+    *tmpl = k.tmpl;
+    *edge = k.tmpl;
+    if (k.tw > 0 && lw % k.tw != 0) *edge += " rx";
+    if (k.th > 0 && lh % k.th != 0) *edge += " ry";
+    if (k.stack && cfg.n % 2 != 0) *edge += " odd";
+}
+
+static void clear_pnp_env() {
+    std::vector<std::string> names;
+    for (char** e = environ; *e; ++e)
+        if (strncmp(*e, "PNP_", 4) == 0) names.emplace_back(*e, strcspn(*e, "="));
+    for (const auto& n : names) unsetenv(n.c_str());
+}
+
+static int schedule_of(const DenoiserPlan& P, int li) {            // pnp_conv_schedules
+    const int at = P.launch_of[li];
+    if (at < 0 || P.family[li] != FAM_WINO4) return 0;
+    const WinoPlan& w = P.launch[at].wino;
+    return w.cs ? 4 : (w.mt == 16 ? 3 : (w.phased ? 2 : 1));
+}
+
+static int describe_stdin() {
+    std::string line;
+    int idx = 0;
+    while (std::getline(std::cin, line)) {
+        if (line.empty() || line[0] == '#') continue;
+        std::istringstream in(line);
+        pnp_config cfg{};
+        if (!(in >> cfg.n >> cfg.h >> cfg.w >> cfg.flags)) { std::fprintf(stderr, "plan_reach_host: cannot read `%s`\n", line.c_str()); return 2; }
+        clear_pnp_env();
+        std::string kv;
+        while (in >> kv) {
+            const size_t eq = kv.find('=');
+            if (eq == std::string::npos || kv.compare(0, 4, "PNP_") != 0) { std::fprintf(stderr, "plan_reach_host: override `%s` is not PNP_NAME=value\n", kv.c_str()); return 2; }
+            setenv(kv.substr(0, eq).c_str(), kv.substr(eq + 1).c_str(), 1);
+        }
+        const Tuning t = tuning_from_env();
+        DenoiserPlan P;
+        std::string err;
+        if (!plan_denoiser(cfg, t, &P, &err)) { std::printf("refused %d %s\n", idx++, err.c_str()); continue; }
+        std::printf("plan %d families=", idx);
+        for (int li = 0; li < N_LAYERS; ++li) std::printf("%s%d", li ? "," : "", P.family[li]);
+        std::printf(" schedules=");
+        for (int li = 0; li < N_LAYERS; ++li) std::printf("%s%d", li ? "," : "", schedule_of(P, li));
+        std::printf("\n");
+        for (int i = 0; i < P.n_launches; ++i) {
+            std::string a, b;
+            launch_keys(cfg, P, P.launch[i], &a, &b);
+            std::printf("launch %d layer=%d | %s | %s\n", idx, P.launch[i].layer, a.c_str(), b.c_str());
+        }
+        ++idx;
+    }
+    return 0;
+}
+
+struct Reach { long px = 0, kpx = 0; int at[4] = {}, kat[4] = {}; };
+
+static int reach() {
+    clear_pnp_env();
+    const Tuning t = tuning_from_env();
+    const int ns[] = {1, 2, 3, 4, 5, 6, 7, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256};
+    const int flagsets[] = {0, PNP_FLAG_BF16_CONVS, PNP_FLAG_KEEP_STAGES, PNP_FLAG_BF16_CONVS | PNP_FLAG_KEEP_STAGES};
+    const long cap = 64L * 256 * 256;
+    std::map<std::string, Reach> seen[2];
+    long handles = 0;
+    for (int h = 16; h <= 1024; h += 16)
+        for (int w = 16; w <= 1024; w += 16)
+            for (int n : ns) {
+                const long px = (long)n * h * w;
+                if (px > cap) continue;
+                const bool ks = kspace_len_ok(h) && kspace_len_ok(w);
+                for (int flags : flagsets) {
+                    pnp_config cfg{n, h, w, flags, 0};
+                    DenoiserPlan P;
+                    std::string err;
+                    if (!plan_denoiser(cfg, t, &P, &err)) continue;
+                    ++handles;
+                    for (int i = 0; i < P.n_launches; ++i) {
+                        std::string key[2];
+                        launch_keys(cfg, P, P.launch[i], &key[0], &key[1]);
+                        for (int lv = 0; lv < 2; ++lv) {
+                            Reach& r = seen[lv][key[lv]];
+                            if (r.px == 0 || px < r.px) { r.px = px; r.at[0] = n; r.at[1] = h; r.at[2] = w; r.at[3] = flags; }
+                            if (ks && (r.kpx == 0 || px < r.kpx)) { r.kpx = px; r.kat[0] = n; r.kat[1] = h; r.kat[2] = w; r.kat[3] = flags; }
+                        }
+                    }
+                }
+            }
+    for (int lv = 0; lv < 2; ++lv)
+        for (const auto& kv : seen[lv]) {
+            const Reach& r = kv.second;
+            std::printf("reach %c | %s | %d %d %d %d | ", lv ? 'E' : 'T', kv.first.c_str(), r.at[0], r.at[1], r.at[2], r.at[3]);
+            if (r.kpx) std::printf("%d %d %d %d\n", r.kat[0], r.kat[1], r.kat[2], r.kat[3]);
+            else std::printf("-\n");
+        }
+    std::printf("plan_reach_host: %ld handles planned, %zu template-level keys, %zu edge-level keys\n", handles, seen[0].size(), seen[1].size());
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && strcmp(argv[1], "--reach") == 0) return reach();
+    if (argc > 1) { std::fprintf(stderr, "usage: plan_reach_host [--reach]   (handle descriptions `n h w flags [PNP_NAME=value ...]` on stdin)\n"); return 2; }
+    return describe_stdin();
+}

@@ -1,5 +1,6 @@
 """Dyadic probe weights for the denoiser's conv kernels (no test in here; tests/test_probe_host.py proves what is claimed below on
-the CPU, tests/test_gpu_probe.py uses it on the GPU).
+the CPU, tests/test_gpu_probe.py uses it on the GPU).  tests/variant_cases.py is the table of every handle the probes and the oracle are
+run on, MATRIX below included; tests/test_variant_reach_host.py checks it against the kernel variants a default handle can plan.
 
 A probe is a full 56-key state dict, an image batch and a sigma vector made of small dyadic rationals, with at most two non-zero taps
 per output channel, non-negative everywhere (LeakyReLU is the identity) and zero weights on the bilinearly upsampled half of every

@@ -48,7 +48,11 @@ def test_fft2c_golden_and_roundtrip(golden_dir):
     assert abs(float((f.abs() ** 2).sum()) / float((c.abs() ** 2).sum()) - 1) < 1e-5
 
 
-@pytest.mark.parametrize("n,h,w", [(1, 32, 32), (2, 48, 64), (1, 128, 128), (3, 64, 16), (2, 16, 16)])
+# (the shape lists of the oracle-compared denoiser tests are module constants: tests/variant_cases.py imports them)
+_PER_STAGE_SHAPES = [(1, 32, 32), (2, 48, 64), (1, 128, 128), (3, 64, 16), (2, 16, 16)]
+
+
+@pytest.mark.parametrize("n,h,w", _PER_STAGE_SHAPES)
 def test_denoiser_matches_oracle_per_stage(sd_np, n, h, w):
     e = _engine(n, h, w, sd_np, keep_stages=True)
     sd = O.torch_weights(sd_np)
@@ -157,7 +161,10 @@ def test_psnr_matches_oracle(golden_dir):
     np.testing.assert_allclose(got.numpy(), O.psnr(a, b)[:, 0].numpy(), rtol=1e-6)
 
 
-@pytest.mark.parametrize("n,h,w", [(64, 128, 128), (1, 32, 32), (2, 48, 64), (3, 64, 16)])
+_WINO2_SHAPES = [(64, 128, 128), (1, 32, 32), (2, 48, 64), (3, 64, 16)]
+
+
+@pytest.mark.parametrize("n,h,w", _WINO2_SHAPES)
 def test_winograd_path_matches_oracle_per_stage(sd_np, n, h, w, monkeypatch):
     """The Winograd kernel on every layer it can take (PNP_WINO_MIN_BLOCKS=1 lifts the workgroup-count gate so that small
     and odd-sized problems - 3x4-pixel bottom level, 8/16/32-wide tile variants - run it too), per stage against the oracle."""
@@ -181,11 +188,15 @@ def test_winograd_path_matches_oracle_per_stage(sd_np, n, h, w, monkeypatch):
     np.testing.assert_allclose(got.cpu().numpy(), torch.clamp(ref_raw, 0, 1).numpy(), rtol=0, atol=1e-5)
 
 
-@pytest.mark.parametrize("n,h,w,min_cin", [(2, 128, 128, 128), (2, 96, 112, 128), (1, 144, 64, 128), (1, 256, 256, 128), (3, 128, 64, 64),
-                                           (3, 256, 256, 64),       # 16 x 16 bottom level: two slices stacked per workgroup (odd batch)
-                                           (2, 128, 128, 32), (1, 80, 48, 32),    # + the Cout = 32 / Cin = 32 layers (4-wave variant)
-                                           (8, 272, 272, 32), (2, 256, 144, 32)])  # level widths 34 / 18, 9: not multiples of 4 - F(2x2) / direct there
-@pytest.mark.parametrize("schedule", ["default", "in-step", "independent"])
+_F4_SHAPES = [(2, 128, 128, 128), (2, 96, 112, 128), (1, 144, 64, 128), (1, 256, 256, 128), (3, 128, 64, 64),
+              (3, 256, 256, 64),       # 16 x 16 bottom level: two slices stacked per workgroup (odd batch)
+              (2, 128, 128, 32), (1, 80, 48, 32),    # + the Cout = 32 / Cin = 32 layers (4-wave variant)
+              (8, 272, 272, 32), (2, 256, 144, 32)]  # level widths 34 / 18, 9: not multiples of 4 - F(2x2) / direct there
+_F4_SCHEDULE_ENV = {"default": {}, "in-step": {"PNP_NO_WINO_F4_PHASED": "1", "PNP_WINO_F4_MT16": "1"}, "independent": {"PNP_WINO_F4_MT16": "3"}}
+
+
+@pytest.mark.parametrize("n,h,w,min_cin", _F4_SHAPES)
+@pytest.mark.parametrize("schedule", list(_F4_SCHEDULE_ENV))
 def test_winograd_f4_path_matches_oracle_per_stage(sd_np, n, h, w, min_cin, schedule, monkeypatch):
     """F(4x4,3x3) (winograd4_kernels.hip, points 0, +-3/4, +-3/2, inf) on every layer it can take - workgroup gate lifted so
     small and ragged sizes run it (partial 4x4 tiles, 16- and 32-wide tile variants, upsample+concat sources, pooled copies
@@ -194,11 +205,8 @@ def test_winograd_f4_path_matches_oracle_per_stage(sd_np, n, h, w, min_cin, sche
     level); every one on 16-tile M-blocks (two independent workgroups per CU)."""
     monkeypatch.setenv("PNP_WINO_MIN_BLOCKS", "1")
     monkeypatch.setenv("PNP_WINO_F4_MIN_CIN", str(min_cin))
-    if schedule == "in-step":
-        monkeypatch.setenv("PNP_NO_WINO_F4_PHASED", "1")
-        monkeypatch.setenv("PNP_WINO_F4_MT16", "1")
-    elif schedule == "independent":
-        monkeypatch.setenv("PNP_WINO_F4_MT16", "3")
+    for k, v in _F4_SCHEDULE_ENV[schedule].items():
+        monkeypatch.setenv(k, v)
     e = _engine(n, h, w, sd_np, keep_stages=True)
     algos = e.conv_algorithms()
     assert sum(1 for v in algos if v == 4) >= (9 if min_cin <= 64 and min(h, w) >= 128 else 1), algos
@@ -221,7 +229,10 @@ def test_winograd_f4_path_matches_oracle_per_stage(sd_np, n, h, w, min_cin, sche
 
 
 # ---- bf16-operand conv mode (PNP_FLAG_BF16_CONVS, BASELINE configs[4]) ------------------------------------------------
-@pytest.mark.parametrize("n,h,w", [(1, 32, 32), (2, 48, 64), (1, 128, 128), (2, 256, 256), (3, 64, 16)])
+_BF16_SHAPES = [(1, 32, 32), (2, 48, 64), (1, 128, 128), (2, 256, 256), (3, 64, 16)]
+
+
+@pytest.mark.parametrize("n,h,w", _BF16_SHAPES)
 def test_bf16_convs_match_bf16_oracle_per_stage(sd_np, n, h, w):
     """Parity target = the oracle with the same operand rounding (conv inputs and weights to bf16, nearest even; f32
     products and sums).  The first stage's first bf16 layer has a single chunk and differs by summation order only; deeper
@@ -297,19 +308,18 @@ def test_bf16_activation_storage_is_bit_neutral(sd_np, n, h, w, monkeypatch):
 
 # ---- shape sweep: every tile-width variant, ragged tile grids, every batch remainder ---------------------------------------
 _SWEEP = [(1, 16, 48), (5, 32, 16), (2, 80, 48), (3, 96, 112), (1, 144, 64), (4, 16, 16), (2, 64, 176), (1, 208, 32)]
+_SWEEP_MODE_ENV = {"default": {}, "winograd": {"PNP_WINO_MIN_BLOCKS": "1"}, "direct": {"PNP_NO_WINOGRAD": "1"}, "bf16": {}}
 
 
-@pytest.mark.parametrize("mode", ["default", "winograd", "direct", "bf16"])
+@pytest.mark.parametrize("mode", list(_SWEEP_MODE_ENV))
 @pytest.mark.parametrize("n,h,w", _SWEEP)
 def test_denoiser_shape_sweep(sd_np, n, h, w, mode, monkeypatch):
     """The U-Net needs H, W multiples of 16 only (noise.py:49-53 pad is then a no-op); sizes that are NOT multiples of the
     kernels' 32-/16-/8-wide tiles exercise partial tiles, odd tile grids and the low-res upsample staging at image borders,
     on each kernel family: plan defaults, Winograd forced on every eligible layer, direct f32 only, bf16 operands."""
     from dt4image_restoration_amd.engine import PnPEngine
-    if mode == "winograd":
-        monkeypatch.setenv("PNP_WINO_MIN_BLOCKS", "1")
-    if mode == "direct":
-        monkeypatch.setenv("PNP_NO_WINOGRAD", "1")
+    for k, v in _SWEEP_MODE_ENV[mode].items():
+        monkeypatch.setenv(k, v)
     e = PnPEngine(n, h, w, bf16_convs=(mode == "bf16"))
     e.load_weights(sd_np)
     algos = e.conv_algorithms()[1:27]
@@ -364,18 +374,22 @@ def test_slice128_single_workgroup_stage_matches_three_launch_path_and_oracle(mo
     assert float((z1[live] - zo[live]).abs().max()) < 3e-6 and float((u1[live] - uo[live]).abs().max()) < 3e-6
 
 
+_FUSED_SHAPE = (3, 256, 256)
+_UNFUSED_ENV = {"PNP_NO_F4_FUSED_FIRST": "1", "PNP_NO_F4_FUSED_LAST": "1"}
+
+
 def test_fused_first_and_last_layer_match_their_own_kernels(sd_np, monkeypatch):
     """At the headline size the first layer (2 -> 32) is evaluated inside inc.conv-1's staging and the last one (1x1, residual, clamp)
     inside up4.conv-2's epilogue; `PNP_NO_F4_FUSED_FIRST` / `PNP_NO_F4_FUSED_LAST` put them back on their own kernels.  Same
     arithmetic up to the order of a few additions: the denoiser output agrees to 2e-6, and both agree with the oracle."""
-    n, h, w = 3, 256, 256
+    n, h, w = _FUSED_SHAPE
     x = (torch.from_numpy(synthetic.hash_uniform(23, 7, n * h * w).reshape(n, 1, h, w)) + 1) * 0.5
     sigma = torch.linspace(4, 40, n) / 255.0
     outs = {}
     for fused in (True, False):
         if not fused:
-            monkeypatch.setenv("PNP_NO_F4_FUSED_FIRST", "1")
-            monkeypatch.setenv("PNP_NO_F4_FUSED_LAST", "1")
+            for k, v in _UNFUSED_ENV.items():
+                monkeypatch.setenv(k, v)
         e = _engine(n, h, w, sd_np)
         algos = e.conv_algorithms()
         assert algos[1] == 4 and algos[26] == (4 if fused else 1), algos   # inc.conv-1 / up4.conv-2: the layers that carry the fusions

@@ -134,20 +134,23 @@ def test_probe_is_bit_exact(arith, probe, seed, shape, row, monkeypatch):
 
 
 # ---- the clamp ----------------------------------------------------------------------------------------------------------------------
+CLAMP_SHAPE = (3, 256, 256)
+CLAMP_ENV = {False: {"PNP_NO_WINOGRAD": "1"}, True: {}}        # by bf16 mode (f32: the direct kernels, exact; F(4x4) is not)
+
+
 @pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
 @pytest.mark.parametrize("shift", [1.0, -1.0, 0.5, -0.5])
 def test_probe_clamp_is_exact(shift, bf16, monkeypatch):
     """`sum` with the read-out bias moved by +-1 (every pixel clamps) and +-1/2 (about half): exact, on the fused last layer of the default
     f32 plan and of the bf16 plan, and on the layer's own kernel (keep_stages)."""
-    n, h, w = 3, 256, 256
+    n, h, w = CLAMP_SHAPE
     bias = 2.0 ** -5 + shift
     sd = P.probe_state_dict("sum", 0, outc_bias=bias)
     x, sigma = P.probe_inputs(0, n, h, w)
     ref_out, _ = P.cached_reference("sum", 0, n, h, w, "bf16" if bf16 else "f32", bias)
     assert float(((ref_out == 0) | (ref_out == 1)).double().mean()) >= (1.0 if abs(shift) == 1 else 0.3)
     for keep_stages in (False, True):
-        env = {} if bf16 else {"PNP_NO_WINOGRAD": "1"}        # (f32: the direct kernels, exact; F(4x4) is not)
-        e = _engine(n, h, w, bf16, keep_stages, env, monkeypatch)
+        e = _engine(n, h, w, bf16, keep_stages, CLAMP_ENV[bf16], monkeypatch)
         try:
             e.load_weights(sd)
             P.assert_same_bits(e.denoise(x.cuda(), sigma.cuda()), ref_out, f"clamp {shift:+} keep_stages={keep_stages}")

@@ -311,6 +311,8 @@ def test_refused_sizes_name_the_shape_and_touch_nothing(h, w):
 # ---- GPU: the denoiser at the sides no other test runs -------------------------------------------------------------------------------
 
 DENOISER_SHAPES = [(1, 1024, 1024), (1, 16, 1024), (1, 1024, 16), (2, 800, 640), (1, 1008, 112)]
+DENOISER_MODE_ENV = {"default": {}, "winograd": {"PNP_WINO_MIN_BLOCKS": "1"}, "direct": {"PNP_NO_WINOGRAD": "1"}, "bf16": {}}
+STAGES_SHAPE = (1, 1024, 1024)          # test_denoiser_stages_at_1024x1024
 _DENOISER_REF = {}
 
 
@@ -334,16 +336,14 @@ def _denoiser_ref(sd_np, n, h, w, bf16):
 
 
 @gpu
-@pytest.mark.parametrize("mode", ["default", "winograd", "direct", "bf16"])
+@pytest.mark.parametrize("mode", list(DENOISER_MODE_ENV))
 @pytest.mark.parametrize("n,h,w", DENOISER_SHAPES, ids=_ids(DENOISER_SHAPES))
 def test_denoiser_at_large_and_extreme_sides(sd_np, n, h, w, mode, monkeypatch):
     """16 x 1024 has a 1 x 64 bottom level, 1024 x 16 a 64 x 1 one, 1008 x 112 a 63 x 7 one (1008 is refused by the k-space stage
     only); each under the modes of test_denoiser_shape_sweep, with its bounds.  In default mode, out == x gives the same bits."""
     from dt4image_restoration_amd.engine import PnPEngine
-    if mode == "winograd":
-        monkeypatch.setenv("PNP_WINO_MIN_BLOCKS", "1")
-    if mode == "direct":
-        monkeypatch.setenv("PNP_NO_WINOGRAD", "1")
+    for k, v in DENOISER_MODE_ENV[mode].items():
+        monkeypatch.setenv(k, v)
     e = PnPEngine(n, h, w, bf16_convs=(mode == "bf16"))
     try:
         e.load_weights(sd_np)
@@ -372,7 +372,7 @@ def test_denoiser_at_large_and_extreme_sides(sd_np, n, h, w, mode, monkeypatch):
 @gpu
 def test_denoiser_stages_at_1024x1024(sd_np):
     from dt4image_restoration_amd.engine import PnPEngine
-    n, h, w = 1, 1024, 1024
+    n, h, w = STAGES_SHAPE
     e = PnPEngine(n, h, w, keep_stages=True)
     try:
         e.load_weights(sd_np)

@@ -30,6 +30,9 @@ SHAPES = [(3, 256, 256), (2, 128, 128), (1, 144, 64), (2, 96, 112), (2, 144, 112
 NO_F4_LEVEL = {(2, 96, 112)}           # no 128-channel level that F(4x4) takes (see the module docstring)
 IDS = ["x".join(map(str, s)) for s in SHAPES]
 SCHED_COUT_SPLIT = 4
+CS_VALUES = (2, 0)                     # PNP_WINO_F4_CS of the two handles every test here compares
+PROBE_SHAPE = (2, 128, 128)            # test_dyadic_probe_weights_under_coutsplit
+STEP_SHAPE = (3, 256, 256)             # test_a_stopped_slice_keeps_its_bits_and_the_live_ones_match
 
 
 @pytest.fixture(scope="module")
@@ -80,7 +83,7 @@ def _run(sd_np, shape):
         n, h, w = shape
         x, sigma = _inputs(n, h, w)
         res = {}
-        for cs in (2, 0):
+        for cs in CS_VALUES:
             e = _engine(n, h, w, sd_np, cs)
             try:
                 out = e.denoise(x.cuda(), sigma.cuda()).cpu()
@@ -133,7 +136,7 @@ def test_coutsplit_matches_the_oracle_per_stage(sd_np, shape):
 def test_a_stopped_slice_keeps_its_bits_and_the_live_ones_match(sd_np):
     """Two pnp_step calls at (3, 256, 256) with slice 1 stopped (done = [0, 1, 0]): its x, z, u keep their bits under the cout-split
     kernels (which skip a stopped slice's workgroups), the live slices equal the PNP_WINO_F4_CS=0 run bit for bit."""
-    n, h, w = 3, 256, 256
+    n, h, w = STEP_SHAPE
     data = synthetic.make_problem(n, h, w, accel=4.0, seed=911)
     st = O.reset(data)
     mu_tab, sig_tab = synthetic.param_table(n, 2, seed=77)
@@ -168,7 +171,7 @@ def test_dyadic_probe_weights_under_coutsplit(seed):
     """tests/probe_weights.py's `route` probe at (2, 128, 128), as test_gpu_probe.py runs it on F(4x4) (whose points +-3/4, +-3/2 are not
     exact in f32 products): within the suite's f32 bound AND equal to the float64-exact answer after rounding to the probe's grid
     (2^-4 for the stages, 2^-17 for the output) - and, the summation order being the same, the very bits of the PNP_WINO_F4_CS=0 handle."""
-    n, h, w = 2, 128, 128
+    n, h, w = PROBE_SHAPE
     sd = P.probe_state_dict("route", seed)
     x, sigma = P.probe_inputs(seed, n, h, w)
     ref_out, ref_stages = P.cached_reference("route", seed, n, h, w, "f32")
