@@ -81,6 +81,16 @@ SIGNATURES = {
     "pnp_mc_cg_residual": (C.c_int, [C.c_void_p, _fp, _vp]),
     "pnp_mc_normal": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),
     "pnp_acquire_mc": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _u8p, C.c_int, C.c_double, C.c_uint64, C.c_int, _fp, _fp, _fp, _vp]),
+    "pnp_nufft_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pnp_nufft_samples": (C.c_int64, [C.c_void_p]),
+    "pnp_nufft_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pnp_nufft_forward": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, _vp]),
+    "pnp_nufft_adjoint": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, _vp]),
+    "pnp_set_kspace_nc": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _vp]),
+    "pnp_reset_nc": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _vp]),
+    "pnp_nc_cg_residual": (C.c_int, [C.c_void_p, _fp, _vp]),
+    "pnp_nc_normal": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),
+    "pnp_acquire_nc": (C.c_int, [C.c_void_p, _fp, _fp, C.c_double, C.c_uint64, C.c_int, _fp, _fp, _fp, _vp]),
     "pnp_estimate_sens": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp, _fp, _vp]),
     "pnp_coil_compress_matrix": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _vp]),
     "pnp_coil_compress_apply": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, C.c_int, C.c_int, _fp, _vp]),

@@ -22,6 +22,7 @@ from . import _lib, synthetic
 from .weights import hash_uniform
 
 MASK_KINDS = ("radial", "cartesian", "uniform")
+NC_KINDS = ("radial-nc",)                                   # task_problem: non-Cartesian acquisitions (no mask: a trajectory)
 
 
 def _engine(engine_or_env, n: int, h: int, w: int, device: torch.device):
@@ -131,7 +132,52 @@ def prewhiten(engine_or_env, y0, noise, sens=None, inplace: bool = True):
     return y, s, wmat, psi
 
 
-def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: int = 0, sens=None, noise_cov=None) -> Dict[str, torch.Tensor]:
+def radial_trajectory(h: int, w: int, spokes: int, readout: int = None, golden: bool = True) -> np.ndarray:
+    """float64 [spokes * R, 2]: the (ky, kx) of a radial acquisition in cycles per pixel (include/pnpadmm.h, "non-Cartesian sampling").
+    Spoke s has the angle s pi (sqrt 5 - 1) / 2 (golden) or s pi / spokes; its R = readout (default 2 max(h, w)) samples sit at
+    r_j = (j - R/2) / R, (ky, kx) = (r sin, r cos).  Sample j of spoke s is row s R + j."""
+    spokes = int(spokes)
+    R = 2 * max(int(h), int(w)) if readout is None else int(readout)
+    if spokes < 1 or R < 2:
+        raise ValueError(f"radial_trajectory: need spokes >= 1 and readout >= 2, got {spokes}, {R}")
+    r = (np.arange(R, dtype=np.float64) - R / 2) / R
+    out = np.empty((spokes, R, 2), dtype=np.float64)
+    for s in range(spokes):
+        a = s * math.pi * (math.sqrt(5.0) - 1.0) / 2.0 if golden else s * math.pi / spokes
+        out[s, :, 0] = r * math.sin(a)
+        out[s, :, 1] = r * math.cos(a)
+    return out.reshape(-1, 2)
+
+
+def radial_dcf(traj, h: int, w: int) -> np.ndarray:
+    """float32 [M]: the ramp density compensation of a radial trajectory, max(|r|, 1 / (2 R)) scaled so that the weights sum to h w (the
+    slice size is not in the trajectory).  R, the readout length, is read from the trajectory itself: the first two samples of a
+    `radial_trajectory` are 1 / R apart."""
+    t = np.asarray(traj.detach().cpu().numpy() if isinstance(traj, torch.Tensor) else traj, dtype=np.float64)
+    if t.ndim != 2 or t.shape[1] != 2 or t.shape[0] < 2:
+        raise ValueError(f"radial_dcf: expected a radial trajectory [M,2] with M >= 2, got {t.shape}")
+    step = float(np.hypot(*(t[1] - t[0])))
+    if not step > 0.0:
+        raise ValueError("radial_dcf: the first two samples coincide: not a radial_trajectory")
+    R = int(round(1.0 / step))
+    d = np.maximum(np.hypot(t[:, 0], t[:, 1]), 1.0 / (2.0 * R))
+    return (d * (h * w / d.sum())).astype(np.float32)
+
+
+def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, width: int, grid) -> Dict[str, torch.Tensor]:
+    t = np.ascontiguousarray(traj.detach().cpu().numpy() if isinstance(traj, torch.Tensor) else traj, dtype=np.float64)
+    eng.nufft_plan(t, grid=grid, width=width)
+    d = None if dcf is None else torch.as_tensor(dcf).to(eng.device, torch.float32).contiguous()
+    y, aty0, x0 = eng.acquire_nc(g, float(sigma_n), seed, dcf=d)
+    out = {"x0": torch.view_as_real(x0), "y0": torch.view_as_real(y.reshape(eng.n, 1, -1)), "ATy0": torch.view_as_real(aty0), "gt": g,
+           "x0_raw": aty0.real.contiguous(), "traj": torch.from_numpy(t)}
+    if d is not None:
+        out["dcf"] = d
+    return out
+
+
+def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: int = 0, sens=None, noise_cov=None, traj=None, dcf=None,
+             nufft_width: int = 6, nufft_grid=None) -> Dict[str, torch.Tensor]:
     """The collated `.mat` dict `PnPEnv.reset` reads, acquired on the device: x0, y0, ATy0 float32 [N,1,H,W,2] (real views of the
     complex outputs), mask bool [H,W] (or [N,H,W]), gt float32 [N,1,H,W], x0_raw = Re ATy0 [N,1,H,W]; every tensor on the GPU.
     gt: [N,H,W] or [N,1,H,W] in [0, 1] (array or tensor), mask: [H,W] or [N,H,W] in the centred layout.  Slice i draws the noise of
@@ -141,7 +187,10 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
     noise_cov (with sens): the channel noise covariance Psi, complex [C,C] Hermitian positive definite (e.g. `synthetic.noise_cov_model`):
     y_c = mask * (fft_c(S_c gt) + sigma_n * sum_k L[c][k] noise_k), Psi = L L^H - the noise-free acquisition plus the masked white noise
     of the plain call mixed by L on the device (pnp_whiten_apply, in place; an unsampled bin stays exactly zero).  ATy0 is the sum of
-    the two parts' A^H (the noise part through the maps mixed by L^H), x0 its clip at 0; the dict carries `noise_cov` (complex128)."""
+    the two parts' A^H (the noise part through the maps mixed by L^H), x0 its clip at 0; the dict carries `noise_cov` (complex128).
+    traj (float64 [M,2], e.g. `radial_trajectory`; mask is then ignored and may be None): the non-Cartesian acquisition (pnp_nufft_plan +
+    pnp_acquire_nc, single-coil): y0 is [N,1,M,2], ATy0 = A^H (dcf y) with dcf float32 [M] or None, and the dict carries `traj` and `dcf`
+    (when given) in place of `mask`."""
     if not torch.cuda.is_available():
         raise RuntimeError("simulate needs a ROCm GPU; the CPU route is synthetic.make_problem")
     g = torch.as_tensor(gt)
@@ -155,6 +204,10 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
     if (eng.n, eng.h, eng.w) != (n, h, w):
         raise ValueError(f"gt {tuple(g.shape)} does not fit the engine [{eng.n},{eng.h},{eng.w}]")
     g = g.to(eng.device, torch.float32).reshape(n, 1, h, w).contiguous()
+    if traj is not None:
+        if sens is not None or noise_cov is not None:
+            raise ValueError("simulate: a non-Cartesian acquisition is single-coil (traj with sens / noise_cov is not supported)")
+        return _simulate_nc(eng, g, traj, dcf, sigma_n, int(seed) + int(first_slice), nufft_width, nufft_grid)
     m = torch.as_tensor(mask)
     if m.numel() == h * w:
         m = m.reshape(h, w)
@@ -510,12 +563,23 @@ def make_mask(h: int, w: int, accel: float, kind: str = "radial", seed: int = 0)
 
 
 def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int = 0, mask_kind: str = "radial",
-                 mask=None, coils: int = 0, noise_cov=None) -> Dict[str, torch.Tensor]:
+                 mask=None, coils: int = 0, noise_cov=None, spokes: int = None, nc_weights: str = "dcf", nufft_width: int = 6,
+                 nufft_grid=None) -> Dict[str, torch.Tensor]:
     """`simulate` for a named task: '4x_10' = acceleration 4, sigma_n = 10 / 255.  mask: a ready mask, or None for
     `make_mask(h, w, accel, mask_kind, seed)` (the same for every shard of a job).  coils > 0: a multi-coil acquisition with the
-    analytic maps `synthetic.coil_maps(coils, h, w)`; noise_cov: their channel noise covariance (`simulate`)."""
+    analytic maps `synthetic.coil_maps(coils, h, w)`; noise_cov: their channel noise covariance (`simulate`).
+    mask_kind "radial-nc": a true radial acquisition, samples off the grid (`simulate(traj=)`): golden-angle `radial_trajectory` of
+    `spokes` spokes (None: ceil(h / accel)), weighted by `radial_dcf` (nc_weights "dcf") or not at all ("none"); single-coil."""
     accel, sigma_n = parse_task(task)
     h, w = (int(v) for v in torch.as_tensor(gt).shape[-2:])
+    if mask_kind in NC_KINDS:
+        if coils or noise_cov is not None or mask is not None:
+            raise ValueError("task_problem: mask_kind 'radial-nc' is single-coil and takes no mask")
+        if nc_weights not in ("none", "dcf"):
+            raise ValueError(f"nc_weights must be 'none' or 'dcf', got {nc_weights!r}")
+        traj = radial_trajectory(h, w, int(math.ceil(h / accel)) if spokes is None else int(spokes))
+        return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, traj=traj, dcf=radial_dcf(traj, h, w) if nc_weights == "dcf" else None,
+                        nufft_width=nufft_width, nufft_grid=nufft_grid)
     if mask is None:
         mask = make_mask(h, w, accel, mask_kind, seed)
     sens = synthetic.coil_maps(coils, h, w).astype(np.complex64) if coils else None

@@ -24,6 +24,7 @@ subproblem is then solved by K conjugate-gradient iterations per step (`acquire`
 layout has none):
 
     ... --coils 4 --cg-iters 8 eval|flex|mcts|fixed ...
+    ... --traj radial [--spokes S] [--nufft-width 4|6|8] [--nufft-grid GH GW] [--nc-weights none|dcf] [--cg-iters K] eval|flex|mcts|fixed|acquire ...
     ... --coils 4 --sens estimate [--sens-window hann|box] [--sens-thresh 0.05] [--acs H W] --mask cartesian fixed ...
 
     ... --coils 8 --sens espirit [--espirit-kernel 6] [--espirit-sv 0.02] [--espirit-crop 0.9] [--espirit-iters 16] --mask cartesian fixed ...
@@ -103,7 +104,8 @@ def _build(args, mode):
         model.load_state_dict(weights.generate_policy_weights(model, args.seed, t_bias=-1.0, head_gain=8.0))
     den = _denoiser(args)
     scorer = (lambda st: 1.0 / (1e-3 + (st["x"] - torch.nn.functional.avg_pool2d(st["x"], 3, 1, 1)).pow(2).mean(dim=(1, 2, 3))))
-    env = PnPEnv(max_episode_step=30, denoiser=den, device_type="cuda", no_ref_scorer=None, cg_iters=args.cg_iters)
+    env = PnPEnv(max_episode_step=30, denoiser=den, device_type="cuda", no_ref_scorer=None, cg_iters=args.cg_iters,
+                 nufft_width=args.nufft_width, nufft_grid=args.nufft_grid)
     if getattr(args, "scorer", "stub") == "neg_dc":            # minus the k-space data misfit of the rollout's final iterate (pnp_residuals)
         scorer = (lambda st: -env.residuals(st, dc=True)[:, 5])
     return model, env, scorer
@@ -208,9 +210,35 @@ def _grappa_start(env, batch, filled):
     return batch
 
 
+def _nc_kwargs(args):
+    """--traj radial: what `acquisition.task_problem` needs for the non-Cartesian acquisition of a task."""
+    return dict(mask_kind="radial-nc", spokes=args.spokes, nc_weights=args.nc_weights, nufft_width=args.nufft_width, nufft_grid=args.nufft_grid)
+
+
 def _sets(args, flex_target=None, env=None):
     """(name, number of images, load(start, stop) -> (batch dict, task tokens)) per evaluation set."""
     from . import acquisition, data as D, synthetic
+    if args.traj and args.data:
+        raise SystemExit("--traj: the reference's .mat layout (--data) holds Cartesian k-space and a mask; use the synthetic sets or --gt")
+    if args.traj:                                            # a true radial acquisition of the --gt images, or of make_problem's phantoms
+        def nc_load(images, task, a, b):
+            try:
+                batch = acquisition.task_problem(task, images(a, b), env, seed=args.seed, first_slice=a, **_nc_kwargs(args))
+            except (ValueError, RuntimeError) as e:          # a grid the rule refuses, a slice side without a grid
+                raise SystemExit(f"--traj radial: task {task}: {e}")
+            return batch, D.task_tokens([task] * (b - a), flex_target)
+        if args.gt:
+            for d in args.gt:
+                for task in _tasks(args):
+                    images = (lambda a, b, d=d: D.load_gt_dir(d, limit=args.limit, start=a, stop=b)[0])
+                    yield f"{d} {task} radial-nc", D.count_gt_dir(d, args.limit), (lambda a, b, im=images, t=task: nc_load(im, t, a, b))
+        else:
+            for accel, sig in ((4, 10), (8, 10)):
+                images = (lambda a, b, accel=accel: np.stack([synthetic.phantom(args.size, args.size, args.seed + accel + i)
+                                                              for i in range(a, b)]).astype(np.float32))
+                yield (f"synthetic {accel}x_{sig} radial-nc", args.limit or 7,
+                       (lambda a, b, im=images, t=f"{accel}x_{sig}": nc_load(im, t, a, b)))
+        return
     if args.gt:
         for d in args.gt:
             for task in _tasks(args):
@@ -291,8 +319,11 @@ def _acquire(args):
                 engines[key] = PnPEngine(*key, denoiser=False)
             for task in tasks:
                 try:
-                    p = acquisition.task_problem(task, gt, engines[key], seed=args.seed, first_slice=a, mask_kind=args.mask)
+                    p = acquisition.task_problem(task, gt, engines[key], seed=args.seed, first_slice=a,
+                                                 **(_nc_kwargs(args) if args.traj else dict(mask_kind=args.mask)))
                 except ValueError as e:
+                    if args.traj:
+                        raise SystemExit(f"--traj radial: task {task}: {e}")
                     if args.mask != "uniform":
                         raise
                     raise SystemExit(f"--mask uniform: task {task}: {e}")
@@ -300,7 +331,7 @@ def _acquire(args):
                 for i, name in enumerate(names):
                     D.save_mat(os.path.join(dsts[task], acquired_name(task, name)), host, i)
         for task in tasks:
-            out.append({"set": d, "task": task, "n": total, "dir": dsts[task], "mask": args.mask})
+            out.append({"set": d, "task": task, "n": total, "dir": dsts[task], "mask": "radial-nc" if args.traj else args.mask})
             print(json.dumps(out[-1]), flush=True)
     return out
 
@@ -331,7 +362,15 @@ def main(argv=None):
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--coils", type=int, default=0, help="multi-coil (SENSE) problems with this many analytic coil maps (1..32; "
                     "default 0: single-coil)")
-    ap.add_argument("--cg-iters", type=int, default=8, help="conjugate-gradient iterations per step of a multi-coil problem (1..64)")
+    ap.add_argument("--cg-iters", type=int, default=8, help="conjugate-gradient iterations per step of a multi-coil or --traj problem (1..64)")
+    ap.add_argument("--traj", choices=("radial",), default=None, help="a non-Cartesian acquisition: golden-angle radial spokes whose samples lie "
+                    "off the grid (NUFFT data fidelity, CG solve), single-coil: the synthetic sets or --gt, not --data")
+    ap.add_argument("--spokes", type=int, default=None, metavar="S", help="--traj radial: spokes (default: ceil(H / acceleration) of the task)")
+    ap.add_argument("--nufft-width", type=int, choices=(4, 6, 8), default=6, help="--traj: width of the gridding kernel in grid points")
+    ap.add_argument("--nufft-grid", type=int, nargs=2, default=None, metavar=("GH", "GW"), help="--traj: sides of the oversampled grid (sides "
+                    "the k-space stage accepts, at least 1.25 x the slice; default: the smallest such)")
+    ap.add_argument("--nc-weights", choices=("none", "dcf"), default="dcf", help="--traj: sample weights of the data term and of ATy0: the "
+                    "radial density compensation, or none")
     ap.add_argument("--sens", choices=("true", "estimate", "espirit"), default="true", help="coil maps of a --coils run: the analytic maps that "
                     "generated the measurements, or maps estimated on the device from the calibration block of each set's own y0 (estimate: "
                     "the low-resolution estimate; espirit: ESPIRiT, at most 16 coils)")
@@ -394,6 +433,15 @@ def main(argv=None):
         raise SystemExit(f"--coils must be 1..32, got {args.coils}")
     if not 1 <= args.cg_iters <= 64:
         raise SystemExit(f"--cg-iters must be 1..64, got {args.cg_iters}")
+    if args.traj:
+        if args.coils:
+            raise SystemExit("--traj with --coils: refused - the non-Cartesian stage is single-coil (multi-coil non-Cartesian is not built)")
+        if args.spokes is not None and args.spokes < 1:
+            raise SystemExit(f"--spokes must be >= 1, got {args.spokes}")
+        if args.grappa or args.mask != "radial":
+            raise SystemExit("--traj takes no --mask / --grappa: its samples are a trajectory, not a mask")
+    elif args.spokes is not None or args.nufft_grid is not None or args.nufft_width != 6 or args.nc_weights != "dcf":
+        raise SystemExit("--spokes / --nufft-width / --nufft-grid / --nc-weights need --traj radial")
     if args.prior == "tv":
         if not (args.tv_scale >= 0.0 and np.isfinite(args.tv_scale)):
             raise SystemExit(f"--tv-scale must be finite and >= 0, got {args.tv_scale}")
@@ -490,7 +538,8 @@ def main(argv=None):
         from .drivers.fixed import FixedScheduleSolver
         from .env import PnPEnv
         den = _denoiser(args)
-        env = PnPEnv(max_episode_step=args.max_iter, denoiser=den, device_type="cuda", cg_iters=args.cg_iters)
+        env = PnPEnv(max_episode_step=args.max_iter, denoiser=den, device_type="cuda", cg_iters=args.cg_iters,
+                     nufft_width=args.nufft_width, nufft_grid=args.nufft_grid)
         solver = FixedScheduleSolver(env, max_iter=args.max_iter, tol=args.tol, sync_every=5, dc=args.dc,
                                      device_type=torch.device("cuda", torch.cuda.current_device()))
         t = np.arange(args.max_iter) / max(args.max_iter - 1, 1)

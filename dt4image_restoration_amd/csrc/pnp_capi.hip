@@ -3,6 +3,7 @@
 #include "../../include/pnpadmm.h"
 #include "pnp_internal.h"
 #include "denoiser_plan.h"
+#include "nufft_plan.h"
 #include "block_reduce.h"
 
 #include <cmath>
@@ -122,6 +123,18 @@ struct pnp_engine {
     // GRAPPA weights (pnp_grappa_weights): allocated inside its first call, grown by a call that needs more
     double2* gr_ws = nullptr;    // per slice M = A^H [A | T], [ns, ns + nt] complex128; the solve factors it in place
     size_t gr_cap = 0;
+    // non-Cartesian stage: the plan and its two buffers by pnp_nufft_plan, the episode constants by pnp_set_kspace_nc / pnp_reset_nc
+    NufftDev nc;                 // the uploaded plan; nc.m == 0: none
+    size_t nc_i0_cap = 0, nc_wts_cap = 0, nc_cy_cap = 0, nc_cx_cap = 0, nc_off_cap = 0, nc_idx_cap = 0, nc_twh_cap = 0, nc_tww_cap = 0;
+    float2* nc_grid = nullptr;   // [N, gh, gw] the oversampled grid
+    float2* nc_samp = nullptr;   // [N, M] sample scratch (A p inside the normal operator, A x of the misfit)
+    float2* nc_y = nullptr;      // [N, M] the installed samples
+    float* nc_w = nullptr;       // [M] the installed weights (read only while nc_has_w)
+    double* nc_mpart = nullptr;  // [N, nufft_sample_chunks(M)] partial sums of the misfit
+    size_t nc_grid_cap = 0, nc_samp_cap = 0, nc_y_cap = 0, nc_w_cap = 0, nc_mpart_cap = 0;
+    bool nc_on = false;          // non-Cartesian constants were installed last: the CG stage runs on the NUFFT normal operator
+    bool nc_has_w = false;
+    int nc_cg = 0;               // CG iterations per step
     // the prior of pnp_step (pnp_set_prior) and the total-variation denoiser's workspace (allocated inside the first call that runs it)
     int prior = PNP_PRIOR_UNET;
     double tv_scale = 1.0;       // as given; applied as float32
@@ -194,12 +207,16 @@ struct SnapLayout {
     size_t bytes() const { return t_off() + t_bytes(); }
 };
 
-int make_twiddles(int L, float2** out) {
+std::vector<float2> twiddle_table(int L) {
     std::vector<float2> t(L);
     for (int m = 0; m < L; ++m) {
         const double a = -2.0 * M_PI * (double)m / (double)L;
         t[m] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
+    return t;
+}
+int make_twiddles(int L, float2** out) {
+    const std::vector<float2> t = twiddle_table(L);
     HIP_TRY(hipMalloc((void**)out, sizeof(float2) * L));
     HIP_TRY(hipMemcpy(*out, t.data(), sizeof(float2) * L, hipMemcpyHostToDevice));
     return PNP_OK;
@@ -362,19 +379,64 @@ int mc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
     return PNP_OK;
 }
 
-// the K-step CG solve of (A^H A + mu I) z = A^H y + mu (x + u), warm-started from z, then u <- u + x - z
-int run_prox_dual_mc(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u, hipStream_t s) {
+// ---- non-Cartesian stage ----------------------------------------------------------------------------
+// the centred transform of pnp_fft2c on the plan's grid, in place in nc_grid: rows then columns in both directions
+int nc_fft(pnp_engine* e, int batch, int inverse, hipStream_t s) {
+    const NufftDev& P = e->nc;
+    {
+        Prof p(e, s, PROF_FFT_ROWS, -1);
+        HIP_TRY(launch_fft_rows(e->nc_grid, e->nc_grid, P.tw_gw, batch, P.gh, P.gw, inverse, P.gw / 2, s));
+    }
+    Prof p(e, s, PROF_FFT_COLS, -1);
+    HIP_TRY(launch_fft_cols(e->nc_grid, P.tw_gh, batch, P.gh, P.gw, inverse, P.gh / 2, s));
+    return PNP_OK;
+}
+// out [batch, M] = A src (src complex, or src_real: a real image)
+int nc_forward(pnp_engine* e, const float2* src, const float* src_real, int batch, float2* out, hipStream_t s) {
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_nufft_pad(src, src_real, e->nc, e->nc_grid, batch, s));
+    }
+    if (int rc = nc_fft(e, batch, 0, s)) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_nufft_interp(e->nc_grid, e->nc, out, batch, s));
+    return PNP_OK;
+}
+// q [batch, h, w] = A^H (w . y) (+ mu pv, with the partial sums of Re<pv, q>: the crop kernel's epilogue)
+int nc_adjoint(pnp_engine* e, const float2* y, const float* w, int batch, const float2* pv, const float* mu, const float* tact, float2* q,
+               double* partial, hipStream_t s) {
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_nufft_grid(y, w, e->nc, e->nc_grid, batch, s));
+    }
+    if (int rc = nc_fft(e, batch, 1, s)) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_nufft_crop(e->nc_grid, e->nc, pv, mu, tact, q, partial, batch, s));
+    return PNP_OK;
+}
+// q = A^H W A pv + mu pv; the partial sums of Re<pv, q> go to mc_part.  Eight launches.  Stopped slices: only the last launch skips them
+// (the others rewrite scratch alone)
+int nc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    if (int rc = nc_forward(e, pv, nullptr, e->cfg.n, e->nc_samp, s)) return rc;
+    return nc_adjoint(e, e->nc_samp, e->nc_has_w ? e->nc_w : nullptr, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
+}
+
+// the K-step CG solve of (A^H A + mu I) z = A^H y + mu (x + u), warm-started from z, then u <- u + x - z; `normal`: the stage's normal
+// operator (mc_normal: the coil operator, nc_normal: the NUFFT pair), which also leaves the partial sums of Re<p, q> in mc_part
+using NormalOp = int (*)(pnp_engine*, const float2*, const float*, const float*, float2*, hipStream_t);
+int run_prox_dual_cg(pnp_engine* e, NormalOp normal, int iters, const float* mu, const float* tact, const float* x, float2* z, float2* u,
+                     hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
     int rc;
-    if ((rc = mc_normal(e, z, mu, tact, mc_q(e), s))) return rc;
+    if ((rc = normal(e, z, mu, tact, mc_q(e), s))) return rc;
     {
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_cg_init(mc_aty(e), x, u, mc_q(e), mu, tact, mc_r(e), mc_p(e), e->mc_part, N, H, W, s));
         HIP_TRY(launch_sense_scalar(e->mc_part, 0, tact, e->mc_sc, N, H, W, s));
         p.end(2);
     }
-    for (int k = 0; k < e->mc_cg; ++k) {
-        if ((rc = mc_normal(e, mc_p(e), mu, tact, mc_q(e), s))) return rc;
+    for (int k = 0; k < iters; ++k) {
+        if ((rc = normal(e, mc_p(e), mu, tact, mc_q(e), s))) return rc;
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_scalar(e->mc_part, 1, tact, e->mc_sc, N, H, W, s));
         HIP_TRY(launch_sense_cg_update(z, mc_r(e), mc_p(e), mc_q(e), e->mc_sc, tact, e->mc_part, N, H, W, s));
@@ -394,7 +456,7 @@ int run_prox_dual_mc(pnp_engine* e, const float* mu, const float* tact, const fl
 // Buffers that grow lose their contents (their callers rewrite them).
 struct WsSlot { void** ptr; size_t* cap; size_t need; bool zero; };
 int ws_grow(pnp_engine* e, const char* label, std::initializer_list<WsSlot> slots) {
-    void* fresh[6] = {};                                   // mc_ensure's six slots are the most
+    void* fresh[10] = {};                                  // pnp_nufft_plan's ten slots are the most
     const auto held = [](const WsSlot& q) { return q.cap ? *q.cap : 0; };
     const auto undo = [&] { for (void* f : fresh) (void)hipFree(f); };   // hipFree(nullptr) is a no-op
     bool any = false, replaces = false;
@@ -471,6 +533,7 @@ int mc_install(pnp_engine* e, const float2* x0, const float2* y0, const float2* 
     HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
     e->mask_n = mask_n;
     e->mc_coils = coils; e->mc_cg = cg_iters; e->mc_sens_n = sens_n;
+    e->nc_on = false;
     e->reset_done = true;
     {
         Prof p(e, s, PROF_OTHER, -1);
@@ -608,7 +671,8 @@ int run_haar(pnp_engine* e, const float* v, const float2* z, const float2* u, co
 int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                   hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
-    if (e->mc_coils > 0) return run_prox_dual_mc(e, mu, tact, x, z, u, s);   // multi-coil constants installed: the CG stage
+    if (e->nc_on) return run_prox_dual_cg(e, nc_normal, e->nc_cg, mu, tact, x, z, u, s);         // non-Cartesian constants installed last
+    if (e->mc_coils > 0) return run_prox_dual_cg(e, mc_normal, e->mc_cg, mu, tact, x, z, u, s);   // multi-coil constants installed: the CG stage
     if (H == 128 && W == 128 && N >= e->tune.slice128_min_n) {   // chip-filling batches of the reference's slice size: 37 B/px
         Prof p(e, s, PROF_FFT_COLS, -1);
         HIP_TRY(launch_admm_slice128(x, z, u, e->plan.tw_w, e->d_y0s, e->d_masks, e->mask_n, mu, tact, N, s));
@@ -727,6 +791,9 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->gr_ws);
     (void)hipFree(e->tv_p);
     (void)hipFree(e->haar_ws);
+    (void)hipFree(e->nc.i0); (void)hipFree(e->nc.wts); (void)hipFree(e->nc.cy); (void)hipFree(e->nc.cx); (void)hipFree(e->nc.bin_off); (void)hipFree(e->nc.bin_idx);
+    (void)hipFree(e->nc.tw_gh); (void)hipFree(e->nc.tw_gw);
+    (void)hipFree(e->nc_grid); (void)hipFree(e->nc_samp); (void)hipFree(e->nc_y); (void)hipFree(e->nc_w); (void)hipFree(e->nc_mpart);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     delete e;
@@ -814,6 +881,7 @@ int pnp_reset(pnp_handle e, const float* x0, const float* y0, const uint8_t* mas
     PNP_ON_DEVICE(e);
     e->mask_n = mask_n;
     e->mc_coils = 0;                                       // back to the single-coil stage
+    e->nc_on = false;
     HIP_TRY(launch_reset((const float2*)x0, (const float2*)y0, mask, mask_n, x, (float2*)z, (float2*)u, e->d_y0s,
                          e->d_masks, e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
     e->reset_done = true;
@@ -829,6 +897,7 @@ int pnp_set_kspace(pnp_handle e, const float* y0, const uint8_t* mask, int mask_
     PNP_ON_DEVICE(e);
     e->mask_n = mask_n;
     e->mc_coils = 0;                                       // back to the single-coil stage
+    e->nc_on = false;
     HIP_TRY(launch_reset(nullptr, (const float2*)y0, mask, mask_n, nullptr, nullptr, nullptr, e->d_y0s, e->d_masks,
                          e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
     e->reset_done = true;
@@ -1062,7 +1131,12 @@ int pnp_residuals(pnp_handle e, const float* x, const float* z, const float* u, 
         HIP_TRY(launch_residual_tiles(x, (const float2*)z, (const float2*)u, (const float*)pv, pv ? (const float2*)(pv + snap.z_off()) : nullptr,
                                       pv ? (const float2*)(pv + snap.u_off()) : nullptr, part, N, H, W, s));
     }
-    if ((flags & PNP_RES_DC) && e->mc_coils > 0) {
+    if ((flags & PNP_RES_DC) && e->nc_on) {
+        // non-Cartesian mode: A x into the sample scratch, then sum_m w_m |(A x)_m - y_m|^2
+        if (int rc = nc_forward(e, nullptr, x, N, e->nc_samp, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_nufft_misfit(e->nc_samp, e->nc_y, e->nc_has_w ? e->nc_w : nullptr, e->nc, e->nc_mpart, dcpart, N, s));
+    } else if ((flags & PNP_RES_DC) && e->mc_coils > 0) {
         // multi-coil mode: the plain transforms of S_c x into the coil scratch, then sum_c ||M (FFT(S_c x) - ys_c)||^2
         int rc;
         {
@@ -1217,6 +1291,213 @@ int pnp_acquire_mc(pnp_handle e, const float* gt, const float* sens, int coils, 
     }
     return PNP_OK;
     PNP_API_END("pnp_acquire_mc")
+}
+
+// ---- non-Cartesian sampling ---------------------------------------------------------------------------
+static_assert(PNP_NUFFT_MAX_SAMPLES == kNufftMaxSamples, "the header's limit is the plan's");
+
+namespace {
+
+hipError_t nc_upload(void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+
+// the episode constants of the non-Cartesian stage: y, w, A^H W y, and optionally the iterate
+int nc_install(pnp_engine* e, const float2* x0, const float2* y, const float* w, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    const size_t M = (size_t)e->nc.m;
+    int rc;
+    if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
+    if ((rc = ws_grow(e, "non-Cartesian constants", {{(void**)&e->nc_y, &e->nc_y_cap, (size_t)N * M * sizeof(float2), false},
+                                                     {(void**)&e->nc_w, &e->nc_w_cap, w ? M * sizeof(float) : 0, false},
+                                                     {(void**)&e->nc_mpart, &e->nc_mpart_cap, (size_t)N * nufft_sample_chunks((int64_t)M) * sizeof(double), false}})))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(e->nc_y, y, (size_t)N * M * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    if (w) HIP_TRY(hipMemcpyAsync(e->nc_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
+    if ((rc = nc_adjoint(e, e->nc_y, w ? e->nc_w : nullptr, N, nullptr, nullptr, nullptr, mc_aty(e), nullptr, s))) return rc;
+    if (x0) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
+    }
+    // every launch was accepted: only now does the handle change mode (a failed call leaves the mode it had; its CG vectors are rewritten
+    // by the next install of either multi-coil or non-Cartesian constants)
+    e->nc_has_w = w != nullptr;
+    e->nc_cg = cg_iters;
+    e->nc_on = true;
+    e->mc_coils = 0;
+    e->reset_done = true;
+    return PNP_OK;
+}
+
+int nc_need_plan(const char* fn, const pnp_engine* e) {
+    return e->nc.m > 0 ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no NUFFT plan (pnp_nufft_plan)", fn);
+}
+int nc_need_mode(const char* fn, const pnp_engine* e) {
+    return e->nc_on ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle is not in non-Cartesian mode (pnp_set_kspace_nc / pnp_reset_nc)", fn);
+}
+int nc_check_cg(const char* fn, int cg_iters) {
+    if (cg_iters < 1 || cg_iters > PNP_MC_MAX_CG) return fail(PNP_ERR_INVALID, "%s: cg_iters must be 1..%d (got %d)", fn, PNP_MC_MAX_CG, cg_iters);
+    return PNP_OK;
+}
+
+}  // namespace
+
+int pnp_nufft_plan(pnp_handle e, const double* traj, int64_t m, int gh, int gw, int width, int flags) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call and leaves the handle as it was; scalar ranges first
+    if (flags != 0) return fail(PNP_ERR_INVALID, "pnp_nufft_plan: flags must be 0 (got 0x%x)", (unsigned)flags);
+    if (m < 1 || m > PNP_NUFFT_MAX_SAMPLES) return fail(PNP_ERR_INVALID, "pnp_nufft_plan: m must be 1..%lld (got %lld)", (long long)PNP_NUFFT_MAX_SAMPLES, (long long)m);
+    if (width != 4 && width != 6 && width != 8) return fail(PNP_ERR_INVALID, "pnp_nufft_plan: width must be 4, 6 or 8 (got %d)", width);
+    if (gh < 0 || gw < 0) return fail(PNP_ERR_INVALID, "pnp_nufft_plan: gh, gw must be 0 or a grid side (got %dx%d)", gh, gw);
+    if (!traj) return fail(PNP_ERR_INVALID, "pnp_nufft_plan: null traj");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_nufft_plan: null handle");
+    NufftPlan P;
+    std::string why;
+    if (!plan_nufft(e->cfg.h, e->cfg.w, gh, gw, width, traj, m, &P, &why)) return fail(PNP_ERR_INVALID, "pnp_nufft_plan: %s", why.c_str());
+    const std::vector<float2> twh = twiddle_table(P.gh), tww = twiddle_table(P.gw);
+    PNP_ON_DEVICE(e);
+    NufftDev& D = e->nc;
+    const size_t N = (size_t)e->cfg.n, G = (size_t)P.gh * P.gw, M = (size_t)P.m;
+    if (int rc = ws_grow(e, "NUFFT plan", {{(void**)&D.i0, &e->nc_i0_cap, P.i0.size() * sizeof(int32_t), false},
+                                           {(void**)&D.wts, &e->nc_wts_cap, P.wts.size() * sizeof(float), false},
+                                           {(void**)&D.cy, &e->nc_cy_cap, P.cy.size() * sizeof(float), false},
+                                           {(void**)&D.cx, &e->nc_cx_cap, P.cx.size() * sizeof(float), false},
+                                           {(void**)&D.bin_off, &e->nc_off_cap, P.bin_off.size() * sizeof(int32_t), false},
+                                           {(void**)&D.bin_idx, &e->nc_idx_cap, P.bin_idx.size() * sizeof(int32_t), false},
+                                           {(void**)&D.tw_gh, &e->nc_twh_cap, twh.size() * sizeof(float2), false},
+                                           {(void**)&D.tw_gw, &e->nc_tww_cap, tww.size() * sizeof(float2), false},
+                                           {(void**)&e->nc_grid, &e->nc_grid_cap, N * G * sizeof(float2), false},
+                                           {(void**)&e->nc_samp, &e->nc_samp_cap, N * M * sizeof(float2), false}}))
+        return rc;
+    if (D.m > 0) (void)hipDeviceSynchronize();              // no launch still reads the plan being replaced
+    // from here on the old plan is gone: its non-Cartesian constants are dropped with it
+    D.m = 0;
+    if (e->nc_on) { e->nc_on = false; e->reset_done = false; }
+    HIP_TRY(nc_upload(D.i0, P.i0.data(), P.i0.size() * sizeof(int32_t)));
+    HIP_TRY(nc_upload(D.wts, P.wts.data(), P.wts.size() * sizeof(float)));
+    HIP_TRY(nc_upload(D.cy, P.cy.data(), P.cy.size() * sizeof(float)));
+    HIP_TRY(nc_upload(D.cx, P.cx.data(), P.cx.size() * sizeof(float)));
+    HIP_TRY(nc_upload(D.bin_off, P.bin_off.data(), P.bin_off.size() * sizeof(int32_t)));
+    HIP_TRY(nc_upload(D.bin_idx, P.bin_idx.data(), P.bin_idx.size() * sizeof(int32_t)));
+    HIP_TRY(nc_upload(D.tw_gh, twh.data(), twh.size() * sizeof(float2)));
+    HIP_TRY(nc_upload(D.tw_gw, tww.data(), tww.size() * sizeof(float2)));
+    D.h = P.h; D.w = P.w; D.gh = P.gh; D.gw = P.gw; D.width = P.width; D.tiles_y = P.tiles_y; D.tiles_x = P.tiles_x;
+    D.m = P.m;
+    return PNP_OK;
+    PNP_API_END("pnp_nufft_plan")
+}
+
+int64_t pnp_nufft_samples(pnp_handle e) { return e ? e->nc.m : 0; }
+
+int pnp_nufft_grid(pnp_handle e, int* gh, int* gw) {
+    PNP_API_BEGIN
+    if (!e || !gh || !gw) return fail(PNP_ERR_INVALID, "pnp_nufft_grid: null argument");
+    if (int rc = nc_need_plan("pnp_nufft_grid", e)) return rc;
+    *gh = e->nc.gh; *gw = e->nc.gw;
+    return PNP_OK;
+    PNP_API_END("pnp_nufft_grid")
+}
+
+int pnp_nufft_forward(pnp_handle e, const float* img, int batch, float* samples, void* stream) {
+    PNP_API_BEGIN
+    if (batch < 1) return fail(PNP_ERR_INVALID, "pnp_nufft_forward: batch must be 1..n (got %d)", batch);
+    if (!img) return fail(PNP_ERR_INVALID, "pnp_nufft_forward: null img");
+    if (!samples) return fail(PNP_ERR_INVALID, "pnp_nufft_forward: null samples");
+    if (img == samples) return fail(PNP_ERR_INVALID, "pnp_nufft_forward: samples must not alias img");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_nufft_forward: null handle");
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "pnp_nufft_forward: batch must be 1..n=%d (got %d)", e->cfg.n, batch);
+    if (int rc = nc_need_plan("pnp_nufft_forward", e)) return rc;
+    PNP_ON_DEVICE(e);
+    return nc_forward(e, (const float2*)img, nullptr, batch, (float2*)samples, (hipStream_t)stream);
+    PNP_API_END("pnp_nufft_forward")
+}
+
+int pnp_nufft_adjoint(pnp_handle e, const float* samples, const float* weights, int batch, float* img, void* stream) {
+    PNP_API_BEGIN
+    if (batch < 1) return fail(PNP_ERR_INVALID, "pnp_nufft_adjoint: batch must be 1..n (got %d)", batch);
+    if (!samples) return fail(PNP_ERR_INVALID, "pnp_nufft_adjoint: null samples");
+    if (!img) return fail(PNP_ERR_INVALID, "pnp_nufft_adjoint: null img");
+    if (img == samples || (const float*)img == weights) return fail(PNP_ERR_INVALID, "pnp_nufft_adjoint: img must not alias samples or weights");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_nufft_adjoint: null handle");
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "pnp_nufft_adjoint: batch must be 1..n=%d (got %d)", e->cfg.n, batch);
+    if (int rc = nc_need_plan("pnp_nufft_adjoint", e)) return rc;
+    PNP_ON_DEVICE(e);
+    return nc_adjoint(e, (const float2*)samples, weights, batch, nullptr, nullptr, nullptr, (float2*)img, nullptr, (hipStream_t)stream);
+    PNP_API_END("pnp_nufft_adjoint")
+}
+
+int pnp_set_kspace_nc(pnp_handle e, const float* y, const float* w, int cg_iters, void* stream) {
+    PNP_API_BEGIN
+    if (int rc = nc_check_cg("pnp_set_kspace_nc", cg_iters)) return rc;
+    if (!y) return fail(PNP_ERR_INVALID, "pnp_set_kspace_nc: null y");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_set_kspace_nc: null handle");
+    if (int rc = nc_need_plan("pnp_set_kspace_nc", e)) return rc;
+    PNP_ON_DEVICE(e);
+    return nc_install(e, nullptr, (const float2*)y, w, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    PNP_API_END("pnp_set_kspace_nc")
+}
+
+int pnp_reset_nc(pnp_handle e, const float* x0, const float* y, const float* w, int cg_iters, float* x, float* z, float* u, void* stream) {
+    PNP_API_BEGIN
+    if (int rc = nc_check_cg("pnp_reset_nc", cg_iters)) return rc;
+    if (!x0) return fail(PNP_ERR_INVALID, "pnp_reset_nc: null x0");
+    if (!y) return fail(PNP_ERR_INVALID, "pnp_reset_nc: null y");
+    if (!x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_reset_nc: null x, z or u");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_reset_nc: null handle");
+    if (int rc = nc_need_plan("pnp_reset_nc", e)) return rc;
+    PNP_ON_DEVICE(e);
+    return nc_install(e, (const float2*)x0, (const float2*)y, w, cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
+    PNP_API_END("pnp_reset_nc")
+}
+
+int pnp_nc_cg_residual(pnp_handle e, float* out, void* stream) {
+    PNP_API_BEGIN
+    if (!e || !out) return fail(PNP_ERR_INVALID, "pnp_nc_cg_residual: null argument");
+    if (int rc = nc_need_mode("pnp_nc_cg_residual", e)) return rc;
+    PNP_ON_DEVICE(e);
+    Prof p(e, (hipStream_t)stream, PROF_OTHER, -1);
+    HIP_TRY(launch_sense_cgres(e->mc_sc, out, e->cfg.n, (hipStream_t)stream));
+    return PNP_OK;
+    PNP_API_END("pnp_nc_cg_residual")
+}
+
+int pnp_nc_normal(pnp_handle e, const float* pv, const float* mu, float* q, void* stream) {
+    PNP_API_BEGIN
+    if (!e || !pv || !mu || !q) return fail(PNP_ERR_INVALID, "pnp_nc_normal: null argument");
+    if (pv == q) return fail(PNP_ERR_INVALID, "pnp_nc_normal: p and q must not alias");
+    if (int rc = nc_need_mode("pnp_nc_normal", e)) return rc;
+    PNP_ON_DEVICE(e);
+    return nc_normal(e, (const float2*)pv, mu, nullptr, (float2*)q, (hipStream_t)stream);
+    PNP_API_END("pnp_nc_normal")
+}
+
+int pnp_acquire_nc(pnp_handle e, const float* gt, const float* dcf, double sigma_n, uint64_t seed, int flags, float* y, float* aty0, float* x0,
+                   void* stream) {
+    PNP_API_BEGIN
+    // every rejection happens before any HIP call, and leaves the outputs untouched
+    if (flags != 0) return fail(PNP_ERR_INVALID, "pnp_acquire_nc: flags must be 0 (got 0x%x)", (unsigned)flags);
+    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "pnp_acquire_nc: sigma_n must be finite and >= 0 (got %g)", sigma_n);
+    if (!gt) return fail(PNP_ERR_INVALID, "pnp_acquire_nc: null gt");
+    if (!y) return fail(PNP_ERR_INVALID, "pnp_acquire_nc: null y");
+    if (!e) return fail(PNP_ERR_INVALID, "pnp_acquire_nc: null handle");
+    if (int rc = nc_need_plan("pnp_acquire_nc", e)) return rc;
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = nc_forward(e, nullptr, gt, N, (float2*)y, s))) return rc;
+    if (sigma_n != 0.0) {                                   // a noiseless acquisition draws nothing and keeps the forward's own bits
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_nufft_noise((float2*)y, sigma_n, seed, e->nc, N, s));
+    }
+    if (!aty0 && !x0) return PNP_OK;
+    float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the image goes to the data-fidelity stage's scratch plane
+    if ((rc = nc_adjoint(e, (const float2*)y, dcf, N, nullptr, nullptr, nullptr, a, nullptr, s))) return rc;
+    if (x0) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
+    }
+    return PNP_OK;
+    PNP_API_END("pnp_acquire_nc")
 }
 
 int pnp_estimate_sens(pnp_handle e, const float* y0, int coils, int acs_h, int acs_w, int window, double thresh, int flags, float* sens,

@@ -357,4 +357,34 @@ hipError_t launch_haar_ti_down(HaarArgs a, int N, hipStream_t s);    // ONE leve
 hipError_t launch_haar_ti_up(HaarArgs a, int N, hipStream_t s);      // ONE level up: (a_src, r_src) -> r_dst, or out at level 1 (out must not be v)
 hipError_t launch_haar_ortho(HaarArgs a, int N, hipStream_t s);      // the whole ORTHO operator; out may alias v
 
+// ---- non-Cartesian sampling (nufft_kernels.hip; the plan: nufft_plan.h) -------------------------------
+// The uploaded plan: every pointer is device memory, laid out as NufftPlan's vectors
+struct NufftDev {
+    int h = 0, w = 0, gh = 0, gw = 0, width = 0, tiles_y = 0, tiles_x = 0;
+    int64_t m = 0;           // 0: no plan
+    int* i0 = nullptr;       // [2][M]
+    float* wts = nullptr;    // [2 J][M]
+    float* cy = nullptr;     // [h]
+    float* cx = nullptr;     // [w]
+    int* bin_off = nullptr;  // [tiles + 1]
+    int* bin_idx = nullptr;
+    float2* tw_gh = nullptr; // twiddles of the grid's sides
+    float2* tw_gw = nullptr;
+};
+// grid [batch, gh, gw] = the zero-padded (cy cx) . image; src complex [batch, h, w], or src_real != nullptr: a real image, no complex copy
+hipError_t launch_nufft_pad(const float2* src, const float* src_real, const NufftDev& P, float2* grid, int batch, hipStream_t s);
+// q = (cy cx) . crop(grid) (+ mu pv); partial ([batch, pixel_chunks, 2], column 0) = Re<pv, q> per chunk, as launch_sense_combine; pv, mu, tact,
+// partial may be nullptr
+hipError_t launch_nufft_crop(const float2* grid, const NufftDev& P, const float2* pv, const float* mu, const float* tact, float2* q, double* partial,
+                             int batch, hipStream_t s);
+hipError_t launch_nufft_interp(const float2* grid, const NufftDev& P, float2* out, int batch, hipStream_t s);   // out: [batch, M]
+// grid = the spread of w . y (w: [M] or nullptr), every grid point written; one workgroup per (tile, slice), no atomics
+hipError_t launch_nufft_grid(const float2* y, const float* w, const NufftDev& P, float2* grid, int batch, hipStream_t s);
+int nufft_sample_chunks(int64_t m);   // workgroups (= partials) per slice of the misfit pass
+// partial: [N, nufft_sample_chunks(M)]; dcpartial: [N, pixel_chunks(h, w)] = (sum_m w_m |a - y|^2, 0, ..): launch_residual_reduce's DC input
+hipError_t launch_nufft_misfit(const float2* a, const float2* y, const float* w, const NufftDev& P, double* partial, double* dcpartial, int N,
+                               hipStream_t s);
+// y [N, M] += sigma (g_re + i g_im): pnp_acquire's counter hash of (seed + n, 9001 / 9003, m)
+hipError_t launch_nufft_noise(float2* y, double sigma, uint64_t seed, const NufftDev& P, int N, hipStream_t s);
+
 }  // namespace pnp

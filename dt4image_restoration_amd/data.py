@@ -36,6 +36,13 @@ def save_mat(path: str, problem: Dict[str, np.ndarray], index: int = 0) -> None:
     """Write slice `index` of a `synthetic.make_problem` dict in the reference's `.mat` layout.  `x0` is stored as the
     raw zero-filled reconstruction (= ATy0, negative pixels included), as a TFPnP-style file holds it; the loader clips."""
     from scipy.io import savemat
+    if "traj" in problem:                                    # a non-Cartesian acquisition: samples [1,M,2], the trajectory and weights, no mask
+        nc = {"x0": problem["ATy0"][index], "y0": problem["y0"][index], "ATy0": problem["ATy0"][index], "gt": problem["gt"][index],
+              "traj": problem["traj"]}
+        if problem.get("dcf") is not None:
+            nc["dcf"] = problem["dcf"]
+        savemat(path, nc)
+        return
     savemat(path, {"x0": problem["ATy0"][index], "y0": problem["y0"][index], "ATy0": problem["ATy0"][index],
                    "mask": problem["mask"].astype(np.uint8), "gt": problem["gt"][index]})
 

@@ -118,6 +118,125 @@ class PnPEngine:
         _lib.check(self.lib.pnp_mc_normal(self._h, p.data_ptr(), mu.data_ptr(), q.data_ptr(), self._stream()), "pnp_mc_normal")
         return q
 
+    # -- non-Cartesian sampling ------------------------------------------------------------
+    def nufft_plan(self, traj, grid: Optional[Tuple[int, int]] = None, width: int = 6) -> None:
+        """Plan the NUFFT pair for one trajectory shared by all slices (pnp_nufft_plan): traj [M,2] = (ky, kx) in cycles per pixel,
+        each in [-0.5, 0.5] (array or tensor; taken as float64 on the host); grid = (gh, gw) or None for the smallest accepted
+        1.25x grid; width = the kernel width J in {4, 6, 8}.  A new plan replaces the old one and drops non-Cartesian constants."""
+        t = np.ascontiguousarray(traj.detach().cpu().numpy() if isinstance(traj, torch.Tensor) else traj, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != 2:
+            raise ValueError(f"traj: expected [M,2], got {t.shape}")
+        gh, gw = (0, 0) if grid is None else (int(grid[0]), int(grid[1]))
+        self._nufft_key = None
+        _lib.check(self.lib.pnp_nufft_plan(self._h, t.ctypes.data, t.shape[0], gh, gw, int(width), 0), "pnp_nufft_plan")
+        self._nufft_key = (t.copy(), gh, gw, int(width), traj)
+        self.live_episode = 0        # non-Cartesian constants are dropped with their plan: whoever binds episodes re-installs
+
+    _nufft_key = None            # (a copy of traj, gh, gw, width, the object traj was given as) of the live plan
+
+    def nufft_planned(self, traj, grid: Optional[Tuple[int, int]] = None, width: int = 6) -> bool:
+        """Whether the live plan was made from exactly these arguments (so that a caller binding episodes need not re-plan).  The very
+        object the plan was made from (an episode's own trajectory tensor, step after step) is recognised without looking at its values."""
+        k = self._nufft_key
+        if k is not None and k[4] is traj:
+            return k[1:4] == ((0, 0) if grid is None else (int(grid[0]), int(grid[1]))) + (int(width),)
+        t = np.asarray(traj.detach().cpu().numpy() if isinstance(traj, torch.Tensor) else traj, dtype=np.float64)
+        gh, gw = (0, 0) if grid is None else (int(grid[0]), int(grid[1]))
+        return k is not None and k[1:4] == (gh, gw, int(width)) and k[0].shape == t.shape and bool(np.array_equal(k[0], t))
+
+    @property
+    def nufft_samples(self) -> int:
+        """M of the handle's NUFFT plan; 0 without one."""
+        return int(self.lib.pnp_nufft_samples(self._h))
+
+    @property
+    def nufft_grid(self) -> Tuple[int, int]:
+        gh, gw = C.c_int(), C.c_int()
+        _lib.check(self.lib.pnp_nufft_grid(self._h, C.byref(gh), C.byref(gw)), "pnp_nufft_grid")
+        return gh.value, gw.value
+
+    def _batch_of(self, t: torch.Tensor, per: int, name: str) -> int:
+        if per < 1 or t.numel() % per or not 1 <= t.numel() // per <= self.n:
+            raise ValueError(f"{name}: expected 1..{self.n} slices of {per} elements, got {tuple(t.shape)}")
+        return t.numel() // per
+
+    def nufft_forward(self, img: torch.Tensor) -> torch.Tensor:
+        """samples complex64 [B,M] = A img (pnp_nufft_forward); img complex64 [B,H,W] (or [B,1,H,W]), B <= N."""
+        b = self._batch_of(img, self.h * self.w, "img")
+        self._chk(img, torch.complex64, img.numel(), "img")
+        out = torch.empty((b, self.nufft_samples), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_nufft_forward(self._h, img.data_ptr(), b, out.data_ptr(), self._stream()), "pnp_nufft_forward")
+        return out
+
+    def nufft_adjoint(self, samples: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """img complex64 [B,H,W] = A^H (weights . samples) (pnp_nufft_adjoint); samples complex64 [B,M], weights float32 [M] or None."""
+        m = self.nufft_samples
+        b = self._batch_of(samples, m, "samples")
+        self._chk(samples, torch.complex64, samples.numel(), "samples")
+        if weights is not None:
+            self._chk(weights, torch.float32, m, "weights")
+        out = torch.empty((b, self.h, self.w), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_nufft_adjoint(self._h, samples.data_ptr(), weights.data_ptr() if weights is not None else None, b,
+                                              out.data_ptr(), self._stream()), "pnp_nufft_adjoint")
+        return out
+
+    def _nc_args(self, y: torch.Tensor, w: Optional[torch.Tensor]):
+        m = self.nufft_samples
+        self._chk(y, torch.complex64, self.n * m if m else y.numel(), "y")     # without a plan the library reports the state error
+        if w is not None:
+            self._chk(w, torch.float32, m, "w")
+        return y.data_ptr(), (w.data_ptr() if w is not None else None)
+
+    def reset_nc(self, x0: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor] = None,
+                 cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Install the non-Cartesian constants (y complex64 [N,M] or [N,1,M], w float32 [M] or None) and start an episode from x0
+        complex64 [N,1,H,W] (pnp_reset_nc).  Returns fresh (x f32, z c64, u c64); steps then solve the k-space subproblem by `cg_iters`
+        CG iterations on the NUFFT normal operator."""
+        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
+        yp, wp = self._nc_args(y, w)
+        x = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device)
+        z = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+        u = torch.empty_like(z)
+        _lib.check(self.lib.pnp_reset_nc(self._h, x0.data_ptr(), yp, wp, int(cg_iters), x.data_ptr(), z.data_ptr(), u.data_ptr(),
+                                         self._stream()), "pnp_reset_nc")
+        self.live_episode = _next_episode()
+        return x, z, u
+
+    def set_kspace_nc(self, y: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0, cg_iters: int = 8) -> None:
+        """Re-install the non-Cartesian constants of another episode without touching any iterate (pnp_set_kspace_nc)."""
+        yp, wp = self._nc_args(y, w)
+        _lib.check(self.lib.pnp_set_kspace_nc(self._h, yp, wp, int(cg_iters), self._stream()), "pnp_set_kspace_nc")
+        self.live_episode = episode or _next_episode()
+
+    def nc_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+        """q = A^H W A p + mu p with the installed non-Cartesian constants (pnp_nc_normal); p complex64 [N,1,H,W], mu float32 [N]."""
+        self._chk(p, torch.complex64, self.n * self.h * self.w, "p"); self._chk(mu, torch.float32, self.n, "mu")
+        q = torch.empty_like(p)
+        _lib.check(self.lib.pnp_nc_normal(self._h, p.data_ptr(), mu.data_ptr(), q.data_ptr(), self._stream()), "pnp_nc_normal")
+        return q
+
+    def nc_cg_residual(self) -> torch.Tensor:
+        """float32 [N]: the relative residual the CG solve of the last step ended with (pnp_nc_cg_residual; non-Cartesian mode only)."""
+        out = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pnp_nc_cg_residual(self._h, out.data_ptr(), self._stream()), "pnp_nc_cg_residual")
+        return out
+
+    def acquire_nc(self, gt: torch.Tensor, sigma_n: float, seed: int,
+                   dcf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Simulated non-Cartesian acquisition on the planned trajectory (pnp_acquire_nc): gt float32 [N,1,H,W]; returns
+        (y complex64 [N,M], aty0 = A^H (dcf . y) complex64 [N,1,H,W], x0 = max(aty0, 0))."""
+        gt = self._chk(gt, torch.float32, self.n * self.h * self.w, "gt")
+        m = self.nufft_samples
+        if dcf is not None:
+            self._chk(dcf, torch.float32, m, "dcf")
+        y = torch.empty((self.n, max(m, 1)), dtype=torch.complex64, device=self.device)
+        aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+        x0 = torch.empty_like(aty0)
+        _lib.check(self.lib.pnp_acquire_nc(self._h, gt.data_ptr(), dcf.data_ptr() if dcf is not None else None, float(sigma_n),
+                                           int(seed) & (2 ** 64 - 1), 0, y.data_ptr(), aty0.data_ptr(), x0.data_ptr(), self._stream()),
+                   "pnp_acquire_nc")
+        return y, aty0, x0
+
     # -- hot path --------------------------------------------------------------------------
     def reset(self, x0: torch.Tensor, y0: torch.Tensor, mask: torch.Tensor, sens: Optional[torch.Tensor] = None,
               cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

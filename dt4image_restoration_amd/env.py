@@ -38,9 +38,12 @@ def _as_complex(t: torch.Tensor) -> torch.Tensor:
 
 class PnPEnv:
     def __init__(self, max_episode_step: int, denoiser: UNetDenoiser2D, device_type,
-                 no_ref_scorer: Optional[Callable[[torch.Tensor], float]] = None, replica: int = 0, cg_iters: int = 8) -> None:
+                 no_ref_scorer: Optional[Callable[[torch.Tensor], float]] = None, replica: int = 0, cg_iters: int = 8,
+                 nufft_width: int = 6, nufft_grid=None) -> None:
         self.max_episode_step = max_episode_step
-        self.cg_iters = int(cg_iters)           # multi-coil episodes: conjugate-gradient iterations per step
+        self.cg_iters = int(cg_iters)           # multi-coil and non-Cartesian episodes: conjugate-gradient iterations per step
+        self.nufft_width = int(nufft_width)     # non-Cartesian episodes (data["traj"]): the kernel width and the grid (None: the default)
+        self.nufft_grid = None if nufft_grid is None else (int(nufft_grid[0]), int(nufft_grid[1]))
         self.denoiser = denoiser.to(device_type)
         self.no_ref_model = no_ref_scorer
         self._engine: Optional[PnPEngine] = None
@@ -50,7 +53,8 @@ class PnPEnv:
     def fork(self, replica: int) -> "PnPEnv":
         """Another env on the same denoiser weights whose engines are replicas of their own (own workspace, own k-space
         constants): two sub-batches of one job can then be stepped concurrently on two streams."""
-        return PnPEnv(self.max_episode_step, self.denoiser, self._device_type, self.no_ref_model, replica=replica, cg_iters=self.cg_iters)
+        return PnPEnv(self.max_episode_step, self.denoiser, self._device_type, self.no_ref_model, replica=replica, cg_iters=self.cg_iters,
+                      nufft_width=self.nufft_width, nufft_grid=self.nufft_grid)
 
     # ---- engine management ------------------------------------------------------------------
     def _engine_for(self, n: int, h: int, w: int, device: torch.device) -> PnPEngine:
@@ -68,6 +72,8 @@ class PnPEnv:
         h, w = x0.shape[-2:]
         n = x0.numel() // (h * w)
         x0 = x0.reshape(n, 1, h, w).to(device).contiguous()
+        if hasattr(data, "get") and data.get("traj") is not None:
+            return self._reset_nc(data, x0, n, h, w, device)
         sens = data.get("sens") if hasattr(data, "get") else None
         if sens is not None:                    # a multi-coil problem: sens [C,H,W] or [N,C,H,W], y0 with a coil axis
             sens = torch.as_tensor(sens)
@@ -92,14 +98,44 @@ class PnPEnv:
                             "T": torch.zeros(n, dtype=torch.float32, device=device),
                             "complex_y0": data["y0"], "_episode": eng.live_episode, "sens": sens})
 
+    def _plan_nc(self, eng: PnPEngine, traj) -> None:
+        """The engine's NUFFT plan is the one of this trajectory: re-planned only when it differs from the live plan."""
+        if not eng.nufft_planned(traj, self.nufft_grid, self.nufft_width):
+            eng.nufft_plan(traj, grid=self.nufft_grid, width=self.nufft_width)
+
+    def _reset_nc(self, data, x0: torch.Tensor, n: int, h: int, w: int, device) -> "OrderedDict[str, torch.Tensor]":
+        """A non-Cartesian episode: data["traj"] float64 [M,2], y0 [N,1,M,2] (or complex [N,M]), optional data["dcf"] float32 [M]."""
+        if data.get("sens") is not None:
+            raise ValueError("PnPEnv.reset: a non-Cartesian episode is single-coil (traj with sens is not supported)")
+        traj = torch.as_tensor(data["traj"]).to(torch.float64).cpu().reshape(-1, 2).contiguous()      # (the caller's own tensor when it is one)
+        m = traj.shape[0]
+        y0 = _as_complex(torch.as_tensor(data["y0"])).reshape(n, m).to(device).contiguous()
+        dcf = data.get("dcf")
+        dcf = None if dcf is None else torch.as_tensor(dcf).to(device, torch.float32).reshape(m).contiguous()
+        gt = torch.as_tensor(data["gt"]).to(device).float()
+        eng = self._engine_for(n, h, w, device)
+        self._plan_nc(eng, traj)
+        x, z, u = eng.reset_nc(x0, y0, dcf, cg_iters=self.cg_iters)
+        aty0 = torch.as_tensor(data["ATy0"])[..., 0] if "ATy0" in data else None
+        return OrderedDict({"x": x, "y0": y0, "z": z, "u": u, "mask": None, "gt": gt, "ATy0": aty0,
+                            "T": torch.zeros(n, dtype=torch.float32, device=device),
+                            "complex_y0": data["y0"], "_episode": eng.live_episode, "sens": None, "traj": traj, "dcf": dcf})
+
     def _bind_episode(self, eng: PnPEngine, states) -> None:
         """Make the engine's k-space constants those of `states` (env.py:88-90 reads y0 / mask from the dict)."""
         ep = states.get("_episode", 0)
+        if states.get("traj") is not None and not eng.nufft_planned(states["traj"], self.nufft_grid, self.nufft_width):
+            eng.nufft_plan(states["traj"], grid=self.nufft_grid, width=self.nufft_width)      # (drops the live episode)
         if ep and ep == eng.live_episode:
             return
         if not ep:                              # a state dict built by hand the reference's way
             ep = states["_episode"] = _next_episode()
         n, h, w = eng.n, eng.h, eng.w
+        if states.get("traj") is not None:
+            y = states["y0"]
+            y = (y if y.is_complex() else _as_complex(y)).reshape(n, -1).to(eng.device).contiguous()
+            eng.set_kspace_nc(y, states.get("dcf"), episode=ep, cg_iters=self.cg_iters)
+            return
         sens = states.get("sens")
         coils = 1 if sens is None else sens.shape[-3]
         y0 = _as_complex(states["y0"]).reshape(n, coils, h, w).to(eng.device).contiguous()

@@ -114,6 +114,43 @@ def make_problem(n: int, h: int, w: int, accel: float = 4.0, sigma_n: float = 10
     return {"x0": x0, "y0": y0, "ATy0": aty0, "mask": mask, "gt": gt, "x0_raw": aty0[..., 0].copy()}
 
 
+def ndft_np(traj: np.ndarray, x: np.ndarray, adjoint_shape=None) -> np.ndarray:
+    """The exact non-Cartesian operator of include/pnpadmm.h in float64: (A x)_m = (1 / sqrt(h w)) sum_q x[q] exp(-2 pi i (ky qy + kx qx)),
+    q centred; x [..., h, w] -> [..., M].  With adjoint_shape = (h, w): A^H, x [..., M] -> [..., h, w].  O(M h w): small sizes only."""
+    traj = np.asarray(traj, dtype=np.float64)
+    h, w = adjoint_shape if adjoint_shape is not None else x.shape[-2:]
+    sgn = 2j if adjoint_shape is not None else -2j
+    ey = np.exp(sgn * math.pi * traj[:, 0:1] * (np.arange(h) - h // 2))
+    ex = np.exp(sgn * math.pi * traj[:, 1:2] * (np.arange(w) - w // 2))
+    x = np.asarray(x, dtype=np.complex128)
+    if adjoint_shape is not None:
+        return np.einsum("my,...m,mx->...yx", ey, x, ex, optimize=True) / math.sqrt(h * w)
+    return np.einsum("my,...yx,mx->...m", ey, x, ex, optimize=True) / math.sqrt(h * w)
+
+
+def make_problem_nc(n: int, h: int, w: int, traj: np.ndarray, dcf: np.ndarray = None, sigma_n: float = 10.0 / 255.0, seed: int = 1234,
+                    first_slice: int = 0) -> Dict[str, np.ndarray]:
+    """`make_problem` for a non-Cartesian trajectory, by the exact NDFT in float64 (meant for small sizes): y0 float32 [n,1,M,2] with
+    y = A gt + sigma_n noise (the counter hash of `make_problem` indexed by the sample m), ATy0 = A^H (dcf y) and x0 = its clip at 0,
+    float32 [n,1,h,w,2]; gt, x0_raw as in `make_problem`; traj float64 [M,2], dcf float32 [M] or None."""
+    traj = np.asarray(traj, dtype=np.float64)
+    m = traj.shape[0]
+    d = None if dcf is None else np.asarray(dcf, dtype=np.float32)
+    gt = np.empty((n, 1, h, w), dtype=np.float32)
+    y0 = np.empty((n, 1, m, 2), dtype=np.float32)
+    aty0 = np.empty((n, 1, h, w, 2), dtype=np.float32)
+    for i in range(n):
+        s = seed + first_slice + i
+        g = phantom(h, w, s)
+        y = ndft_np(traj, g) + (_gauss(s, 9001, m) + 1j * _gauss(s, 9003, m)) * sigma_n
+        a = ndft_np(traj, y if d is None else y * d.astype(np.float64), adjoint_shape=(h, w))
+        gt[i, 0] = g
+        y0[i, 0, :, 0], y0[i, 0, :, 1] = y.real, y.imag
+        aty0[i, 0, ..., 0], aty0[i, 0, ..., 1] = a.real, a.imag
+    x0 = np.clip(aty0, 0.0, None)
+    return {"x0": x0, "y0": y0, "ATy0": aty0, "gt": gt, "x0_raw": aty0[..., 0].copy(), "traj": traj, "dcf": d}
+
+
 def param_table(n: int, iters: int, seed: int = 77):
     """Seeded per-slice (mu_t, sigma_t) schedule standing in for DT-chosen parameters at
     sizes the 128x128-only policy cannot see: mu in (0.05,0.6), sigma_d

@@ -370,6 +370,84 @@ int pnp_mc_normal(pnp_handle h, const float* p, const float* mu, float* q, void*
 int pnp_acquire_mc(pnp_handle h, const float* gt, const float* sens, int coils, int sens_n, const uint8_t* mask, int mask_n, double sigma_n,
                    uint64_t seed, int flags, float* y0, float* aty0, float* x0, void* stream);
 
+/* ---- non-Cartesian sampling: NUFFT pair and CG data fidelity ------------------------------------
+ * The reference's "radial" acquisition is a radial MASK rasterised on the Cartesian grid.  A real radial, spiral or rosette acquisition has
+ * its samples off the grid; this section is the single-coil stage for such data.  One trajectory is shared by all slices of a handle.
+ *
+ * COORDINATES AND THE EXACT OPERATOR.  Sample m has the frequency (ky, kx) in cycles per pixel, each in [-0.5, 0.5]; with the centred pixel
+ * coordinates qy = iy - H/2, qx = ix - W/2
+ *     (A x)_m = (1 / sqrt(H W)) sum_q x[q] exp(-2 pi i (ky qy + kx qx))
+ * so that the sample at ky = (j - H/2) / H, kx = (l - W/2) / W is bin (j, l) of pnp_fft2c.
+ * GRID.  The operator is evaluated on an oversampled gh x gw grid: each side is a side the k-space stage accepts with 4 gh >= 5 H and
+ * 4 gw >= 5 W; 0 selects the smallest such side (64 -> 80, 128 -> 160, 256 -> 320, 320 -> 400, 512 -> 640, 640 -> 800, 800 -> 1024; 16 -> 32,
+ * 32 -> 64, 80 -> 128, 160 -> 256, 400 -> 512).  H and W are therefore at most 800: a 1024 side is refused with a message.  The oversampling
+ * ratio is per axis, sigma = g / side.
+ * KERNEL.  The "exponential of semicircle" kernel of width J in {4, 6, 8} grid points,
+ *     phi(t) = exp(beta (sqrt(1 - (2 t / J)^2) - 1)) for |2 t / J| < 1, 0 elsewhere;   beta = 2.30 J when sigma == 2, else 0.97 pi J (1 - 1 / (2 sigma)).
+ * FOOTPRINT AND WEIGHTS of one sample, per axis: the grid coordinate is u = k g + g/2; the footprint starts at i0 = ceil(u - J/2) and covers
+ * the points i0 .. i0 + J - 1 taken mod g (the grid is periodic); the weights phi(u - i) are formed in float64 on the host and rounded to
+ * float32 once.
+ * DECONVOLUTION.  c[q] = 1 / phihat(q), phihat(q) = 2 int_0^{J/2} phi(t) cos(2 pi q t / g) dt by a 128-node Gauss-Legendre quadrature in
+ * float64, rounded to float32 once; the scale sqrt(gh gw / (H W)) between the grid's orthonormal transform and 1 / sqrt(H W) is folded in
+ * (per axis: cy[qy] = sqrt(gh / H) / phihat_y(qy)).
+ * FORWARD (pnp_nufft_forward): the image times cy[qy] cx[qx] (the float32 product of the two factors), zero-padded, centred, into the grid;
+ * the centred forward transform of pnp_fft2c on the grid (the engine's row and column passes with the plan's own twiddles); then per sample
+ * t_iy = sum over ix ascending of wx[ix] X[iy][ix] and acc = sum over iy ascending of wy[iy] t_iy, real and imaginary part each an fma chain
+ * from +0.
+ * ADJOINT (pnp_nufft_adjoint): the conjugate transpose of the forward as implemented - the same float32 weights and factors.  v_m = w_m y_m
+ * (w optional, NULL = 1) is spread onto the grid, the centred inverse transform runs, the grid is cropped and multiplied by cy cx.
+ * SPREADING ORDER.  The value of a grid point is ONE fma chain from +0 over the samples whose footprint contains it, in ascending sample
+ * index, of the terms (v_m wy) * wx (v_m wy rounded first).  A sample cannot reach a point twice through the wrap (J <= 8 < 32 <= g).  There
+ * are no atomics: the bits depend on (plan, input) only - not on N, the slice's place in the batch, the stream, or the workgroup that owns
+ * the point.  (Samples are assumed finite: a non-finite sample spoils the whole gridding tiles its footprint meets.)
+ *
+ * pnp_nufft_plan: SETUP-TIME SEMANTICS, as pnp_load_unet_weights - it builds the plan on the host, uploads it and allocates inside the call,
+ * all-or-nothing through the handle's workspace (on PNP_ERR_NOMEM the handle keeps the plan and the workspace it had), counted by
+ * pnp_workspace_bytes: the grid buffer 8 n gh gw, the sample buffer 8 n M, and the plan itself: 8 M (footprint starts) + 8 J M (weights) +
+ * 4 (H + W) (factors) + 8 (gh + gw) (twiddles) + 4 (gh gw / 256 + 1) + 4 B (the gridding bins: B <= 4 M entries).  A later plan allocates
+ * only what it needs beyond the plan before it, and waits for the device.  One plan per handle: a new plan replaces the old one.  If
+ * non-Cartesian constants were installed they are dropped - the handle then has NO episode constants, and pnp_step / pnp_prox_dual give
+ * PNP_ERR_STATE until some are installed; Cartesian and multi-coil constants are not touched.
+ *   traj : HOST float64 [M][2] = (ky, kx), every coordinate finite and in [-0.5, 0.5];   m : 1..PNP_NUFFT_MAX_SAMPLES
+ *   gh, gw : grid sides or 0;   width : J in {4, 6, 8};   flags : reserved, must be 0
+ * pnp_nufft_samples: M of the handle's plan, 0 without one (and on NULL).  pnp_nufft_grid: the plan's grid sides (PNP_ERR_STATE without one).
+ * pnp_nufft_forward / pnp_nufft_adjoint: img DEVICE complex64 [batch,H,W], samples DEVICE complex64 [batch,M], weights DEVICE float32 [M] or
+ * NULL; 1 <= batch <= n; no input may alias an output.  Without a plan: PNP_ERR_STATE.  They use the plan's grid buffer: calls on one handle
+ * are stream-ordered.
+ *
+ * DATA FIDELITY.  pnp_set_kspace_nc / pnp_reset_nc install y (complex64 [N,M]), w (float32 [M] or NULL = 1; e.g. density compensation) and
+ * aty = A^H W y, and put the handle in non-Cartesian mode by the rule of the multi-coil section: the stage that runs is the one whose
+ * constants were installed LAST (pnp_mc_coils stays 0 in this mode; pnp_set_kspace / pnp_reset / the _mc calls leave it).  pnp_step and
+ * pnp_prox_dual then run the multi-coil section's CG, word for word, on Nop(p) = A^H W A p + mu p and b = aty + mu (x + u): K = cg_iters
+ * fixed iterations warm-started from z, float64 scalars on the device, a frozen slice never NaN, stopped slices keep their bits,
+ * u <- u + x - z.  pnp_reset_nc also sets the iterate: x = Re(x0), z = x0, u = 0.  They copy y and w (8 n M + 4 M bytes, 8 n ceil(M / 2048)
+ * for the misfit's partial sums, and the coil workspace's coil-independent part: four vectors 8 n H W each, partial sums and scalars), with
+ * the setup-time semantics of pnp_set_kspace_mc.  The handle changes mode only after every launch of the install was accepted: a call
+ * that fails (argument error, PNP_ERR_NOMEM, a refused launch) leaves the mode and the iterate as they were.  In this mode pnp_residuals'
+ * PNP_RES_DC column is sqrt(sum_m w_m |(A x)_m - y_m|^2).
+ * pnp_nc_normal (q = Nop(p)) and pnp_nc_cg_residual are the counterparts of pnp_mc_normal and pnp_mc_cg_residual: PNP_ERR_STATE on a handle
+ * that is not in non-Cartesian mode.
+ *
+ * pnp_acquire_nc: pnp_acquire for the planned trajectory,  y = A gt + sigma_n (g_re + i g_im),  aty0 = A^H (dcf . y),  x0 = max(aty0, 0) on
+ * both planes;  gt DEVICE float32 [N,1,H,W], dcf DEVICE float32 [M] or NULL, y DEVICE complex64 [N,M], aty0, x0 complex64 [N,1,H,W] or NULL.
+ * Noise: pnp_acquire's counter hash with p = m, the streams 9001 / 9003 and seed + n; with sigma_n == 0 nothing is drawn and y equals
+ * pnp_nufft_forward's bits.  A slice's outputs depend neither on N nor on its place in the batch.  It does not change the handle's mode.
+ *
+ * Every entry point here takes any handle kind with sides the k-space stage accepts, and reports every argument error (NULLs, a count or
+ * size out of range, flags != 0, forbidden aliasing, a refused trajectory or grid) before any HIP call, leaving the outputs untouched. */
+#define PNP_NUFFT_MAX_SAMPLES (1 << 22)
+int pnp_nufft_plan(pnp_handle h, const double* traj, int64_t m, int gh, int gw, int width, int flags);
+int64_t pnp_nufft_samples(pnp_handle h);
+int pnp_nufft_grid(pnp_handle h, int* gh, int* gw);
+int pnp_nufft_forward(pnp_handle h, const float* img, int batch, float* samples, void* stream);
+int pnp_nufft_adjoint(pnp_handle h, const float* samples, const float* weights, int batch, float* img, void* stream);
+int pnp_set_kspace_nc(pnp_handle h, const float* y, const float* w, int cg_iters, void* stream);
+int pnp_reset_nc(pnp_handle h, const float* x0, const float* y, const float* w, int cg_iters, float* x, float* z, float* u, void* stream);
+int pnp_nc_cg_residual(pnp_handle h, float* out, void* stream);
+int pnp_nc_normal(pnp_handle h, const float* p, const float* mu, float* q, void* stream);
+int pnp_acquire_nc(pnp_handle h, const float* gt, const float* dcf, double sigma_n, uint64_t seed, int flags, float* y, float* aty0, float* x0,
+                   void* stream);
+
 /* Coil sensitivity maps from the fully sampled calibration (ACS) block of multi-coil k-space: the low-resolution estimate, the first stage of
  * the multi-coil path when the acquisition brings no maps (the reference restores single-coil data and has no counterpart).  Per slice n, with
  * the centred bin p = (ky, kx), dy = ky - H/2, dx = kx - W/2:
