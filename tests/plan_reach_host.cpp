@@ -24,7 +24,10 @@
 //                                    flags  0, BF16_CONVS, KEEP_STAGES, both
 //                                  and prints, per key of either level, the reaching handle of smallest N H W and, where one exists, the
 //                                  smallest whose sides both pass kspace_len_ok:
-//                                    reach T|E | <key> | n h w flags | n h w flags   (or `-`)
+//                                    reach T|E | <key> | n h w flags | n h w flags (or `-`) | <the flag sets whose handles reach it>
+//                                  then, per level and flag set, how many keys handles of that flag set ALONE reach (a reach that lost
+//                                  its flags shows here: three of the four would print 0), and a summary line:
+//                                    only T|E | <flags> | <keys>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -260,7 +263,7 @@ static int describe_stdin() {
     return 0;
 }
 
-struct Reach { long px = 0, kpx = 0; int at[4] = {}, kat[4] = {}; };
+struct Reach { long px = 0, kpx = 0; int at[4] = {}, kat[4] = {}; unsigned by = 0; };   // by: bit i = reached by a handle of flagsets[i]
 
 static int reach() {
     clear_pnp_env();
@@ -276,8 +279,10 @@ static int reach() {
                 const long px = (long)n * h * w;
                 if (px > cap) continue;
                 const bool ks = kspace_len_ok(h) && kspace_len_ok(w);
-                for (int flags : flagsets) {
-                    pnp_config cfg{n, h, w, flags, 0};
+                for (int fi = 0; fi < 4; ++fi) {
+                    const int flags = flagsets[fi];
+                    pnp_config cfg{};                              // by field name: {n, h, w, device, flags} is not the order a reader expects
+                    cfg.n = n; cfg.h = h; cfg.w = w; cfg.device = 0; cfg.flags = flags;
                     DenoiserPlan P;
                     std::string err;
                     if (!plan_denoiser(cfg, t, &P, &err)) continue;
@@ -287,6 +292,7 @@ static int reach() {
                         launch_keys(cfg, P, P.launch[i], &key[0], &key[1]);
                         for (int lv = 0; lv < 2; ++lv) {
                             Reach& r = seen[lv][key[lv]];
+                            r.by |= 1u << fi;
                             if (r.px == 0 || px < r.px) { r.px = px; r.at[0] = n; r.at[1] = h; r.at[2] = w; r.at[3] = flags; }
                             if (ks && (r.kpx == 0 || px < r.kpx)) { r.kpx = px; r.kat[0] = n; r.kat[1] = h; r.kat[2] = w; r.kat[3] = flags; }
                         }
@@ -297,8 +303,17 @@ static int reach() {
         for (const auto& kv : seen[lv]) {
             const Reach& r = kv.second;
             std::printf("reach %c | %s | %d %d %d %d | ", lv ? 'E' : 'T', kv.first.c_str(), r.at[0], r.at[1], r.at[2], r.at[3]);
-            if (r.kpx) std::printf("%d %d %d %d\n", r.kat[0], r.kat[1], r.kat[2], r.kat[3]);
-            else std::printf("-\n");
+            if (r.kpx) std::printf("%d %d %d %d |", r.kat[0], r.kat[1], r.kat[2], r.kat[3]);
+            else std::printf("- |");
+            for (int fi = 0; fi < 4; ++fi)
+                if (r.by >> fi & 1) std::printf(" %d", flagsets[fi]);
+            std::printf("\n");
+        }
+    for (int lv = 0; lv < 2; ++lv)
+        for (int fi = 0; fi < 4; ++fi) {
+            long only = 0;
+            for (const auto& kv : seen[lv]) only += kv.second.by == 1u << fi;
+            std::printf("only %c | %d | %ld\n", lv ? 'E' : 'T', flagsets[fi], only);
         }
     std::printf("plan_reach_host: %ld handles planned, %zu template-level keys, %zu edge-level keys\n", handles, seen[0].size(), seen[1].size());
     return 0;

@@ -13,7 +13,10 @@ The existing tests' cases are assembled from the parameter lists those tests use
 (Tests that compare two handles with each other, a golden file or a PSNR series only are not in the table: they cannot tell a variant
 that is wrong in both.  The switches a test sets inside its body, such as PNP_WINO_MIN_BLOCKS=1 in the F(4x4) test, are restated here.)
 NEW_SHAPES are the shapes of tests/test_gpu_variant_reach.py: default tuning, chosen - greedy set cover by N H W over the handles of the
-tool's --reach range, k-space-valid sides preferred - to run every key the existing cases leave out."""
+tool's --reach range, k-space-valid sides preferred - to run every key the existing cases leave out.
+NEW_BF16_CASES are the handles of tests/test_gpu_variant_reach_bf16.py: the bf16 variants (conv_kernels.hip with BF16=2 and the `ws`
+producer / consumer kernel of conv_bf16_kernels.hip) that everything above leaves out, chosen the same way over the BF16_CONVS and
+BF16_CONVS | KEEP_STAGES handles of the range."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -30,6 +33,21 @@ NEW_SHAPES = [
     (7, 128, 320), (8, 400, 128), (16, 400, 64), (3, 592, 272), (64, 128, 80), (6, 592, 256), (96, 80, 128), (128, 128, 64), (24, 160, 320),
 ]
 NEW_FLAGS = (KEEP_STAGES, 0)
+
+# The handles (n, h, w, flags) of tests/test_gpu_variant_reach_bf16.py, default tuning.  Greedy set cover over ALL bf16 handles of the reach
+# range (not each key's smallest alone): first the keys some k-space-valid handle reaches, over those handles, then the rest over all; a
+# handle's worth is the unrun edge keys it adds per N H W + 300,000 pixels (the constant: what a case costs whatever its size); last, an entry
+# whose keys the others run between them is dropped, so each entry runs a key no other entry does.  Sorted by N H W.
+_B, _BK = BF16_CONVS, BF16_CONVS | KEEP_STAGES
+NEW_BF16_CASES = [
+    (1, 16, 128, _B), (128, 16, 16, _B), (64, 16, 48, _B), (96, 16, 48, _B), (192, 16, 32, _BK), (3, 512, 80, _B), (128, 16, 64, _B),
+    (3, 1024, 48, _B), (96, 112, 16, _B), (6, 1024, 32, _B), (12, 1024, 16, _B), (192, 16, 64, _B), (4, 1024, 48, _B), (96, 16, 160, _BK),
+    (48, 32, 160, _B), (4, 400, 160, _B), (48, 112, 48, _BK), (128, 16, 128, _B), (8, 1024, 32, _B), (16, 1024, 16, _B), (6, 1024, 48, _B),
+    (6, 1024, 48, _BK), (24, 400, 32, _B), (24, 16, 800, _B), (32, 64, 160, _B), (96, 112, 32, _B), (24, 112, 144, _B), (12, 1024, 32, _B),
+    (192, 16, 128, _BK), (6, 1024, 64, _B), (8, 80, 640, _B), (3, 1024, 160, _B), (6, 1024, 80, _B), (6, 1024, 80, _BK), (48, 64, 160, _B),
+    (16, 1024, 32, _BK), (8, 1024, 64, _B), (4, 1024, 160, _BK), (48, 112, 128, _B), (12, 112, 528, _B), (12, 1024, 64, _BK),
+    (12, 1024, 64, _B), (12, 112, 1024, _B),
+]
 
 
 def _case(shape, flags, env, source):
@@ -92,8 +110,12 @@ def new_cases():
     return [_case(shape, flags, {}, "variant_reach") for shape in NEW_SHAPES for flags in NEW_FLAGS]
 
 
+def new_bf16_cases():
+    return [_case((n, h, w), flags, {}, "variant_reach_bf16") for n, h, w, flags in NEW_BF16_CASES]
+
+
 def all_cases():
-    return existing_cases() + new_cases()
+    return existing_cases() + new_cases() + new_bf16_cases()
 
 
 def describe(case) -> str:
@@ -155,11 +177,21 @@ def plan_cases(exe, cases):
 
 
 def reach(exe):
-    """({template key: (smallest handle, smallest k-space-valid handle or None)}, the same for edge keys, the tool's summary line);
+    """({template key: (smallest handle, smallest k-space-valid handle or None)}, the same for edge keys, the tool's summary line,
+    {level: {flags: number of keys that handles of this flag set alone reach}}, {level: {key: the flag sets whose handles reach it}});
     a handle is (n, h, w, flags)"""
     out = _run(exe, ["--reach"]).splitlines()
     levels = {"T": {}, "E": {}}
+    only, reached_by = {"T": {}, "E": {}}, {"T": {}, "E": {}}
     for line in out[:-1]:
-        head, key, at, kat = line.split(" | ")
-        levels[head.split()[1]][key] = (tuple(int(v) for v in at.split()), None if kat == "-" else tuple(int(v) for v in kat.split()))
-    return levels["T"], levels["E"], out[-1]
+        head, rest = line.split(" | ", 1)
+        word, level = head.split()
+        if word == "only":
+            flags, count = rest.split(" | ")
+            only[level][int(flags)] = int(count)
+            continue
+        assert word == "reach", line
+        key, at, kat, by = rest.split(" | ")
+        levels[level][key] = (tuple(int(v) for v in at.split()), None if kat == "-" else tuple(int(v) for v in kat.split()))
+        reached_by[level][key] = frozenset(int(v) for v in by.split())
+    return levels["T"], levels["E"], out[-1], only, reached_by
