@@ -116,6 +116,18 @@ SIGNATURES = {
     "pnp_workspace_bytes": (C.c_size_t, [C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/pnpadmm_ncsense.h declares (non-Cartesian SENSE: the extension header of the same library)
+SIGNATURES_NCSENSE = {
+    "pnp_nufft_forward_mc": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_nufft_adjoint_mc": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_set_kspace_ncsense": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _fp, C.c_int, _vp]),
+    "pnp_reset_ncsense": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _vp]),
+    "pnp_ncsense_coils": (C.c_int, [C.c_void_p]),
+    "pnp_ncsense_cg_residual": (C.c_int, [C.c_void_p, _fp, _vp]),
+    "pnp_ncsense_normal": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),
+    "pnp_acquire_ncsense": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _fp, C.c_double, C.c_uint64, C.c_int, _fp, _fp, _fp, _vp]),
+}
+
 _lib = None
 
 
@@ -132,7 +144,7 @@ def load() -> C.CDLL:
         raise PnPError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        f"or `make -C {os.path.dirname(LIB_PATH)}`; there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE}.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -164,15 +164,22 @@ def radial_dcf(traj, h: int, w: int) -> np.ndarray:
     return (d * (h * w / d.sum())).astype(np.float32)
 
 
-def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, width: int, grid) -> Dict[str, torch.Tensor]:
+def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, width: int, grid, sens=None) -> Dict[str, torch.Tensor]:
     t = np.ascontiguousarray(traj.detach().cpu().numpy() if isinstance(traj, torch.Tensor) else traj, dtype=np.float64)
     eng.nufft_plan(t, grid=grid, width=width)
     d = None if dcf is None else torch.as_tensor(dcf).to(eng.device, torch.float32).contiguous()
-    y, aty0, x0 = eng.acquire_nc(g, float(sigma_n), seed, dcf=d)
-    out = {"x0": torch.view_as_real(x0), "y0": torch.view_as_real(y.reshape(eng.n, 1, -1)), "ATy0": torch.view_as_real(aty0), "gt": g,
+    if sens is not None:                                     # non-Cartesian SENSE: y [N,C,M]
+        sens = torch.as_tensor(sens).to(eng.device, torch.complex64).contiguous()
+        y, aty0, x0 = eng.acquire_ncsense(g, sens, float(sigma_n), seed, dcf=d)
+    else:
+        y, aty0, x0 = eng.acquire_nc(g, float(sigma_n), seed, dcf=d)
+        y = y.reshape(eng.n, 1, -1)
+    out = {"x0": torch.view_as_real(x0), "y0": torch.view_as_real(y), "ATy0": torch.view_as_real(aty0), "gt": g,
            "x0_raw": aty0.real.contiguous(), "traj": torch.from_numpy(t)}
     if d is not None:
         out["dcf"] = d
+    if sens is not None:
+        out["sens"] = sens
     return out
 
 
@@ -189,8 +196,9 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
     of the plain call mixed by L on the device (pnp_whiten_apply, in place; an unsampled bin stays exactly zero).  ATy0 is the sum of
     the two parts' A^H (the noise part through the maps mixed by L^H), x0 its clip at 0; the dict carries `noise_cov` (complex128).
     traj (float64 [M,2], e.g. `radial_trajectory`; mask is then ignored and may be None): the non-Cartesian acquisition (pnp_nufft_plan +
-    pnp_acquire_nc, single-coil): y0 is [N,1,M,2], ATy0 = A^H (dcf y) with dcf float32 [M] or None, and the dict carries `traj` and `dcf`
-    (when given) in place of `mask`."""
+    pnp_acquire_nc): y0 is [N,1,M,2], ATy0 = A^H (dcf y) with dcf float32 [M] or None, and the dict carries `traj` and `dcf`
+    (when given) in place of `mask`.  traj with sens: the non-Cartesian SENSE acquisition (pnp_acquire_ncsense): y0 is [N,C,M,2],
+    ATy0 = sum_c conj(S_c) F_nu^H (dcf y_c), and the dict carries `sens` too; traj with noise_cov is refused."""
     if not torch.cuda.is_available():
         raise RuntimeError("simulate needs a ROCm GPU; the CPU route is synthetic.make_problem")
     g = torch.as_tensor(gt)
@@ -205,9 +213,9 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
         raise ValueError(f"gt {tuple(g.shape)} does not fit the engine [{eng.n},{eng.h},{eng.w}]")
     g = g.to(eng.device, torch.float32).reshape(n, 1, h, w).contiguous()
     if traj is not None:
-        if sens is not None or noise_cov is not None:
-            raise ValueError("simulate: a non-Cartesian acquisition is single-coil (traj with sens / noise_cov is not supported)")
-        return _simulate_nc(eng, g, traj, dcf, sigma_n, int(seed) + int(first_slice), nufft_width, nufft_grid)
+        if noise_cov is not None:
+            raise ValueError("simulate: a non-Cartesian acquisition draws white noise (traj with noise_cov is not supported)")
+        return _simulate_nc(eng, g, traj, dcf, sigma_n, int(seed) + int(first_slice), nufft_width, nufft_grid, sens=sens)
     m = torch.as_tensor(mask)
     if m.numel() == h * w:
         m = m.reshape(h, w)
@@ -569,17 +577,19 @@ def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int =
     `make_mask(h, w, accel, mask_kind, seed)` (the same for every shard of a job).  coils > 0: a multi-coil acquisition with the
     analytic maps `synthetic.coil_maps(coils, h, w)`; noise_cov: their channel noise covariance (`simulate`).
     mask_kind "radial-nc": a true radial acquisition, samples off the grid (`simulate(traj=)`): golden-angle `radial_trajectory` of
-    `spokes` spokes (None: ceil(h / accel)), weighted by `radial_dcf` (nc_weights "dcf") or not at all ("none"); single-coil."""
+    `spokes` spokes (None: ceil(h / accel)), weighted by `radial_dcf` (nc_weights "dcf") or not at all ("none"); with coils > 0 the
+    non-Cartesian SENSE acquisition with the maps `synthetic.coil_maps(coils, h, w)`."""
     accel, sigma_n = parse_task(task)
     h, w = (int(v) for v in torch.as_tensor(gt).shape[-2:])
     if mask_kind in NC_KINDS:
-        if coils or noise_cov is not None or mask is not None:
-            raise ValueError("task_problem: mask_kind 'radial-nc' is single-coil and takes no mask")
+        if noise_cov is not None or mask is not None:
+            raise ValueError("task_problem: mask_kind 'radial-nc' takes no mask and no noise_cov")
         if nc_weights not in ("none", "dcf"):
             raise ValueError(f"nc_weights must be 'none' or 'dcf', got {nc_weights!r}")
         traj = radial_trajectory(h, w, int(math.ceil(h / accel)) if spokes is None else int(spokes))
-        return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, traj=traj, dcf=radial_dcf(traj, h, w) if nc_weights == "dcf" else None,
-                        nufft_width=nufft_width, nufft_grid=nufft_grid)
+        sens = synthetic.coil_maps(coils, h, w).astype(np.complex64) if coils else None
+        return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, sens=sens, traj=traj,
+                        dcf=radial_dcf(traj, h, w) if nc_weights == "dcf" else None, nufft_width=nufft_width, nufft_grid=nufft_grid)
     if mask is None:
         mask = make_mask(h, w, accel, mask_kind, seed)
     sens = synthetic.coil_maps(coils, h, w).astype(np.complex64) if coils else None

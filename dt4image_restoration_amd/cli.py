@@ -25,6 +25,7 @@ layout has none):
 
     ... --coils 4 --cg-iters 8 eval|flex|mcts|fixed ...
     ... --traj radial [--spokes S] [--nufft-width 4|6|8] [--nufft-grid GH GW] [--nc-weights none|dcf] [--cg-iters K] eval|flex|mcts|fixed|acquire ...
+    ... --traj radial --nc-coils 4 [--cg-iters K] eval|flex|mcts|fixed|acquire ...      (non-Cartesian SENSE: the radial acquisition of C coils)
     ... --coils 4 --sens estimate [--sens-window hann|box] [--sens-thresh 0.05] [--acs H W] --mask cartesian fixed ...
 
     ... --coils 8 --sens espirit [--espirit-kernel 6] [--espirit-sv 0.02] [--espirit-crop 0.9] [--espirit-iters 16] --mask cartesian fixed ...
@@ -212,7 +213,8 @@ def _grappa_start(env, batch, filled):
 
 def _nc_kwargs(args):
     """--traj radial: what `acquisition.task_problem` needs for the non-Cartesian acquisition of a task."""
-    return dict(mask_kind="radial-nc", spokes=args.spokes, nc_weights=args.nc_weights, nufft_width=args.nufft_width, nufft_grid=args.nufft_grid)
+    return dict(mask_kind="radial-nc", spokes=args.spokes, nc_weights=args.nc_weights, nufft_width=args.nufft_width, nufft_grid=args.nufft_grid,
+                coils=args.nc_coils)
 
 
 def _sets(args, flex_target=None, env=None):
@@ -365,6 +367,8 @@ def main(argv=None):
     ap.add_argument("--cg-iters", type=int, default=8, help="conjugate-gradient iterations per step of a multi-coil or --traj problem (1..64)")
     ap.add_argument("--traj", choices=("radial",), default=None, help="a non-Cartesian acquisition: golden-angle radial spokes whose samples lie "
                     "off the grid (NUFFT data fidelity, CG solve), single-coil: the synthetic sets or --gt, not --data")
+    ap.add_argument("--nc-coils", type=int, default=0, metavar="C", help="--traj radial: non-Cartesian SENSE, the radial acquisition of C "
+                    "coils with analytic coil maps (1..32; default 0: single-coil)")
     ap.add_argument("--spokes", type=int, default=None, metavar="S", help="--traj radial: spokes (default: ceil(H / acceleration) of the task)")
     ap.add_argument("--nufft-width", type=int, choices=(4, 6, 8), default=6, help="--traj: width of the gridding kernel in grid points")
     ap.add_argument("--nufft-grid", type=int, nargs=2, default=None, metavar=("GH", "GW"), help="--traj: sides of the oversampled grid (sides "
@@ -435,11 +439,16 @@ def main(argv=None):
         raise SystemExit(f"--cg-iters must be 1..64, got {args.cg_iters}")
     if args.traj:
         if args.coils:
-            raise SystemExit("--traj with --coils: refused - the non-Cartesian stage is single-coil (multi-coil non-Cartesian is not built)")
+            raise SystemExit("--traj with --coils: refused - --coils selects the Cartesian multi-coil chain; the multi-coil radial acquisition "
+                             "is --traj radial --nc-coils C")
+        if args.nc_coils and not 1 <= args.nc_coils <= 32:
+            raise SystemExit(f"--nc-coils must be 1..32, got {args.nc_coils}")
         if args.spokes is not None and args.spokes < 1:
             raise SystemExit(f"--spokes must be >= 1, got {args.spokes}")
         if args.grappa or args.mask != "radial":
             raise SystemExit("--traj takes no --mask / --grappa: its samples are a trajectory, not a mask")
+    elif args.nc_coils:
+        raise SystemExit(f"--nc-coils needs --traj radial (got --nc-coils {args.nc_coils} without it)")
     elif args.spokes is not None or args.nufft_grid is not None or args.nufft_width != 6 or args.nc_weights != "dcf":
         raise SystemExit("--spokes / --nufft-width / --nufft-grid / --nc-weights need --traj radial")
     if args.prior == "tv":

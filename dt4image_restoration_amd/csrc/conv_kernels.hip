@@ -794,6 +794,8 @@ Tuning tuning_from_env() {
     if (const char* v = getenv("PNP_SLICE128_MIN_N")) t.slice128_min_n = atoi(v);
     if (const char* v = getenv("PNP_TV_NAIVE")) t.tv_naive = atoi(v) != 0;
     if (const char* v = getenv("PNP_HAAR_NAIVE")) t.haar_naive = atoi(v) != 0;
+    if (const char* v = getenv("PNP_NCSENSE_COIL_BLOCK")) t.ncsense_block = atoi(v);
+    if (const char* v = getenv("PNP_NCSENSE_NAIVE")) t.ncsense_naive = atoi(v) != 0 ? 1 : 0;
     return t;
 }
 

@@ -1,6 +1,7 @@
 // C ABI of libpnpadmm.so (declared in include/pnpadmm.h): engine object, weight ingest, launch
 // sequencing of one PnP-ADMM iteration, kernel-level event timing.
 #include "../../include/pnpadmm.h"
+#include "../../include/pnpadmm_ncsense.h"
 #include "pnp_internal.h"
 #include "denoiser_plan.h"
 #include "nufft_plan.h"
@@ -135,6 +136,22 @@ struct pnp_engine {
     bool nc_on = false;          // non-Cartesian constants were installed last: the CG stage runs on the NUFFT normal operator
     bool nc_has_w = false;
     int nc_cg = 0;               // CG iterations per step
+    // non-Cartesian SENSE (include/pnpadmm_ncsense.h): the coil-block scratch by every entry point of that header, the constants by its installers
+    int ns_block = kNcsenseBlock; // coils per block: kNcsenseBlock, or PNP_NCSENSE_COIL_BLOCK (read at pnp_create)
+    int ns_naive = kNcsenseNaiveSteps;   // NcsenseStep bits: the steps that run as the single-coil launches at batch N cb (PNP_NCSENSE_NAIVE: all or none)
+    float2* ns_img = nullptr;    // naive pad or crop only: [N, cb, H, W] the block's coil images
+    size_t ns_img_cap = 0;
+    float2* ns_grid = nullptr;   // [N, cb, gh, gw] the block's oversampled grids
+    float2* ns_samp = nullptr;   // [N, cb, M] the block's samples (A p inside the normal operator, A x of the misfit)
+    float2* ns_y = nullptr;      // [N, C, M] the installed samples
+    float2* ns_sens = nullptr;   // [sens_n, C, H, W] the installed maps
+    float* ns_w = nullptr;       // [M] the installed weights (read only while ns_has_w)
+    double* ns_mpart = nullptr;  // [N, C, nufft_sample_chunks(M)] partial sums of the misfit
+    size_t ns_grid_cap = 0, ns_samp_cap = 0, ns_y_cap = 0, ns_sens_cap = 0, ns_w_cap = 0, ns_mpart_cap = 0;
+    int ns_coils = 0;            // coils of the installed constants; > 0: they were installed last and the CG stage runs on the coil operator
+    int ns_sens_n = 1;
+    bool ns_has_w = false;
+    int ns_cg = 0;               // CG iterations per step
     // the prior of pnp_step (pnp_set_prior) and the total-variation denoiser's workspace (allocated inside the first call that runs it)
     int prior = PNP_PRIOR_UNET;
     double tv_scale = 1.0;       // as given; applied as float32
@@ -421,8 +438,102 @@ int nc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
     return nc_adjoint(e, e->nc_samp, e->nc_has_w ? e->nc_w : nullptr, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
 }
 
+// ---- non-Cartesian SENSE stage (include/pnpadmm_ncsense.h) --------------------------------------------
+// the centred transform of `planes` planes of the block's grids, in place in ns_grid
+int ns_fft(pnp_engine* e, int planes, int inverse, hipStream_t s) {
+    const NufftDev& P = e->nc;
+    {
+        Prof p(e, s, PROF_FFT_ROWS, -1);
+        HIP_TRY(launch_fft_rows(e->ns_grid, e->ns_grid, P.tw_gw, planes, P.gh, P.gw, inverse, P.gw / 2, s));
+    }
+    Prof p(e, s, PROF_FFT_COLS, -1);
+    HIP_TRY(launch_fft_cols(e->ns_grid, P.tw_gh, planes, P.gh, P.gw, inverse, P.gh / 2, s));
+    return PNP_OK;
+}
+int ns_block_of(const pnp_engine* e, int coils) { return coils < e->ns_block ? coils : e->ns_block; }
+// F_nu(S_c . src) for the block's coils c0 .. c0 + cb - 1 into out [batch, ocs, M] at the coils oc0 ..
+int ns_forward_block(pnp_engine* e, const float2* src, const float* src_real, const float2* sens, int sens_n, int C, int c0, int cb, int batch,
+                     float2* out, int ocs, int oc0, hipStream_t s) {
+    const size_t row = (size_t)cb * e->nc.m * sizeof(float2);          // one slice's samples of the block
+    const bool direct = ocs == cb;                                     // (then oc0 == 0) the block's samples are contiguous in out
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        if (e->ns_naive & NS_PAD) {
+            HIP_TRY(launch_ncsense_expand(src, src_real, sens, sens_n, C, c0, cb, e->nc, e->ns_img, batch, s));
+            HIP_TRY(launch_nufft_pad(e->ns_img, nullptr, e->nc, e->ns_grid, batch * cb, s));
+            p.end(2);
+        } else {
+            HIP_TRY(launch_ncsense_pad(src, src_real, sens, sens_n, C, c0, cb, e->nc, e->ns_grid, batch, s));
+        }
+    }
+    if (int rc = ns_fft(e, batch * cb, 0, s)) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
+    if (!(e->ns_naive & NS_GATHER)) {
+        HIP_TRY(launch_ncsense_interp(e->ns_grid, e->nc, out, ocs, oc0, cb, batch, s));
+        return PNP_OK;
+    }
+    HIP_TRY(launch_nufft_interp(e->ns_grid, e->nc, direct ? out : e->ns_samp, batch * cb, s));
+    if (!direct)
+        HIP_TRY(hipMemcpy2DAsync(out + (size_t)oc0 * e->nc.m, (size_t)ocs * e->nc.m * sizeof(float2), e->ns_samp, row, row, (size_t)batch,
+                                 hipMemcpyDeviceToDevice, s));
+    return PNP_OK;
+}
+// q (+)= sum over the block's coils of conj(S_c) . F_nu^H(w . y[., yc0 + j]); the last block adds mu pv and leaves the partial sums of Re<pv, q>
+int ns_adjoint_block(pnp_engine* e, const float2* y, int ycs, int yc0, const float* w, const float2* sens, int sens_n, int C, int c0, int cb,
+                     int batch, const float2* pv, const float* mu, const float* tact, float2* q, double* partial, hipStream_t s) {
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        if (e->ns_naive & NS_GRID) {
+            const size_t row = (size_t)cb * e->nc.m * sizeof(float2);
+            if (ycs != cb)                                             // the block's samples gathered into the contiguous scratch
+                HIP_TRY(hipMemcpy2DAsync(e->ns_samp, row, y + (size_t)yc0 * e->nc.m, (size_t)ycs * e->nc.m * sizeof(float2), row, (size_t)batch,
+                                         hipMemcpyDeviceToDevice, s));
+            HIP_TRY(launch_nufft_grid(ycs != cb ? e->ns_samp : y, w, e->nc, e->ns_grid, batch * cb, s));
+        } else {
+            HIP_TRY(launch_ncsense_grid(y, ycs, yc0, cb, w, e->nc, e->ns_grid, batch, s));
+        }
+    }
+    if (int rc = ns_fft(e, batch * cb, 1, s)) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
+    if (e->ns_naive & NS_CROP) {
+        HIP_TRY(launch_nufft_crop(e->ns_grid, e->nc, nullptr, nullptr, nullptr, e->ns_img, nullptr, batch * cb, s));
+        HIP_TRY(launch_ncsense_combine(e->ns_img, sens, sens_n, C, c0, cb, e->nc, pv, mu, tact, q, partial, batch, s));
+        p.end(2);
+    } else {
+        HIP_TRY(launch_ncsense_crop(e->ns_grid, sens, sens_n, C, c0, cb, e->nc, pv, mu, tact, q, partial, batch, s));
+    }
+    return PNP_OK;
+}
+// out [batch, C, M] = A src, block by block
+int ns_forward(pnp_engine* e, const float2* src, const float* src_real, const float2* sens, int sens_n, int C, int batch, float2* out, hipStream_t s) {
+    const int B = ns_block_of(e, C);
+    for (int c0 = 0; c0 < C; c0 += B)
+        if (int rc = ns_forward_block(e, src, src_real, sens, sens_n, C, c0, std::min(B, C - c0), batch, out, C, c0, s)) return rc;
+    return PNP_OK;
+}
+// q [batch, h, w] = A^H (w . y), y: [batch, C, M]
+int ns_adjoint(pnp_engine* e, const float2* y, const float* w, const float2* sens, int sens_n, int C, int batch, float2* q, hipStream_t s) {
+    const int B = ns_block_of(e, C);
+    for (int c0 = 0; c0 < C; c0 += B)
+        if (int rc = ns_adjoint_block(e, y, C, c0, w, sens, sens_n, C, c0, std::min(B, C - c0), batch, nullptr, nullptr, nullptr, q, nullptr, s))
+            return rc;
+    return PNP_OK;
+}
+// q = A^H W A pv + mu pv with the installed constants; the partial sums of Re<pv, q> go to mc_part.  Eight launches per coil block: a block's
+// samples go through ns_samp and are gridded before the next block's grids replace them.  Stopped slices: only the combine launches skip them
+int ns_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    const int N = e->cfg.n, C = e->ns_coils, B = ns_block_of(e, C);
+    const float* w = e->ns_has_w ? e->ns_w : nullptr;
+    for (int c0 = 0; c0 < C; c0 += B) {
+        const int cb = std::min(B, C - c0);
+        if (int rc = ns_forward_block(e, pv, nullptr, e->ns_sens, e->ns_sens_n, C, c0, cb, N, e->ns_samp, cb, 0, s)) return rc;
+        if (int rc = ns_adjoint_block(e, e->ns_samp, cb, 0, w, e->ns_sens, e->ns_sens_n, C, c0, cb, N, pv, mu, tact, q, e->mc_part, s)) return rc;
+    }
+    return PNP_OK;
+}
+
 // the K-step CG solve of (A^H A + mu I) z = A^H y + mu (x + u), warm-started from z, then u <- u + x - z; `normal`: the stage's normal
-// operator (mc_normal: the coil operator, nc_normal: the NUFFT pair), which also leaves the partial sums of Re<p, q> in mc_part
+// operator (mc_normal: the coil operator, nc_normal: the NUFFT pair, ns_normal: both), which also leaves the partial sums of Re<p, q> in mc_part
 using NormalOp = int (*)(pnp_engine*, const float2*, const float*, const float*, float2*, hipStream_t);
 int run_prox_dual_cg(pnp_engine* e, NormalOp normal, int iters, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                      hipStream_t s) {
@@ -534,6 +645,7 @@ int mc_install(pnp_engine* e, const float2* x0, const float2* y0, const float2* 
     e->mask_n = mask_n;
     e->mc_coils = coils; e->mc_cg = cg_iters; e->mc_sens_n = sens_n;
     e->nc_on = false;
+    e->ns_coils = 0;
     e->reset_done = true;
     {
         Prof p(e, s, PROF_OTHER, -1);
@@ -671,6 +783,7 @@ int run_haar(pnp_engine* e, const float* v, const float2* z, const float2* u, co
 int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                   hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    if (e->ns_coils > 0) return run_prox_dual_cg(e, ns_normal, e->ns_cg, mu, tact, x, z, u, s);  // non-Cartesian SENSE constants installed last
     if (e->nc_on) return run_prox_dual_cg(e, nc_normal, e->nc_cg, mu, tact, x, z, u, s);         // non-Cartesian constants installed last
     if (e->mc_coils > 0) return run_prox_dual_cg(e, mc_normal, e->mc_cg, mu, tact, x, z, u, s);   // multi-coil constants installed: the CG stage
     if (H == 128 && W == 128 && N >= e->tune.slice128_min_n) {   // chip-filling batches of the reference's slice size: 37 B/px
@@ -761,6 +874,8 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     if (!e) return fail(PNP_ERR_NOMEM, "pnp_create: out of host memory");
     e->cfg = *cfg;
     e->tune = tune;
+    if (tune.ncsense_block >= 1 && tune.ncsense_block <= PNP_MC_MAX_COILS) e->ns_block = tune.ncsense_block;   // a check and a timing knob
+    if (tune.ncsense_naive >= 0) e->ns_naive = tune.ncsense_naive ? NS_ALL : 0;
     e->dplan = plan;
     int rc;
     {
@@ -793,6 +908,8 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->haar_ws);
     (void)hipFree(e->nc.i0); (void)hipFree(e->nc.wts); (void)hipFree(e->nc.cy); (void)hipFree(e->nc.cx); (void)hipFree(e->nc.bin_off); (void)hipFree(e->nc.bin_idx);
     (void)hipFree(e->nc.tw_gh); (void)hipFree(e->nc.tw_gw);
+    (void)hipFree(e->ns_img);
+    (void)hipFree(e->ns_grid); (void)hipFree(e->ns_samp); (void)hipFree(e->ns_y); (void)hipFree(e->ns_sens); (void)hipFree(e->ns_w); (void)hipFree(e->ns_mpart);
     (void)hipFree(e->nc_grid); (void)hipFree(e->nc_samp); (void)hipFree(e->nc_y); (void)hipFree(e->nc_w); (void)hipFree(e->nc_mpart);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -882,6 +999,7 @@ int pnp_reset(pnp_handle e, const float* x0, const float* y0, const uint8_t* mas
     e->mask_n = mask_n;
     e->mc_coils = 0;                                       // back to the single-coil stage
     e->nc_on = false;
+    e->ns_coils = 0;
     HIP_TRY(launch_reset((const float2*)x0, (const float2*)y0, mask, mask_n, x, (float2*)z, (float2*)u, e->d_y0s,
                          e->d_masks, e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
     e->reset_done = true;
@@ -898,6 +1016,7 @@ int pnp_set_kspace(pnp_handle e, const float* y0, const uint8_t* mask, int mask_
     e->mask_n = mask_n;
     e->mc_coils = 0;                                       // back to the single-coil stage
     e->nc_on = false;
+    e->ns_coils = 0;
     HIP_TRY(launch_reset(nullptr, (const float2*)y0, mask, mask_n, nullptr, nullptr, nullptr, e->d_y0s, e->d_masks,
                          e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
     e->reset_done = true;
@@ -1131,7 +1250,18 @@ int pnp_residuals(pnp_handle e, const float* x, const float* z, const float* u, 
         HIP_TRY(launch_residual_tiles(x, (const float2*)z, (const float2*)u, (const float*)pv, pv ? (const float2*)(pv + snap.z_off()) : nullptr,
                                       pv ? (const float2*)(pv + snap.u_off()) : nullptr, part, N, H, W, s));
     }
-    if ((flags & PNP_RES_DC) && e->nc_on) {
+    if ((flags & PNP_RES_DC) && e->ns_coils > 0) {
+        // non-Cartesian SENSE mode: A x block by block into the sample scratch, then sum_c sum_m w_m |(A x)_{c,m} - y_{c,m}|^2
+        const int C = e->ns_coils, B = ns_block_of(e, C);
+        for (int c0 = 0; c0 < C; c0 += B) {
+            const int cb = std::min(B, C - c0);
+            if (int rc = ns_forward_block(e, nullptr, x, e->ns_sens, e->ns_sens_n, C, c0, cb, N, e->ns_samp, cb, 0, s)) return rc;
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_ncsense_misfit(e->ns_samp, e->ns_y, e->ns_has_w ? e->ns_w : nullptr, C, c0, cb, e->nc, e->ns_mpart, N, s));
+        }
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_ncsense_misfit_sum(e->ns_mpart, C, e->nc, dcpart, N, s));
+    } else if ((flags & PNP_RES_DC) && e->nc_on) {
         // non-Cartesian mode: A x into the sample scratch, then sum_m w_m |(A x)_m - y_m|^2
         if (int rc = nc_forward(e, nullptr, x, N, e->nc_samp, s)) return rc;
         Prof p(e, s, PROF_OTHER, -1);
@@ -1324,6 +1454,7 @@ int nc_install(pnp_engine* e, const float2* x0, const float2* y, const float* w,
     e->nc_cg = cg_iters;
     e->nc_on = true;
     e->mc_coils = 0;
+    e->ns_coils = 0;
     e->reset_done = true;
     return PNP_OK;
 }
@@ -1371,7 +1502,7 @@ int pnp_nufft_plan(pnp_handle e, const double* traj, int64_t m, int gh, int gw, 
     if (D.m > 0) (void)hipDeviceSynchronize();              // no launch still reads the plan being replaced
     // from here on the old plan is gone: its non-Cartesian constants are dropped with it
     D.m = 0;
-    if (e->nc_on) { e->nc_on = false; e->reset_done = false; }
+    if (e->nc_on || e->ns_coils > 0) { e->nc_on = false; e->ns_coils = 0; e->reset_done = false; }
     HIP_TRY(nc_upload(D.i0, P.i0.data(), P.i0.size() * sizeof(int32_t)));
     HIP_TRY(nc_upload(D.wts, P.wts.data(), P.wts.size() * sizeof(float)));
     HIP_TRY(nc_upload(D.cy, P.cy.data(), P.cy.size() * sizeof(float)));
@@ -1498,6 +1629,197 @@ int pnp_acquire_nc(pnp_handle e, const float* gt, const float* dcf, double sigma
     }
     return PNP_OK;
     PNP_API_END("pnp_acquire_nc")
+}
+
+// ---- non-Cartesian SENSE (include/pnpadmm_ncsense.h) ---------------------------------------------------
+namespace {
+
+// the coil-block scratch for `coils` coils: the block's grids and samples
+int ns_ensure(pnp_engine* e, int coils) {
+    const size_t planes = (size_t)e->cfg.n * ns_block_of(e, coils);
+    return ws_grow(e, "non-Cartesian SENSE scratch", {{(void**)&e->ns_grid, &e->ns_grid_cap, planes * e->nc.gh * e->nc.gw * sizeof(float2), false},
+                                                     {(void**)&e->ns_samp, &e->ns_samp_cap, planes * (size_t)e->nc.m * sizeof(float2), false},
+                                                     {(void**)&e->ns_img, &e->ns_img_cap,
+                                                      (e->ns_naive & (NS_PAD | NS_CROP)) ? planes * e->cfg.h * e->cfg.w * sizeof(float2) : 0, false}});
+}
+
+// argument errors shared by the entry points that take maps: the scalar ranges need no handle and come first
+int ns_check_scalars(const char* fn, int coils, int sens_n) {
+    if (coils < 1 || coils > PNP_MC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_MC_MAX_COILS, coils);
+    if (sens_n < 1) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n (got %d)", fn, sens_n);
+    return PNP_OK;
+}
+int ns_check(const char* fn, const pnp_engine* e, int coils, int sens_n) {
+    const int N = e->cfg.n;
+    if (sens_n != 1 && sens_n != N) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n=%d", fn, N);
+    if ((long long)N * ns_block_of(e, coils) > 65535)
+        return fail(PNP_ERR_INVALID, "%s: n * min(coils, block) must be <= 65535 (got %d * %d)", fn, N, ns_block_of(e, coils));
+    return nc_need_plan(fn, e);
+}
+int ns_need_mode(const char* fn, const pnp_engine* e) {
+    return e->ns_coils > 0 ? PNP_OK
+                           : fail(PNP_ERR_STATE, "%s: the handle is not in non-Cartesian SENSE mode (pnp_set_kspace_ncsense / pnp_reset_ncsense)", fn);
+}
+
+// the episode constants of the stage: y, w, the maps, A^H W y, and optionally the iterate
+int ns_install(pnp_engine* e, const float2* x0, const float2* y, const float2* sens, int coils, int sens_n, const float* w, int cg_iters, float* x,
+               float2* z, float2* u, hipStream_t s) {
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    const size_t M = (size_t)e->nc.m, ym = (size_t)N * coils * M, sn = (size_t)sens_n * coils * H * W;
+    int rc;
+    if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
+    if ((rc = ns_ensure(e, coils))) return rc;
+    if ((rc = ws_grow(e, "non-Cartesian SENSE constants",
+                      {{(void**)&e->ns_y, &e->ns_y_cap, ym * sizeof(float2), false},
+                       {(void**)&e->ns_sens, &e->ns_sens_cap, sn * sizeof(float2), false},
+                       {(void**)&e->ns_w, &e->ns_w_cap, w ? M * sizeof(float) : 0, false},
+                       {(void**)&e->ns_mpart, &e->ns_mpart_cap, (size_t)N * coils * nufft_sample_chunks((int64_t)M) * sizeof(double), false}})))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(e->ns_y, y, ym * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->ns_sens, sens, sn * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    if (w) HIP_TRY(hipMemcpyAsync(e->ns_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
+    if ((rc = ns_adjoint(e, e->ns_y, w ? e->ns_w : nullptr, e->ns_sens, sens_n, coils, N, mc_aty(e), s))) return rc;
+    if (x0) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
+    }
+    // every launch was accepted: only now does the handle change mode (nc_install's rule)
+    e->ns_coils = coils; e->ns_sens_n = sens_n; e->ns_has_w = w != nullptr; e->ns_cg = cg_iters;
+    e->nc_on = false;
+    e->mc_coils = 0;
+    e->reset_done = true;
+    return PNP_OK;
+}
+
+}  // namespace
+
+int pnp_nufft_forward_mc(pnp_handle e, const float* img, const float* sens, int coils, int sens_n, int batch, float* samples, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_nufft_forward_mc";
+    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
+    if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!samples) return fail(PNP_ERR_INVALID, "%s: null samples", fn);
+    if (samples == img || samples == sens) return fail(PNP_ERR_INVALID, "%s: samples must not alias img or sens", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
+    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = ns_ensure(e, coils)) return rc;
+    return ns_forward(e, (const float2*)img, nullptr, (const float2*)sens, sens_n, coils, batch, (float2*)samples, (hipStream_t)stream);
+    PNP_API_END("pnp_nufft_forward_mc")
+}
+
+int pnp_nufft_adjoint_mc(pnp_handle e, const float* samples, const float* weights, const float* sens, int coils, int sens_n, int batch, float* img,
+                         void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_nufft_adjoint_mc";
+    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
+    if (!samples) return fail(PNP_ERR_INVALID, "%s: null samples", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
+    if (img == samples || img == sens || (const float*)img == weights) return fail(PNP_ERR_INVALID, "%s: img must not alias samples, weights or sens", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
+    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = ns_ensure(e, coils)) return rc;
+    return ns_adjoint(e, (const float2*)samples, weights, (const float2*)sens, sens_n, coils, batch, (float2*)img, (hipStream_t)stream);
+    PNP_API_END("pnp_nufft_adjoint_mc")
+}
+
+int pnp_set_kspace_ncsense(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, const float* w, int cg_iters, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_set_kspace_ncsense";
+    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    PNP_ON_DEVICE(e);
+    return ns_install(e, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, w, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    PNP_API_END("pnp_set_kspace_ncsense")
+}
+
+int pnp_reset_ncsense(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, const float* w, int cg_iters, float* x,
+                      float* z, float* u, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_reset_ncsense";
+    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
+    if (!x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!x || !z || !u) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    PNP_ON_DEVICE(e);
+    return ns_install(e, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, w, cg_iters, x, (float2*)z, (float2*)u,
+                      (hipStream_t)stream);
+    PNP_API_END("pnp_reset_ncsense")
+}
+
+int pnp_ncsense_coils(pnp_handle e) { return e ? e->ns_coils : 0; }
+
+int pnp_ncsense_cg_residual(pnp_handle e, float* out, void* stream) {
+    PNP_API_BEGIN
+    if (!e || !out) return fail(PNP_ERR_INVALID, "pnp_ncsense_cg_residual: null argument");
+    if (int rc = ns_need_mode("pnp_ncsense_cg_residual", e)) return rc;
+    PNP_ON_DEVICE(e);
+    Prof p(e, (hipStream_t)stream, PROF_OTHER, -1);
+    HIP_TRY(launch_sense_cgres(e->mc_sc, out, e->cfg.n, (hipStream_t)stream));
+    return PNP_OK;
+    PNP_API_END("pnp_ncsense_cg_residual")
+}
+
+int pnp_ncsense_normal(pnp_handle e, const float* pv, const float* mu, float* q, void* stream) {
+    PNP_API_BEGIN
+    if (!e || !pv || !mu || !q) return fail(PNP_ERR_INVALID, "pnp_ncsense_normal: null argument");
+    if (pv == q) return fail(PNP_ERR_INVALID, "pnp_ncsense_normal: p and q must not alias");
+    if (int rc = ns_need_mode("pnp_ncsense_normal", e)) return rc;
+    PNP_ON_DEVICE(e);
+    return ns_normal(e, (const float2*)pv, mu, nullptr, (float2*)q, (hipStream_t)stream);
+    PNP_API_END("pnp_ncsense_normal")
+}
+
+int pnp_acquire_ncsense(pnp_handle e, const float* gt, const float* sens, int coils, int sens_n, const float* dcf, double sigma_n, uint64_t seed,
+                        int flags, float* y, float* aty0, float* x0, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_acquire_ncsense";
+    // every rejection happens before any HIP call, and leaves the outputs untouched
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "%s: sigma_n must be finite and >= 0 (got %g)", fn, sigma_n);
+    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (!gt) return fail(PNP_ERR_INVALID, "%s: null gt", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (y == gt || y == sens || (aty0 && (aty0 == gt || aty0 == sens || aty0 == y)) || (x0 && (x0 == gt || x0 == sens || x0 == y)))
+        return fail(PNP_ERR_INVALID, "%s: no output may alias gt, sens or another output", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = ns_ensure(e, coils))) return rc;
+    if ((rc = ns_forward(e, nullptr, gt, (const float2*)sens, sens_n, coils, N, (float2*)y, s))) return rc;
+    if (sigma_n != 0.0) {                                   // a noiseless acquisition draws nothing and keeps the forward's own bits
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_ncsense_noise((float2*)y, sigma_n, seed, coils, e->nc, N, s));
+    }
+    if (!aty0 && !x0) return PNP_OK;
+    float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the image goes to the data-fidelity stage's scratch plane
+    if ((rc = ns_adjoint(e, (const float2*)y, dcf, (const float2*)sens, sens_n, coils, N, a, s))) return rc;
+    if (x0) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
+    }
+    return PNP_OK;
+    PNP_API_END("pnp_acquire_ncsense")
 }
 
 int pnp_estimate_sens(pnp_handle e, const float* y0, int coils, int acs_h, int acs_w, int window, double thresh, int flags, float* sens,

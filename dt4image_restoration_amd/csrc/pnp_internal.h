@@ -36,6 +36,9 @@ struct Tuning {
                                   // needs a chip-filling batch to beat the three-launch path: 64.1 vs 78.8 us at 256 slices, 48.9 vs 34.9 at 64)
     bool tv_naive = false;        // PNP_TV_NAIVE (tests): the TV prior as one launch per iteration instead of the fused kernel
     bool haar_naive = false;      // PNP_HAAR_NAIVE (tests): the Haar TI prior as one launch per level instead of the fused kernel
+    int ncsense_block = 0;        // PNP_NCSENSE_COIL_BLOCK (tests, timing): coils per block of the non-Cartesian SENSE stage, 1..32 (else: kNcsenseBlock)
+    int ncsense_naive = -1;       // PNP_NCSENSE_NAIVE (tests, timing): 1 = every step of that stage as the single-coil launches between an expand and a
+                                  // combine kernel, 0 = every step coil-batched; unset: kNcsenseNaiveSteps, the choice per step by measurement
 };
 Tuning tuning_from_env();
 
@@ -386,5 +389,38 @@ hipError_t launch_nufft_misfit(const float2* a, const float2* y, const float* w,
                                hipStream_t s);
 // y [N, M] += sigma (g_re + i g_im): pnp_acquire's counter hash of (seed + n, 9001 / 9003, m)
 hipError_t launch_nufft_noise(float2* y, double sigma, uint64_t seed, const NufftDev& P, int N, hipStream_t s);
+
+// ---- non-Cartesian SENSE (ncsense_kernels.hip; the operator: include/pnpadmm_ncsense.h) ---------------
+// A block of cb coils c0 .. c0 + cb - 1 of every slice per launch.  grid: [batch, cb, gh, gw]; sens: [sens_n, C, h, w], sens_n 1 or batch's n
+static constexpr int kNcsenseBlock = 8;    // default coils per block (PNP_NCSENSE_COIL_BLOCK overrides it)
+static constexpr int kNcsenseSub = 8;      // coils per workgroup of the gridding: its register sub-block
+// the steps of the stage, as bits: which of them run as the naive launches.  Both forms give the same bits (include/pnpadmm_ncsense.h)
+enum NcsenseStep : int { NS_PAD = 1, NS_GATHER = 2, NS_GRID = 4, NS_CROP = 8, NS_ALL = 15 };
+// the shipped choice (profiles/ncsense_bench.json): a coil-batched kernel ships only where it is not slower than the launch it replaces
+static constexpr int kNcsenseNaiveSteps = NS_GATHER | NS_GRID;
+// grid[n, j] = the zero-padded (cy cx) . (S_(c0+j) . src[n]); src complex [batch, h, w], or src_real != nullptr: a real image
+hipError_t launch_ncsense_pad(const float2* src, const float* src_real, const float2* sens, int sens_n, int C, int c0, int cb, const NufftDev& P,
+                              float2* grid, int batch, hipStream_t s);
+// out[n, oc0 + j] = the gather of grid[n, j]; out: [batch, ocs, M]
+hipError_t launch_ncsense_interp(const float2* grid, const NufftDev& P, float2* out, int ocs, int oc0, int cb, int batch, hipStream_t s);
+// grid[n, j] = the spread of w . y[n, yc0 + j] (y: [batch, ycs, M]; w: [M] or nullptr), every grid point written, no atomics
+hipError_t launch_ncsense_grid(const float2* y, int ycs, int yc0, int cb, const float* w, const NufftDev& P, float2* grid, int batch, hipStream_t s);
+// q (+)= sum_j conj(S_(c0+j)) . (cy cx) . crop(grid[n, j]): the first block (c0 == 0) starts from +0, a later one from q; the last block
+// (c0 + cb == C) adds mu pv and leaves the partial sums of Re<pv, q> as launch_nufft_crop does (pv, mu, tact, partial may be nullptr)
+hipError_t launch_ncsense_crop(const float2* grid, const float2* sens, int sens_n, int C, int c0, int cb, const NufftDev& P, const float2* pv,
+                               const float* mu, const float* tact, float2* q, double* partial, int batch, hipStream_t s);
+// the naive form (PNP_NCSENSE_NAIVE): img [batch, cb, h, w] = S_(c0+j) . src, for launch_nufft_pad at batch * cb planes; and launch_ncsense_crop's
+// combine on the coil images [batch, cb, h, w] that launch_nufft_crop left
+hipError_t launch_ncsense_expand(const float2* src, const float* src_real, const float2* sens, int sens_n, int C, int c0, int cb, const NufftDev& P,
+                                 float2* img, int batch, hipStream_t s);
+hipError_t launch_ncsense_combine(const float2* img, const float2* sens, int sens_n, int C, int c0, int cb, const NufftDev& P, const float2* pv,
+                                  const float* mu, const float* tact, float2* q, double* partial, int batch, hipStream_t s);
+// partial [N, C, nufft_sample_chunks(M)] at the block's coils = sum_m w_m |a[n, j] - y[n, c0 + j]|^2 per chunk; a: [N, cb, M], y: [N, C, M]
+hipError_t launch_ncsense_misfit(const float2* a, const float2* y, const float* w, int C, int c0, int cb, const NufftDev& P, double* partial, int N,
+                                 hipStream_t s);
+// dcpartial: [N, pixel_chunks(h, w)] = (the slice's partials summed in (coil, chunk) order, 0, ..): launch_residual_reduce's DC input
+hipError_t launch_ncsense_misfit_sum(const double* partial, int C, const NufftDev& P, double* dcpartial, int N, hipStream_t s);
+// y [N, C, M] += sigma (g_re + i g_im): pnp_acquire's counter hash of (seed + n, 9001 + 4 c / 9003 + 4 c, m)
+hipError_t launch_ncsense_noise(float2* y, double sigma, uint64_t seed, int C, const NufftDev& P, int N, hipStream_t s);
 
 }  // namespace pnp

@@ -41,6 +41,9 @@ def save_mat(path: str, problem: Dict[str, np.ndarray], index: int = 0) -> None:
               "traj": problem["traj"]}
         if problem.get("dcf") is not None:
             nc["dcf"] = problem["dcf"]
+        if problem.get("sens") is not None:                  # non-Cartesian SENSE: samples [C,M,2] and the maps [C,H,W] of this slice
+            s = np.asarray(problem["sens"])
+            nc["sens"] = s if s.ndim == 3 else s[index]
         savemat(path, nc)
         return
     savemat(path, {"x0": problem["ATy0"][index], "y0": problem["y0"][index], "ATy0": problem["ATy0"][index],

@@ -237,6 +237,97 @@ class PnPEngine:
                    "pnp_acquire_nc")
         return y, aty0, x0
 
+    # -- non-Cartesian SENSE (include/pnpadmm_ncsense.h) --------------------------------------
+    @property
+    def ncsense_coils(self) -> int:
+        """Coils of the installed non-Cartesian SENSE constants; 0 unless that mode is live."""
+        return int(self.lib.pnp_ncsense_coils(self._h))
+
+    def nufft_forward_mc(self, img: torch.Tensor, sens: torch.Tensor) -> torch.Tensor:
+        """samples complex64 [B,C,M] = [F_nu(S_c . img)]_c (pnp_nufft_forward_mc); img complex64 [B,H,W] (or [B,1,H,W]), B <= N; sens
+        complex64 [C,H,W] or [N,C,H,W]."""
+        b = self._batch_of(img, self.h * self.w, "img")
+        self._chk(img, torch.complex64, img.numel(), "img")
+        sens, coils, sens_n = self._sens(sens)
+        out = torch.empty((b, coils, max(self.nufft_samples, 1)), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_nufft_forward_mc(self._h, img.data_ptr(), sens.data_ptr(), coils, sens_n, b, out.data_ptr(), self._stream()),
+                   "pnp_nufft_forward_mc")
+        return out
+
+    def nufft_adjoint_mc(self, samples: torch.Tensor, sens: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """img complex64 [B,H,W] = sum_c conj(S_c) . F_nu^H(weights . samples_c) (pnp_nufft_adjoint_mc); samples complex64 [B,C,M], weights
+        float32 [M] or None."""
+        m = self.nufft_samples
+        sens, coils, sens_n = self._sens(sens)
+        b = self._batch_of(samples, coils * m, "samples")
+        self._chk(samples, torch.complex64, samples.numel(), "samples")
+        if weights is not None:
+            self._chk(weights, torch.float32, m, "weights")
+        out = torch.empty((b, self.h, self.w), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_nufft_adjoint_mc(self._h, samples.data_ptr(), weights.data_ptr() if weights is not None else None,
+                                                 sens.data_ptr(), coils, sens_n, b, out.data_ptr(), self._stream()), "pnp_nufft_adjoint_mc")
+        return out
+
+    def _ncsense_args(self, y: torch.Tensor, sens: torch.Tensor, w: Optional[torch.Tensor]):
+        m = self.nufft_samples
+        sens, coils, sens_n = self._sens(sens)
+        self._chk(y, torch.complex64, self.n * coils * m if m else y.numel(), "y")     # without a plan the library reports the state error
+        if w is not None:
+            self._chk(w, torch.float32, m, "w")
+        return y.data_ptr(), sens.data_ptr(), coils, sens_n, (w.data_ptr() if w is not None else None)
+
+    def reset_ncsense(self, x0: torch.Tensor, y: torch.Tensor, sens: torch.Tensor, w: Optional[torch.Tensor] = None,
+                      cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Install the non-Cartesian SENSE constants (y complex64 [N,C,M], sens complex64 [C,H,W] or [N,C,H,W], w float32 [M] or None) and
+        start an episode from x0 complex64 [N,1,H,W] (pnp_reset_ncsense).  Returns fresh (x f32, z c64, u c64); steps then solve the
+        k-space subproblem by `cg_iters` CG iterations on A^H W A + mu I, A p = [F_nu(S_c . p)]_c."""
+        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
+        yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
+        x = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device)
+        z = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+        u = torch.empty_like(z)
+        _lib.check(self.lib.pnp_reset_ncsense(self._h, x0.data_ptr(), yp, sp, coils, sens_n, wp, int(cg_iters), x.data_ptr(), z.data_ptr(),
+                                              u.data_ptr(), self._stream()), "pnp_reset_ncsense")
+        self.live_episode = _next_episode()
+        return x, z, u
+
+    def set_kspace_ncsense(self, y: torch.Tensor, sens: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0,
+                           cg_iters: int = 8) -> None:
+        """Re-install the non-Cartesian SENSE constants of another episode without touching any iterate (pnp_set_kspace_ncsense)."""
+        yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
+        _lib.check(self.lib.pnp_set_kspace_ncsense(self._h, yp, sp, coils, sens_n, wp, int(cg_iters), self._stream()), "pnp_set_kspace_ncsense")
+        self.live_episode = episode or _next_episode()
+
+    def ncsense_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+        """q = A^H W A p + mu p with the installed non-Cartesian SENSE constants (pnp_ncsense_normal); p complex64 [N,1,H,W], mu float32 [N]."""
+        self._chk(p, torch.complex64, self.n * self.h * self.w, "p"); self._chk(mu, torch.float32, self.n, "mu")
+        q = torch.empty_like(p)
+        _lib.check(self.lib.pnp_ncsense_normal(self._h, p.data_ptr(), mu.data_ptr(), q.data_ptr(), self._stream()), "pnp_ncsense_normal")
+        return q
+
+    def ncsense_cg_residual(self) -> torch.Tensor:
+        """float32 [N]: the relative residual the CG solve of the last step ended with (pnp_ncsense_cg_residual; that mode only)."""
+        out = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pnp_ncsense_cg_residual(self._h, out.data_ptr(), self._stream()), "pnp_ncsense_cg_residual")
+        return out
+
+    def acquire_ncsense(self, gt: torch.Tensor, sens: torch.Tensor, sigma_n: float, seed: int,
+                        dcf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Simulated multi-coil acquisition on the planned trajectory (pnp_acquire_ncsense): gt float32 [N,1,H,W]; returns
+        (y complex64 [N,C,M], aty0 = A^H (dcf . y) complex64 [N,1,H,W], x0 = max(aty0, 0))."""
+        gt = self._chk(gt, torch.float32, self.n * self.h * self.w, "gt")
+        sens, coils, sens_n = self._sens(sens)
+        m = self.nufft_samples
+        if dcf is not None:
+            self._chk(dcf, torch.float32, m, "dcf")
+        y = torch.empty((self.n, coils, max(m, 1)), dtype=torch.complex64, device=self.device)
+        aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+        x0 = torch.empty_like(aty0)
+        _lib.check(self.lib.pnp_acquire_ncsense(self._h, gt.data_ptr(), sens.data_ptr(), coils, sens_n, dcf.data_ptr() if dcf is not None else None,
+                                                float(sigma_n), int(seed) & (2 ** 64 - 1), 0, y.data_ptr(), aty0.data_ptr(), x0.data_ptr(),
+                                                self._stream()), "pnp_acquire_ncsense")
+        return y, aty0, x0
+
     # -- hot path --------------------------------------------------------------------------
     def reset(self, x0: torch.Tensor, y0: torch.Tensor, mask: torch.Tensor, sens: Optional[torch.Tensor] = None,
               cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -104,22 +104,32 @@ class PnPEnv:
             eng.nufft_plan(traj, grid=self.nufft_grid, width=self.nufft_width)
 
     def _reset_nc(self, data, x0: torch.Tensor, n: int, h: int, w: int, device) -> "OrderedDict[str, torch.Tensor]":
-        """A non-Cartesian episode: data["traj"] float64 [M,2], y0 [N,1,M,2] (or complex [N,M]), optional data["dcf"] float32 [M]."""
-        if data.get("sens") is not None:
-            raise ValueError("PnPEnv.reset: a non-Cartesian episode is single-coil (traj with sens is not supported)")
+        """A non-Cartesian episode: data["traj"] float64 [M,2], y0 [N,1,M,2] (or complex [N,M]), optional data["dcf"] float32 [M].  With
+        data["sens"] (complex [C,H,W] or [N,C,H,W]) it is a non-Cartesian SENSE episode: y0 [N,C,M,2] (or complex [N,C,M])."""
         traj = torch.as_tensor(data["traj"]).to(torch.float64).cpu().reshape(-1, 2).contiguous()      # (the caller's own tensor when it is one)
         m = traj.shape[0]
-        y0 = _as_complex(torch.as_tensor(data["y0"])).reshape(n, m).to(device).contiguous()
+        sens = data.get("sens")
+        if sens is not None:
+            sens = torch.as_tensor(sens)
+            sens = (sens if sens.is_complex() else _as_complex(sens)).to(torch.complex64)
+            if sens.dim() not in (3, 4) or tuple(sens.shape[-2:]) != (h, w) or (sens.dim() == 4 and sens.shape[0] != n):
+                raise ValueError(f"sens: expected [C,{h},{w}] or [{n},C,{h},{w}], got {tuple(sens.shape)}")
+            sens = sens.to(device).contiguous()
+        y0 = _as_complex(torch.as_tensor(data["y0"]))
+        y0 = (y0.reshape(n, m) if sens is None else y0.reshape(n, sens.shape[-3], m)).to(device).contiguous()
         dcf = data.get("dcf")
         dcf = None if dcf is None else torch.as_tensor(dcf).to(device, torch.float32).reshape(m).contiguous()
         gt = torch.as_tensor(data["gt"]).to(device).float()
         eng = self._engine_for(n, h, w, device)
         self._plan_nc(eng, traj)
-        x, z, u = eng.reset_nc(x0, y0, dcf, cg_iters=self.cg_iters)
+        if sens is None:
+            x, z, u = eng.reset_nc(x0, y0, dcf, cg_iters=self.cg_iters)
+        else:
+            x, z, u = eng.reset_ncsense(x0, y0, sens, dcf, cg_iters=self.cg_iters)
         aty0 = torch.as_tensor(data["ATy0"])[..., 0] if "ATy0" in data else None
         return OrderedDict({"x": x, "y0": y0, "z": z, "u": u, "mask": None, "gt": gt, "ATy0": aty0,
                             "T": torch.zeros(n, dtype=torch.float32, device=device),
-                            "complex_y0": data["y0"], "_episode": eng.live_episode, "sens": None, "traj": traj, "dcf": dcf})
+                            "complex_y0": data["y0"], "_episode": eng.live_episode, "sens": sens, "traj": traj, "dcf": dcf})
 
     def _bind_episode(self, eng: PnPEngine, states) -> None:
         """Make the engine's k-space constants those of `states` (env.py:88-90 reads y0 / mask from the dict)."""
@@ -133,8 +143,13 @@ class PnPEnv:
         n, h, w = eng.n, eng.h, eng.w
         if states.get("traj") is not None:
             y = states["y0"]
-            y = (y if y.is_complex() else _as_complex(y)).reshape(n, -1).to(eng.device).contiguous()
-            eng.set_kspace_nc(y, states.get("dcf"), episode=ep, cg_iters=self.cg_iters)
+            y = y if y.is_complex() else _as_complex(y)
+            if states.get("sens") is not None:  # a non-Cartesian SENSE episode
+                sens = states["sens"]
+                y = y.reshape(n, sens.shape[-3], -1).to(eng.device).contiguous()
+                eng.set_kspace_ncsense(y, sens, states.get("dcf"), episode=ep, cg_iters=self.cg_iters)
+                return
+            eng.set_kspace_nc(y.reshape(n, -1).to(eng.device).contiguous(), states.get("dcf"), episode=ep, cg_iters=self.cg_iters)
             return
         sens = states.get("sens")
         coils = 1 if sens is None else sens.shape[-3]

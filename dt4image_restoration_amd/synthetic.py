@@ -230,3 +230,30 @@ def make_problem_mc(n: int, h: int, w: int, coils: int, accel: float = 4.0, sigm
         aty0[i, 0, ..., 0], aty0[i, 0, ..., 1] = a.real, a.imag
         x0[i, 0] = np.clip(aty0[i, 0], 0.0, None)
     return {"x0": x0, "y0": y0, "ATy0": aty0, "mask": mask, "gt": gt, "x0_raw": aty0[..., 0].copy(), "sens": sens.astype(np.complex64)}
+
+
+def make_problem_ncmc(n: int, h: int, w: int, coils: int, traj: np.ndarray, dcf: np.ndarray = None, sigma_n: float = 10.0 / 255.0,
+                      seed: int = 1234, first_slice: int = 0, sens: np.ndarray = None) -> Dict[str, np.ndarray]:
+    """`make_problem_nc` for `coils` coils (non-Cartesian SENSE), by the exact NDFT in float64 (meant for small sizes): y0 float32
+    [n,coils,M,2] with y_c = A (S_c gt) + sigma_n noise_c, noise_c = the counter hash indexed by the sample m with the streams 9001 + 4 c /
+    9003 + 4 c (`make_problem_mc`'s) ; ATy0 = sum_c conj(S_c) A^H (dcf y_c) and x0 = its clip at 0, float32 [n,1,h,w,2]; sens complex64
+    [coils,h,w] (`coil_maps` unless given); gt, x0_raw, traj, dcf as in `make_problem_nc`."""
+    traj = np.asarray(traj, dtype=np.float64)
+    m = traj.shape[0]
+    d = None if dcf is None else np.asarray(dcf, dtype=np.float32)
+    sens = (coil_maps(coils, h, w) if sens is None else np.asarray(sens)).astype(np.complex64)
+    s64 = sens.astype(np.complex128)
+    gt = np.empty((n, 1, h, w), dtype=np.float32)
+    y0 = np.empty((n, coils, m, 2), dtype=np.float32)
+    aty0 = np.empty((n, 1, h, w, 2), dtype=np.float32)
+    for i in range(n):
+        s = seed + first_slice + i
+        g = phantom(h, w, s)
+        noise = np.stack([_gauss(s, 9001 + 4 * c, m) + 1j * _gauss(s, 9003 + 4 * c, m) for c in range(coils)])
+        y = ndft_np(traj, s64 * g) + sigma_n * noise
+        a = (np.conj(s64) * ndft_np(traj, y if d is None else y * d.astype(np.float64), adjoint_shape=(h, w))).sum(axis=0)
+        gt[i, 0] = g
+        y0[i, ..., 0], y0[i, ..., 1] = y.real, y.imag
+        aty0[i, 0, ..., 0], aty0[i, 0, ..., 1] = a.real, a.imag
+    x0 = np.clip(aty0, 0.0, None)
+    return {"x0": x0, "y0": y0, "ATy0": aty0, "gt": gt, "x0_raw": aty0[..., 0].copy(), "traj": traj, "dcf": d, "sens": sens}
