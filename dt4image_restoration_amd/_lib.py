@@ -128,6 +128,29 @@ SIGNATURES_NCSENSE = {
     "pnp_acquire_ncsense": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _fp, C.c_double, C.c_uint64, C.c_int, _fp, _fp, _fp, _vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/pnpadmm_toeplitz.h declares (the Toeplitz normal operator of the non-Cartesian CG stages)
+SIGNATURES_TOEPLITZ = {
+    "pnp_toeplitz_plan": (C.c_int, [C.c_void_p, _fp, C.c_int, _vp]),
+    "pnp_toeplitz_planned": (C.c_int, [C.c_void_p]),
+    "pnp_toeplitz_live": (C.c_int, [C.c_void_p]),
+    "pnp_toeplitz_spectrum": (C.c_int, [C.c_void_p, _fp, _vp]),
+    "pnp_toeplitz_apply": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, _vp]),
+    "pnp_toeplitz_apply_mc": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_set_kspace_nc_tz": (C.c_int, [C.c_void_p, _fp, C.c_int, _vp]),
+    "pnp_reset_nc_tz": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, _fp, _fp, _vp]),
+    "pnp_set_kspace_ncsense_tz": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.c_int, _vp]),
+    "pnp_reset_ncsense_tz": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _vp]),
+}
+PNP_TOEPLITZ_MAX_SIDE = 512
+
+
+def toeplitz_size_error(fn: str, h: int, w: int):
+    """The library's refusal of a slice too large for the Toeplitz operator, word for word (pnp_capi.hip: tz_check_sizes), or None: for a
+    caller that knows the size before it has a handle."""
+    if h <= PNP_TOEPLITZ_MAX_SIDE and w <= PNP_TOEPLITZ_MAX_SIDE:
+        return None
+    return f"{fn}: the Toeplitz operator transforms a 2h x 2w grid, so it takes h, w up to {PNP_TOEPLITZ_MAX_SIDE} (got {int(h)}x{int(w)})"
+
 _lib = None
 
 
@@ -144,7 +167,7 @@ def load() -> C.CDLL:
         raise PnPError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        f"or `make -C {os.path.dirname(LIB_PATH)}`; there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE}.items():
+    for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE, **SIGNATURES_TOEPLITZ}.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

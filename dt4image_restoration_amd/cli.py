@@ -106,7 +106,7 @@ def _build(args, mode):
     den = _denoiser(args)
     scorer = (lambda st: 1.0 / (1e-3 + (st["x"] - torch.nn.functional.avg_pool2d(st["x"], 3, 1, 1)).pow(2).mean(dim=(1, 2, 3))))
     env = PnPEnv(max_episode_step=30, denoiser=den, device_type="cuda", no_ref_scorer=None, cg_iters=args.cg_iters,
-                 nufft_width=args.nufft_width, nufft_grid=args.nufft_grid)
+                 nufft_width=args.nufft_width, nufft_grid=args.nufft_grid, nc_normal=args.nc_normal)
     if getattr(args, "scorer", "stub") == "neg_dc":            # minus the k-space data misfit of the rollout's final iterate (pnp_residuals)
         scorer = (lambda st: -env.residuals(st, dc=True)[:, 5])
     return model, env, scorer
@@ -219,7 +219,7 @@ def _nc_kwargs(args):
 
 def _sets(args, flex_target=None, env=None):
     """(name, number of images, load(start, stop) -> (batch dict, task tokens)) per evaluation set."""
-    from . import acquisition, data as D, synthetic
+    from . import _lib, acquisition, data as D, synthetic
     if args.traj and args.data:
         raise SystemExit("--traj: the reference's .mat layout (--data) holds Cartesian k-space and a mask; use the synthetic sets or --gt")
     if args.traj:                                            # a true radial acquisition of the --gt images, or of make_problem's phantoms
@@ -228,6 +228,10 @@ def _sets(args, flex_target=None, env=None):
                 batch = acquisition.task_problem(task, images(a, b), env, seed=args.seed, first_slice=a, **_nc_kwargs(args))
             except (ValueError, RuntimeError) as e:          # a grid the rule refuses, a slice side without a grid
                 raise SystemExit(f"--traj radial: task {task}: {e}")
+            if args.nc_normal == "toeplitz":                 # refused here, in the library's words, before any episode is set up
+                why = _lib.toeplitz_size_error("pnp_toeplitz_plan", *batch["gt"].shape[-2:])
+                if why:
+                    raise SystemExit(f"--nc-normal toeplitz: task {task}: {why}")
             return batch, D.task_tokens([task] * (b - a), flex_target)
         if args.gt:
             for d in args.gt:
@@ -369,6 +373,9 @@ def main(argv=None):
                     "off the grid (NUFFT data fidelity, CG solve), single-coil: the synthetic sets or --gt, not --data")
     ap.add_argument("--nc-coils", type=int, default=0, metavar="C", help="--traj radial: non-Cartesian SENSE, the radial acquisition of C "
                     "coils with analytic coil maps (1..32; default 0: single-coil)")
+    ap.add_argument("--nc-normal", choices=("nufft", "toeplitz"), default="nufft", help="--traj radial: the normal operator A^H W A inside the "
+                    "CG of eval / flex / mcts / fixed: the NUFFT pair, or its Toeplitz form - two transforms of the 2H x 2W grid and a multiply "
+                    "by a spectrum built once per trajectory (sides up to 512)")
     ap.add_argument("--spokes", type=int, default=None, metavar="S", help="--traj radial: spokes (default: ceil(H / acceleration) of the task)")
     ap.add_argument("--nufft-width", type=int, choices=(4, 6, 8), default=6, help="--traj: width of the gridding kernel in grid points")
     ap.add_argument("--nufft-grid", type=int, nargs=2, default=None, metavar=("GH", "GW"), help="--traj: sides of the oversampled grid (sides "
@@ -447,6 +454,15 @@ def main(argv=None):
             raise SystemExit(f"--spokes must be >= 1, got {args.spokes}")
         if args.grappa or args.mask != "radial":
             raise SystemExit("--traj takes no --mask / --grappa: its samples are a trajectory, not a mask")
+        if args.nc_normal == "toeplitz" and args.mode == "acquire":
+            raise SystemExit("acquire runs no CG: drop --nc-normal toeplitz")
+        if args.nc_normal == "toeplitz" and not getattr(args, "gt", None):      # the synthetic sets: the size is known here
+            from ._lib import toeplitz_size_error
+            why = toeplitz_size_error("pnp_toeplitz_plan", args.size, args.size)
+            if why:
+                raise SystemExit(f"--nc-normal toeplitz: {why}")
+    elif args.nc_normal != "nufft":
+        raise SystemExit(f"--nc-normal {args.nc_normal} needs --traj radial")
     elif args.nc_coils:
         raise SystemExit(f"--nc-coils needs --traj radial (got --nc-coils {args.nc_coils} without it)")
     elif args.spokes is not None or args.nufft_grid is not None or args.nufft_width != 6 or args.nc_weights != "dcf":
@@ -548,7 +564,7 @@ def main(argv=None):
         from .env import PnPEnv
         den = _denoiser(args)
         env = PnPEnv(max_episode_step=args.max_iter, denoiser=den, device_type="cuda", cg_iters=args.cg_iters,
-                     nufft_width=args.nufft_width, nufft_grid=args.nufft_grid)
+                     nufft_width=args.nufft_width, nufft_grid=args.nufft_grid, nc_normal=args.nc_normal)
         solver = FixedScheduleSolver(env, max_iter=args.max_iter, tol=args.tol, sync_every=5, dc=args.dc,
                                      device_type=torch.device("cuda", torch.cuda.current_device()))
         t = np.arange(args.max_iter) / max(args.max_iter - 1, 1)

@@ -796,6 +796,7 @@ Tuning tuning_from_env() {
     if (const char* v = getenv("PNP_HAAR_NAIVE")) t.haar_naive = atoi(v) != 0;
     if (const char* v = getenv("PNP_NCSENSE_COIL_BLOCK")) t.ncsense_block = atoi(v);
     if (const char* v = getenv("PNP_NCSENSE_NAIVE")) t.ncsense_naive = atoi(v) != 0 ? 1 : 0;
+    if (const char* v = getenv("PNP_TOEPLITZ_NAIVE")) t.toeplitz_naive = atoi(v) != 0;
     return t;
 }
 

@@ -959,6 +959,223 @@ hipError_t launch_fft_rows_inv_admm(const float2* work, const float* x, float2* 
                              : pow2::launch_fft_rows_inv_admm(work, x, z, u, tw, tact, N, H, W, s);
 }
 
+// ---- Toeplitz normal operator: the fused application (include/pnpadmm_toeplitz.h) ------------------------------------------------
+// q = crop(ifft2c(K . fft2c(pad(p)))) on the 2H x 2W grid in three launches, none of which touches the grid's zero half:
+//   rows forward : p [planes, H, W] -> zero-filled to 2W in LDS -> row transforms of the H live rows -> buf [planes, H, 2W] (centred columns)
+//   columns      : a strip's H live rows into lines of 2H, zeros elsewhere -> forward -> . K / (4 H W) -> inverse -> the H cropped rows, in
+//                  place in buf: fft_cols_body<1, LC>'s shape with K in place of the masked solve
+//   rows inverse : row transforms back, cropped to W, (+ mu p by one fma, the partial sums of Re<p, q>) -> q
+// The four orthonormal scalings are one power of two, 1 / (4 H W): it rides on K, an exact scaling of the spectrum, and the transforms
+// store unscaled.  Lines of 256 and 512 points run the register-resident radix-16 / radix-8 passes, every other length fft_lines.
+// A workgroup of the row passes owns the rows of ONE pixel chunk of a slice (block_reduce.h: kPixelChunk pixels, min(H, 2048 / W) rows,
+// at most 4096 grid elements), so the inverse pass leaves the partial sums in nufft_crop_kernel's ranges, by its tree.
+// New kernels beside the six passes above, which they leave as they were; power-of-two sides only (mixed_radix below).
+static_assert(kPixelChunk == ROW_ELEMS, "a row workgroup of the Toeplitz passes owns one pixel chunk");
+
+template <int LC>
+__device__ __forceinline__ int tz_slot(int r, int c, int L) {
+    return LC == 256 ? r * SK256_LS + sk256(c) : (LC == 512 ? r * SK512_LS + sk512(c) : r * L + c);
+}
+// the workgroup's row transforms (loads synchronised by the caller); returns the buffer holding the synchronised result
+template <bool INV, int LC>
+__device__ __forceinline__ float2* tz_row_lines(float2* buf0, float2* buf1, const float2* tw, int L, int rows) {
+    if constexpr (LC == 256) { fft256_radix16_inplace<INV, 16>(buf0, tw); return buf0; }
+    else if constexpr (LC == 512) { fft512_radix8_inplace<INV, 8, 32>(buf0, tw); return buf0; }
+    else return fft_lines<INV>(buf0, buf1, tw, L, rows, L);
+}
+static inline int tz_rows_per_block(int H, int W) { return H < kPixelChunk / W ? H : kPixelChunk / W; }
+static inline size_t tz_rows_lds(int L, int rows) {
+    return (size_t)(L == 256 ? 16 * SK256_LS + L : (L == 512 ? 8 * SK512_LS + L : 2 * rows * L + L)) * sizeof(float2);
+}
+
+// LC: 256 / 512 = the line length 2W, on the register-resident passes (16 / 8 rows per workgroup); 0: any other length
+template <int LC>
+__global__ __launch_bounds__(256) void tz_rows_fwd_kernel(const float2* __restrict__ p, float2* __restrict__ out, const float2* __restrict__ twg,
+                                                          int H, int W, int rows) {
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    const int L = 2 * W, lw = 31 - __builtin_clz(L), tot = rows * L;
+    const int blocks_per_img = H / rows;
+    const int n = blockIdx.x / blocks_per_img, y0 = (blockIdx.x % blocks_per_img) * rows;
+    float2* buf0 = smem;
+    float2* buf1 = smem + (LC ? 0 : tot);
+    float2* tw = smem + (LC == 256 ? 16 * SK256_LS : (LC == 512 ? 8 * SK512_LS : 2 * tot));
+    for (int i = threadIdx.x; i < L; i += 256) tw[i] = twg[i];
+    const float2* src = p + ((size_t)n * H + y0) * W;
+    for (int e = threadIdx.x; e < tot; e += 256) {
+        const int r = e >> lw, c = e & (L - 1);
+        const int ix = (c ^ W) - W / 2;                    // position c of the unshifted line holds the centred padded column c ^ W
+        float2 v = make_float2(0.f, 0.f);
+        if (ix >= 0 && ix < W) v = src[(size_t)r * W + ix];
+        buf0[tz_slot<LC>(r, c, L)] = v;
+    }
+    __syncthreads();
+    const float2* res = tz_row_lines<false, LC>(buf0, buf1, tw, L, rows);
+    float2* dst = out + ((size_t)n * H + y0) * L;
+    for (int e = threadIdx.x; e < tot; e += 256) {
+        const int r = e >> lw, c = e & (L - 1);
+        dst[(size_t)r * L + (c ^ W)] = res[tz_slot<LC>(r, c, L)];
+    }
+}
+
+template <int LC>
+__global__ __launch_bounds__(256) void tz_rows_inv_kernel(const float2* __restrict__ in, const float2* __restrict__ twg,
+                                                          const float2* __restrict__ pv, const float* __restrict__ mu,
+                                                          const float* __restrict__ tact, float2* __restrict__ q, double* __restrict__ partial,
+                                                          int H, int W, int rows) {
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    __shared__ double red[256 / 64];
+    const int L = 2 * W, lw = 31 - __builtin_clz(L), tot = rows * L;
+    const int chunks = H / rows;                           // = pixel_chunks(H, W)
+    const int n = blockIdx.x / chunks, chunk = blockIdx.x % chunks, y0 = chunk * rows;
+    if (tact != nullptr && tact[n] > 0.5f) return;
+    float2* buf0 = smem;
+    float2* buf1 = smem + (LC ? 0 : tot);
+    float2* tw = smem + (LC == 256 ? 16 * SK256_LS : (LC == 512 ? 8 * SK512_LS : 2 * tot));
+    for (int i = threadIdx.x; i < L; i += 256) tw[i] = twg[i];
+    const float2* src = in + ((size_t)n * H + y0) * L;
+    for (int e = threadIdx.x; e < tot; e += 256) {
+        const int r = e >> lw, c = e & (L - 1);
+        buf0[tz_slot<LC>(r, c, L)] = src[(size_t)r * L + (c ^ W)];
+    }
+    __syncthreads();
+    const float2* res = tz_row_lines<true, LC>(buf0, buf1, tw, L, rows);
+    const int px = rows * W, lpw = 31 - __builtin_clz(W);
+    const size_t base = ((size_t)n * H + y0) * W;
+    const float m = (pv != nullptr && mu != nullptr) ? mu[n] : 0.f;
+    double dot[1] = {0.0};
+#pragma unroll
+    for (int j = 0; j < kPixelChunk / 256; ++j) {
+        const int pl = threadIdx.x + j * 256;              // nufft_crop_kernel's pixel order within the chunk
+        if (pl < px) {
+            const int r = pl >> lpw, ix = pl & (W - 1);
+            float2 o = res[tz_slot<LC>(r, (ix + W / 2) ^ W, L)];
+            if (pv != nullptr) {
+                const float2 pp = pv[base + pl];
+                o.x = __fmaf_rn(m, pp.x, o.x); o.y = __fmaf_rn(m, pp.y, o.y);
+                dot[0] += (double)pp.x * (double)o.x + (double)pp.y * (double)o.y;
+            }
+            q[base + pl] = o;
+        }
+    }
+    if (partial == nullptr) return;                        // (uniform)
+    block_sums_fixed<256, 1>(dot, red);
+    if (threadIdx.x == 0) partial[((size_t)n * chunks + chunk) * 2] = dot[0];
+}
+
+// LC: 256 / 512 = the line length 2H on the register-resident passes (strips of 16 / 8 columns, in place in one skewed buffer); 0: any other
+template <int LC>
+__global__ __launch_bounds__(256) void tz_cols_kernel(float2* __restrict__ data, const float* __restrict__ K, const float2* __restrict__ twg, int H,
+                                                      int W, int cw) {
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    constexpr bool R16 = LC == 256, R8 = LC == 512;
+    const int L = 2 * H, GW = 2 * W, strips = GW / cw;
+    int vb = blockIdx.x;                                   // fft_cols_kernel's (slice, strip) -> XCD map
+    if ((gridDim.x & 7) == 0) vb = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
+    const int n = vb / strips, x0 = (vb % strips) * cw;
+    const int lstr = R16 ? SK256_LS : (R8 ? SK512_LS : L + 1);
+    auto rpos = [](int r) { return R16 ? sk256(r) : (R8 ? sk512(r) : r); };
+    float2* buf0 = smem;
+    float2* buf1 = smem + cw * lstr;
+    float2* tw = smem + (LC > 0 ? 1 : 2) * cw * lstr;
+    float2* img = data + (size_t)n * H * GW;
+    const int lcw = 31 - __builtin_clz(cw), tot = cw * L;
+    const float inv = 1.f / (4.f * (float)H * (float)W);   // a power of two
+    for (int i = threadIdx.x; i < L; i += 256) tw[i] = twg[i];
+    for (int e = threadIdx.x; e < tot; e += 256) {
+        const int r = e >> lcw, c = e & (cw - 1);
+        const int iy = (r ^ H) - H / 2;                    // position r of the unshifted line holds the centred padded row r ^ H
+        float2 v = make_float2(0.f, 0.f);
+        if (iy >= 0 && iy < H) v = img[(size_t)iy * GW + x0 + c];
+        buf0[c * lstr + rpos(r)] = v;
+    }
+    const float2* res;
+    if constexpr (LC > 0) {
+        // 2H == LC, cw == CWC (checked by the launcher): the strip's K values are fetched BEFORE the forward transform and sit in registers under it
+        constexpr int CWC = LC <= 256 ? 16 : 8, LS = R16 ? SK256_LS : SK512_LS, PER = CWC * LC / 256;
+        float kk[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int e = threadIdx.x + k * 256;
+            kk[k] = K[(size_t)((e / CWC) ^ H) * GW + x0 + (e % CWC)];
+        }
+        __syncthreads();
+        if constexpr (R16) fft256_radix16_inplace<false, CWC>(buf0, tw);
+        else fft512_radix8_inplace<false, CWC, 32>(buf0, tw);
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int e = threadIdx.x + k * 256;
+            float2* p = &buf0[(e % CWC) * LS + rpos(e / CWC)];
+            const float f = kk[k] * inv;
+            float2 v = *p;
+            v.x *= f; v.y *= f;
+            *p = v;
+        }
+        __syncthreads();
+        if constexpr (R16) fft256_radix16_inplace<true, CWC>(buf0, tw);
+        else fft512_radix8_inplace<true, CWC, 32>(buf0, tw);
+        res = buf0;
+    } else {
+        __syncthreads();
+        float2* fw = fft_lines<false>(buf0, buf1, tw, L, cw, lstr);
+        float2* oth = (fw == buf0) ? buf1 : buf0;
+        for (int e = threadIdx.x; e < tot; e += 256) {
+            const int r = e >> lcw, c = e & (cw - 1);
+            const float f = K[(size_t)(r ^ H) * GW + x0 + c] * inv;
+            float2 v = fw[c * lstr + r];
+            v.x *= f; v.y *= f;
+            fw[c * lstr + r] = v;
+        }
+        __syncthreads();
+        res = fft_lines<true>(fw, oth, tw, L, cw, lstr);
+    }
+    for (int e = threadIdx.x; e < cw * H; e += 256) {
+        const int iy = e >> lcw, c = e & (cw - 1);
+        img[(size_t)iy * GW + x0 + c] = res[c * lstr + rpos((iy + H / 2) ^ H)];
+    }
+}
+
+static hipError_t tz_raise_lds_cap() {
+    static DeviceOnce once[3];
+    const void* fns[3] = {(const void*)tz_rows_fwd_kernel<0>, (const void*)tz_rows_inv_kernel<0>, (const void*)tz_cols_kernel<0>};
+    for (int i = 0; i < 3; ++i)
+        if (hipError_t e = pnp::raise_lds_cap(fns[i], 80 * 1024, once[i]); e != hipSuccess) return e;
+    return hipSuccess;
+}
+
+bool toeplitz_fused_ok(int H, int W) { return !mixed_radix(2 * H, 2 * W); }
+
+hipError_t launch_toeplitz_rows_fwd(const float2* p, float2* buf, const float2* tw, int planes, int H, int W, hipStream_t s) {
+    if (!toeplitz_fused_ok(H, W)) return hipErrorInvalidValue;
+    if (hipError_t e = tz_raise_lds_cap()) return e;
+    const int rows = tz_rows_per_block(H, W), L = 2 * W;
+    const dim3 g((unsigned)(planes * (H / rows)));
+    if (L == 256) hipLaunchKernelGGL((tz_rows_fwd_kernel<256>), g, dim3(256), tz_rows_lds(L, rows), s, p, buf, tw, H, W, rows);
+    else if (L == 512) hipLaunchKernelGGL((tz_rows_fwd_kernel<512>), g, dim3(256), tz_rows_lds(L, rows), s, p, buf, tw, H, W, rows);
+    else hipLaunchKernelGGL((tz_rows_fwd_kernel<0>), g, dim3(256), tz_rows_lds(L, rows), s, p, buf, tw, H, W, rows);
+    return hipGetLastError();
+}
+hipError_t launch_toeplitz_cols(float2* buf, const float* K, const float2* tw, int planes, int H, int W, hipStream_t s) {
+    if (!toeplitz_fused_ok(H, W)) return hipErrorInvalidValue;
+    if (hipError_t e = tz_raise_lds_cap()) return e;
+    const int L = 2 * H, cw = cols_per_block(L, 2 * W);
+    const dim3 g((unsigned)(planes * (2 * W / cw)));
+    if (L == 256) hipLaunchKernelGGL((tz_cols_kernel<256>), g, dim3(256), (size_t)(cw * SK256_LS + L) * sizeof(float2), s, buf, K, tw, H, W, cw);
+    else if (L == 512) hipLaunchKernelGGL((tz_cols_kernel<512>), g, dim3(256), (size_t)(cw * SK512_LS + L) * sizeof(float2), s, buf, K, tw, H, W, cw);
+    else hipLaunchKernelGGL((tz_cols_kernel<0>), g, dim3(256), (size_t)(2 * cw * (L + 1) + L) * sizeof(float2), s, buf, K, tw, H, W, cw);
+    return hipGetLastError();
+}
+hipError_t launch_toeplitz_rows_inv(const float2* buf, const float2* tw, const float2* pv, const float* mu, const float* tact, float2* q,
+                                    double* partial, int planes, int H, int W, hipStream_t s) {
+    if (!toeplitz_fused_ok(H, W)) return hipErrorInvalidValue;
+    if (hipError_t e = tz_raise_lds_cap()) return e;
+    const int rows = tz_rows_per_block(H, W), L = 2 * W;
+    const dim3 g((unsigned)(planes * (H / rows)));
+    if (L == 256) hipLaunchKernelGGL((tz_rows_inv_kernel<256>), g, dim3(256), tz_rows_lds(L, rows), s, buf, tw, pv, mu, tact, q, partial, H, W, rows);
+    else if (L == 512) hipLaunchKernelGGL((tz_rows_inv_kernel<512>), g, dim3(256), tz_rows_lds(L, rows), s, buf, tw, pv, mu, tact, q, partial, H, W, rows);
+    else hipLaunchKernelGGL((tz_rows_inv_kernel<0>), g, dim3(256), tz_rows_lds(L, rows), s, buf, tw, pv, mu, tact, q, partial, H, W, rows);
+    return hipGetLastError();
+}
+
 // ---- reset: x = Re(x0), z = x0, u = 0; fold the fftshifts into the episode constants -------------
 __global__ void reset_kernel(const float2* __restrict__ x0, const float2* __restrict__ y0,
                              const uint8_t* __restrict__ mask, int mask_n, float* __restrict__ x,

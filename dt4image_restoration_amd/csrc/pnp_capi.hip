@@ -2,6 +2,7 @@
 // sequencing of one PnP-ADMM iteration, kernel-level event timing.
 #include "../../include/pnpadmm.h"
 #include "../../include/pnpadmm_ncsense.h"
+#include "../../include/pnpadmm_toeplitz.h"
 #include "pnp_internal.h"
 #include "denoiser_plan.h"
 #include "nufft_plan.h"
@@ -152,6 +153,20 @@ struct pnp_engine {
     int ns_sens_n = 1;
     bool ns_has_w = false;
     int ns_cg = 0;               // CG iterations per step
+    // Toeplitz normal operator (include/pnpadmm_toeplitz.h): the spectrum and its buffers by pnp_toeplitz_plan
+    std::vector<double> nc_traj; // host copy of the planned trajectory [M][2] (ky, kx): what the spectrum is built from
+    double* tz_traj = nullptr;   // [M][2] its device copy
+    float* tz_k = nullptr;       // [2H, 2W] the spectrum, centred
+    float* tz_w = nullptr;       // [M] the weights the spectrum was built with (read only while tz_has_w): the installers' weights
+    float2* tz_tw_h = nullptr;   // twiddles of 2H and 2W
+    float2* tz_tw_w = nullptr;
+    bool tz_fused = false;       // the application runs its three fused launches (set at pnp_create: a power-of-two padded grid and no
+                                 // PNP_TOEPLITZ_NAIVE); else the seven composed ones
+    float2* tz_grid = nullptr;   // the pass buffer, N planes (N cb for a multi-coil application): [planes, H, 2W] fused, [planes, 2H, 2W] composed
+    size_t tz_traj_cap = 0, tz_k_cap = 0, tz_w_cap = 0, tz_twh_cap = 0, tz_tww_cap = 0, tz_grid_cap = 0;
+    bool tz_planned = false;     // a spectrum exists for the handle's NUFFT plan
+    bool tz_has_w = false;
+    bool tz_on = false;          // the live non-Cartesian stage (nc_on or ns_coils > 0) runs its CG on the Toeplitz operator
     // the prior of pnp_step (pnp_set_prior) and the total-variation denoiser's workspace (allocated inside the first call that runs it)
     int prior = PNP_PRIOR_UNET;
     double tv_scale = 1.0;       // as given; applied as float32
@@ -532,6 +547,74 @@ int ns_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
     return PNP_OK;
 }
 
+// ---- Toeplitz normal operator (include/pnpadmm_toeplitz.h) ----------------------------------------------
+// q [planes, h, w] = crop(ifft2c(K . fft2c(pad(src)))) (+ mu pv with the partial sums of Re<pv, q>: the last launch's epilogue), through
+// tz_grid.  Three fused launches, or the seven composed ones; src may be q (the grid lies between them).  Stopped slices: only the last
+// launch skips them
+int tz_apply(pnp_engine* e, const float2* src, int planes, const float2* pv, const float* mu, const float* tact, float2* q, double* partial,
+             hipStream_t s) {
+    const int H = e->cfg.h, W = e->cfg.w;
+    if (e->tz_fused) {
+        {
+            Prof p(e, s, PROF_FFT_ROWS, -1);
+            HIP_TRY(launch_toeplitz_rows_fwd(src, e->tz_grid, e->tz_tw_w, planes, H, W, s));
+        }
+        {
+            Prof p(e, s, PROF_FFT_COLS, -1);
+            HIP_TRY(launch_toeplitz_cols(e->tz_grid, e->tz_k, e->tz_tw_h, planes, H, W, s));
+        }
+        Prof p(e, s, PROF_FFT_ROWS, -1);
+        HIP_TRY(launch_toeplitz_rows_inv(e->tz_grid, e->tz_tw_w, pv, mu, tact, q, partial, planes, H, W, s));
+        return PNP_OK;
+    }
+    auto fft = [&](int inverse) -> int {
+        {
+            Prof p(e, s, PROF_FFT_ROWS, -1);
+            HIP_TRY(launch_fft_rows(e->tz_grid, e->tz_grid, e->tz_tw_w, planes, 2 * H, 2 * W, inverse, W, s));
+        }
+        Prof p(e, s, PROF_FFT_COLS, -1);
+        HIP_TRY(launch_fft_cols(e->tz_grid, e->tz_tw_h, planes, 2 * H, 2 * W, inverse, H, s));
+        return PNP_OK;
+    };
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_toeplitz_pad(src, e->tz_grid, H, W, planes, s));
+    }
+    if (int rc = fft(0)) return rc;
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_toeplitz_mul(e->tz_grid, e->tz_k, H, W, planes, s));
+    }
+    if (int rc = fft(1)) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_toeplitz_crop(e->tz_grid, pv, mu, tact, q, partial, H, W, planes, s));
+    return PNP_OK;
+}
+// out [batch, h, w] (+)= sum over the coils of conj(S_c) . Toep(S_c . src), block by block through ns_img; the last block adds mu pv and leaves
+// the partial sums of Re<pv, out> (pv, mu, tact, partial may be nullptr)
+int tz_apply_mc(pnp_engine* e, const float2* src, const float2* sens, int sens_n, int C, int batch, const float2* pv, const float* mu,
+                const float* tact, float2* out, double* partial, hipStream_t s) {
+    const int B = ns_block_of(e, C);
+    for (int c0 = 0; c0 < C; c0 += B) {
+        const int cb = std::min(B, C - c0);
+        {
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_ncsense_expand(src, nullptr, sens, sens_n, C, c0, cb, e->nc, e->ns_img, batch, s));
+        }
+        if (int rc = tz_apply(e, e->ns_img, batch * cb, nullptr, nullptr, nullptr, e->ns_img, nullptr, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_ncsense_combine(e->ns_img, sens, sens_n, C, c0, cb, e->nc, pv, mu, tact, out, partial, batch, s));
+    }
+    return PNP_OK;
+}
+// the two stages' normal operators in Toeplitz form: q = A^H W A pv + mu pv, the partial sums of Re<pv, q> in mc_part
+int tz_nc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    return tz_apply(e, pv, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
+}
+int tz_ns_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    return tz_apply_mc(e, pv, e->ns_sens, e->ns_sens_n, e->ns_coils, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
+}
+
 // the K-step CG solve of (A^H A + mu I) z = A^H y + mu (x + u), warm-started from z, then u <- u + x - z; `normal`: the stage's normal
 // operator (mc_normal: the coil operator, nc_normal: the NUFFT pair, ns_normal: both), which also leaves the partial sums of Re<p, q> in mc_part
 using NormalOp = int (*)(pnp_engine*, const float2*, const float*, const float*, float2*, hipStream_t);
@@ -646,6 +729,7 @@ int mc_install(pnp_engine* e, const float2* x0, const float2* y0, const float2* 
     e->mc_coils = coils; e->mc_cg = cg_iters; e->mc_sens_n = sens_n;
     e->nc_on = false;
     e->ns_coils = 0;
+    e->tz_on = false;
     e->reset_done = true;
     {
         Prof p(e, s, PROF_OTHER, -1);
@@ -783,8 +867,9 @@ int run_haar(pnp_engine* e, const float* v, const float2* z, const float2* u, co
 int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                   hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
-    if (e->ns_coils > 0) return run_prox_dual_cg(e, ns_normal, e->ns_cg, mu, tact, x, z, u, s);  // non-Cartesian SENSE constants installed last
-    if (e->nc_on) return run_prox_dual_cg(e, nc_normal, e->nc_cg, mu, tact, x, z, u, s);         // non-Cartesian constants installed last
+    // non-Cartesian SENSE / non-Cartesian constants installed last; a _tz installer: the same CG on the Toeplitz operator
+    if (e->ns_coils > 0) return run_prox_dual_cg(e, e->tz_on ? tz_ns_normal : ns_normal, e->ns_cg, mu, tact, x, z, u, s);
+    if (e->nc_on) return run_prox_dual_cg(e, e->tz_on ? tz_nc_normal : nc_normal, e->nc_cg, mu, tact, x, z, u, s);
     if (e->mc_coils > 0) return run_prox_dual_cg(e, mc_normal, e->mc_cg, mu, tact, x, z, u, s);   // multi-coil constants installed: the CG stage
     if (H == 128 && W == 128 && N >= e->tune.slice128_min_n) {   // chip-filling batches of the reference's slice size: 37 B/px
         Prof p(e, s, PROF_FFT_COLS, -1);
@@ -876,6 +961,7 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     e->tune = tune;
     if (tune.ncsense_block >= 1 && tune.ncsense_block <= PNP_MC_MAX_COILS) e->ns_block = tune.ncsense_block;   // a check and a timing knob
     if (tune.ncsense_naive >= 0) e->ns_naive = tune.ncsense_naive ? NS_ALL : 0;
+    e->tz_fused = !tune.toeplitz_naive && kspace_len_ok(2 * cfg->h) && kspace_len_ok(2 * cfg->w) && toeplitz_fused_ok(cfg->h, cfg->w);
     e->dplan = plan;
     int rc;
     {
@@ -909,6 +995,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->nc.i0); (void)hipFree(e->nc.wts); (void)hipFree(e->nc.cy); (void)hipFree(e->nc.cx); (void)hipFree(e->nc.bin_off); (void)hipFree(e->nc.bin_idx);
     (void)hipFree(e->nc.tw_gh); (void)hipFree(e->nc.tw_gw);
     (void)hipFree(e->ns_img);
+    (void)hipFree(e->tz_traj); (void)hipFree(e->tz_k); (void)hipFree(e->tz_w); (void)hipFree(e->tz_tw_h); (void)hipFree(e->tz_tw_w); (void)hipFree(e->tz_grid);
     (void)hipFree(e->ns_grid); (void)hipFree(e->ns_samp); (void)hipFree(e->ns_y); (void)hipFree(e->ns_sens); (void)hipFree(e->ns_w); (void)hipFree(e->ns_mpart);
     (void)hipFree(e->nc_grid); (void)hipFree(e->nc_samp); (void)hipFree(e->nc_y); (void)hipFree(e->nc_w); (void)hipFree(e->nc_mpart);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
@@ -1000,6 +1087,7 @@ int pnp_reset(pnp_handle e, const float* x0, const float* y0, const uint8_t* mas
     e->mc_coils = 0;                                       // back to the single-coil stage
     e->nc_on = false;
     e->ns_coils = 0;
+    e->tz_on = false;
     HIP_TRY(launch_reset((const float2*)x0, (const float2*)y0, mask, mask_n, x, (float2*)z, (float2*)u, e->d_y0s,
                          e->d_masks, e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
     e->reset_done = true;
@@ -1017,6 +1105,7 @@ int pnp_set_kspace(pnp_handle e, const float* y0, const uint8_t* mask, int mask_
     e->mc_coils = 0;                                       // back to the single-coil stage
     e->nc_on = false;
     e->ns_coils = 0;
+    e->tz_on = false;
     HIP_TRY(launch_reset(nullptr, (const float2*)y0, mask, mask_n, nullptr, nullptr, nullptr, e->d_y0s, e->d_masks,
                          e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
     e->reset_done = true;
@@ -1453,6 +1542,7 @@ int nc_install(pnp_engine* e, const float2* x0, const float2* y, const float* w,
     e->nc_has_w = w != nullptr;
     e->nc_cg = cg_iters;
     e->nc_on = true;
+    e->tz_on = false;
     e->mc_coils = 0;
     e->ns_coils = 0;
     e->reset_done = true;
@@ -1503,6 +1593,9 @@ int pnp_nufft_plan(pnp_handle e, const double* traj, int64_t m, int gh, int gw, 
     // from here on the old plan is gone: its non-Cartesian constants are dropped with it
     D.m = 0;
     if (e->nc_on || e->ns_coils > 0) { e->nc_on = false; e->ns_coils = 0; e->reset_done = false; }
+    e->tz_on = false;
+    e->tz_planned = false;                                  // the spectrum belongs to the plan it was built for
+    e->nc_traj.assign(traj, traj + 2 * (size_t)m);
     HIP_TRY(nc_upload(D.i0, P.i0.data(), P.i0.size() * sizeof(int32_t)));
     HIP_TRY(nc_upload(D.wts, P.wts.data(), P.wts.size() * sizeof(float)));
     HIP_TRY(nc_upload(D.cy, P.cy.data(), P.cy.size() * sizeof(float)));
@@ -1597,7 +1690,7 @@ int pnp_nc_normal(pnp_handle e, const float* pv, const float* mu, float* q, void
     if (pv == q) return fail(PNP_ERR_INVALID, "pnp_nc_normal: p and q must not alias");
     if (int rc = nc_need_mode("pnp_nc_normal", e)) return rc;
     PNP_ON_DEVICE(e);
-    return nc_normal(e, (const float2*)pv, mu, nullptr, (float2*)q, (hipStream_t)stream);
+    return (e->tz_on ? tz_nc_normal : nc_normal)(e, (const float2*)pv, mu, nullptr, (float2*)q, (hipStream_t)stream);
     PNP_API_END("pnp_nc_normal")
 }
 
@@ -1687,6 +1780,7 @@ int ns_install(pnp_engine* e, const float2* x0, const float2* y, const float2* s
     // every launch was accepted: only now does the handle change mode (nc_install's rule)
     e->ns_coils = coils; e->ns_sens_n = sens_n; e->ns_has_w = w != nullptr; e->ns_cg = cg_iters;
     e->nc_on = false;
+    e->tz_on = false;
     e->mc_coils = 0;
     e->reset_done = true;
     return PNP_OK;
@@ -1782,7 +1876,7 @@ int pnp_ncsense_normal(pnp_handle e, const float* pv, const float* mu, float* q,
     if (pv == q) return fail(PNP_ERR_INVALID, "pnp_ncsense_normal: p and q must not alias");
     if (int rc = ns_need_mode("pnp_ncsense_normal", e)) return rc;
     PNP_ON_DEVICE(e);
-    return ns_normal(e, (const float2*)pv, mu, nullptr, (float2*)q, (hipStream_t)stream);
+    return (e->tz_on ? tz_ns_normal : ns_normal)(e, (const float2*)pv, mu, nullptr, (float2*)q, (hipStream_t)stream);
     PNP_API_END("pnp_ncsense_normal")
 }
 
@@ -1820,6 +1914,196 @@ int pnp_acquire_ncsense(pnp_handle e, const float* gt, const float* sens, int co
     }
     return PNP_OK;
     PNP_API_END("pnp_acquire_ncsense")
+}
+
+// ---- Toeplitz normal operator (include/pnpadmm_toeplitz.h) ----------------------------------------------
+static_assert(2 * PNP_TOEPLITZ_MAX_SIDE == 1024, "the padded grid's sides are sides of the k-space stage");
+
+namespace {
+
+int tz_check_sizes(const char* fn, const pnp_engine* e) {
+    if (e->cfg.h <= PNP_TOEPLITZ_MAX_SIDE && e->cfg.w <= PNP_TOEPLITZ_MAX_SIDE)
+        return kspace_len_ok(2 * e->cfg.h) && kspace_len_ok(2 * e->cfg.w)
+                   ? PNP_OK
+                   : fail(PNP_ERR_INVALID, "%s: 2h and 2w must be sides of the k-space stage {" PNP_KSPACE_SIZES "} (got %dx%d)", fn, e->cfg.h, e->cfg.w);
+    return fail(PNP_ERR_INVALID, "%s: the Toeplitz operator transforms a 2h x 2w grid, so it takes h, w up to %d (got %dx%d)", fn,
+                PNP_TOEPLITZ_MAX_SIDE, e->cfg.h, e->cfg.w);
+}
+int tz_need_spectrum(const char* fn, const pnp_engine* e) {
+    if (int rc = nc_need_plan(fn, e)) return rc;
+    return e->tz_planned ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no Toeplitz spectrum (pnp_toeplitz_plan)", fn);
+}
+// the pass buffer for `planes` planes and, with `coil_images`, the block's coil images
+int tz_ensure(pnp_engine* e, size_t planes, bool coil_images) {
+    const size_t hw = (size_t)e->cfg.h * e->cfg.w;
+    return ws_grow(e, "Toeplitz scratch", {{(void**)&e->tz_grid, &e->tz_grid_cap, planes * (e->tz_fused ? 2 : 4) * hw * sizeof(float2), false},
+                                          {(void**)&e->ns_img, &e->ns_img_cap, coil_images ? planes * hw * sizeof(float2) : 0, false}});
+}
+
+}  // namespace
+
+int pnp_toeplitz_plan(pnp_handle e, const float* weights, int flags, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_toeplitz_plan";
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = nc_need_plan(fn, e)) return rc;
+    if (int rc = tz_check_sizes(fn, e)) return rc;
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    const size_t M = (size_t)e->nc.m;
+    const std::vector<float2> twh = twiddle_table(2 * H), tww = twiddle_table(2 * W);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ws_grow(e, "Toeplitz spectrum", {{(void**)&e->tz_k, &e->tz_k_cap, (size_t)4 * H * W * sizeof(float), false},
+                                                  {(void**)&e->tz_w, &e->tz_w_cap, weights ? M * sizeof(float) : 0, false},
+                                                  {(void**)&e->tz_traj, &e->tz_traj_cap, M * 2 * sizeof(double), false},
+                                                  {(void**)&e->tz_tw_h, &e->tz_twh_cap, twh.size() * sizeof(float2), false},
+                                                  {(void**)&e->tz_tw_w, &e->tz_tww_cap, tww.size() * sizeof(float2), false},
+                                                  {(void**)&e->tz_grid, &e->tz_grid_cap, (size_t)N * (e->tz_fused ? 2 : 4) * H * W * sizeof(float2), false}}))
+        return rc;
+    if (e->tz_planned) (void)hipDeviceSynchronize();        // no launch still reads the spectrum being replaced
+    // from here on the old spectrum is gone: a live Toeplitz stage's constants are dropped with it, as pnp_nufft_plan drops them
+    e->tz_planned = false;
+    if (e->tz_on) { e->tz_on = false; e->nc_on = false; e->ns_coils = 0; e->reset_done = false; }
+    HIP_TRY(nc_upload(e->tz_traj, e->nc_traj.data(), M * 2 * sizeof(double)));
+    HIP_TRY(nc_upload(e->tz_tw_h, twh.data(), twh.size() * sizeof(float2)));
+    HIP_TRY(nc_upload(e->tz_tw_w, tww.data(), tww.size() * sizeof(float2)));
+    if (weights) HIP_TRY(hipMemcpyAsync(e->tz_w, weights, M * sizeof(float), hipMemcpyDeviceToDevice, s));
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_toeplitz_spectrum(e->tz_traj, weights ? e->tz_w : nullptr, e->nc.m, H, W, e->tz_k, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    e->tz_has_w = weights != nullptr;
+    e->tz_planned = true;
+    return PNP_OK;
+    PNP_API_END("pnp_toeplitz_plan")
+}
+
+int pnp_toeplitz_planned(pnp_handle e) { return e && e->tz_planned ? 1 : 0; }
+int pnp_toeplitz_live(pnp_handle e) { return e && e->tz_on ? 1 : 0; }
+
+int pnp_toeplitz_spectrum(pnp_handle e, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_toeplitz_spectrum";
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = tz_need_spectrum(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    HIP_TRY(hipMemcpyAsync(out, e->tz_k, (size_t)4 * e->cfg.h * e->cfg.w * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PNP_OK;
+    PNP_API_END("pnp_toeplitz_spectrum")
+}
+
+int pnp_toeplitz_apply(pnp_handle e, const float* img, int batch, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_toeplitz_apply";
+    if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
+    if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (img == out) return fail(PNP_ERR_INVALID, "%s: out must not alias img", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
+    if (int rc = tz_need_spectrum(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    return tz_apply(e, (const float2*)img, batch, nullptr, nullptr, nullptr, (float2*)out, nullptr, (hipStream_t)stream);
+    PNP_API_END("pnp_toeplitz_apply")
+}
+
+int pnp_toeplitz_apply_mc(pnp_handle e, const float* img, const float* sens, int coils, int sens_n, int batch, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_toeplitz_apply_mc";
+    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
+    if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (out == img || out == sens) return fail(PNP_ERR_INVALID, "%s: out must not alias img or sens", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
+    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    if (int rc = tz_need_spectrum(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = tz_ensure(e, (size_t)e->cfg.n * ns_block_of(e, coils), true)) return rc;
+    return tz_apply_mc(e, (const float2*)img, (const float2*)sens, sens_n, coils, batch, nullptr, nullptr, nullptr, (float2*)out, nullptr,
+                       (hipStream_t)stream);
+    PNP_API_END("pnp_toeplitz_apply_mc")
+}
+
+int pnp_set_kspace_nc_tz(pnp_handle e, const float* y, int cg_iters, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_set_kspace_nc_tz";
+    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = tz_need_spectrum(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = nc_install(e, nullptr, (const float2*)y, e->tz_has_w ? e->tz_w : nullptr, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream))
+        return rc;
+    e->tz_on = true;
+    return PNP_OK;
+    PNP_API_END("pnp_set_kspace_nc_tz")
+}
+
+int pnp_reset_nc_tz(pnp_handle e, const float* x0, const float* y, int cg_iters, float* x, float* z, float* u, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_reset_nc_tz";
+    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
+    if (!x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (!x || !z || !u) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = tz_need_spectrum(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = nc_install(e, (const float2*)x0, (const float2*)y, e->tz_has_w ? e->tz_w : nullptr, cg_iters, x, (float2*)z, (float2*)u,
+                            (hipStream_t)stream))
+        return rc;
+    e->tz_on = true;
+    return PNP_OK;
+    PNP_API_END("pnp_reset_nc_tz")
+}
+
+int pnp_set_kspace_ncsense_tz(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, int cg_iters, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_set_kspace_ncsense_tz";
+    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    if (int rc = tz_need_spectrum(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = tz_ensure(e, (size_t)e->cfg.n * ns_block_of(e, coils), true)) return rc;
+    if (int rc = ns_install(e, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, e->tz_has_w ? e->tz_w : nullptr, cg_iters, nullptr,
+                            nullptr, nullptr, (hipStream_t)stream))
+        return rc;
+    e->tz_on = true;
+    return PNP_OK;
+    PNP_API_END("pnp_set_kspace_ncsense_tz")
+}
+
+int pnp_reset_ncsense_tz(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, int cg_iters, float* x, float* z,
+                         float* u, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_reset_ncsense_tz";
+    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
+    if (!x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!x || !z || !u) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    if (int rc = tz_need_spectrum(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = tz_ensure(e, (size_t)e->cfg.n * ns_block_of(e, coils), true)) return rc;
+    if (int rc = ns_install(e, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, e->tz_has_w ? e->tz_w : nullptr, cg_iters, x,
+                            (float2*)z, (float2*)u, (hipStream_t)stream))
+        return rc;
+    e->tz_on = true;
+    return PNP_OK;
+    PNP_API_END("pnp_reset_ncsense_tz")
 }
 
 int pnp_estimate_sens(pnp_handle e, const float* y0, int coils, int acs_h, int acs_w, int window, double thresh, int flags, float* sens,

@@ -39,6 +39,7 @@ struct Tuning {
     int ncsense_block = 0;        // PNP_NCSENSE_COIL_BLOCK (tests, timing): coils per block of the non-Cartesian SENSE stage, 1..32 (else: kNcsenseBlock)
     int ncsense_naive = -1;       // PNP_NCSENSE_NAIVE (tests, timing): 1 = every step of that stage as the single-coil launches between an expand and a
                                   // combine kernel, 0 = every step coil-batched; unset: kNcsenseNaiveSteps, the choice per step by measurement
+    bool toeplitz_naive = false;  // PNP_TOEPLITZ_NAIVE (tests, timing): the Toeplitz normal operator as its seven composed launches instead of the fused three
 };
 Tuning tuning_from_env();
 
@@ -422,5 +423,25 @@ hipError_t launch_ncsense_misfit(const float2* a, const float2* y, const float* 
 hipError_t launch_ncsense_misfit_sum(const double* partial, int C, const NufftDev& P, double* dcpartial, int N, hipStream_t s);
 // y [N, C, M] += sigma (g_re + i g_im): pnp_acquire's counter hash of (seed + n, 9001 + 4 c / 9003 + 4 c, m)
 hipError_t launch_ncsense_noise(float2* y, double sigma, uint64_t seed, int C, const NufftDev& P, int N, hipStream_t s);
+
+// ---- Toeplitz normal operator (toeplitz_kernels.hip; the operator: include/pnpadmm_toeplitz.h) ---------
+static constexpr int kToeplitzTile = 32;   // outputs per side of a spectrum workgroup's tile: divides 2 L for every k-space side L
+// K [2H, 2W] float32 from traj [M][2] float64 (ky, kx) and w [M] float32 or nullptr (1): the header's float64 Dirichlet sum, no atomics
+hipError_t launch_toeplitz_spectrum(const double* traj, const float* w, int64_t m, int H, int W, float* K, hipStream_t s);
+// grid [planes, 2H, 2W] = src [planes, H, W] in the centred window, zeros elsewhere
+hipError_t launch_toeplitz_pad(const float2* src, float2* grid, int H, int W, int planes, hipStream_t s);
+hipError_t launch_toeplitz_mul(float2* grid, const float* K, int H, int W, int planes, hipStream_t s);   // grid *= K per plane
+// q = crop(grid) (+ mu pv by one fma, with partial ([planes, pixel_chunks, 2], column 0) = Re<pv, q> per chunk, as launch_nufft_crop); pv, mu,
+// tact, partial may be nullptr
+hipError_t launch_toeplitz_crop(const float2* grid, const float2* pv, const float* mu, const float* tact, float2* q, double* partial, int H, int W,
+                                int planes, hipStream_t s);
+// the fused application (fft_kernels.hip), three launches through buf [planes, H, 2W]: the grid's live rows only.  Sides whose padded
+// grid runs the power-of-two k-space kernels (toeplitz_fused_ok, by the one rule of fft_kernels.hip); other handles run the composed form
+bool toeplitz_fused_ok(int H, int W);
+hipError_t launch_toeplitz_rows_fwd(const float2* p, float2* buf, const float2* tw, int planes, int H, int W, hipStream_t s);
+hipError_t launch_toeplitz_cols(float2* buf, const float* K, const float2* tw, int planes, int H, int W, hipStream_t s);   // tw: of 2H
+// q = the cropped inverse rows (+ mu pv by one fma; partial as launch_toeplitz_crop; stopped slices skipped)
+hipError_t launch_toeplitz_rows_inv(const float2* buf, const float2* tw, const float2* pv, const float* mu, const float* tact, float2* q,
+                                    double* partial, int planes, int H, int W, hipStream_t s);
 
 }  // namespace pnp

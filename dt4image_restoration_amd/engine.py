@@ -128,6 +128,7 @@ class PnPEngine:
             raise ValueError(f"traj: expected [M,2], got {t.shape}")
         gh, gw = (0, 0) if grid is None else (int(grid[0]), int(grid[1]))
         self._nufft_key = None
+        self._tz_weights = None      # the library drops the Toeplitz spectrum with the plan it was built for
         _lib.check(self.lib.pnp_nufft_plan(self._h, t.ctypes.data, t.shape[0], gh, gw, int(width), 0), "pnp_nufft_plan")
         self._nufft_key = (t.copy(), gh, gw, int(width), traj)
         self.live_episode = 0        # non-Cartesian constants are dropped with their plan: whoever binds episodes re-installs
@@ -192,21 +193,104 @@ class PnPEngine:
         """Install the non-Cartesian constants (y complex64 [N,M] or [N,1,M], w float32 [M] or None) and start an episode from x0
         complex64 [N,1,H,W] (pnp_reset_nc).  Returns fresh (x f32, z c64, u c64); steps then solve the k-space subproblem by `cg_iters`
         CG iterations on the NUFFT normal operator."""
+        return self._reset_nc(x0, y, w, cg_iters, False)
+
+    def reset_nc_tz(self, x0: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor] = None,
+                    cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """`reset_nc` with the CG on the Toeplitz form of A^H W A (pnp_reset_nc_tz): the spectrum is planned here when none exists for these
+        weights, which are then the weights of aty and of the DC column too."""
+        return self._reset_nc(x0, y, w, cg_iters, True)
+
+    def _reset_nc(self, x0, y, w, cg_iters, toeplitz):
         x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
         yp, wp = self._nc_args(y, w)
         x = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device)
         z = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
         u = torch.empty_like(z)
-        _lib.check(self.lib.pnp_reset_nc(self._h, x0.data_ptr(), yp, wp, int(cg_iters), x.data_ptr(), z.data_ptr(), u.data_ptr(),
-                                         self._stream()), "pnp_reset_nc")
+        if toeplitz:
+            self._toeplitz_for(w)
+            _lib.check(self.lib.pnp_reset_nc_tz(self._h, x0.data_ptr(), yp, int(cg_iters), x.data_ptr(), z.data_ptr(), u.data_ptr(),
+                                                self._stream()), "pnp_reset_nc_tz")
+        else:
+            _lib.check(self.lib.pnp_reset_nc(self._h, x0.data_ptr(), yp, wp, int(cg_iters), x.data_ptr(), z.data_ptr(), u.data_ptr(),
+                                             self._stream()), "pnp_reset_nc")
         self.live_episode = _next_episode()
         return x, z, u
 
     def set_kspace_nc(self, y: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0, cg_iters: int = 8) -> None:
         """Re-install the non-Cartesian constants of another episode without touching any iterate (pnp_set_kspace_nc)."""
+        self._set_kspace_nc(y, w, episode, cg_iters, False)
+
+    def set_kspace_nc_tz(self, y: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0, cg_iters: int = 8) -> None:
+        """`set_kspace_nc` for an episode whose CG runs the Toeplitz operator (pnp_set_kspace_nc_tz; the spectrum as in `reset_nc_tz`)."""
+        self._set_kspace_nc(y, w, episode, cg_iters, True)
+
+    def _set_kspace_nc(self, y, w, episode, cg_iters, toeplitz):
         yp, wp = self._nc_args(y, w)
-        _lib.check(self.lib.pnp_set_kspace_nc(self._h, yp, wp, int(cg_iters), self._stream()), "pnp_set_kspace_nc")
+        if toeplitz:
+            self._toeplitz_for(w)
+            _lib.check(self.lib.pnp_set_kspace_nc_tz(self._h, yp, int(cg_iters), self._stream()), "pnp_set_kspace_nc_tz")
+        else:
+            _lib.check(self.lib.pnp_set_kspace_nc(self._h, yp, wp, int(cg_iters), self._stream()), "pnp_set_kspace_nc")
         self.live_episode = episode or _next_episode()
+
+    # -- Toeplitz normal operator (include/pnpadmm_toeplitz.h) ----------------------------------
+    _tz_weights = None           # (the weights tensor the live spectrum was planned from, or None for unit weights,)
+
+    def toeplitz_plan(self, weights: Optional[torch.Tensor] = None) -> None:
+        """Build the Toeplitz spectrum of A^H W A for the planned trajectory and these weights (pnp_toeplitz_plan): weights float32 [M]
+        or None (1).  Replaces an earlier spectrum; a live Toeplitz stage's constants are dropped."""
+        if weights is not None:
+            self._chk(weights, torch.float32, self.nufft_samples or weights.numel(), "weights")
+        was_live = self.toeplitz_live
+        self._tz_weights = None
+        _lib.check(self.lib.pnp_toeplitz_plan(self._h, weights.data_ptr() if weights is not None else None, 0, self._stream()),
+                   "pnp_toeplitz_plan")
+        self._tz_weights = (weights.clone() if weights is not None else None,)
+        if was_live:
+            self.live_episode = 0    # dropped with the spectrum: whoever binds episodes re-installs
+
+    def _toeplitz_for(self, w: Optional[torch.Tensor]) -> None:
+        """plan the spectrum unless the live one was planned from these very weights"""
+        k = self._tz_weights
+        if k is not None and self.toeplitz_planned:
+            if (k[0] is None and w is None) or (k[0] is not None and w is not None and k[0].shape == w.shape and torch.equal(k[0], w)):
+                return
+        self.toeplitz_plan(w)
+
+    @property
+    def toeplitz_planned(self) -> bool:
+        """Whether a Toeplitz spectrum exists for the handle's NUFFT plan."""
+        return bool(self.lib.pnp_toeplitz_planned(self._h))
+
+    @property
+    def toeplitz_live(self) -> bool:
+        """Whether the live stage's CG runs the Toeplitz operator."""
+        return bool(self.lib.pnp_toeplitz_live(self._h))
+
+    def toeplitz_spectrum(self) -> torch.Tensor:
+        """float32 [2H,2W]: the spectrum K, centred like `fft2c`'s output (pnp_toeplitz_spectrum)."""
+        out = torch.empty((2 * self.h, 2 * self.w), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pnp_toeplitz_spectrum(self._h, out.data_ptr(), self._stream()), "pnp_toeplitz_spectrum")
+        return out
+
+    def toeplitz_apply(self, img: torch.Tensor) -> torch.Tensor:
+        """complex64 [B,H,W] = A^H W A img by the Toeplitz form, without mu (pnp_toeplitz_apply); img complex64 [B,H,W] (or [B,1,H,W])."""
+        b = self._batch_of(img, self.h * self.w, "img")
+        self._chk(img, torch.complex64, img.numel(), "img")
+        out = torch.empty((b, self.h, self.w), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_toeplitz_apply(self._h, img.data_ptr(), b, out.data_ptr(), self._stream()), "pnp_toeplitz_apply")
+        return out
+
+    def toeplitz_apply_mc(self, img: torch.Tensor, sens: torch.Tensor) -> torch.Tensor:
+        """complex64 [B,H,W] = sum_c conj(S_c) . Toep(S_c . img) (pnp_toeplitz_apply_mc); sens complex64 [C,H,W] or [N,C,H,W]."""
+        b = self._batch_of(img, self.h * self.w, "img")
+        self._chk(img, torch.complex64, img.numel(), "img")
+        sens, coils, sens_n = self._sens(sens)
+        out = torch.empty((b, self.h, self.w), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_toeplitz_apply_mc(self._h, img.data_ptr(), sens.data_ptr(), coils, sens_n, b, out.data_ptr(), self._stream()),
+                   "pnp_toeplitz_apply_mc")
+        return out
 
     def nc_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
         """q = A^H W A p + mu p with the installed non-Cartesian constants (pnp_nc_normal); p complex64 [N,1,H,W], mu float32 [N]."""
@@ -281,21 +365,48 @@ class PnPEngine:
         """Install the non-Cartesian SENSE constants (y complex64 [N,C,M], sens complex64 [C,H,W] or [N,C,H,W], w float32 [M] or None) and
         start an episode from x0 complex64 [N,1,H,W] (pnp_reset_ncsense).  Returns fresh (x f32, z c64, u c64); steps then solve the
         k-space subproblem by `cg_iters` CG iterations on A^H W A + mu I, A p = [F_nu(S_c . p)]_c."""
+        return self._reset_ncsense(x0, y, sens, w, cg_iters, False)
+
+    def reset_ncsense_tz(self, x0: torch.Tensor, y: torch.Tensor, sens: torch.Tensor, w: Optional[torch.Tensor] = None,
+                         cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """`reset_ncsense` with the CG on the Toeplitz form of each coil's A^H W A (pnp_reset_ncsense_tz; the spectrum as in `reset_nc_tz`)."""
+        return self._reset_ncsense(x0, y, sens, w, cg_iters, True)
+
+    def _reset_ncsense(self, x0, y, sens, w, cg_iters, toeplitz):
         x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
         yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
         x = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device)
         z = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
         u = torch.empty_like(z)
-        _lib.check(self.lib.pnp_reset_ncsense(self._h, x0.data_ptr(), yp, sp, coils, sens_n, wp, int(cg_iters), x.data_ptr(), z.data_ptr(),
-                                              u.data_ptr(), self._stream()), "pnp_reset_ncsense")
+        if toeplitz:
+            self._toeplitz_for(w)
+            _lib.check(self.lib.pnp_reset_ncsense_tz(self._h, x0.data_ptr(), yp, sp, coils, sens_n, int(cg_iters), x.data_ptr(), z.data_ptr(),
+                                                     u.data_ptr(), self._stream()), "pnp_reset_ncsense_tz")
+        else:
+            _lib.check(self.lib.pnp_reset_ncsense(self._h, x0.data_ptr(), yp, sp, coils, sens_n, wp, int(cg_iters), x.data_ptr(), z.data_ptr(),
+                                                  u.data_ptr(), self._stream()), "pnp_reset_ncsense")
         self.live_episode = _next_episode()
         return x, z, u
 
     def set_kspace_ncsense(self, y: torch.Tensor, sens: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0,
                            cg_iters: int = 8) -> None:
         """Re-install the non-Cartesian SENSE constants of another episode without touching any iterate (pnp_set_kspace_ncsense)."""
+        self._set_kspace_ncsense(y, sens, w, episode, cg_iters, False)
+
+    def set_kspace_ncsense_tz(self, y: torch.Tensor, sens: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0,
+                              cg_iters: int = 8) -> None:
+        """`set_kspace_ncsense` for an episode whose CG runs the Toeplitz operator (pnp_set_kspace_ncsense_tz)."""
+        self._set_kspace_ncsense(y, sens, w, episode, cg_iters, True)
+
+    def _set_kspace_ncsense(self, y, sens, w, episode, cg_iters, toeplitz):
         yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
-        _lib.check(self.lib.pnp_set_kspace_ncsense(self._h, yp, sp, coils, sens_n, wp, int(cg_iters), self._stream()), "pnp_set_kspace_ncsense")
+        if toeplitz:
+            self._toeplitz_for(w)
+            _lib.check(self.lib.pnp_set_kspace_ncsense_tz(self._h, yp, sp, coils, sens_n, int(cg_iters), self._stream()),
+                       "pnp_set_kspace_ncsense_tz")
+        else:
+            _lib.check(self.lib.pnp_set_kspace_ncsense(self._h, yp, sp, coils, sens_n, wp, int(cg_iters), self._stream()),
+                       "pnp_set_kspace_ncsense")
         self.live_episode = episode or _next_episode()
 
     def ncsense_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:

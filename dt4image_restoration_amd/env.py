@@ -39,7 +39,10 @@ def _as_complex(t: torch.Tensor) -> torch.Tensor:
 class PnPEnv:
     def __init__(self, max_episode_step: int, denoiser: UNetDenoiser2D, device_type,
                  no_ref_scorer: Optional[Callable[[torch.Tensor], float]] = None, replica: int = 0, cg_iters: int = 8,
-                 nufft_width: int = 6, nufft_grid=None) -> None:
+                 nufft_width: int = 6, nufft_grid=None, nc_normal: str = "nufft") -> None:
+        if nc_normal not in ("nufft", "toeplitz"):
+            raise ValueError(f"nc_normal must be 'nufft' or 'toeplitz', got {nc_normal!r}")
+        self.nc_normal = nc_normal              # non-Cartesian episodes: the form of A^H W A inside the CG (include/pnpadmm_toeplitz.h)
         self.max_episode_step = max_episode_step
         self.cg_iters = int(cg_iters)           # multi-coil and non-Cartesian episodes: conjugate-gradient iterations per step
         self.nufft_width = int(nufft_width)     # non-Cartesian episodes (data["traj"]): the kernel width and the grid (None: the default)
@@ -54,7 +57,7 @@ class PnPEnv:
         """Another env on the same denoiser weights whose engines are replicas of their own (own workspace, own k-space
         constants): two sub-batches of one job can then be stepped concurrently on two streams."""
         return PnPEnv(self.max_episode_step, self.denoiser, self._device_type, self.no_ref_model, replica=replica, cg_iters=self.cg_iters,
-                      nufft_width=self.nufft_width, nufft_grid=self.nufft_grid)
+                      nufft_width=self.nufft_width, nufft_grid=self.nufft_grid, nc_normal=self.nc_normal)
 
     # ---- engine management ------------------------------------------------------------------
     def _engine_for(self, n: int, h: int, w: int, device: torch.device) -> PnPEngine:
@@ -123,9 +126,9 @@ class PnPEnv:
         eng = self._engine_for(n, h, w, device)
         self._plan_nc(eng, traj)
         if sens is None:
-            x, z, u = eng.reset_nc(x0, y0, dcf, cg_iters=self.cg_iters)
+            x, z, u = (eng.reset_nc_tz if self.nc_normal == "toeplitz" else eng.reset_nc)(x0, y0, dcf, cg_iters=self.cg_iters)
         else:
-            x, z, u = eng.reset_ncsense(x0, y0, sens, dcf, cg_iters=self.cg_iters)
+            x, z, u = (eng.reset_ncsense_tz if self.nc_normal == "toeplitz" else eng.reset_ncsense)(x0, y0, sens, dcf, cg_iters=self.cg_iters)
         aty0 = torch.as_tensor(data["ATy0"])[..., 0] if "ATy0" in data else None
         return OrderedDict({"x": x, "y0": y0, "z": z, "u": u, "mask": None, "gt": gt, "ATy0": aty0,
                             "T": torch.zeros(n, dtype=torch.float32, device=device),
@@ -142,14 +145,16 @@ class PnPEnv:
             ep = states["_episode"] = _next_episode()
         n, h, w = eng.n, eng.h, eng.w
         if states.get("traj") is not None:
+            tz = self.nc_normal == "toeplitz"   # (the engine re-plans the spectrum when the plan or the episode's weights changed)
             y = states["y0"]
             y = y if y.is_complex() else _as_complex(y)
             if states.get("sens") is not None:  # a non-Cartesian SENSE episode
                 sens = states["sens"]
                 y = y.reshape(n, sens.shape[-3], -1).to(eng.device).contiguous()
-                eng.set_kspace_ncsense(y, sens, states.get("dcf"), episode=ep, cg_iters=self.cg_iters)
+                (eng.set_kspace_ncsense_tz if tz else eng.set_kspace_ncsense)(y, sens, states.get("dcf"), episode=ep, cg_iters=self.cg_iters)
                 return
-            eng.set_kspace_nc(y.reshape(n, -1).to(eng.device).contiguous(), states.get("dcf"), episode=ep, cg_iters=self.cg_iters)
+            (eng.set_kspace_nc_tz if tz else eng.set_kspace_nc)(y.reshape(n, -1).to(eng.device).contiguous(), states.get("dcf"), episode=ep,
+                                                                cg_iters=self.cg_iters)
             return
         sens = states.get("sens")
         coils = 1 if sens is None else sens.shape[-3]
