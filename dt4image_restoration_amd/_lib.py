@@ -143,6 +143,13 @@ SIGNATURES_TOEPLITZ = {
 }
 PNP_TOEPLITZ_MAX_SIDE = 512
 
+# name -> (restype, argtypes); every symbol include/pnpadmm_dcf.h declares (density weights for any trajectory: Pipe and Menon's iteration)
+SIGNATURES_DCF = {
+    "pnp_nufft_psi": (C.c_int, [C.c_void_p, _fp, _fp, _vp]),
+    "pnp_nufft_dcf": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int, _fp, _fp, _vp]),
+}
+PNP_DCF_MAX_ITERS = 256
+
 
 def toeplitz_size_error(fn: str, h: int, w: int):
     """The library's refusal of a slice too large for the Toeplitz operator, word for word (pnp_capi.hip: tz_check_sizes), or None: for a
@@ -167,7 +174,7 @@ def load() -> C.CDLL:
         raise PnPError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        f"or `make -C {os.path.dirname(LIB_PATH)}`; there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE, **SIGNATURES_TOEPLITZ}.items():
+    for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE, **SIGNATURES_TOEPLITZ, **SIGNATURES_DCF}.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -22,7 +22,7 @@ from . import _lib, synthetic
 from .weights import hash_uniform
 
 MASK_KINDS = ("radial", "cartesian", "uniform")
-NC_KINDS = ("radial-nc",)                                   # task_problem: non-Cartesian acquisitions (no mask: a trajectory)
+NC_KINDS = ("radial-nc", "spiral-nc", "rosette-nc")          # task_problem: non-Cartesian acquisitions (no mask: a trajectory)
 
 
 def _engine(engine_or_env, n: int, h: int, w: int, device: torch.device):
@@ -162,6 +162,59 @@ def radial_dcf(traj, h: int, w: int) -> np.ndarray:
     R = int(round(1.0 / step))
     d = np.maximum(np.hypot(t[:, 0], t[:, 1]), 1.0 / (2.0 * R))
     return (d * (h * w / d.sum())).astype(np.float32)
+
+
+def spiral_trajectory(h: int, w: int, interleaves: int, readout: int = None, turns: float = None) -> np.ndarray:
+    """float64 [interleaves * R, 2]: the (ky, kx) of an Archimedean spiral acquisition in cycles per pixel.  Sample j of interleaf l (row
+    l R + j) sits at t = j / R, a = 2 pi (turns t + l / L), (ky, kx) = (0.5 t sin a, 0.5 t cos a): every interleaf starts at k = 0 and
+    |k| < 0.5.  turns (default ceil(max(h, w) / (2 L)), at least 1): revolutions per interleaf; the default puts neighbouring arms of the
+    L interleaves 1 / max(h, w) apart, the Nyquist spacing.  readout (default max(2 max(h, w), ceil(pi turns max(h, w)))): samples per
+    interleaf; the default keeps the step along the arm at the edge, pi turns / R, within 1 / max(h, w)."""
+    L, side = int(interleaves), max(int(h), int(w))
+    if L < 1:
+        raise ValueError(f"spiral_trajectory: need interleaves >= 1, got {L}")
+    turns = float(max(1, math.ceil(side / (2.0 * L)))) if turns is None else float(turns)
+    R = max(2 * side, int(math.ceil(math.pi * turns * side))) if readout is None else int(readout)
+    if R < 2 or not turns > 0.0:
+        raise ValueError(f"spiral_trajectory: need readout >= 2 and turns > 0, got {R}, {turns}")
+    t = np.arange(R, dtype=np.float64) / R
+    out = np.empty((L, R, 2), dtype=np.float64)
+    for l in range(L):
+        a = 2.0 * math.pi * (turns * t + l / L)
+        out[l, :, 0] = 0.5 * t * np.sin(a)
+        out[l, :, 1] = 0.5 * t * np.cos(a)
+    return out.reshape(-1, 2)
+
+
+def rosette_trajectory(h: int, w: int, petals: int, readout: int = None) -> np.ndarray:
+    """float64 [R, 2]: the (ky, kx) of a rosette in cycles per pixel, one shot.  Sample j sits at t = j / R, r = 0.5 sin(pi petals t),
+    a = pi (petals - 2) t, (ky, kx) = (r sin a, r cos a): `petals` petals through k = 0, |k| <= 0.5 (0.5 itself only where a sample
+    falls on a petal's tip).  readout (default ceil(pi petals max(h, w) / 2)): the default keeps the step along the curve, at most
+    pi petals / (2 R), within 1 / max(h, w)."""
+    P, side = int(petals), max(int(h), int(w))
+    if P < 1:
+        raise ValueError(f"rosette_trajectory: need petals >= 1, got {P}")
+    R = int(math.ceil(0.5 * math.pi * P * side)) if readout is None else int(readout)
+    if R < 2:
+        raise ValueError(f"rosette_trajectory: need readout >= 2, got {R}")
+    t = np.arange(R, dtype=np.float64) / R
+    r = 0.5 * np.sin(math.pi * P * t)
+    a = math.pi * (P - 2) * t
+    return np.stack([r * np.sin(a), r * np.cos(a)], axis=1)
+
+
+def pipe_dcf(engine_or_env, traj, iters: int = 30, width: int = 6, grid=None) -> torch.Tensor:
+    """float32 [M] on the engine's device: density weights of ANY trajectory by Pipe and Menon's iteration w <- w / (Psi w) on the
+    engine's own gridding kernel (pnp_nufft_dcf, include/pnpadmm_dcf.h), `iters` iterations from ones, scaled to sum h w as `radial_dcf`.
+    Plans the trajectory first (width, grid as `PnPEngine.nufft_plan`) unless the live plan is this one.  engine_or_env: a PnPEngine, or
+    a PnPEnv that holds one (the handle of its latest reset or `simulate`)."""
+    eng = engine_or_env if hasattr(engine_or_env, "nufft_dcf") else getattr(engine_or_env, "_engine", None)
+    if eng is None or not hasattr(eng, "nufft_dcf"):
+        raise TypeError(f"pipe_dcf: expected a PnPEngine, or a PnPEnv that holds one, got {type(engine_or_env).__name__}")
+    t = np.ascontiguousarray(traj.detach().cpu().numpy() if isinstance(traj, torch.Tensor) else traj, dtype=np.float64)
+    if not eng.nufft_planned(t, grid, width):
+        eng.nufft_plan(t, grid=grid, width=width)
+    return eng.nufft_dcf(iters=iters)
 
 
 def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, width: int, grid, sens=None) -> Dict[str, torch.Tensor]:
@@ -572,24 +625,41 @@ def make_mask(h: int, w: int, accel: float, kind: str = "radial", seed: int = 0)
 
 def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int = 0, mask_kind: str = "radial",
                  mask=None, coils: int = 0, noise_cov=None, spokes: int = None, nc_weights: str = "dcf", nufft_width: int = 6,
-                 nufft_grid=None) -> Dict[str, torch.Tensor]:
+                 nufft_grid=None, interleaves: int = None, petals: int = None, dcf_iters: int = 30) -> Dict[str, torch.Tensor]:
     """`simulate` for a named task: '4x_10' = acceleration 4, sigma_n = 10 / 255.  mask: a ready mask, or None for
     `make_mask(h, w, accel, mask_kind, seed)` (the same for every shard of a job).  coils > 0: a multi-coil acquisition with the
     analytic maps `synthetic.coil_maps(coils, h, w)`; noise_cov: their channel noise covariance (`simulate`).
     mask_kind "radial-nc": a true radial acquisition, samples off the grid (`simulate(traj=)`): golden-angle `radial_trajectory` of
-    `spokes` spokes (None: ceil(h / accel)), weighted by `radial_dcf` (nc_weights "dcf") or not at all ("none"); with coils > 0 the
-    non-Cartesian SENSE acquisition with the maps `synthetic.coil_maps(coils, h, w)`."""
+    `spokes` spokes (None: ceil(h / accel)); "spiral-nc": `spiral_trajectory` of `interleaves` interleaves (None: ceil(h / (2 accel)),
+    about the samples of the radial acquisition); "rosette-nc": `rosette_trajectory` of `petals` petals (None: an odd count near
+    h / accel).  nc_weights: "none"; "pipe", the iterated density weights `pipe_dcf` (`dcf_iters` iterations); "dcf", the weights written
+    for the trajectory: the ramp `radial_dcf` on "radial-nc" and `pipe_dcf` on the other two (the ramp is never applied to a trajectory
+    it was not written for).  With coils > 0 the non-Cartesian SENSE acquisition with the maps `synthetic.coil_maps(coils, h, w)`."""
     accel, sigma_n = parse_task(task)
     h, w = (int(v) for v in torch.as_tensor(gt).shape[-2:])
     if mask_kind in NC_KINDS:
         if noise_cov is not None or mask is not None:
-            raise ValueError("task_problem: mask_kind 'radial-nc' takes no mask and no noise_cov")
-        if nc_weights not in ("none", "dcf"):
-            raise ValueError(f"nc_weights must be 'none' or 'dcf', got {nc_weights!r}")
-        traj = radial_trajectory(h, w, int(math.ceil(h / accel)) if spokes is None else int(spokes))
+            raise ValueError(f"task_problem: mask_kind {mask_kind!r} takes no mask and no noise_cov")
+        if nc_weights not in ("none", "dcf", "pipe"):
+            raise ValueError(f"nc_weights must be 'none', 'dcf' or 'pipe', got {nc_weights!r}")
+        if mask_kind == "radial-nc":
+            traj = radial_trajectory(h, w, int(math.ceil(h / accel)) if spokes is None else int(spokes))
+        elif mask_kind == "spiral-nc":
+            traj = spiral_trajectory(h, w, int(math.ceil(h / (2.0 * accel))) if interleaves is None else int(interleaves))
+        else:
+            traj = rosette_trajectory(h, w, (int(math.ceil(h / accel)) | 1) if petals is None else int(petals))
         sens = synthetic.coil_maps(coils, h, w).astype(np.complex64) if coils else None
-        return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, sens=sens, traj=traj,
-                        dcf=radial_dcf(traj, h, w) if nc_weights == "dcf" else None, nufft_width=nufft_width, nufft_grid=nufft_grid)
+        if nc_weights == "none":
+            dcf = None
+        elif nc_weights == "dcf" and mask_kind == "radial-nc":
+            dcf = radial_dcf(traj, h, w)
+        else:                                                # the handle `simulate` will use plans this trajectory and iterates on it
+            g = torch.as_tensor(gt)
+            eng = engine_or_env if hasattr(engine_or_env, "acquire") else None
+            device = eng.device if eng is not None else torch.device("cuda", torch.cuda.current_device())
+            dcf = pipe_dcf(_engine(engine_or_env, g.numel() // (h * w), h, w, device), traj, iters=dcf_iters, width=nufft_width, grid=nufft_grid)
+        return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, sens=sens, traj=traj, dcf=dcf, nufft_width=nufft_width,
+                        nufft_grid=nufft_grid)
     if mask is None:
         mask = make_mask(h, w, accel, mask_kind, seed)
     sens = synthetic.coil_maps(coils, h, w).astype(np.complex64) if coils else None

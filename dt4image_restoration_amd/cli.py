@@ -24,7 +24,8 @@ subproblem is then solved by K conjugate-gradient iterations per step (`acquire`
 layout has none):
 
     ... --coils 4 --cg-iters 8 eval|flex|mcts|fixed ...
-    ... --traj radial [--spokes S] [--nufft-width 4|6|8] [--nufft-grid GH GW] [--nc-weights none|dcf] [--cg-iters K] eval|flex|mcts|fixed|acquire ...
+    ... --traj radial [--spokes S] [--nufft-width 4|6|8] [--nufft-grid GH GW] [--nc-weights none|dcf|pipe] [--cg-iters K] eval|flex|mcts|fixed|acquire ...
+    ... --traj spiral [--interleaves L] | --traj rosette [--petals P]  [--nc-weights none|dcf|pipe] [--dcf-iters I] eval|flex|mcts|fixed|acquire ...
     ... --traj radial --nc-coils 4 [--cg-iters K] eval|flex|mcts|fixed|acquire ...      (non-Cartesian SENSE: the radial acquisition of C coils)
     ... --coils 4 --sens estimate [--sens-window hann|box] [--sens-thresh 0.05] [--acs H W] --mask cartesian fixed ...
 
@@ -213,8 +214,8 @@ def _grappa_start(env, batch, filled):
 
 def _nc_kwargs(args):
     """--traj radial: what `acquisition.task_problem` needs for the non-Cartesian acquisition of a task."""
-    return dict(mask_kind="radial-nc", spokes=args.spokes, nc_weights=args.nc_weights, nufft_width=args.nufft_width, nufft_grid=args.nufft_grid,
-                coils=args.nc_coils)
+    return dict(mask_kind=f"{args.traj}-nc", spokes=args.spokes, nc_weights=args.nc_weights, nufft_width=args.nufft_width,
+                nufft_grid=args.nufft_grid, coils=args.nc_coils, interleaves=args.interleaves, petals=args.petals, dcf_iters=args.dcf_iters)
 
 
 def _sets(args, flex_target=None, env=None):
@@ -227,7 +228,7 @@ def _sets(args, flex_target=None, env=None):
             try:
                 batch = acquisition.task_problem(task, images(a, b), env, seed=args.seed, first_slice=a, **_nc_kwargs(args))
             except (ValueError, RuntimeError) as e:          # a grid the rule refuses, a slice side without a grid
-                raise SystemExit(f"--traj radial: task {task}: {e}")
+                raise SystemExit(f"--traj {args.traj}: task {task}: {e}")
             if args.nc_normal == "toeplitz":                 # refused here, in the library's words, before any episode is set up
                 why = _lib.toeplitz_size_error("pnp_toeplitz_plan", *batch["gt"].shape[-2:])
                 if why:
@@ -237,12 +238,12 @@ def _sets(args, flex_target=None, env=None):
             for d in args.gt:
                 for task in _tasks(args):
                     images = (lambda a, b, d=d: D.load_gt_dir(d, limit=args.limit, start=a, stop=b)[0])
-                    yield f"{d} {task} radial-nc", D.count_gt_dir(d, args.limit), (lambda a, b, im=images, t=task: nc_load(im, t, a, b))
+                    yield f"{d} {task} {args.traj}-nc", D.count_gt_dir(d, args.limit), (lambda a, b, im=images, t=task: nc_load(im, t, a, b))
         else:
             for accel, sig in ((4, 10), (8, 10)):
                 images = (lambda a, b, accel=accel: np.stack([synthetic.phantom(args.size, args.size, args.seed + accel + i)
                                                               for i in range(a, b)]).astype(np.float32))
-                yield (f"synthetic {accel}x_{sig} radial-nc", args.limit or 7,
+                yield (f"synthetic {accel}x_{sig} {args.traj}-nc", args.limit or 7,
                        (lambda a, b, im=images, t=f"{accel}x_{sig}": nc_load(im, t, a, b)))
         return
     if args.gt:
@@ -329,7 +330,7 @@ def _acquire(args):
                                                  **(_nc_kwargs(args) if args.traj else dict(mask_kind=args.mask)))
                 except ValueError as e:
                     if args.traj:
-                        raise SystemExit(f"--traj radial: task {task}: {e}")
+                        raise SystemExit(f"--traj {args.traj}: task {task}: {e}")
                     if args.mask != "uniform":
                         raise
                     raise SystemExit(f"--mask uniform: task {task}: {e}")
@@ -337,7 +338,7 @@ def _acquire(args):
                 for i, name in enumerate(names):
                     D.save_mat(os.path.join(dsts[task], acquired_name(task, name)), host, i)
         for task in tasks:
-            out.append({"set": d, "task": task, "n": total, "dir": dsts[task], "mask": "radial-nc" if args.traj else args.mask})
+            out.append({"set": d, "task": task, "n": total, "dir": dsts[task], "mask": f"{args.traj}-nc" if args.traj else args.mask})
             print(json.dumps(out[-1]), flush=True)
     return out
 
@@ -369,8 +370,14 @@ def main(argv=None):
     ap.add_argument("--coils", type=int, default=0, help="multi-coil (SENSE) problems with this many analytic coil maps (1..32; "
                     "default 0: single-coil)")
     ap.add_argument("--cg-iters", type=int, default=8, help="conjugate-gradient iterations per step of a multi-coil or --traj problem (1..64)")
-    ap.add_argument("--traj", choices=("radial",), default=None, help="a non-Cartesian acquisition: golden-angle radial spokes whose samples lie "
-                    "off the grid (NUFFT data fidelity, CG solve), single-coil: the synthetic sets or --gt, not --data")
+    ap.add_argument("--traj", choices=("radial", "spiral", "rosette"), default=None, help="a non-Cartesian acquisition: golden-angle radial "
+                    "spokes, interleaved spirals or a rosette, whose samples lie off the grid (NUFFT data fidelity, CG solve), single-coil: the "
+                    "synthetic sets or --gt, not --data")
+    ap.add_argument("--interleaves", type=int, default=None, metavar="L", help="--traj spiral: interleaves (default: ceil(H / (2 acceleration)) "
+                    "of the task)")
+    ap.add_argument("--petals", type=int, default=None, metavar="P", help="--traj rosette: petals (default: an odd count near H / acceleration)")
+    ap.add_argument("--dcf-iters", type=int, default=30, metavar="I", help="--traj: iterations of the density weights of --nc-weights pipe, and "
+                    "of dcf on a spiral or a rosette (1..256)")
     ap.add_argument("--nc-coils", type=int, default=0, metavar="C", help="--traj radial: non-Cartesian SENSE, the radial acquisition of C "
                     "coils with analytic coil maps (1..32; default 0: single-coil)")
     ap.add_argument("--nc-normal", choices=("nufft", "toeplitz"), default="nufft", help="--traj radial: the normal operator A^H W A inside the "
@@ -380,8 +387,9 @@ def main(argv=None):
     ap.add_argument("--nufft-width", type=int, choices=(4, 6, 8), default=6, help="--traj: width of the gridding kernel in grid points")
     ap.add_argument("--nufft-grid", type=int, nargs=2, default=None, metavar=("GH", "GW"), help="--traj: sides of the oversampled grid (sides "
                     "the k-space stage accepts, at least 1.25 x the slice; default: the smallest such)")
-    ap.add_argument("--nc-weights", choices=("none", "dcf"), default="dcf", help="--traj: sample weights of the data term and of ATy0: the "
-                    "radial density compensation, or none")
+    ap.add_argument("--nc-weights", choices=("none", "dcf", "pipe"), default="dcf", help="--traj: sample weights of the data term and of ATy0: "
+                    "none; pipe, the density weights iterated on the device for any trajectory; dcf, the analytic ramp on radial spokes and "
+                    "the iterated weights on a spiral or a rosette")
     ap.add_argument("--sens", choices=("true", "estimate", "espirit"), default="true", help="coil maps of a --coils run: the analytic maps that "
                     "generated the measurements, or maps estimated on the device from the calibration block of each set's own y0 (estimate: "
                     "the low-resolution estimate; espirit: ESPIRiT, at most 16 coils)")
@@ -452,6 +460,14 @@ def main(argv=None):
             raise SystemExit(f"--nc-coils must be 1..32, got {args.nc_coils}")
         if args.spokes is not None and args.spokes < 1:
             raise SystemExit(f"--spokes must be >= 1, got {args.spokes}")
+        for flag, value, traj in (("--spokes", args.spokes, "radial"), ("--interleaves", args.interleaves, "spiral"),
+                                  ("--petals", args.petals, "rosette")):
+            if value is not None and args.traj != traj:
+                raise SystemExit(f"{flag} needs --traj {traj} (got --traj {args.traj})")
+            if value is not None and value < 1:
+                raise SystemExit(f"{flag} must be >= 1, got {value}")
+        if not 1 <= args.dcf_iters <= 256:
+            raise SystemExit(f"--dcf-iters must be 1..256, got {args.dcf_iters}")
         if args.grappa or args.mask != "radial":
             raise SystemExit("--traj takes no --mask / --grappa: its samples are a trajectory, not a mask")
         if args.nc_normal == "toeplitz" and args.mode == "acquire":
@@ -467,6 +483,12 @@ def main(argv=None):
         raise SystemExit(f"--nc-coils needs --traj radial (got --nc-coils {args.nc_coils} without it)")
     elif args.spokes is not None or args.nufft_grid is not None or args.nufft_width != 6 or args.nc_weights != "dcf":
         raise SystemExit("--spokes / --nufft-width / --nufft-grid / --nc-weights need --traj radial")
+    elif args.interleaves is not None:
+        raise SystemExit("--interleaves needs --traj spiral")
+    elif args.petals is not None:
+        raise SystemExit("--petals needs --traj rosette")
+    elif args.dcf_iters != 30:
+        raise SystemExit("--dcf-iters needs --traj")
     if args.prior == "tv":
         if not (args.tv_scale >= 0.0 and np.isfinite(args.tv_scale)):
             raise SystemExit(f"--tv-scale must be finite and >= 0, got {args.tv_scale}")

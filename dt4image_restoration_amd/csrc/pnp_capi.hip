@@ -3,6 +3,7 @@
 #include "../../include/pnpadmm.h"
 #include "../../include/pnpadmm_ncsense.h"
 #include "../../include/pnpadmm_toeplitz.h"
+#include "../../include/pnpadmm_dcf.h"
 #include "pnp_internal.h"
 #include "denoiser_plan.h"
 #include "nufft_plan.h"
@@ -167,6 +168,12 @@ struct pnp_engine {
     bool tz_planned = false;     // a spectrum exists for the handle's NUFFT plan
     bool tz_has_w = false;
     bool tz_on = false;          // the live non-Cartesian stage (nc_on or ns_coils > 0) runs its CG on the Toeplitz operator
+    // density compensation (include/pnpadmm_dcf.h): its own workspace, grown inside pnp_nufft_psi / pnp_nufft_dcf
+    double* dcf_grid = nullptr;  // [gh, gw] G^T w
+    double* dcf_w = nullptr;     // [M] the float64 iterate
+    double* dcf_part = nullptr;  // [dcf_sum_chunks(M)] chunk sums of the finish
+    float* dcf_max = nullptr;    // [iters + 1, dcf_gather_blocks(M)] workgroup maxima of |Psi w - 1| (only with info)
+    size_t dcf_grid_cap = 0, dcf_w_cap = 0, dcf_part_cap = 0, dcf_max_cap = 0;
     // the prior of pnp_step (pnp_set_prior) and the total-variation denoiser's workspace (allocated inside the first call that runs it)
     int prior = PNP_PRIOR_UNET;
     double tv_scale = 1.0;       // as given; applied as float32
@@ -996,6 +1003,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->nc.tw_gh); (void)hipFree(e->nc.tw_gw);
     (void)hipFree(e->ns_img);
     (void)hipFree(e->tz_traj); (void)hipFree(e->tz_k); (void)hipFree(e->tz_w); (void)hipFree(e->tz_tw_h); (void)hipFree(e->tz_tw_w); (void)hipFree(e->tz_grid);
+    (void)hipFree(e->dcf_grid); (void)hipFree(e->dcf_w); (void)hipFree(e->dcf_part); (void)hipFree(e->dcf_max);
     (void)hipFree(e->ns_grid); (void)hipFree(e->ns_samp); (void)hipFree(e->ns_y); (void)hipFree(e->ns_sens); (void)hipFree(e->ns_w); (void)hipFree(e->ns_mpart);
     (void)hipFree(e->nc_grid); (void)hipFree(e->nc_samp); (void)hipFree(e->nc_y); (void)hipFree(e->nc_w); (void)hipFree(e->nc_mpart);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
@@ -2104,6 +2112,71 @@ int pnp_reset_ncsense_tz(pnp_handle e, const float* x0, const float* y, const fl
     e->tz_on = true;
     return PNP_OK;
     PNP_API_END("pnp_reset_ncsense_tz")
+}
+
+// ---- density compensation (include/pnpadmm_dcf.h) -------------------------------------------------------
+namespace {
+
+int dcf_need_plan(const char* fn, const pnp_engine* e) {
+    return e->nc.m > 0 ? PNP_OK : fail(PNP_ERR_INVALID, "%s: the handle has no NUFFT plan (pnp_nufft_plan)", fn);
+}
+// the feature's own workspace: the grid, the float64 weights, the chunk sums and, for `passes` > 0, that many rows of workgroup maxima
+int dcf_ensure(pnp_engine* e, int passes) {
+    const size_t M = (size_t)e->nc.m;
+    return ws_grow(e, "density compensation workspace",
+                   {{(void**)&e->dcf_grid, &e->dcf_grid_cap, (size_t)e->nc.gh * e->nc.gw * sizeof(double), false},
+                    {(void**)&e->dcf_w, &e->dcf_w_cap, M * sizeof(double), false},
+                    {(void**)&e->dcf_part, &e->dcf_part_cap, (size_t)dcf_sum_chunks(e->nc.m) * sizeof(double), false},
+                    {(void**)&e->dcf_max, &e->dcf_max_cap, (size_t)passes * dcf_gather_blocks(e->nc.m) * sizeof(float), false}});
+}
+
+}  // namespace
+
+int pnp_nufft_psi(pnp_handle e, const float* w, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_nufft_psi";
+    if (!w) return fail(PNP_ERR_INVALID, "%s: null w", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = dcf_need_plan(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = dcf_ensure(e, 0)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_dcf_spread(nullptr, w, e->nc, e->dcf_grid, s));
+    HIP_TRY(launch_dcf_gather(e->dcf_grid, e->nc, nullptr, nullptr, nullptr, out, nullptr, s));
+    p.end(2);
+    return PNP_OK;
+    PNP_API_END("pnp_nufft_psi")
+}
+
+int pnp_nufft_dcf(pnp_handle e, const float* w0, int iters, int flags, float* w, float* info, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_nufft_dcf";
+    if (iters < 1 || iters > PNP_DCF_MAX_ITERS) return fail(PNP_ERR_INVALID, "%s: iters must be 1..%d (got %d)", fn, PNP_DCF_MAX_ITERS, iters);
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (!w) return fail(PNP_ERR_INVALID, "%s: null w", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = dcf_need_plan(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = dcf_ensure(e, info ? iters + 1 : 0)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nb = (size_t)dcf_gather_blocks(e->nc.m);
+    Prof p(e, s, PROF_OTHER, -1);
+    for (int k = 0; k < iters; ++k) {
+        const double* w64 = k ? e->dcf_w : nullptr;         // the first pass reads the caller's start (or ones)
+        const float* w32 = k ? nullptr : w0;
+        HIP_TRY(launch_dcf_spread(w64, w32, e->nc, e->dcf_grid, s));
+        HIP_TRY(launch_dcf_gather(e->dcf_grid, e->nc, w64, w32, e->dcf_w, nullptr, info ? e->dcf_max + k * nb : nullptr, s));
+    }
+    if (info) {                                             // max |Psi w - 1| of the result: one more spread and gather
+        HIP_TRY(launch_dcf_spread(e->dcf_w, nullptr, e->nc, e->dcf_grid, s));
+        HIP_TRY(launch_dcf_gather(e->dcf_grid, e->nc, nullptr, nullptr, nullptr, nullptr, e->dcf_max + (size_t)iters * nb, s));
+    }
+    HIP_TRY(launch_dcf_finish(e->dcf_w, e->dcf_part, e->nc, w, e->dcf_max, iters + 1, info, s));
+    p.end(2 * iters + (info ? 2 : 0) + 2);
+    return PNP_OK;
+    PNP_API_END("pnp_nufft_dcf")
 }
 
 int pnp_estimate_sens(pnp_handle e, const float* y0, int coils, int acs_h, int acs_w, int window, double thresh, int flags, float* sens,

@@ -444,4 +444,18 @@ hipError_t launch_toeplitz_cols(float2* buf, const float* K, const float2* tw, i
 hipError_t launch_toeplitz_rows_inv(const float2* buf, const float2* tw, const float2* pv, const float* mu, const float* tact, float2* q,
                                     double* partial, int planes, int H, int W, hipStream_t s);
 
+// ---- density compensation (dcf_kernels.hip; the iteration: include/pnpadmm_dcf.h) ----------------------
+// The weights of a pass: w64 [M] (the float64 iterate), else w32 [M] (the caller's float32 start; an entry that is not positive and finite
+// reads as 1), else 1.
+int dcf_gather_blocks(int64_t m);                          // workgroups (= maxima per pass) of the gather
+int dcf_sum_chunks(int64_t m);                             // partial sums of the finish
+// grid [gh, gw] float64 = G^T w: every grid point is written
+hipError_t launch_dcf_spread(const double* w64, const float* w32, const NufftDev& P, double* grid, hipStream_t s);
+// d = G grid; psi [M] = float32(d), wout [M] = w / d, wmax [dcf_gather_blocks] = max |d - 1| per workgroup; each may be nullptr
+hipError_t launch_dcf_gather(const double* grid, const NufftDev& P, const double* w64, const float* w32, double* wout, float* psi, float* wmax,
+                             hipStream_t s);
+// out [M] = float32(w (h w / sum w)); info [passes] = the maximum of each pass's wmax row (info may be nullptr); partial [dcf_sum_chunks]
+hipError_t launch_dcf_finish(const double* w, double* partial, const NufftDev& P, float* out, const float* wmax, int passes, float* info,
+                             hipStream_t s);
+
 }  // namespace pnp

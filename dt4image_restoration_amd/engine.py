@@ -292,6 +292,34 @@ class PnPEngine:
                    "pnp_toeplitz_apply_mc")
         return out
 
+    # -- density compensation (include/pnpadmm_dcf.h) ------------------------------------------
+    def _positive(self, w: torch.Tensor, name: str) -> torch.Tensor:
+        """float32 [M] weights that are positive and finite (one read-back: a setup-time check; the library reads any other entry as 1)"""
+        self._chk(w, torch.float32, self.nufft_samples or w.numel(), name)
+        if not bool(((w > 0) & torch.isfinite(w)).all()):
+            raise ValueError(f"{name}: every weight must be positive and finite")
+        return w
+
+    def nufft_psi(self, w: torch.Tensor) -> torch.Tensor:
+        """float32 [M] = Psi w, Psi = G G^T with G the planned gridding kernel, evaluated in float64 (pnp_nufft_psi); w float32 [M],
+        positive and finite (ValueError otherwise)."""
+        self._positive(w, "w")
+        out = torch.empty(w.numel(), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pnp_nufft_psi(self._h, w.data_ptr(), out.data_ptr(), self._stream()), "pnp_nufft_psi")
+        return out
+
+    def nufft_dcf(self, iters: int = 30, w0: Optional[torch.Tensor] = None, return_info: bool = False):
+        """float32 [M]: density weights of the planned trajectory by `iters` (1..256) Pipe-Menon iterations w <- w / (Psi w) from w0 (float32
+        [M], positive and finite - ValueError otherwise - or None: ones), scaled to sum h w (pnp_nufft_dcf).  return_info: (w, info) with
+        info float32 [iters + 1] = max |Psi w - 1| before each iteration and after the last."""
+        iters = int(iters)
+        if w0 is not None:
+            self._positive(w0, "w0")
+        w = torch.empty(max(self.nufft_samples, 1), dtype=torch.float32, device=self.device)
+        info = torch.empty(max(iters, 0) + 1, dtype=torch.float32, device=self.device) if return_info else None
+        _lib.check(self.lib.pnp_nufft_dcf(self._h, _ptr(w0), iters, 0, w.data_ptr(), _ptr(info), self._stream()), "pnp_nufft_dcf")
+        return (w, info) if return_info else w
+
     def nc_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
         """q = A^H W A p + mu p with the installed non-Cartesian constants (pnp_nc_normal); p complex64 [N,1,H,W], mu float32 [N]."""
         self._chk(p, torch.complex64, self.n * self.h * self.w, "p"); self._chk(mu, torch.float32, self.n, "mu")
