@@ -76,12 +76,26 @@ struct EventPair {
     int count;      // kernel launches between the two events (a run of same-class kernels shares one pair)
 };
 
+// The handle's live data-fidelity stage: the constants installed LAST, which pnp_step / pnp_prox_dual solve with and PNP_RES_DC measures
+// against.  STAGE_NONE: nothing installed yet, or dropped with the plan it was built on; STAGE_CART: the closed form (pnp_reset /
+// pnp_set_kspace); STAGE_MC: SENSE; STAGE_NC: non-Cartesian; STAGE_NS: non-Cartesian SENSE.  The three last run a CG on stage_normal().
+// Written by commit_stage and drop_stage only.
+enum StageKind { STAGE_NONE, STAGE_CART, STAGE_MC, STAGE_NC, STAGE_NS };
+struct LiveStage {
+    StageKind kind = STAGE_NONE;
+    bool toeplitz = false;       // STAGE_NC, STAGE_NS: a _tz installer, the CG runs on the Toeplitz operator
+    int coils = 0;               // STAGE_MC, STAGE_NS: coils of the installed constants
+    int sens_n = 1;
+    int cg = 0;                  // CG iterations per step
+    bool has_w = false;          // STAGE_NC, STAGE_NS: weights were installed (nc_w / ns_w; else they are 1)
+};
+
 }  // namespace
 
 struct pnp_engine {
     pnp_config cfg;
     bool weights_loaded = false;
-    bool reset_done = false;
+    LiveStage stage;
     // denoiser
     float* d_wpack[N_LAYERS] = {};   // packed conv3x3 weights, raw for the first and the last layer
     float* d_bias[N_LAYERS] = {};
@@ -100,9 +114,6 @@ struct pnp_engine {
     int mask_n = 1;
     size_t ws_bytes = 0;
     // multi-coil (SENSE) data-fidelity stage: allocated / grown by pnp_set_kspace_mc, pnp_reset_mc, pnp_acquire_mc
-    int mc_coils = 0;            // coils of the installed constants; 0: the single-coil stage runs
-    int mc_cg = 0;               // CG iterations per step
-    int mc_sens_n = 1;
     float2* mc_y = nullptr;      // [N,C,H,W] sgn * S y per coil (reset_kernel's y0s convention)
     float2* mc_work = nullptr;   // [N,C,H,W] coil-image scratch
     float2* mc_sens = nullptr;   // [sens_n,C,H,W]
@@ -132,12 +143,9 @@ struct pnp_engine {
     float2* nc_grid = nullptr;   // [N, gh, gw] the oversampled grid
     float2* nc_samp = nullptr;   // [N, M] sample scratch (A p inside the normal operator, A x of the misfit)
     float2* nc_y = nullptr;      // [N, M] the installed samples
-    float* nc_w = nullptr;       // [M] the installed weights (read only while nc_has_w)
+    float* nc_w = nullptr;       // [M] the installed weights (read only through stage_w)
     double* nc_mpart = nullptr;  // [N, nufft_sample_chunks(M)] partial sums of the misfit
     size_t nc_grid_cap = 0, nc_samp_cap = 0, nc_y_cap = 0, nc_w_cap = 0, nc_mpart_cap = 0;
-    bool nc_on = false;          // non-Cartesian constants were installed last: the CG stage runs on the NUFFT normal operator
-    bool nc_has_w = false;
-    int nc_cg = 0;               // CG iterations per step
     // non-Cartesian SENSE (include/pnpadmm_ncsense.h): the coil-block scratch by every entry point of that header, the constants by its installers
     int ns_block = kNcsenseBlock; // coils per block: kNcsenseBlock, or PNP_NCSENSE_COIL_BLOCK (read at pnp_create)
     int ns_naive = kNcsenseNaiveSteps;   // NcsenseStep bits: the steps that run as the single-coil launches at batch N cb (PNP_NCSENSE_NAIVE: all or none)
@@ -147,13 +155,9 @@ struct pnp_engine {
     float2* ns_samp = nullptr;   // [N, cb, M] the block's samples (A p inside the normal operator, A x of the misfit)
     float2* ns_y = nullptr;      // [N, C, M] the installed samples
     float2* ns_sens = nullptr;   // [sens_n, C, H, W] the installed maps
-    float* ns_w = nullptr;       // [M] the installed weights (read only while ns_has_w)
+    float* ns_w = nullptr;       // [M] the installed weights (read only through stage_w)
     double* ns_mpart = nullptr;  // [N, C, nufft_sample_chunks(M)] partial sums of the misfit
     size_t ns_grid_cap = 0, ns_samp_cap = 0, ns_y_cap = 0, ns_sens_cap = 0, ns_w_cap = 0, ns_mpart_cap = 0;
-    int ns_coils = 0;            // coils of the installed constants; > 0: they were installed last and the CG stage runs on the coil operator
-    int ns_sens_n = 1;
-    bool ns_has_w = false;
-    int ns_cg = 0;               // CG iterations per step
     // Toeplitz normal operator (include/pnpadmm_toeplitz.h): the spectrum and its buffers by pnp_toeplitz_plan
     std::vector<double> nc_traj; // host copy of the planned trajectory [M][2] (ky, kx): what the spectrum is built from
     double* tz_traj = nullptr;   // [M][2] its device copy
@@ -167,7 +171,6 @@ struct pnp_engine {
     size_t tz_traj_cap = 0, tz_k_cap = 0, tz_w_cap = 0, tz_twh_cap = 0, tz_tww_cap = 0, tz_grid_cap = 0;
     bool tz_planned = false;     // a spectrum exists for the handle's NUFFT plan
     bool tz_has_w = false;
-    bool tz_on = false;          // the live non-Cartesian stage (nc_on or ns_coils > 0) runs its CG on the Toeplitz operator
     // density compensation (include/pnpadmm_dcf.h): its own workspace, grown inside pnp_nufft_psi / pnp_nufft_dcf
     double* dcf_grid = nullptr;  // [gh, gw] G^T w
     double* dcf_w = nullptr;     // [M] the float64 iterate
@@ -401,11 +404,11 @@ float2* mc_q(pnp_engine* e) { return e->mc_vec + 3 * (size_t)e->cfg.n * e->cfg.h
 
 // q = A^H A pv + mu pv; the partial sums of Re<pv, q> go to mc_part.  Unfused: seven launches.
 int mc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, C = e->mc_coils;
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, C = e->stage.coils;
     int rc;
     {
         Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_sense_expand(pv, nullptr, e->mc_sens, e->mc_sens_n, C, tact, e->mc_work, N, H, W, s));
+        HIP_TRY(launch_sense_expand(pv, nullptr, e->mc_sens, e->stage.sens_n, C, tact, e->mc_work, N, H, W, s));
     }
     if ((rc = plain_fft2(e, e->mc_work, e->mc_work, N * C, 0, s))) return rc;
     {
@@ -414,11 +417,13 @@ int mc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
     }
     if ((rc = plain_fft2(e, e->mc_work, e->mc_work, N * C, 1, s))) return rc;
     Prof p(e, s, PROF_OTHER, -1);
-    HIP_TRY(launch_sense_combine(e->mc_work, e->mc_sens, e->mc_sens_n, C, pv, mu, tact, q, e->mc_part, N, H, W, s));
+    HIP_TRY(launch_sense_combine(e->mc_work, e->mc_sens, e->stage.sens_n, C, pv, mu, tact, q, e->mc_part, N, H, W, s));
     return PNP_OK;
 }
 
 // ---- non-Cartesian stage ----------------------------------------------------------------------------
+// the live non-Cartesian stage's weights (nullptr: 1)
+const float* stage_w(const pnp_engine* e) { return !e->stage.has_w ? nullptr : e->stage.kind == STAGE_NS ? e->ns_w : e->nc_w; }
 // the centred transform of pnp_fft2c on the plan's grid, in place in nc_grid: rows then columns in both directions
 int nc_fft(pnp_engine* e, int batch, int inverse, hipStream_t s) {
     const NufftDev& P = e->nc;
@@ -457,7 +462,7 @@ int nc_adjoint(pnp_engine* e, const float2* y, const float* w, int batch, const 
 // (the others rewrite scratch alone)
 int nc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
     if (int rc = nc_forward(e, pv, nullptr, e->cfg.n, e->nc_samp, s)) return rc;
-    return nc_adjoint(e, e->nc_samp, e->nc_has_w ? e->nc_w : nullptr, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
+    return nc_adjoint(e, e->nc_samp, stage_w(e), e->cfg.n, pv, mu, tact, q, e->mc_part, s);
 }
 
 // ---- non-Cartesian SENSE stage (include/pnpadmm_ncsense.h) --------------------------------------------
@@ -544,12 +549,12 @@ int ns_adjoint(pnp_engine* e, const float2* y, const float* w, const float2* sen
 // q = A^H W A pv + mu pv with the installed constants; the partial sums of Re<pv, q> go to mc_part.  Eight launches per coil block: a block's
 // samples go through ns_samp and are gridded before the next block's grids replace them.  Stopped slices: only the combine launches skip them
 int ns_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    const int N = e->cfg.n, C = e->ns_coils, B = ns_block_of(e, C);
-    const float* w = e->ns_has_w ? e->ns_w : nullptr;
+    const int N = e->cfg.n, C = e->stage.coils, sens_n = e->stage.sens_n, B = ns_block_of(e, C);
+    const float* w = stage_w(e);
     for (int c0 = 0; c0 < C; c0 += B) {
         const int cb = std::min(B, C - c0);
-        if (int rc = ns_forward_block(e, pv, nullptr, e->ns_sens, e->ns_sens_n, C, c0, cb, N, e->ns_samp, cb, 0, s)) return rc;
-        if (int rc = ns_adjoint_block(e, e->ns_samp, cb, 0, w, e->ns_sens, e->ns_sens_n, C, c0, cb, N, pv, mu, tact, q, e->mc_part, s)) return rc;
+        if (int rc = ns_forward_block(e, pv, nullptr, e->ns_sens, sens_n, C, c0, cb, N, e->ns_samp, cb, 0, s)) return rc;
+        if (int rc = ns_adjoint_block(e, e->ns_samp, cb, 0, w, e->ns_sens, sens_n, C, c0, cb, N, pv, mu, tact, q, e->mc_part, s)) return rc;
     }
     return PNP_OK;
 }
@@ -619,12 +624,21 @@ int tz_nc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* 
     return tz_apply(e, pv, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
 }
 int tz_ns_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    return tz_apply_mc(e, pv, e->ns_sens, e->ns_sens_n, e->ns_coils, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
+    return tz_apply_mc(e, pv, e->ns_sens, e->stage.sens_n, e->stage.coils, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
 }
 
 // the K-step CG solve of (A^H A + mu I) z = A^H y + mu (x + u), warm-started from z, then u <- u + x - z; `normal`: the stage's normal
 // operator (mc_normal: the coil operator, nc_normal: the NUFFT pair, ns_normal: both), which also leaves the partial sums of Re<p, q> in mc_part
 using NormalOp = int (*)(pnp_engine*, const float2*, const float*, const float*, float2*, hipStream_t);
+// the live stage's normal operator, run stage.cg times per step (nullptr: the stage has none - the closed form, or nothing installed)
+NormalOp stage_normal(const pnp_engine* e) {
+    switch (e->stage.kind) {
+    case STAGE_MC: return mc_normal;
+    case STAGE_NC: return e->stage.toeplitz ? tz_nc_normal : nc_normal;
+    case STAGE_NS: return e->stage.toeplitz ? tz_ns_normal : ns_normal;
+    default: return nullptr;
+    }
+}
 int run_prox_dual_cg(pnp_engine* e, NormalOp normal, int iters, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                      hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
@@ -724,20 +738,50 @@ int mc_check(const char* fn, pnp_engine* e, int coils, int sens_n, int mask_n) {
     return PNP_OK;
 }
 
-int mc_install(pnp_engine* e, const float2* x0, const float2* y0, const float2* sens, int coils, int sens_n, const uint8_t* mask, int mask_n,
-               int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
+// The one way a stage becomes live: an installer's last statement, after its last launch was accepted.  A failed HIP call inside an
+// installer therefore leaves the handle in the stage it had (its CG vectors and, for the Cartesian stages, its mask are rewritten by the
+// next install); nothing between an installer's first launch and this line reads the record - the launches take the new constants as arguments.
+void commit_stage(pnp_engine* e, const LiveStage& st) { e->stage = st; }
+// pnp_nufft_plan (any non-Cartesian stage) and pnp_toeplitz_plan (`toeplitz_only`): a live stage built on the plan or spectrum being
+// replaced loses its constants with it.  The closed-form and SENSE stages use neither and stay.
+void drop_stage(pnp_engine* e, bool toeplitz_only) {
+    const LiveStage& st = e->stage;
+    if ((st.kind == STAGE_NC || st.kind == STAGE_NS) && (st.toeplitz || !toeplitz_only)) e->stage = LiveStage{};
+}
+
+// pnp_set_kspace (no iterate) / pnp_reset: the closed-form stage's constants
+int cart_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x0, const float2* y0, const uint8_t* mask, int mask_n, float* x,
+                 float2* z, float2* u, hipStream_t s) {
+    if (!e || !y0 || !mask || (with_iterate && (!x0 || !x || !z || !u))) return fail(PNP_ERR_INVALID, "%s: null argument", fn);
+    if (mask_n != 1 && mask_n != e->cfg.n) return fail(PNP_ERR_INVALID, "%s: mask_n must be 1 or n=%d", fn, e->cfg.n);
+    if (int rc = check_kspace_sizes(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    e->mask_n = mask_n;
+    HIP_TRY(launch_reset(x0, y0, mask, mask_n, x, z, u, e->d_y0s, e->d_masks, e->cfg.n, e->cfg.h, e->cfg.w, s));
+    commit_stage(e, {STAGE_CART});
+    return PNP_OK;
+}
+
+// pnp_set_kspace_mc (no iterate) / pnp_reset_mc: the SENSE stage's constants.  Every rejection happens before any HIP call; scalar ranges first
+int mc_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x0, const float2* y0, const float2* sens, int coils, int sens_n,
+               const uint8_t* mask, int mask_n, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
+    if (cg_iters < 1 || cg_iters > PNP_MC_MAX_CG) return fail(PNP_ERR_INVALID, "%s: cg_iters must be 1..%d (got %d)", fn, PNP_MC_MAX_CG, cg_iters);
+    int rc;
+    if ((rc = mc_check_scalars(fn, coils, sens_n, mask_n))) return rc;
+    if (with_iterate && !x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
+    if (!y0) return fail(PNP_ERR_INVALID, "%s: null y0", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!mask) return fail(PNP_ERR_INVALID, "%s: null mask", fn);
+    if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if ((rc = mc_check(fn, e, coils, sens_n, mask_n))) return rc;
+    PNP_ON_DEVICE(e);
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
     const size_t hw = (size_t)H * W, img = (size_t)N * coils * hw, sn = (size_t)sens_n * coils * hw;
-    int rc;
     if ((rc = mc_ensure(e, img, img, sn))) return rc;
     HIP_TRY(hipMemcpyAsync(e->mc_sens, sens, sn * sizeof(float2), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
     e->mask_n = mask_n;
-    e->mc_coils = coils; e->mc_cg = cg_iters; e->mc_sens_n = sens_n;
-    e->nc_on = false;
-    e->ns_coils = 0;
-    e->tz_on = false;
-    e->reset_done = true;
     {
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_install(y0, mask, mask_n, coils, e->mc_y, e->mc_work, e->d_masks, N, H, W, s));
@@ -748,10 +792,11 @@ int mc_install(pnp_engine* e, const float2* x0, const float2* y0, const float2* 
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_combine(e->mc_work, e->mc_sens, sens_n, coils, nullptr, nullptr, nullptr, mc_aty(e), nullptr, N, H, W, s));
     }
-    if (x0) {
+    if (with_iterate) {
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
     }
+    commit_stage(e, {STAGE_MC, false, coils, sens_n, cg_iters});
     return PNP_OK;
 }
 
@@ -874,10 +919,7 @@ int run_haar(pnp_engine* e, const float* v, const float2* z, const float2* u, co
 int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                   hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
-    // non-Cartesian SENSE / non-Cartesian constants installed last; a _tz installer: the same CG on the Toeplitz operator
-    if (e->ns_coils > 0) return run_prox_dual_cg(e, e->tz_on ? tz_ns_normal : ns_normal, e->ns_cg, mu, tact, x, z, u, s);
-    if (e->nc_on) return run_prox_dual_cg(e, e->tz_on ? tz_nc_normal : nc_normal, e->nc_cg, mu, tact, x, z, u, s);
-    if (e->mc_coils > 0) return run_prox_dual_cg(e, mc_normal, e->mc_cg, mu, tact, x, z, u, s);   // multi-coil constants installed: the CG stage
+    if (NormalOp normal = stage_normal(e)) return run_prox_dual_cg(e, normal, e->stage.cg, mu, tact, x, z, u, s);   // a CG stage
     if (H == 128 && W == 128 && N >= e->tune.slice128_min_n) {   // chip-filling batches of the reference's slice size: 37 B/px
         Prof p(e, s, PROF_FFT_COLS, -1);
         HIP_TRY(launch_admm_slice128(x, z, u, e->plan.tw_w, e->d_y0s, e->d_masks, e->mask_n, mu, tact, N, s));
@@ -896,6 +938,80 @@ int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float
         HIP_TRY(launch_fft_rows_inv_admm(e->d_work, x, z, u, e->plan.tw_w, tact, N, H, W, s));
     }
     return PNP_OK;
+}
+
+// pnp_residuals' PNP_RES_DC: the partial sums of the live stage's data misfit of x into dcpart
+int stage_misfit(pnp_engine* e, const float* x, double* dcpart, hipStream_t s) {
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, C = e->stage.coils;
+    switch (e->stage.kind) {
+    case STAGE_NS: {
+        // A x block by block into the sample scratch, then sum_c sum_m w_m |(A x)_{c,m} - y_{c,m}|^2
+        const int B = ns_block_of(e, C);
+        for (int c0 = 0; c0 < C; c0 += B) {
+            const int cb = std::min(B, C - c0);
+            if (int rc = ns_forward_block(e, nullptr, x, e->ns_sens, e->stage.sens_n, C, c0, cb, N, e->ns_samp, cb, 0, s)) return rc;
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_ncsense_misfit(e->ns_samp, e->ns_y, stage_w(e), C, c0, cb, e->nc, e->ns_mpart, N, s));
+        }
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_ncsense_misfit_sum(e->ns_mpart, C, e->nc, dcpart, N, s));
+        return PNP_OK;
+    }
+    case STAGE_NC: {
+        // A x into the sample scratch, then sum_m w_m |(A x)_m - y_m|^2
+        if (int rc = nc_forward(e, nullptr, x, N, e->nc_samp, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_nufft_misfit(e->nc_samp, e->nc_y, stage_w(e), e->nc, e->nc_mpart, dcpart, N, s));
+        return PNP_OK;
+    }
+    case STAGE_MC: {
+        // the plain transforms of S_c x into the coil scratch, then sum_c ||M (FFT(S_c x) - ys_c)||^2
+        {
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_sense_expand(nullptr, x, e->mc_sens, e->stage.sens_n, C, nullptr, e->mc_work, N, H, W, s));
+        }
+        if (int rc = plain_fft2(e, e->mc_work, e->mc_work, N * C, 0, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_sense_misfit(e->mc_work, e->mc_y, e->d_masks, e->mask_n, C, dcpart, N, H, W, s));
+        return PNP_OK;
+    }
+    case STAGE_CART: {
+        // the plain transform of x into the data-fidelity stage's scratch; the shifts of fft_c live in the stored constants (reset_kernel)
+        if (int rc = plain_fft2(e, nullptr, e->d_work, N, 0, s, x)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_misfit_tiles(e->d_work, e->d_y0s, e->d_masks, e->mask_n, dcpart, N, H, W, s));
+        return PNP_OK;
+    }
+    case STAGE_NONE: break;                                // pnp_residuals has refused it
+    }
+    return PNP_OK;
+}
+
+// the refusal of an entry point that serves one CG stage while another stage is live: each stage's own sentence
+int need_stage(const char* fn, const pnp_engine* e, StageKind kind) {
+    if (e->stage.kind == kind) return PNP_OK;
+    switch (kind) {
+    case STAGE_MC: return fail(PNP_ERR_STATE, "%s: the handle is in single-coil mode (pnp_set_kspace_mc / pnp_reset_mc)", fn);
+    case STAGE_NC: return fail(PNP_ERR_STATE, "%s: the handle is not in non-Cartesian mode (pnp_set_kspace_nc / pnp_reset_nc)", fn);
+    default: return fail(PNP_ERR_STATE, "%s: the handle is not in non-Cartesian SENSE mode (pnp_set_kspace_ncsense / pnp_reset_ncsense)", fn);
+    }
+}
+// pnp_{mc,nc,ncsense}_cg_residual
+int stage_cg_residual(const char* fn, pnp_engine* e, StageKind kind, float* out, hipStream_t s) {
+    if (!e || !out) return fail(PNP_ERR_INVALID, "%s: null argument", fn);
+    if (int rc = need_stage(fn, e, kind)) return rc;
+    PNP_ON_DEVICE(e);
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_sense_cgres(e->mc_sc, out, e->cfg.n, s));
+    return PNP_OK;
+}
+// pnp_{mc,nc,ncsense}_normal
+int stage_normal_op(const char* fn, pnp_engine* e, StageKind kind, const float* pv, const float* mu, float* q, hipStream_t s) {
+    if (!e || !pv || !mu || !q) return fail(PNP_ERR_INVALID, "%s: null argument", fn);
+    if (pv == q) return fail(PNP_ERR_INVALID, "%s: p and q must not alias", fn);
+    if (int rc = need_stage(fn, e, kind)) return rc;
+    PNP_ON_DEVICE(e);
+    return stage_normal(e)(e, (const float2*)pv, mu, nullptr, (float2*)q, s);
 }
 
 }  // namespace
@@ -1087,37 +1203,13 @@ int pnp_load_unet_weights(pnp_handle e, const float* blob, size_t n_floats) {
 int pnp_reset(pnp_handle e, const float* x0, const float* y0, const uint8_t* mask, int mask_n, float* x, float* z,
               float* u, void* stream) {
     PNP_API_BEGIN
-    if (!e || !x0 || !y0 || !mask || !x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_reset: null argument");
-    if (mask_n != 1 && mask_n != e->cfg.n) return fail(PNP_ERR_INVALID, "pnp_reset: mask_n must be 1 or n=%d", e->cfg.n);
-    if (int rc = check_kspace_sizes("pnp_reset", e)) return rc;
-    PNP_ON_DEVICE(e);
-    e->mask_n = mask_n;
-    e->mc_coils = 0;                                       // back to the single-coil stage
-    e->nc_on = false;
-    e->ns_coils = 0;
-    e->tz_on = false;
-    HIP_TRY(launch_reset((const float2*)x0, (const float2*)y0, mask, mask_n, x, (float2*)z, (float2*)u, e->d_y0s,
-                         e->d_masks, e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
-    e->reset_done = true;
-    return PNP_OK;
+    return cart_install("pnp_reset", e, true, (const float2*)x0, (const float2*)y0, mask, mask_n, x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset")
 }
 
 int pnp_set_kspace(pnp_handle e, const float* y0, const uint8_t* mask, int mask_n, void* stream) {
     PNP_API_BEGIN
-    if (!e || !y0 || !mask) return fail(PNP_ERR_INVALID, "pnp_set_kspace: null argument");
-    if (mask_n != 1 && mask_n != e->cfg.n) return fail(PNP_ERR_INVALID, "pnp_set_kspace: mask_n must be 1 or n=%d", e->cfg.n);
-    if (int rc = check_kspace_sizes("pnp_set_kspace", e)) return rc;
-    PNP_ON_DEVICE(e);
-    e->mask_n = mask_n;
-    e->mc_coils = 0;                                       // back to the single-coil stage
-    e->nc_on = false;
-    e->ns_coils = 0;
-    e->tz_on = false;
-    HIP_TRY(launch_reset(nullptr, (const float2*)y0, mask, mask_n, nullptr, nullptr, nullptr, e->d_y0s, e->d_masks,
-                         e->cfg.n, e->cfg.h, e->cfg.w, (hipStream_t)stream));
-    e->reset_done = true;
-    return PNP_OK;
+    return cart_install("pnp_set_kspace", e, false, nullptr, (const float2*)y0, mask, mask_n, nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace")
 }
 
@@ -1127,7 +1219,7 @@ int pnp_step(pnp_handle e, const float* mu, const float* sigma_d, const float* t
     if (!e || !mu || !sigma_d || !x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_step: null argument");
     const bool tv = e->prior == PNP_PRIOR_TV, haar = e->prior == PNP_PRIOR_HAAR;
     if (!tv && !haar && !e->weights_loaded) return fail(PNP_ERR_STATE, "pnp_step: denoiser weights not loaded (pnp_load_unet_weights)");
-    if (!e->reset_done) return fail(PNP_ERR_STATE, "pnp_step: pnp_reset has not been called");
+    if (e->stage.kind == STAGE_NONE) return fail(PNP_ERR_STATE, "pnp_step: pnp_reset has not been called");
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     int rc;
@@ -1275,7 +1367,7 @@ int pnp_prox_dual(pnp_handle e, const float* mu, const float* t_action, const fl
                   void* stream) {
     PNP_API_BEGIN
     if (!e || !mu || !x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_prox_dual: null argument");
-    if (!e->reset_done) return fail(PNP_ERR_STATE, "pnp_prox_dual: pnp_reset has not been called");
+    if (e->stage.kind == STAGE_NONE) return fail(PNP_ERR_STATE, "pnp_prox_dual: pnp_reset has not been called");
     PNP_ON_DEVICE(e);
     return run_prox_dual(e, mu, t_action, x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_prox_dual")
@@ -1334,7 +1426,7 @@ int pnp_residuals(pnp_handle e, const float* x, const float* z, const float* u, 
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
     if (flags & PNP_RES_DC) {
         if (int rc = check_kspace_sizes("pnp_residuals", e, "PNP_RES_DC takes h, w in")) return rc;
-        if (!e->reset_done) return fail(PNP_ERR_STATE, "pnp_residuals: PNP_RES_DC needs the episode's k-space constants (pnp_reset / pnp_set_kspace)");
+        if (e->stage.kind == STAGE_NONE) return fail(PNP_ERR_STATE, "pnp_residuals: PNP_RES_DC needs the episode's k-space constants (pnp_reset / pnp_set_kspace)");
     }
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
@@ -1347,38 +1439,8 @@ int pnp_residuals(pnp_handle e, const float* x, const float* z, const float* u, 
         HIP_TRY(launch_residual_tiles(x, (const float2*)z, (const float2*)u, (const float*)pv, pv ? (const float2*)(pv + snap.z_off()) : nullptr,
                                       pv ? (const float2*)(pv + snap.u_off()) : nullptr, part, N, H, W, s));
     }
-    if ((flags & PNP_RES_DC) && e->ns_coils > 0) {
-        // non-Cartesian SENSE mode: A x block by block into the sample scratch, then sum_c sum_m w_m |(A x)_{c,m} - y_{c,m}|^2
-        const int C = e->ns_coils, B = ns_block_of(e, C);
-        for (int c0 = 0; c0 < C; c0 += B) {
-            const int cb = std::min(B, C - c0);
-            if (int rc = ns_forward_block(e, nullptr, x, e->ns_sens, e->ns_sens_n, C, c0, cb, N, e->ns_samp, cb, 0, s)) return rc;
-            Prof p(e, s, PROF_OTHER, -1);
-            HIP_TRY(launch_ncsense_misfit(e->ns_samp, e->ns_y, e->ns_has_w ? e->ns_w : nullptr, C, c0, cb, e->nc, e->ns_mpart, N, s));
-        }
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_ncsense_misfit_sum(e->ns_mpart, C, e->nc, dcpart, N, s));
-    } else if ((flags & PNP_RES_DC) && e->nc_on) {
-        // non-Cartesian mode: A x into the sample scratch, then sum_m w_m |(A x)_m - y_m|^2
-        if (int rc = nc_forward(e, nullptr, x, N, e->nc_samp, s)) return rc;
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_nufft_misfit(e->nc_samp, e->nc_y, e->nc_has_w ? e->nc_w : nullptr, e->nc, e->nc_mpart, dcpart, N, s));
-    } else if ((flags & PNP_RES_DC) && e->mc_coils > 0) {
-        // multi-coil mode: the plain transforms of S_c x into the coil scratch, then sum_c ||M (FFT(S_c x) - ys_c)||^2
-        int rc;
-        {
-            Prof p(e, s, PROF_OTHER, -1);
-            HIP_TRY(launch_sense_expand(nullptr, x, e->mc_sens, e->mc_sens_n, e->mc_coils, nullptr, e->mc_work, N, H, W, s));
-        }
-        if ((rc = plain_fft2(e, e->mc_work, e->mc_work, N * e->mc_coils, 0, s))) return rc;
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_sense_misfit(e->mc_work, e->mc_y, e->d_masks, e->mask_n, e->mc_coils, dcpart, N, H, W, s));
-    } else if (flags & PNP_RES_DC) {
-        // the plain transform of x into the data-fidelity stage's scratch; the shifts of fft_c live in the stored constants (reset_kernel)
-        if (int rc = plain_fft2(e, nullptr, e->d_work, N, 0, s, x)) return rc;
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_misfit_tiles(e->d_work, e->d_y0s, e->d_masks, e->mask_n, dcpart, N, H, W, s));
-    }
+    if (flags & PNP_RES_DC)
+        if (int rc = stage_misfit(e, x, dcpart, s)) return rc;
     Prof p(e, s, PROF_OTHER, -1);
     HIP_TRY(launch_residual_reduce(part, dcpart, (flags & PNP_RES_DELTA) ? 1 : 0, (flags & PNP_RES_DC) ? 1 : 0, out, N, H, W, s));
     return PNP_OK;
@@ -1422,58 +1484,30 @@ int pnp_acquire(pnp_handle e, const float* gt, const uint8_t* mask, int mask_n, 
 int pnp_set_kspace_mc(pnp_handle e, const float* y0, const float* sens, int coils, int sens_n, const uint8_t* mask, int mask_n, int cg_iters,
                       void* stream) {
     PNP_API_BEGIN
-    // every rejection happens before any HIP call; scalar ranges first
-    if (cg_iters < 1 || cg_iters > PNP_MC_MAX_CG) return fail(PNP_ERR_INVALID, "pnp_set_kspace_mc: cg_iters must be 1..%d (got %d)", PNP_MC_MAX_CG, cg_iters);
-    if (int rc = mc_check_scalars("pnp_set_kspace_mc", coils, sens_n, mask_n)) return rc;
-    if (!y0) return fail(PNP_ERR_INVALID, "pnp_set_kspace_mc: null y0");
-    if (!sens) return fail(PNP_ERR_INVALID, "pnp_set_kspace_mc: null sens");
-    if (!mask) return fail(PNP_ERR_INVALID, "pnp_set_kspace_mc: null mask");
-    if (!e) return fail(PNP_ERR_INVALID, "pnp_set_kspace_mc: null handle");
-    if (int rc = mc_check("pnp_set_kspace_mc", e, coils, sens_n, mask_n)) return rc;
-    PNP_ON_DEVICE(e);
-    return mc_install(e, nullptr, (const float2*)y0, (const float2*)sens, coils, sens_n, mask, mask_n, cg_iters, nullptr, nullptr, nullptr,
-                      (hipStream_t)stream);
+    return mc_install("pnp_set_kspace_mc", e, false, nullptr, (const float2*)y0, (const float2*)sens, coils, sens_n, mask, mask_n, cg_iters, nullptr,
+                      nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_mc")
 }
 
 int pnp_reset_mc(pnp_handle e, const float* x0, const float* y0, const float* sens, int coils, int sens_n, const uint8_t* mask, int mask_n,
                  int cg_iters, float* x, float* z, float* u, void* stream) {
     PNP_API_BEGIN
-    if (cg_iters < 1 || cg_iters > PNP_MC_MAX_CG) return fail(PNP_ERR_INVALID, "pnp_reset_mc: cg_iters must be 1..%d (got %d)", PNP_MC_MAX_CG, cg_iters);
-    if (int rc = mc_check_scalars("pnp_reset_mc", coils, sens_n, mask_n)) return rc;
-    if (!x0) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null x0");
-    if (!y0) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null y0");
-    if (!sens) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null sens");
-    if (!mask) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null mask");
-    if (!x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null x, z or u");
-    if (!e) return fail(PNP_ERR_INVALID, "pnp_reset_mc: null handle");
-    if (int rc = mc_check("pnp_reset_mc", e, coils, sens_n, mask_n)) return rc;
-    PNP_ON_DEVICE(e);
-    return mc_install(e, (const float2*)x0, (const float2*)y0, (const float2*)sens, coils, sens_n, mask, mask_n, cg_iters, x, (float2*)z,
-                      (float2*)u, (hipStream_t)stream);
+    return mc_install("pnp_reset_mc", e, true, (const float2*)x0, (const float2*)y0, (const float2*)sens, coils, sens_n, mask, mask_n, cg_iters, x,
+                      (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_mc")
 }
 
-int pnp_mc_coils(pnp_handle e) { return e ? e->mc_coils : 0; }
+int pnp_mc_coils(pnp_handle e) { return e && e->stage.kind == STAGE_MC ? e->stage.coils : 0; }
 
 int pnp_mc_cg_residual(pnp_handle e, float* out, void* stream) {
     PNP_API_BEGIN
-    if (!e || !out) return fail(PNP_ERR_INVALID, "pnp_mc_cg_residual: null argument");
-    if (e->mc_coils == 0) return fail(PNP_ERR_STATE, "pnp_mc_cg_residual: the handle is in single-coil mode (pnp_set_kspace_mc / pnp_reset_mc)");
-    PNP_ON_DEVICE(e);
-    Prof p(e, (hipStream_t)stream, PROF_OTHER, -1);
-    HIP_TRY(launch_sense_cgres(e->mc_sc, out, e->cfg.n, (hipStream_t)stream));
-    return PNP_OK;
+    return stage_cg_residual("pnp_mc_cg_residual", e, STAGE_MC, out, (hipStream_t)stream);
     PNP_API_END("pnp_mc_cg_residual")
 }
 
 int pnp_mc_normal(pnp_handle e, const float* pv, const float* mu, float* q, void* stream) {
     PNP_API_BEGIN
-    if (!e || !pv || !mu || !q) return fail(PNP_ERR_INVALID, "pnp_mc_normal: null argument");
-    if (pv == q) return fail(PNP_ERR_INVALID, "pnp_mc_normal: p and q must not alias");
-    if (e->mc_coils == 0) return fail(PNP_ERR_STATE, "pnp_mc_normal: the handle is in single-coil mode (pnp_set_kspace_mc / pnp_reset_mc)");
-    PNP_ON_DEVICE(e);
-    return mc_normal(e, (const float2*)pv, mu, nullptr, (float2*)q, (hipStream_t)stream);
+    return stage_normal_op("pnp_mc_normal", e, STAGE_MC, pv, mu, q, (hipStream_t)stream);
     PNP_API_END("pnp_mc_normal")
 }
 
@@ -1527,11 +1561,39 @@ namespace {
 
 hipError_t nc_upload(void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
 
-// the episode constants of the non-Cartesian stage: y, w, A^H W y, and optionally the iterate
-int nc_install(pnp_engine* e, const float2* x0, const float2* y, const float* w, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
+int nc_need_plan(const char* fn, const pnp_engine* e) {
+    return e->nc.m > 0 ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no NUFFT plan (pnp_nufft_plan)", fn);
+}
+int tz_need_spectrum(const char* fn, const pnp_engine* e) {
+    if (int rc = nc_need_plan(fn, e)) return rc;
+    return e->tz_planned ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no Toeplitz spectrum (pnp_toeplitz_plan)", fn);
+}
+// the Toeplitz pass buffer for `planes` planes and, with `coil_images`, the block's coil images
+int tz_ensure(pnp_engine* e, size_t planes, bool coil_images) {
+    const size_t hw = (size_t)e->cfg.h * e->cfg.w;
+    return ws_grow(e, "Toeplitz scratch", {{(void**)&e->tz_grid, &e->tz_grid_cap, planes * (e->tz_fused ? 2 : 4) * hw * sizeof(float2), false},
+                                          {(void**)&e->ns_img, &e->ns_img_cap, coil_images ? planes * hw * sizeof(float2) : 0, false}});
+}
+int nc_check_cg(const char* fn, int cg_iters) {
+    if (cg_iters < 1 || cg_iters > PNP_MC_MAX_CG) return fail(PNP_ERR_INVALID, "%s: cg_iters must be 1..%d (got %d)", fn, PNP_MC_MAX_CG, cg_iters);
+    return PNP_OK;
+}
+
+// pnp_set_kspace_nc (no iterate) / pnp_reset_nc and, `toeplitz`, their _tz forms (w: the spectrum's weights, whatever is passed): the episode
+// constants of the non-Cartesian stage - y, w, A^H W y - and optionally the iterate.  Every rejection happens before any HIP call
+int nc_install(const char* fn, pnp_engine* e, bool with_iterate, bool toeplitz, const float2* x0, const float2* y, const float* w, int cg_iters,
+               float* x, float2* z, float2* u, hipStream_t s) {
+    int rc;
+    if ((rc = nc_check_cg(fn, cg_iters))) return rc;
+    if (with_iterate && !x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if ((rc = toeplitz ? tz_need_spectrum(fn, e) : nc_need_plan(fn, e))) return rc;
+    PNP_ON_DEVICE(e);
+    if (toeplitz) w = e->tz_has_w ? e->tz_w : nullptr;
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
     const size_t M = (size_t)e->nc.m;
-    int rc;
     if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
     if ((rc = ws_grow(e, "non-Cartesian constants", {{(void**)&e->nc_y, &e->nc_y_cap, (size_t)N * M * sizeof(float2), false},
                                                      {(void**)&e->nc_w, &e->nc_w_cap, w ? M * sizeof(float) : 0, false},
@@ -1541,30 +1603,11 @@ int nc_install(pnp_engine* e, const float2* x0, const float2* y, const float* w,
     if (w) HIP_TRY(hipMemcpyAsync(e->nc_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
     if ((rc = nc_adjoint(e, e->nc_y, w ? e->nc_w : nullptr, N, nullptr, nullptr, nullptr, mc_aty(e), nullptr, s))) return rc;
-    if (x0) {
+    if (with_iterate) {
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
     }
-    // every launch was accepted: only now does the handle change mode (a failed call leaves the mode it had; its CG vectors are rewritten
-    // by the next install of either multi-coil or non-Cartesian constants)
-    e->nc_has_w = w != nullptr;
-    e->nc_cg = cg_iters;
-    e->nc_on = true;
-    e->tz_on = false;
-    e->mc_coils = 0;
-    e->ns_coils = 0;
-    e->reset_done = true;
-    return PNP_OK;
-}
-
-int nc_need_plan(const char* fn, const pnp_engine* e) {
-    return e->nc.m > 0 ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no NUFFT plan (pnp_nufft_plan)", fn);
-}
-int nc_need_mode(const char* fn, const pnp_engine* e) {
-    return e->nc_on ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle is not in non-Cartesian mode (pnp_set_kspace_nc / pnp_reset_nc)", fn);
-}
-int nc_check_cg(const char* fn, int cg_iters) {
-    if (cg_iters < 1 || cg_iters > PNP_MC_MAX_CG) return fail(PNP_ERR_INVALID, "%s: cg_iters must be 1..%d (got %d)", fn, PNP_MC_MAX_CG, cg_iters);
+    commit_stage(e, {STAGE_NC, toeplitz, 0, 1, cg_iters, w != nullptr});
     return PNP_OK;
 }
 
@@ -1600,8 +1643,7 @@ int pnp_nufft_plan(pnp_handle e, const double* traj, int64_t m, int gh, int gw, 
     if (D.m > 0) (void)hipDeviceSynchronize();              // no launch still reads the plan being replaced
     // from here on the old plan is gone: its non-Cartesian constants are dropped with it
     D.m = 0;
-    if (e->nc_on || e->ns_coils > 0) { e->nc_on = false; e->ns_coils = 0; e->reset_done = false; }
-    e->tz_on = false;
+    drop_stage(e, false);
     e->tz_planned = false;                                  // the spectrum belongs to the plan it was built for
     e->nc_traj.assign(traj, traj + 2 * (size_t)m);
     HIP_TRY(nc_upload(D.i0, P.i0.data(), P.i0.size() * sizeof(int32_t)));
@@ -1659,46 +1701,25 @@ int pnp_nufft_adjoint(pnp_handle e, const float* samples, const float* weights, 
 
 int pnp_set_kspace_nc(pnp_handle e, const float* y, const float* w, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    if (int rc = nc_check_cg("pnp_set_kspace_nc", cg_iters)) return rc;
-    if (!y) return fail(PNP_ERR_INVALID, "pnp_set_kspace_nc: null y");
-    if (!e) return fail(PNP_ERR_INVALID, "pnp_set_kspace_nc: null handle");
-    if (int rc = nc_need_plan("pnp_set_kspace_nc", e)) return rc;
-    PNP_ON_DEVICE(e);
-    return nc_install(e, nullptr, (const float2*)y, w, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return nc_install("pnp_set_kspace_nc", e, false, false, nullptr, (const float2*)y, w, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_nc")
 }
 
 int pnp_reset_nc(pnp_handle e, const float* x0, const float* y, const float* w, int cg_iters, float* x, float* z, float* u, void* stream) {
     PNP_API_BEGIN
-    if (int rc = nc_check_cg("pnp_reset_nc", cg_iters)) return rc;
-    if (!x0) return fail(PNP_ERR_INVALID, "pnp_reset_nc: null x0");
-    if (!y) return fail(PNP_ERR_INVALID, "pnp_reset_nc: null y");
-    if (!x || !z || !u) return fail(PNP_ERR_INVALID, "pnp_reset_nc: null x, z or u");
-    if (!e) return fail(PNP_ERR_INVALID, "pnp_reset_nc: null handle");
-    if (int rc = nc_need_plan("pnp_reset_nc", e)) return rc;
-    PNP_ON_DEVICE(e);
-    return nc_install(e, (const float2*)x0, (const float2*)y, w, cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
+    return nc_install("pnp_reset_nc", e, true, false, (const float2*)x0, (const float2*)y, w, cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_nc")
 }
 
 int pnp_nc_cg_residual(pnp_handle e, float* out, void* stream) {
     PNP_API_BEGIN
-    if (!e || !out) return fail(PNP_ERR_INVALID, "pnp_nc_cg_residual: null argument");
-    if (int rc = nc_need_mode("pnp_nc_cg_residual", e)) return rc;
-    PNP_ON_DEVICE(e);
-    Prof p(e, (hipStream_t)stream, PROF_OTHER, -1);
-    HIP_TRY(launch_sense_cgres(e->mc_sc, out, e->cfg.n, (hipStream_t)stream));
-    return PNP_OK;
+    return stage_cg_residual("pnp_nc_cg_residual", e, STAGE_NC, out, (hipStream_t)stream);
     PNP_API_END("pnp_nc_cg_residual")
 }
 
 int pnp_nc_normal(pnp_handle e, const float* pv, const float* mu, float* q, void* stream) {
     PNP_API_BEGIN
-    if (!e || !pv || !mu || !q) return fail(PNP_ERR_INVALID, "pnp_nc_normal: null argument");
-    if (pv == q) return fail(PNP_ERR_INVALID, "pnp_nc_normal: p and q must not alias");
-    if (int rc = nc_need_mode("pnp_nc_normal", e)) return rc;
-    PNP_ON_DEVICE(e);
-    return (e->tz_on ? tz_nc_normal : nc_normal)(e, (const float2*)pv, mu, nullptr, (float2*)q, (hipStream_t)stream);
+    return stage_normal_op("pnp_nc_normal", e, STAGE_NC, pv, mu, q, (hipStream_t)stream);
     PNP_API_END("pnp_nc_normal")
 }
 
@@ -1757,17 +1778,27 @@ int ns_check(const char* fn, const pnp_engine* e, int coils, int sens_n) {
         return fail(PNP_ERR_INVALID, "%s: n * min(coils, block) must be <= 65535 (got %d * %d)", fn, N, ns_block_of(e, coils));
     return nc_need_plan(fn, e);
 }
-int ns_need_mode(const char* fn, const pnp_engine* e) {
-    return e->ns_coils > 0 ? PNP_OK
-                           : fail(PNP_ERR_STATE, "%s: the handle is not in non-Cartesian SENSE mode (pnp_set_kspace_ncsense / pnp_reset_ncsense)", fn);
-}
-
-// the episode constants of the stage: y, w, the maps, A^H W y, and optionally the iterate
-int ns_install(pnp_engine* e, const float2* x0, const float2* y, const float2* sens, int coils, int sens_n, const float* w, int cg_iters, float* x,
-               float2* z, float2* u, hipStream_t s) {
+// pnp_set_kspace_ncsense (no iterate) / pnp_reset_ncsense and, `toeplitz`, their _tz forms (w: the spectrum's weights, whatever is passed):
+// the episode constants of the stage - y, w, the maps, A^H W y - and optionally the iterate.  Every rejection happens before any HIP call
+int ns_install(const char* fn, pnp_engine* e, bool with_iterate, bool toeplitz, const float2* x0, const float2* y, const float2* sens, int coils,
+               int sens_n, const float* w, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
+    int rc;
+    if ((rc = ns_check_scalars(fn, coils, sens_n))) return rc;
+    if ((rc = nc_check_cg(fn, cg_iters))) return rc;
+    if (with_iterate && !x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if ((rc = ns_check(fn, e, coils, sens_n))) return rc;
+    if (toeplitz && (rc = tz_need_spectrum(fn, e))) return rc;
+    PNP_ON_DEVICE(e);
+    if (toeplitz) {
+        if ((rc = tz_ensure(e, (size_t)e->cfg.n * ns_block_of(e, coils), true))) return rc;
+        w = e->tz_has_w ? e->tz_w : nullptr;
+    }
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
     const size_t M = (size_t)e->nc.m, ym = (size_t)N * coils * M, sn = (size_t)sens_n * coils * H * W;
-    int rc;
     if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
     if ((rc = ns_ensure(e, coils))) return rc;
     if ((rc = ws_grow(e, "non-Cartesian SENSE constants",
@@ -1781,16 +1812,11 @@ int ns_install(pnp_engine* e, const float2* x0, const float2* y, const float2* s
     if (w) HIP_TRY(hipMemcpyAsync(e->ns_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
     if ((rc = ns_adjoint(e, e->ns_y, w ? e->ns_w : nullptr, e->ns_sens, sens_n, coils, N, mc_aty(e), s))) return rc;
-    if (x0) {
+    if (with_iterate) {
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
     }
-    // every launch was accepted: only now does the handle change mode (nc_install's rule)
-    e->ns_coils = coils; e->ns_sens_n = sens_n; e->ns_has_w = w != nullptr; e->ns_cg = cg_iters;
-    e->nc_on = false;
-    e->tz_on = false;
-    e->mc_coils = 0;
-    e->reset_done = true;
+    commit_stage(e, {STAGE_NS, toeplitz, coils, sens_n, cg_iters, w != nullptr});
     return PNP_OK;
 }
 
@@ -1835,56 +1861,30 @@ int pnp_nufft_adjoint_mc(pnp_handle e, const float* samples, const float* weight
 
 int pnp_set_kspace_ncsense(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, const float* w, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    const char* fn = "pnp_set_kspace_ncsense";
-    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
-    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
-    PNP_ON_DEVICE(e);
-    return ns_install(e, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, w, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return ns_install("pnp_set_kspace_ncsense", e, false, false, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, w, cg_iters, nullptr,
+                      nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_ncsense")
 }
 
 int pnp_reset_ncsense(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, const float* w, int cg_iters, float* x,
                       float* z, float* u, void* stream) {
     PNP_API_BEGIN
-    const char* fn = "pnp_reset_ncsense";
-    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
-    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
-    if (!x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
-    if (!x || !z || !u) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
-    PNP_ON_DEVICE(e);
-    return ns_install(e, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, w, cg_iters, x, (float2*)z, (float2*)u,
-                      (hipStream_t)stream);
+    return ns_install("pnp_reset_ncsense", e, true, false, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, w, cg_iters, x,
+                      (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_ncsense")
 }
 
-int pnp_ncsense_coils(pnp_handle e) { return e ? e->ns_coils : 0; }
+int pnp_ncsense_coils(pnp_handle e) { return e && e->stage.kind == STAGE_NS ? e->stage.coils : 0; }
 
 int pnp_ncsense_cg_residual(pnp_handle e, float* out, void* stream) {
     PNP_API_BEGIN
-    if (!e || !out) return fail(PNP_ERR_INVALID, "pnp_ncsense_cg_residual: null argument");
-    if (int rc = ns_need_mode("pnp_ncsense_cg_residual", e)) return rc;
-    PNP_ON_DEVICE(e);
-    Prof p(e, (hipStream_t)stream, PROF_OTHER, -1);
-    HIP_TRY(launch_sense_cgres(e->mc_sc, out, e->cfg.n, (hipStream_t)stream));
-    return PNP_OK;
+    return stage_cg_residual("pnp_ncsense_cg_residual", e, STAGE_NS, out, (hipStream_t)stream);
     PNP_API_END("pnp_ncsense_cg_residual")
 }
 
 int pnp_ncsense_normal(pnp_handle e, const float* pv, const float* mu, float* q, void* stream) {
     PNP_API_BEGIN
-    if (!e || !pv || !mu || !q) return fail(PNP_ERR_INVALID, "pnp_ncsense_normal: null argument");
-    if (pv == q) return fail(PNP_ERR_INVALID, "pnp_ncsense_normal: p and q must not alias");
-    if (int rc = ns_need_mode("pnp_ncsense_normal", e)) return rc;
-    PNP_ON_DEVICE(e);
-    return (e->tz_on ? tz_ns_normal : ns_normal)(e, (const float2*)pv, mu, nullptr, (float2*)q, (hipStream_t)stream);
+    return stage_normal_op("pnp_ncsense_normal", e, STAGE_NS, pv, mu, q, (hipStream_t)stream);
     PNP_API_END("pnp_ncsense_normal")
 }
 
@@ -1937,16 +1937,6 @@ int tz_check_sizes(const char* fn, const pnp_engine* e) {
     return fail(PNP_ERR_INVALID, "%s: the Toeplitz operator transforms a 2h x 2w grid, so it takes h, w up to %d (got %dx%d)", fn,
                 PNP_TOEPLITZ_MAX_SIDE, e->cfg.h, e->cfg.w);
 }
-int tz_need_spectrum(const char* fn, const pnp_engine* e) {
-    if (int rc = nc_need_plan(fn, e)) return rc;
-    return e->tz_planned ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no Toeplitz spectrum (pnp_toeplitz_plan)", fn);
-}
-// the pass buffer for `planes` planes and, with `coil_images`, the block's coil images
-int tz_ensure(pnp_engine* e, size_t planes, bool coil_images) {
-    const size_t hw = (size_t)e->cfg.h * e->cfg.w;
-    return ws_grow(e, "Toeplitz scratch", {{(void**)&e->tz_grid, &e->tz_grid_cap, planes * (e->tz_fused ? 2 : 4) * hw * sizeof(float2), false},
-                                          {(void**)&e->ns_img, &e->ns_img_cap, coil_images ? planes * hw * sizeof(float2) : 0, false}});
-}
 
 }  // namespace
 
@@ -1972,7 +1962,7 @@ int pnp_toeplitz_plan(pnp_handle e, const float* weights, int flags, void* strea
     if (e->tz_planned) (void)hipDeviceSynchronize();        // no launch still reads the spectrum being replaced
     // from here on the old spectrum is gone: a live Toeplitz stage's constants are dropped with it, as pnp_nufft_plan drops them
     e->tz_planned = false;
-    if (e->tz_on) { e->tz_on = false; e->nc_on = false; e->ns_coils = 0; e->reset_done = false; }
+    drop_stage(e, true);
     HIP_TRY(nc_upload(e->tz_traj, e->nc_traj.data(), M * 2 * sizeof(double)));
     HIP_TRY(nc_upload(e->tz_tw_h, twh.data(), twh.size() * sizeof(float2)));
     HIP_TRY(nc_upload(e->tz_tw_w, tww.data(), tww.size() * sizeof(float2)));
@@ -1989,7 +1979,7 @@ int pnp_toeplitz_plan(pnp_handle e, const float* weights, int flags, void* strea
 }
 
 int pnp_toeplitz_planned(pnp_handle e) { return e && e->tz_planned ? 1 : 0; }
-int pnp_toeplitz_live(pnp_handle e) { return e && e->tz_on ? 1 : 0; }
+int pnp_toeplitz_live(pnp_handle e) { return e && e->stage.toeplitz ? 1 : 0; }
 
 int pnp_toeplitz_spectrum(pnp_handle e, float* out, void* stream) {
     PNP_API_BEGIN
@@ -2040,77 +2030,29 @@ int pnp_toeplitz_apply_mc(pnp_handle e, const float* img, const float* sens, int
 
 int pnp_set_kspace_nc_tz(pnp_handle e, const float* y, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    const char* fn = "pnp_set_kspace_nc_tz";
-    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if (int rc = tz_need_spectrum(fn, e)) return rc;
-    PNP_ON_DEVICE(e);
-    if (int rc = nc_install(e, nullptr, (const float2*)y, e->tz_has_w ? e->tz_w : nullptr, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream))
-        return rc;
-    e->tz_on = true;
-    return PNP_OK;
+    return nc_install("pnp_set_kspace_nc_tz", e, false, true, nullptr, (const float2*)y, nullptr, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_nc_tz")
 }
 
 int pnp_reset_nc_tz(pnp_handle e, const float* x0, const float* y, int cg_iters, float* x, float* z, float* u, void* stream) {
     PNP_API_BEGIN
-    const char* fn = "pnp_reset_nc_tz";
-    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
-    if (!x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (!x || !z || !u) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if (int rc = tz_need_spectrum(fn, e)) return rc;
-    PNP_ON_DEVICE(e);
-    if (int rc = nc_install(e, (const float2*)x0, (const float2*)y, e->tz_has_w ? e->tz_w : nullptr, cg_iters, x, (float2*)z, (float2*)u,
-                            (hipStream_t)stream))
-        return rc;
-    e->tz_on = true;
-    return PNP_OK;
+    return nc_install("pnp_reset_nc_tz", e, true, true, (const float2*)x0, (const float2*)y, nullptr, cg_iters, x, (float2*)z, (float2*)u,
+                      (hipStream_t)stream);
     PNP_API_END("pnp_reset_nc_tz")
 }
 
 int pnp_set_kspace_ncsense_tz(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    const char* fn = "pnp_set_kspace_ncsense_tz";
-    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
-    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
-    if (int rc = tz_need_spectrum(fn, e)) return rc;
-    PNP_ON_DEVICE(e);
-    if (int rc = tz_ensure(e, (size_t)e->cfg.n * ns_block_of(e, coils), true)) return rc;
-    if (int rc = ns_install(e, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, e->tz_has_w ? e->tz_w : nullptr, cg_iters, nullptr,
-                            nullptr, nullptr, (hipStream_t)stream))
-        return rc;
-    e->tz_on = true;
-    return PNP_OK;
+    return ns_install("pnp_set_kspace_ncsense_tz", e, false, true, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, nullptr, cg_iters,
+                      nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_ncsense_tz")
 }
 
 int pnp_reset_ncsense_tz(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, int cg_iters, float* x, float* z,
                          float* u, void* stream) {
     PNP_API_BEGIN
-    const char* fn = "pnp_reset_ncsense_tz";
-    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
-    if (int rc = nc_check_cg(fn, cg_iters)) return rc;
-    if (!x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
-    if (!x || !z || !u) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
-    if (int rc = tz_need_spectrum(fn, e)) return rc;
-    PNP_ON_DEVICE(e);
-    if (int rc = tz_ensure(e, (size_t)e->cfg.n * ns_block_of(e, coils), true)) return rc;
-    if (int rc = ns_install(e, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, e->tz_has_w ? e->tz_w : nullptr, cg_iters, x,
-                            (float2*)z, (float2*)u, (hipStream_t)stream))
-        return rc;
-    e->tz_on = true;
-    return PNP_OK;
+    return ns_install("pnp_reset_ncsense_tz", e, true, true, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, nullptr, cg_iters,
+                      x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_ncsense_tz")
 }
 

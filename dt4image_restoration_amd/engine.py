@@ -79,6 +79,34 @@ class PnPEngine:
             raise ValueError(f"{name}: tensor must be contiguous")
         return t
 
+    def _iterate(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """fresh (x f32, z c64, u c64) [N,1,H,W] for a reset to fill"""
+        x = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device)
+        z = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+        return x, z, torch.empty_like(z)
+
+    def _mask(self, mask: torch.Tensor) -> Tuple[torch.Tensor, int]:
+        """mask bool/uint8 [H,W] or [N,H,W] -> (uint8 tensor, mask_n)"""
+        hw = self.h * self.w
+        m = mask.to(torch.uint8).contiguous()
+        if m.numel() not in (hw, self.n * hw):
+            raise ValueError(f"mask: expected {hw} or {self.n * hw} elements, got {tuple(mask.shape)}")
+        self._chk(m, torch.uint8, m.numel(), "mask")
+        return m, (1 if m.numel() == hw else self.n)
+
+    def _cg_residual(self, fn: str) -> torch.Tensor:
+        """float32 [N] from the live stage's pnp_*_cg_residual"""
+        out = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        _lib.check(getattr(self.lib, fn)(self._h, out.data_ptr(), self._stream()), fn)
+        return out
+
+    def _normal(self, fn: str, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+        """q = the live stage's pnp_*_normal of p complex64 [N,1,H,W] and mu float32 [N]"""
+        self._chk(p, torch.complex64, self.n * self.h * self.w, "p"); self._chk(mu, torch.float32, self.n, "mu")
+        q = torch.empty_like(p)
+        _lib.check(getattr(self.lib, fn)(self._h, p.data_ptr(), mu.data_ptr(), q.data_ptr(), self._stream()), fn)
+        return q
+
     @property
     def workspace_bytes(self) -> int:
         return int(self.lib.pnp_workspace_bytes(self._h))
@@ -106,17 +134,11 @@ class PnPEngine:
 
     def cg_residual(self) -> torch.Tensor:
         """float32 [N]: the relative residual the CG solve of the last step ended with (pnp_mc_cg_residual; multi-coil mode only)."""
-        out = torch.empty(self.n, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.pnp_mc_cg_residual(self._h, out.data_ptr(), self._stream()), "pnp_mc_cg_residual")
-        return out
+        return self._cg_residual("pnp_mc_cg_residual")
 
     def normal_op(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
         """q = A^H A p + mu p with the installed multi-coil constants (pnp_mc_normal); p complex64 [N,1,H,W], mu float32 [N]."""
-        nhw = self.n * self.h * self.w
-        self._chk(p, torch.complex64, nhw, "p"); self._chk(mu, torch.float32, self.n, "mu")
-        q = torch.empty_like(p)
-        _lib.check(self.lib.pnp_mc_normal(self._h, p.data_ptr(), mu.data_ptr(), q.data_ptr(), self._stream()), "pnp_mc_normal")
-        return q
+        return self._normal("pnp_mc_normal", p, mu)
 
     # -- non-Cartesian sampling ------------------------------------------------------------
     def nufft_plan(self, traj, grid: Optional[Tuple[int, int]] = None, width: int = 6) -> None:
@@ -204,9 +226,7 @@ class PnPEngine:
     def _reset_nc(self, x0, y, w, cg_iters, toeplitz):
         x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
         yp, wp = self._nc_args(y, w)
-        x = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device)
-        z = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
-        u = torch.empty_like(z)
+        x, z, u = self._iterate()
         if toeplitz:
             self._toeplitz_for(w)
             _lib.check(self.lib.pnp_reset_nc_tz(self._h, x0.data_ptr(), yp, int(cg_iters), x.data_ptr(), z.data_ptr(), u.data_ptr(),
@@ -322,16 +342,11 @@ class PnPEngine:
 
     def nc_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
         """q = A^H W A p + mu p with the installed non-Cartesian constants (pnp_nc_normal); p complex64 [N,1,H,W], mu float32 [N]."""
-        self._chk(p, torch.complex64, self.n * self.h * self.w, "p"); self._chk(mu, torch.float32, self.n, "mu")
-        q = torch.empty_like(p)
-        _lib.check(self.lib.pnp_nc_normal(self._h, p.data_ptr(), mu.data_ptr(), q.data_ptr(), self._stream()), "pnp_nc_normal")
-        return q
+        return self._normal("pnp_nc_normal", p, mu)
 
     def nc_cg_residual(self) -> torch.Tensor:
         """float32 [N]: the relative residual the CG solve of the last step ended with (pnp_nc_cg_residual; non-Cartesian mode only)."""
-        out = torch.empty(self.n, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.pnp_nc_cg_residual(self._h, out.data_ptr(), self._stream()), "pnp_nc_cg_residual")
-        return out
+        return self._cg_residual("pnp_nc_cg_residual")
 
     def acquire_nc(self, gt: torch.Tensor, sigma_n: float, seed: int,
                    dcf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -403,9 +418,7 @@ class PnPEngine:
     def _reset_ncsense(self, x0, y, sens, w, cg_iters, toeplitz):
         x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
         yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
-        x = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device)
-        z = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
-        u = torch.empty_like(z)
+        x, z, u = self._iterate()
         if toeplitz:
             self._toeplitz_for(w)
             _lib.check(self.lib.pnp_reset_ncsense_tz(self._h, x0.data_ptr(), yp, sp, coils, sens_n, int(cg_iters), x.data_ptr(), z.data_ptr(),
@@ -439,16 +452,11 @@ class PnPEngine:
 
     def ncsense_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
         """q = A^H W A p + mu p with the installed non-Cartesian SENSE constants (pnp_ncsense_normal); p complex64 [N,1,H,W], mu float32 [N]."""
-        self._chk(p, torch.complex64, self.n * self.h * self.w, "p"); self._chk(mu, torch.float32, self.n, "mu")
-        q = torch.empty_like(p)
-        _lib.check(self.lib.pnp_ncsense_normal(self._h, p.data_ptr(), mu.data_ptr(), q.data_ptr(), self._stream()), "pnp_ncsense_normal")
-        return q
+        return self._normal("pnp_ncsense_normal", p, mu)
 
     def ncsense_cg_residual(self) -> torch.Tensor:
         """float32 [N]: the relative residual the CG solve of the last step ended with (pnp_ncsense_cg_residual; that mode only)."""
-        out = torch.empty(self.n, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.pnp_ncsense_cg_residual(self._h, out.data_ptr(), self._stream()), "pnp_ncsense_cg_residual")
-        return out
+        return self._cg_residual("pnp_ncsense_cg_residual")
 
     def acquire_ncsense(self, gt: torch.Tensor, sens: torch.Tensor, sigma_n: float, seed: int,
                         dcf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -478,31 +486,16 @@ class PnPEngine:
         if sens is not None:
             sens, coils, sens_n = self._sens(sens)
             y0 = self._chk(y0, torch.complex64, nhw * coils, "y0")
-            m = mask.to(torch.uint8).contiguous()
-            if m.numel() not in (self.h * self.w, nhw):
-                raise ValueError(f"mask: expected {self.h * self.w} or {nhw} elements, got {tuple(mask.shape)}")
-            x = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device)
-            z = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
-            u = torch.empty_like(z)
-            _lib.check(self.lib.pnp_reset_mc(self._h, x0.data_ptr(), y0.data_ptr(), sens.data_ptr(), coils, sens_n, m.data_ptr(),
-                                             1 if m.numel() == self.h * self.w else self.n, int(cg_iters), x.data_ptr(), z.data_ptr(),
-                                             u.data_ptr(), self._stream()), "pnp_reset_mc")
-            self.live_episode = _next_episode()
-            return x, z, u
-        y0 = self._chk(y0, torch.complex64, nhw, "y0")
-        m = mask.to(torch.uint8).contiguous()
-        if m.numel() == self.h * self.w:
-            mask_n = 1
-        elif m.numel() == nhw:
-            mask_n = self.n
+            m, mask_n = self._mask(mask)
+            x, z, u = self._iterate()
+            _lib.check(self.lib.pnp_reset_mc(self._h, x0.data_ptr(), y0.data_ptr(), sens.data_ptr(), coils, sens_n, m.data_ptr(), mask_n,
+                                             int(cg_iters), x.data_ptr(), z.data_ptr(), u.data_ptr(), self._stream()), "pnp_reset_mc")
         else:
-            raise ValueError(f"mask: expected {self.h * self.w} or {nhw} elements, got {tuple(mask.shape)}")
-        self._chk(m, torch.uint8, m.numel(), "mask")
-        x = torch.empty((self.n, 1, self.h, self.w), dtype=torch.float32, device=self.device)
-        z = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
-        u = torch.empty_like(z)
-        _lib.check(self.lib.pnp_reset(self._h, x0.data_ptr(), y0.data_ptr(), m.data_ptr(), mask_n, x.data_ptr(),
-                                      z.data_ptr(), u.data_ptr(), self._stream()), "pnp_reset")
+            y0 = self._chk(y0, torch.complex64, nhw, "y0")
+            m, mask_n = self._mask(mask)
+            x, z, u = self._iterate()
+            _lib.check(self.lib.pnp_reset(self._h, x0.data_ptr(), y0.data_ptr(), m.data_ptr(), mask_n, x.data_ptr(),
+                                          z.data_ptr(), u.data_ptr(), self._stream()), "pnp_reset")
         self.live_episode = _next_episode()
         return x, z, u
 
@@ -512,21 +505,15 @@ class PnPEngine:
         (pnp_set_kspace); `episode` = the id that episode's reset returned (0: a fresh id).  With sens: a multi-coil episode's
         constants (pnp_set_kspace_mc), as in `reset`."""
         nhw = self.n * self.h * self.w
-        m = mask.to(torch.uint8).contiguous()
-        if m.numel() not in (self.h * self.w, nhw):
-            raise ValueError(f"mask: expected {self.h * self.w} or {nhw} elements, got {tuple(mask.shape)}")
-        self._chk(m, torch.uint8, m.numel(), "mask")
+        m, mask_n = self._mask(mask)
         if sens is not None:
             sens, coils, sens_n = self._sens(sens)
             y0 = self._chk(y0, torch.complex64, nhw * coils, "y0")
-            _lib.check(self.lib.pnp_set_kspace_mc(self._h, y0.data_ptr(), sens.data_ptr(), coils, sens_n, m.data_ptr(),
-                                                  1 if m.numel() == self.h * self.w else self.n, int(cg_iters), self._stream()),
-                       "pnp_set_kspace_mc")
-            self.live_episode = episode or _next_episode()
-            return
-        y0 = self._chk(y0, torch.complex64, nhw, "y0")
-        _lib.check(self.lib.pnp_set_kspace(self._h, y0.data_ptr(), m.data_ptr(), 1 if m.numel() == self.h * self.w else self.n,
-                                           self._stream()), "pnp_set_kspace")
+            _lib.check(self.lib.pnp_set_kspace_mc(self._h, y0.data_ptr(), sens.data_ptr(), coils, sens_n, m.data_ptr(), mask_n,
+                                                  int(cg_iters), self._stream()), "pnp_set_kspace_mc")
+        else:
+            y0 = self._chk(y0, torch.complex64, nhw, "y0")
+            _lib.check(self.lib.pnp_set_kspace(self._h, y0.data_ptr(), m.data_ptr(), mask_n, self._stream()), "pnp_set_kspace")
         self.live_episode = episode or _next_episode()
 
     def step(self, x: torch.Tensor, z: torch.Tensor, u: torch.Tensor, mu: torch.Tensor, sigma_d: torch.Tensor,
@@ -682,10 +669,7 @@ class PnPEngine:
         `synthetic.make_problem` draws for seed + n."""
         nhw = self.n * self.h * self.w
         gt = self._chk(gt, torch.float32, nhw, "gt")
-        m = mask.to(torch.uint8).contiguous()
-        if m.numel() not in (self.h * self.w, nhw):
-            raise ValueError(f"mask: expected {self.h * self.w} or {nhw} elements, got {tuple(mask.shape)}")
-        self._chk(m, torch.uint8, m.numel(), "mask")
+        m, mask_n = self._mask(mask)
         seed = int(seed)
         if not 0 <= seed < 2 ** 64 - self.n:
             raise ValueError(f"seed: expected 0 <= seed < 2**64 - n, got {seed}")
@@ -694,15 +678,13 @@ class PnPEngine:
             y0 = torch.empty((self.n, coils, self.h, self.w), dtype=torch.complex64, device=self.device)
             aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
             x0 = torch.empty_like(aty0)
-            _lib.check(self.lib.pnp_acquire_mc(self._h, gt.data_ptr(), sens.data_ptr(), coils, sens_n, m.data_ptr(),
-                                               1 if m.numel() == self.h * self.w else self.n, float(sigma_n), seed, 0, y0.data_ptr(),
-                                               aty0.data_ptr(), x0.data_ptr(), self._stream()), "pnp_acquire_mc")
+            _lib.check(self.lib.pnp_acquire_mc(self._h, gt.data_ptr(), sens.data_ptr(), coils, sens_n, m.data_ptr(), mask_n, float(sigma_n),
+                                               seed, 0, y0.data_ptr(), aty0.data_ptr(), x0.data_ptr(), self._stream()), "pnp_acquire_mc")
             return y0, aty0, x0
         y0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
         aty0, x0 = torch.empty_like(y0), torch.empty_like(y0)
-        _lib.check(self.lib.pnp_acquire(self._h, gt.data_ptr(), m.data_ptr(), 1 if m.numel() == self.h * self.w else self.n,
-                                        float(sigma_n), seed, 0, y0.data_ptr(), aty0.data_ptr(), x0.data_ptr(), self._stream()),
-                   "pnp_acquire")
+        _lib.check(self.lib.pnp_acquire(self._h, gt.data_ptr(), m.data_ptr(), mask_n, float(sigma_n), seed, 0, y0.data_ptr(), aty0.data_ptr(),
+                                        x0.data_ptr(), self._stream()), "pnp_acquire")
         return y0, aty0, x0
 
     def estimate_sens(self, y0: torch.Tensor, acs: Tuple[int, int], window: str = "hann", thresh: float = 0.0, return_rss: bool = False):
@@ -897,17 +879,14 @@ class PnPEngine:
             raise ValueError(f"wts: expected [{nt},{ns}] or [{self.n},{nt},{ns}], got {tuple(wts.shape)}")
         wts_n = 1 if wts.numel() == nt * ns else self.n
         wts = self._chk(wts, torch.complex64, wts_n * nt * ns, "wts")
-        m = mask.to(torch.uint8).contiguous()
-        if m.numel() not in (self.h * self.w, self.n * self.h * self.w):
-            raise ValueError(f"mask: expected {self.h * self.w} or {self.n * self.h * self.w} elements, got {tuple(mask.shape)}")
-        self._chk(m, torch.uint8, m.numel(), "mask")
+        m, mask_n = self._mask(mask)
         if out is None:
             out = torch.empty_like(y0)
         elif tuple(out.shape) != tuple(y0.shape):
             raise ValueError(f"out: expected {tuple(y0.shape)}, got {tuple(out.shape)}")
         out = self._chk(out, torch.complex64, y0.numel(), "out")
-        _lib.check(self.lib.pnp_grappa_apply(self._h, y0.data_ptr(), coils, m.data_ptr(), 1 if m.numel() == self.h * self.w else self.n, accel,
-                                             offset, by, bx, wts.data_ptr(), wts_n, out.data_ptr(), self._stream()), "pnp_grappa_apply")
+        _lib.check(self.lib.pnp_grappa_apply(self._h, y0.data_ptr(), coils, m.data_ptr(), mask_n, accel, offset, by, bx, wts.data_ptr(), wts_n,
+                                             out.data_ptr(), self._stream()), "pnp_grappa_apply")
         return out
 
     def snapshot(self, x: torch.Tensor, z: torch.Tensor, u: torch.Tensor, t_state: Optional[torch.Tensor] = None,
