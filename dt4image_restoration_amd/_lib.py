@@ -150,6 +150,21 @@ SIGNATURES_DCF = {
 }
 PNP_DCF_MAX_ITERS = 256
 
+# name -> (restype, argtypes); every symbol include/pnpadmm_offres.h declares (off-resonance correction by time segmentation)
+SIGNATURES_OFFRES = {
+    "pnp_offres_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "pnp_offres_segments": (C.c_int, [C.c_void_p]),
+    "pnp_offres_maps": (C.c_int, [C.c_void_p, _fp, C.c_int, _fp, _vp]),
+    "pnp_offres_forward": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_offres_adjoint": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_set_kspace_offres": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, C.c_int, _vp]),
+    "pnp_reset_offres": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _vp]),
+    "pnp_offres_live": (C.c_int, [C.c_void_p]),
+    "pnp_offres_cg_residual": (C.c_int, [C.c_void_p, _fp, _vp]),
+    "pnp_offres_normal": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),
+    "pnp_acquire_offres": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, C.c_double, C.c_uint64, C.c_int, _fp, _fp, _fp, _vp]),
+}
+
 
 def toeplitz_size_error(fn: str, h: int, w: int):
     """The library's refusal of a slice too large for the Toeplitz operator, word for word (pnp_capi.hip: tz_check_sizes), or None: for a
@@ -174,7 +189,7 @@ def load() -> C.CDLL:
         raise PnPError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        f"or `make -C {os.path.dirname(LIB_PATH)}`; there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE, **SIGNATURES_TOEPLITZ, **SIGNATURES_DCF}.items():
+    for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE, **SIGNATURES_TOEPLITZ, **SIGNATURES_DCF, **SIGNATURES_OFFRES}.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

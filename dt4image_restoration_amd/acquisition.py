@@ -203,6 +203,48 @@ def rosette_trajectory(h: int, w: int, petals: int, readout: int = None) -> np.n
     return np.stack([r * np.sin(a), r * np.cos(a)], axis=1)
 
 
+def readout_times(traj_kind: str, m: int, readout: int, t_read: float, te: float = 0.0) -> np.ndarray:
+    """float64 [m] seconds: the time of every sample of a `radial_trajectory`, `spiral_trajectory` or `rosette_trajectory` of m samples.  The
+    generators emit `readout` samples per spoke / interleaf / petal (a rosette is one shot: readout = m), in order; sample i of each is taken
+    at te + i t_read / readout.  traj_kind: "radial", "spiral" or "rosette"."""
+    m, readout = int(m), int(readout)
+    if traj_kind not in ("radial", "spiral", "rosette"):
+        raise ValueError(f"readout_times: traj_kind must be radial, spiral or rosette, got {traj_kind!r}")
+    if readout < 1 or m < 1 or m % readout:
+        raise ValueError(f"readout_times: m = {m} is not a whole number of readouts of {readout} samples")
+    if not (math.isfinite(t_read) and t_read > 0.0 and math.isfinite(te)):
+        raise ValueError(f"readout_times: need t_read > 0 and a finite te, got {t_read}, {te}")
+    return np.tile(float(te) + np.arange(readout, dtype=np.float64) * float(t_read) / readout, m // readout)
+
+
+def offres_segments(omega_max: float, span: float, tol: float = 1e-3) -> int:
+    """The smallest number of time segments L whose linear interpolator keeps the model error of include/pnpadmm_offres.h,
+    1 - cos(omega_max D / 2) with D = span / (L - 1), within tol: omega_max in rad/s, span = t_max - t_min in seconds.  1 where there is
+    nothing to correct (omega_max span = 0).  The answer is arithmetic and may exceed what pnp_offres_plan takes (`OFFRES_MAX_SEGMENTS`): the
+    linear interpolator needs about 11 segments per radian of omega_max span at tol = 1e-3; `offres_bound` gives the error of a given L."""
+    omega_max, span = abs(float(omega_max)), float(span)
+    if not (math.isfinite(omega_max) and math.isfinite(span) and span >= 0.0 and 0.0 < tol < 1.0):
+        raise ValueError(f"offres_segments: need finite omega_max, span >= 0 and 0 < tol < 1, got {omega_max}, {span}, {tol}")
+    if omega_max * span == 0.0:
+        return 1
+    L = max(2, int(omega_max * span / (2.0 * math.acos(1.0 - tol))))              # from just below the closed form, then exactly
+    while not (omega_max * span / (L - 1) / 2.0 <= math.pi and 1.0 - math.cos(omega_max * span / (L - 1) / 2.0) <= tol):
+        L += 1
+    while L > 2 and omega_max * span / (L - 2) / 2.0 <= math.pi and 1.0 - math.cos(omega_max * span / (L - 2) / 2.0) <= tol:
+        L -= 1
+    return L
+
+
+OFFRES_MAX_SEGMENTS = _lib.PNP_MC_MAX_COILS                  # segments pnp_offres_plan takes
+
+
+def offres_bound(omega_max: float, span: float, segments: int) -> float:
+    """The model error 1 - cos(omega_max D / 2), D = span / (segments - 1), of `segments` >= 2 time segments (per unit of ||p||_1)."""
+    if int(segments) < 2:
+        raise ValueError(f"offres_bound: need segments >= 2, got {segments}")
+    return 1.0 - math.cos(min(abs(float(omega_max)) * float(span) / (int(segments) - 1) / 2.0, math.pi))
+
+
 def pipe_dcf(engine_or_env, traj, iters: int = 30, width: int = 6, grid=None) -> torch.Tensor:
     """float32 [M] on the engine's device: density weights of ANY trajectory by Pipe and Menon's iteration w <- w / (Psi w) on the
     engine's own gridding kernel (pnp_nufft_dcf, include/pnpadmm_dcf.h), `iters` iterations from ones, scaled to sum h w as `radial_dcf`.
@@ -217,11 +259,28 @@ def pipe_dcf(engine_or_env, traj, iters: int = 30, width: int = 6, grid=None) ->
     return eng.nufft_dcf(iters=iters)
 
 
-def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, width: int, grid, sens=None) -> Dict[str, torch.Tensor]:
+def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, width: int, grid, sens=None, omega=None, times=None,
+                 segments=None) -> Dict[str, torch.Tensor]:
     t = np.ascontiguousarray(traj.detach().cpu().numpy() if isinstance(traj, torch.Tensor) else traj, dtype=np.float64)
     eng.nufft_plan(t, grid=grid, width=width)
     d = None if dcf is None else torch.as_tensor(dcf).to(eng.device, torch.float32).contiguous()
-    if sens is not None:                                     # non-Cartesian SENSE: y [N,C,M]
+    om = None
+    if omega is not None:                                    # under a field map: the time-segmented acquisition, y [N,1,M]
+        tm = np.ascontiguousarray(times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else times, dtype=np.float64).reshape(-1)
+        om = torch.as_tensor(omega).to(eng.device, torch.float32).contiguous()
+        L = segments
+        if L is None or L == "auto":
+            om_max, span = float(om.abs().max()), float(tm.max() - tm.min())
+            L = offres_segments(om_max, span)
+            if L > OFFRES_MAX_SEGMENTS:                      # the library's most: a larger model error, said aloud
+                import warnings
+                warnings.warn(f"simulate: tol = 1e-3 needs {L} time segments for omega_max span = {om_max * span:.3g} rad; using "
+                              f"{OFFRES_MAX_SEGMENTS} (model error {offres_bound(om_max, span, OFFRES_MAX_SEGMENTS):.2e} ||p||_1)")
+                L = OFFRES_MAX_SEGMENTS
+        eng.offres_plan(tm, int(L))
+        y, aty0, x0 = eng.acquire_offres(g, om, float(sigma_n), seed, dcf=d)
+        y = y.reshape(eng.n, 1, -1)
+    elif sens is not None:                                     # non-Cartesian SENSE: y [N,C,M]
         sens = torch.as_tensor(sens).to(eng.device, torch.complex64).contiguous()
         y, aty0, x0 = eng.acquire_ncsense(g, sens, float(sigma_n), seed, dcf=d)
     else:
@@ -233,11 +292,13 @@ def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, wid
         out["dcf"] = d
     if sens is not None:
         out["sens"] = sens
+    if om is not None:
+        out["omega"], out["times"], out["segments"] = om, torch.from_numpy(tm), int(L)
     return out
 
 
 def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: int = 0, sens=None, noise_cov=None, traj=None, dcf=None,
-             nufft_width: int = 6, nufft_grid=None) -> Dict[str, torch.Tensor]:
+             nufft_width: int = 6, nufft_grid=None, omega=None, times=None, segments="auto") -> Dict[str, torch.Tensor]:
     """The collated `.mat` dict `PnPEnv.reset` reads, acquired on the device: x0, y0, ATy0 float32 [N,1,H,W,2] (real views of the
     complex outputs), mask bool [H,W] (or [N,H,W]), gt float32 [N,1,H,W], x0_raw = Re ATy0 [N,1,H,W]; every tensor on the GPU.
     gt: [N,H,W] or [N,1,H,W] in [0, 1] (array or tensor), mask: [H,W] or [N,H,W] in the centred layout.  Slice i draws the noise of
@@ -251,7 +312,11 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
     traj (float64 [M,2], e.g. `radial_trajectory`; mask is then ignored and may be None): the non-Cartesian acquisition (pnp_nufft_plan +
     pnp_acquire_nc): y0 is [N,1,M,2], ATy0 = A^H (dcf y) with dcf float32 [M] or None, and the dict carries `traj` and `dcf`
     (when given) in place of `mask`.  traj with sens: the non-Cartesian SENSE acquisition (pnp_acquire_ncsense): y0 is [N,C,M,2],
-    ATy0 = sum_c conj(S_c) F_nu^H (dcf y_c), and the dict carries `sens` too; traj with noise_cov is refused."""
+    ATy0 = sum_c conj(S_c) F_nu^H (dcf y_c), and the dict carries `sens` too; traj with noise_cov is refused.
+    traj with omega (field map in rad/s, float32 [H,W] or [N,H,W]) and times (seconds, [M], e.g. `readout_times`): the acquisition under
+    main-field inhomogeneity by the time-segmented operator (pnp_offres_plan + pnp_acquire_offres, include/pnpadmm_offres.h) with
+    `segments` segments ("auto": `offres_segments` of max |omega| and the span of the times); single-coil only.  The dict carries `omega`,
+    `times` and `segments` beside `traj`."""
     if not torch.cuda.is_available():
         raise RuntimeError("simulate needs a ROCm GPU; the CPU route is synthetic.make_problem")
     g = torch.as_tensor(gt)
@@ -268,7 +333,14 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
     if traj is not None:
         if noise_cov is not None:
             raise ValueError("simulate: a non-Cartesian acquisition draws white noise (traj with noise_cov is not supported)")
-        return _simulate_nc(eng, g, traj, dcf, sigma_n, int(seed) + int(first_slice), nufft_width, nufft_grid, sens=sens)
+        if (omega is None) != (times is None):
+            raise ValueError("simulate: omega and times go together")
+        if omega is not None and sens is not None:
+            raise ValueError("simulate: the off-resonance acquisition is single-coil (omega with sens is not supported)")
+        return _simulate_nc(eng, g, traj, dcf, sigma_n, int(seed) + int(first_slice), nufft_width, nufft_grid, sens=sens, omega=omega,
+                            times=times, segments=segments)
+    if omega is not None or times is not None:
+        raise ValueError("simulate: omega and times need traj (a non-Cartesian acquisition)")
     m = torch.as_tensor(mask)
     if m.numel() == h * w:
         m = m.reshape(h, w)
@@ -625,6 +697,7 @@ def make_mask(h: int, w: int, accel: float, kind: str = "radial", seed: int = 0)
 
 def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int = 0, mask_kind: str = "radial",
                  mask=None, coils: int = 0, noise_cov=None, spokes: int = None, nc_weights: str = "dcf", nufft_width: int = 6,
+                 b0_hz: float = None, readout_ms: float = None, b0_segments="auto",
                  nufft_grid=None, interleaves: int = None, petals: int = None, dcf_iters: int = 30) -> Dict[str, torch.Tensor]:
     """`simulate` for a named task: '4x_10' = acceleration 4, sigma_n = 10 / 255.  mask: a ready mask, or None for
     `make_mask(h, w, accel, mask_kind, seed)` (the same for every shard of a job).  coils > 0: a multi-coil acquisition with the
@@ -634,7 +707,11 @@ def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int =
     about the samples of the radial acquisition); "rosette-nc": `rosette_trajectory` of `petals` petals (None: an odd count near
     h / accel).  nc_weights: "none"; "pipe", the iterated density weights `pipe_dcf` (`dcf_iters` iterations); "dcf", the weights written
     for the trajectory: the ramp `radial_dcf` on "radial-nc" and `pipe_dcf` on the other two (the ramp is never applied to a trajectory
-    it was not written for).  With coils > 0 the non-Cartesian SENSE acquisition with the maps `synthetic.coil_maps(coils, h, w)`."""
+    it was not written for).  With coils > 0 the non-Cartesian SENSE acquisition with the maps `synthetic.coil_maps(coils, h, w)`.
+    b0_hz (with a non-Cartesian mask_kind, single-coil): the acquisition under main-field inhomogeneity - the smooth map
+    `synthetic.field_map(h, w, b0_hz, seed)` shared by the slices, every readout (spoke, interleaf, shot) `readout_ms` long
+    (`readout_times`), by the time-segmented operator with `b0_segments` segments ("auto": `simulate`'s rule); the dict then carries
+    `omega`, `times` and `segments`, and `PnPEnv.reset` installs the off-resonance stage."""
     accel, sigma_n = parse_task(task)
     h, w = (int(v) for v in torch.as_tensor(gt).shape[-2:])
     if mask_kind in NC_KINDS:
@@ -658,8 +735,27 @@ def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int =
             eng = engine_or_env if hasattr(engine_or_env, "acquire") else None
             device = eng.device if eng is not None else torch.device("cuda", torch.cuda.current_device())
             dcf = pipe_dcf(_engine(engine_or_env, g.numel() // (h * w), h, w, device), traj, iters=dcf_iters, width=nufft_width, grid=nufft_grid)
-        return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, sens=sens, traj=traj, dcf=dcf, nufft_width=nufft_width,
-                        nufft_grid=nufft_grid)
+        if b0_hz is None:
+            return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, sens=sens, traj=traj, dcf=dcf, nufft_width=nufft_width,
+                            nufft_grid=nufft_grid)
+        # under main-field inhomogeneity: one smooth field map of at most b0_hz shared by the slices, every readout readout_ms long
+        if coils:
+            raise ValueError("task_problem: the off-resonance acquisition is single-coil (b0_hz with coils is not supported)")
+        if readout_ms is None or not (math.isfinite(readout_ms) and readout_ms > 0.0 and math.isfinite(b0_hz) and b0_hz >= 0.0):
+            raise ValueError(f"task_problem: b0_hz needs b0_hz >= 0 and readout_ms > 0, got {b0_hz}, {readout_ms}")
+        m = traj.shape[0]
+        if mask_kind == "radial-nc":                         # samples per spoke / interleaf / shot, as the generators emit them
+            readout = 2 * max(h, w)
+        elif mask_kind == "spiral-nc":
+            readout = m // (int(math.ceil(h / (2.0 * accel))) if interleaves is None else int(interleaves))
+        else:
+            readout = m
+        times = readout_times(mask_kind[:-3], m, readout, float(readout_ms) * 1e-3)
+        omega = (2.0 * math.pi * synthetic.field_map(h, w, float(b0_hz), seed)).astype(np.float32)
+        return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, traj=traj, dcf=dcf, nufft_width=nufft_width, nufft_grid=nufft_grid,
+                        omega=omega, times=times, segments=b0_segments)
+    if b0_hz is not None or readout_ms is not None:
+        raise ValueError("task_problem: b0_hz and readout_ms need a non-Cartesian mask_kind (radial-nc, spiral-nc, rosette-nc)")
     if mask is None:
         mask = make_mask(h, w, accel, mask_kind, seed)
     sens = synthetic.coil_maps(coils, h, w).astype(np.complex64) if coils else None

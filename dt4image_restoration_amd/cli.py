@@ -214,8 +214,11 @@ def _grappa_start(env, batch, filled):
 
 def _nc_kwargs(args):
     """--traj radial: what `acquisition.task_problem` needs for the non-Cartesian acquisition of a task."""
-    return dict(mask_kind=f"{args.traj}-nc", spokes=args.spokes, nc_weights=args.nc_weights, nufft_width=args.nufft_width,
-                nufft_grid=args.nufft_grid, coils=args.nc_coils, interleaves=args.interleaves, petals=args.petals, dcf_iters=args.dcf_iters)
+    kw = dict(mask_kind=f"{args.traj}-nc", spokes=args.spokes, nc_weights=args.nc_weights, nufft_width=args.nufft_width,
+              nufft_grid=args.nufft_grid, coils=args.nc_coils, interleaves=args.interleaves, petals=args.petals, dcf_iters=args.dcf_iters)
+    if args.b0 is not None:                                  # --b0: the acquisition under a field map and the off-resonance stage
+        kw.update(b0_hz=args.b0, readout_ms=args.readout_ms, b0_segments=args.b0_segments)
+    return kw
 
 
 def _sets(args, flex_target=None, env=None):
@@ -390,6 +393,12 @@ def main(argv=None):
     ap.add_argument("--nc-weights", choices=("none", "dcf", "pipe"), default="dcf", help="--traj: sample weights of the data term and of ATy0: "
                     "none; pipe, the density weights iterated on the device for any trajectory; dcf, the analytic ramp on radial spokes and "
                     "the iterated weights on a spiral or a rosette")
+    ap.add_argument("--b0", type=float, default=None, metavar="HZ", help="--traj: acquire under a smooth main-field inhomogeneity map of at most "
+                    "HZ hertz and reconstruct with the time-segmented off-resonance stage (eval / flex / mcts / fixed; single-coil, NUFFT normal "
+                    "operator); needs --readout-ms")
+    ap.add_argument("--readout-ms", type=float, default=None, metavar="T", help="--b0: the length of every readout (spoke, interleaf, shot) in ms")
+    ap.add_argument("--b0-segments", default="auto", metavar="L|auto", help="--b0: time segments, 1..32, or auto: the smallest count whose "
+                    "interpolation error stays within 1e-3, at most 32")
     ap.add_argument("--sens", choices=("true", "estimate", "espirit"), default="true", help="coil maps of a --coils run: the analytic maps that "
                     "generated the measurements, or maps estimated on the device from the calibration block of each set's own y0 (estimate: "
                     "the low-resolution estimate; espirit: ESPIRiT, at most 16 coils)")
@@ -470,6 +479,23 @@ def main(argv=None):
             raise SystemExit(f"--dcf-iters must be 1..256, got {args.dcf_iters}")
         if args.grappa or args.mask != "radial":
             raise SystemExit("--traj takes no --mask / --grappa: its samples are a trajectory, not a mask")
+        if args.b0 is not None:
+            if args.readout_ms is None or not (np.isfinite(args.readout_ms) and args.readout_ms > 0.0):
+                raise SystemExit(f"--b0 needs --readout-ms T with T > 0, got {args.readout_ms}")
+            if not (np.isfinite(args.b0) and args.b0 >= 0.0):
+                raise SystemExit(f"--b0 must be finite and >= 0, got {args.b0}")
+            if args.nc_coils:
+                raise SystemExit("--b0 with --nc-coils: the off-resonance stage is single-coil")
+            if args.nc_normal == "toeplitz":
+                raise SystemExit("--b0 with --nc-normal toeplitz: the off-resonance stage has no Toeplitz form")
+            if args.mode == "acquire":
+                raise SystemExit("--b0 is for eval / flex / mcts / fixed")
+            if args.b0_segments != "auto":
+                if not str(args.b0_segments).isdigit() or not 1 <= int(args.b0_segments) <= 32:
+                    raise SystemExit(f"--b0-segments must be 1..32 or auto, got {args.b0_segments}")
+                args.b0_segments = int(args.b0_segments)
+        elif args.readout_ms is not None or args.b0_segments != "auto":
+            raise SystemExit("--readout-ms / --b0-segments need --b0")
         if args.nc_normal == "toeplitz" and args.mode == "acquire":
             raise SystemExit("acquire runs no CG: drop --nc-normal toeplitz")
         if args.nc_normal == "toeplitz" and not getattr(args, "gt", None):      # the synthetic sets: the size is known here
@@ -489,6 +515,8 @@ def main(argv=None):
         raise SystemExit("--petals needs --traj rosette")
     elif args.dcf_iters != 30:
         raise SystemExit("--dcf-iters needs --traj")
+    elif args.b0 is not None or args.readout_ms is not None or args.b0_segments != "auto":
+        raise SystemExit("--b0 / --readout-ms / --b0-segments need --traj")
     if args.prior == "tv":
         if not (args.tv_scale >= 0.0 and np.isfinite(args.tv_scale)):
             raise SystemExit(f"--tv-scale must be finite and >= 0, got {args.tv_scale}")

@@ -797,6 +797,9 @@ Tuning tuning_from_env() {
     if (const char* v = getenv("PNP_NCSENSE_COIL_BLOCK")) t.ncsense_block = atoi(v);
     if (const char* v = getenv("PNP_NCSENSE_NAIVE")) t.ncsense_naive = atoi(v) != 0 ? 1 : 0;
     if (const char* v = getenv("PNP_TOEPLITZ_NAIVE")) t.toeplitz_naive = atoi(v) != 0;
+    if (const char* v = getenv("PNP_OFFRES_SEG_BLOCK")) t.offres_block = atoi(v);
+    if (const char* v = getenv("PNP_OFFRES_GRID_FILTER")) t.offres_grid_filter = atoi(v) != 0;
+    if (const char* v = getenv("PNP_OFFRES_NAIVE")) t.offres_naive = atoi(v) != 0 ? 1 : 0;
     return t;
 }
 

@@ -4,9 +4,11 @@
 #include "../../include/pnpadmm_ncsense.h"
 #include "../../include/pnpadmm_toeplitz.h"
 #include "../../include/pnpadmm_dcf.h"
+#include "../../include/pnpadmm_offres.h"
 #include "pnp_internal.h"
 #include "denoiser_plan.h"
 #include "nufft_plan.h"
+#include "offres_plan.h"
 #include "block_reduce.h"
 
 #include <cmath>
@@ -78,16 +80,17 @@ struct EventPair {
 
 // The handle's live data-fidelity stage: the constants installed LAST, which pnp_step / pnp_prox_dual solve with and PNP_RES_DC measures
 // against.  STAGE_NONE: nothing installed yet, or dropped with the plan it was built on; STAGE_CART: the closed form (pnp_reset /
-// pnp_set_kspace); STAGE_MC: SENSE; STAGE_NC: non-Cartesian; STAGE_NS: non-Cartesian SENSE.  The three last run a CG on stage_normal().
+// pnp_set_kspace); STAGE_MC: SENSE; STAGE_NC: non-Cartesian; STAGE_NS: non-Cartesian SENSE; STAGE_OR: non-Cartesian with the
+// time-segmented off-resonance operator (include/pnpadmm_offres.h).  The four last run a CG on stage_normal().
 // Written by commit_stage and drop_stage only.
-enum StageKind { STAGE_NONE, STAGE_CART, STAGE_MC, STAGE_NC, STAGE_NS };
+enum StageKind { STAGE_NONE, STAGE_CART, STAGE_MC, STAGE_NC, STAGE_NS, STAGE_OR };
 struct LiveStage {
     StageKind kind = STAGE_NONE;
     bool toeplitz = false;       // STAGE_NC, STAGE_NS: a _tz installer, the CG runs on the Toeplitz operator
     int coils = 0;               // STAGE_MC, STAGE_NS: coils of the installed constants
-    int sens_n = 1;
+    int sens_n = 1;              // STAGE_OR: map_n of the installed field map
     int cg = 0;                  // CG iterations per step
-    bool has_w = false;          // STAGE_NC, STAGE_NS: weights were installed (nc_w / ns_w; else they are 1)
+    bool has_w = false;          // STAGE_NC, STAGE_NS, STAGE_OR: weights were installed (nc_w / ns_w / or_w; else they are 1)
 };
 
 }  // namespace
@@ -158,6 +161,19 @@ struct pnp_engine {
     float* ns_w = nullptr;       // [M] the installed weights (read only through stage_w)
     double* ns_mpart = nullptr;  // [N, C, nufft_sample_chunks(M)] partial sums of the misfit
     size_t ns_grid_cap = 0, ns_samp_cap = 0, ns_y_cap = 0, ns_sens_cap = 0, ns_w_cap = 0, ns_mpart_cap = 0;
+    // off-resonance correction (include/pnpadmm_offres.h): the plan by pnp_offres_plan, the constants by its installers; the segment-block
+    // scratch is the coil-block scratch above
+    std::vector<int32_t> nc_bin_off_h, nc_bin_idx_h;   // host copy of the NUFFT plan's tile bins: what the per-segment lists are built from
+    OffresDev orp;               // the uploaded plan; orp.segments == 0: none
+    size_t or_tau_cap = 0, or_seg_cap = 0, or_b0_cap = 0, or_b1_cap = 0, or_loff_cap = 0, or_lidx_cap = 0;
+    int or_block = kOffresBlock; // segments per block: kOffresBlock, or PNP_OFFRES_SEG_BLOCK (read at pnp_create)
+    int or_naive = kOffresNaiveSteps;   // OffresStep bits: the steps that run as the naive launches (PNP_OFFRES_NAIVE: all or none)
+    float2* or_maps = nullptr;   // [map_n, L, H, W] the installed segment maps
+    float2* or_y = nullptr;      // [N, M] the installed samples
+    float* or_w = nullptr;       // [M] the installed weights (read only through stage_w)
+    double* or_mpart = nullptr;  // [N, nufft_sample_chunks(M)] partial sums of the misfit
+    float2* or_amaps = nullptr;  // [map_n, L, H, W] pnp_acquire_offres' own segment maps: the installed ones stay as they are
+    size_t or_maps_cap = 0, or_y_cap = 0, or_w_cap = 0, or_mpart_cap = 0, or_amaps_cap = 0;
     // Toeplitz normal operator (include/pnpadmm_toeplitz.h): the spectrum and its buffers by pnp_toeplitz_plan
     std::vector<double> nc_traj; // host copy of the planned trajectory [M][2] (ky, kx): what the spectrum is built from
     double* tz_traj = nullptr;   // [M][2] its device copy
@@ -423,7 +439,9 @@ int mc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
 
 // ---- non-Cartesian stage ----------------------------------------------------------------------------
 // the live non-Cartesian stage's weights (nullptr: 1)
-const float* stage_w(const pnp_engine* e) { return !e->stage.has_w ? nullptr : e->stage.kind == STAGE_NS ? e->ns_w : e->nc_w; }
+const float* stage_w(const pnp_engine* e) {
+    return !e->stage.has_w ? nullptr : e->stage.kind == STAGE_NS ? e->ns_w : e->stage.kind == STAGE_OR ? e->or_w : e->nc_w;
+}
 // the centred transform of pnp_fft2c on the plan's grid, in place in nc_grid: rows then columns in both directions
 int nc_fft(pnp_engine* e, int batch, int inverse, hipStream_t s) {
     const NufftDev& P = e->nc;
@@ -559,6 +577,75 @@ int ns_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
     return PNP_OK;
 }
 
+// ---- off-resonance correction (include/pnpadmm_offres.h) ------------------------------------------------
+int or_block_of(const pnp_engine* e) { return e->orp.segments < e->or_block ? e->orp.segments : e->or_block; }
+// out [batch, M] = A src with the segment maps `maps` [map_n, L, h, w], block by block: a block's samples are blended into out before the
+// next block's grids replace them
+int or_forward(pnp_engine* e, const float2* src, const float* src_real, const float2* maps, int map_n, int batch, float2* out, hipStream_t s) {
+    const int L = e->orp.segments, B = or_block_of(e);
+    for (int l0 = 0; l0 < L; l0 += B) {
+        const int cb = std::min(B, L - l0);
+        if (e->or_naive & OR_GATHER) {
+            if (int rc = ns_forward_block(e, src, src_real, maps, map_n, L, l0, cb, batch, e->ns_samp, cb, 0, s)) return rc;
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_offres_blend(e->ns_samp, e->orp, e->nc, out, l0, cb, batch, s));
+            continue;
+        }
+        {
+            Prof p(e, s, PROF_OTHER, -1);
+            if (e->ns_naive & NS_PAD) {
+                HIP_TRY(launch_ncsense_expand(src, src_real, maps, map_n, L, l0, cb, e->nc, e->ns_img, batch, s));
+                HIP_TRY(launch_nufft_pad(e->ns_img, nullptr, e->nc, e->ns_grid, batch * cb, s));
+                p.end(2);
+            } else {
+                HIP_TRY(launch_ncsense_pad(src, src_real, maps, map_n, L, l0, cb, e->nc, e->ns_grid, batch, s));
+            }
+        }
+        if (int rc = ns_fft(e, batch * cb, 0, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_offres_interp(e->ns_grid, e->orp, e->nc, out, l0, cb, batch, s));
+    }
+    return PNP_OK;
+}
+// q [batch, h, w] = A^H (w . y), y: [batch, M] (+ mu pv with the partial sums of Re<pv, q>: the last block's epilogue; pv, mu, tact, partial
+// may be nullptr)
+int or_adjoint(pnp_engine* e, const float2* y, const float* w, const float2* maps, int map_n, int batch, const float2* pv, const float* mu,
+               const float* tact, float2* q, double* partial, hipStream_t s) {
+    const int L = e->orp.segments, B = or_block_of(e);
+    for (int l0 = 0; l0 < L; l0 += B) {
+        const int cb = std::min(B, L - l0);
+        if (e->or_naive & OR_GRID) {
+            {
+                Prof p(e, s, PROF_OTHER, -1);
+                HIP_TRY(launch_offres_expand(y, e->orp, e->nc, e->ns_samp, l0, cb, batch, s));
+            }
+            if (int rc = ns_adjoint_block(e, e->ns_samp, cb, 0, w, maps, map_n, L, l0, cb, batch, pv, mu, tact, q, partial, s)) return rc;
+            continue;
+        }
+        {
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_offres_grid(y, w, e->orp, e->nc, e->ns_grid, l0, cb, batch, s, e->tune.offres_grid_filter));
+        }
+        if (int rc = ns_fft(e, batch * cb, 1, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        if (e->ns_naive & NS_CROP) {
+            HIP_TRY(launch_nufft_crop(e->ns_grid, e->nc, nullptr, nullptr, nullptr, e->ns_img, nullptr, batch * cb, s));
+            HIP_TRY(launch_ncsense_combine(e->ns_img, maps, map_n, L, l0, cb, e->nc, pv, mu, tact, q, partial, batch, s));
+            p.end(2);
+        } else {
+            HIP_TRY(launch_ncsense_crop(e->ns_grid, maps, map_n, L, l0, cb, e->nc, pv, mu, tact, q, partial, batch, s));
+        }
+    }
+    return PNP_OK;
+}
+// q = A^H W A pv + mu pv with the installed constants; the partial sums of Re<pv, q> go to mc_part.  A pv goes through nc_samp whole - the
+// blend joins neighbouring segments - before the adjoint starts.  Stopped slices: only the combine launches skip them
+int or_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    const int N = e->cfg.n;
+    if (int rc = or_forward(e, pv, nullptr, e->or_maps, e->stage.sens_n, N, e->nc_samp, s)) return rc;
+    return or_adjoint(e, e->nc_samp, stage_w(e), e->or_maps, e->stage.sens_n, N, pv, mu, tact, q, e->mc_part, s);
+}
+
 // ---- Toeplitz normal operator (include/pnpadmm_toeplitz.h) ----------------------------------------------
 // q [planes, h, w] = crop(ifft2c(K . fft2c(pad(src)))) (+ mu pv with the partial sums of Re<pv, q>: the last launch's epilogue), through
 // tz_grid.  Three fused launches, or the seven composed ones; src may be q (the grid lies between them).  Stopped slices: only the last
@@ -636,6 +723,7 @@ NormalOp stage_normal(const pnp_engine* e) {
     case STAGE_MC: return mc_normal;
     case STAGE_NC: return e->stage.toeplitz ? tz_nc_normal : nc_normal;
     case STAGE_NS: return e->stage.toeplitz ? tz_ns_normal : ns_normal;
+    case STAGE_OR: return or_normal;
     default: return nullptr;
     }
 }
@@ -746,7 +834,7 @@ void commit_stage(pnp_engine* e, const LiveStage& st) { e->stage = st; }
 // replaced loses its constants with it.  The closed-form and SENSE stages use neither and stay.
 void drop_stage(pnp_engine* e, bool toeplitz_only) {
     const LiveStage& st = e->stage;
-    if ((st.kind == STAGE_NC || st.kind == STAGE_NS) && (st.toeplitz || !toeplitz_only)) e->stage = LiveStage{};
+    if ((st.kind == STAGE_NC || st.kind == STAGE_NS || st.kind == STAGE_OR) && (st.toeplitz || !toeplitz_only)) e->stage = LiveStage{};
 }
 
 // pnp_set_kspace (no iterate) / pnp_reset: the closed-form stage's constants
@@ -944,6 +1032,13 @@ int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float
 int stage_misfit(pnp_engine* e, const float* x, double* dcpart, hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, C = e->stage.coils;
     switch (e->stage.kind) {
+    case STAGE_OR: {
+        // the segmented A x into the sample scratch, then sum_m w_m |(A x)_m - y_m|^2
+        if (int rc = or_forward(e, nullptr, x, e->or_maps, e->stage.sens_n, N, e->nc_samp, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_nufft_misfit(e->nc_samp, e->or_y, stage_w(e), e->nc, e->or_mpart, dcpart, N, s));
+        return PNP_OK;
+    }
     case STAGE_NS: {
         // A x block by block into the sample scratch, then sum_c sum_m w_m |(A x)_{c,m} - y_{c,m}|^2
         const int B = ns_block_of(e, C);
@@ -993,6 +1088,7 @@ int need_stage(const char* fn, const pnp_engine* e, StageKind kind) {
     switch (kind) {
     case STAGE_MC: return fail(PNP_ERR_STATE, "%s: the handle is in single-coil mode (pnp_set_kspace_mc / pnp_reset_mc)", fn);
     case STAGE_NC: return fail(PNP_ERR_STATE, "%s: the handle is not in non-Cartesian mode (pnp_set_kspace_nc / pnp_reset_nc)", fn);
+    case STAGE_OR: return fail(PNP_ERR_STATE, "%s: the handle is not in off-resonance mode (pnp_set_kspace_offres / pnp_reset_offres)", fn);
     default: return fail(PNP_ERR_STATE, "%s: the handle is not in non-Cartesian SENSE mode (pnp_set_kspace_ncsense / pnp_reset_ncsense)", fn);
     }
 }
@@ -1084,6 +1180,8 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     e->tune = tune;
     if (tune.ncsense_block >= 1 && tune.ncsense_block <= PNP_MC_MAX_COILS) e->ns_block = tune.ncsense_block;   // a check and a timing knob
     if (tune.ncsense_naive >= 0) e->ns_naive = tune.ncsense_naive ? NS_ALL : 0;
+    if (tune.offres_block >= 1 && tune.offres_block <= PNP_MC_MAX_COILS) e->or_block = tune.offres_block;     // a check and a timing knob
+    if (tune.offres_naive >= 0) e->or_naive = tune.offres_naive ? OR_ALL : 0;
     e->tz_fused = !tune.toeplitz_naive && kspace_len_ok(2 * cfg->h) && kspace_len_ok(2 * cfg->w) && toeplitz_fused_ok(cfg->h, cfg->w);
     e->dplan = plan;
     int rc;
@@ -1119,6 +1217,8 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->nc.tw_gh); (void)hipFree(e->nc.tw_gw);
     (void)hipFree(e->ns_img);
     (void)hipFree(e->tz_traj); (void)hipFree(e->tz_k); (void)hipFree(e->tz_w); (void)hipFree(e->tz_tw_h); (void)hipFree(e->tz_tw_w); (void)hipFree(e->tz_grid);
+    (void)hipFree(e->orp.tau); (void)hipFree(e->orp.seg); (void)hipFree(e->orp.b0); (void)hipFree(e->orp.b1); (void)hipFree(e->orp.list_off);
+    (void)hipFree(e->orp.list_idx); (void)hipFree(e->or_maps); (void)hipFree(e->or_y); (void)hipFree(e->or_w); (void)hipFree(e->or_mpart); (void)hipFree(e->or_amaps);
     (void)hipFree(e->dcf_grid); (void)hipFree(e->dcf_w); (void)hipFree(e->dcf_part); (void)hipFree(e->dcf_max);
     (void)hipFree(e->ns_grid); (void)hipFree(e->ns_samp); (void)hipFree(e->ns_y); (void)hipFree(e->ns_sens); (void)hipFree(e->ns_w); (void)hipFree(e->ns_mpart);
     (void)hipFree(e->nc_grid); (void)hipFree(e->nc_samp); (void)hipFree(e->nc_y); (void)hipFree(e->nc_w); (void)hipFree(e->nc_mpart);
@@ -1645,7 +1745,10 @@ int pnp_nufft_plan(pnp_handle e, const double* traj, int64_t m, int gh, int gw, 
     D.m = 0;
     drop_stage(e, false);
     e->tz_planned = false;                                  // the spectrum belongs to the plan it was built for
+    e->orp.segments = 0;                                    // ... and so does the off-resonance plan
     e->nc_traj.assign(traj, traj + 2 * (size_t)m);
+    e->nc_bin_off_h = P.bin_off;
+    e->nc_bin_idx_h = P.bin_idx;
     HIP_TRY(nc_upload(D.i0, P.i0.data(), P.i0.size() * sizeof(int32_t)));
     HIP_TRY(nc_upload(D.wts, P.wts.data(), P.wts.size() * sizeof(float)));
     HIP_TRY(nc_upload(D.cy, P.cy.data(), P.cy.size() * sizeof(float)));
@@ -1922,6 +2025,239 @@ int pnp_acquire_ncsense(pnp_handle e, const float* gt, const float* sens, int co
     }
     return PNP_OK;
     PNP_API_END("pnp_acquire_ncsense")
+}
+
+// ---- off-resonance correction (include/pnpadmm_offres.h) -------------------------------------------------
+static_assert(PNP_MC_MAX_COILS == kOffresMaxSegments, "the header's limit is the plan's");
+
+namespace {
+
+int or_need_plan(const char* fn, const pnp_engine* e) {
+    if (int rc = nc_need_plan(fn, e)) return rc;
+    return e->orp.segments > 0 ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no off-resonance plan (pnp_offres_plan)", fn);
+}
+// the handle-dependent argument errors of the entry points that take a field map or segment maps
+int or_check(const char* fn, const pnp_engine* e, int map_n) {
+    if (map_n != 1 && map_n != e->cfg.n) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n=%d", fn, e->cfg.n);
+    if (int rc = or_need_plan(fn, e)) return rc;
+    if ((long long)e->cfg.n * or_block_of(e) > 65535)
+        return fail(PNP_ERR_INVALID, "%s: n * min(segments, block) must be <= 65535 (got %d * %d)", fn, e->cfg.n, or_block_of(e));
+    return PNP_OK;
+}
+// the segment-block scratch (the coil-block scratch of the non-Cartesian SENSE stage, for a block of segments) and `maps_need` bytes of the
+// acquisition's own segment maps
+int or_ensure(pnp_engine* e, size_t maps_need = 0) {
+    const size_t planes = (size_t)e->cfg.n * or_block_of(e);
+    return ws_grow(e, "off-resonance scratch", {{(void**)&e->ns_grid, &e->ns_grid_cap, planes * e->nc.gh * e->nc.gw * sizeof(float2), false},
+                                               {(void**)&e->ns_samp, &e->ns_samp_cap, planes * (size_t)e->nc.m * sizeof(float2), false},
+                                               {(void**)&e->ns_img, &e->ns_img_cap,
+                                                (e->ns_naive & (NS_PAD | NS_CROP)) ? planes * e->cfg.h * e->cfg.w * sizeof(float2) : 0, false},
+                                               {(void**)&e->or_amaps, &e->or_amaps_cap, maps_need, false}});
+}
+
+// pnp_set_kspace_offres (no iterate) / pnp_reset_offres: the episode constants of the stage - y, w, the segment maps of omega, A^H W y - and
+// optionally the iterate.  Every rejection happens before any HIP call
+int or_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x0, const float2* y, const float* omega, int map_n, const float* w,
+               int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
+    int rc;
+    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    if ((rc = nc_check_cg(fn, cg_iters))) return rc;
+    if (with_iterate && !x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (!omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
+    if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if ((rc = or_check(fn, e, map_n))) return rc;
+    PNP_ON_DEVICE(e);
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, L = e->orp.segments;
+    const size_t M = (size_t)e->nc.m;
+    if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
+    if ((rc = or_ensure(e))) return rc;
+    if ((rc = ws_grow(e, "off-resonance constants",
+                      {{(void**)&e->or_y, &e->or_y_cap, (size_t)N * M * sizeof(float2), false},
+                       {(void**)&e->or_maps, &e->or_maps_cap, (size_t)map_n * L * H * W * sizeof(float2), false},
+                       {(void**)&e->or_w, &e->or_w_cap, w ? M * sizeof(float) : 0, false},
+                       {(void**)&e->or_mpart, &e->or_mpart_cap, (size_t)N * nufft_sample_chunks((int64_t)M) * sizeof(double), false}})))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(e->or_y, y, (size_t)N * M * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    if (w) HIP_TRY(hipMemcpyAsync(e->or_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, e->or_maps, s));
+    }
+    if ((rc = or_adjoint(e, e->or_y, w ? e->or_w : nullptr, e->or_maps, map_n, N, nullptr, nullptr, nullptr, mc_aty(e), nullptr, s))) return rc;
+    if (with_iterate) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
+    }
+    commit_stage(e, {STAGE_OR, false, 0, map_n, cg_iters, w != nullptr});
+    return PNP_OK;
+}
+
+}  // namespace
+
+int pnp_offres_plan(pnp_handle e, const double* t, int segments, int flags) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_plan";
+    // every rejection happens before any HIP call and leaves the handle as it was; scalar ranges first
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (segments < 1 || segments > PNP_MC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: segments must be 1..%d (got %d)", fn, PNP_MC_MAX_COILS, segments);
+    if (!t) return fail(PNP_ERR_INVALID, "%s: null t", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = nc_need_plan(fn, e)) return rc;
+    OffresPlan P;
+    std::string why;
+    const int tiles = e->nc.tiles_y * e->nc.tiles_x;
+    if (!plan_offres(t, e->nc.m, segments, tiles, e->nc_bin_off_h.data(), e->nc_bin_idx_h.data(), &P, &why)) return fail(PNP_ERR_INVALID, "%s: %s", fn, why.c_str());
+    PNP_ON_DEVICE(e);
+    OffresDev& D = e->orp;
+    const size_t M = (size_t)P.m;
+    if (int rc = ws_grow(e, "off-resonance plan", {{(void**)&D.tau, &e->or_tau_cap, P.tau.size() * sizeof(double), false},
+                                                   {(void**)&D.seg, &e->or_seg_cap, M * sizeof(int32_t), false},
+                                                   {(void**)&D.b0, &e->or_b0_cap, M * sizeof(float), false},
+                                                   {(void**)&D.b1, &e->or_b1_cap, M * sizeof(float), false},
+                                                   {(void**)&D.list_off, &e->or_loff_cap, P.list_off.size() * sizeof(int32_t), false},
+                                                   {(void**)&D.list_idx, &e->or_lidx_cap, std::max<size_t>(P.list_idx.size(), 1) * sizeof(int32_t), false}}))
+        return rc;
+    if (D.segments > 0) (void)hipDeviceSynchronize();       // no launch still reads the plan being replaced
+    // from here on the old plan is gone: a live off-resonance stage's maps belong to its centres and are dropped with it
+    D.segments = 0;
+    if (e->stage.kind == STAGE_OR) drop_stage(e, false);
+    HIP_TRY(nc_upload(D.tau, P.tau.data(), P.tau.size() * sizeof(double)));
+    HIP_TRY(nc_upload(D.seg, P.seg.data(), M * sizeof(int32_t)));
+    HIP_TRY(nc_upload(D.b0, P.b0.data(), M * sizeof(float)));
+    HIP_TRY(nc_upload(D.b1, P.b1.data(), M * sizeof(float)));
+    HIP_TRY(nc_upload(D.list_off, P.list_off.data(), P.list_off.size() * sizeof(int32_t)));
+    if (!P.list_idx.empty()) HIP_TRY(nc_upload(D.list_idx, P.list_idx.data(), P.list_idx.size() * sizeof(int32_t)));
+    D.segments = P.segments;
+    return PNP_OK;
+    PNP_API_END("pnp_offres_plan")
+}
+
+int pnp_offres_segments(pnp_handle e) { return e && e->nc.m > 0 ? e->orp.segments : 0; }
+
+int pnp_offres_maps(pnp_handle e, const float* omega, int map_n, float* maps, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_maps";
+    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    if (!omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
+    if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
+    if (maps == omega) return fail(PNP_ERR_INVALID, "%s: maps must not alias omega", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = or_check(fn, e, map_n)) return rc;
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, (float2*)maps, s));
+    return PNP_OK;
+    PNP_API_END("pnp_offres_maps")
+}
+
+int pnp_offres_forward(pnp_handle e, const float* img, const float* maps, int map_n, int batch, float* samples, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_forward";
+    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
+    if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
+    if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
+    if (!samples) return fail(PNP_ERR_INVALID, "%s: null samples", fn);
+    if (samples == img || samples == maps) return fail(PNP_ERR_INVALID, "%s: samples must not alias img or maps", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
+    if (int rc = or_check(fn, e, map_n)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = or_ensure(e)) return rc;
+    return or_forward(e, (const float2*)img, nullptr, (const float2*)maps, map_n, batch, (float2*)samples, (hipStream_t)stream);
+    PNP_API_END("pnp_offres_forward")
+}
+
+int pnp_offres_adjoint(pnp_handle e, const float* samples, const float* weights, const float* maps, int map_n, int batch, float* img, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_adjoint";
+    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
+    if (!samples) return fail(PNP_ERR_INVALID, "%s: null samples", fn);
+    if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
+    if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
+    if (img == samples || img == maps || (const float*)img == weights) return fail(PNP_ERR_INVALID, "%s: img must not alias samples, weights or maps", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
+    if (int rc = or_check(fn, e, map_n)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = or_ensure(e)) return rc;
+    return or_adjoint(e, (const float2*)samples, weights, (const float2*)maps, map_n, batch, nullptr, nullptr, nullptr, (float2*)img, nullptr,
+                      (hipStream_t)stream);
+    PNP_API_END("pnp_offres_adjoint")
+}
+
+int pnp_set_kspace_offres(pnp_handle e, const float* y, const float* omega, int map_n, const float* w, int cg_iters, void* stream) {
+    PNP_API_BEGIN
+    return or_install("pnp_set_kspace_offres", e, false, nullptr, (const float2*)y, omega, map_n, w, cg_iters, nullptr, nullptr, nullptr,
+                      (hipStream_t)stream);
+    PNP_API_END("pnp_set_kspace_offres")
+}
+
+int pnp_reset_offres(pnp_handle e, const float* x0, const float* y, const float* omega, int map_n, const float* w, int cg_iters, float* x, float* z,
+                     float* u, void* stream) {
+    PNP_API_BEGIN
+    return or_install("pnp_reset_offres", e, true, (const float2*)x0, (const float2*)y, omega, map_n, w, cg_iters, x, (float2*)z, (float2*)u,
+                      (hipStream_t)stream);
+    PNP_API_END("pnp_reset_offres")
+}
+
+int pnp_offres_live(pnp_handle e) { return e && e->stage.kind == STAGE_OR ? 1 : 0; }
+
+int pnp_offres_cg_residual(pnp_handle e, float* out, void* stream) {
+    PNP_API_BEGIN
+    return stage_cg_residual("pnp_offres_cg_residual", e, STAGE_OR, out, (hipStream_t)stream);
+    PNP_API_END("pnp_offres_cg_residual")
+}
+
+int pnp_offres_normal(pnp_handle e, const float* pv, const float* mu, float* q, void* stream) {
+    PNP_API_BEGIN
+    return stage_normal_op("pnp_offres_normal", e, STAGE_OR, pv, mu, q, (hipStream_t)stream);
+    PNP_API_END("pnp_offres_normal")
+}
+
+int pnp_acquire_offres(pnp_handle e, const float* gt, const float* omega, int map_n, const float* dcf, double sigma_n, uint64_t seed, int flags,
+                       float* y, float* aty0, float* x0, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_acquire_offres";
+    // every rejection happens before any HIP call, and leaves the outputs untouched
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "%s: sigma_n must be finite and >= 0 (got %g)", fn, sigma_n);
+    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    if (!gt) return fail(PNP_ERR_INVALID, "%s: null gt", fn);
+    if (!omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (y == gt || y == omega || (aty0 && (aty0 == gt || aty0 == omega || aty0 == y)) || (x0 && (x0 == gt || x0 == omega || x0 == y)))
+        return fail(PNP_ERR_INVALID, "%s: no output may alias gt, omega or another output", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = or_check(fn, e, map_n)) return rc;
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = or_ensure(e, (size_t)map_n * e->orp.segments * H * W * sizeof(float2)))) return rc;
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, e->or_amaps, s));
+    }
+    if ((rc = or_forward(e, nullptr, gt, e->or_amaps, map_n, N, (float2*)y, s))) return rc;
+    if (sigma_n != 0.0) {                                   // a noiseless acquisition draws nothing and keeps the forward's own bits
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_nufft_noise((float2*)y, sigma_n, seed, e->nc, N, s));
+    }
+    if (!aty0 && !x0) return PNP_OK;
+    float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the image goes to the data-fidelity stage's scratch plane
+    if ((rc = or_adjoint(e, (const float2*)y, dcf, e->or_amaps, map_n, N, nullptr, nullptr, nullptr, a, nullptr, s))) return rc;
+    if (x0) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
+    }
+    return PNP_OK;
+    PNP_API_END("pnp_acquire_offres")
 }
 
 // ---- Toeplitz normal operator (include/pnpadmm_toeplitz.h) ----------------------------------------------

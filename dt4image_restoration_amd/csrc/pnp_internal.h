@@ -40,6 +40,11 @@ struct Tuning {
     int ncsense_naive = -1;       // PNP_NCSENSE_NAIVE (tests, timing): 1 = every step of that stage as the single-coil launches between an expand and a
                                   // combine kernel, 0 = every step coil-batched; unset: kNcsenseNaiveSteps, the choice per step by measurement
     bool toeplitz_naive = false;  // PNP_TOEPLITZ_NAIVE (tests, timing): the Toeplitz normal operator as its seven composed launches instead of the fused three
+    int offres_block = 0;         // PNP_OFFRES_SEG_BLOCK (tests, timing): segments per block of the off-resonance operator, 1..32 (else: kOffresBlock)
+    bool offres_grid_filter = false;   // PNP_OFFRES_GRID_FILTER (timing): the two-segment gridding filters the tile's whole bin per segment
+                                  // instead of walking the plan's per-(segment, tile) list; the same numbers
+    int offres_naive = -1;        // PNP_OFFRES_NAIVE (tests, timing): 1 = the operator composed from the non-Cartesian SENSE launches and two sample
+                                  // kernels, 0 = the two-segment gather and gridding; unset: kOffresNaiveSteps, the choice per step by measurement
 };
 Tuning tuning_from_env();
 
@@ -457,5 +462,35 @@ hipError_t launch_dcf_gather(const double* grid, const NufftDev& P, const double
 // out [M] = float32(w (h w / sum w)); info [passes] = the maximum of each pass's wmax row (info may be nullptr); partial [dcf_sum_chunks]
 hipError_t launch_dcf_finish(const double* w, double* partial, const NufftDev& P, float* out, const float* wmax, int passes, float* info,
                              hipStream_t s);
+
+// ---- off-resonance correction (offres_kernels.hip; the operator: include/pnpadmm_offres.h; the plan: offres_plan.h) ---
+// The uploaded plan: every pointer is device memory, laid out as OffresPlan's vectors
+struct OffresDev {
+    int segments = 0;        // L; 0: no plan
+    double* tau = nullptr;   // [L]
+    int* seg = nullptr;      // [M]
+    float* b0 = nullptr;     // [M]
+    float* b1 = nullptr;     // [M]
+    int* list_off = nullptr; // [L tiles + 1]
+    int* list_idx = nullptr;
+};
+static constexpr int kOffresBlock = 8;     // default segments per block (PNP_OFFRES_SEG_BLOCK overrides it)
+// the steps of the operator, as bits: which of them run as the naive launches.  Both forms give the same numbers (include/pnpadmm_offres.h)
+enum OffresStep : int { OR_GATHER = 1, OR_GRID = 2, OR_ALL = 3 };
+// the shipped choice (profiles/offres_bench.json): a two-segment kernel ships only where it is not slower than the naive form
+static constexpr int kOffresNaiveSteps = 0;
+// maps [map_n, L, h, w] = exp(-i omega tau_l); omega: [map_n, h, w]
+hipError_t launch_offres_maps(const float* omega, int map_n, const OffresDev& R, const NufftDev& P, float2* maps, hipStream_t s);
+// out [batch, M] (+)= the blended gather of the block's grids [batch, cb, gh, gw] (segments l0 .. l0 + cb - 1); a sample whose first segment
+// lies before the block continues from out
+hipError_t launch_offres_interp(const float2* grid, const OffresDev& R, const NufftDev& P, float2* out, int l0, int cb, int batch, hipStream_t s);
+// the naive form's blend of the block's samples samp [batch, cb, M]
+hipError_t launch_offres_blend(const float2* samp, const OffresDev& R, const NufftDev& P, float2* out, int l0, int cb, int batch, hipStream_t s);
+// the naive form's expansion ye [batch, cb, M] = b_l . y of y [batch, M]
+hipError_t launch_offres_expand(const float2* y, const OffresDev& R, const NufftDev& P, float2* ye, int l0, int cb, int batch, hipStream_t s);
+// grid [batch, cb, gh, gw] = per segment of the block the spread of w . b_l . y, every grid point written, no atomics
+// filter: walk the NUFFT plan's whole tile bin per segment instead of the plan's per-(segment, tile) list (PNP_OFFRES_GRID_FILTER: timing)
+hipError_t launch_offres_grid(const float2* y, const float* w, const OffresDev& R, const NufftDev& P, float2* grid, int l0, int cb, int batch,
+                              hipStream_t s, bool filter = false);
 
 }  // namespace pnp

@@ -442,8 +442,10 @@ class GreedyEvaluator:
                     return v if v.numel() == hw else v.reshape(-1, *v.shape[-2:])[a:b]
                 if key == "sens" and v.dim() == 3:          # coil maps [C,H,W] shared by every slice
                     return v
-                if key in ("traj", "dcf"):                  # a non-Cartesian episode's trajectory and weights, shared by every slice
-                    return v
+                if key in ("traj", "dcf", "times", "segments") or (key == "omega" and v.dim() == 2):
+                    return v                                # a non-Cartesian episode's trajectory, weights, sample times and shared field map
+                if key == "omega":
+                    return v.reshape(-1, *v.shape[-2:])[a:b]
                 return v[a:b] if v.dim() > 0 and v.shape[0] == n else v
             sub = {key: cut(key, v) for key, v in mat.items()}
             st = self._streams[k]

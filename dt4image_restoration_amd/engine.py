@@ -151,6 +151,7 @@ class PnPEngine:
         gh, gw = (0, 0) if grid is None else (int(grid[0]), int(grid[1]))
         self._nufft_key = None
         self._tz_weights = None      # the library drops the Toeplitz spectrum with the plan it was built for
+        self._offres_key = None      # ... and the off-resonance plan
         _lib.check(self.lib.pnp_nufft_plan(self._h, t.ctypes.data, t.shape[0], gh, gw, int(width), 0), "pnp_nufft_plan")
         self._nufft_key = (t.copy(), gh, gw, int(width), traj)
         self.live_episode = 0        # non-Cartesian constants are dropped with their plan: whoever binds episodes re-installs
@@ -475,12 +476,164 @@ class PnPEngine:
                                                 self._stream()), "pnp_acquire_ncsense")
         return y, aty0, x0
 
+    # -- off-resonance correction (include/pnpadmm_offres.h) ------------------------------------
+    def offres_plan(self, times, segments: int) -> None:
+        """Plan the time-segmented off-resonance operator on the live NUFFT plan (pnp_offres_plan): times [M] seconds, one per trajectory
+        sample (array or tensor; taken as float64 on the host), segments = L in 1..32.  Replaces an earlier off-resonance plan and drops a
+        live off-resonance stage; `nufft_plan` drops this plan."""
+        t = np.ascontiguousarray(times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else times, dtype=np.float64).reshape(-1)
+        m = self.nufft_samples
+        if m and t.size != m:
+            raise ValueError(f"times: expected {m} samples, got {t.shape}")
+        if self.offres_live:
+            self.live_episode = 0
+        self._offres_key = None
+        _lib.check(self.lib.pnp_offres_plan(self._h, t.ctypes.data, int(segments), 0), "pnp_offres_plan")
+        self._offres_key = (t.copy(), int(segments))
+
+    _offres_key = None           # (a copy of times, segments) of the live off-resonance plan
+
+    def offres_planned(self, times, segments: int) -> bool:
+        """Whether the live off-resonance plan was made from exactly these times and segments on the live NUFFT plan."""
+        k = self._offres_key
+        if k is None or self.offres_segments != int(segments) or k[1] != int(segments):      # (pnp_nufft_plan drops the plan: 0 segments)
+            return False
+        t = np.asarray(times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else times, dtype=np.float64).reshape(-1)
+        return k[0].shape == t.shape and bool(np.array_equal(k[0], t))
+
+    @property
+    def offres_segments(self) -> int:
+        """L of the handle's off-resonance plan; 0 without one."""
+        return int(self.lib.pnp_offres_segments(self._h))
+
+    @property
+    def offres_live(self) -> bool:
+        """Whether the live data-fidelity stage is the off-resonance one."""
+        return bool(self.lib.pnp_offres_live(self._h))
+
+    def _omega(self, omega: torch.Tensor, name: str = "omega") -> Tuple[torch.Tensor, int]:
+        """Field map float32 [H,W] (shared) or [N,H,W] in rad/s -> (tensor, map_n)."""
+        hw = self.h * self.w
+        if omega.numel() not in (hw, self.n * hw):
+            raise ValueError(f"{name}: expected {hw} or {self.n * hw} elements, got {tuple(omega.shape)}")
+        self._chk(omega, torch.float32, omega.numel(), name)
+        return omega, (1 if omega.numel() == hw and (self.n > 1 or omega.dim() < 3) else self.n)
+
+    def _offres_maps_arg(self, maps: torch.Tensor) -> Tuple[torch.Tensor, int]:
+        """Segment maps complex64 [L,H,W] (shared) or [N,L,H,W] -> (tensor, map_n)."""
+        per = max(self.offres_segments, 1) * self.h * self.w
+        if maps.numel() not in (per, self.n * per):
+            raise ValueError(f"maps: expected {per} or {self.n * per} elements, got {tuple(maps.shape)}")
+        self._chk(maps, torch.complex64, maps.numel(), "maps")
+        return maps, (1 if maps.numel() == per and (self.n > 1 or maps.dim() < 4) else self.n)
+
+    def offres_maps(self, omega: torch.Tensor) -> torch.Tensor:
+        """E_l = exp(-i omega tau_l), complex64 [L,H,W] for a shared map omega float32 [H,W], [N,L,H,W] for [N,H,W] (pnp_offres_maps)."""
+        omega, map_n = self._omega(omega)
+        shape = (self.offres_segments, self.h, self.w)
+        maps = torch.empty(shape if map_n == 1 and omega.dim() < 3 else (map_n,) + shape, dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_offres_maps(self._h, omega.data_ptr(), map_n, maps.data_ptr(), self._stream()), "pnp_offres_maps")
+        return maps
+
+    def offres_forward(self, img: torch.Tensor, maps: torch.Tensor) -> torch.Tensor:
+        """samples complex64 [B,M] = the segmented A img (pnp_offres_forward); img complex64 [B,H,W] (or [B,1,H,W]), B <= N; maps from
+        `offres_maps`."""
+        b = self._batch_of(img, self.h * self.w, "img")
+        self._chk(img, torch.complex64, img.numel(), "img")
+        maps, map_n = self._offres_maps_arg(maps)
+        out = torch.empty((b, max(self.nufft_samples, 1)), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_offres_forward(self._h, img.data_ptr(), maps.data_ptr(), map_n, b, out.data_ptr(), self._stream()),
+                   "pnp_offres_forward")
+        return out
+
+    def offres_adjoint(self, samples: torch.Tensor, maps: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """img complex64 [B,H,W] = sum_l conj(E_l) . F_nu^H(weights . b_l . samples) (pnp_offres_adjoint); samples complex64 [B,M], weights
+        float32 [M] or None."""
+        m = self.nufft_samples
+        b = self._batch_of(samples, m, "samples")
+        self._chk(samples, torch.complex64, samples.numel(), "samples")
+        maps, map_n = self._offres_maps_arg(maps)
+        if weights is not None:
+            self._chk(weights, torch.float32, m, "weights")
+        out = torch.empty((b, self.h, self.w), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_offres_adjoint(self._h, samples.data_ptr(), weights.data_ptr() if weights is not None else None, maps.data_ptr(),
+                                               map_n, b, out.data_ptr(), self._stream()), "pnp_offres_adjoint")
+        return out
+
+    def reset_offres(self, x0: torch.Tensor, y: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None,
+                     cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Install the off-resonance constants (y complex64 [N,M], omega float32 [H,W] or [N,H,W] in rad/s, w float32 [M] or None) and start an
+        episode from x0 complex64 [N,1,H,W] (pnp_reset_offres).  Returns fresh (x f32, z c64, u c64); steps then solve the k-space subproblem
+        by `cg_iters` CG iterations on A^H W A + mu I with the time-segmented A."""
+        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
+        yp, wp = self._nc_args(y, w)
+        omega, map_n = self._omega(omega)
+        x, z, u = self._iterate()
+        _lib.check(self.lib.pnp_reset_offres(self._h, x0.data_ptr(), yp, omega.data_ptr(), map_n, wp, int(cg_iters), x.data_ptr(), z.data_ptr(),
+                                             u.data_ptr(), self._stream()), "pnp_reset_offres")
+        self.live_episode = _next_episode()
+        return x, z, u
+
+    def set_kspace_offres(self, y: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0,
+                          cg_iters: int = 8) -> None:
+        """Re-install the off-resonance constants of another episode without touching any iterate (pnp_set_kspace_offres)."""
+        yp, wp = self._nc_args(y, w)
+        omega, map_n = self._omega(omega)
+        _lib.check(self.lib.pnp_set_kspace_offres(self._h, yp, omega.data_ptr(), map_n, wp, int(cg_iters), self._stream()),
+                   "pnp_set_kspace_offres")
+        self.live_episode = episode or _next_episode()
+
+    def offres_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+        """q = A^H W A p + mu p with the installed off-resonance constants (pnp_offres_normal); p complex64 [N,1,H,W], mu float32 [N]."""
+        return self._normal("pnp_offres_normal", p, mu)
+
+    def offres_cg_residual(self) -> torch.Tensor:
+        """float32 [N]: the relative residual the CG solve of the last step ended with (pnp_offres_cg_residual; that mode only)."""
+        return self._cg_residual("pnp_offres_cg_residual")
+
+    def acquire_offres(self, gt: torch.Tensor, omega: torch.Tensor, sigma_n: float, seed: int,
+                       dcf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Simulated acquisition under the field map on the planned trajectory and times (pnp_acquire_offres): gt float32 [N,1,H,W]; returns
+        (y complex64 [N,M], aty0 = A^H (dcf . y) complex64 [N,1,H,W], x0 = max(aty0, 0))."""
+        gt = self._chk(gt, torch.float32, self.n * self.h * self.w, "gt")
+        omega, map_n = self._omega(omega)
+        m = self.nufft_samples
+        if dcf is not None:
+            self._chk(dcf, torch.float32, m, "dcf")
+        y = torch.empty((self.n, max(m, 1)), dtype=torch.complex64, device=self.device)
+        aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+        x0 = torch.empty_like(aty0)
+        _lib.check(self.lib.pnp_acquire_offres(self._h, gt.data_ptr(), omega.data_ptr(), map_n, dcf.data_ptr() if dcf is not None else None,
+                                               float(sigma_n), int(seed) & (2 ** 64 - 1), 0, y.data_ptr(), aty0.data_ptr(), x0.data_ptr(),
+                                               self._stream()), "pnp_acquire_offres")
+        return y, aty0, x0
+
     # -- hot path --------------------------------------------------------------------------
-    def reset(self, x0: torch.Tensor, y0: torch.Tensor, mask: torch.Tensor, sens: Optional[torch.Tensor] = None,
-              cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def _offres_for(self, times, segments) -> None:
+        """the off-resonance plan of `reset` / `set_kspace` with omega: planned here when times are given and differ from the live plan's"""
+        if times is None:
+            return
+        if segments is None:
+            raise ValueError("times needs segments (acquisition.offres_segments chooses them)")
+        if not self.offres_planned(times, segments):
+            self.offres_plan(times, segments)
+
+    def reset(self, x0: torch.Tensor, y0: torch.Tensor, mask: Optional[torch.Tensor] = None, sens: Optional[torch.Tensor] = None,
+              cg_iters: int = 8, omega: Optional[torch.Tensor] = None, times=None, segments: Optional[int] = None,
+              w: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """x0, y0 complex64 [N,1,H,W]; mask bool/uint8 [H,W] (or [N,H,W]).  Returns fresh (x f32, z c64, u c64).
         With sens (complex64 [C,H,W] or [N,C,H,W]) y0 is [N,C,H,W] and the handle enters multi-coil mode (pnp_reset_mc): the k-space
-        subproblem is then solved by `cg_iters` conjugate-gradient iterations per step."""
+        subproblem is then solved by `cg_iters` conjugate-gradient iterations per step.
+        With omega (field map, float32 [H,W] or [N,H,W] in rad/s) the episode is the off-resonance one on the planned trajectory
+        (`reset_offres`): y0 is the samples [N,M], mask is not read, w float32 [M] or None are the sample weights; times with segments plan
+        the time segments first (`offres_plan`) unless the live plan is that one."""
+        if omega is not None:
+            if sens is not None:
+                raise ValueError("reset: the off-resonance stage is single-coil (omega with sens is not supported)")
+            self._offres_for(times, segments)
+            return self.reset_offres(x0, y0, omega, w, cg_iters=cg_iters)
+        if times is not None or segments is not None or w is not None:
+            raise ValueError("reset: times, segments and w go with omega")
         nhw = self.n * self.h * self.w
         x0 = self._chk(x0, torch.complex64, nhw, "x0")
         if sens is not None:
@@ -499,11 +652,19 @@ class PnPEngine:
         self.live_episode = _next_episode()
         return x, z, u
 
-    def set_kspace(self, y0: torch.Tensor, mask: torch.Tensor, episode: int = 0, sens: Optional[torch.Tensor] = None,
-                   cg_iters: int = 8) -> None:
+    def set_kspace(self, y0: torch.Tensor, mask: Optional[torch.Tensor] = None, episode: int = 0, sens: Optional[torch.Tensor] = None,
+                   cg_iters: int = 8, omega: Optional[torch.Tensor] = None, times=None, segments: Optional[int] = None,
+                   w: Optional[torch.Tensor] = None) -> None:
         """Re-install the k-space constants (y0, mask) of another episode without touching any iterate
         (pnp_set_kspace); `episode` = the id that episode's reset returned (0: a fresh id).  With sens: a multi-coil episode's
-        constants (pnp_set_kspace_mc), as in `reset`."""
+        constants (pnp_set_kspace_mc), as in `reset`.  With omega: an off-resonance episode's (`set_kspace_offres`), as in `reset`."""
+        if omega is not None:
+            if sens is not None:
+                raise ValueError("set_kspace: the off-resonance stage is single-coil (omega with sens is not supported)")
+            self._offres_for(times, segments)
+            return self.set_kspace_offres(y0, omega, w, episode=episode, cg_iters=cg_iters)
+        if times is not None or segments is not None or w is not None:
+            raise ValueError("set_kspace: times, segments and w go with omega")
         nhw = self.n * self.h * self.w
         m, mask_n = self._mask(mask)
         if sens is not None:

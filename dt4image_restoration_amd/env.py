@@ -112,6 +112,8 @@ class PnPEnv:
         traj = torch.as_tensor(data["traj"]).to(torch.float64).cpu().reshape(-1, 2).contiguous()      # (the caller's own tensor when it is one)
         m = traj.shape[0]
         sens = data.get("sens")
+        if sens is not None and data.get("omega") is not None:
+            raise ValueError("an off-resonance episode is single-coil (data['omega'] with data['sens'] is not supported)")
         if sens is not None:
             sens = torch.as_tensor(sens)
             sens = (sens if sens.is_complex() else _as_complex(sens)).to(torch.complex64)
@@ -125,6 +127,8 @@ class PnPEnv:
         gt = torch.as_tensor(data["gt"]).to(device).float()
         eng = self._engine_for(n, h, w, device)
         self._plan_nc(eng, traj)
+        if data.get("omega") is not None:                   # under a field map: the time-segmented stage (include/pnpadmm_offres.h)
+            return self._reset_offres(data, eng, x0, y0, sens, dcf, gt, traj, n, device)
         if sens is None:
             x, z, u = (eng.reset_nc_tz if self.nc_normal == "toeplitz" else eng.reset_nc)(x0, y0, dcf, cg_iters=self.cg_iters)
         else:
@@ -134,11 +138,47 @@ class PnPEnv:
                             "T": torch.zeros(n, dtype=torch.float32, device=device),
                             "complex_y0": data["y0"], "_episode": eng.live_episode, "sens": sens, "traj": traj, "dcf": dcf})
 
+    @staticmethod
+    def _offres_args(data, m: int):
+        """(times float64 [M] on the host, segments) of an off-resonance episode: data["times"], and data["segments"] or the chooser's
+        (`acquisition.offres_segments` of max |omega| and the span of the times, at most the library's 32)"""
+        from . import acquisition
+        if data.get("times") is None:
+            raise ValueError('an off-resonance episode (data["omega"]) needs data["times"]: the time of every trajectory sample')
+        times = torch.as_tensor(data["times"]).to(torch.float64).cpu().reshape(-1).contiguous()
+        if times.numel() != m:
+            raise ValueError(f"times: expected {m} samples, got {tuple(times.shape)}")
+        seg = data.get("segments")
+        if seg is None:
+            om_max = float(torch.as_tensor(data["omega"]).abs().max())
+            seg = min(acquisition.offres_segments(om_max, float(times.max() - times.min())), acquisition.OFFRES_MAX_SEGMENTS)
+        return times, int(seg)
+
+    def _reset_offres(self, data, eng: PnPEngine, x0, y0, sens, dcf, gt, traj, n: int, device) -> "OrderedDict[str, torch.Tensor]":
+        """An off-resonance episode: data["omega"] float32 [H,W] or [N,H,W] in rad/s, data["times"] float64 [M] seconds, optional
+        data["segments"]; single-coil, gridding form of the normal operator."""
+        if sens is not None:
+            raise ValueError("an off-resonance episode is single-coil (data['omega'] with data['sens'] is not supported)")
+        if self.nc_normal == "toeplitz":
+            raise ValueError("an off-resonance episode has no Toeplitz normal operator (nc_normal='toeplitz' with data['omega'])")
+        times, seg = self._offres_args(data, traj.shape[0])
+        omega = torch.as_tensor(data["omega"]).to(device, torch.float32).contiguous()
+        if not eng.offres_planned(times, seg):
+            eng.offres_plan(times, seg)
+        x, z, u = eng.reset_offres(x0, y0, omega, dcf, cg_iters=self.cg_iters)
+        aty0 = torch.as_tensor(data["ATy0"])[..., 0] if "ATy0" in data else None
+        return OrderedDict({"x": x, "y0": y0, "z": z, "u": u, "mask": None, "gt": gt, "ATy0": aty0,
+                            "T": torch.zeros(n, dtype=torch.float32, device=device),
+                            "complex_y0": data["y0"], "_episode": eng.live_episode, "sens": None, "traj": traj, "dcf": dcf,
+                            "omega": omega, "times": times, "segments": seg})
+
     def _bind_episode(self, eng: PnPEngine, states) -> None:
         """Make the engine's k-space constants those of `states` (env.py:88-90 reads y0 / mask from the dict)."""
         ep = states.get("_episode", 0)
         if states.get("traj") is not None and not eng.nufft_planned(states["traj"], self.nufft_grid, self.nufft_width):
             eng.nufft_plan(states["traj"], grid=self.nufft_grid, width=self.nufft_width)      # (drops the live episode)
+        if states.get("omega") is not None and not eng.offres_planned(states["times"], int(states["segments"])):
+            eng.offres_plan(states["times"], int(states["segments"]))                         # (drops a live off-resonance episode)
         if ep and ep == eng.live_episode:
             return
         if not ep:                              # a state dict built by hand the reference's way
@@ -148,6 +188,10 @@ class PnPEnv:
             tz = self.nc_normal == "toeplitz"   # (the engine re-plans the spectrum when the plan or the episode's weights changed)
             y = states["y0"]
             y = y if y.is_complex() else _as_complex(y)
+            if states.get("omega") is not None:  # an off-resonance episode
+                eng.set_kspace_offres(y.reshape(n, -1).to(eng.device).contiguous(), states["omega"], states.get("dcf"), episode=ep,
+                                      cg_iters=self.cg_iters)
+                return
             if states.get("sens") is not None:  # a non-Cartesian SENSE episode
                 sens = states["sens"]
                 y = y.reshape(n, sens.shape[-3], -1).to(eng.device).contiguous()

@@ -151,6 +151,65 @@ def make_problem_nc(n: int, h: int, w: int, traj: np.ndarray, dcf: np.ndarray = 
     return {"x0": x0, "y0": y0, "ATy0": aty0, "gt": gt, "x0_raw": aty0[..., 0].copy(), "traj": traj, "dcf": d}
 
 
+def field_map(h: int, w: int, max_hz: float, seed: int = 0) -> np.ndarray:
+    """float64 [h,w] in Hz: a smooth main-field inhomogeneity map, a second-order polynomial plus one Gaussian lobe (an air-tissue
+    interface), scaled so that max |f| = max_hz.  Multiply by 2 pi for the rad/s of include/pnpadmm_offres.h."""
+    u = hash_uniform(seed, 7101, 12).astype(np.float64)       # [-1, 1)
+    yy, xx = np.meshgrid((np.arange(h) + 0.5) / h * 2 - 1, (np.arange(w) + 0.5) / w * 2 - 1, indexing="ij")
+    f = u[0] * xx + u[1] * yy + u[2] * xx * yy + u[3] * (xx * xx - 0.5) + u[4] * (yy * yy - 0.5)
+    cx, cy, s = 0.6 * u[5], 0.6 * u[6], 0.25 + 0.1 * (u[7] + 1.0)
+    f = f + (1.5 if u[8] >= 0 else -1.5) * np.exp(-((xx - cx) ** 2 + (yy - cy) ** 2) / (2.0 * s * s))
+    return f * (float(max_hz) / max(float(np.abs(f).max()), 1e-30))
+
+
+def offres_ndft_np(traj: np.ndarray, times: np.ndarray, omega: np.ndarray, x: np.ndarray, adjoint_shape=None) -> np.ndarray:
+    """`ndft_np` under a field map, exact in float64: (A x)_m = (1 / sqrt(h w)) sum_q x[q] exp(-i omega[q] t_m) exp(-2 pi i k_m . q); with
+    adjoint_shape = (h, w): A^H.  x [h,w] -> [M] (or [M] -> [h,w]): one slice; omega [h,w] rad/s, times [M] s.  O(M h w)."""
+    traj = np.asarray(traj, dtype=np.float64)
+    t = np.asarray(times, dtype=np.float64).reshape(-1)
+    om = np.asarray(omega, dtype=np.float64)
+    h, w = om.shape
+    sgn = 1.0 if adjoint_shape is not None else -1.0
+    ey = np.exp(sgn * 2j * math.pi * traj[:, 0:1] * (np.arange(h) - h // 2))
+    ex = np.exp(sgn * 2j * math.pi * traj[:, 1:2] * (np.arange(w) - w // 2))
+    x = np.asarray(x, dtype=np.complex128)
+    out = np.zeros((h, w), dtype=np.complex128) if adjoint_shape is not None else np.empty(t.size, dtype=np.complex128)
+    for m0 in range(0, t.size, 256):
+        sl = slice(m0, m0 + 256)
+        ph = np.exp(sgn * 1j * om[None] * t[sl, None, None])
+        if adjoint_shape is not None:
+            out += np.einsum("my,m,mx,myx->yx", ey[sl], x[sl], ex[sl], ph, optimize=True)
+        else:
+            out[sl] = np.einsum("my,myx,mx->m", ey[sl], ph * x[None], ex[sl], optimize=True)
+    return out / math.sqrt(h * w)
+
+
+def make_problem_ncb0(n: int, h: int, w: int, traj: np.ndarray, times: np.ndarray, omega: np.ndarray, dcf: np.ndarray = None,
+                      sigma_n: float = 10.0 / 255.0, seed: int = 1234, first_slice: int = 0) -> Dict[str, np.ndarray]:
+    """`make_problem_nc` under main-field inhomogeneity, by the exact operator in float64 (small sizes): y = A_exact gt + noise with the
+    sample times `times` float64 [M] (seconds) and the field map `omega` float32 [h,w] (shared) or [n,h,w] in rad/s; ATy0 = A_exact^H (dcf y).
+    The dict carries `omega` and `times` beside `traj` and `dcf`."""
+    traj = np.asarray(traj, dtype=np.float64)
+    t = np.asarray(times, dtype=np.float64).reshape(-1)
+    m = traj.shape[0]
+    om = np.asarray(omega, dtype=np.float32)
+    d = None if dcf is None else np.asarray(dcf, dtype=np.float32)
+    gt = np.empty((n, 1, h, w), dtype=np.float32)
+    y0 = np.empty((n, 1, m, 2), dtype=np.float32)
+    aty0 = np.empty((n, 1, h, w, 2), dtype=np.float32)
+    for i in range(n):
+        s = seed + first_slice + i
+        g = phantom(h, w, s)
+        oi = om if om.ndim == 2 else om[i]
+        y = offres_ndft_np(traj, t, oi, g) + (_gauss(s, 9001, m) + 1j * _gauss(s, 9003, m)) * sigma_n
+        a = offres_ndft_np(traj, t, oi, y if d is None else y * d.astype(np.float64), adjoint_shape=(h, w))
+        gt[i, 0] = g
+        y0[i, 0, :, 0], y0[i, 0, :, 1] = y.real, y.imag
+        aty0[i, 0, ..., 0], aty0[i, 0, ..., 1] = a.real, a.imag
+    x0 = np.clip(aty0, 0.0, None)
+    return {"x0": x0, "y0": y0, "ATy0": aty0, "gt": gt, "x0_raw": aty0[..., 0].copy(), "traj": traj, "dcf": d, "omega": om, "times": t}
+
+
 def param_table(n: int, iters: int, seed: int = 77):
     """Seeded per-slice (mu_t, sigma_t) schedule standing in for DT-chosen parameters at
     sizes the 128x128-only policy cannot see: mu in (0.05,0.6), sigma_d
