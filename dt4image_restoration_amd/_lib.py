@@ -165,6 +165,14 @@ SIGNATURES_OFFRES = {
     "pnp_acquire_offres": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, C.c_double, C.c_uint64, C.c_int, _fp, _fp, _fp, _vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/pnpadmm_fieldmap.h declares (the B0 field map from two echo images)
+SIGNATURES_FIELDMAP = {
+    "pnp_fieldmap_estimate": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_double, C.c_float, C.c_int, C.c_int, _fp, _fp, _vp]),
+    "pnp_fieldmap_cost": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_double, C.c_float, _fp, _fp, _vp]),
+}
+PNP_FIELDMAP_MAX_ITERS = 4096
+PNP_FIELDMAP_T = 10          # sweeps per launch of the fused kernel
+
 
 def toeplitz_size_error(fn: str, h: int, w: int):
     """The library's refusal of a slice too large for the Toeplitz operator, word for word (pnp_capi.hip: tz_check_sizes), or None: for a
@@ -189,7 +197,8 @@ def load() -> C.CDLL:
         raise PnPError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        f"or `make -C {os.path.dirname(LIB_PATH)}`; there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE, **SIGNATURES_TOEPLITZ, **SIGNATURES_DCF, **SIGNATURES_OFFRES}.items():
+    for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE, **SIGNATURES_TOEPLITZ, **SIGNATURES_DCF, **SIGNATURES_OFFRES,
+                              **SIGNATURES_FIELDMAP}.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

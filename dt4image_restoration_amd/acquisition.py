@@ -259,6 +259,65 @@ def pipe_dcf(engine_or_env, traj, iters: int = 30, width: int = 6, grid=None) ->
     return eng.nufft_dcf(iters=iters)
 
 
+FIELD_MAP_STREAM = 9601      # hash streams of the field map scan's noise: 9601 + 8 c + 4 e (+ 0, 1 real; + 2, 3 imaginary), coil c, echo e
+
+
+def field_map_dte(omega_max: float, margin: float = 0.8) -> float:
+    """The largest echo spacing dte (seconds) with omega_max * dte <= margin * pi: the two-echo field map estimate has no phase
+    unwrapping, so it is valid only while |omega| dte < pi (include/pnpadmm_fieldmap.h); omega_max in rad/s, 0 < margin < 1."""
+    omega_max, margin = abs(float(omega_max)), float(margin)
+    if not (math.isfinite(omega_max) and omega_max > 0.0 and 0.0 < margin < 1.0):
+        raise ValueError(f"field_map_dte: need finite omega_max > 0 and 0 < margin < 1, got {omega_max}, {margin}")
+    return margin * math.pi / omega_max
+
+
+def field_map_scan(gt, omega, te: float, dte: float, sigma_n: float, seed: int, sens=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The two echo images of a field map scan, complex64 [N,C,H,W] on the host (C = 1 without sens):
+        x_e = S_c gt exp(-i omega te_e) + sigma_n (g_re + i g_im),   te_1 = te, te_2 = te + dte
+    with the sign of include/pnpadmm_offres.h and readouts short enough that the blur is neglected.  gt [N,H,W] or [N,1,H,W]; omega rad/s
+    [H,W] or [N,H,W]; sens complex [C,H,W] or None.  Slice i draws its noise from the `synthetic` counter hash at seed + i on the streams
+    FIELD_MAP_STREAM + 8 c + 4 e, so a slice's scan does not depend on the batch it is in."""
+    g = torch.as_tensor(gt).detach().cpu().numpy().astype(np.float64)
+    if g.ndim == 4 and g.shape[1] == 1:
+        g = g[:, 0]
+    if g.ndim != 3:
+        raise ValueError(f"field_map_scan: gt must be [N,H,W] or [N,1,H,W], got {g.shape}")
+    n, h, w = g.shape
+    om = torch.as_tensor(omega).detach().cpu().numpy().astype(np.float64)
+    if om.shape not in ((h, w), (n, h, w)):
+        raise ValueError(f"field_map_scan: omega must be [{h},{w}] or [{n},{h},{w}], got {om.shape}")
+    om = np.broadcast_to(om, (n, h, w))
+    te, dte, sigma_n = float(te), float(dte), float(sigma_n)
+    if not (math.isfinite(te) and te >= 0.0 and math.isfinite(dte) and dte > 0.0 and math.isfinite(sigma_n) and sigma_n >= 0.0):
+        raise ValueError(f"field_map_scan: need te >= 0, dte > 0 and sigma_n >= 0, all finite, got {te}, {dte}, {sigma_n}")
+    s = np.ones((1, h, w), dtype=np.complex128) if sens is None else torch.as_tensor(sens).detach().cpu().numpy().astype(np.complex128)
+    if s.ndim != 3 or s.shape[1:] != (h, w) or not 1 <= s.shape[0] <= _lib.PNP_MC_MAX_COILS:
+        raise ValueError(f"field_map_scan: sens must be [C,{h},{w}] with C = 1..{_lib.PNP_MC_MAX_COILS}, got {s.shape}")
+    out = []
+    for e, t in enumerate((te, te + dte)):
+        x = np.empty((n, s.shape[0], h, w), dtype=np.complex64)
+        for i in range(n):
+            for c in range(s.shape[0]):
+                st = FIELD_MAP_STREAM + 8 * c + 4 * e
+                noise = (synthetic._gauss(int(seed) + i, st, h * w) + 1j * synthetic._gauss(int(seed) + i, st + 2, h * w)).reshape(h, w)
+                x[i, c] = s[c] * g[i] * np.exp(-1j * om[i] * t) + sigma_n * noise
+        out.append(x)
+    return out[0], out[1]
+
+
+def estimate_field_map(engine_or_env, x1, x2, dte: float, beta: float = 0.05, iters: int = 200) -> torch.Tensor:
+    """float32 [N,H,W] rad/s on the engine's device: the field map of the echo images x1, x2 (complex64 [N,C,H,W], `field_map_scan`'s or a
+    scanner's) by the regularised two-echo fit on the device (pnp_fieldmap_estimate, include/pnpadmm_fieldmap.h).  No phase unwrapping: valid
+    for |omega| dte < pi (`field_map_dte`).  engine_or_env: a PnPEngine, or a PnPEnv that holds one (the handle of its latest reset or
+    `simulate`)."""
+    eng = engine_or_env if hasattr(engine_or_env, "fieldmap_estimate") else getattr(engine_or_env, "_engine", None)
+    if eng is None or not hasattr(eng, "fieldmap_estimate"):
+        raise TypeError(f"estimate_field_map: expected a PnPEngine, or a PnPEnv that holds one, got {type(engine_or_env).__name__}")
+    a = torch.as_tensor(x1).to(eng.device, torch.complex64).contiguous()
+    b = torch.as_tensor(x2).to(eng.device, torch.complex64).contiguous()
+    return eng.fieldmap_estimate(a, b, float(dte), beta=float(beta), iters=int(iters))
+
+
 def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, width: int, grid, sens=None, omega=None, times=None,
                  segments=None) -> Dict[str, torch.Tensor]:
     t = np.ascontiguousarray(traj.detach().cpu().numpy() if isinstance(traj, torch.Tensor) else traj, dtype=np.float64)
@@ -696,8 +755,9 @@ def make_mask(h: int, w: int, accel: float, kind: str = "radial", seed: int = 0)
 
 
 def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int = 0, mask_kind: str = "radial",
-                 mask=None, coils: int = 0, noise_cov=None, spokes: int = None, nc_weights: str = "dcf", nufft_width: int = 6,
-                 b0_hz: float = None, readout_ms: float = None, b0_segments="auto",
+                 mask=None, coils: int = 0, noise_cov=None, spokes: int = None, nc_weights: str = "dcf",
+                 b0_map: str = "true", b0_dte_ms: float = None, b0_beta: float = 0.05, b0_iters: int = 200, b0_scan_noise: float = None,
+                 nufft_width: int = 6, b0_hz: float = None, readout_ms: float = None, b0_segments="auto",
                  nufft_grid=None, interleaves: int = None, petals: int = None, dcf_iters: int = 30) -> Dict[str, torch.Tensor]:
     """`simulate` for a named task: '4x_10' = acceleration 4, sigma_n = 10 / 255.  mask: a ready mask, or None for
     `make_mask(h, w, accel, mask_kind, seed)` (the same for every shard of a job).  coils > 0: a multi-coil acquisition with the
@@ -711,8 +771,17 @@ def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int =
     b0_hz (with a non-Cartesian mask_kind, single-coil): the acquisition under main-field inhomogeneity - the smooth map
     `synthetic.field_map(h, w, b0_hz, seed)` shared by the slices, every readout (spoke, interleaf, shot) `readout_ms` long
     (`readout_times`), by the time-segmented operator with `b0_segments` segments ("auto": `simulate`'s rule); the dict then carries
-    `omega`, `times` and `segments`, and `PnPEnv.reset` installs the off-resonance stage."""
+    `omega`, `times` and `segments`, and `PnPEnv.reset` installs the off-resonance stage.
+    b0_map (with b0_hz): "true" hands the solver the map that made the data; "estimate" does what a scanner does: it simulates a two-echo
+    field map scan of the task's own ground truth under the true map (`field_map_scan`: echo spacing `b0_dte_ms`, None for
+    `field_map_dte(2 pi b0_hz)`; image noise `b0_scan_noise`, None for the task's sigma_n), estimates the map on the device
+    (`estimate_field_map` with `b0_beta`, `b0_iters`: no phase unwrapping, so b0_hz * b0_dte_ms must stay below 500) and installs the
+    estimate, float32 [N,H,W], as `omega`; the truth stays under `omega_true`.  The data y are the true map's either way."""
     accel, sigma_n = parse_task(task)
+    if b0_map not in ("true", "estimate"):
+        raise ValueError(f"task_problem: b0_map must be 'true' or 'estimate', got {b0_map!r}")
+    if b0_map == "estimate" and b0_hz is None:
+        raise ValueError("task_problem: b0_map='estimate' needs b0_hz (a field map to estimate)")
     h, w = (int(v) for v in torch.as_tensor(gt).shape[-2:])
     if mask_kind in NC_KINDS:
         if noise_cov is not None or mask is not None:
@@ -752,8 +821,27 @@ def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int =
             readout = m
         times = readout_times(mask_kind[:-3], m, readout, float(readout_ms) * 1e-3)
         omega = (2.0 * math.pi * synthetic.field_map(h, w, float(b0_hz), seed)).astype(np.float32)
-        return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, traj=traj, dcf=dcf, nufft_width=nufft_width, nufft_grid=nufft_grid,
-                        omega=omega, times=times, segments=b0_segments)
+        if b0_map == "true":
+            return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, traj=traj, dcf=dcf, nufft_width=nufft_width,
+                            nufft_grid=nufft_grid, omega=omega, times=times, segments=b0_segments)
+        dte = field_map_dte(2.0 * math.pi * max(float(b0_hz), 1.0)) if b0_dte_ms is None else float(b0_dte_ms) * 1e-3
+        noise = sigma_n if b0_scan_noise is None else float(b0_scan_noise)
+        if not (math.isfinite(dte) and dte > 0.0 and math.isfinite(noise) and noise >= 0.0 and math.isfinite(b0_beta) and b0_beta > 0.0
+                and 0 <= int(b0_iters) <= _lib.PNP_FIELDMAP_MAX_ITERS):
+            raise ValueError(f"task_problem: b0_map='estimate' needs b0_dte_ms > 0, b0_scan_noise >= 0, b0_beta > 0 and b0_iters in "
+                             f"0..{_lib.PNP_FIELDMAP_MAX_ITERS}, got {b0_dte_ms}, {b0_scan_noise}, {b0_beta}, {b0_iters}")
+        if 2.0 * math.pi * float(b0_hz) * dte >= math.pi:
+            raise ValueError(f"task_problem: the two-echo estimate has no phase unwrapping: b0_hz * b0_dte_ms must stay below 500, got "
+                             f"{b0_hz} * {dte * 1e3:g}")
+        out = simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, traj=traj, dcf=dcf, nufft_width=nufft_width, nufft_grid=nufft_grid,
+                       omega=omega, times=times, segments=b0_segments)
+        g = torch.as_tensor(gt)
+        eng = engine_or_env if hasattr(engine_or_env, "acquire") else None
+        device = eng.device if eng is not None else torch.device("cuda", torch.cuda.current_device())
+        x1, x2 = field_map_scan(g.reshape(-1, h, w), omega, 0.0, dte, noise, int(seed) + int(first_slice))
+        out["omega_true"] = torch.as_tensor(out.get("omega", omega))
+        out["omega"] = estimate_field_map(_engine(engine_or_env, g.numel() // (h * w), h, w, device), x1, x2, dte, beta=b0_beta, iters=b0_iters)
+        return out
     if b0_hz is not None or readout_ms is not None:
         raise ValueError("task_problem: b0_hz and readout_ms need a non-Cartesian mask_kind (radial-nc, spiral-nc, rosette-nc)")
     if mask is None:

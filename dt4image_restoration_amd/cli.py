@@ -218,6 +218,9 @@ def _nc_kwargs(args):
               nufft_grid=args.nufft_grid, coils=args.nc_coils, interleaves=args.interleaves, petals=args.petals, dcf_iters=args.dcf_iters)
     if args.b0 is not None:                                  # --b0: the acquisition under a field map and the off-resonance stage
         kw.update(b0_hz=args.b0, readout_ms=args.readout_ms, b0_segments=args.b0_segments)
+        if getattr(args, "b0_map", "true") != "true":        # --b0-map estimate: the solver gets a map estimated from a two-echo scan
+            kw.update(b0_map=args.b0_map, b0_dte_ms=args.b0_dte, b0_beta=0.05 if args.b0_beta is None else args.b0_beta,
+                      b0_iters=200 if args.b0_iters is None else args.b0_iters)
     return kw
 
 
@@ -399,6 +402,14 @@ def main(argv=None):
     ap.add_argument("--readout-ms", type=float, default=None, metavar="T", help="--b0: the length of every readout (spoke, interleaf, shot) in ms")
     ap.add_argument("--b0-segments", default="auto", metavar="L|auto", help="--b0: time segments, 1..32, or auto: the smallest count whose "
                     "interpolation error stays within 1e-3, at most 32")
+    ap.add_argument("--b0-map", choices=("true", "estimate"), default="true", help="--b0: the field map the solver is given: the map that made "
+                    "the data, or one estimated on the device from a simulated two-echo scan of the same object (regularised fit, no phase "
+                    "unwrapping)")
+    ap.add_argument("--b0-dte", type=float, default=None, metavar="MS", help="--b0-map estimate: echo spacing of the field map scan in ms "
+                    "(default: the largest with 2 pi HZ dte <= 0.8 pi); HZ * MS must stay below 500")
+    ap.add_argument("--b0-beta", type=float, default=None, metavar="B", help="--b0-map estimate: roughness weight of the fit (default 0.05)")
+    ap.add_argument("--b0-iters", type=int, default=None, metavar="K", help="--b0-map estimate: sweeps of the fit, 0..4096 (default 200; 0: the "
+                    "raw phase difference)")
     ap.add_argument("--sens", choices=("true", "estimate", "espirit"), default="true", help="coil maps of a --coils run: the analytic maps that "
                     "generated the measurements, or maps estimated on the device from the calibration block of each set's own y0 (estimate: "
                     "the low-resolution estimate; espirit: ESPIRiT, at most 16 coils)")
@@ -517,6 +528,21 @@ def main(argv=None):
         raise SystemExit("--dcf-iters needs --traj")
     elif args.b0 is not None or args.readout_ms is not None or args.b0_segments != "auto":
         raise SystemExit("--b0 / --readout-ms / --b0-segments need --traj")
+    if args.b0 is None:
+        if args.b0_map != "true" or args.b0_dte is not None or args.b0_beta is not None or args.b0_iters is not None:
+            raise SystemExit("--b0-map / --b0-dte / --b0-beta / --b0-iters need --b0")
+    elif args.b0_map == "true":
+        if args.b0_dte is not None or args.b0_beta is not None or args.b0_iters is not None:
+            raise SystemExit("--b0-dte / --b0-beta / --b0-iters need --b0-map estimate")
+    else:
+        if args.b0_dte is not None and not (np.isfinite(args.b0_dte) and args.b0_dte > 0.0):
+            raise SystemExit(f"--b0-dte must be finite and > 0, got {args.b0_dte}")
+        if args.b0_dte is not None and args.b0 * args.b0_dte >= 500.0:
+            raise SystemExit(f"--b0-map estimate has no phase unwrapping: --b0 times --b0-dte must stay below 500, got {args.b0} * {args.b0_dte}")
+        if args.b0_beta is not None and not (np.isfinite(args.b0_beta) and args.b0_beta > 0.0):
+            raise SystemExit(f"--b0-beta must be finite and > 0, got {args.b0_beta}")
+        if args.b0_iters is not None and not 0 <= args.b0_iters <= 4096:
+            raise SystemExit(f"--b0-iters must be 0..4096, got {args.b0_iters}")
     if args.prior == "tv":
         if not (args.tv_scale >= 0.0 and np.isfinite(args.tv_scale)):
             raise SystemExit(f"--tv-scale must be finite and >= 0, got {args.tv_scale}")

@@ -799,6 +799,7 @@ Tuning tuning_from_env() {
     if (const char* v = getenv("PNP_TOEPLITZ_NAIVE")) t.toeplitz_naive = atoi(v) != 0;
     if (const char* v = getenv("PNP_OFFRES_SEG_BLOCK")) t.offres_block = atoi(v);
     if (const char* v = getenv("PNP_OFFRES_GRID_FILTER")) t.offres_grid_filter = atoi(v) != 0;
+    if (const char* v = getenv("PNP_FIELDMAP_NAIVE")) t.fieldmap_naive = atoi(v) != 0;
     if (const char* v = getenv("PNP_OFFRES_NAIVE")) t.offres_naive = atoi(v) != 0 ? 1 : 0;
     return t;
 }

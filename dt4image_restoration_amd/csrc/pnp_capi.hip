@@ -5,6 +5,7 @@
 #include "../../include/pnpadmm_toeplitz.h"
 #include "../../include/pnpadmm_dcf.h"
 #include "../../include/pnpadmm_offres.h"
+#include "../../include/pnpadmm_fieldmap.h"
 #include "pnp_internal.h"
 #include "denoiser_plan.h"
 #include "nufft_plan.h"
@@ -203,6 +204,9 @@ struct pnp_engine {
     int haar_levels = 3;
     int haar_mode = PNP_HAAR_TI;
     float* haar_ws = nullptr;    // naive form only, allocated inside its first TI call: kHaarNaivePlanes planes [N,H,W] (a_1 .. a_3, two of r_j)
+    // field map estimation (include/pnpadmm_fieldmap.h): its own workspace, allocated inside the first call that runs it
+    float* fm_ws = nullptr;      // five planes [N,H,W]: phi, w, rd and the two of theta; then [N, pixel_chunks] workgroup maxima
+    double* fm_part = nullptr;   // [N, pixel_chunks] chunk sums of the cost
     // profiling
     std::vector<EventPair> events;
     size_t ev_used = 0;
@@ -1213,6 +1217,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->gr_ws);
     (void)hipFree(e->tv_p);
     (void)hipFree(e->haar_ws);
+    (void)hipFree(e->fm_ws); (void)hipFree(e->fm_part);
     (void)hipFree(e->nc.i0); (void)hipFree(e->nc.wts); (void)hipFree(e->nc.cy); (void)hipFree(e->nc.cx); (void)hipFree(e->nc.bin_off); (void)hipFree(e->nc.bin_idx);
     (void)hipFree(e->nc.tw_gh); (void)hipFree(e->nc.tw_gw);
     (void)hipFree(e->ns_img);
@@ -2455,6 +2460,102 @@ int pnp_nufft_dcf(pnp_handle e, const float* w0, int iters, int flags, float* w,
     p.end(2 * iters + (info ? 2 : 0) + 2);
     return PNP_OK;
     PNP_API_END("pnp_nufft_dcf")
+}
+
+// ---- field map estimation (include/pnpadmm_fieldmap.h) --------------------------------------------------
+namespace {
+
+static_assert(PNP_FIELDMAP_T == kFmT, "the header's sweeps per launch are the kernels'");
+
+// the feature's own workspace, never replaced: the five planes and the workgroup maxima in one buffer, the cost's chunk sums in another
+int fm_ensure(pnp_engine* e) {
+    const size_t px = (size_t)e->cfg.n * e->cfg.h * e->cfg.w, chunks = (size_t)e->cfg.n * pixel_chunks(e->cfg.h, e->cfg.w);
+    return ws_grow(e, "field map workspace", {{(void**)&e->fm_ws, nullptr, e->fm_ws ? 0 : (5 * px + chunks) * sizeof(float), false},
+                                              {(void**)&e->fm_part, nullptr, e->fm_part ? 0 : chunks * sizeof(double), false}});
+}
+
+// every argument error of the two entry points, before any HIP call
+int fm_check(const char* fn, const pnp_engine* e, const float* x1, const float* x2, int coils, double dte, float beta, bool omega_in,
+             const float* omega, const void* out, const char* out_name) {
+    if (coils < 1 || coils > PNP_MC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_MC_MAX_COILS, coils);
+    if (!(dte > 0.0) || !std::isfinite(dte)) return fail(PNP_ERR_INVALID, "%s: dte must be finite and > 0 (got %g)", fn, dte);
+    if (!(beta > 0.0f) || !std::isfinite(beta)) return fail(PNP_ERR_INVALID, "%s: beta must be finite and > 0 (got %g)", fn, (double)beta);
+    if (!x1) return fail(PNP_ERR_INVALID, "%s: null x1", fn);
+    if (!x2) return fail(PNP_ERR_INVALID, "%s: null x2", fn);
+    if (omega_in && !omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null %s", fn, out_name);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if ((long long)e->cfg.n > 65535) return fail(PNP_ERR_INVALID, "%s: n must be <= 65535 (got %d)", fn, e->cfg.n);
+    return PNP_OK;
+}
+
+// the planes of the workspace, and phi, w, rd, theta^0 of (x1, x2) in them: two launches
+int fm_prepare(pnp_engine* e, FmArgs& a, float* (&th)[2], const float* x1, const float* x2, int coils, double dte, float beta, float* weight,
+               hipStream_t s) {
+    const size_t px = (size_t)e->cfg.n * e->cfg.h * e->cfg.w;
+    a.x1 = (const float2*)x1; a.x2 = (const float2*)x2; a.C = coils; a.dte = dte; a.beta = beta; a.H = e->cfg.h; a.W = e->cfg.w;
+    a.phi = e->fm_ws; a.w = e->fm_ws + px; a.rd = e->fm_ws + 2 * px;
+    th[0] = e->fm_ws + 3 * px; th[1] = e->fm_ws + 4 * px;
+    a.maxpart = e->fm_ws + 5 * px;
+    a.part = e->fm_part;
+    a.weight = weight;
+    a.th_out = th[0];
+    HIP_TRY(launch_fm_prepare(a, e->cfg.n, s));
+    return PNP_OK;
+}
+
+}  // namespace
+
+int pnp_fieldmap_estimate(pnp_handle e, const float* x1, const float* x2, int coils, double dte, float beta, int iters, int flags, float* omega,
+                          float* weight, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_fieldmap_estimate";
+    if (iters < 0 || iters > PNP_FIELDMAP_MAX_ITERS) return fail(PNP_ERR_INVALID, "%s: iters must be 0..%d (got %d)", fn, PNP_FIELDMAP_MAX_ITERS, iters);
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (int rc = fm_check(fn, e, x1, x2, coils, dte, beta, false, nullptr, omega, "omega")) return rc;
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    const int N = e->cfg.n;
+    FmArgs a{};
+    float* th[2];
+    if (int rc = fm_ensure(e)) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
+    if (int rc = fm_prepare(e, a, th, x1, x2, coils, dte, beta, weight, s)) return rc;
+    const bool naive = e->tune.fieldmap_naive;
+    const int L = naive ? iters : (iters + kFmT - 1) / kFmT;
+    for (int l = 0; l < L; ++l) {                            // theta ping-pongs through the two planes; no launch writes the plane it reads
+        a.th_in = th[l & 1];
+        a.th_out = th[(l + 1) & 1];
+        if (naive) { HIP_TRY(launch_fm_sweep(a, N, s)); continue; }
+        a.iters = iters - l * kFmT < kFmT ? iters - l * kFmT : kFmT;
+        HIP_TRY(launch_fm_fused(a, N, s));
+    }
+    a.th_in = th[L & 1];
+    a.omega_out = omega;
+    HIP_TRY(launch_fm_finish(a, N, s));
+    p.end(L + 3);
+    return PNP_OK;
+    PNP_API_END("pnp_fieldmap_estimate")
+}
+
+int pnp_fieldmap_cost(pnp_handle e, const float* x1, const float* x2, int coils, double dte, float beta, const float* omega, double* cost,
+                      void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_fieldmap_cost";
+    if (int rc = fm_check(fn, e, x1, x2, coils, dte, beta, true, omega, cost, "cost")) return rc;
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    FmArgs a{};
+    float* th[2];
+    if (int rc = fm_ensure(e)) return rc;
+    Prof p(e, s, PROF_OTHER, -1);
+    if (int rc = fm_prepare(e, a, th, x1, x2, coils, dte, beta, nullptr, s)) return rc;
+    a.omega_in = omega;
+    a.cost = cost;
+    HIP_TRY(launch_fm_cost(a, e->cfg.n, s));
+    p.end(4);
+    return PNP_OK;
+    PNP_API_END("pnp_fieldmap_cost")
 }
 
 int pnp_estimate_sens(pnp_handle e, const float* y0, int coils, int acs_h, int acs_w, int window, double thresh, int flags, float* sens,

@@ -43,6 +43,7 @@ struct Tuning {
     int offres_block = 0;         // PNP_OFFRES_SEG_BLOCK (tests, timing): segments per block of the off-resonance operator, 1..32 (else: kOffresBlock)
     bool offres_grid_filter = false;   // PNP_OFFRES_GRID_FILTER (timing): the two-segment gridding filters the tile's whole bin per segment
                                   // instead of walking the plan's per-(segment, tile) list; the same numbers
+    bool fieldmap_naive = false;  // PNP_FIELDMAP_NAIVE (tests, timing): the field map fit as one launch per sweep instead of the fused kernel
     int offres_naive = -1;        // PNP_OFFRES_NAIVE (tests, timing): 1 = the operator composed from the non-Cartesian SENSE launches and two sample
                                   // kernels, 0 = the two-segment gather and gridding; unset: kOffresNaiveSteps, the choice per step by measurement
 };
@@ -492,5 +493,35 @@ hipError_t launch_offres_expand(const float2* y, const OffresDev& R, const Nufft
 // filter: walk the NUFFT plan's whole tile bin per segment instead of the plan's per-(segment, tile) list (PNP_OFFRES_GRID_FILTER: timing)
 hipError_t launch_offres_grid(const float2* y, const float* w, const OffresDev& R, const NufftDev& P, float2* grid, int l0, int cb, int batch,
                               hipStream_t s, bool filter = false);
+
+// ---- field map estimation (fieldmap_kernels.hip; the fit: include/pnpadmm_fieldmap.h) ----------------------------
+// The fused kernel's plan: kFmT sweeps per launch over a kFmRegion^2 region, of which the kFmTile^2 tile is stored
+static constexpr int kFmT = 10, kFmRegion = 128, kFmTile = kFmRegion - 2 * kFmT;
+struct FmArgs {
+    const float2* x1;      // [N,C,H,W] the echo images (prepare)
+    const float2* x2;
+    int C;
+    float* phi;            // [N,H,W] planes of the workspace: prepare writes phi, w (m, then normalised by the weights kernel) and rd
+    float* w;
+    float* rd;
+    const float* th_in;    // [N,H,W] the iterate a sweep / the finish reads
+    float* th_out;         // [N,H,W] the iterate a sweep writes (never th_in); prepare: theta^0 = phi
+    float* maxpart;        // [N, pixel_chunks] workgroup maxima of m
+    float* weight;         // [N,H,W] the caller's copy of w, or nullptr
+    float* omega_out;      // [N,H,W] (finish)
+    const float* omega_in; // [N,H,W] (cost)
+    double* part;          // [N, pixel_chunks] chunk sums of the cost
+    double* cost;          // [N]
+    double dte;
+    float beta;
+    int H, W;
+    int iters;             // fused kernel: sweeps of this launch, 1..kFmT
+    int tiles_x, tiles_y;  // set by the launchers
+};
+hipError_t launch_fm_prepare(FmArgs a, int N, hipStream_t s);  // phi, w, rd, theta^0 (th_out), weight: two launches
+hipError_t launch_fm_fused(FmArgs a, int N, hipStream_t s);    // a.iters sweeps th_in -> th_out
+hipError_t launch_fm_sweep(FmArgs a, int N, hipStream_t s);    // ONE sweep th_in -> th_out, a thread per pixel
+hipError_t launch_fm_finish(FmArgs a, int N, hipStream_t s);   // omega_out = th_in / dte
+hipError_t launch_fm_cost(FmArgs a, int N, hipStream_t s);     // cost [N] = Psi at omega_in with the planes of launch_fm_prepare: two launches
 
 }  // namespace pnp

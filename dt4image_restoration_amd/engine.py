@@ -608,6 +608,39 @@ class PnPEngine:
                                                self._stream()), "pnp_acquire_offres")
         return y, aty0, x0
 
+    # -- field map estimation (include/pnpadmm_fieldmap.h) ----------------------------------
+    def _echoes(self, x1: torch.Tensor, x2: torch.Tensor) -> int:
+        """the coil count of two echo images complex64 [N,C,H,W] (or [N,H,W]: one coil)"""
+        per = self.n * self.h * self.w
+        if x1.numel() == 0 or x1.numel() % per or x1.numel() // per > _lib.PNP_MC_MAX_COILS:
+            raise ValueError(f"x1: expected [{self.n},C,{self.h},{self.w}] with C = 1..{_lib.PNP_MC_MAX_COILS}, got {tuple(x1.shape)}")
+        self._chk(x1, torch.complex64, x1.numel(), "x1")
+        self._chk(x2, torch.complex64, x1.numel(), "x2")
+        return x1.numel() // per
+
+    def fieldmap_estimate(self, x1: torch.Tensor, x2: torch.Tensor, dte: float, beta: float = 0.05, iters: int = 200,
+                          return_weight: bool = False):
+        """float32 [N,H,W] rad/s: the field map of two echo images x1, x2 (complex64 [N,C,H,W], taken `dte` seconds apart) by the regularised
+        fit of pnp_fieldmap_estimate - `iters` (0..4096) Jacobi sweeps of the separable quadratic surrogate at roughness weight `beta`;
+        iters = 0 is the raw phase difference.  No phase unwrapping: valid for |omega| dte < pi.  The result is what `reset_offres` takes as
+        its per-slice omega.  return_weight: (omega, weight) with the normalised magnitude weights float32 [N,H,W]."""
+        coils = self._echoes(x1, x2)
+        omega = torch.empty((self.n, self.h, self.w), dtype=torch.float32, device=self.device)
+        weight = torch.empty_like(omega) if return_weight else None
+        _lib.check(self.lib.pnp_fieldmap_estimate(self._h, x1.data_ptr(), x2.data_ptr(), coils, float(dte), float(beta), int(iters), 0,
+                                                  omega.data_ptr(), _ptr(weight), self._stream()), "pnp_fieldmap_estimate")
+        return (omega, weight) if return_weight else omega
+
+    def fieldmap_cost(self, x1: torch.Tensor, x2: torch.Tensor, dte: float, beta: float, omega: torch.Tensor) -> torch.Tensor:
+        """float64 [N]: the cost Psi of pnpadmm_fieldmap.h at omega (float32 [N,H,W] rad/s) for the echo images x1, x2: the reference-free
+        convergence figure of `fieldmap_estimate` (pnp_fieldmap_cost)."""
+        coils = self._echoes(x1, x2)
+        self._chk(omega, torch.float32, self.n * self.h * self.w, "omega")
+        cost = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.pnp_fieldmap_cost(self._h, x1.data_ptr(), x2.data_ptr(), coils, float(dte), float(beta), omega.data_ptr(),
+                                              cost.data_ptr(), self._stream()), "pnp_fieldmap_cost")
+        return cost
+
     # -- hot path --------------------------------------------------------------------------
     def _offres_for(self, times, segments) -> None:
         """the off-resonance plan of `reset` / `set_kspace` with omega: planned here when times are given and differ from the live plan's"""
