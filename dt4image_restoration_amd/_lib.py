@@ -165,6 +165,14 @@ SIGNATURES_OFFRES = {
     "pnp_acquire_offres": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, C.c_double, C.c_uint64, C.c_int, _fp, _fp, _fp, _vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/pnpadmm_offres_ls.h declares (the least-squares temporal interpolator)
+SIGNATURES_OFFRES_LS = {
+    "pnp_offres_plan_ls": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int]),
+    "pnp_offres_interpolator": (C.c_int, [C.c_void_p]),
+    "pnp_offres_ls_coeffs": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+OFFRES_INTERPOLATORS = {"linear": 1, "ls": 2}
+
 # name -> (restype, argtypes); every symbol include/pnpadmm_fieldmap.h declares (the B0 field map from two echo images)
 SIGNATURES_FIELDMAP = {
     "pnp_fieldmap_estimate": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_double, C.c_float, C.c_int, C.c_int, _fp, _fp, _vp]),
@@ -198,7 +206,7 @@ def load() -> C.CDLL:
                        f"or `make -C {os.path.dirname(LIB_PATH)}`; there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE, **SIGNATURES_TOEPLITZ, **SIGNATURES_DCF, **SIGNATURES_OFFRES,
-                              **SIGNATURES_FIELDMAP}.items():
+                              **SIGNATURES_OFFRES_LS, **SIGNATURES_FIELDMAP}.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -245,6 +245,86 @@ def offres_bound(omega_max: float, span: float, segments: int) -> float:
     return 1.0 - math.cos(min(abs(float(omega_max)) * float(span) / (int(segments) - 1) / 2.0, math.pi))
 
 
+OFFRES_LS_RIDGE = 1e-10                                      # kOffresLsRidge of csrc/offres_ls_plan.h
+
+
+def _sinc(x: np.ndarray) -> np.ndarray:
+    x = np.asarray(x, dtype=np.float64)
+    safe = np.where(x == 0.0, 1.0, x)
+    return np.where(x == 0.0, 1.0, np.sin(safe) / safe)
+
+
+def offres_ls_centres(times, segments: int) -> np.ndarray:
+    """float64 [L]: the segment centres of pnp_offres_plan / pnp_offres_plan_ls: t_min + l D, D = span / (L - 1); L = 1: the midpoint."""
+    t = np.asarray(times, dtype=np.float64).reshape(-1)
+    L, lo, hi = int(segments), float(t.min()), float(t.max())
+    if L == 1:
+        return np.array([0.5 * (lo + hi)])
+    return lo + np.arange(L, dtype=np.float64) * ((hi - lo) / (L - 1))
+
+
+def offres_ls_coeffs(times, segments: int, omega_max: float) -> np.ndarray:
+    """float64 [L, M]: the numpy statement of the least-squares temporal interpolator's plan (include/pnpadmm_offres_ls.h): b(t) = G^-1 r(t)
+    with G[l][l'] = sinc(omega_max (tau_l - tau_l')) + OFFRES_LS_RIDGE [l == l'], r_l(t) = sinc(omega_max (t - tau_l)), by a float64 Cholesky
+    factor of G.  L = 1: all ones.  The library stores float32(b); G is ill-conditioned by design, so two correct solvers may differ in b far
+    more than in the fit (`offres_ls_error` measures the fit)."""
+    t = np.asarray(times, dtype=np.float64).reshape(-1)
+    L, om = int(segments), float(omega_max)
+    if not 1 <= L <= OFFRES_MAX_SEGMENTS or t.size < 1 or not np.isfinite(t).all():
+        raise ValueError(f"offres_ls_coeffs: need 1 <= segments <= {OFFRES_MAX_SEGMENTS} and finite times, got {L}")
+    if L == 1:
+        return np.ones((1, t.size))
+    if not (math.isfinite(om) and om > 0.0 and t.max() > t.min()):
+        raise ValueError(f"offres_ls_coeffs: segments = {L} needs a finite omega_max > 0 and times of a positive span, got {omega_max}")
+    tau = offres_ls_centres(t, L)
+    G = _sinc(om * (tau[:, None] - tau[None, :])) + OFFRES_LS_RIDGE * np.eye(L)
+    C = np.linalg.cholesky(G)                                # raises LinAlgError on a failed pivot
+    r = _sinc(om * (t[None, :] - tau[:, None]))
+    z = np.linalg.solve(C, r)
+    return np.linalg.solve(C.T, z)
+
+
+def offres_ls_error(times, segments: int, omega_max: float, omega=None, coef=None) -> float:
+    """The worst model error max |exp(-i omega t) - sum_l b_l(t) exp(-i omega tau_l)| over the given times and over a frequency grid of
+    max(16 L + 1, 257) equispaced points across |omega| <= omega_max - or over the values of the field map `omega` (rad/s) when given.  The
+    coefficients are `coef` [L, M] (the device's own, say) or float32(offres_ls_coeffs): what the library multiplies with."""
+    t = np.asarray(times, dtype=np.float64).reshape(-1)
+    L = int(segments)
+    b = np.asarray(offres_ls_coeffs(t, L, omega_max) if coef is None else coef).astype(np.float32).astype(np.float64).reshape(L, t.size)
+    tau = offres_ls_centres(t, L)
+    if omega is None:
+        om = np.linspace(-abs(float(omega_max)), abs(float(omega_max)), max(16 * L + 1, 257))
+    else:
+        om = np.unique(np.asarray(torch.as_tensor(omega).detach().cpu().numpy(), dtype=np.float64).reshape(-1))
+    worst = 0.0
+    for k0 in range(0, om.size, 512):                        # [K, M] blocks: a 256 x 256 map has 65536 values
+        o = om[k0:k0 + 512]
+        fit = np.exp(-1j * o[:, None, None] * tau[None, :, None]) * b[None]
+        worst = max(worst, float(np.abs(np.exp(-1j * o[:, None] * t[None, :]) - fit.sum(axis=1)).max()))
+    return worst
+
+
+def offres_ls_segments(omega_max: float, span: float, tol: float = 1e-3) -> int:
+    """`offres_segments` for the least-squares interpolator: the smallest L whose `offres_ls_error` on 257 equispaced times across the span
+    is <= tol; 1 where there is nothing to correct.  A result above OFFRES_MAX_SEGMENTS is reported as it is (OFFRES_MAX_SEGMENTS + 1: "more
+    than the library takes" - the plan's float64 Cholesky factor is not established beyond)."""
+    omega_max, span = abs(float(omega_max)), float(span)
+    if not (math.isfinite(omega_max) and math.isfinite(span) and span >= 0.0 and 0.0 < tol < 1.0):
+        raise ValueError(f"offres_ls_segments: need finite omega_max, span >= 0 and 0 < tol < 1, got {omega_max}, {span}, {tol}")
+    if omega_max * span == 0.0:
+        return 1
+    t = np.linspace(0.0, span, 257)
+    for L in range(2, OFFRES_MAX_SEGMENTS + 1):
+        if L < omega_max * span / math.pi:                   # fewer centres than the band's Nyquist count: no fit to try
+            continue
+        try:
+            if offres_ls_error(t, L, omega_max) <= tol:
+                return L
+        except np.linalg.LinAlgError:
+            continue
+    return OFFRES_MAX_SEGMENTS + 1
+
+
 def pipe_dcf(engine_or_env, traj, iters: int = 30, width: int = 6, grid=None) -> torch.Tensor:
     """float32 [M] on the engine's device: density weights of ANY trajectory by Pipe and Menon's iteration w <- w / (Psi w) on the
     engine's own gridding kernel (pnp_nufft_dcf, include/pnpadmm_dcf.h), `iters` iterations from ones, scaled to sum h w as `radial_dcf`.
@@ -319,7 +399,7 @@ def estimate_field_map(engine_or_env, x1, x2, dte: float, beta: float = 0.05, it
 
 
 def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, width: int, grid, sens=None, omega=None, times=None,
-                 segments=None) -> Dict[str, torch.Tensor]:
+                 segments=None, interpolator: str = "linear", omega_max=None) -> Dict[str, torch.Tensor]:
     t = np.ascontiguousarray(traj.detach().cpu().numpy() if isinstance(traj, torch.Tensor) else traj, dtype=np.float64)
     eng.nufft_plan(t, grid=grid, width=width)
     d = None if dcf is None else torch.as_tensor(dcf).to(eng.device, torch.float32).contiguous()
@@ -328,15 +408,28 @@ def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, wid
         tm = np.ascontiguousarray(times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else times, dtype=np.float64).reshape(-1)
         om = torch.as_tensor(omega).to(eng.device, torch.float32).contiguous()
         L = segments
+        ls = interpolator == "ls"
+        if ls:                                               # the band of the least-squares fit: given, or the map's own
+            top = float(om.abs().max())
+            if omega_max is None:
+                omega_max = top * (1.0 + 1e-6)
+            elif top > float(omega_max):
+                raise ValueError(f"simulate: the field map reaches {top:g} rad/s, outside the band omega_max = {float(omega_max):g}")
         if L is None or L == "auto":
-            om_max, span = float(om.abs().max()), float(tm.max() - tm.min())
-            L = offres_segments(om_max, span)
+            om_max, span = float(omega_max) if ls else float(om.abs().max()), float(tm.max() - tm.min())
+            L = offres_ls_segments(om_max, span) if ls else offres_segments(om_max, span)
             if L > OFFRES_MAX_SEGMENTS:                      # the library's most: a larger model error, said aloud
                 import warnings
-                warnings.warn(f"simulate: tol = 1e-3 needs {L} time segments for omega_max span = {om_max * span:.3g} rad; using "
-                              f"{OFFRES_MAX_SEGMENTS} (model error {offres_bound(om_max, span, OFFRES_MAX_SEGMENTS):.2e} ||p||_1)")
+                err = offres_ls_error(tm, OFFRES_MAX_SEGMENTS, om_max) if ls else offres_bound(om_max, span, OFFRES_MAX_SEGMENTS)
+                warnings.warn(f"simulate: tol = 1e-3 needs {'more than ' if ls else ''}{L - 1 if ls else L} time segments for omega_max span = "
+                              f"{om_max * span:.3g} rad; using {OFFRES_MAX_SEGMENTS} (model error {err:.2e} ||p||_1)")
                 L = OFFRES_MAX_SEGMENTS
-        eng.offres_plan(tm, int(L))
+        if ls and int(L) > 1:
+            eng.offres_plan_ls(tm, int(L), float(omega_max))
+        elif ls:
+            eng.offres_plan_ls(tm, 1, 0.0)
+        else:
+            eng.offres_plan(tm, int(L))
         y, aty0, x0 = eng.acquire_offres(g, om, float(sigma_n), seed, dcf=d)
         y = y.reshape(eng.n, 1, -1)
     elif sens is not None:                                     # non-Cartesian SENSE: y [N,C,M]
@@ -353,11 +446,14 @@ def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, wid
         out["sens"] = sens
     if om is not None:
         out["omega"], out["times"], out["segments"] = om, torch.from_numpy(tm), int(L)
+        if interpolator == "ls":                             # (a linear acquisition's dict is the one it always was)
+            out["b0_interp"] = _lib.OFFRES_INTERPOLATORS["ls"]
     return out
 
 
 def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: int = 0, sens=None, noise_cov=None, traj=None, dcf=None,
-             nufft_width: int = 6, nufft_grid=None, omega=None, times=None, segments="auto") -> Dict[str, torch.Tensor]:
+             nufft_width: int = 6, nufft_grid=None, omega=None, times=None, segments="auto", interpolator: str = "linear",
+             omega_max=None) -> Dict[str, torch.Tensor]:
     """The collated `.mat` dict `PnPEnv.reset` reads, acquired on the device: x0, y0, ATy0 float32 [N,1,H,W,2] (real views of the
     complex outputs), mask bool [H,W] (or [N,H,W]), gt float32 [N,1,H,W], x0_raw = Re ATy0 [N,1,H,W]; every tensor on the GPU.
     gt: [N,H,W] or [N,1,H,W] in [0, 1] (array or tensor), mask: [H,W] or [N,H,W] in the centred layout.  Slice i draws the noise of
@@ -375,7 +471,16 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
     traj with omega (field map in rad/s, float32 [H,W] or [N,H,W]) and times (seconds, [M], e.g. `readout_times`): the acquisition under
     main-field inhomogeneity by the time-segmented operator (pnp_offres_plan + pnp_acquire_offres, include/pnpadmm_offres.h) with
     `segments` segments ("auto": `offres_segments` of max |omega| and the span of the times); single-coil only.  The dict carries `omega`,
-    `times` and `segments` beside `traj`."""
+    `times` and `segments` beside `traj`.  interpolator "ls": the least-squares temporal interpolator (pnp_offres_plan_ls,
+    include/pnpadmm_offres_ls.h) over |omega| <= omega_max (None: the map's max |omega| (1 + 1e-6); a map beyond a given omega_max is
+    refused), "auto" segments by `offres_ls_segments`; the dict then carries `b0_interp` = 2 (pnp_offres_interpolator's code: a dict of
+    numbers stays one)."""
+    if interpolator not in _lib.OFFRES_INTERPOLATORS:
+        raise ValueError(f"simulate: interpolator must be one of {sorted(_lib.OFFRES_INTERPOLATORS)}, got {interpolator!r}")
+    if (interpolator != "linear" or omega_max is not None) and omega is None:
+        raise ValueError("simulate: interpolator and omega_max go with omega")
+    if omega_max is not None and interpolator != "ls":
+        raise ValueError("simulate: omega_max goes with interpolator='ls'")
     if not torch.cuda.is_available():
         raise RuntimeError("simulate needs a ROCm GPU; the CPU route is synthetic.make_problem")
     g = torch.as_tensor(gt)
@@ -397,7 +502,7 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
         if omega is not None and sens is not None:
             raise ValueError("simulate: the off-resonance acquisition is single-coil (omega with sens is not supported)")
         return _simulate_nc(eng, g, traj, dcf, sigma_n, int(seed) + int(first_slice), nufft_width, nufft_grid, sens=sens, omega=omega,
-                            times=times, segments=segments)
+                            times=times, segments=segments, interpolator=interpolator, omega_max=omega_max)
     if omega is not None or times is not None:
         raise ValueError("simulate: omega and times need traj (a non-Cartesian acquisition)")
     m = torch.as_tensor(mask)
@@ -755,7 +860,7 @@ def make_mask(h: int, w: int, accel: float, kind: str = "radial", seed: int = 0)
 
 
 def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int = 0, mask_kind: str = "radial",
-                 mask=None, coils: int = 0, noise_cov=None, spokes: int = None, nc_weights: str = "dcf",
+                 mask=None, coils: int = 0, noise_cov=None, spokes: int = None, b0_interp: str = "linear", nc_weights: str = "dcf",
                  b0_map: str = "true", b0_dte_ms: float = None, b0_beta: float = 0.05, b0_iters: int = 200, b0_scan_noise: float = None,
                  nufft_width: int = 6, b0_hz: float = None, readout_ms: float = None, b0_segments="auto",
                  nufft_grid=None, interleaves: int = None, petals: int = None, dcf_iters: int = 30) -> Dict[str, torch.Tensor]:
@@ -776,8 +881,14 @@ def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int =
     field map scan of the task's own ground truth under the true map (`field_map_scan`: echo spacing `b0_dte_ms`, None for
     `field_map_dte(2 pi b0_hz)`; image noise `b0_scan_noise`, None for the task's sigma_n), estimates the map on the device
     (`estimate_field_map` with `b0_beta`, `b0_iters`: no phase unwrapping, so b0_hz * b0_dte_ms must stay below 500) and installs the
-    estimate, float32 [N,H,W], as `omega`; the truth stays under `omega_true`.  The data y are the true map's either way."""
+    estimate, float32 [N,H,W], as `omega`; the truth stays under `omega_true`.  The data y are the true map's either way.
+    b0_interp (with b0_hz): "linear", or "ls" for the least-squares temporal interpolator (`simulate(interpolator=)`)."""
     accel, sigma_n = parse_task(task)
+    if b0_interp not in _lib.OFFRES_INTERPOLATORS:
+        raise ValueError(f"task_problem: b0_interp must be one of {sorted(_lib.OFFRES_INTERPOLATORS)}, got {b0_interp!r}")
+    if b0_interp != "linear" and b0_hz is None:
+        raise ValueError("task_problem: b0_interp needs b0_hz (a field map to correct)")
+    interp = {} if b0_interp == "linear" else {"interpolator": b0_interp}      # the linear call is the call it always was
     if b0_map not in ("true", "estimate"):
         raise ValueError(f"task_problem: b0_map must be 'true' or 'estimate', got {b0_map!r}")
     if b0_map == "estimate" and b0_hz is None:
@@ -823,7 +934,7 @@ def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int =
         omega = (2.0 * math.pi * synthetic.field_map(h, w, float(b0_hz), seed)).astype(np.float32)
         if b0_map == "true":
             return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, traj=traj, dcf=dcf, nufft_width=nufft_width,
-                            nufft_grid=nufft_grid, omega=omega, times=times, segments=b0_segments)
+                            nufft_grid=nufft_grid, omega=omega, times=times, segments=b0_segments, **interp)
         dte = field_map_dte(2.0 * math.pi * max(float(b0_hz), 1.0)) if b0_dte_ms is None else float(b0_dte_ms) * 1e-3
         noise = sigma_n if b0_scan_noise is None else float(b0_scan_noise)
         if not (math.isfinite(dte) and dte > 0.0 and math.isfinite(noise) and noise >= 0.0 and math.isfinite(b0_beta) and b0_beta > 0.0
@@ -834,7 +945,7 @@ def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int =
             raise ValueError(f"task_problem: the two-echo estimate has no phase unwrapping: b0_hz * b0_dte_ms must stay below 500, got "
                              f"{b0_hz} * {dte * 1e3:g}")
         out = simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, traj=traj, dcf=dcf, nufft_width=nufft_width, nufft_grid=nufft_grid,
-                       omega=omega, times=times, segments=b0_segments)
+                       omega=omega, times=times, segments=b0_segments, **interp)
         g = torch.as_tensor(gt)
         eng = engine_or_env if hasattr(engine_or_env, "acquire") else None
         device = eng.device if eng is not None else torch.device("cuda", torch.cuda.current_device())

@@ -218,6 +218,8 @@ def _nc_kwargs(args):
               nufft_grid=args.nufft_grid, coils=args.nc_coils, interleaves=args.interleaves, petals=args.petals, dcf_iters=args.dcf_iters)
     if args.b0 is not None:                                  # --b0: the acquisition under a field map and the off-resonance stage
         kw.update(b0_hz=args.b0, readout_ms=args.readout_ms, b0_segments=args.b0_segments)
+        if getattr(args, "b0_interp", "linear") != "linear": # --b0-interp ls: the least-squares temporal interpolator
+            kw.update(b0_interp=args.b0_interp)
         if getattr(args, "b0_map", "true") != "true":        # --b0-map estimate: the solver gets a map estimated from a two-echo scan
             kw.update(b0_map=args.b0_map, b0_dte_ms=args.b0_dte, b0_beta=0.05 if args.b0_beta is None else args.b0_beta,
                       b0_iters=200 if args.b0_iters is None else args.b0_iters)
@@ -402,6 +404,9 @@ def main(argv=None):
     ap.add_argument("--readout-ms", type=float, default=None, metavar="T", help="--b0: the length of every readout (spoke, interleaf, shot) in ms")
     ap.add_argument("--b0-segments", default="auto", metavar="L|auto", help="--b0: time segments, 1..32, or auto: the smallest count whose "
                     "interpolation error stays within 1e-3, at most 32")
+    ap.add_argument("--b0-interp", choices=("linear", "ls"), default="linear", help="--b0: the temporal interpolator between the time segments: "
+                    "linear (two segments per sample), or ls: least-squares coefficients for every segment, fitted over the map's band - the "
+                    "same accuracy from about a quarter of the segments")
     ap.add_argument("--b0-map", choices=("true", "estimate"), default="true", help="--b0: the field map the solver is given: the map that made "
                     "the data, or one estimated on the device from a simulated two-echo scan of the same object (regularised fit, no phase "
                     "unwrapping)")
@@ -507,6 +512,8 @@ def main(argv=None):
                 args.b0_segments = int(args.b0_segments)
         elif args.readout_ms is not None or args.b0_segments != "auto":
             raise SystemExit("--readout-ms / --b0-segments need --b0")
+        elif args.b0_interp != "linear":
+            raise SystemExit("--b0-interp needs --b0")
         if args.nc_normal == "toeplitz" and args.mode == "acquire":
             raise SystemExit("acquire runs no CG: drop --nc-normal toeplitz")
         if args.nc_normal == "toeplitz" and not getattr(args, "gt", None):      # the synthetic sets: the size is known here
@@ -528,6 +535,8 @@ def main(argv=None):
         raise SystemExit("--dcf-iters needs --traj")
     elif args.b0 is not None or args.readout_ms is not None or args.b0_segments != "auto":
         raise SystemExit("--b0 / --readout-ms / --b0-segments need --traj")
+    elif args.b0_interp != "linear":
+        raise SystemExit("--b0-interp needs --b0")
     if args.b0 is None:
         if args.b0_map != "true" or args.b0_dte is not None or args.b0_beta is not None or args.b0_iters is not None:
             raise SystemExit("--b0-map / --b0-dte / --b0-beta / --b0-iters need --b0")

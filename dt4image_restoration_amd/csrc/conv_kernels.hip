@@ -801,6 +801,8 @@ Tuning tuning_from_env() {
     if (const char* v = getenv("PNP_OFFRES_GRID_FILTER")) t.offres_grid_filter = atoi(v) != 0;
     if (const char* v = getenv("PNP_FIELDMAP_NAIVE")) t.fieldmap_naive = atoi(v) != 0;
     if (const char* v = getenv("PNP_OFFRES_NAIVE")) t.offres_naive = atoi(v) != 0 ? 1 : 0;
+    if (const char* v = getenv("PNP_OFFRES_LS_NAIVE")) t.offres_ls_naive = atoi(v) != 0 ? 1 : 0;
+    if (const char* v = getenv("PNP_OFFRES_LS_NOSKIP")) t.offres_ls_noskip = atoi(v) != 0;
     return t;
 }
 

@@ -5,11 +5,13 @@
 #include "../../include/pnpadmm_toeplitz.h"
 #include "../../include/pnpadmm_dcf.h"
 #include "../../include/pnpadmm_offres.h"
+#include "../../include/pnpadmm_offres_ls.h"
 #include "../../include/pnpadmm_fieldmap.h"
 #include "pnp_internal.h"
 #include "denoiser_plan.h"
 #include "nufft_plan.h"
 #include "offres_plan.h"
+#include "offres_ls_plan.h"
 #include "block_reduce.h"
 
 #include <cmath>
@@ -166,9 +168,10 @@ struct pnp_engine {
     // scratch is the coil-block scratch above
     std::vector<int32_t> nc_bin_off_h, nc_bin_idx_h;   // host copy of the NUFFT plan's tile bins: what the per-segment lists are built from
     OffresDev orp;               // the uploaded plan; orp.segments == 0: none
-    size_t or_tau_cap = 0, or_seg_cap = 0, or_b0_cap = 0, or_b1_cap = 0, or_loff_cap = 0, or_lidx_cap = 0;
+    size_t or_tau_cap = 0, or_seg_cap = 0, or_b0_cap = 0, or_b1_cap = 0, or_loff_cap = 0, or_lidx_cap = 0, or_coef_cap = 0;
     int or_block = kOffresBlock; // segments per block: kOffresBlock, or PNP_OFFRES_SEG_BLOCK (read at pnp_create)
     int or_naive = kOffresNaiveSteps;   // OffresStep bits: the steps that run as the naive launches (PNP_OFFRES_NAIVE: all or none)
+    int orls_naive = kOffresLsNaiveSteps;   // ... under a least-squares plan (PNP_OFFRES_LS_NAIVE: all or none)
     float2* or_maps = nullptr;   // [map_n, L, H, W] the installed segment maps
     float2* or_y = nullptr;      // [N, M] the installed samples
     float* or_w = nullptr;       // [M] the installed weights (read only through stage_w)
@@ -583,16 +586,20 @@ int ns_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
 
 // ---- off-resonance correction (include/pnpadmm_offres.h) ------------------------------------------------
 int or_block_of(const pnp_engine* e) { return e->orp.segments < e->or_block ? e->orp.segments : e->or_block; }
+// the steps that run as the naive launches under the live plan's interpolator
+int or_naive_of(const pnp_engine* e) { return e->orp.kind == 2 ? e->orls_naive : e->or_naive; }
 // out [batch, M] = A src with the segment maps `maps` [map_n, L, h, w], block by block: a block's samples are blended into out before the
 // next block's grids replace them
 int or_forward(pnp_engine* e, const float2* src, const float* src_real, const float2* maps, int map_n, int batch, float2* out, hipStream_t s) {
     const int L = e->orp.segments, B = or_block_of(e);
+    const bool ls = e->orp.kind == 2;
     for (int l0 = 0; l0 < L; l0 += B) {
         const int cb = std::min(B, L - l0);
-        if (e->or_naive & OR_GATHER) {
+        if (or_naive_of(e) & OR_GATHER) {
             if (int rc = ns_forward_block(e, src, src_real, maps, map_n, L, l0, cb, batch, e->ns_samp, cb, 0, s)) return rc;
             Prof p(e, s, PROF_OTHER, -1);
-            HIP_TRY(launch_offres_blend(e->ns_samp, e->orp, e->nc, out, l0, cb, batch, s));
+            if (ls) HIP_TRY(launch_offres_ls_blend(e->ns_samp, e->orp, e->nc, out, l0, cb, batch, s));
+            else HIP_TRY(launch_offres_blend(e->ns_samp, e->orp, e->nc, out, l0, cb, batch, s));
             continue;
         }
         {
@@ -607,7 +614,8 @@ int or_forward(pnp_engine* e, const float2* src, const float* src_real, const fl
         }
         if (int rc = ns_fft(e, batch * cb, 0, s)) return rc;
         Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_offres_interp(e->ns_grid, e->orp, e->nc, out, l0, cb, batch, s));
+        if (ls) HIP_TRY(launch_offres_ls_interp(e->ns_grid, e->orp, e->nc, out, l0, cb, batch, s));
+        else HIP_TRY(launch_offres_interp(e->ns_grid, e->orp, e->nc, out, l0, cb, batch, s));
     }
     return PNP_OK;
 }
@@ -616,19 +624,25 @@ int or_forward(pnp_engine* e, const float2* src, const float* src_real, const fl
 int or_adjoint(pnp_engine* e, const float2* y, const float* w, const float2* maps, int map_n, int batch, const float2* pv, const float* mu,
                const float* tact, float2* q, double* partial, hipStream_t s) {
     const int L = e->orp.segments, B = or_block_of(e);
+    const bool ls = e->orp.kind == 2;
     for (int l0 = 0; l0 < L; l0 += B) {
         const int cb = std::min(B, L - l0);
-        if (e->or_naive & OR_GRID) {
+        // the dense least-squares gridding costs what a full sub-block of 8 segments costs: by default it runs on full sub-blocks only
+        // (measured: 0.92x of the naive launches at 8 segments, 1.09x at 6); PNP_OFFRES_LS_NAIVE=0 runs it on every block
+        const bool ragged = ls && e->tune.offres_ls_naive < 0 && cb % kOffresLsSub != 0;
+        if ((or_naive_of(e) & OR_GRID) || ragged) {
             {
                 Prof p(e, s, PROF_OTHER, -1);
-                HIP_TRY(launch_offres_expand(y, e->orp, e->nc, e->ns_samp, l0, cb, batch, s));
+                if (ls) HIP_TRY(launch_offres_ls_expand(y, e->orp, e->nc, e->ns_samp, l0, cb, batch, s));
+                else HIP_TRY(launch_offres_expand(y, e->orp, e->nc, e->ns_samp, l0, cb, batch, s));
             }
             if (int rc = ns_adjoint_block(e, e->ns_samp, cb, 0, w, maps, map_n, L, l0, cb, batch, pv, mu, tact, q, partial, s)) return rc;
             continue;
         }
         {
             Prof p(e, s, PROF_OTHER, -1);
-            HIP_TRY(launch_offres_grid(y, w, e->orp, e->nc, e->ns_grid, l0, cb, batch, s, e->tune.offres_grid_filter));
+            if (ls) HIP_TRY(launch_offres_ls_grid(y, w, e->orp, e->nc, e->ns_grid, l0, cb, batch, s, !e->tune.offres_ls_noskip));
+            else HIP_TRY(launch_offres_grid(y, w, e->orp, e->nc, e->ns_grid, l0, cb, batch, s, e->tune.offres_grid_filter));
         }
         if (int rc = ns_fft(e, batch * cb, 1, s)) return rc;
         Prof p(e, s, PROF_OTHER, -1);
@@ -1186,6 +1200,7 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     if (tune.ncsense_naive >= 0) e->ns_naive = tune.ncsense_naive ? NS_ALL : 0;
     if (tune.offres_block >= 1 && tune.offres_block <= PNP_MC_MAX_COILS) e->or_block = tune.offres_block;     // a check and a timing knob
     if (tune.offres_naive >= 0) e->or_naive = tune.offres_naive ? OR_ALL : 0;
+    if (tune.offres_ls_naive >= 0) e->orls_naive = tune.offres_ls_naive ? OR_ALL : 0;
     e->tz_fused = !tune.toeplitz_naive && kspace_len_ok(2 * cfg->h) && kspace_len_ok(2 * cfg->w) && toeplitz_fused_ok(cfg->h, cfg->w);
     e->dplan = plan;
     int rc;
@@ -1223,6 +1238,7 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->ns_img);
     (void)hipFree(e->tz_traj); (void)hipFree(e->tz_k); (void)hipFree(e->tz_w); (void)hipFree(e->tz_tw_h); (void)hipFree(e->tz_tw_w); (void)hipFree(e->tz_grid);
     (void)hipFree(e->orp.tau); (void)hipFree(e->orp.seg); (void)hipFree(e->orp.b0); (void)hipFree(e->orp.b1); (void)hipFree(e->orp.list_off);
+    (void)hipFree(e->orp.coef);
     (void)hipFree(e->orp.list_idx); (void)hipFree(e->or_maps); (void)hipFree(e->or_y); (void)hipFree(e->or_w); (void)hipFree(e->or_mpart); (void)hipFree(e->or_amaps);
     (void)hipFree(e->dcf_grid); (void)hipFree(e->dcf_w); (void)hipFree(e->dcf_part); (void)hipFree(e->dcf_max);
     (void)hipFree(e->ns_grid); (void)hipFree(e->ns_samp); (void)hipFree(e->ns_y); (void)hipFree(e->ns_sens); (void)hipFree(e->ns_w); (void)hipFree(e->ns_mpart);
@@ -1751,6 +1767,7 @@ int pnp_nufft_plan(pnp_handle e, const double* traj, int64_t m, int gh, int gw, 
     drop_stage(e, false);
     e->tz_planned = false;                                  // the spectrum belongs to the plan it was built for
     e->orp.segments = 0;                                    // ... and so does the off-resonance plan
+    e->orp.kind = 0;
     e->nc_traj.assign(traj, traj + 2 * (size_t)m);
     e->nc_bin_off_h = P.bin_off;
     e->nc_bin_idx_h = P.bin_idx;
@@ -2128,6 +2145,7 @@ int pnp_offres_plan(pnp_handle e, const double* t, int segments, int flags) {
     if (D.segments > 0) (void)hipDeviceSynchronize();       // no launch still reads the plan being replaced
     // from here on the old plan is gone: a live off-resonance stage's maps belong to its centres and are dropped with it
     D.segments = 0;
+    D.kind = 0;
     if (e->stage.kind == STAGE_OR) drop_stage(e, false);
     HIP_TRY(nc_upload(D.tau, P.tau.data(), P.tau.size() * sizeof(double)));
     HIP_TRY(nc_upload(D.seg, P.seg.data(), M * sizeof(int32_t)));
@@ -2136,8 +2154,59 @@ int pnp_offres_plan(pnp_handle e, const double* t, int segments, int flags) {
     HIP_TRY(nc_upload(D.list_off, P.list_off.data(), P.list_off.size() * sizeof(int32_t)));
     if (!P.list_idx.empty()) HIP_TRY(nc_upload(D.list_idx, P.list_idx.data(), P.list_idx.size() * sizeof(int32_t)));
     D.segments = P.segments;
+    D.kind = 1;
     return PNP_OK;
     PNP_API_END("pnp_offres_plan")
+}
+
+// ---- the least-squares interpolator (include/pnpadmm_offres_ls.h) ----
+int pnp_offres_plan_ls(pnp_handle e, const double* t, int segments, double omega_max, int flags) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_plan_ls";
+    // every rejection happens before any HIP call and leaves the handle as it was; scalar ranges first
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (segments < 1 || segments > PNP_MC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: segments must be 1..%d (got %d)", fn, PNP_MC_MAX_COILS, segments);
+    if (segments > 1 && (!std::isfinite(omega_max) || !(omega_max > 0.0)))
+        return fail(PNP_ERR_INVALID, "%s: omega_max must be finite and > 0 (got %g)", fn, omega_max);
+    if (!t) return fail(PNP_ERR_INVALID, "%s: null t", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = nc_need_plan(fn, e)) return rc;
+    OffresLsPlan P;
+    std::string why;
+    if (!plan_offres_ls(t, e->nc.m, segments, omega_max, &P, &why)) return fail(PNP_ERR_INVALID, "%s: %s", fn, why.c_str());
+    PNP_ON_DEVICE(e);
+    OffresDev& D = e->orp;
+    if (int rc = ws_grow(e, "off-resonance plan", {{(void**)&D.tau, &e->or_tau_cap, P.tau.size() * sizeof(double), false},
+                                                   {(void**)&D.coef, &e->or_coef_cap, P.coef.size() * sizeof(float), false}}))
+        return rc;
+    if (D.segments > 0) (void)hipDeviceSynchronize();       // no launch still reads the plan being replaced
+    // from here on the old plan is gone: a live off-resonance stage's maps belong to its plan and are dropped with it
+    D.segments = 0;
+    D.kind = 0;
+    if (e->stage.kind == STAGE_OR) drop_stage(e, false);
+    HIP_TRY(nc_upload(D.tau, P.tau.data(), P.tau.size() * sizeof(double)));
+    HIP_TRY(nc_upload(D.coef, P.coef.data(), P.coef.size() * sizeof(float)));
+    D.segments = P.segments;
+    D.kind = 2;
+    return PNP_OK;
+    PNP_API_END("pnp_offres_plan_ls")
+}
+
+int pnp_offres_interpolator(pnp_handle e) { return e && e->nc.m > 0 && e->orp.segments > 0 ? e->orp.kind : 0; }
+
+int pnp_offres_ls_coeffs(pnp_handle e, float* coef_host) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_ls_coeffs";
+    if (!coef_host) return fail(PNP_ERR_INVALID, "%s: null coef_host", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = nc_need_plan(fn, e)) return rc;
+    if (e->orp.segments < 1 || e->orp.kind != 2)
+        return fail(PNP_ERR_STATE, "%s: the handle has no least-squares off-resonance plan (pnp_offres_plan_ls)", fn);
+    PNP_ON_DEVICE(e);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(coef_host, e->orp.coef, (size_t)e->orp.segments * (size_t)e->nc.m * sizeof(float), hipMemcpyDeviceToHost));
+    return PNP_OK;
+    PNP_API_END("pnp_offres_ls_coeffs")
 }
 
 int pnp_offres_segments(pnp_handle e) { return e && e->nc.m > 0 ? e->orp.segments : 0; }

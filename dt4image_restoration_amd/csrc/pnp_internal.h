@@ -46,6 +46,8 @@ struct Tuning {
     bool fieldmap_naive = false;  // PNP_FIELDMAP_NAIVE (tests, timing): the field map fit as one launch per sweep instead of the fused kernel
     int offres_naive = -1;        // PNP_OFFRES_NAIVE (tests, timing): 1 = the operator composed from the non-Cartesian SENSE launches and two sample
                                   // kernels, 0 = the two-segment gather and gridding; unset: kOffresNaiveSteps, the choice per step by measurement
+    int offres_ls_naive = -1;     // PNP_OFFRES_LS_NAIVE (tests, timing): the same choice under a least-squares plan; unset: kOffresLsNaiveSteps
+    bool offres_ls_noskip = false;   // PNP_OFFRES_LS_NOSKIP (timing): the dense gridding without its wave-uniform row skip; the same numbers
 };
 Tuning tuning_from_env();
 
@@ -474,6 +476,8 @@ struct OffresDev {
     float* b1 = nullptr;     // [M]
     int* list_off = nullptr; // [L tiles + 1]
     int* list_idx = nullptr;
+    int kind = 0;            // 0: no plan, 1: the linear interpolator (seg, b0, b1, lists), 2: least squares (coef; include/pnpadmm_offres_ls.h)
+    float* coef = nullptr;   // [L][M] segment-major, kind == 2
 };
 static constexpr int kOffresBlock = 8;     // default segments per block (PNP_OFFRES_SEG_BLOCK overrides it)
 // the steps of the operator, as bits: which of them run as the naive launches.  Both forms give the same numbers (include/pnpadmm_offres.h)
@@ -493,6 +497,23 @@ hipError_t launch_offres_expand(const float2* y, const OffresDev& R, const Nufft
 // filter: walk the NUFFT plan's whole tile bin per segment instead of the plan's per-(segment, tile) list (PNP_OFFRES_GRID_FILTER: timing)
 hipError_t launch_offres_grid(const float2* y, const float* w, const OffresDev& R, const NufftDev& P, float2* grid, int l0, int cb, int batch,
                               hipStream_t s, bool filter = false);
+
+// ---- off-resonance correction, least-squares interpolator (offres_ls_kernels.hip; include/pnpadmm_offres_ls.h; the plan: offres_ls_plan.h) ---
+// the steps, as OffresStep bits, that run as the naive launches under a least-squares plan.  The shipped choice (profiles/offres_ls_bench.json,
+// DESIGN.md 4a): a dense kernel ships only where it is not slower than the naive launches.  At the benchmark shape the dense gridding takes
+// 0.92x of the naive launches' adjoint and ships; the dense gather takes 1.46x of their forward, so the gather ships naive and the dense
+// one stays behind PNP_OFFRES_LS_NAIVE=0
+static constexpr int kOffresLsNaiveSteps = OR_GATHER;
+static constexpr int kOffresLsSub = 8;     // segments per workgroup of the dense gridding (its register and LDS sub-block)
+// out [batch, M] = the chain over the block's segments of coef_l . gather(grid l); l0 > 0 continues from out
+hipError_t launch_offres_ls_interp(const float2* grid, const OffresDev& R, const NufftDev& P, float2* out, int l0, int cb, int batch, hipStream_t s);
+// the naive form's blend of the block's samples samp [batch, cb, M], and its expansion ye [batch, cb, M] = coef_l . y of y [batch, M]
+hipError_t launch_offres_ls_blend(const float2* samp, const OffresDev& R, const NufftDev& P, float2* out, int l0, int cb, int batch, hipStream_t s);
+hipError_t launch_offres_ls_expand(const float2* y, const OffresDev& R, const NufftDev& P, float2* ye, int l0, int cb, int batch, hipStream_t s);
+// grid [batch, cb, gh, gw] = per segment of the block the spread of w . coef_l . y over the tile's whole bin, every grid point written, no
+// atomics; skip: a wave passes over a sample that touches none of its rows (false: PNP_OFFRES_LS_NOSKIP, timing)
+hipError_t launch_offres_ls_grid(const float2* y, const float* w, const OffresDev& R, const NufftDev& P, float2* grid, int l0, int cb, int batch,
+                                 hipStream_t s, bool skip = true);
 
 // ---- field map estimation (fieldmap_kernels.hip; the fit: include/pnpadmm_fieldmap.h) ----------------------------
 // The fused kernel's plan: kFmT sweeps per launch over a kFmRegion^2 region, of which the kFmTile^2 tile is stored

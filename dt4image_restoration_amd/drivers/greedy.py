@@ -442,7 +442,7 @@ class GreedyEvaluator:
                     return v if v.numel() == hw else v.reshape(-1, *v.shape[-2:])[a:b]
                 if key == "sens" and v.dim() == 3:          # coil maps [C,H,W] shared by every slice
                     return v
-                if key in ("traj", "dcf", "times", "segments") or (key in ("omega", "omega_true") and v.dim() == 2):
+                if key in ("traj", "dcf", "times", "segments", "b0_interp") or (key in ("omega", "omega_true") and v.dim() == 2):
                     return v                                # a non-Cartesian episode's trajectory, weights, sample times and shared field map
                 if key == "omega":
                     return v.reshape(-1, *v.shape[-2:])[a:b]

@@ -227,7 +227,7 @@ class MCTS:
                 return v.reshape(-1, *v.shape[-2:]).repeat_interleave(k, dim=0) if v.numel() != hw else v
             if key == "sens" and v.dim() == 3:              # coil maps [C,H,W] shared by every slice
                 return v
-            if key in ("traj", "dcf", "times", "segments") or (key in ("omega", "omega_true") and v.dim() == 2):
+            if key in ("traj", "dcf", "times", "segments", "b0_interp") or (key in ("omega", "omega_true") and v.dim() == 2):
                 return v                                    # a non-Cartesian episode's trajectory, weights, sample times and shared field map
             return v.repeat_interleave(k, dim=0) if v.dim() > 2 else v
         rep = {key: replicate(key, v) for key, v in mat.items()}

@@ -491,12 +491,44 @@ class PnPEngine:
         _lib.check(self.lib.pnp_offres_plan(self._h, t.ctypes.data, int(segments), 0), "pnp_offres_plan")
         self._offres_key = (t.copy(), int(segments))
 
-    _offres_key = None           # (a copy of times, segments) of the live off-resonance plan
+    _offres_key = None           # (a copy of times, segments[, omega_max: a least-squares plan]) of the live off-resonance plan
+
+    def offres_plan_ls(self, times, segments: int, omega_max: float) -> None:
+        """Plan the off-resonance operator with the least-squares temporal interpolator (pnp_offres_plan_ls, include/pnpadmm_offres_ls.h):
+        as `offres_plan`, with one coefficient per (segment, sample) fitted over the band |omega| <= omega_max (rad/s).  Replaces an earlier
+        off-resonance plan of either kind; `offres_plan` and `nufft_plan` replace / drop this one."""
+        t = np.ascontiguousarray(times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else times, dtype=np.float64).reshape(-1)
+        m = self.nufft_samples
+        if m and t.size != m:
+            raise ValueError(f"times: expected {m} samples, got {t.shape}")
+        if self.offres_live:
+            self.live_episode = 0
+        self._offres_key = None
+        _lib.check(self.lib.pnp_offres_plan_ls(self._h, t.ctypes.data, int(segments), float(omega_max), 0), "pnp_offres_plan_ls")
+        self._offres_key = (t.copy(), int(segments), float(omega_max))
+
+    def offres_ls_planned(self, times, segments: int, omega_max: float) -> bool:
+        """Whether the live off-resonance plan is the least-squares plan of exactly these times, segments and omega_max."""
+        k = self._offres_key
+        if k is None or len(k) != 3 or self.offres_interpolator() != "ls" or self.offres_segments != int(segments) or k[1] != int(segments):
+            return False
+        t = np.asarray(times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else times, dtype=np.float64).reshape(-1)
+        return k[2] == float(omega_max) and k[0].shape == t.shape and bool(np.array_equal(k[0], t))
+
+    def offres_interpolator(self) -> Optional[str]:
+        """"linear" or "ls": the temporal interpolator of the live off-resonance plan (pnp_offres_interpolator); None without a plan."""
+        return {1: "linear", 2: "ls"}.get(int(self.lib.pnp_offres_interpolator(self._h)))
+
+    def offres_ls_coeffs(self) -> np.ndarray:
+        """float32 [L, M]: the coefficient table of the live least-squares plan, copied back from the device (pnp_offres_ls_coeffs)."""
+        out = np.empty((max(self.offres_segments, 1), max(self.nufft_samples, 1)), dtype=np.float32)
+        _lib.check(self.lib.pnp_offres_ls_coeffs(self._h, out.ctypes.data), "pnp_offres_ls_coeffs")
+        return out
 
     def offres_planned(self, times, segments: int) -> bool:
         """Whether the live off-resonance plan was made from exactly these times and segments on the live NUFFT plan."""
         k = self._offres_key
-        if k is None or self.offres_segments != int(segments) or k[1] != int(segments):      # (pnp_nufft_plan drops the plan: 0 segments)
+        if k is None or len(k) != 2 or self.offres_segments != int(segments) or k[1] != int(segments):   # (pnp_nufft_plan drops the plan: 0 segments)
             return False
         t = np.asarray(times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else times, dtype=np.float64).reshape(-1)
         return k[0].shape == t.shape and bool(np.array_equal(k[0], t))
@@ -642,31 +674,56 @@ class PnPEngine:
         return cost
 
     # -- hot path --------------------------------------------------------------------------
-    def _offres_for(self, times, segments) -> None:
-        """the off-resonance plan of `reset` / `set_kspace` with omega: planned here when times are given and differ from the live plan's"""
+    def _offres_for(self, times, segments, interpolator: str = "linear", omega_max: Optional[float] = None,
+                    omega: Optional[torch.Tensor] = None) -> None:
+        """the off-resonance plan of `reset` / `set_kspace` with omega: planned here when times are given and differ from the live plan's.
+        interpolator "ls": the least-squares plan over |omega| <= omega_max, by default max |omega| (1 + 1e-6) of the map in hand; a map
+        that exceeds a given omega_max is refused (the library does not detect it)."""
+        if interpolator not in _lib.OFFRES_INTERPOLATORS:
+            raise ValueError(f"interpolator must be one of {sorted(_lib.OFFRES_INTERPOLATORS)} (got {interpolator!r})")
+        if interpolator == "linear":
+            if omega_max is not None:
+                raise ValueError("omega_max goes with interpolator='ls'")
+        elif omega is not None:
+            top = float(omega.abs().max())
+            if omega_max is None:
+                omega_max = top * (1.0 + 1e-6)
+            elif top > float(omega_max):
+                raise ValueError(f"the field map reaches {top:g} rad/s, outside the band omega_max = {float(omega_max):g} of the least-squares plan")
         if times is None:
+            if interpolator == "ls" and self.offres_interpolator() != "ls":
+                raise ValueError("interpolator='ls' without times needs a live least-squares plan (offres_plan_ls)")
             return
         if segments is None:
             raise ValueError("times needs segments (acquisition.offres_segments chooses them)")
-        if not self.offres_planned(times, segments):
+        if interpolator == "ls":
+            if omega_max is None:
+                raise ValueError("interpolator='ls' needs omega_max or a field map")
+            if int(segments) == 1:
+                omega_max = 0.0                                  # one centre: the band is not read
+            if not self.offres_ls_planned(times, segments, omega_max):
+                self.offres_plan_ls(times, segments, omega_max)
+        elif not self.offres_planned(times, segments):
             self.offres_plan(times, segments)
 
     def reset(self, x0: torch.Tensor, y0: torch.Tensor, mask: Optional[torch.Tensor] = None, sens: Optional[torch.Tensor] = None,
               cg_iters: int = 8, omega: Optional[torch.Tensor] = None, times=None, segments: Optional[int] = None,
-              w: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+              w: Optional[torch.Tensor] = None, interpolator: str = "linear",
+              omega_max: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """x0, y0 complex64 [N,1,H,W]; mask bool/uint8 [H,W] (or [N,H,W]).  Returns fresh (x f32, z c64, u c64).
         With sens (complex64 [C,H,W] or [N,C,H,W]) y0 is [N,C,H,W] and the handle enters multi-coil mode (pnp_reset_mc): the k-space
         subproblem is then solved by `cg_iters` conjugate-gradient iterations per step.
         With omega (field map, float32 [H,W] or [N,H,W] in rad/s) the episode is the off-resonance one on the planned trajectory
         (`reset_offres`): y0 is the samples [N,M], mask is not read, w float32 [M] or None are the sample weights; times with segments plan
-        the time segments first (`offres_plan`) unless the live plan is that one."""
+        the time segments first (`offres_plan`) unless the live plan is that one; interpolator "ls" plans the least-squares interpolator
+        instead (`offres_plan_ls`), over omega_max or, by default, the map's own max |omega| (1 + 1e-6)."""
         if omega is not None:
             if sens is not None:
                 raise ValueError("reset: the off-resonance stage is single-coil (omega with sens is not supported)")
-            self._offres_for(times, segments)
+            self._offres_for(times, segments, interpolator, omega_max, omega)
             return self.reset_offres(x0, y0, omega, w, cg_iters=cg_iters)
-        if times is not None or segments is not None or w is not None:
-            raise ValueError("reset: times, segments and w go with omega")
+        if times is not None or segments is not None or w is not None or interpolator != "linear" or omega_max is not None:
+            raise ValueError("reset: times, segments, w, interpolator and omega_max go with omega")
         nhw = self.n * self.h * self.w
         x0 = self._chk(x0, torch.complex64, nhw, "x0")
         if sens is not None:
@@ -687,17 +744,17 @@ class PnPEngine:
 
     def set_kspace(self, y0: torch.Tensor, mask: Optional[torch.Tensor] = None, episode: int = 0, sens: Optional[torch.Tensor] = None,
                    cg_iters: int = 8, omega: Optional[torch.Tensor] = None, times=None, segments: Optional[int] = None,
-                   w: Optional[torch.Tensor] = None) -> None:
+                   w: Optional[torch.Tensor] = None, interpolator: str = "linear", omega_max: Optional[float] = None) -> None:
         """Re-install the k-space constants (y0, mask) of another episode without touching any iterate
         (pnp_set_kspace); `episode` = the id that episode's reset returned (0: a fresh id).  With sens: a multi-coil episode's
         constants (pnp_set_kspace_mc), as in `reset`.  With omega: an off-resonance episode's (`set_kspace_offres`), as in `reset`."""
         if omega is not None:
             if sens is not None:
                 raise ValueError("set_kspace: the off-resonance stage is single-coil (omega with sens is not supported)")
-            self._offres_for(times, segments)
+            self._offres_for(times, segments, interpolator, omega_max, omega)
             return self.set_kspace_offres(y0, omega, w, episode=episode, cg_iters=cg_iters)
-        if times is not None or segments is not None or w is not None:
-            raise ValueError("set_kspace: times, segments and w go with omega")
+        if times is not None or segments is not None or w is not None or interpolator != "linear" or omega_max is not None:
+            raise ValueError("set_kspace: times, segments, w, interpolator and omega_max go with omega")
         nhw = self.n * self.h * self.w
         m, mask_n = self._mask(mask)
         if sens is not None:

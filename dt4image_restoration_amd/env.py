@@ -151,34 +151,59 @@ class PnPEnv:
         seg = data.get("segments")
         if seg is None:
             om_max = float(torch.as_tensor(data["omega"]).abs().max())
-            seg = min(acquisition.offres_segments(om_max, float(times.max() - times.min())), acquisition.OFFRES_MAX_SEGMENTS)
+            if PnPEnv._interp_of(data) == "ls":
+                seg = min(acquisition.offres_ls_segments(om_max * (1.0 + 1e-6), float(times.max() - times.min())), acquisition.OFFRES_MAX_SEGMENTS)
+            else:
+                seg = min(acquisition.offres_segments(om_max, float(times.max() - times.min())), acquisition.OFFRES_MAX_SEGMENTS)
         return times, int(seg)
+
+    @staticmethod
+    def _interp_of(data) -> str:
+        """data["b0_interp"]: "linear" | "ls", or pnp_offres_interpolator's code 1 | 2 (what `acquisition.simulate` writes); absent: linear"""
+        v = data.get("b0_interp", "linear")
+        if not isinstance(v, str):
+            v = {1: "linear", 2: "ls"}.get(int(v), v)
+        if v not in ("linear", "ls"):
+            raise ValueError(f"data['b0_interp'] must be 'linear' or 'ls' (or 1 or 2), got {v!r}")
+        return v
+
+    @staticmethod
+    def _offres_plan(eng: PnPEngine, times, seg: int, interp: str, omega_max) -> None:
+        """make the engine's off-resonance plan the episode's, unless it is the live one"""
+        if interp == "ls":
+            band = float(omega_max) if seg > 1 else 0.0
+            if not eng.offres_ls_planned(times, seg, band):
+                eng.offres_plan_ls(times, seg, band)
+        elif not eng.offres_planned(times, seg):
+            eng.offres_plan(times, seg)
 
     def _reset_offres(self, data, eng: PnPEngine, x0, y0, sens, dcf, gt, traj, n: int, device) -> "OrderedDict[str, torch.Tensor]":
         """An off-resonance episode: data["omega"] float32 [H,W] or [N,H,W] in rad/s, data["times"] float64 [M] seconds, optional
-        data["segments"]; single-coil, gridding form of the normal operator."""
+        data["segments"], optional data["b0_interp"] "linear" | "ls" (the least-squares temporal interpolator over the map's own band,
+        max |omega| (1 + 1e-6)); single-coil, gridding form of the normal operator."""
         if sens is not None:
             raise ValueError("an off-resonance episode is single-coil (data['omega'] with data['sens'] is not supported)")
         if self.nc_normal == "toeplitz":
             raise ValueError("an off-resonance episode has no Toeplitz normal operator (nc_normal='toeplitz' with data['omega'])")
         times, seg = self._offres_args(data, traj.shape[0])
         omega = torch.as_tensor(data["omega"]).to(device, torch.float32).contiguous()
-        if not eng.offres_planned(times, seg):
-            eng.offres_plan(times, seg)
+        interp = self._interp_of(data)
+        extra = {} if interp == "linear" else {"b0_interp": interp, "omega_max": float(omega.abs().max()) * (1.0 + 1e-6)}
+        self._offres_plan(eng, times, seg, interp, extra.get("omega_max"))
         x, z, u = eng.reset_offres(x0, y0, omega, dcf, cg_iters=self.cg_iters)
         aty0 = torch.as_tensor(data["ATy0"])[..., 0] if "ATy0" in data else None
         return OrderedDict({"x": x, "y0": y0, "z": z, "u": u, "mask": None, "gt": gt, "ATy0": aty0,
                             "T": torch.zeros(n, dtype=torch.float32, device=device),
                             "complex_y0": data["y0"], "_episode": eng.live_episode, "sens": None, "traj": traj, "dcf": dcf,
-                            "omega": omega, "times": times, "segments": seg})
+                            "omega": omega, "times": times, "segments": seg, **extra})
 
     def _bind_episode(self, eng: PnPEngine, states) -> None:
         """Make the engine's k-space constants those of `states` (env.py:88-90 reads y0 / mask from the dict)."""
         ep = states.get("_episode", 0)
         if states.get("traj") is not None and not eng.nufft_planned(states["traj"], self.nufft_grid, self.nufft_width):
             eng.nufft_plan(states["traj"], grid=self.nufft_grid, width=self.nufft_width)      # (drops the live episode)
-        if states.get("omega") is not None and not eng.offres_planned(states["times"], int(states["segments"])):
-            eng.offres_plan(states["times"], int(states["segments"]))                         # (drops a live off-resonance episode)
+        if states.get("omega") is not None:                                                   # (a new plan drops a live off-resonance episode)
+            self._offres_plan(eng, states["times"], int(states["segments"]), self._interp_of(states), states.get("omega_max"))
         if ep and ep == eng.live_episode:
             return
         if not ep:                              # a state dict built by hand the reference's way
