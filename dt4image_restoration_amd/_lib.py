@@ -173,6 +173,21 @@ SIGNATURES_OFFRES_LS = {
 }
 OFFRES_INTERPOLATORS = {"linear": 1, "ls": 2}
 
+# name -> (restype, argtypes); every symbol include/pnpadmm_offres_mc.h declares (off-resonance correction for multi-coil data)
+SIGNATURES_OFFRES_MC = {
+    "pnp_offres_forward_mc": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_offres_adjoint_mc": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_set_kspace_offres_mc": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _vp]),
+    "pnp_reset_offres_mc": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _vp]),
+    "pnp_offres_mc_coils": (C.c_int, [C.c_void_p]),
+    "pnp_offres_mc_cg_residual": (C.c_int, [C.c_void_p, _fp, _vp]),
+    "pnp_offres_mc_normal": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _vp]),
+    "pnp_acquire_offres_mc": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_double, C.c_uint64, C.c_int, _fp, _fp, _fp,
+                                       _vp]),
+}
+PNP_OFFRES_MC_COIL_BLOCK = 4     # default coils per block under a least-squares plan, and 2 under a linear one (the environment variable of the
+PNP_OFFRES_MC_COIL_BLOCK_LINEAR = 2   # first name, read at pnp_create, overrides both)
+
 # name -> (restype, argtypes); every symbol include/pnpadmm_fieldmap.h declares (the B0 field map from two echo images)
 SIGNATURES_FIELDMAP = {
     "pnp_fieldmap_estimate": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_double, C.c_float, C.c_int, C.c_int, _fp, _fp, _vp]),
@@ -206,7 +221,7 @@ def load() -> C.CDLL:
                        f"or `make -C {os.path.dirname(LIB_PATH)}`; there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE, **SIGNATURES_TOEPLITZ, **SIGNATURES_DCF, **SIGNATURES_OFFRES,
-                              **SIGNATURES_OFFRES_LS, **SIGNATURES_FIELDMAP}.items():
+                              **SIGNATURES_OFFRES_LS, **SIGNATURES_OFFRES_MC, **SIGNATURES_FIELDMAP}.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -430,8 +430,12 @@ def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, wid
             eng.offres_plan_ls(tm, 1, 0.0)
         else:
             eng.offres_plan(tm, int(L))
-        y, aty0, x0 = eng.acquire_offres(g, om, float(sigma_n), seed, dcf=d)
-        y = y.reshape(eng.n, 1, -1)
+        if sens is not None:                                   # coils times segments (include/pnpadmm_offres_mc.h): y [N,C,M]
+            sens = torch.as_tensor(sens).to(eng.device, torch.complex64).contiguous()
+            y, aty0, x0 = eng.acquire_offres_mc(g, sens, om, float(sigma_n), seed, dcf=d)
+        else:
+            y, aty0, x0 = eng.acquire_offres(g, om, float(sigma_n), seed, dcf=d)
+            y = y.reshape(eng.n, 1, -1)
     elif sens is not None:                                     # non-Cartesian SENSE: y [N,C,M]
         sens = torch.as_tensor(sens).to(eng.device, torch.complex64).contiguous()
         y, aty0, x0 = eng.acquire_ncsense(g, sens, float(sigma_n), seed, dcf=d)
@@ -453,7 +457,7 @@ def _simulate_nc(eng, g: torch.Tensor, traj, dcf, sigma_n: float, seed: int, wid
 
 def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: int = 0, sens=None, noise_cov=None, traj=None, dcf=None,
              nufft_width: int = 6, nufft_grid=None, omega=None, times=None, segments="auto", interpolator: str = "linear",
-             omega_max=None) -> Dict[str, torch.Tensor]:
+             omega_max=None, offres_mc: bool = False) -> Dict[str, torch.Tensor]:
     """The collated `.mat` dict `PnPEnv.reset` reads, acquired on the device: x0, y0, ATy0 float32 [N,1,H,W,2] (real views of the
     complex outputs), mask bool [H,W] (or [N,H,W]), gt float32 [N,1,H,W], x0_raw = Re ATy0 [N,1,H,W]; every tensor on the GPU.
     gt: [N,H,W] or [N,1,H,W] in [0, 1] (array or tensor), mask: [H,W] or [N,H,W] in the centred layout.  Slice i draws the noise of
@@ -474,7 +478,9 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
     `times` and `segments` beside `traj`.  interpolator "ls": the least-squares temporal interpolator (pnp_offres_plan_ls,
     include/pnpadmm_offres_ls.h) over |omega| <= omega_max (None: the map's max |omega| (1 + 1e-6); a map beyond a given omega_max is
     refused), "auto" segments by `offres_ls_segments`; the dict then carries `b0_interp` = 2 (pnp_offres_interpolator's code: a dict of
-    numbers stays one)."""
+    numbers stays one).  offres_mc=True lifts "single-coil only": traj with omega, times AND sens is the multi-coil acquisition under the
+    field map (pnp_acquire_offres_mc, include/pnpadmm_offres_mc.h), y0 [N,C,M,2], the dict carries `sens` beside `omega`, `times` and
+    `segments`, and `PnPEnv(offres_mc=True).reset` installs the coils x segments stage.  The default False keeps the refusal."""
     if interpolator not in _lib.OFFRES_INTERPOLATORS:
         raise ValueError(f"simulate: interpolator must be one of {sorted(_lib.OFFRES_INTERPOLATORS)}, got {interpolator!r}")
     if (interpolator != "linear" or omega_max is not None) and omega is None:
@@ -499,7 +505,7 @@ def simulate(engine_or_env, gt, mask, sigma_n: float, seed: int, first_slice: in
             raise ValueError("simulate: a non-Cartesian acquisition draws white noise (traj with noise_cov is not supported)")
         if (omega is None) != (times is None):
             raise ValueError("simulate: omega and times go together")
-        if omega is not None and sens is not None:
+        if omega is not None and sens is not None and not offres_mc:
             raise ValueError("simulate: the off-resonance acquisition is single-coil (omega with sens is not supported)")
         return _simulate_nc(eng, g, traj, dcf, sigma_n, int(seed) + int(first_slice), nufft_width, nufft_grid, sens=sens, omega=omega,
                             times=times, segments=segments, interpolator=interpolator, omega_max=omega_max)
@@ -860,7 +866,8 @@ def make_mask(h: int, w: int, accel: float, kind: str = "radial", seed: int = 0)
 
 
 def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int = 0, mask_kind: str = "radial",
-                 mask=None, coils: int = 0, noise_cov=None, spokes: int = None, b0_interp: str = "linear", nc_weights: str = "dcf",
+                 mask=None, coils: int = 0, noise_cov=None, spokes: int = None, b0_interp: str = "linear", b0_coils: int = 0,
+                 nc_weights: str = "dcf",
                  b0_map: str = "true", b0_dte_ms: float = None, b0_beta: float = 0.05, b0_iters: int = 200, b0_scan_noise: float = None,
                  nufft_width: int = 6, b0_hz: float = None, readout_ms: float = None, b0_segments="auto",
                  nufft_grid=None, interleaves: int = None, petals: int = None, dcf_iters: int = 30) -> Dict[str, torch.Tensor]:
@@ -882,8 +889,22 @@ def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int =
     `field_map_dte(2 pi b0_hz)`; image noise `b0_scan_noise`, None for the task's sigma_n), estimates the map on the device
     (`estimate_field_map` with `b0_beta`, `b0_iters`: no phase unwrapping, so b0_hz * b0_dte_ms must stay below 500) and installs the
     estimate, float32 [N,H,W], as `omega`; the truth stays under `omega_true`.  The data y are the true map's either way.
-    b0_interp (with b0_hz): "linear", or "ls" for the least-squares temporal interpolator (`simulate(interpolator=)`)."""
+    b0_interp (with b0_hz): "linear", or "ls" for the least-squares temporal interpolator (`simulate(interpolator=)`).
+    b0_coils (with b0_hz, 1..32; not with coils): the multi-coil acquisition under the field map, with the maps
+    `synthetic.coil_maps(b0_coils, h, w)` (`simulate(..., sens=, offres_mc=True)`); the dict then carries `sens` too and
+    `PnPEnv(offres_mc=True).reset` installs the coils x segments stage.  The map is the true one: b0_map="estimate" is refused with b0_coils."""
     accel, sigma_n = parse_task(task)
+    b0_coils = int(b0_coils)
+    if b0_coils:
+        if not 1 <= b0_coils <= _lib.PNP_MC_MAX_COILS:
+            raise ValueError(f"task_problem: b0_coils must be 1..{_lib.PNP_MC_MAX_COILS}, got {b0_coils}")
+        if b0_hz is None:
+            raise ValueError("task_problem: b0_coils needs b0_hz (the multi-coil acquisition under a field map)")
+        if coils:
+            raise ValueError("task_problem: b0_coils is the coil count of the off-resonance acquisition; it does not go with coils")
+        if b0_map == "estimate":
+            raise ValueError("task_problem: b0_map='estimate' is not supported with b0_coils: estimating the field map inside a multi-coil "
+                             "episode is out of scope (estimate it beforehand and pass the map)")
     if b0_interp not in _lib.OFFRES_INTERPOLATORS:
         raise ValueError(f"task_problem: b0_interp must be one of {sorted(_lib.OFFRES_INTERPOLATORS)}, got {b0_interp!r}")
     if b0_interp != "linear" and b0_hz is None:
@@ -932,6 +953,10 @@ def task_problem(task: str, gt, engine_or_env, seed: int = 0, first_slice: int =
             readout = m
         times = readout_times(mask_kind[:-3], m, readout, float(readout_ms) * 1e-3)
         omega = (2.0 * math.pi * synthetic.field_map(h, w, float(b0_hz), seed)).astype(np.float32)
+        if b0_coils:
+            return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, sens=synthetic.coil_maps(b0_coils, h, w).astype(np.complex64),
+                            traj=traj, dcf=dcf, nufft_width=nufft_width, nufft_grid=nufft_grid, omega=omega, times=times, segments=b0_segments,
+                            offres_mc=True, **interp)
         if b0_map == "true":
             return simulate(engine_or_env, gt, None, sigma_n, seed, first_slice, traj=traj, dcf=dcf, nufft_width=nufft_width,
                             nufft_grid=nufft_grid, omega=omega, times=times, segments=b0_segments, **interp)

@@ -27,6 +27,7 @@ layout has none):
     ... --traj radial [--spokes S] [--nufft-width 4|6|8] [--nufft-grid GH GW] [--nc-weights none|dcf|pipe] [--cg-iters K] eval|flex|mcts|fixed|acquire ...
     ... --traj spiral [--interleaves L] | --traj rosette [--petals P]  [--nc-weights none|dcf|pipe] [--dcf-iters I] eval|flex|mcts|fixed|acquire ...
     ... --traj radial --nc-coils 4 [--cg-iters K] eval|flex|mcts|fixed|acquire ...      (non-Cartesian SENSE: the radial acquisition of C coils)
+    ... --traj spiral --b0 HZ --readout-ms T --b0-coils 4 [--b0-interp ls] [--b0-segments L] eval|flex|mcts|fixed ...   (coils x segments stage)
     ... --coils 4 --sens estimate [--sens-window hann|box] [--sens-thresh 0.05] [--acs H W] --mask cartesian fixed ...
 
     ... --coils 8 --sens espirit [--espirit-kernel 6] [--espirit-sv 0.02] [--espirit-crop 0.9] [--espirit-iters 16] --mask cartesian fixed ...
@@ -107,7 +108,8 @@ def _build(args, mode):
     den = _denoiser(args)
     scorer = (lambda st: 1.0 / (1e-3 + (st["x"] - torch.nn.functional.avg_pool2d(st["x"], 3, 1, 1)).pow(2).mean(dim=(1, 2, 3))))
     env = PnPEnv(max_episode_step=30, denoiser=den, device_type="cuda", no_ref_scorer=None, cg_iters=args.cg_iters,
-                 nufft_width=args.nufft_width, nufft_grid=args.nufft_grid, nc_normal=args.nc_normal)
+                 nufft_width=args.nufft_width, nufft_grid=args.nufft_grid, nc_normal=args.nc_normal,
+                 offres_mc=bool(getattr(args, "b0_coils", 0)))
     if getattr(args, "scorer", "stub") == "neg_dc":            # minus the k-space data misfit of the rollout's final iterate (pnp_residuals)
         scorer = (lambda st: -env.residuals(st, dc=True)[:, 5])
     return model, env, scorer
@@ -223,6 +225,8 @@ def _nc_kwargs(args):
         if getattr(args, "b0_map", "true") != "true":        # --b0-map estimate: the solver gets a map estimated from a two-echo scan
             kw.update(b0_map=args.b0_map, b0_dte_ms=args.b0_dte, b0_beta=0.05 if args.b0_beta is None else args.b0_beta,
                       b0_iters=200 if args.b0_iters is None else args.b0_iters)
+        if getattr(args, "b0_coils", 0):                     # --b0-coils C: the multi-coil acquisition under the field map, coils x segments stage
+            kw.update(b0_coils=args.b0_coils)
     return kw
 
 
@@ -407,6 +411,9 @@ def main(argv=None):
     ap.add_argument("--b0-interp", choices=("linear", "ls"), default="linear", help="--b0: the temporal interpolator between the time segments: "
                     "linear (two segments per sample), or ls: least-squares coefficients for every segment, fitted over the map's band - the "
                     "same accuracy from about a quarter of the segments")
+    ap.add_argument("--b0-coils", type=int, default=0, metavar="C", help="--b0: the multi-coil acquisition under the field map, C coils with "
+                    "analytic coil maps (1..32; default 0: single-coil), reconstructed with the coils x segments off-resonance stage (eval / flex / "
+                    "mcts / fixed; not with --nc-coils, --coils, --nc-normal toeplitz or --b0-map estimate)")
     ap.add_argument("--b0-map", choices=("true", "estimate"), default="true", help="--b0: the field map the solver is given: the map that made "
                     "the data, or one estimated on the device from a simulated two-echo scan of the same object (regularised fit, no phase "
                     "unwrapping)")
@@ -477,6 +484,19 @@ def main(argv=None):
         raise SystemExit(f"--coils must be 1..32, got {args.coils}")
     if not 1 <= args.cg_iters <= 64:
         raise SystemExit(f"--cg-iters must be 1..64, got {args.cg_iters}")
+    if args.b0_coils:
+        if not 1 <= args.b0_coils <= 32:
+            raise SystemExit(f"--b0-coils must be 1..32, got {args.b0_coils}")
+        if args.b0 is None:
+            raise SystemExit("--b0-coils needs --b0 (the multi-coil acquisition under a field map)")
+        if args.coils:
+            raise SystemExit("--b0-coils with --coils: refused - --coils selects the Cartesian multi-coil chain")
+        if args.nc_coils:
+            raise SystemExit("--b0-coils with --nc-coils: refused - --b0-coils is the coil count of the off-resonance acquisition")
+        if args.nc_normal == "toeplitz":
+            raise SystemExit("--b0-coils with --nc-normal toeplitz: the off-resonance stage has no Toeplitz form")
+        if args.b0_map != "true":
+            raise SystemExit("--b0-coils with --b0-map estimate: estimating the field map inside a multi-coil episode is out of scope")
     if args.traj:
         if args.coils:
             raise SystemExit("--traj with --coils: refused - --coils selects the Cartesian multi-coil chain; the multi-coil radial acquisition "
@@ -649,7 +669,8 @@ def main(argv=None):
         from .env import PnPEnv
         den = _denoiser(args)
         env = PnPEnv(max_episode_step=args.max_iter, denoiser=den, device_type="cuda", cg_iters=args.cg_iters,
-                     nufft_width=args.nufft_width, nufft_grid=args.nufft_grid, nc_normal=args.nc_normal)
+                     nufft_width=args.nufft_width, nufft_grid=args.nufft_grid, nc_normal=args.nc_normal,
+                 offres_mc=bool(getattr(args, "b0_coils", 0)))
         solver = FixedScheduleSolver(env, max_iter=args.max_iter, tol=args.tol, sync_every=5, dc=args.dc,
                                      device_type=torch.device("cuda", torch.cuda.current_device()))
         t = np.arange(args.max_iter) / max(args.max_iter - 1, 1)

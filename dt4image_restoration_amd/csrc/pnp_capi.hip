@@ -6,6 +6,7 @@
 #include "../../include/pnpadmm_dcf.h"
 #include "../../include/pnpadmm_offres.h"
 #include "../../include/pnpadmm_offres_ls.h"
+#include "../../include/pnpadmm_offres_mc.h"
 #include "../../include/pnpadmm_fieldmap.h"
 #include "pnp_internal.h"
 #include "denoiser_plan.h"
@@ -84,16 +85,18 @@ struct EventPair {
 // The handle's live data-fidelity stage: the constants installed LAST, which pnp_step / pnp_prox_dual solve with and PNP_RES_DC measures
 // against.  STAGE_NONE: nothing installed yet, or dropped with the plan it was built on; STAGE_CART: the closed form (pnp_reset /
 // pnp_set_kspace); STAGE_MC: SENSE; STAGE_NC: non-Cartesian; STAGE_NS: non-Cartesian SENSE; STAGE_OR: non-Cartesian with the
-// time-segmented off-resonance operator (include/pnpadmm_offres.h).  The four last run a CG on stage_normal().
+// time-segmented off-resonance operator (include/pnpadmm_offres.h); STAGE_ORS: that operator with coils (include/pnpadmm_offres_mc.h).
+// The five last run a CG on stage_normal().
 // Written by commit_stage and drop_stage only.
-enum StageKind { STAGE_NONE, STAGE_CART, STAGE_MC, STAGE_NC, STAGE_NS, STAGE_OR };
+enum StageKind { STAGE_NONE, STAGE_CART, STAGE_MC, STAGE_NC, STAGE_NS, STAGE_OR, STAGE_ORS };
 struct LiveStage {
     StageKind kind = STAGE_NONE;
     bool toeplitz = false;       // STAGE_NC, STAGE_NS: a _tz installer, the CG runs on the Toeplitz operator
-    int coils = 0;               // STAGE_MC, STAGE_NS: coils of the installed constants
+    int coils = 0;               // STAGE_MC, STAGE_NS, STAGE_ORS: coils of the installed constants
     int sens_n = 1;              // STAGE_OR: map_n of the installed field map
     int cg = 0;                  // CG iterations per step
-    bool has_w = false;          // STAGE_NC, STAGE_NS, STAGE_OR: weights were installed (nc_w / ns_w / or_w; else they are 1)
+    bool has_w = false;          // STAGE_NC, STAGE_NS, STAGE_OR, STAGE_ORS: weights were installed (nc_w / ns_w / or_w / om_w; else they are 1)
+    int map_n = 1;               // STAGE_ORS: map_n of the installed field map (sens_n is the coil maps')
 };
 
 }  // namespace
@@ -178,6 +181,23 @@ struct pnp_engine {
     double* or_mpart = nullptr;  // [N, nufft_sample_chunks(M)] partial sums of the misfit
     float2* or_amaps = nullptr;  // [map_n, L, H, W] pnp_acquire_offres' own segment maps: the installed ones stay as they are
     size_t or_maps_cap = 0, or_y_cap = 0, or_w_cap = 0, or_mpart_cap = 0, or_amaps_cap = 0;
+    // off-resonance correction for multi-coil data (include/pnpadmm_offres_mc.h): blocks of coils x segments go through the coil-block scratch
+    // above (ns_grid, ns_samp, ns_img), sized for them by om_ensure; the rest is this section's own
+    int om_block = 0;                    // coils per block: PNP_OFFRES_MC_COIL_BLOCK (read at pnp_create), or 0: the measured default of the live
+                                         // plan's interpolator (om_block_of)
+    int om_naive = kOffresMcNaiveSteps;  // OffresMcStep bits: the steps that run composed per coil (PNP_OFFRES_MC_NAIVE: all or none)
+    float2* om_samp = nullptr;   // [N, cbc, M] a coil block's samples (A p inside the normal operator, A x of the misfit)
+    float2* om_part = nullptr;   // [N, cbc, H, W] the segment chain's partials (allocated only when L > SB); composed adjoint: the coil images a_c
+    float2* om_img = nullptr;    // composed form only: [N, H, W] one coil's image
+    float2* om_line = nullptr;   // composed form only: [N, M] one coil's samples
+    float2* om_y = nullptr;      // [N, C, M] the installed samples
+    float2* om_sens = nullptr;   // [sens_n, C, H, W] the installed coil maps
+    float2* om_maps = nullptr;   // [map_n, L, H, W] the installed segment maps
+    float* om_w = nullptr;       // [M] the installed weights (read only through stage_w)
+    double* om_mpart = nullptr;  // [N, C, nufft_sample_chunks(M)] partial sums of the misfit
+    float2* om_amaps = nullptr;  // [map_n, L, H, W] pnp_acquire_offres_mc's own segment maps
+    size_t om_samp_cap = 0, om_part_cap = 0, om_img_cap = 0, om_line_cap = 0, om_y_cap = 0, om_sens_cap = 0, om_maps_cap = 0, om_w_cap = 0,
+           om_mpart_cap = 0, om_amaps_cap = 0;
     // Toeplitz normal operator (include/pnpadmm_toeplitz.h): the spectrum and its buffers by pnp_toeplitz_plan
     std::vector<double> nc_traj; // host copy of the planned trajectory [M][2] (ky, kx): what the spectrum is built from
     double* tz_traj = nullptr;   // [M][2] its device copy
@@ -447,7 +467,8 @@ int mc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
 // ---- non-Cartesian stage ----------------------------------------------------------------------------
 // the live non-Cartesian stage's weights (nullptr: 1)
 const float* stage_w(const pnp_engine* e) {
-    return !e->stage.has_w ? nullptr : e->stage.kind == STAGE_NS ? e->ns_w : e->stage.kind == STAGE_OR ? e->or_w : e->nc_w;
+    if (!e->stage.has_w) return nullptr;
+    return e->stage.kind == STAGE_NS ? e->ns_w : e->stage.kind == STAGE_OR ? e->or_w : e->stage.kind == STAGE_ORS ? e->om_w : e->nc_w;
 }
 // the centred transform of pnp_fft2c on the plan's grid, in place in nc_grid: rows then columns in both directions
 int nc_fft(pnp_engine* e, int batch, int inverse, hipStream_t s) {
@@ -664,6 +685,156 @@ int or_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
     return or_adjoint(e, e->nc_samp, stage_w(e), e->or_maps, e->stage.sens_n, N, pv, mu, tact, q, e->mc_part, s);
 }
 
+// ---- off-resonance correction for multi-coil data (include/pnpadmm_offres_mc.h) ----------------------------
+// coils per block: the knob, else the block that measured fastest under the live plan's interpolator (profiles/offres_mc_bench.json)
+int om_block_of(const pnp_engine* e, int coils) {
+    const int b = e->om_block > 0 ? e->om_block : e->orp.kind == 2 ? kOffresMcBlock : kOffresMcBlockLinear;
+    return coils < b ? coils : b;
+}
+// one coil's plane of a block buffer [batch, cb, len] <-> a contiguous [batch, len]
+int om_copy_out(float2* blk, int cb, int j, const float2* line, size_t len, int batch, hipStream_t s) {
+    HIP_TRY(hipMemcpy2DAsync(blk + (size_t)j * len, (size_t)cb * len * sizeof(float2), line, len * sizeof(float2), len * sizeof(float2), (size_t)batch,
+                             hipMemcpyDeviceToDevice, s));
+    return PNP_OK;
+}
+int om_copy_in(float2* line, const float2* blk, int cb, int j, size_t len, int batch, hipStream_t s) {
+    HIP_TRY(hipMemcpy2DAsync(line, len * sizeof(float2), blk + (size_t)j * len, (size_t)cb * len * sizeof(float2), len * sizeof(float2), (size_t)batch,
+                             hipMemcpyDeviceToDevice, s));
+    return PNP_OK;
+}
+// blk [batch, cb, M] = the samples of the coils c0 .. c0 + cb - 1 of A src, segment block by segment block: a sample's blend continues
+// through blk.  Composed: per coil the image S_c . src, the single-coil forward at batch `batch`, a strided copy
+int om_forward_block(pnp_engine* e, const float2* src, const float* src_real, const float2* maps, int map_n, const float2* sens, int sens_n, int C,
+                     int c0, int cb, int batch, float2* blk, hipStream_t s) {
+    const int L = e->orp.segments, B = or_block_of(e);
+    const size_t M = (size_t)e->nc.m;
+    const bool ls = e->orp.kind == 2;
+    if (e->om_naive & ORM_PAD) {
+        for (int j = 0; j < cb; ++j) {
+            {
+                Prof p(e, s, PROF_OTHER, -1);
+                HIP_TRY(launch_ncsense_expand(src, src_real, sens, sens_n, C, c0 + j, 1, e->nc, e->om_img, batch, s));
+            }
+            if (int rc = or_forward(e, e->om_img, nullptr, maps, map_n, batch, cb == 1 ? blk : e->om_line, s)) return rc;
+            if (cb != 1)
+                if (int rc = om_copy_out(blk, cb, j, e->om_line, M, batch, s)) return rc;
+        }
+        return PNP_OK;
+    }
+    for (int l0 = 0; l0 < L; l0 += B) {
+        const int sb = std::min(B, L - l0);
+        {
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_offres_mc_pad(src, src_real, sens, sens_n, C, c0, cb, maps, map_n, L, l0, sb, e->nc, e->ns_grid, batch, s));
+        }
+        if (int rc = ns_fft(e, batch * cb * sb, 0, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        if (or_naive_of(e) & OR_GATHER) {                  // the plan's gather ships composed: every plane's samples, then the blend
+            if (e->ns_naive & NS_GATHER) HIP_TRY(launch_nufft_interp(e->ns_grid, e->nc, e->ns_samp, batch * cb * sb, s));
+            else HIP_TRY(launch_ncsense_interp(e->ns_grid, e->nc, e->ns_samp, sb, 0, sb, batch * cb, s));
+            if (ls) HIP_TRY(launch_offres_ls_blend(e->ns_samp, e->orp, e->nc, blk, l0, sb, batch * cb, s));
+            else HIP_TRY(launch_offres_blend(e->ns_samp, e->orp, e->nc, blk, l0, sb, batch * cb, s));
+            p.end(2);
+        } else if (ls) {
+            HIP_TRY(launch_offres_ls_interp(e->ns_grid, e->orp, e->nc, blk, l0, sb, batch * cb, s));
+        } else {
+            HIP_TRY(launch_offres_interp(e->ns_grid, e->orp, e->nc, blk, l0, sb, batch * cb, s));
+        }
+    }
+    return PNP_OK;
+}
+// q (+)= sum over the block's coils of conj(S_c) . A_1^H(w . blk[., j]), A_1 the single-coil operator; blk: [batch, cb, M].  The coil chain
+// is carried from block to block through q; the last block adds mu pv and leaves the partial sums of Re<pv, q> (pv, mu, tact, partial may
+// be nullptr).  Composed: the single-coil adjoint per coil into om_part, then the SENSE combine
+int om_adjoint_block(pnp_engine* e, const float2* blk, const float* w, const float2* maps, int map_n, const float2* sens, int sens_n, int C, int c0,
+                     int cb, int batch, const float2* pv, const float* mu, const float* tact, float2* q, double* partial, hipStream_t s) {
+    const int L = e->orp.segments, B = or_block_of(e), H = e->cfg.h, W = e->cfg.w;
+    const size_t M = (size_t)e->nc.m;
+    const bool ls = e->orp.kind == 2;
+    if (e->om_naive & ORM_CROP) {
+        for (int j = 0; j < cb; ++j) {
+            const float2* yj = blk;
+            if (cb != 1) {
+                if (int rc = om_copy_in(e->om_line, blk, cb, j, M, batch, s)) return rc;
+                yj = e->om_line;
+            }
+            if (int rc = or_adjoint(e, yj, w, maps, map_n, batch, nullptr, nullptr, nullptr, cb == 1 ? e->om_part : e->om_img, nullptr, s)) return rc;
+            if (cb != 1)
+                if (int rc = om_copy_out(e->om_part, cb, j, e->om_img, (size_t)H * W, batch, s)) return rc;
+        }
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_ncsense_combine(e->om_part, sens, sens_n, C, c0, cb, e->nc, pv, mu, tact, q, partial, batch, s));
+        return PNP_OK;
+    }
+    for (int l0 = 0; l0 < L; l0 += B) {
+        const int sb = std::min(B, L - l0);
+        // the per-plan choices of or_adjoint, at batch `batch` cb
+        const bool ragged = ls && e->tune.offres_ls_naive < 0 && sb % kOffresLsSub != 0;
+        {
+            Prof p(e, s, PROF_OTHER, -1);
+            if ((or_naive_of(e) & OR_GRID) || ragged) {
+                if (ls) HIP_TRY(launch_offres_ls_expand(blk, e->orp, e->nc, e->ns_samp, l0, sb, batch * cb, s));
+                else HIP_TRY(launch_offres_expand(blk, e->orp, e->nc, e->ns_samp, l0, sb, batch * cb, s));
+                if (e->ns_naive & NS_GRID) HIP_TRY(launch_nufft_grid(e->ns_samp, w, e->nc, e->ns_grid, batch * cb * sb, s));
+                else HIP_TRY(launch_ncsense_grid(e->ns_samp, sb, 0, sb, w, e->nc, e->ns_grid, batch * cb, s));
+                p.end(2);
+            } else if (ls) {
+                HIP_TRY(launch_offres_ls_grid(blk, w, e->orp, e->nc, e->ns_grid, l0, sb, batch * cb, s, !e->tune.offres_ls_noskip));
+            } else {
+                HIP_TRY(launch_offres_grid(blk, w, e->orp, e->nc, e->ns_grid, l0, sb, batch * cb, s, e->tune.offres_grid_filter));
+            }
+        }
+        if (int rc = ns_fft(e, batch * cb * sb, 1, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_offres_mc_crop(e->ns_grid, sens, sens_n, C, c0, cb, maps, map_n, L, l0, sb, e->nc, e->om_part, pv, mu, tact, q, partial, batch,
+                                      s));
+    }
+    return PNP_OK;
+}
+// out [batch, C, M] = A src, coil block by coil block (a block that is not all of C goes through om_samp and a 2-D copy)
+int om_forward(pnp_engine* e, const float2* src, const float* src_real, const float2* maps, int map_n, const float2* sens, int sens_n, int C,
+               int batch, float2* out, hipStream_t s) {
+    const int B = om_block_of(e, C);
+    const size_t M = (size_t)e->nc.m;
+    for (int c0 = 0; c0 < C; c0 += B) {
+        const int cb = std::min(B, C - c0);
+        if (int rc = om_forward_block(e, src, src_real, maps, map_n, sens, sens_n, C, c0, cb, batch, cb == C ? out : e->om_samp, s)) return rc;
+        if (cb != C)
+            HIP_TRY(hipMemcpy2DAsync(out + (size_t)c0 * M, (size_t)C * M * sizeof(float2), e->om_samp, (size_t)cb * M * sizeof(float2),
+                                     (size_t)cb * M * sizeof(float2), (size_t)batch, hipMemcpyDeviceToDevice, s));
+    }
+    return PNP_OK;
+}
+// q [batch, h, w] = A^H (w . y), y: [batch, C, M]
+int om_adjoint(pnp_engine* e, const float2* y, const float* w, const float2* maps, int map_n, const float2* sens, int sens_n, int C, int batch,
+               float2* q, hipStream_t s) {
+    const int B = om_block_of(e, C);
+    const size_t M = (size_t)e->nc.m;
+    for (int c0 = 0; c0 < C; c0 += B) {
+        const int cb = std::min(B, C - c0);
+        if (cb != C)
+            HIP_TRY(hipMemcpy2DAsync(e->om_samp, (size_t)cb * M * sizeof(float2), y + (size_t)c0 * M, (size_t)C * M * sizeof(float2),
+                                     (size_t)cb * M * sizeof(float2), (size_t)batch, hipMemcpyDeviceToDevice, s));
+        if (int rc = om_adjoint_block(e, cb == C ? y : e->om_samp, w, maps, map_n, sens, sens_n, C, c0, cb, batch, nullptr, nullptr, nullptr, q,
+                                      nullptr, s))
+            return rc;
+    }
+    return PNP_OK;
+}
+// q = A^H W A pv + mu pv with the installed constants; the partial sums of Re<pv, q> go to mc_part.  Coil block by coil block, as ns_normal:
+// a block's samples go through om_samp whole - the blend joins segments - and are gridded before the next block's replace them.
+// Stopped slices: only the launches that write q skip them
+int om_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    const int N = e->cfg.n, C = e->stage.coils, sens_n = e->stage.sens_n, map_n = e->stage.map_n, B = om_block_of(e, C);
+    const float* w = stage_w(e);
+    for (int c0 = 0; c0 < C; c0 += B) {
+        const int cb = std::min(B, C - c0);
+        if (int rc = om_forward_block(e, pv, nullptr, e->om_maps, map_n, e->om_sens, sens_n, C, c0, cb, N, e->om_samp, s)) return rc;
+        if (int rc = om_adjoint_block(e, e->om_samp, w, e->om_maps, map_n, e->om_sens, sens_n, C, c0, cb, N, pv, mu, tact, q, e->mc_part, s)) return rc;
+    }
+    return PNP_OK;
+}
+
 // ---- Toeplitz normal operator (include/pnpadmm_toeplitz.h) ----------------------------------------------
 // q [planes, h, w] = crop(ifft2c(K . fft2c(pad(src)))) (+ mu pv with the partial sums of Re<pv, q>: the last launch's epilogue), through
 // tz_grid.  Three fused launches, or the seven composed ones; src may be q (the grid lies between them).  Stopped slices: only the last
@@ -742,6 +913,7 @@ NormalOp stage_normal(const pnp_engine* e) {
     case STAGE_NC: return e->stage.toeplitz ? tz_nc_normal : nc_normal;
     case STAGE_NS: return e->stage.toeplitz ? tz_ns_normal : ns_normal;
     case STAGE_OR: return or_normal;
+    case STAGE_ORS: return om_normal;
     default: return nullptr;
     }
 }
@@ -852,7 +1024,8 @@ void commit_stage(pnp_engine* e, const LiveStage& st) { e->stage = st; }
 // replaced loses its constants with it.  The closed-form and SENSE stages use neither and stay.
 void drop_stage(pnp_engine* e, bool toeplitz_only) {
     const LiveStage& st = e->stage;
-    if ((st.kind == STAGE_NC || st.kind == STAGE_NS || st.kind == STAGE_OR) && (st.toeplitz || !toeplitz_only)) e->stage = LiveStage{};
+    if ((st.kind == STAGE_NC || st.kind == STAGE_NS || st.kind == STAGE_OR || st.kind == STAGE_ORS) && (st.toeplitz || !toeplitz_only))
+        e->stage = LiveStage{};
 }
 
 // pnp_set_kspace (no iterate) / pnp_reset: the closed-form stage's constants
@@ -1050,6 +1223,20 @@ int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float
 int stage_misfit(pnp_engine* e, const float* x, double* dcpart, hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, C = e->stage.coils;
     switch (e->stage.kind) {
+    case STAGE_ORS: {
+        // the segmented A x coil block by coil block into the sample scratch, then the non-Cartesian SENSE stage's sums, coil-major
+        const int B = om_block_of(e, C);
+        for (int c0 = 0; c0 < C; c0 += B) {
+            const int cb = std::min(B, C - c0);
+            if (int rc = om_forward_block(e, nullptr, x, e->om_maps, e->stage.map_n, e->om_sens, e->stage.sens_n, C, c0, cb, N, e->om_samp, s))
+                return rc;
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_ncsense_misfit(e->om_samp, e->om_y, stage_w(e), C, c0, cb, e->nc, e->om_mpart, N, s));
+        }
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_ncsense_misfit_sum(e->om_mpart, C, e->nc, dcpart, N, s));
+        return PNP_OK;
+    }
     case STAGE_OR: {
         // the segmented A x into the sample scratch, then sum_m w_m |(A x)_m - y_m|^2
         if (int rc = or_forward(e, nullptr, x, e->or_maps, e->stage.sens_n, N, e->nc_samp, s)) return rc;
@@ -1107,6 +1294,8 @@ int need_stage(const char* fn, const pnp_engine* e, StageKind kind) {
     case STAGE_MC: return fail(PNP_ERR_STATE, "%s: the handle is in single-coil mode (pnp_set_kspace_mc / pnp_reset_mc)", fn);
     case STAGE_NC: return fail(PNP_ERR_STATE, "%s: the handle is not in non-Cartesian mode (pnp_set_kspace_nc / pnp_reset_nc)", fn);
     case STAGE_OR: return fail(PNP_ERR_STATE, "%s: the handle is not in off-resonance mode (pnp_set_kspace_offres / pnp_reset_offres)", fn);
+    case STAGE_ORS:
+        return fail(PNP_ERR_STATE, "%s: the handle is not in multi-coil off-resonance mode (pnp_set_kspace_offres_mc / pnp_reset_offres_mc)", fn);
     default: return fail(PNP_ERR_STATE, "%s: the handle is not in non-Cartesian SENSE mode (pnp_set_kspace_ncsense / pnp_reset_ncsense)", fn);
     }
 }
@@ -1201,6 +1390,8 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     if (tune.offres_block >= 1 && tune.offres_block <= PNP_MC_MAX_COILS) e->or_block = tune.offres_block;     // a check and a timing knob
     if (tune.offres_naive >= 0) e->or_naive = tune.offres_naive ? OR_ALL : 0;
     if (tune.offres_ls_naive >= 0) e->orls_naive = tune.offres_ls_naive ? OR_ALL : 0;
+    if (tune.offres_mc_block >= 1 && tune.offres_mc_block <= PNP_MC_MAX_COILS) e->om_block = tune.offres_mc_block;   // a check and a timing knob
+    if (tune.offres_mc_naive >= 0) e->om_naive = tune.offres_mc_naive ? ORM_ALL : 0;
     e->tz_fused = !tune.toeplitz_naive && kspace_len_ok(2 * cfg->h) && kspace_len_ok(2 * cfg->w) && toeplitz_fused_ok(cfg->h, cfg->w);
     e->dplan = plan;
     int rc;
@@ -1240,6 +1431,8 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->orp.tau); (void)hipFree(e->orp.seg); (void)hipFree(e->orp.b0); (void)hipFree(e->orp.b1); (void)hipFree(e->orp.list_off);
     (void)hipFree(e->orp.coef);
     (void)hipFree(e->orp.list_idx); (void)hipFree(e->or_maps); (void)hipFree(e->or_y); (void)hipFree(e->or_w); (void)hipFree(e->or_mpart); (void)hipFree(e->or_amaps);
+    (void)hipFree(e->om_samp); (void)hipFree(e->om_part); (void)hipFree(e->om_img); (void)hipFree(e->om_line); (void)hipFree(e->om_y);
+    (void)hipFree(e->om_sens); (void)hipFree(e->om_maps); (void)hipFree(e->om_w); (void)hipFree(e->om_mpart); (void)hipFree(e->om_amaps);
     (void)hipFree(e->dcf_grid); (void)hipFree(e->dcf_w); (void)hipFree(e->dcf_part); (void)hipFree(e->dcf_max);
     (void)hipFree(e->ns_grid); (void)hipFree(e->ns_samp); (void)hipFree(e->ns_y); (void)hipFree(e->ns_sens); (void)hipFree(e->ns_w); (void)hipFree(e->ns_mpart);
     (void)hipFree(e->nc_grid); (void)hipFree(e->nc_samp); (void)hipFree(e->nc_y); (void)hipFree(e->nc_w); (void)hipFree(e->nc_mpart);
@@ -2146,7 +2339,7 @@ int pnp_offres_plan(pnp_handle e, const double* t, int segments, int flags) {
     // from here on the old plan is gone: a live off-resonance stage's maps belong to its centres and are dropped with it
     D.segments = 0;
     D.kind = 0;
-    if (e->stage.kind == STAGE_OR) drop_stage(e, false);
+    if (e->stage.kind == STAGE_OR || e->stage.kind == STAGE_ORS) drop_stage(e, false);
     HIP_TRY(nc_upload(D.tau, P.tau.data(), P.tau.size() * sizeof(double)));
     HIP_TRY(nc_upload(D.seg, P.seg.data(), M * sizeof(int32_t)));
     HIP_TRY(nc_upload(D.b0, P.b0.data(), M * sizeof(float)));
@@ -2183,7 +2376,7 @@ int pnp_offres_plan_ls(pnp_handle e, const double* t, int segments, double omega
     // from here on the old plan is gone: a live off-resonance stage's maps belong to its plan and are dropped with it
     D.segments = 0;
     D.kind = 0;
-    if (e->stage.kind == STAGE_OR) drop_stage(e, false);
+    if (e->stage.kind == STAGE_OR || e->stage.kind == STAGE_ORS) drop_stage(e, false);
     HIP_TRY(nc_upload(D.tau, P.tau.data(), P.tau.size() * sizeof(double)));
     HIP_TRY(nc_upload(D.coef, P.coef.data(), P.coef.size() * sizeof(float)));
     D.segments = P.segments;
@@ -2332,6 +2525,204 @@ int pnp_acquire_offres(pnp_handle e, const float* gt, const float* omega, int ma
     }
     return PNP_OK;
     PNP_API_END("pnp_acquire_offres")
+}
+
+// ---- off-resonance correction for multi-coil data (include/pnpadmm_offres_mc.h) ----------------------------
+namespace {
+
+// argument errors shared by the entry points of that header: the scalar ranges need no handle and come first
+int om_check_scalars(const char* fn, int coils, int sens_n, int map_n) {
+    if (coils < 1 || coils > PNP_MC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_MC_MAX_COILS, coils);
+    if (sens_n < 1) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n (got %d)", fn, sens_n);
+    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    return PNP_OK;
+}
+int om_check(const char* fn, const pnp_engine* e, int coils, int sens_n, int map_n) {
+    const int N = e->cfg.n;
+    if (sens_n != 1 && sens_n != N) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n=%d", fn, N);
+    if (map_n != 1 && map_n != N) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n=%d", fn, N);
+    if (int rc = or_need_plan(fn, e)) return rc;
+    if ((long long)N * om_block_of(e, coils) * or_block_of(e) > 65535)
+        return fail(PNP_ERR_INVALID, "%s: n * min(coils, coil block) * min(segments, block) must be <= 65535 (got %d * %d * %d)", fn, N,
+                    om_block_of(e, coils), or_block_of(e));
+    return PNP_OK;
+}
+// the block scratch for `coils` coils - the coil-block scratch of the non-Cartesian SENSE stage for a block of coils x segments, the block's
+// samples and the segment chain's partials - and `amaps_need` bytes of the acquisition's own segment maps
+int om_ensure(pnp_engine* e, int coils, size_t amaps_need = 0) {
+    const size_t N = (size_t)e->cfg.n, cbc = (size_t)om_block_of(e, coils), planes = N * cbc * or_block_of(e);
+    const size_t HW = (size_t)e->cfg.h * e->cfg.w, M = (size_t)e->nc.m;
+    return ws_grow(e, "multi-coil off-resonance scratch",
+                   {{(void**)&e->ns_grid, &e->ns_grid_cap, planes * e->nc.gh * e->nc.gw * sizeof(float2), false},
+                    {(void**)&e->ns_samp, &e->ns_samp_cap, planes * M * sizeof(float2), false},
+                    {(void**)&e->ns_img, &e->ns_img_cap, (e->ns_naive & (NS_PAD | NS_CROP)) ? planes * HW * sizeof(float2) : 0, false},
+                    {(void**)&e->om_samp, &e->om_samp_cap, N * cbc * M * sizeof(float2), false},
+                    // the partials: the fused crop touches them only when the segments do not fit one block; the composed adjoint's coil images
+                    {(void**)&e->om_part, &e->om_part_cap,
+                     ((e->om_naive & ORM_CROP) || e->orp.segments > or_block_of(e)) ? N * cbc * HW * sizeof(float2) : 0, false},
+                    {(void**)&e->om_img, &e->om_img_cap, e->om_naive ? N * HW * sizeof(float2) : 0, false},
+                    {(void**)&e->om_line, &e->om_line_cap, e->om_naive ? N * M * sizeof(float2) : 0, false},
+                    {(void**)&e->om_amaps, &e->om_amaps_cap, amaps_need, false}});
+}
+
+// pnp_set_kspace_offres_mc (no iterate) / pnp_reset_offres_mc: the episode constants of the stage - y, w, the coil maps, the segment maps of
+// omega, A^H W y - and optionally the iterate.  Every rejection happens before any HIP call
+int om_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x0, const float2* y, const float2* sens, int coils, int sens_n,
+               const float* omega, int map_n, const float* w, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
+    int rc;
+    if ((rc = om_check_scalars(fn, coils, sens_n, map_n))) return rc;
+    if ((rc = nc_check_cg(fn, cg_iters))) return rc;
+    if (with_iterate && !x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
+    if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if ((rc = om_check(fn, e, coils, sens_n, map_n))) return rc;
+    PNP_ON_DEVICE(e);
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, L = e->orp.segments;
+    const size_t M = (size_t)e->nc.m, ym = (size_t)N * coils * M, sn = (size_t)sens_n * coils * H * W;
+    if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
+    if ((rc = om_ensure(e, coils))) return rc;
+    if ((rc = ws_grow(e, "multi-coil off-resonance constants",
+                      {{(void**)&e->om_y, &e->om_y_cap, ym * sizeof(float2), false},
+                       {(void**)&e->om_sens, &e->om_sens_cap, sn * sizeof(float2), false},
+                       {(void**)&e->om_maps, &e->om_maps_cap, (size_t)map_n * L * H * W * sizeof(float2), false},
+                       {(void**)&e->om_w, &e->om_w_cap, w ? M * sizeof(float) : 0, false},
+                       {(void**)&e->om_mpart, &e->om_mpart_cap, (size_t)N * coils * nufft_sample_chunks((int64_t)M) * sizeof(double), false}})))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(e->om_y, y, ym * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->om_sens, sens, sn * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    if (w) HIP_TRY(hipMemcpyAsync(e->om_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, e->om_maps, s));
+    }
+    if ((rc = om_adjoint(e, e->om_y, w ? e->om_w : nullptr, e->om_maps, map_n, e->om_sens, sens_n, coils, N, mc_aty(e), s))) return rc;
+    if (with_iterate) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
+    }
+    commit_stage(e, {STAGE_ORS, false, coils, sens_n, cg_iters, w != nullptr, map_n});
+    return PNP_OK;
+}
+
+}  // namespace
+
+int pnp_offres_forward_mc(pnp_handle e, const float* img, const float* maps, int map_n, const float* sens, int sens_n, int coils, int batch,
+                          float* samples, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_forward_mc";
+    if (int rc = om_check_scalars(fn, coils, sens_n, map_n)) return rc;
+    if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
+    if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
+    if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!samples) return fail(PNP_ERR_INVALID, "%s: null samples", fn);
+    if (samples == img || samples == maps || samples == sens) return fail(PNP_ERR_INVALID, "%s: samples must not alias img, maps or sens", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
+    if (int rc = om_check(fn, e, coils, sens_n, map_n)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = om_ensure(e, coils)) return rc;
+    return om_forward(e, (const float2*)img, nullptr, (const float2*)maps, map_n, (const float2*)sens, sens_n, coils, batch, (float2*)samples,
+                      (hipStream_t)stream);
+    PNP_API_END("pnp_offres_forward_mc")
+}
+
+int pnp_offres_adjoint_mc(pnp_handle e, const float* samples, const float* weights, const float* maps, int map_n, const float* sens, int sens_n,
+                          int coils, int batch, float* img, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_adjoint_mc";
+    if (int rc = om_check_scalars(fn, coils, sens_n, map_n)) return rc;
+    if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
+    if (!samples) return fail(PNP_ERR_INVALID, "%s: null samples", fn);
+    if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
+    if (img == samples || img == maps || img == sens || (const float*)img == weights)
+        return fail(PNP_ERR_INVALID, "%s: img must not alias samples, weights, maps or sens", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
+    if (int rc = om_check(fn, e, coils, sens_n, map_n)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = om_ensure(e, coils)) return rc;
+    return om_adjoint(e, (const float2*)samples, weights, (const float2*)maps, map_n, (const float2*)sens, sens_n, coils, batch, (float2*)img,
+                      (hipStream_t)stream);
+    PNP_API_END("pnp_offres_adjoint_mc")
+}
+
+int pnp_set_kspace_offres_mc(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, const float* omega, int map_n, const float* w,
+                             int cg_iters, void* stream) {
+    PNP_API_BEGIN
+    return om_install("pnp_set_kspace_offres_mc", e, false, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n, w, cg_iters,
+                      nullptr, nullptr, nullptr, (hipStream_t)stream);
+    PNP_API_END("pnp_set_kspace_offres_mc")
+}
+
+int pnp_reset_offres_mc(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, const float* omega, int map_n,
+                        const float* w, int cg_iters, float* x, float* z, float* u, void* stream) {
+    PNP_API_BEGIN
+    return om_install("pnp_reset_offres_mc", e, true, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n, w,
+                      cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
+    PNP_API_END("pnp_reset_offres_mc")
+}
+
+int pnp_offres_mc_coils(pnp_handle e) { return e && e->stage.kind == STAGE_ORS ? e->stage.coils : 0; }
+
+int pnp_offres_mc_cg_residual(pnp_handle e, float* out, void* stream) {
+    PNP_API_BEGIN
+    return stage_cg_residual("pnp_offres_mc_cg_residual", e, STAGE_ORS, out, (hipStream_t)stream);
+    PNP_API_END("pnp_offres_mc_cg_residual")
+}
+
+int pnp_offres_mc_normal(pnp_handle e, const float* pv, const float* mu, float* q, void* stream) {
+    PNP_API_BEGIN
+    return stage_normal_op("pnp_offres_mc_normal", e, STAGE_ORS, pv, mu, q, (hipStream_t)stream);
+    PNP_API_END("pnp_offres_mc_normal")
+}
+
+int pnp_acquire_offres_mc(pnp_handle e, const float* gt, const float* sens, int coils, int sens_n, const float* omega, int map_n, const float* dcf,
+                          double sigma_n, uint64_t seed, int flags, float* y, float* aty0, float* x0, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_acquire_offres_mc";
+    // every rejection happens before any HIP call, and leaves the outputs untouched
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "%s: sigma_n must be finite and >= 0 (got %g)", fn, sigma_n);
+    if (int rc = om_check_scalars(fn, coils, sens_n, map_n)) return rc;
+    if (!gt) return fail(PNP_ERR_INVALID, "%s: null gt", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    const auto input = [&](const float* p) { return p == gt || p == sens || p == omega; };
+    if (input(y) || (aty0 && (input(aty0) || aty0 == y)) || (x0 && (input(x0) || x0 == y)))
+        return fail(PNP_ERR_INVALID, "%s: no output may alias gt, sens, omega or another output", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = om_check(fn, e, coils, sens_n, map_n)) return rc;
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = om_ensure(e, coils, (size_t)map_n * e->orp.segments * H * W * sizeof(float2)))) return rc;
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, e->om_amaps, s));
+    }
+    if ((rc = om_forward(e, nullptr, gt, e->om_amaps, map_n, (const float2*)sens, sens_n, coils, N, (float2*)y, s))) return rc;
+    if (sigma_n != 0.0) {                                   // a noiseless acquisition draws nothing and keeps the forward's own bits
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_ncsense_noise((float2*)y, sigma_n, seed, coils, e->nc, N, s));
+    }
+    if (!aty0 && !x0) return PNP_OK;
+    float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the image goes to the data-fidelity stage's scratch plane
+    if ((rc = om_adjoint(e, (const float2*)y, dcf, e->om_amaps, map_n, (const float2*)sens, sens_n, coils, N, a, s))) return rc;
+    if (x0) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
+    }
+    return PNP_OK;
+    PNP_API_END("pnp_acquire_offres_mc")
 }
 
 // ---- Toeplitz normal operator (include/pnpadmm_toeplitz.h) ----------------------------------------------

@@ -48,6 +48,10 @@ struct Tuning {
                                   // kernels, 0 = the two-segment gather and gridding; unset: kOffresNaiveSteps, the choice per step by measurement
     int offres_ls_naive = -1;     // PNP_OFFRES_LS_NAIVE (tests, timing): the same choice under a least-squares plan; unset: kOffresLsNaiveSteps
     bool offres_ls_noskip = false;   // PNP_OFFRES_LS_NOSKIP (timing): the dense gridding without its wave-uniform row skip; the same numbers
+    int offres_mc_block = 0;      // PNP_OFFRES_MC_COIL_BLOCK (tests, timing): coils per block of the multi-coil off-resonance operator, 1..32
+                                  // (else: kOffresMcBlock)
+    int offres_mc_naive = -1;     // PNP_OFFRES_MC_NAIVE (tests, timing): 1 = that operator composed per coil from the single-coil operator between
+                                  // an expand and a combine kernel, 0 = the fused pad and crop; unset: kOffresMcNaiveSteps
 };
 Tuning tuning_from_env();
 
@@ -514,6 +518,26 @@ hipError_t launch_offres_ls_expand(const float2* y, const OffresDev& R, const Nu
 // atomics; skip: a wave passes over a sample that touches none of its rows (false: PNP_OFFRES_LS_NOSKIP, timing)
 hipError_t launch_offres_ls_grid(const float2* y, const float* w, const OffresDev& R, const NufftDev& P, float2* grid, int l0, int cb, int batch,
                                  hipStream_t s, bool skip = true);
+
+// ---- off-resonance correction for multi-coil data (offres_mc_kernels.hip; include/pnpadmm_offres_mc.h) ---------
+// default coils per block (PNP_OFFRES_MC_COIL_BLOCK overrides both): the fastest of 1 / 2 / 4 as measured (profiles/offres_mc_bench.json,
+// DESIGN.md 4a) - 4 under a least-squares plan (step 0.72x of the composed form at L = 8; 2: 0.79x), 2 under a linear plan (0.92x at
+// L = 32; 4: 0.99x)
+static constexpr int kOffresMcBlock = 4;
+static constexpr int kOffresMcBlockLinear = 2;
+// the two steps that exist in a fused and a composed form, as bits: which of them run composed.  Both give the same bits
+enum OffresMcStep : int { ORM_PAD = 1, ORM_CROP = 2, ORM_ALL = 3 };
+// the shipped choice (profiles/offres_mc_bench.json): both fused steps measured no slower than the composed form
+static constexpr int kOffresMcNaiveSteps = 0;
+// grid [batch, cbc, sb, gh, gw] = zero-padded (cy cx) . (E_(l0+k) . (S_(c0+j) . src)); src complex, or src_real
+hipError_t launch_offres_mc_pad(const float2* src, const float* src_real, const float2* sens, int sens_n, int C, int c0, int cbc, const float2* maps,
+                                int map_n, int L, int l0, int sb, const NufftDev& P, float2* grid, int batch, hipStream_t s);
+// the segment chain per coil through part [batch, cbc, h, w] (read unless l0 == 0, written unless l0 + sb == L), then on the last segment
+// block the coil chain through q (read unless c0 == 0); the last coil block adds mu pv and leaves the partial sums of Re<pv, q> (pv, mu,
+// tact, partial may be nullptr)
+hipError_t launch_offres_mc_crop(const float2* grid, const float2* sens, int sens_n, int C, int c0, int cbc, const float2* maps, int map_n, int L,
+                                 int l0, int sb, const NufftDev& P, float2* part, const float2* pv, const float* mu, const float* tact, float2* q,
+                                 double* partial, int batch, hipStream_t s);
 
 // ---- field map estimation (fieldmap_kernels.hip; the fit: include/pnpadmm_fieldmap.h) ----------------------------
 // The fused kernel's plan: kFmT sweeps per launch over a kFmRegion^2 region, of which the kFmTile^2 tile is stored

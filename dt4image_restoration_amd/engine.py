@@ -485,7 +485,7 @@ class PnPEngine:
         m = self.nufft_samples
         if m and t.size != m:
             raise ValueError(f"times: expected {m} samples, got {t.shape}")
-        if self.offres_live:
+        if self.offres_live or self.offres_mc_coils:
             self.live_episode = 0
         self._offres_key = None
         _lib.check(self.lib.pnp_offres_plan(self._h, t.ctypes.data, int(segments), 0), "pnp_offres_plan")
@@ -501,7 +501,7 @@ class PnPEngine:
         m = self.nufft_samples
         if m and t.size != m:
             raise ValueError(f"times: expected {m} samples, got {t.shape}")
-        if self.offres_live:
+        if self.offres_live or self.offres_mc_coils:
             self.live_episode = 0
         self._offres_key = None
         _lib.check(self.lib.pnp_offres_plan_ls(self._h, t.ctypes.data, int(segments), float(omega_max), 0), "pnp_offres_plan_ls")
@@ -638,6 +638,92 @@ class PnPEngine:
         _lib.check(self.lib.pnp_acquire_offres(self._h, gt.data_ptr(), omega.data_ptr(), map_n, dcf.data_ptr() if dcf is not None else None,
                                                float(sigma_n), int(seed) & (2 ** 64 - 1), 0, y.data_ptr(), aty0.data_ptr(), x0.data_ptr(),
                                                self._stream()), "pnp_acquire_offres")
+        return y, aty0, x0
+
+    # -- off-resonance correction for multi-coil data (include/pnpadmm_offres_mc.h) -----------
+    @property
+    def offres_mc_coils(self) -> int:
+        """Coils of the live multi-coil off-resonance stage (pnp_offres_mc_coils); 0 while another stage is live."""
+        return int(self.lib.pnp_offres_mc_coils(self._h))
+
+    def offres_forward_mc(self, img: torch.Tensor, maps: torch.Tensor, sens: torch.Tensor) -> torch.Tensor:
+        """samples complex64 [B,C,M] = [sum_l b_l F_nu(E_l . S_c . img)]_c (pnp_offres_forward_mc) on the live off-resonance plan, linear or
+        least squares; img complex64 [B,H,W] (or [B,1,H,W]), B <= N; maps from `offres_maps`; sens complex64 [C,H,W] or [N,C,H,W]."""
+        b = self._batch_of(img, self.h * self.w, "img")
+        self._chk(img, torch.complex64, img.numel(), "img")
+        maps, map_n = self._offres_maps_arg(maps)
+        sens, coils, sens_n = self._sens(sens)
+        out = torch.empty((b, coils, max(self.nufft_samples, 1)), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_offres_forward_mc(self._h, img.data_ptr(), maps.data_ptr(), map_n, sens.data_ptr(), sens_n, coils, b,
+                                                  out.data_ptr(), self._stream()), "pnp_offres_forward_mc")
+        return out
+
+    def offres_adjoint_mc(self, samples: torch.Tensor, maps: torch.Tensor, sens: torch.Tensor,
+                          weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """img complex64 [B,H,W] = sum_c conj(S_c) . sum_l conj(E_l) . F_nu^H(weights . b_l . samples_c) (pnp_offres_adjoint_mc); samples
+        complex64 [B,C,M], weights float32 [M] or None."""
+        m = self.nufft_samples
+        maps, map_n = self._offres_maps_arg(maps)
+        sens, coils, sens_n = self._sens(sens)
+        b = self._batch_of(samples, coils * m, "samples")
+        self._chk(samples, torch.complex64, samples.numel(), "samples")
+        if weights is not None:
+            self._chk(weights, torch.float32, m, "weights")
+        out = torch.empty((b, self.h, self.w), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_offres_adjoint_mc(self._h, samples.data_ptr(), weights.data_ptr() if weights is not None else None,
+                                                  maps.data_ptr(), map_n, sens.data_ptr(), sens_n, coils, b, out.data_ptr(), self._stream()),
+                   "pnp_offres_adjoint_mc")
+        return out
+
+    def reset_offres_mc(self, x0: torch.Tensor, y: torch.Tensor, sens: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None,
+                        cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Install the multi-coil off-resonance constants (y complex64 [N,C,M], sens complex64 [C,H,W] or [N,C,H,W], omega float32 [H,W] or
+        [N,H,W] in rad/s, w float32 [M] or None) and start an episode from x0 complex64 [N,1,H,W] (pnp_reset_offres_mc).  Returns fresh
+        (x f32, z c64, u c64); steps then solve the k-space subproblem by `cg_iters` CG iterations on A^H W A + mu I with the coils times
+        segments operator A."""
+        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
+        yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
+        omega, map_n = self._omega(omega)
+        x, z, u = self._iterate()
+        _lib.check(self.lib.pnp_reset_offres_mc(self._h, x0.data_ptr(), yp, sp, coils, sens_n, omega.data_ptr(), map_n, wp, int(cg_iters),
+                                                x.data_ptr(), z.data_ptr(), u.data_ptr(), self._stream()), "pnp_reset_offres_mc")
+        self.live_episode = _next_episode()
+        return x, z, u
+
+    def set_kspace_offres_mc(self, y: torch.Tensor, sens: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None,
+                             episode: int = 0, cg_iters: int = 8) -> None:
+        """Re-install the multi-coil off-resonance constants of another episode without touching any iterate (pnp_set_kspace_offres_mc)."""
+        yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
+        omega, map_n = self._omega(omega)
+        _lib.check(self.lib.pnp_set_kspace_offres_mc(self._h, yp, sp, coils, sens_n, omega.data_ptr(), map_n, wp, int(cg_iters), self._stream()),
+                   "pnp_set_kspace_offres_mc")
+        self.live_episode = episode or _next_episode()
+
+    def offres_mc_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+        """q = A^H W A p + mu p with the installed multi-coil off-resonance constants (pnp_offres_mc_normal); p complex64 [N,1,H,W], mu
+        float32 [N]."""
+        return self._normal("pnp_offres_mc_normal", p, mu)
+
+    def offres_mc_cg_residual(self) -> torch.Tensor:
+        """float32 [N]: the relative residual the CG solve of the last step ended with (pnp_offres_mc_cg_residual; that mode only)."""
+        return self._cg_residual("pnp_offres_mc_cg_residual")
+
+    def acquire_offres_mc(self, gt: torch.Tensor, sens: torch.Tensor, omega: torch.Tensor, sigma_n: float, seed: int,
+                          dcf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Simulated multi-coil acquisition under the field map on the planned trajectory and times (pnp_acquire_offres_mc): gt float32
+        [N,1,H,W]; returns (y complex64 [N,C,M], aty0 = A^H (dcf . y) complex64 [N,1,H,W], x0 = max(aty0, 0))."""
+        gt = self._chk(gt, torch.float32, self.n * self.h * self.w, "gt")
+        sens, coils, sens_n = self._sens(sens)
+        omega, map_n = self._omega(omega)
+        m = self.nufft_samples
+        if dcf is not None:
+            self._chk(dcf, torch.float32, m, "dcf")
+        y = torch.empty((self.n, coils, max(m, 1)), dtype=torch.complex64, device=self.device)
+        aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+        x0 = torch.empty_like(aty0)
+        _lib.check(self.lib.pnp_acquire_offres_mc(self._h, gt.data_ptr(), sens.data_ptr(), coils, sens_n, omega.data_ptr(), map_n,
+                                                  dcf.data_ptr() if dcf is not None else None, float(sigma_n), int(seed) & (2 ** 64 - 1), 0,
+                                                  y.data_ptr(), aty0.data_ptr(), x0.data_ptr(), self._stream()), "pnp_acquire_offres_mc")
         return y, aty0, x0
 
     # -- field map estimation (include/pnpadmm_fieldmap.h) ----------------------------------

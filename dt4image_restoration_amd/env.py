@@ -39,9 +39,10 @@ def _as_complex(t: torch.Tensor) -> torch.Tensor:
 class PnPEnv:
     def __init__(self, max_episode_step: int, denoiser: UNetDenoiser2D, device_type,
                  no_ref_scorer: Optional[Callable[[torch.Tensor], float]] = None, replica: int = 0, cg_iters: int = 8,
-                 nufft_width: int = 6, nufft_grid=None, nc_normal: str = "nufft") -> None:
+                 nufft_width: int = 6, nufft_grid=None, nc_normal: str = "nufft", offres_mc: bool = False) -> None:
         if nc_normal not in ("nufft", "toeplitz"):
             raise ValueError(f"nc_normal must be 'nufft' or 'toeplitz', got {nc_normal!r}")
+        self.offres_mc = bool(offres_mc)        # data["omega"] with data["sens"]: the coils x segments stage (include/pnpadmm_offres_mc.h)
         self.nc_normal = nc_normal              # non-Cartesian episodes: the form of A^H W A inside the CG (include/pnpadmm_toeplitz.h)
         self.max_episode_step = max_episode_step
         self.cg_iters = int(cg_iters)           # multi-coil and non-Cartesian episodes: conjugate-gradient iterations per step
@@ -57,7 +58,8 @@ class PnPEnv:
         """Another env on the same denoiser weights whose engines are replicas of their own (own workspace, own k-space
         constants): two sub-batches of one job can then be stepped concurrently on two streams."""
         return PnPEnv(self.max_episode_step, self.denoiser, self._device_type, self.no_ref_model, replica=replica, cg_iters=self.cg_iters,
-                      nufft_width=self.nufft_width, nufft_grid=self.nufft_grid, nc_normal=self.nc_normal)
+                      nufft_width=self.nufft_width, nufft_grid=self.nufft_grid, nc_normal=self.nc_normal,
+                      offres_mc=getattr(self, "offres_mc", False))
 
     # ---- engine management ------------------------------------------------------------------
     def _engine_for(self, n: int, h: int, w: int, device: torch.device) -> PnPEngine:
@@ -112,7 +114,7 @@ class PnPEnv:
         traj = torch.as_tensor(data["traj"]).to(torch.float64).cpu().reshape(-1, 2).contiguous()      # (the caller's own tensor when it is one)
         m = traj.shape[0]
         sens = data.get("sens")
-        if sens is not None and data.get("omega") is not None:
+        if sens is not None and data.get("omega") is not None and not getattr(self, "offres_mc", False):
             raise ValueError("an off-resonance episode is single-coil (data['omega'] with data['sens'] is not supported)")
         if sens is not None:
             sens = torch.as_tensor(sens)
@@ -180,8 +182,9 @@ class PnPEnv:
     def _reset_offres(self, data, eng: PnPEngine, x0, y0, sens, dcf, gt, traj, n: int, device) -> "OrderedDict[str, torch.Tensor]":
         """An off-resonance episode: data["omega"] float32 [H,W] or [N,H,W] in rad/s, data["times"] float64 [M] seconds, optional
         data["segments"], optional data["b0_interp"] "linear" | "ls" (the least-squares temporal interpolator over the map's own band,
-        max |omega| (1 + 1e-6)); single-coil, gridding form of the normal operator."""
-        if sens is not None:
+        max |omega| (1 + 1e-6)); gridding form of the normal operator.  Single-coil, unless the env was made with offres_mc=True: then
+        data["sens"] beside data["omega"] installs the coils x segments stage (`PnPEngine.reset_offres_mc`), y0 [N,C,M]."""
+        if sens is not None and not getattr(self, "offres_mc", False):
             raise ValueError("an off-resonance episode is single-coil (data['omega'] with data['sens'] is not supported)")
         if self.nc_normal == "toeplitz":
             raise ValueError("an off-resonance episode has no Toeplitz normal operator (nc_normal='toeplitz' with data['omega'])")
@@ -190,11 +193,14 @@ class PnPEnv:
         interp = self._interp_of(data)
         extra = {} if interp == "linear" else {"b0_interp": interp, "omega_max": float(omega.abs().max()) * (1.0 + 1e-6)}
         self._offres_plan(eng, times, seg, interp, extra.get("omega_max"))
-        x, z, u = eng.reset_offres(x0, y0, omega, dcf, cg_iters=self.cg_iters)
+        if sens is not None:
+            x, z, u = eng.reset_offres_mc(x0, y0, sens, omega, dcf, cg_iters=self.cg_iters)
+        else:
+            x, z, u = eng.reset_offres(x0, y0, omega, dcf, cg_iters=self.cg_iters)
         aty0 = torch.as_tensor(data["ATy0"])[..., 0] if "ATy0" in data else None
         return OrderedDict({"x": x, "y0": y0, "z": z, "u": u, "mask": None, "gt": gt, "ATy0": aty0,
                             "T": torch.zeros(n, dtype=torch.float32, device=device),
-                            "complex_y0": data["y0"], "_episode": eng.live_episode, "sens": None, "traj": traj, "dcf": dcf,
+                            "complex_y0": data["y0"], "_episode": eng.live_episode, "sens": sens, "traj": traj, "dcf": dcf,
                             "omega": omega, "times": times, "segments": seg, **extra})
 
     def _bind_episode(self, eng: PnPEngine, states) -> None:
@@ -213,6 +219,11 @@ class PnPEnv:
             tz = self.nc_normal == "toeplitz"   # (the engine re-plans the spectrum when the plan or the episode's weights changed)
             y = states["y0"]
             y = y if y.is_complex() else _as_complex(y)
+            if states.get("omega") is not None and states.get("sens") is not None:      # a multi-coil off-resonance episode
+                sens = states["sens"]
+                eng.set_kspace_offres_mc(y.reshape(n, sens.shape[-3], -1).to(eng.device).contiguous(), sens, states["omega"], states.get("dcf"),
+                                         episode=ep, cg_iters=self.cg_iters)
+                return
             if states.get("omega") is not None:  # an off-resonance episode
                 eng.set_kspace_offres(y.reshape(n, -1).to(eng.device).contiguous(), states["omega"], states.get("dcf"), episode=ep,
                                       cg_iters=self.cg_iters)

@@ -316,3 +316,35 @@ def make_problem_ncmc(n: int, h: int, w: int, coils: int, traj: np.ndarray, dcf:
         aty0[i, 0, ..., 0], aty0[i, 0, ..., 1] = a.real, a.imag
     x0 = np.clip(aty0, 0.0, None)
     return {"x0": x0, "y0": y0, "ATy0": aty0, "gt": gt, "x0_raw": aty0[..., 0].copy(), "traj": traj, "dcf": d, "sens": sens}
+
+
+def make_problem_ncmcb0(n: int, h: int, w: int, coils: int, traj: np.ndarray, times: np.ndarray, omega: np.ndarray, dcf: np.ndarray = None,
+                        sigma_n: float = 10.0 / 255.0, seed: int = 1234, first_slice: int = 0, sens: np.ndarray = None) -> Dict[str, np.ndarray]:
+    """`make_problem_ncb0` for `coils` coils (off-resonance correction for multi-coil data, include/pnpadmm_offres_mc.h), by the exact
+    operator in float64 (small sizes): y0 float32 [n,coils,M,2] with y_c = A_exact (S_c gt) + sigma_n noise_c under the field map `omega`
+    (float32 [h,w] or [n,h,w], rad/s) at the sample times `times`, noise_c as in `make_problem_ncmc`; ATy0 = sum_c conj(S_c) A_exact^H (dcf y_c)
+    and x0 = its clip at 0.  The dict carries `omega`, `times` and `sens` (complex64 [coils,h,w]: `coil_maps` unless given) beside `traj` and `dcf`."""
+    traj = np.asarray(traj, dtype=np.float64)
+    t = np.asarray(times, dtype=np.float64).reshape(-1)
+    m = traj.shape[0]
+    om = np.asarray(omega, dtype=np.float32)
+    d = None if dcf is None else np.asarray(dcf, dtype=np.float32)
+    sens = (coil_maps(coils, h, w) if sens is None else np.asarray(sens)).astype(np.complex64)
+    s64 = sens.astype(np.complex128)
+    gt = np.empty((n, 1, h, w), dtype=np.float32)
+    y0 = np.empty((n, coils, m, 2), dtype=np.float32)
+    aty0 = np.empty((n, 1, h, w, 2), dtype=np.float32)
+    for i in range(n):
+        s = seed + first_slice + i
+        g = phantom(h, w, s)
+        oi = om if om.ndim == 2 else om[i]
+        a = np.zeros((h, w), dtype=np.complex128)
+        for c in range(coils):
+            y = offres_ndft_np(traj, t, oi, s64[c] * g) + (_gauss(s, 9001 + 4 * c, m) + 1j * _gauss(s, 9003 + 4 * c, m)) * sigma_n
+            a += np.conj(s64[c]) * offres_ndft_np(traj, t, oi, y if d is None else y * d.astype(np.float64), adjoint_shape=(h, w))
+            y0[i, c, :, 0], y0[i, c, :, 1] = y.real, y.imag
+        gt[i, 0] = g
+        aty0[i, 0, ..., 0], aty0[i, 0, ..., 1] = a.real, a.imag
+    x0 = np.clip(aty0, 0.0, None)
+    return {"x0": x0, "y0": y0, "ATy0": aty0, "gt": gt, "x0_raw": aty0[..., 0].copy(), "traj": traj, "dcf": d, "omega": om, "times": t,
+            "sens": sens}

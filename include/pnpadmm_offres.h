@@ -17,7 +17,8 @@
  * ERROR OF THE MODEL.  Between two centres the chord deviates from the arc by at most 1 - cos(omega D / 2), so
  *     |A p - A_exact p|_m  <=  (1 - cos(omega_max D / 2)) ||p||_1   for every m
  * (on top of the NUFFT's own error).  Min-max interpolators, coils times segments, and a Toeplitz form of this operator are OUT OF SCOPE:
- * the stage is single-coil and its CG runs on the gridding form; the _tz installers of pnpadmm_toeplitz.h are untouched.
+ * the stage is single-coil and its CG runs on the gridding form; the _tz installers of pnpadmm_toeplitz.h are untouched.  (Coils times
+ * segments have since been added as an operator pair and a stage of their own: pnpadmm_offres_mc.h.  This header is as it was.)
  *
  * EXPRESSION ORDER.  float32 throughout; every operation named below is ONE IEEE operation, an fma only where one is written.  F_nu / F_nu^H
  * are pnp_nufft_forward_mc / pnp_nufft_adjoint_mc of pnpadmm_ncsense.h with the L maps E_l in the place of the coil maps: the segment image
