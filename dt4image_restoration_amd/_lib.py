@@ -188,6 +188,23 @@ SIGNATURES_OFFRES_MC = {
 PNP_OFFRES_MC_COIL_BLOCK = 4     # default coils per block under a least-squares plan, and 2 under a linear one (the environment variable of the
 PNP_OFFRES_MC_COIL_BLOCK_LINEAR = 2   # first name, read at pnp_create, overrides both)
 
+# name -> (restype, argtypes); every symbol include/pnpadmm_offres_tz.h declares (the Toeplitz form of the off-resonance normal operator)
+SIGNATURES_OFFRES_TZ = {
+    "pnp_offres_tz_plan": (C.c_int, [C.c_void_p, _fp, C.c_int, _vp]),
+    "pnp_offres_tz_planned": (C.c_int, [C.c_void_p]),
+    "pnp_offres_tz_live": (C.c_int, [C.c_void_p]),
+    "pnp_offres_tz_spectra": (C.c_int, [C.c_void_p]),
+    "pnp_offres_tz_spectrum": (C.c_int, [C.c_void_p, _fp, _vp]),
+    "pnp_offres_tz_apply": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_offres_tz_apply_mc": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _vp]),
+    "pnp_set_kspace_offres_tz": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _vp]),
+    "pnp_reset_offres_tz": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _vp]),
+    "pnp_set_kspace_offres_mc_tz": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _vp]),
+    "pnp_reset_offres_mc_tz": (C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _vp]),
+}
+PNP_OFFRES_TZ_MAX_PAIRS = 136    # spectra of one plan: 16 segments under a least-squares plan, 32 under a linear one
+PNP_OFFRES_TZ_PLANES = 512       # planes (slices x segments) in flight in the pass buffers
+
 # name -> (restype, argtypes); every symbol include/pnpadmm_fieldmap.h declares (the B0 field map from two echo images)
 SIGNATURES_FIELDMAP = {
     "pnp_fieldmap_estimate": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_double, C.c_float, C.c_int, C.c_int, _fp, _fp, _vp]),
@@ -203,6 +220,24 @@ def toeplitz_size_error(fn: str, h: int, w: int):
     if h <= PNP_TOEPLITZ_MAX_SIDE and w <= PNP_TOEPLITZ_MAX_SIDE:
         return None
     return f"{fn}: the Toeplitz operator transforms a 2h x 2w grid, so it takes h, w up to {PNP_TOEPLITZ_MAX_SIDE} (got {int(h)}x{int(w)})"
+
+def offres_tz_pairs(interpolator: str, segments: int) -> int:
+    """P, the spectra the Toeplitz form of the off-resonance operator stores for a plan: the band under the linear interpolator, the upper
+    triangle under least squares."""
+    L = int(segments)
+    return 2 * L - 1 if interpolator == "linear" else L * (L + 1) // 2
+
+
+def offres_tz_pairs_error(fn: str, interpolator: str, segments: int):
+    """The library's refusal of a plan with too many spectra, word for word (offres_tz_plan.hip: plan_offres_tz), or None: for a caller that
+    knows the plan before it has a handle."""
+    pairs = offres_tz_pairs(interpolator, segments)
+    if pairs <= PNP_OFFRES_TZ_MAX_PAIRS:
+        return None
+    kind = "linear" if interpolator == "linear" else "least-squares"
+    return (f"{fn}: {int(segments)} segments under a {kind} plan need {pairs} spectra, more than the limit of {PNP_OFFRES_TZ_MAX_PAIRS} "
+            f"(16 segments least squares, 32 linear)")
+
 
 _lib = None
 
@@ -221,7 +256,7 @@ def load() -> C.CDLL:
                        f"or `make -C {os.path.dirname(LIB_PATH)}`; there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **SIGNATURES_NCSENSE, **SIGNATURES_TOEPLITZ, **SIGNATURES_DCF, **SIGNATURES_OFFRES,
-                              **SIGNATURES_OFFRES_LS, **SIGNATURES_OFFRES_MC, **SIGNATURES_FIELDMAP}.items():
+                              **SIGNATURES_OFFRES_LS, **SIGNATURES_OFFRES_MC, **SIGNATURES_FIELDMAP, **SIGNATURES_OFFRES_TZ}.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -28,6 +28,7 @@ layout has none):
     ... --traj spiral [--interleaves L] | --traj rosette [--petals P]  [--nc-weights none|dcf|pipe] [--dcf-iters I] eval|flex|mcts|fixed|acquire ...
     ... --traj radial --nc-coils 4 [--cg-iters K] eval|flex|mcts|fixed|acquire ...      (non-Cartesian SENSE: the radial acquisition of C coils)
     ... --traj spiral --b0 HZ --readout-ms T --b0-coils 4 [--b0-interp ls] [--b0-segments L] eval|flex|mcts|fixed ...   (coils x segments stage)
+    ... --traj spiral --b0 HZ --readout-ms T [--b0-coils 4] --b0-normal toeplitz eval|flex|mcts|fixed ...   (the CG on the Toeplitz form of A^H W A)
     ... --coils 4 --sens estimate [--sens-window hann|box] [--sens-thresh 0.05] [--acs H W] --mask cartesian fixed ...
 
     ... --coils 8 --sens espirit [--espirit-kernel 6] [--espirit-sv 0.02] [--espirit-crop 0.9] [--espirit-iters 16] --mask cartesian fixed ...
@@ -109,7 +110,7 @@ def _build(args, mode):
     scorer = (lambda st: 1.0 / (1e-3 + (st["x"] - torch.nn.functional.avg_pool2d(st["x"], 3, 1, 1)).pow(2).mean(dim=(1, 2, 3))))
     env = PnPEnv(max_episode_step=30, denoiser=den, device_type="cuda", no_ref_scorer=None, cg_iters=args.cg_iters,
                  nufft_width=args.nufft_width, nufft_grid=args.nufft_grid, nc_normal=args.nc_normal,
-                 offres_mc=bool(getattr(args, "b0_coils", 0)))
+                 offres_mc=bool(getattr(args, "b0_coils", 0)), offres_normal=getattr(args, "b0_normal", "nufft"))
     if getattr(args, "scorer", "stub") == "neg_dc":            # minus the k-space data misfit of the rollout's final iterate (pnp_residuals)
         scorer = (lambda st: -env.residuals(st, dc=True)[:, 5])
     return model, env, scorer
@@ -245,6 +246,12 @@ def _sets(args, flex_target=None, env=None):
                 why = _lib.toeplitz_size_error("pnp_toeplitz_plan", *batch["gt"].shape[-2:])
                 if why:
                     raise SystemExit(f"--nc-normal toeplitz: task {task}: {why}")
+            if getattr(args, "b0_normal", "nufft") == "toeplitz":   # likewise: the slice size and the plan's spectra are known here
+                interp = "ls" if batch.get("b0_interp") in ("ls", _lib.OFFRES_INTERPOLATORS["ls"]) else "linear"
+                why = (_lib.toeplitz_size_error("pnp_offres_tz_plan", *batch["gt"].shape[-2:])
+                       or _lib.offres_tz_pairs_error("pnp_offres_tz_plan", interp, int(batch["segments"])))
+                if why:
+                    raise SystemExit(f"--b0-normal toeplitz: task {task}: {why}")
             return batch, D.task_tokens([task] * (b - a), flex_target)
         if args.gt:
             for d in args.gt:
@@ -411,6 +418,10 @@ def main(argv=None):
     ap.add_argument("--b0-interp", choices=("linear", "ls"), default="linear", help="--b0: the temporal interpolator between the time segments: "
                     "linear (two segments per sample), or ls: least-squares coefficients for every segment, fitted over the map's band - the "
                     "same accuracy from about a quarter of the segments")
+    ap.add_argument("--b0-normal", choices=("nufft", "toeplitz"), default="nufft", help="--b0: the normal operator A^H W A inside the CG of the "
+                    "off-resonance stage, single-coil or --b0-coils: the gridding pair, or its Toeplitz form - 2 L transforms of the 2H x 2W grid "
+                    "and one mix with spectra built once per trajectory, times plan and weights (sides up to 512; at most 136 spectra: 32 "
+                    "segments linear, 16 with --b0-interp ls)")
     ap.add_argument("--b0-coils", type=int, default=0, metavar="C", help="--b0: the multi-coil acquisition under the field map, C coils with "
                     "analytic coil maps (1..32; default 0: single-coil), reconstructed with the coils x segments off-resonance stage (eval / flex / "
                     "mcts / fixed; not with --nc-coils, --coils, --nc-normal toeplitz or --b0-map estimate)")
@@ -524,12 +535,21 @@ def main(argv=None):
                 raise SystemExit("--b0 with --nc-coils: the off-resonance stage is single-coil")
             if args.nc_normal == "toeplitz":
                 raise SystemExit("--b0 with --nc-normal toeplitz: the off-resonance stage has no Toeplitz form")
+            if args.b0_normal == "toeplitz" and args.mode == "acquire":
+                raise SystemExit("acquire runs no CG: drop --b0-normal toeplitz")
             if args.mode == "acquire":
                 raise SystemExit("--b0 is for eval / flex / mcts / fixed")
             if args.b0_segments != "auto":
                 if not str(args.b0_segments).isdigit() or not 1 <= int(args.b0_segments) <= 32:
                     raise SystemExit(f"--b0-segments must be 1..32 or auto, got {args.b0_segments}")
                 args.b0_segments = int(args.b0_segments)
+            if args.b0_normal == "toeplitz":                 # what is known here is refused here, in the library's words
+                from ._lib import offres_tz_pairs_error, toeplitz_size_error
+                why = None if getattr(args, "gt", None) else toeplitz_size_error("pnp_offres_tz_plan", args.size, args.size)
+                if not why and args.b0_segments != "auto":
+                    why = offres_tz_pairs_error("pnp_offres_tz_plan", args.b0_interp, args.b0_segments)
+                if why:
+                    raise SystemExit(f"--b0-normal toeplitz: {why}")
         elif args.readout_ms is not None or args.b0_segments != "auto":
             raise SystemExit("--readout-ms / --b0-segments need --b0")
         elif args.b0_interp != "linear":
@@ -557,6 +577,8 @@ def main(argv=None):
         raise SystemExit("--b0 / --readout-ms / --b0-segments need --traj")
     elif args.b0_interp != "linear":
         raise SystemExit("--b0-interp needs --b0")
+    if args.b0 is None and args.b0_normal != "nufft":
+        raise SystemExit(f"--b0-normal {args.b0_normal} needs --b0")
     if args.b0 is None:
         if args.b0_map != "true" or args.b0_dte is not None or args.b0_beta is not None or args.b0_iters is not None:
             raise SystemExit("--b0-map / --b0-dte / --b0-beta / --b0-iters need --b0")
@@ -670,7 +692,7 @@ def main(argv=None):
         den = _denoiser(args)
         env = PnPEnv(max_episode_step=args.max_iter, denoiser=den, device_type="cuda", cg_iters=args.cg_iters,
                      nufft_width=args.nufft_width, nufft_grid=args.nufft_grid, nc_normal=args.nc_normal,
-                 offres_mc=bool(getattr(args, "b0_coils", 0)))
+                     offres_mc=bool(getattr(args, "b0_coils", 0)), offres_normal=getattr(args, "b0_normal", "nufft"))
         solver = FixedScheduleSolver(env, max_iter=args.max_iter, tol=args.tol, sync_every=5, dc=args.dc,
                                      device_type=torch.device("cuda", torch.cuda.current_device()))
         t = np.arange(args.max_iter) / max(args.max_iter - 1, 1)

@@ -805,6 +805,8 @@ Tuning tuning_from_env() {
     if (const char* v = getenv("PNP_OFFRES_LS_NOSKIP")) t.offres_ls_noskip = atoi(v) != 0;
     if (const char* v = getenv("PNP_OFFRES_MC_COIL_BLOCK")) t.offres_mc_block = atoi(v);
     if (const char* v = getenv("PNP_OFFRES_MC_NAIVE")) t.offres_mc_naive = atoi(v) != 0 ? 1 : 0;
+    if (const char* v = getenv("PNP_OFFRES_TZ_NAIVE")) t.offres_tz_naive = atoi(v) != 0;
+    if (const char* v = getenv("PNP_OFFRES_TZ_SLICE_BLOCK")) t.offres_tz_slices = atoi(v);
     return t;
 }
 

@@ -1176,6 +1176,81 @@ hipError_t launch_toeplitz_rows_inv(const float2* buf, const float2* tw, const f
     return hipGetLastError();
 }
 
+// ---- Toeplitz form of the off-resonance operator: the two column passes of its fused application (include/pnpadmm_offres_tz.h) ----------
+// tz_cols_kernel cut in two, because the spectral mix between the transforms reads all L planes of a slice at one bin:
+//   columns forward : a strip's H live rows of half [planes, H, 2W] into lines of 2H, zeros elsewhere -> forward -> the whole column spectrum
+//                     into full [planes, 2H, 2W], centred rows
+//   columns inverse : a strip's lines of full -> inverse -> the H cropped rows into half
+// Both store unscaled, as the row passes do: the mix carries 1 / (4 H W).  The same line transforms as tz_cols_kernel, by the same rule.
+// INV = false: in = half, out = full; INV = true: in = full, out = half
+template <int LC, bool INV>
+__global__ __launch_bounds__(256) void tz_cols_half_kernel(const float2* __restrict__ in, float2* __restrict__ out, const float2* __restrict__ twg,
+                                                           int H, int W, int cw) {
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    constexpr bool R16 = LC == 256, R8 = LC == 512;
+    const int L = 2 * H, GW = 2 * W, strips = GW / cw;
+    int vb = blockIdx.x;                                   // fft_cols_kernel's (slice, strip) -> XCD map
+    if ((gridDim.x & 7) == 0) vb = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
+    const int n = vb / strips, x0 = (vb % strips) * cw;
+    const int lstr = R16 ? SK256_LS : (R8 ? SK512_LS : L + 1);
+    auto rpos = [](int r) { return R16 ? sk256(r) : (R8 ? sk512(r) : r); };
+    float2* buf0 = smem;
+    float2* buf1 = smem + cw * lstr;
+    float2* tw = smem + (LC > 0 ? 1 : 2) * cw * lstr;
+    const float2* half_in = in + (size_t)n * H * GW;
+    const float2* full_in = in + (size_t)n * L * GW;
+    float2* half_out = out + (size_t)n * H * GW;
+    float2* full_out = out + (size_t)n * L * GW;
+    const int lcw = 31 - __builtin_clz(cw), tot = cw * L;
+    for (int i = threadIdx.x; i < L; i += 256) tw[i] = twg[i];
+    for (int e = threadIdx.x; e < tot; e += 256) {
+        const int r = e >> lcw, c = e & (cw - 1);          // position r of the unshifted line holds the centred padded row r ^ H
+        float2 v = make_float2(0.f, 0.f);
+        if (INV) {
+            v = full_in[(size_t)(r ^ H) * GW + x0 + c];
+        } else {
+            const int iy = (r ^ H) - H / 2;
+            if (iy >= 0 && iy < H) v = half_in[(size_t)iy * GW + x0 + c];
+        }
+        buf0[c * lstr + rpos(r)] = v;
+    }
+    __syncthreads();
+    const float2* res;
+    if constexpr (R16) { fft256_radix16_inplace<INV, 16>(buf0, tw); res = buf0; }
+    else if constexpr (R8) { fft512_radix8_inplace<INV, 8, 32>(buf0, tw); res = buf0; }
+    else res = fft_lines<INV>(buf0, buf1, tw, L, cw, lstr);
+    if (INV) {
+        for (int e = threadIdx.x; e < cw * H; e += 256) {
+            const int iy = e >> lcw, c = e & (cw - 1);
+            half_out[(size_t)iy * GW + x0 + c] = res[c * lstr + rpos((iy + H / 2) ^ H)];
+        }
+    } else {
+        for (int e = threadIdx.x; e < tot; e += 256) {
+            const int r = e >> lcw, c = e & (cw - 1);
+            full_out[(size_t)(r ^ H) * GW + x0 + c] = res[c * lstr + rpos(r)];
+        }
+    }
+}
+
+template <bool INV>
+static hipError_t launch_tz_cols_half(const float2* in, float2* out, const float2* tw, int planes, int H, int W, hipStream_t s) {
+    if (!toeplitz_fused_ok(H, W)) return hipErrorInvalidValue;
+    static DeviceOnce once;
+    if (hipError_t e = pnp::raise_lds_cap((const void*)tz_cols_half_kernel<0, INV>, 80 * 1024, once); e != hipSuccess) return e;
+    const int L = 2 * H, cw = cols_per_block(L, 2 * W);
+    const dim3 g((unsigned)(planes * (2 * W / cw)));
+    if (L == 256) hipLaunchKernelGGL((tz_cols_half_kernel<256, INV>), g, dim3(256), (size_t)(cw * SK256_LS + L) * sizeof(float2), s, in, out, tw, H, W, cw);
+    else if (L == 512) hipLaunchKernelGGL((tz_cols_half_kernel<512, INV>), g, dim3(256), (size_t)(cw * SK512_LS + L) * sizeof(float2), s, in, out, tw, H, W, cw);
+    else hipLaunchKernelGGL((tz_cols_half_kernel<0, INV>), g, dim3(256), (size_t)(2 * cw * (L + 1) + L) * sizeof(float2), s, in, out, tw, H, W, cw);
+    return hipGetLastError();
+}
+hipError_t launch_offres_tz_cols_fwd(const float2* half, float2* full, const float2* tw, int planes, int H, int W, hipStream_t s) {
+    return launch_tz_cols_half<false>(half, full, tw, planes, H, W, s);
+}
+hipError_t launch_offres_tz_cols_inv(const float2* full, float2* half, const float2* tw, int planes, int H, int W, hipStream_t s) {
+    return launch_tz_cols_half<true>(full, half, tw, planes, H, W, s);
+}
+
 // ---- reset: x = Re(x0), z = x0, u = 0; fold the fftshifts into the episode constants -------------
 __global__ void reset_kernel(const float2* __restrict__ x0, const float2* __restrict__ y0,
                              const uint8_t* __restrict__ mask, int mask_n, float* __restrict__ x,

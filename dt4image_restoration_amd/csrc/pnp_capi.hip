@@ -8,11 +8,13 @@
 #include "../../include/pnpadmm_offres_ls.h"
 #include "../../include/pnpadmm_offres_mc.h"
 #include "../../include/pnpadmm_fieldmap.h"
+#include "../../include/pnpadmm_offres_tz.h"
 #include "pnp_internal.h"
 #include "denoiser_plan.h"
 #include "nufft_plan.h"
 #include "offres_plan.h"
 #include "offres_ls_plan.h"
+#include "offres_tz_plan.h"
 #include "block_reduce.h"
 
 #include <cmath>
@@ -97,6 +99,7 @@ struct LiveStage {
     int cg = 0;                  // CG iterations per step
     bool has_w = false;          // STAGE_NC, STAGE_NS, STAGE_OR, STAGE_ORS: weights were installed (nc_w / ns_w / or_w / om_w; else they are 1)
     int map_n = 1;               // STAGE_ORS: map_n of the installed field map (sens_n is the coil maps')
+    bool offres_tz = false;      // STAGE_OR, STAGE_ORS: a _tz installer of include/pnpadmm_offres_tz.h, the CG runs on that header's operator
 };
 
 }  // namespace
@@ -211,6 +214,24 @@ struct pnp_engine {
     size_t tz_traj_cap = 0, tz_k_cap = 0, tz_w_cap = 0, tz_twh_cap = 0, tz_tww_cap = 0, tz_grid_cap = 0;
     bool tz_planned = false;     // a spectrum exists for the handle's NUFFT plan
     bool tz_has_w = false;
+    // Toeplitz form of the off-resonance operator (include/pnpadmm_offres_tz.h): the spectra and the pass buffers by pnp_offres_tz_plan
+    std::vector<int32_t> or_seg_h;   // host copy of the linear plan's segment per sample: what the per-pair sample lists are built from
+    OffresTzDev otz;             // the uploaded pair plan; otz.pairs == 0: none
+    double* otz_traj = nullptr;  // [M][2] device copy of the trajectory
+    float* otz_k = nullptr;      // [P, 2H, 2W] the spectra, centred
+    float* otz_w = nullptr;      // [M] the weights the spectra were built with (read only while otz_has_w): the installers' weights
+    float2* otz_tw_h = nullptr;  // twiddles of 2H and 2W
+    float2* otz_tw_w = nullptr;
+    float2* otz_img = nullptr;   // [planes, H, W] the slice block's segment images E_l . p, then the cropped results
+    float2* otz_x = nullptr;     // [planes, 2H, 2W] the two pass buffers: transforms in x, mix x -> y, transforms back in y (composed);
+    float2* otz_y = nullptr;     // fused: rows into y's first half, columns y -> x, mix x -> y, columns y -> x's first half, rows out of x
+    float2* otz_cimg = nullptr;  // multi-coil: [N, CB, H, W] the coil block's images S_c . p, then their results
+    size_t otz_off_cap = 0, otz_idx_cap = 0, otz_traj_cap = 0, otz_k_cap = 0, otz_w_cap = 0, otz_twh_cap = 0, otz_tww_cap = 0, otz_img_cap = 0,
+           otz_x_cap = 0, otz_y_cap = 0, otz_cimg_cap = 0;
+    bool otz_planned = false;    // spectra exist for the handle's NUFFT plan and off-resonance plan
+    bool otz_has_w = false;
+    bool otz_fused = false;      // the application runs the fused passes (set at pnp_create: a power-of-two padded grid and no PNP_OFFRES_TZ_NAIVE)
+    int otz_slices = 0;          // PNP_OFFRES_TZ_SLICE_BLOCK (read at pnp_create), or 0: kOffresTzPlanes / L
     // density compensation (include/pnpadmm_dcf.h): its own workspace, grown inside pnp_nufft_psi / pnp_nufft_dcf
     double* dcf_grid = nullptr;  // [gh, gw] G^T w
     double* dcf_w = nullptr;     // [M] the float64 iterate
@@ -903,6 +924,105 @@ int tz_ns_normal(pnp_engine* e, const float2* pv, const float* mu, const float* 
     return tz_apply_mc(e, pv, e->ns_sens, e->stage.sens_n, e->stage.coils, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
 }
 
+// ---- Toeplitz form of the off-resonance operator (include/pnpadmm_offres_tz.h) ------------------------------
+// slices per block of an application over `batch` slices: all L planes of a slice are in flight for the mix
+int otz_slice_block(const pnp_engine* e, int batch) {
+    const int L = e->orp.segments;
+    int nb = e->otz_slices > 0 ? e->otz_slices : std::max(1, kOffresTzPlanes / L);
+    nb = std::min(nb, std::max(1, 16384 / L));              // (planes index a launch grid's y)
+    return std::min(nb, batch);
+}
+// q [batch, h, w] = sum_l conj(E_l) . crop(ifft2c(sum_l' K_ll' . fft2c(pad(E_l' . src)))) (+ mu pv with the partial sums of Re<pv, q>: the
+// combine's epilogue; pv, mu, tact, partial may be nullptr), slice block by slice block through otz_img, otz_x and otz_y.  src may be q: a
+// block's slices are read by its first launch and written by its last.  Stopped slices: only the combine skips them
+int otz_apply(pnp_engine* e, const float2* src, const float2* maps, int map_n, int batch, const float2* pv, const float* mu, const float* tact,
+              float2* q, double* partial, hipStream_t s) {
+    const int H = e->cfg.h, W = e->cfg.w, L = e->orp.segments, kind = e->orp.kind;
+    const size_t hw = (size_t)H * W;
+    const int NB = otz_slice_block(e, batch), chunks = pixel_chunks(H, W);
+    for (int n0 = 0; n0 < batch; n0 += NB) {
+        const int nb = std::min(NB, batch - n0), planes = nb * L;
+        const float2* mb = map_n == 1 ? maps : maps + (size_t)n0 * L * hw;
+        {
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_ncsense_expand(src + (size_t)n0 * hw, nullptr, mb, map_n, L, 0, L, e->nc, e->otz_img, nb, s));
+        }
+        if (e->otz_fused) {
+            {
+                Prof p(e, s, PROF_FFT_ROWS, -1);
+                HIP_TRY(launch_toeplitz_rows_fwd(e->otz_img, e->otz_y, e->otz_tw_w, planes, H, W, s));
+            }
+            {
+                Prof p(e, s, PROF_FFT_COLS, -1);
+                HIP_TRY(launch_offres_tz_cols_fwd(e->otz_y, e->otz_x, e->otz_tw_h, planes, H, W, s));
+            }
+            {
+                Prof p(e, s, PROF_OTHER, -1);
+                HIP_TRY(launch_offres_tz_mix(e->otz_x, e->otz_y, e->otz_k, kind, L, H, W, nb, 1.f / (4.f * (float)H * (float)W), s));
+            }
+            {
+                Prof p(e, s, PROF_FFT_COLS, -1);
+                HIP_TRY(launch_offres_tz_cols_inv(e->otz_y, e->otz_x, e->otz_tw_h, planes, H, W, s));
+            }
+            Prof p(e, s, PROF_FFT_ROWS, -1);
+            HIP_TRY(launch_toeplitz_rows_inv(e->otz_x, e->otz_tw_w, nullptr, nullptr, nullptr, e->otz_img, nullptr, planes, H, W, s));
+        } else {
+            auto fft = [&](float2* grid, int inverse) -> int {
+                {
+                    Prof p(e, s, PROF_FFT_ROWS, -1);
+                    HIP_TRY(launch_fft_rows(grid, grid, e->otz_tw_w, planes, 2 * H, 2 * W, inverse, W, s));
+                }
+                Prof p(e, s, PROF_FFT_COLS, -1);
+                HIP_TRY(launch_fft_cols(grid, e->otz_tw_h, planes, 2 * H, 2 * W, inverse, H, s));
+                return PNP_OK;
+            };
+            {
+                Prof p(e, s, PROF_OTHER, -1);
+                HIP_TRY(launch_toeplitz_pad(e->otz_img, e->otz_x, H, W, planes, s));
+            }
+            if (int rc = fft(e->otz_x, 0)) return rc;
+            {
+                Prof p(e, s, PROF_OTHER, -1);
+                HIP_TRY(launch_offres_tz_mix(e->otz_x, e->otz_y, e->otz_k, kind, L, H, W, nb, 1.f, s));
+            }
+            if (int rc = fft(e->otz_y, 1)) return rc;
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_toeplitz_crop(e->otz_y, nullptr, nullptr, nullptr, e->otz_img, nullptr, H, W, planes, s));
+        }
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_ncsense_combine(e->otz_img, mb, map_n, L, 0, L, e->nc, pv ? pv + (size_t)n0 * hw : nullptr, mu ? mu + n0 : nullptr,
+                                       tact ? tact + n0 : nullptr, q + (size_t)n0 * hw, partial ? partial + (size_t)n0 * chunks * 2 : nullptr, nb, s));
+    }
+    return PNP_OK;
+}
+// coils per block of the multi-coil application: the coil block of the multi-coil off-resonance stage while the segment maps are shared; with
+// per-slice maps a coil image's slice must stay the slice of its maps, so the coils go one at a time
+int otz_coil_block(const pnp_engine* e, int coils, int map_n) { return map_n == 1 ? om_block_of(e, coils) : 1; }
+// out [batch, h, w] = sum over the coils of conj(S_c) . [otz_apply](S_c . src), block by block in place in otz_cimg; the coil chain is
+// carried through out, the last block adds mu pv and leaves the partial sums of Re<pv, out>
+int otz_apply_mc(pnp_engine* e, const float2* src, const float2* maps, int map_n, const float2* sens, int sens_n, int C, int batch, const float2* pv,
+                 const float* mu, const float* tact, float2* out, double* partial, hipStream_t s) {
+    const int B = otz_coil_block(e, C, map_n);
+    for (int c0 = 0; c0 < C; c0 += B) {
+        const int cb = std::min(B, C - c0);
+        {
+            Prof p(e, s, PROF_OTHER, -1);
+            HIP_TRY(launch_ncsense_expand(src, nullptr, sens, sens_n, C, c0, cb, e->nc, e->otz_cimg, batch, s));
+        }
+        if (int rc = otz_apply(e, e->otz_cimg, maps, map_n, batch * cb, nullptr, nullptr, nullptr, e->otz_cimg, nullptr, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_ncsense_combine(e->otz_cimg, sens, sens_n, C, c0, cb, e->nc, pv, mu, tact, out, partial, batch, s));
+    }
+    return PNP_OK;
+}
+// the two stages' normal operators in this form: q = A^H W A pv + mu pv, the partial sums of Re<pv, q> in mc_part
+int otz_or_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    return otz_apply(e, pv, e->or_maps, e->stage.sens_n, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
+}
+int otz_om_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    return otz_apply_mc(e, pv, e->om_maps, e->stage.map_n, e->om_sens, e->stage.sens_n, e->stage.coils, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
+}
+
 // the K-step CG solve of (A^H A + mu I) z = A^H y + mu (x + u), warm-started from z, then u <- u + x - z; `normal`: the stage's normal
 // operator (mc_normal: the coil operator, nc_normal: the NUFFT pair, ns_normal: both), which also leaves the partial sums of Re<p, q> in mc_part
 using NormalOp = int (*)(pnp_engine*, const float2*, const float*, const float*, float2*, hipStream_t);
@@ -912,8 +1032,8 @@ NormalOp stage_normal(const pnp_engine* e) {
     case STAGE_MC: return mc_normal;
     case STAGE_NC: return e->stage.toeplitz ? tz_nc_normal : nc_normal;
     case STAGE_NS: return e->stage.toeplitz ? tz_ns_normal : ns_normal;
-    case STAGE_OR: return or_normal;
-    case STAGE_ORS: return om_normal;
+    case STAGE_OR: return e->stage.offres_tz ? otz_or_normal : or_normal;
+    case STAGE_ORS: return e->stage.offres_tz ? otz_om_normal : om_normal;
     default: return nullptr;
     }
 }
@@ -1393,6 +1513,8 @@ int pnp_create(const pnp_config* cfg, pnp_handle* out) {
     if (tune.offres_mc_block >= 1 && tune.offres_mc_block <= PNP_MC_MAX_COILS) e->om_block = tune.offres_mc_block;   // a check and a timing knob
     if (tune.offres_mc_naive >= 0) e->om_naive = tune.offres_mc_naive ? ORM_ALL : 0;
     e->tz_fused = !tune.toeplitz_naive && kspace_len_ok(2 * cfg->h) && kspace_len_ok(2 * cfg->w) && toeplitz_fused_ok(cfg->h, cfg->w);
+    e->otz_fused = !tune.offres_tz_naive && kspace_len_ok(2 * cfg->h) && kspace_len_ok(2 * cfg->w) && toeplitz_fused_ok(cfg->h, cfg->w);
+    if (tune.offres_tz_slices >= 1) e->otz_slices = tune.offres_tz_slices;   // a check, not a mode
     e->dplan = plan;
     int rc;
     {
@@ -1433,6 +1555,8 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->orp.list_idx); (void)hipFree(e->or_maps); (void)hipFree(e->or_y); (void)hipFree(e->or_w); (void)hipFree(e->or_mpart); (void)hipFree(e->or_amaps);
     (void)hipFree(e->om_samp); (void)hipFree(e->om_part); (void)hipFree(e->om_img); (void)hipFree(e->om_line); (void)hipFree(e->om_y);
     (void)hipFree(e->om_sens); (void)hipFree(e->om_maps); (void)hipFree(e->om_w); (void)hipFree(e->om_mpart); (void)hipFree(e->om_amaps);
+    (void)hipFree(e->otz.blk_off); (void)hipFree(e->otz.blk_idx); (void)hipFree(e->otz_traj); (void)hipFree(e->otz_k); (void)hipFree(e->otz_w);
+    (void)hipFree(e->otz_tw_h); (void)hipFree(e->otz_tw_w); (void)hipFree(e->otz_img); (void)hipFree(e->otz_x); (void)hipFree(e->otz_y); (void)hipFree(e->otz_cimg);
     (void)hipFree(e->dcf_grid); (void)hipFree(e->dcf_w); (void)hipFree(e->dcf_part); (void)hipFree(e->dcf_max);
     (void)hipFree(e->ns_grid); (void)hipFree(e->ns_samp); (void)hipFree(e->ns_y); (void)hipFree(e->ns_sens); (void)hipFree(e->ns_w); (void)hipFree(e->ns_mpart);
     (void)hipFree(e->nc_grid); (void)hipFree(e->nc_samp); (void)hipFree(e->nc_y); (void)hipFree(e->nc_w); (void)hipFree(e->nc_mpart);
@@ -1961,6 +2085,7 @@ int pnp_nufft_plan(pnp_handle e, const double* traj, int64_t m, int gh, int gw, 
     e->tz_planned = false;                                  // the spectrum belongs to the plan it was built for
     e->orp.segments = 0;                                    // ... and so does the off-resonance plan
     e->orp.kind = 0;
+    e->otz_planned = false;                                 // ... and the spectra built on the two
     e->nc_traj.assign(traj, traj + 2 * (size_t)m);
     e->nc_bin_off_h = P.bin_off;
     e->nc_bin_idx_h = P.bin_idx;
@@ -2270,10 +2395,25 @@ int or_ensure(pnp_engine* e, size_t maps_need = 0) {
                                                {(void**)&e->or_amaps, &e->or_amaps_cap, maps_need, false}});
 }
 
-// pnp_set_kspace_offres (no iterate) / pnp_reset_offres: the episode constants of the stage - y, w, the segment maps of omega, A^H W y - and
-// optionally the iterate.  Every rejection happens before any HIP call
-int or_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x0, const float2* y, const float* omega, int map_n, const float* w,
-               int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
+// the Toeplitz spectra of include/pnpadmm_offres_tz.h, which its installers and applications need
+int otz_need_spectra(const char* fn, const pnp_engine* e) {
+    if (int rc = or_need_plan(fn, e)) return rc;
+    return e->otz_planned ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no Toeplitz off-resonance spectra (pnp_offres_tz_plan)", fn);
+}
+// the pass buffers of that form for applications over `slices` slices and, multi-coil, `cimg_planes` coil images
+int otz_ensure(pnp_engine* e, int slices, size_t cimg_planes) {
+    const size_t hw = (size_t)e->cfg.h * e->cfg.w, planes = (size_t)otz_slice_block(e, slices) * e->orp.segments;
+    return ws_grow(e, "Toeplitz off-resonance scratch", {{(void**)&e->otz_img, &e->otz_img_cap, planes * hw * sizeof(float2), false},
+                                                        {(void**)&e->otz_x, &e->otz_x_cap, planes * 4 * hw * sizeof(float2), false},
+                                                        {(void**)&e->otz_y, &e->otz_y_cap, planes * 4 * hw * sizeof(float2), false},
+                                                        {(void**)&e->otz_cimg, &e->otz_cimg_cap, cimg_planes * hw * sizeof(float2), false}});
+}
+
+// pnp_set_kspace_offres (no iterate) / pnp_reset_offres and, `toeplitz`, their _tz forms of include/pnpadmm_offres_tz.h (w: the spectra's
+// weights, whatever is passed): the episode constants of the stage - y, w, the segment maps of omega, A^H W y - and optionally the iterate.
+// Every rejection happens before any HIP call
+int or_install(const char* fn, pnp_engine* e, bool with_iterate, bool toeplitz, const float2* x0, const float2* y, const float* omega, int map_n,
+               const float* w, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
     int rc;
     if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
     if ((rc = nc_check_cg(fn, cg_iters))) return rc;
@@ -2283,11 +2423,14 @@ int or_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x
     if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if ((rc = or_check(fn, e, map_n))) return rc;
+    if (toeplitz && (rc = otz_need_spectra(fn, e))) return rc;
     PNP_ON_DEVICE(e);
+    if (toeplitz) w = e->otz_has_w ? e->otz_w : nullptr;
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, L = e->orp.segments;
     const size_t M = (size_t)e->nc.m;
     if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
     if ((rc = or_ensure(e))) return rc;
+    if (toeplitz && (rc = otz_ensure(e, N, 0))) return rc;
     if ((rc = ws_grow(e, "off-resonance constants",
                       {{(void**)&e->or_y, &e->or_y_cap, (size_t)N * M * sizeof(float2), false},
                        {(void**)&e->or_maps, &e->or_maps_cap, (size_t)map_n * L * H * W * sizeof(float2), false},
@@ -2306,7 +2449,7 @@ int or_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
     }
-    commit_stage(e, {STAGE_OR, false, 0, map_n, cg_iters, w != nullptr});
+    commit_stage(e, {STAGE_OR, false, 0, map_n, cg_iters, w != nullptr, 1, toeplitz});
     return PNP_OK;
 }
 
@@ -2339,7 +2482,9 @@ int pnp_offres_plan(pnp_handle e, const double* t, int segments, int flags) {
     // from here on the old plan is gone: a live off-resonance stage's maps belong to its centres and are dropped with it
     D.segments = 0;
     D.kind = 0;
+    e->otz_planned = false;                                 // the Toeplitz spectra belong to the plan's coefficients
     if (e->stage.kind == STAGE_OR || e->stage.kind == STAGE_ORS) drop_stage(e, false);
+    e->or_seg_h = P.seg;
     HIP_TRY(nc_upload(D.tau, P.tau.data(), P.tau.size() * sizeof(double)));
     HIP_TRY(nc_upload(D.seg, P.seg.data(), M * sizeof(int32_t)));
     HIP_TRY(nc_upload(D.b0, P.b0.data(), M * sizeof(float)));
@@ -2376,6 +2521,7 @@ int pnp_offres_plan_ls(pnp_handle e, const double* t, int segments, double omega
     // from here on the old plan is gone: a live off-resonance stage's maps belong to its plan and are dropped with it
     D.segments = 0;
     D.kind = 0;
+    e->otz_planned = false;                                 // the Toeplitz spectra belong to the plan's coefficients
     if (e->stage.kind == STAGE_OR || e->stage.kind == STAGE_ORS) drop_stage(e, false);
     HIP_TRY(nc_upload(D.tau, P.tau.data(), P.tau.size() * sizeof(double)));
     HIP_TRY(nc_upload(D.coef, P.coef.data(), P.coef.size() * sizeof(float)));
@@ -2460,7 +2606,7 @@ int pnp_offres_adjoint(pnp_handle e, const float* samples, const float* weights,
 
 int pnp_set_kspace_offres(pnp_handle e, const float* y, const float* omega, int map_n, const float* w, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    return or_install("pnp_set_kspace_offres", e, false, nullptr, (const float2*)y, omega, map_n, w, cg_iters, nullptr, nullptr, nullptr,
+    return or_install("pnp_set_kspace_offres", e, false, false, nullptr, (const float2*)y, omega, map_n, w, cg_iters, nullptr, nullptr, nullptr,
                       (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_offres")
 }
@@ -2468,7 +2614,7 @@ int pnp_set_kspace_offres(pnp_handle e, const float* y, const float* omega, int 
 int pnp_reset_offres(pnp_handle e, const float* x0, const float* y, const float* omega, int map_n, const float* w, int cg_iters, float* x, float* z,
                      float* u, void* stream) {
     PNP_API_BEGIN
-    return or_install("pnp_reset_offres", e, true, (const float2*)x0, (const float2*)y, omega, map_n, w, cg_iters, x, (float2*)z, (float2*)u,
+    return or_install("pnp_reset_offres", e, true, false, (const float2*)x0, (const float2*)y, omega, map_n, w, cg_iters, x, (float2*)z, (float2*)u,
                       (hipStream_t)stream);
     PNP_API_END("pnp_reset_offres")
 }
@@ -2565,9 +2711,10 @@ int om_ensure(pnp_engine* e, int coils, size_t amaps_need = 0) {
                     {(void**)&e->om_amaps, &e->om_amaps_cap, amaps_need, false}});
 }
 
-// pnp_set_kspace_offres_mc (no iterate) / pnp_reset_offres_mc: the episode constants of the stage - y, w, the coil maps, the segment maps of
-// omega, A^H W y - and optionally the iterate.  Every rejection happens before any HIP call
-int om_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x0, const float2* y, const float2* sens, int coils, int sens_n,
+// pnp_set_kspace_offres_mc (no iterate) / pnp_reset_offres_mc and, `toeplitz`, their _tz forms of include/pnpadmm_offres_tz.h (w: the spectra's
+// weights, whatever is passed): the episode constants of the stage - y, w, the coil maps, the segment maps of omega, A^H W y - and optionally
+// the iterate.  Every rejection happens before any HIP call
+int om_install(const char* fn, pnp_engine* e, bool with_iterate, bool toeplitz, const float2* x0, const float2* y, const float2* sens, int coils, int sens_n,
                const float* omega, int map_n, const float* w, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
     int rc;
     if ((rc = om_check_scalars(fn, coils, sens_n, map_n))) return rc;
@@ -2579,11 +2726,14 @@ int om_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x
     if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if ((rc = om_check(fn, e, coils, sens_n, map_n))) return rc;
+    if (toeplitz && (rc = otz_need_spectra(fn, e))) return rc;
     PNP_ON_DEVICE(e);
+    if (toeplitz) w = e->otz_has_w ? e->otz_w : nullptr;
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, L = e->orp.segments;
     const size_t M = (size_t)e->nc.m, ym = (size_t)N * coils * M, sn = (size_t)sens_n * coils * H * W;
     if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
     if ((rc = om_ensure(e, coils))) return rc;
+    if (toeplitz && (rc = otz_ensure(e, N * otz_coil_block(e, coils, map_n), (size_t)N * otz_coil_block(e, coils, map_n)))) return rc;
     if ((rc = ws_grow(e, "multi-coil off-resonance constants",
                       {{(void**)&e->om_y, &e->om_y_cap, ym * sizeof(float2), false},
                        {(void**)&e->om_sens, &e->om_sens_cap, sn * sizeof(float2), false},
@@ -2604,7 +2754,7 @@ int om_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
     }
-    commit_stage(e, {STAGE_ORS, false, coils, sens_n, cg_iters, w != nullptr, map_n});
+    commit_stage(e, {STAGE_ORS, false, coils, sens_n, cg_iters, w != nullptr, map_n, toeplitz});
     return PNP_OK;
 }
 
@@ -2656,7 +2806,7 @@ int pnp_offres_adjoint_mc(pnp_handle e, const float* samples, const float* weigh
 int pnp_set_kspace_offres_mc(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, const float* omega, int map_n, const float* w,
                              int cg_iters, void* stream) {
     PNP_API_BEGIN
-    return om_install("pnp_set_kspace_offres_mc", e, false, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n, w, cg_iters,
+    return om_install("pnp_set_kspace_offres_mc", e, false, false, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n, w, cg_iters,
                       nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_offres_mc")
 }
@@ -2664,7 +2814,7 @@ int pnp_set_kspace_offres_mc(pnp_handle e, const float* y, const float* sens, in
 int pnp_reset_offres_mc(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, const float* omega, int map_n,
                         const float* w, int cg_iters, float* x, float* z, float* u, void* stream) {
     PNP_API_BEGIN
-    return om_install("pnp_reset_offres_mc", e, true, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n, w,
+    return om_install("pnp_reset_offres_mc", e, true, false, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n, w,
                       cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_offres_mc")
 }
@@ -2855,6 +3005,153 @@ int pnp_reset_ncsense_tz(pnp_handle e, const float* x0, const float* y, const fl
     return ns_install("pnp_reset_ncsense_tz", e, true, true, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, nullptr, cg_iters,
                       x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_ncsense_tz")
+}
+
+// ---- Toeplitz form of the off-resonance operator (include/pnpadmm_offres_tz.h) ------------------------------
+static_assert(PNP_OFFRES_TZ_MAX_PAIRS == kOffresTzMaxPairs && PNP_OFFRES_TZ_PLANES == kOffresTzPlanes, "the header's limits are the plan's");
+
+int pnp_offres_tz_plan(pnp_handle e, const float* weights, int flags, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_tz_plan";
+    // every rejection happens before any HIP call and leaves the handle as it was
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = or_need_plan(fn, e)) return rc;
+    if (int rc = tz_check_sizes(fn, e)) return rc;
+    OffresTzPlan P;
+    std::string why;
+    if (!plan_offres_tz(e->orp.kind, e->orp.segments, e->nc.m, e->orp.kind == 1 ? e->or_seg_h.data() : nullptr, &P, &why))
+        return fail(PNP_ERR_INVALID, "%s: %s", fn, why.c_str());
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    const size_t M = (size_t)e->nc.m, hw = (size_t)H * W, planes = (size_t)otz_slice_block(e, N) * e->orp.segments;
+    const std::vector<float2> twh = twiddle_table(2 * H), tww = twiddle_table(2 * W);
+    PNP_ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ws_grow(e, "Toeplitz off-resonance spectra",
+                         {{(void**)&e->otz_k, &e->otz_k_cap, (size_t)P.pairs * 4 * hw * sizeof(float), false},
+                          {(void**)&e->otz_w, &e->otz_w_cap, weights ? M * sizeof(float) : 0, false},
+                          {(void**)&e->otz_traj, &e->otz_traj_cap, M * 2 * sizeof(double), false},
+                          {(void**)&e->otz_tw_h, &e->otz_twh_cap, twh.size() * sizeof(float2), false},
+                          {(void**)&e->otz_tw_w, &e->otz_tww_cap, tww.size() * sizeof(float2), false},
+                          {(void**)&e->otz.blk_off, &e->otz_off_cap, P.blk_off.size() * sizeof(int32_t), false},
+                          {(void**)&e->otz.blk_idx, &e->otz_idx_cap, P.blk_idx.size() * sizeof(int32_t), false},
+                          {(void**)&e->otz_img, &e->otz_img_cap, planes * hw * sizeof(float2), false},
+                          {(void**)&e->otz_x, &e->otz_x_cap, planes * 4 * hw * sizeof(float2), false},
+                          {(void**)&e->otz_y, &e->otz_y_cap, planes * 4 * hw * sizeof(float2), false}}))
+        return rc;
+    if (e->otz_planned) (void)hipDeviceSynchronize();       // no launch still reads the spectra being replaced
+    // from here on the old spectra are gone: a live stage that runs on them loses its constants, as pnp_offres_plan drops them
+    e->otz_planned = false;
+    e->otz.pairs = 0;
+    if (e->stage.offres_tz) e->stage = LiveStage{};
+    HIP_TRY(nc_upload(e->otz_traj, e->nc_traj.data(), M * 2 * sizeof(double)));
+    HIP_TRY(nc_upload(e->otz_tw_h, twh.data(), twh.size() * sizeof(float2)));
+    HIP_TRY(nc_upload(e->otz_tw_w, tww.data(), tww.size() * sizeof(float2)));
+    if (!P.blk_off.empty()) HIP_TRY(nc_upload(e->otz.blk_off, P.blk_off.data(), P.blk_off.size() * sizeof(int32_t)));
+    if (!P.blk_idx.empty()) HIP_TRY(nc_upload(e->otz.blk_idx, P.blk_idx.data(), P.blk_idx.size() * sizeof(int32_t)));
+    if (weights) HIP_TRY(hipMemcpyAsync(e->otz_w, weights, M * sizeof(float), hipMemcpyDeviceToDevice, s));
+    OffresTzDev T = e->otz;                                 // a least-squares plan has no lists: its workgroups walk every sample
+    T.pairs = P.pairs; T.pair_block = P.pair_block; T.blocks = P.blocks;
+    if (P.blk_off.empty()) { T.blk_off = nullptr; T.blk_idx = nullptr; }
+    {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_offres_tz_spectra(e->otz_traj, weights ? e->otz_w : nullptr, e->orp, T, e->nc.m, H, W, e->otz_k, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    e->otz.pairs = P.pairs; e->otz.pair_block = P.pair_block; e->otz.blocks = P.blocks;
+    e->otz_has_w = weights != nullptr;
+    e->otz_planned = true;
+    return PNP_OK;
+    PNP_API_END("pnp_offres_tz_plan")
+}
+
+int pnp_offres_tz_planned(pnp_handle e) { return e && e->otz_planned ? 1 : 0; }
+int pnp_offres_tz_live(pnp_handle e) { return e && e->stage.offres_tz ? 1 : 0; }
+int pnp_offres_tz_spectra(pnp_handle e) { return e && e->otz_planned ? e->otz.pairs : 0; }
+
+int pnp_offres_tz_spectrum(pnp_handle e, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_tz_spectrum";
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = otz_need_spectra(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    HIP_TRY(hipMemcpyAsync(out, e->otz_k, (size_t)e->otz.pairs * 4 * e->cfg.h * e->cfg.w * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PNP_OK;
+    PNP_API_END("pnp_offres_tz_spectrum")
+}
+
+int pnp_offres_tz_apply(pnp_handle e, const float* img, const float* maps, int map_n, int batch, float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_tz_apply";
+    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
+    if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
+    if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (out == img || out == maps) return fail(PNP_ERR_INVALID, "%s: out must not alias img or maps", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
+    if (int rc = or_check(fn, e, map_n)) return rc;
+    if (int rc = otz_need_spectra(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    if (int rc = otz_ensure(e, e->cfg.n, 0)) return rc;
+    return otz_apply(e, (const float2*)img, (const float2*)maps, map_n, batch, nullptr, nullptr, nullptr, (float2*)out, nullptr, (hipStream_t)stream);
+    PNP_API_END("pnp_offres_tz_apply")
+}
+
+int pnp_offres_tz_apply_mc(pnp_handle e, const float* img, const float* maps, int map_n, const float* sens, int sens_n, int coils, int batch,
+                           float* out, void* stream) {
+    PNP_API_BEGIN
+    const char* fn = "pnp_offres_tz_apply_mc";
+    if (int rc = om_check_scalars(fn, coils, sens_n, map_n)) return rc;
+    if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
+    if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
+    if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
+    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (!out) return fail(PNP_ERR_INVALID, "%s: null out", fn);
+    if (out == img || out == maps || out == sens) return fail(PNP_ERR_INVALID, "%s: out must not alias img, maps or sens", fn);
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
+    if (int rc = om_check(fn, e, coils, sens_n, map_n)) return rc;
+    if (int rc = otz_need_spectra(fn, e)) return rc;
+    PNP_ON_DEVICE(e);
+    const int cb = otz_coil_block(e, coils, map_n);
+    if (int rc = otz_ensure(e, e->cfg.n * cb, (size_t)e->cfg.n * cb)) return rc;
+    return otz_apply_mc(e, (const float2*)img, (const float2*)maps, map_n, (const float2*)sens, sens_n, coils, batch, nullptr, nullptr, nullptr,
+                        (float2*)out, nullptr, (hipStream_t)stream);
+    PNP_API_END("pnp_offres_tz_apply_mc")
+}
+
+int pnp_set_kspace_offres_tz(pnp_handle e, const float* y, const float* omega, int map_n, int cg_iters, void* stream) {
+    PNP_API_BEGIN
+    return or_install("pnp_set_kspace_offres_tz", e, false, true, nullptr, (const float2*)y, omega, map_n, nullptr, cg_iters, nullptr, nullptr, nullptr,
+                      (hipStream_t)stream);
+    PNP_API_END("pnp_set_kspace_offres_tz")
+}
+
+int pnp_reset_offres_tz(pnp_handle e, const float* x0, const float* y, const float* omega, int map_n, int cg_iters, float* x, float* z, float* u,
+                        void* stream) {
+    PNP_API_BEGIN
+    return or_install("pnp_reset_offres_tz", e, true, true, (const float2*)x0, (const float2*)y, omega, map_n, nullptr, cg_iters, x, (float2*)z,
+                      (float2*)u, (hipStream_t)stream);
+    PNP_API_END("pnp_reset_offres_tz")
+}
+
+int pnp_set_kspace_offres_mc_tz(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, const float* omega, int map_n, int cg_iters,
+                                void* stream) {
+    PNP_API_BEGIN
+    return om_install("pnp_set_kspace_offres_mc_tz", e, false, true, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n,
+                      nullptr, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    PNP_API_END("pnp_set_kspace_offres_mc_tz")
+}
+
+int pnp_reset_offres_mc_tz(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, const float* omega, int map_n,
+                           int cg_iters, float* x, float* z, float* u, void* stream) {
+    PNP_API_BEGIN
+    return om_install("pnp_reset_offres_mc_tz", e, true, true, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n,
+                      nullptr, cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
+    PNP_API_END("pnp_reset_offres_mc_tz")
 }
 
 // ---- density compensation (include/pnpadmm_dcf.h) -------------------------------------------------------

@@ -52,6 +52,10 @@ struct Tuning {
                                   // (else: kOffresMcBlock)
     int offres_mc_naive = -1;     // PNP_OFFRES_MC_NAIVE (tests, timing): 1 = that operator composed per coil from the single-coil operator between
                                   // an expand and a combine kernel, 0 = the fused pad and crop; unset: kOffresMcNaiveSteps
+    bool offres_tz_naive = false; // PNP_OFFRES_TZ_NAIVE (tests, timing): the Toeplitz form of the off-resonance operator composed on full 2H x 2W
+                                  // planes instead of the fused passes
+    int offres_tz_slices = 0;     // PNP_OFFRES_TZ_SLICE_BLOCK (tests): slices per block of that application (else: kOffresTzPlanes / L); no bit
+                                  // depends on it
 };
 Tuning tuning_from_env();
 
@@ -538,6 +542,26 @@ hipError_t launch_offres_mc_pad(const float2* src, const float* src_real, const 
 hipError_t launch_offres_mc_crop(const float2* grid, const float2* sens, int sens_n, int C, int c0, int cbc, const float2* maps, int map_n, int L,
                                  int l0, int sb, const NufftDev& P, float2* part, const float2* pv, const float* mu, const float* tact, float2* q,
                                  double* partial, int batch, hipStream_t s);
+
+// ---- Toeplitz form of the off-resonance operator (offres_tz_kernels.hip; include/pnpadmm_offres_tz.h; the plan: offres_tz_plan.h) -----
+static constexpr int kOffresTzPlanes = 512;   // planes (slices x segments) in flight in the pass buffers: a slice block is kOffresTzPlanes / L slices
+// the uploaded pair plan: which samples the workgroups of pair block b walk (nullptr: all of them, in order)
+struct OffresTzDev {
+    int pairs = 0;           // P; 0: no plan
+    int pair_block = 0;      // pairs per workgroup of the build
+    int blocks = 0;
+    int* blk_off = nullptr;  // [blocks + 1], or nullptr: every block walks samples 0 .. M - 1
+    int* blk_idx = nullptr;  // ascending sample indices per block
+};
+// K [P, 2H, 2W] float32 from traj [M][2] float64 (ky, kx), w [M] float32 or nullptr (1) and the coefficients of R: the header's float64
+// Dirichlet sums, no atomics
+hipError_t launch_offres_tz_spectra(const double* traj, const float* w, const OffresDev& R, const OffresTzDev& T, int64_t m, int H, int W, float* K,
+                                    hipStream_t s);
+// y [slices, L, 2H, 2W] = scale . (sum over ascending l' of K_ll' x_l'), restricted to the band |l - l'| <= 1 under a linear plan (kind == 1)
+hipError_t launch_offres_tz_mix(const float2* x, float2* y, const float* K, int kind, int L, int H, int W, int slices, float scale, hipStream_t s);
+// the column passes of the fused application (fft_kernels.hip): half [planes, H, 2W] -> full [planes, 2H, 2W] and back, unscaled
+hipError_t launch_offres_tz_cols_fwd(const float2* half, float2* full, const float2* tw, int planes, int H, int W, hipStream_t s);
+hipError_t launch_offres_tz_cols_inv(const float2* full, float2* half, const float2* tw, int planes, int H, int W, hipStream_t s);
 
 // ---- field map estimation (fieldmap_kernels.hip; the fit: include/pnpadmm_fieldmap.h) ----------------------------
 // The fused kernel's plan: kFmT sweeps per launch over a kFmRegion^2 region, of which the kFmTile^2 tile is stored

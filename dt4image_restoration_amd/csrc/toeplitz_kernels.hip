@@ -19,6 +19,8 @@
 
 #pragma clang fp contract(off)
 
+#include "toeplitz_dirichlet.h"
+
 namespace pnp {
 
 namespace {
@@ -33,17 +35,7 @@ constexpr int kTzChunk = 32;                               // samples staged per
 
 __device__ __forceinline__ bool stopped(const float* tact, int n) { return tact != nullptr && tact[n] > 0.5f; }
 
-// D_n(t) = sin((2n - 1) pi t) / sin(pi t), t reduced to [-0.5, 0.5] first; 2n - 1 at t == 0.  The rounding error of the product (2n - 1) t,
-// up to 2^-44 of a period at n = 512, is put back to first order
-__device__ __forceinline__ double dirichlet(double t, int n) {
-    t = t - rint(t);
-    if (t == 0.0) return (double)(2 * n - 1);
-    const double a = (double)(2 * n - 1);
-    const double hi = a * t, lo = fma(a, t, -hi);
-    double sn, cs;
-    sincospi(hi, &sn, &cs);
-    return fma(3.14159265358979323846 * lo, cs, sn) / sinpi(t);
-}
+// (dirichlet(): toeplitz_dirichlet.h)
 
 __global__ __launch_bounds__(kTzSpecThreads) void toeplitz_spectrum_kernel(const double2* __restrict__ traj, const float* __restrict__ w, int M, int H,
                                                                            int W, float* __restrict__ K) {

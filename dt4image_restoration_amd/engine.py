@@ -726,6 +726,123 @@ class PnPEngine:
                                                   y.data_ptr(), aty0.data_ptr(), x0.data_ptr(), self._stream()), "pnp_acquire_offres_mc")
         return y, aty0, x0
 
+    # -- Toeplitz form of the off-resonance operator (include/pnpadmm_offres_tz.h) -------------
+    _otz_weights = None          # (the weights tensor the live spectra were planned from, or None for unit weights,)
+
+    def offres_tz_plan(self, weights: Optional[torch.Tensor] = None) -> None:
+        """Build the Toeplitz spectra of A^H W A for the planned trajectory, the live off-resonance plan (linear or least squares) and these
+        weights (pnp_offres_tz_plan): weights float32 [M] or None (1).  Replaces earlier spectra; a live Toeplitz off-resonance stage's
+        constants are dropped.  `nufft_plan`, `offres_plan` and `offres_plan_ls` drop the spectra."""
+        if weights is not None:
+            self._chk(weights, torch.float32, self.nufft_samples or weights.numel(), "weights")
+        was_live = self.offres_tz_live
+        self._otz_weights = None
+        _lib.check(self.lib.pnp_offres_tz_plan(self._h, weights.data_ptr() if weights is not None else None, 0, self._stream()),
+                   "pnp_offres_tz_plan")
+        self._otz_weights = (weights.clone() if weights is not None else None,)
+        if was_live:
+            self.live_episode = 0    # dropped with the spectra: whoever binds episodes re-installs
+
+    def _offres_tz_for(self, w: Optional[torch.Tensor]) -> None:
+        """plan the spectra unless the live ones were planned from these very weights on the live plans (the library forgets them when
+        either plan is replaced)"""
+        k = self._otz_weights
+        if k is not None and self.offres_tz_planned:
+            if (k[0] is None and w is None) or (k[0] is not None and w is not None and k[0].shape == w.shape and torch.equal(k[0], w)):
+                return
+        self.offres_tz_plan(w)
+
+    @property
+    def offres_tz_planned(self) -> bool:
+        """Whether Toeplitz spectra exist for the handle's NUFFT plan and off-resonance plan."""
+        return bool(self.lib.pnp_offres_tz_planned(self._h))
+
+    @property
+    def offres_tz_live(self) -> bool:
+        """Whether the live stage's CG runs the Toeplitz form of the off-resonance operator."""
+        return bool(self.lib.pnp_offres_tz_live(self._h))
+
+    @property
+    def offres_tz_spectra(self) -> int:
+        """P, the number of stored spectra (2L - 1 under a linear plan, L (L + 1) / 2 under least squares); 0 without them."""
+        return int(self.lib.pnp_offres_tz_spectra(self._h))
+
+    def offres_tz_spectrum(self) -> torch.Tensor:
+        """float32 [P,2H,2W]: the spectra K_ll', each centred like `fft2c`'s output (pnp_offres_tz_spectrum); the pair order is the upper
+        triangle row by row under least squares and (l, l), (l, l+1) interleaved under a linear plan."""
+        out = torch.empty((max(self.offres_tz_spectra, 1), 2 * self.h, 2 * self.w), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pnp_offres_tz_spectrum(self._h, out.data_ptr(), self._stream()), "pnp_offres_tz_spectrum")
+        return out
+
+    def offres_tz_apply(self, img: torch.Tensor, maps: torch.Tensor) -> torch.Tensor:
+        """complex64 [B,H,W] = A^H W A img of the segmented model by its Toeplitz form, without mu (pnp_offres_tz_apply); img complex64
+        [B,H,W] (or [B,1,H,W]); maps from `offres_maps`."""
+        b = self._batch_of(img, self.h * self.w, "img")
+        self._chk(img, torch.complex64, img.numel(), "img")
+        maps, map_n = self._offres_maps_arg(maps)
+        out = torch.empty((b, self.h, self.w), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_offres_tz_apply(self._h, img.data_ptr(), maps.data_ptr(), map_n, b, out.data_ptr(), self._stream()),
+                   "pnp_offres_tz_apply")
+        return out
+
+    def offres_tz_apply_mc(self, img: torch.Tensor, maps: torch.Tensor, sens: torch.Tensor) -> torch.Tensor:
+        """complex64 [B,H,W] = sum_c conj(S_c) . [offres_tz_apply](S_c . img) (pnp_offres_tz_apply_mc); sens complex64 [C,H,W] or [N,C,H,W]."""
+        b = self._batch_of(img, self.h * self.w, "img")
+        self._chk(img, torch.complex64, img.numel(), "img")
+        maps, map_n = self._offres_maps_arg(maps)
+        sens, coils, sens_n = self._sens(sens)
+        out = torch.empty((b, self.h, self.w), dtype=torch.complex64, device=self.device)
+        _lib.check(self.lib.pnp_offres_tz_apply_mc(self._h, img.data_ptr(), maps.data_ptr(), map_n, sens.data_ptr(), sens_n, coils, b,
+                                                   out.data_ptr(), self._stream()), "pnp_offres_tz_apply_mc")
+        return out
+
+    def reset_offres_tz(self, x0: torch.Tensor, y: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None,
+                        cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """`reset_offres` with the CG on the Toeplitz form of A^H W A (pnp_reset_offres_tz): the spectra are planned here when none exist
+        for these weights and the live plans; the weights are then those of aty and of the DC column too."""
+        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
+        yp, _ = self._nc_args(y, w)
+        omega, map_n = self._omega(omega)
+        x, z, u = self._iterate()
+        self._offres_tz_for(w)
+        _lib.check(self.lib.pnp_reset_offres_tz(self._h, x0.data_ptr(), yp, omega.data_ptr(), map_n, int(cg_iters), x.data_ptr(), z.data_ptr(),
+                                                u.data_ptr(), self._stream()), "pnp_reset_offres_tz")
+        self.live_episode = _next_episode()
+        return x, z, u
+
+    def set_kspace_offres_tz(self, y: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0,
+                             cg_iters: int = 8) -> None:
+        """`set_kspace_offres` for an episode whose CG runs the Toeplitz form (pnp_set_kspace_offres_tz; the spectra as in `reset_offres_tz`)."""
+        yp, _ = self._nc_args(y, w)
+        omega, map_n = self._omega(omega)
+        self._offres_tz_for(w)
+        _lib.check(self.lib.pnp_set_kspace_offres_tz(self._h, yp, omega.data_ptr(), map_n, int(cg_iters), self._stream()),
+                   "pnp_set_kspace_offres_tz")
+        self.live_episode = episode or _next_episode()
+
+    def reset_offres_mc_tz(self, x0: torch.Tensor, y: torch.Tensor, sens: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None,
+                           cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """`reset_offres_mc` with the CG on the Toeplitz form of A^H W A (pnp_reset_offres_mc_tz; the spectra as in `reset_offres_tz`)."""
+        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
+        yp, sp, coils, sens_n, _ = self._ncsense_args(y, sens, w)
+        omega, map_n = self._omega(omega)
+        x, z, u = self._iterate()
+        self._offres_tz_for(w)
+        _lib.check(self.lib.pnp_reset_offres_mc_tz(self._h, x0.data_ptr(), yp, sp, coils, sens_n, omega.data_ptr(), map_n, int(cg_iters),
+                                                   x.data_ptr(), z.data_ptr(), u.data_ptr(), self._stream()), "pnp_reset_offres_mc_tz")
+        self.live_episode = _next_episode()
+        return x, z, u
+
+    def set_kspace_offres_mc_tz(self, y: torch.Tensor, sens: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None,
+                                episode: int = 0, cg_iters: int = 8) -> None:
+        """`set_kspace_offres_mc` for an episode whose CG runs the Toeplitz form (pnp_set_kspace_offres_mc_tz)."""
+        yp, sp, coils, sens_n, _ = self._ncsense_args(y, sens, w)
+        omega, map_n = self._omega(omega)
+        self._offres_tz_for(w)
+        _lib.check(self.lib.pnp_set_kspace_offres_mc_tz(self._h, yp, sp, coils, sens_n, omega.data_ptr(), map_n, int(cg_iters), self._stream()),
+                   "pnp_set_kspace_offres_mc_tz")
+        self.live_episode = episode or _next_episode()
+
     # -- field map estimation (include/pnpadmm_fieldmap.h) ----------------------------------
     def _echoes(self, x1: torch.Tensor, x2: torch.Tensor) -> int:
         """the coil count of two echo images complex64 [N,C,H,W] (or [N,H,W]: one coil)"""

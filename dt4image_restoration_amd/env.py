@@ -39,9 +39,13 @@ def _as_complex(t: torch.Tensor) -> torch.Tensor:
 class PnPEnv:
     def __init__(self, max_episode_step: int, denoiser: UNetDenoiser2D, device_type,
                  no_ref_scorer: Optional[Callable[[torch.Tensor], float]] = None, replica: int = 0, cg_iters: int = 8,
-                 nufft_width: int = 6, nufft_grid=None, nc_normal: str = "nufft", offres_mc: bool = False) -> None:
+                 nufft_width: int = 6, nufft_grid=None, nc_normal: str = "nufft",
+                 offres_normal: str = "nufft", offres_mc: bool = False) -> None:
         if nc_normal not in ("nufft", "toeplitz"):
             raise ValueError(f"nc_normal must be 'nufft' or 'toeplitz', got {nc_normal!r}")
+        if offres_normal not in ("nufft", "toeplitz"):
+            raise ValueError(f"offres_normal must be 'nufft' or 'toeplitz', got {offres_normal!r}")
+        self.offres_normal = offres_normal      # off-resonance episodes: the form of A^H W A inside the CG (include/pnpadmm_offres_tz.h)
         self.offres_mc = bool(offres_mc)        # data["omega"] with data["sens"]: the coils x segments stage (include/pnpadmm_offres_mc.h)
         self.nc_normal = nc_normal              # non-Cartesian episodes: the form of A^H W A inside the CG (include/pnpadmm_toeplitz.h)
         self.max_episode_step = max_episode_step
@@ -59,7 +63,7 @@ class PnPEnv:
         constants): two sub-batches of one job can then be stepped concurrently on two streams."""
         return PnPEnv(self.max_episode_step, self.denoiser, self._device_type, self.no_ref_model, replica=replica, cg_iters=self.cg_iters,
                       nufft_width=self.nufft_width, nufft_grid=self.nufft_grid, nc_normal=self.nc_normal,
-                      offres_mc=getattr(self, "offres_mc", False))
+                      offres_mc=getattr(self, "offres_mc", False), offres_normal=getattr(self, "offres_normal", "nufft"))
 
     # ---- engine management ------------------------------------------------------------------
     def _engine_for(self, n: int, h: int, w: int, device: torch.device) -> PnPEngine:
@@ -182,7 +186,7 @@ class PnPEnv:
     def _reset_offres(self, data, eng: PnPEngine, x0, y0, sens, dcf, gt, traj, n: int, device) -> "OrderedDict[str, torch.Tensor]":
         """An off-resonance episode: data["omega"] float32 [H,W] or [N,H,W] in rad/s, data["times"] float64 [M] seconds, optional
         data["segments"], optional data["b0_interp"] "linear" | "ls" (the least-squares temporal interpolator over the map's own band,
-        max |omega| (1 + 1e-6)); gridding form of the normal operator.  Single-coil, unless the env was made with offres_mc=True: then
+        max |omega| (1 + 1e-6)); gridding form of the normal operator, or with offres_normal="toeplitz" its Toeplitz form.  Single-coil, unless the env was made with offres_mc=True: then
         data["sens"] beside data["omega"] installs the coils x segments stage (`PnPEngine.reset_offres_mc`), y0 [N,C,M]."""
         if sens is not None and not getattr(self, "offres_mc", False):
             raise ValueError("an off-resonance episode is single-coil (data['omega'] with data['sens'] is not supported)")
@@ -193,10 +197,11 @@ class PnPEnv:
         interp = self._interp_of(data)
         extra = {} if interp == "linear" else {"b0_interp": interp, "omega_max": float(omega.abs().max()) * (1.0 + 1e-6)}
         self._offres_plan(eng, times, seg, interp, extra.get("omega_max"))
+        tz = getattr(self, "offres_normal", "nufft") == "toeplitz"   # (the engine plans the spectra when the plans or the weights changed)
         if sens is not None:
-            x, z, u = eng.reset_offres_mc(x0, y0, sens, omega, dcf, cg_iters=self.cg_iters)
+            x, z, u = (eng.reset_offres_mc_tz if tz else eng.reset_offres_mc)(x0, y0, sens, omega, dcf, cg_iters=self.cg_iters)
         else:
-            x, z, u = eng.reset_offres(x0, y0, omega, dcf, cg_iters=self.cg_iters)
+            x, z, u = (eng.reset_offres_tz if tz else eng.reset_offres)(x0, y0, omega, dcf, cg_iters=self.cg_iters)
         aty0 = torch.as_tensor(data["ATy0"])[..., 0] if "ATy0" in data else None
         return OrderedDict({"x": x, "y0": y0, "z": z, "u": u, "mask": None, "gt": gt, "ATy0": aty0,
                             "T": torch.zeros(n, dtype=torch.float32, device=device),
@@ -219,14 +224,16 @@ class PnPEnv:
             tz = self.nc_normal == "toeplitz"   # (the engine re-plans the spectrum when the plan or the episode's weights changed)
             y = states["y0"]
             y = y if y.is_complex() else _as_complex(y)
+            otz = getattr(self, "offres_normal", "nufft") == "toeplitz"
             if states.get("omega") is not None and states.get("sens") is not None:      # a multi-coil off-resonance episode
                 sens = states["sens"]
-                eng.set_kspace_offres_mc(y.reshape(n, sens.shape[-3], -1).to(eng.device).contiguous(), sens, states["omega"], states.get("dcf"),
-                                         episode=ep, cg_iters=self.cg_iters)
+                install = eng.set_kspace_offres_mc_tz if otz else eng.set_kspace_offres_mc
+                install(y.reshape(n, sens.shape[-3], -1).to(eng.device).contiguous(), sens, states["omega"], states.get("dcf"), episode=ep,
+                        cg_iters=self.cg_iters)
                 return
             if states.get("omega") is not None:  # an off-resonance episode
-                eng.set_kspace_offres(y.reshape(n, -1).to(eng.device).contiguous(), states["omega"], states.get("dcf"), episode=ep,
-                                      cg_iters=self.cg_iters)
+                (eng.set_kspace_offres_tz if otz else eng.set_kspace_offres)(y.reshape(n, -1).to(eng.device).contiguous(), states["omega"],
+                                                                             states.get("dcf"), episode=ep, cg_iters=self.cg_iters)
                 return
             if states.get("sens") is not None:  # a non-Cartesian SENSE episode
                 sens = states["sens"]
