@@ -86,21 +86,27 @@ struct EventPair {
 
 // The handle's live data-fidelity stage: the constants installed LAST, which pnp_step / pnp_prox_dual solve with and PNP_RES_DC measures
 // against.  STAGE_NONE: nothing installed yet, or dropped with the plan it was built on; STAGE_CART: the closed form (pnp_reset /
-// pnp_set_kspace); STAGE_MC: SENSE; STAGE_NC: non-Cartesian; STAGE_NS: non-Cartesian SENSE; STAGE_OR: non-Cartesian with the
-// time-segmented off-resonance operator (include/pnpadmm_offres.h); STAGE_ORS: that operator with coils (include/pnpadmm_offres_mc.h).
-// The five last run a CG on stage_normal().
+// pnp_set_kspace); STAGE_MC: SENSE; the four non-Cartesian kinds are one operator (NcOp below) with or without coil maps and with or without
+// the segment maps of a field map - STAGE_NC: neither; STAGE_NS: coils (include/pnpadmm_ncsense.h); STAGE_OR: segments
+// (include/pnpadmm_offres.h); STAGE_ORS: both (include/pnpadmm_offres_mc.h).  Their constants live in the handle's one set of slots
+// (pnp_engine::st_*).  Every kind but the closed form runs a CG on stage_normal().
+// `form`: the normal operator a non-Cartesian stage's CG runs - the gridding pair, the Toeplitz spectrum of include/pnpadmm_toeplitz.h
+// (a _tz installer of STAGE_NC / STAGE_NS) or the spectra of include/pnpadmm_offres_tz.h (a _tz installer of STAGE_OR / STAGE_ORS).
+// aty, the misfit and the acquisitions run on the gridding pair whatever the form.
 // Written by commit_stage and drop_stage only.
 enum StageKind { STAGE_NONE, STAGE_CART, STAGE_MC, STAGE_NC, STAGE_NS, STAGE_OR, STAGE_ORS };
+enum StageForm { FORM_GRID, FORM_TZ, FORM_OTZ };
 struct LiveStage {
     StageKind kind = STAGE_NONE;
-    bool toeplitz = false;       // STAGE_NC, STAGE_NS: a _tz installer, the CG runs on the Toeplitz operator
-    int coils = 0;               // STAGE_MC, STAGE_NS, STAGE_ORS: coils of the installed constants
-    int sens_n = 1;              // STAGE_OR: map_n of the installed field map
+    StageForm form = FORM_GRID;
+    int coils = 0;               // STAGE_MC, STAGE_NS, STAGE_ORS: coils of the installed constants (else 0)
+    int sens_n = 1;              // ... and the sens_n of the installed coil maps
     int cg = 0;                  // CG iterations per step
-    bool has_w = false;          // STAGE_NC, STAGE_NS, STAGE_OR, STAGE_ORS: weights were installed (nc_w / ns_w / or_w / om_w; else they are 1)
-    int map_n = 1;               // STAGE_ORS: map_n of the installed field map (sens_n is the coil maps')
-    bool offres_tz = false;      // STAGE_OR, STAGE_ORS: a _tz installer of include/pnpadmm_offres_tz.h, the CG runs on that header's operator
+    bool has_w = false;          // the non-Cartesian kinds: weights were installed (st_w; else they are 1)
+    int map_n = 1;               // STAGE_OR, STAGE_ORS: map_n of the installed field map
 };
+inline bool stage_noncart(StageKind k) { return k == STAGE_NC || k == STAGE_NS || k == STAGE_OR || k == STAGE_ORS; }
+inline bool stage_segmented(StageKind k) { return k == STAGE_OR || k == STAGE_ORS; }
 
 }  // namespace
 
@@ -154,38 +160,34 @@ struct pnp_engine {
     size_t nc_i0_cap = 0, nc_wts_cap = 0, nc_cy_cap = 0, nc_cx_cap = 0, nc_off_cap = 0, nc_idx_cap = 0, nc_twh_cap = 0, nc_tww_cap = 0;
     float2* nc_grid = nullptr;   // [N, gh, gw] the oversampled grid
     float2* nc_samp = nullptr;   // [N, M] sample scratch (A p inside the normal operator, A x of the misfit)
-    float2* nc_y = nullptr;      // [N, M] the installed samples
-    float* nc_w = nullptr;       // [M] the installed weights (read only through stage_w)
-    double* nc_mpart = nullptr;  // [N, nufft_sample_chunks(M)] partial sums of the misfit
-    size_t nc_grid_cap = 0, nc_samp_cap = 0, nc_y_cap = 0, nc_w_cap = 0, nc_mpart_cap = 0;
-    // non-Cartesian SENSE (include/pnpadmm_ncsense.h): the coil-block scratch by every entry point of that header, the constants by its installers
+    size_t nc_grid_cap = 0, nc_samp_cap = 0;
+    // the constants of the live non-Cartesian stage, whichever kind it is (the installers' last ws_grow): one set of slots, each as large as
+    // the largest install so far needed it
+    float2* st_y = nullptr;      // [N, M] or [N, C, M] the installed samples
+    float* st_w = nullptr;       // [M] the installed weights (read only through stage_w)
+    float2* st_sens = nullptr;   // [sens_n, C, H, W] the installed coil maps
+    float2* st_maps = nullptr;   // [map_n, L, H, W] the installed segment maps
+    double* st_mpart = nullptr;  // [N, nufft_sample_chunks(M)] or [N, C, nufft_sample_chunks(M)] partial sums of the misfit
+    float2* acq_maps = nullptr;  // [map_n, L, H, W] the off-resonance acquisitions' own segment maps: the installed ones stay as they are
+    size_t st_y_cap = 0, st_w_cap = 0, st_sens_cap = 0, st_maps_cap = 0, st_mpart_cap = 0, acq_maps_cap = 0;
+    // non-Cartesian SENSE (include/pnpadmm_ncsense.h): the coil-block scratch by every entry point of that header
     int ns_block = kNcsenseBlock; // coils per block: kNcsenseBlock, or PNP_NCSENSE_COIL_BLOCK (read at pnp_create)
     int ns_naive = kNcsenseNaiveSteps;   // NcsenseStep bits: the steps that run as the single-coil launches at batch N cb (PNP_NCSENSE_NAIVE: all or none)
     float2* ns_img = nullptr;    // naive pad or crop only: [N, cb, H, W] the block's coil images
     size_t ns_img_cap = 0;
     float2* ns_grid = nullptr;   // [N, cb, gh, gw] the block's oversampled grids
     float2* ns_samp = nullptr;   // [N, cb, M] the block's samples (A p inside the normal operator, A x of the misfit)
-    float2* ns_y = nullptr;      // [N, C, M] the installed samples
-    float2* ns_sens = nullptr;   // [sens_n, C, H, W] the installed maps
-    float* ns_w = nullptr;       // [M] the installed weights (read only through stage_w)
-    double* ns_mpart = nullptr;  // [N, C, nufft_sample_chunks(M)] partial sums of the misfit
-    size_t ns_grid_cap = 0, ns_samp_cap = 0, ns_y_cap = 0, ns_sens_cap = 0, ns_w_cap = 0, ns_mpart_cap = 0;
-    // off-resonance correction (include/pnpadmm_offres.h): the plan by pnp_offres_plan, the constants by its installers; the segment-block
-    // scratch is the coil-block scratch above
+    size_t ns_grid_cap = 0, ns_samp_cap = 0;
+    // off-resonance correction (include/pnpadmm_offres.h): the plan by pnp_offres_plan; the segment-block scratch is the coil-block
+    // scratch above
     std::vector<int32_t> nc_bin_off_h, nc_bin_idx_h;   // host copy of the NUFFT plan's tile bins: what the per-segment lists are built from
     OffresDev orp;               // the uploaded plan; orp.segments == 0: none
     size_t or_tau_cap = 0, or_seg_cap = 0, or_b0_cap = 0, or_b1_cap = 0, or_loff_cap = 0, or_lidx_cap = 0, or_coef_cap = 0;
     int or_block = kOffresBlock; // segments per block: kOffresBlock, or PNP_OFFRES_SEG_BLOCK (read at pnp_create)
     int or_naive = kOffresNaiveSteps;   // OffresStep bits: the steps that run as the naive launches (PNP_OFFRES_NAIVE: all or none)
     int orls_naive = kOffresLsNaiveSteps;   // ... under a least-squares plan (PNP_OFFRES_LS_NAIVE: all or none)
-    float2* or_maps = nullptr;   // [map_n, L, H, W] the installed segment maps
-    float2* or_y = nullptr;      // [N, M] the installed samples
-    float* or_w = nullptr;       // [M] the installed weights (read only through stage_w)
-    double* or_mpart = nullptr;  // [N, nufft_sample_chunks(M)] partial sums of the misfit
-    float2* or_amaps = nullptr;  // [map_n, L, H, W] pnp_acquire_offres' own segment maps: the installed ones stay as they are
-    size_t or_maps_cap = 0, or_y_cap = 0, or_w_cap = 0, or_mpart_cap = 0, or_amaps_cap = 0;
     // off-resonance correction for multi-coil data (include/pnpadmm_offres_mc.h): blocks of coils x segments go through the coil-block scratch
-    // above (ns_grid, ns_samp, ns_img), sized for them by om_ensure; the rest is this section's own
+    // above (ns_grid, ns_samp, ns_img), sized for them by op_ensure; the rest is this section's own
     int om_block = 0;                    // coils per block: PNP_OFFRES_MC_COIL_BLOCK (read at pnp_create), or 0: the measured default of the live
                                          // plan's interpolator (om_block_of)
     int om_naive = kOffresMcNaiveSteps;  // OffresMcStep bits: the steps that run composed per coil (PNP_OFFRES_MC_NAIVE: all or none)
@@ -193,14 +195,7 @@ struct pnp_engine {
     float2* om_part = nullptr;   // [N, cbc, H, W] the segment chain's partials (allocated only when L > SB); composed adjoint: the coil images a_c
     float2* om_img = nullptr;    // composed form only: [N, H, W] one coil's image
     float2* om_line = nullptr;   // composed form only: [N, M] one coil's samples
-    float2* om_y = nullptr;      // [N, C, M] the installed samples
-    float2* om_sens = nullptr;   // [sens_n, C, H, W] the installed coil maps
-    float2* om_maps = nullptr;   // [map_n, L, H, W] the installed segment maps
-    float* om_w = nullptr;       // [M] the installed weights (read only through stage_w)
-    double* om_mpart = nullptr;  // [N, C, nufft_sample_chunks(M)] partial sums of the misfit
-    float2* om_amaps = nullptr;  // [map_n, L, H, W] pnp_acquire_offres_mc's own segment maps
-    size_t om_samp_cap = 0, om_part_cap = 0, om_img_cap = 0, om_line_cap = 0, om_y_cap = 0, om_sens_cap = 0, om_maps_cap = 0, om_w_cap = 0,
-           om_mpart_cap = 0, om_amaps_cap = 0;
+    size_t om_samp_cap = 0, om_part_cap = 0, om_img_cap = 0, om_line_cap = 0;
     // Toeplitz normal operator (include/pnpadmm_toeplitz.h): the spectrum and its buffers by pnp_toeplitz_plan
     std::vector<double> nc_traj; // host copy of the planned trajectory [M][2] (ky, kx): what the spectrum is built from
     double* tz_traj = nullptr;   // [M][2] its device copy
@@ -487,20 +482,20 @@ int mc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tac
 
 // ---- non-Cartesian stage ----------------------------------------------------------------------------
 // the live non-Cartesian stage's weights (nullptr: 1)
-const float* stage_w(const pnp_engine* e) {
-    if (!e->stage.has_w) return nullptr;
-    return e->stage.kind == STAGE_NS ? e->ns_w : e->stage.kind == STAGE_OR ? e->or_w : e->stage.kind == STAGE_ORS ? e->om_w : e->nc_w;
-}
-// the centred transform of pnp_fft2c on the plan's grid, in place in nc_grid: rows then columns in both directions
-int nc_fft(pnp_engine* e, int batch, int inverse, hipStream_t s) {
-    const NufftDev& P = e->nc;
+const float* stage_w(const pnp_engine* e) { return e->stage.has_w ? e->st_w : nullptr; }
+// the centred transform of pnp_fft2c of `planes` planes of gh x gw, in place in `grid`: rows then columns in both directions
+int grid_fft(pnp_engine* e, float2* grid, const float2* tw_h, const float2* tw_w, int planes, int gh, int gw, int inverse, hipStream_t s) {
     {
         Prof p(e, s, PROF_FFT_ROWS, -1);
-        HIP_TRY(launch_fft_rows(e->nc_grid, e->nc_grid, P.tw_gw, batch, P.gh, P.gw, inverse, P.gw / 2, s));
+        HIP_TRY(launch_fft_rows(grid, grid, tw_w, planes, gh, gw, inverse, gw / 2, s));
     }
     Prof p(e, s, PROF_FFT_COLS, -1);
-    HIP_TRY(launch_fft_cols(e->nc_grid, P.tw_gh, batch, P.gh, P.gw, inverse, P.gh / 2, s));
+    HIP_TRY(launch_fft_cols(grid, tw_h, planes, gh, gw, inverse, gh / 2, s));
     return PNP_OK;
+}
+// ... on the NUFFT plan's oversampled grid: nc_grid, or the block's grids in ns_grid
+int nc_fft(pnp_engine* e, float2* grid, int planes, int inverse, hipStream_t s) {
+    return grid_fft(e, grid, e->nc.tw_gh, e->nc.tw_gw, planes, e->nc.gh, e->nc.gw, inverse, s);
 }
 // out [batch, M] = A src (src complex, or src_real: a real image)
 int nc_forward(pnp_engine* e, const float2* src, const float* src_real, int batch, float2* out, hipStream_t s) {
@@ -508,7 +503,7 @@ int nc_forward(pnp_engine* e, const float2* src, const float* src_real, int batc
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_nufft_pad(src, src_real, e->nc, e->nc_grid, batch, s));
     }
-    if (int rc = nc_fft(e, batch, 0, s)) return rc;
+    if (int rc = nc_fft(e, e->nc_grid, batch, 0, s)) return rc;
     Prof p(e, s, PROF_OTHER, -1);
     HIP_TRY(launch_nufft_interp(e->nc_grid, e->nc, out, batch, s));
     return PNP_OK;
@@ -520,30 +515,13 @@ int nc_adjoint(pnp_engine* e, const float2* y, const float* w, int batch, const 
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_nufft_grid(y, w, e->nc, e->nc_grid, batch, s));
     }
-    if (int rc = nc_fft(e, batch, 1, s)) return rc;
+    if (int rc = nc_fft(e, e->nc_grid, batch, 1, s)) return rc;
     Prof p(e, s, PROF_OTHER, -1);
     HIP_TRY(launch_nufft_crop(e->nc_grid, e->nc, pv, mu, tact, q, partial, batch, s));
     return PNP_OK;
 }
-// q = A^H W A pv + mu pv; the partial sums of Re<pv, q> go to mc_part.  Eight launches.  Stopped slices: only the last launch skips them
-// (the others rewrite scratch alone)
-int nc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    if (int rc = nc_forward(e, pv, nullptr, e->cfg.n, e->nc_samp, s)) return rc;
-    return nc_adjoint(e, e->nc_samp, stage_w(e), e->cfg.n, pv, mu, tact, q, e->mc_part, s);
-}
 
 // ---- non-Cartesian SENSE stage (include/pnpadmm_ncsense.h) --------------------------------------------
-// the centred transform of `planes` planes of the block's grids, in place in ns_grid
-int ns_fft(pnp_engine* e, int planes, int inverse, hipStream_t s) {
-    const NufftDev& P = e->nc;
-    {
-        Prof p(e, s, PROF_FFT_ROWS, -1);
-        HIP_TRY(launch_fft_rows(e->ns_grid, e->ns_grid, P.tw_gw, planes, P.gh, P.gw, inverse, P.gw / 2, s));
-    }
-    Prof p(e, s, PROF_FFT_COLS, -1);
-    HIP_TRY(launch_fft_cols(e->ns_grid, P.tw_gh, planes, P.gh, P.gw, inverse, P.gh / 2, s));
-    return PNP_OK;
-}
 int ns_block_of(const pnp_engine* e, int coils) { return coils < e->ns_block ? coils : e->ns_block; }
 // F_nu(S_c . src) for the block's coils c0 .. c0 + cb - 1 into out [batch, ocs, M] at the coils oc0 ..
 int ns_forward_block(pnp_engine* e, const float2* src, const float* src_real, const float2* sens, int sens_n, int C, int c0, int cb, int batch,
@@ -560,7 +538,7 @@ int ns_forward_block(pnp_engine* e, const float2* src, const float* src_real, co
             HIP_TRY(launch_ncsense_pad(src, src_real, sens, sens_n, C, c0, cb, e->nc, e->ns_grid, batch, s));
         }
     }
-    if (int rc = ns_fft(e, batch * cb, 0, s)) return rc;
+    if (int rc = nc_fft(e, e->ns_grid, batch * cb, 0, s)) return rc;
     Prof p(e, s, PROF_OTHER, -1);
     if (!(e->ns_naive & NS_GATHER)) {
         HIP_TRY(launch_ncsense_interp(e->ns_grid, e->nc, out, ocs, oc0, cb, batch, s));
@@ -587,7 +565,7 @@ int ns_adjoint_block(pnp_engine* e, const float2* y, int ycs, int yc0, const flo
             HIP_TRY(launch_ncsense_grid(y, ycs, yc0, cb, w, e->nc, e->ns_grid, batch, s));
         }
     }
-    if (int rc = ns_fft(e, batch * cb, 1, s)) return rc;
+    if (int rc = nc_fft(e, e->ns_grid, batch * cb, 1, s)) return rc;
     Prof p(e, s, PROF_OTHER, -1);
     if (e->ns_naive & NS_CROP) {
         HIP_TRY(launch_nufft_crop(e->ns_grid, e->nc, nullptr, nullptr, nullptr, e->ns_img, nullptr, batch * cb, s));
@@ -611,18 +589,6 @@ int ns_adjoint(pnp_engine* e, const float2* y, const float* w, const float2* sen
     for (int c0 = 0; c0 < C; c0 += B)
         if (int rc = ns_adjoint_block(e, y, C, c0, w, sens, sens_n, C, c0, std::min(B, C - c0), batch, nullptr, nullptr, nullptr, q, nullptr, s))
             return rc;
-    return PNP_OK;
-}
-// q = A^H W A pv + mu pv with the installed constants; the partial sums of Re<pv, q> go to mc_part.  Eight launches per coil block: a block's
-// samples go through ns_samp and are gridded before the next block's grids replace them.  Stopped slices: only the combine launches skip them
-int ns_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    const int N = e->cfg.n, C = e->stage.coils, sens_n = e->stage.sens_n, B = ns_block_of(e, C);
-    const float* w = stage_w(e);
-    for (int c0 = 0; c0 < C; c0 += B) {
-        const int cb = std::min(B, C - c0);
-        if (int rc = ns_forward_block(e, pv, nullptr, e->ns_sens, sens_n, C, c0, cb, N, e->ns_samp, cb, 0, s)) return rc;
-        if (int rc = ns_adjoint_block(e, e->ns_samp, cb, 0, w, e->ns_sens, sens_n, C, c0, cb, N, pv, mu, tact, q, e->mc_part, s)) return rc;
-    }
     return PNP_OK;
 }
 
@@ -654,7 +620,7 @@ int or_forward(pnp_engine* e, const float2* src, const float* src_real, const fl
                 HIP_TRY(launch_ncsense_pad(src, src_real, maps, map_n, L, l0, cb, e->nc, e->ns_grid, batch, s));
             }
         }
-        if (int rc = ns_fft(e, batch * cb, 0, s)) return rc;
+        if (int rc = nc_fft(e, e->ns_grid, batch * cb, 0, s)) return rc;
         Prof p(e, s, PROF_OTHER, -1);
         if (ls) HIP_TRY(launch_offres_ls_interp(e->ns_grid, e->orp, e->nc, out, l0, cb, batch, s));
         else HIP_TRY(launch_offres_interp(e->ns_grid, e->orp, e->nc, out, l0, cb, batch, s));
@@ -686,7 +652,7 @@ int or_adjoint(pnp_engine* e, const float2* y, const float* w, const float2* map
             if (ls) HIP_TRY(launch_offres_ls_grid(y, w, e->orp, e->nc, e->ns_grid, l0, cb, batch, s, !e->tune.offres_ls_noskip));
             else HIP_TRY(launch_offres_grid(y, w, e->orp, e->nc, e->ns_grid, l0, cb, batch, s, e->tune.offres_grid_filter));
         }
-        if (int rc = ns_fft(e, batch * cb, 1, s)) return rc;
+        if (int rc = nc_fft(e, e->ns_grid, batch * cb, 1, s)) return rc;
         Prof p(e, s, PROF_OTHER, -1);
         if (e->ns_naive & NS_CROP) {
             HIP_TRY(launch_nufft_crop(e->ns_grid, e->nc, nullptr, nullptr, nullptr, e->ns_img, nullptr, batch * cb, s));
@@ -697,13 +663,6 @@ int or_adjoint(pnp_engine* e, const float2* y, const float* w, const float2* map
         }
     }
     return PNP_OK;
-}
-// q = A^H W A pv + mu pv with the installed constants; the partial sums of Re<pv, q> go to mc_part.  A pv goes through nc_samp whole - the
-// blend joins neighbouring segments - before the adjoint starts.  Stopped slices: only the combine launches skip them
-int or_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    const int N = e->cfg.n;
-    if (int rc = or_forward(e, pv, nullptr, e->or_maps, e->stage.sens_n, N, e->nc_samp, s)) return rc;
-    return or_adjoint(e, e->nc_samp, stage_w(e), e->or_maps, e->stage.sens_n, N, pv, mu, tact, q, e->mc_part, s);
 }
 
 // ---- off-resonance correction for multi-coil data (include/pnpadmm_offres_mc.h) ----------------------------
@@ -748,7 +707,7 @@ int om_forward_block(pnp_engine* e, const float2* src, const float* src_real, co
             Prof p(e, s, PROF_OTHER, -1);
             HIP_TRY(launch_offres_mc_pad(src, src_real, sens, sens_n, C, c0, cb, maps, map_n, L, l0, sb, e->nc, e->ns_grid, batch, s));
         }
-        if (int rc = ns_fft(e, batch * cb * sb, 0, s)) return rc;
+        if (int rc = nc_fft(e, e->ns_grid, batch * cb * sb, 0, s)) return rc;
         Prof p(e, s, PROF_OTHER, -1);
         if (or_naive_of(e) & OR_GATHER) {                  // the plan's gather ships composed: every plane's samples, then the blend
             if (e->ns_naive & NS_GATHER) HIP_TRY(launch_nufft_interp(e->ns_grid, e->nc, e->ns_samp, batch * cb * sb, s));
@@ -805,7 +764,7 @@ int om_adjoint_block(pnp_engine* e, const float2* blk, const float* w, const flo
                 HIP_TRY(launch_offres_grid(blk, w, e->orp, e->nc, e->ns_grid, l0, sb, batch * cb, s, e->tune.offres_grid_filter));
             }
         }
-        if (int rc = ns_fft(e, batch * cb * sb, 1, s)) return rc;
+        if (int rc = nc_fft(e, e->ns_grid, batch * cb * sb, 1, s)) return rc;
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_offres_mc_crop(e->ns_grid, sens, sens_n, C, c0, cb, maps, map_n, L, l0, sb, e->nc, e->om_part, pv, mu, tact, q, partial, batch,
                                       s));
@@ -842,20 +801,91 @@ int om_adjoint(pnp_engine* e, const float2* y, const float* w, const float2* map
     }
     return PNP_OK;
 }
-// q = A^H W A pv + mu pv with the installed constants; the partial sums of Re<pv, q> go to mc_part.  Coil block by coil block, as ns_normal:
-// a block's samples go through om_samp whole - the blend joins segments - and are gridded before the next block's replace them.
-// Stopped slices: only the launches that write q skip them
-int om_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    const int N = e->cfg.n, C = e->stage.coils, sens_n = e->stage.sens_n, map_n = e->stage.map_n, B = om_block_of(e, C);
-    const float* w = stage_w(e);
+
+// ---- the one non-Cartesian operator ----------------------------------------------------------------------
+// What a non-Cartesian operator is made of beyond the NUFFT plan: coil maps (coils == 0: single-coil) and the segment maps of a field map
+// (maps == nullptr: unsegmented).  The four combinations are the four families above; every caller that serves them all goes through the
+// op_* dispatchers below and never asks which family it has.
+struct NcOp {
+    int coils;
+    const float2* sens;
+    int sens_n;
+    const float2* maps;
+    int map_n;
+};
+// the live stage's operator: the installed constants
+NcOp live_op(const pnp_engine* e) {
+    const LiveStage& st = e->stage;
+    return {st.coils, st.coils ? e->st_sens : nullptr, st.sens_n, stage_segmented(st.kind) ? e->st_maps : nullptr, st.map_n};
+}
+// out [batch, M] or [batch, C, M] = A src (src complex, or src_real: a real image)
+int op_forward(pnp_engine* e, const NcOp& o, const float2* src, const float* src_real, int batch, float2* out, hipStream_t s) {
+    if (o.coils) return o.maps ? om_forward(e, src, src_real, o.maps, o.map_n, o.sens, o.sens_n, o.coils, batch, out, s)
+                               : ns_forward(e, src, src_real, o.sens, o.sens_n, o.coils, batch, out, s);
+    return o.maps ? or_forward(e, src, src_real, o.maps, o.map_n, batch, out, s) : nc_forward(e, src, src_real, batch, out, s);
+}
+// q [batch, h, w] = A^H (w . y)
+int op_adjoint(pnp_engine* e, const NcOp& o, const float2* y, const float* w, int batch, float2* q, hipStream_t s) {
+    if (o.coils) return o.maps ? om_adjoint(e, y, w, o.maps, o.map_n, o.sens, o.sens_n, o.coils, batch, q, s)
+                               : ns_adjoint(e, y, w, o.sens, o.sens_n, o.coils, batch, q, s);
+    return o.maps ? or_adjoint(e, y, w, o.maps, o.map_n, batch, nullptr, nullptr, nullptr, q, nullptr, s)
+                  : nc_adjoint(e, y, w, batch, nullptr, nullptr, nullptr, q, nullptr, s);
+}
+// a multi-coil operator's coils per block, and the scratch [N, cb, M] a block's samples go through
+int op_block_of(const pnp_engine* e, const NcOp& o) { return o.maps ? om_block_of(e, o.coils) : ns_block_of(e, o.coils); }
+float2* op_block_samp(const pnp_engine* e, const NcOp& o) { return o.maps ? e->om_samp : e->ns_samp; }
+// blk [batch, cb, M] = the samples of the coils c0 .. c0 + cb - 1 of A src
+int op_forward_block(pnp_engine* e, const NcOp& o, const float2* src, const float* src_real, int c0, int cb, int batch, float2* blk, hipStream_t s) {
+    return o.maps ? om_forward_block(e, src, src_real, o.maps, o.map_n, o.sens, o.sens_n, o.coils, c0, cb, batch, blk, s)
+                  : ns_forward_block(e, src, src_real, o.sens, o.sens_n, o.coils, c0, cb, batch, blk, cb, 0, s);
+}
+// q (+)= the block's part of A^H (w . blk); the last block adds mu pv and leaves the partial sums of Re<pv, q>
+int op_adjoint_block(pnp_engine* e, const NcOp& o, const float2* blk, const float* w, int c0, int cb, int batch, const float2* pv, const float* mu,
+                     const float* tact, float2* q, double* partial, hipStream_t s) {
+    return o.maps ? om_adjoint_block(e, blk, w, o.maps, o.map_n, o.sens, o.sens_n, o.coils, c0, cb, batch, pv, mu, tact, q, partial, s)
+                  : ns_adjoint_block(e, blk, cb, 0, w, o.sens, o.sens_n, o.coils, c0, cb, batch, pv, mu, tact, q, partial, s);
+}
+// q = A^H W A pv + mu pv by the gridding pair; the partial sums of Re<pv, q> go to mc_part.  Single-coil: A pv goes through nc_samp whole (a
+// segmented blend joins neighbouring segments) before the adjoint starts.  Multi-coil: coil block by coil block, a block's samples go through
+// the block scratch and are gridded before the next block's replace them.  Stopped slices: only the launches that write q skip them
+int op_normal(pnp_engine* e, const NcOp& o, const float* w, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    const int N = e->cfg.n;
+    if (!o.coils) {
+        if (int rc = op_forward(e, o, pv, nullptr, N, e->nc_samp, s)) return rc;
+        return o.maps ? or_adjoint(e, e->nc_samp, w, o.maps, o.map_n, N, pv, mu, tact, q, e->mc_part, s)
+                      : nc_adjoint(e, e->nc_samp, w, N, pv, mu, tact, q, e->mc_part, s);
+    }
+    const int C = o.coils, B = op_block_of(e, o);
+    float2* const blk = op_block_samp(e, o);
     for (int c0 = 0; c0 < C; c0 += B) {
         const int cb = std::min(B, C - c0);
-        if (int rc = om_forward_block(e, pv, nullptr, e->om_maps, map_n, e->om_sens, sens_n, C, c0, cb, N, e->om_samp, s)) return rc;
-        if (int rc = om_adjoint_block(e, e->om_samp, w, e->om_maps, map_n, e->om_sens, sens_n, C, c0, cb, N, pv, mu, tact, q, e->mc_part, s)) return rc;
+        if (int rc = op_forward_block(e, o, pv, nullptr, c0, cb, N, blk, s)) return rc;
+        if (int rc = op_adjoint_block(e, o, blk, w, c0, cb, N, pv, mu, tact, q, e->mc_part, s)) return rc;
     }
     return PNP_OK;
 }
-
+// the partial sums of sum_m w_m |(A x)_m - y_m|^2 (summed over the coils) into dcpart: A x into the sample scratch - whole, or coil block by
+// coil block with the coil-major sums in between
+int op_misfit(pnp_engine* e, const NcOp& o, const float* x, const float2* y, const float* w, double* mpart, double* dcpart, hipStream_t s) {
+    const int N = e->cfg.n;
+    if (!o.coils) {
+        if (int rc = op_forward(e, o, nullptr, x, N, e->nc_samp, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_nufft_misfit(e->nc_samp, y, w, e->nc, mpart, dcpart, N, s));
+        return PNP_OK;
+    }
+    const int C = o.coils, B = op_block_of(e, o);
+    float2* const blk = op_block_samp(e, o);
+    for (int c0 = 0; c0 < C; c0 += B) {
+        const int cb = std::min(B, C - c0);
+        if (int rc = op_forward_block(e, o, nullptr, x, c0, cb, N, blk, s)) return rc;
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_ncsense_misfit(blk, y, w, C, c0, cb, e->nc, mpart, N, s));
+    }
+    Prof p(e, s, PROF_OTHER, -1);
+    HIP_TRY(launch_ncsense_misfit_sum(mpart, C, e->nc, dcpart, N, s));
+    return PNP_OK;
+}
 // ---- Toeplitz normal operator (include/pnpadmm_toeplitz.h) ----------------------------------------------
 // q [planes, h, w] = crop(ifft2c(K . fft2c(pad(src)))) (+ mu pv with the partial sums of Re<pv, q>: the last launch's epilogue), through
 // tz_grid.  Three fused launches, or the seven composed ones; src may be q (the grid lies between them).  Stopped slices: only the last
@@ -876,15 +906,7 @@ int tz_apply(pnp_engine* e, const float2* src, int planes, const float2* pv, con
         HIP_TRY(launch_toeplitz_rows_inv(e->tz_grid, e->tz_tw_w, pv, mu, tact, q, partial, planes, H, W, s));
         return PNP_OK;
     }
-    auto fft = [&](int inverse) -> int {
-        {
-            Prof p(e, s, PROF_FFT_ROWS, -1);
-            HIP_TRY(launch_fft_rows(e->tz_grid, e->tz_grid, e->tz_tw_w, planes, 2 * H, 2 * W, inverse, W, s));
-        }
-        Prof p(e, s, PROF_FFT_COLS, -1);
-        HIP_TRY(launch_fft_cols(e->tz_grid, e->tz_tw_h, planes, 2 * H, 2 * W, inverse, H, s));
-        return PNP_OK;
-    };
+    const auto fft = [&](int inverse) { return grid_fft(e, e->tz_grid, e->tz_tw_h, e->tz_tw_w, planes, 2 * H, 2 * W, inverse, s); };
     {
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_toeplitz_pad(src, e->tz_grid, H, W, planes, s));
@@ -915,13 +937,6 @@ int tz_apply_mc(pnp_engine* e, const float2* src, const float2* sens, int sens_n
         HIP_TRY(launch_ncsense_combine(e->ns_img, sens, sens_n, C, c0, cb, e->nc, pv, mu, tact, out, partial, batch, s));
     }
     return PNP_OK;
-}
-// the two stages' normal operators in Toeplitz form: q = A^H W A pv + mu pv, the partial sums of Re<pv, q> in mc_part
-int tz_nc_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    return tz_apply(e, pv, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
-}
-int tz_ns_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    return tz_apply_mc(e, pv, e->ns_sens, e->stage.sens_n, e->stage.coils, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
 }
 
 // ---- Toeplitz form of the off-resonance operator (include/pnpadmm_offres_tz.h) ------------------------------
@@ -967,15 +982,7 @@ int otz_apply(pnp_engine* e, const float2* src, const float2* maps, int map_n, i
             Prof p(e, s, PROF_FFT_ROWS, -1);
             HIP_TRY(launch_toeplitz_rows_inv(e->otz_x, e->otz_tw_w, nullptr, nullptr, nullptr, e->otz_img, nullptr, planes, H, W, s));
         } else {
-            auto fft = [&](float2* grid, int inverse) -> int {
-                {
-                    Prof p(e, s, PROF_FFT_ROWS, -1);
-                    HIP_TRY(launch_fft_rows(grid, grid, e->otz_tw_w, planes, 2 * H, 2 * W, inverse, W, s));
-                }
-                Prof p(e, s, PROF_FFT_COLS, -1);
-                HIP_TRY(launch_fft_cols(grid, e->otz_tw_h, planes, 2 * H, 2 * W, inverse, H, s));
-                return PNP_OK;
-            };
+            const auto fft = [&](float2* grid, int inverse) { return grid_fft(e, grid, e->otz_tw_h, e->otz_tw_w, planes, 2 * H, 2 * W, inverse, s); };
             {
                 Prof p(e, s, PROF_OTHER, -1);
                 HIP_TRY(launch_toeplitz_pad(e->otz_img, e->otz_x, H, W, planes, s));
@@ -1015,27 +1022,28 @@ int otz_apply_mc(pnp_engine* e, const float2* src, const float2* maps, int map_n
     }
     return PNP_OK;
 }
-// the two stages' normal operators in this form: q = A^H W A pv + mu pv, the partial sums of Re<pv, q> in mc_part
-int otz_or_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    return otz_apply(e, pv, e->or_maps, e->stage.sens_n, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
+// the live non-Cartesian stage's normal operator in its three forms: q = A^H W A pv + mu pv, the partial sums of Re<pv, q> in mc_part
+int grid_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    return op_normal(e, live_op(e), stage_w(e), pv, mu, tact, q, s);
 }
-int otz_om_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
-    return otz_apply_mc(e, pv, e->om_maps, e->stage.map_n, e->om_sens, e->stage.sens_n, e->stage.coils, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
+int tz_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    const NcOp o = live_op(e);
+    return o.coils ? tz_apply_mc(e, pv, o.sens, o.sens_n, o.coils, e->cfg.n, pv, mu, tact, q, e->mc_part, s)
+                   : tz_apply(e, pv, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
 }
-
+int otz_normal(pnp_engine* e, const float2* pv, const float* mu, const float* tact, float2* q, hipStream_t s) {
+    const NcOp o = live_op(e);
+    return o.coils ? otz_apply_mc(e, pv, o.maps, o.map_n, o.sens, o.sens_n, o.coils, e->cfg.n, pv, mu, tact, q, e->mc_part, s)
+                   : otz_apply(e, pv, o.maps, o.map_n, e->cfg.n, pv, mu, tact, q, e->mc_part, s);
+}
 // the K-step CG solve of (A^H A + mu I) z = A^H y + mu (x + u), warm-started from z, then u <- u + x - z; `normal`: the stage's normal
-// operator (mc_normal: the coil operator, nc_normal: the NUFFT pair, ns_normal: both), which also leaves the partial sums of Re<p, q> in mc_part
+// operator (mc_normal: the coil operator; grid_normal, tz_normal, otz_normal: the non-Cartesian stage's three forms), which also leaves the partial sums of Re<p, q> in mc_part
 using NormalOp = int (*)(pnp_engine*, const float2*, const float*, const float*, float2*, hipStream_t);
 // the live stage's normal operator, run stage.cg times per step (nullptr: the stage has none - the closed form, or nothing installed)
 NormalOp stage_normal(const pnp_engine* e) {
-    switch (e->stage.kind) {
-    case STAGE_MC: return mc_normal;
-    case STAGE_NC: return e->stage.toeplitz ? tz_nc_normal : nc_normal;
-    case STAGE_NS: return e->stage.toeplitz ? tz_ns_normal : ns_normal;
-    case STAGE_OR: return e->stage.offres_tz ? otz_or_normal : or_normal;
-    case STAGE_ORS: return e->stage.offres_tz ? otz_om_normal : om_normal;
-    default: return nullptr;
-    }
+    if (e->stage.kind == STAGE_MC) return mc_normal;
+    if (!stage_noncart(e->stage.kind)) return nullptr;
+    return e->stage.form == FORM_TZ ? tz_normal : e->stage.form == FORM_OTZ ? otz_normal : grid_normal;
 }
 int run_prox_dual_cg(pnp_engine* e, NormalOp normal, int iters, const float* mu, const float* tact, const float* x, float2* z, float2* u,
                      hipStream_t s) {
@@ -1140,12 +1148,15 @@ int mc_check(const char* fn, pnp_engine* e, int coils, int sens_n, int mask_n) {
 // installer therefore leaves the handle in the stage it had (its CG vectors and, for the Cartesian stages, its mask are rewritten by the
 // next install); nothing between an installer's first launch and this line reads the record - the launches take the new constants as arguments.
 void commit_stage(pnp_engine* e, const LiveStage& st) { e->stage = st; }
-// pnp_nufft_plan (any non-Cartesian stage) and pnp_toeplitz_plan (`toeplitz_only`): a live stage built on the plan or spectrum being
-// replaced loses its constants with it.  The closed-form and SENSE stages use neither and stay.
-void drop_stage(pnp_engine* e, bool toeplitz_only) {
+// The four plan calls that replace what a live stage was built on: the stage loses its constants with it.  pnp_nufft_plan: every
+// non-Cartesian stage (DROP_NONCART); pnp_offres_plan / pnp_offres_plan_ls: the segmented ones (DROP_SEGMENTED); pnp_toeplitz_plan and
+// pnp_offres_tz_plan: the stages whose CG runs on that spectrum (DROP_FORM with the form).  The closed-form and SENSE stages use none of
+// these and stay.
+enum StageDrop { DROP_NONCART, DROP_SEGMENTED, DROP_FORM };
+void drop_stage(pnp_engine* e, StageDrop what, StageForm form = FORM_GRID) {
     const LiveStage& st = e->stage;
-    if ((st.kind == STAGE_NC || st.kind == STAGE_NS || st.kind == STAGE_OR || st.kind == STAGE_ORS) && (st.toeplitz || !toeplitz_only))
-        e->stage = LiveStage{};
+    if (!stage_noncart(st.kind)) return;
+    if (what == DROP_NONCART || (what == DROP_SEGMENTED && stage_segmented(st.kind)) || (what == DROP_FORM && st.form == form)) e->stage = LiveStage{};
 }
 
 // pnp_set_kspace (no iterate) / pnp_reset: the closed-form stage's constants
@@ -1195,7 +1206,7 @@ int mc_install(const char* fn, pnp_engine* e, bool with_iterate, const float2* x
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
     }
-    commit_stage(e, {STAGE_MC, false, coils, sens_n, cg_iters});
+    commit_stage(e, {STAGE_MC, FORM_GRID, coils, sens_n, cg_iters});
     return PNP_OK;
 }
 
@@ -1343,47 +1354,8 @@ int run_prox_dual(pnp_engine* e, const float* mu, const float* tact, const float
 int stage_misfit(pnp_engine* e, const float* x, double* dcpart, hipStream_t s) {
     const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, C = e->stage.coils;
     switch (e->stage.kind) {
-    case STAGE_ORS: {
-        // the segmented A x coil block by coil block into the sample scratch, then the non-Cartesian SENSE stage's sums, coil-major
-        const int B = om_block_of(e, C);
-        for (int c0 = 0; c0 < C; c0 += B) {
-            const int cb = std::min(B, C - c0);
-            if (int rc = om_forward_block(e, nullptr, x, e->om_maps, e->stage.map_n, e->om_sens, e->stage.sens_n, C, c0, cb, N, e->om_samp, s))
-                return rc;
-            Prof p(e, s, PROF_OTHER, -1);
-            HIP_TRY(launch_ncsense_misfit(e->om_samp, e->om_y, stage_w(e), C, c0, cb, e->nc, e->om_mpart, N, s));
-        }
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_ncsense_misfit_sum(e->om_mpart, C, e->nc, dcpart, N, s));
-        return PNP_OK;
-    }
-    case STAGE_OR: {
-        // the segmented A x into the sample scratch, then sum_m w_m |(A x)_m - y_m|^2
-        if (int rc = or_forward(e, nullptr, x, e->or_maps, e->stage.sens_n, N, e->nc_samp, s)) return rc;
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_nufft_misfit(e->nc_samp, e->or_y, stage_w(e), e->nc, e->or_mpart, dcpart, N, s));
-        return PNP_OK;
-    }
-    case STAGE_NS: {
-        // A x block by block into the sample scratch, then sum_c sum_m w_m |(A x)_{c,m} - y_{c,m}|^2
-        const int B = ns_block_of(e, C);
-        for (int c0 = 0; c0 < C; c0 += B) {
-            const int cb = std::min(B, C - c0);
-            if (int rc = ns_forward_block(e, nullptr, x, e->ns_sens, e->stage.sens_n, C, c0, cb, N, e->ns_samp, cb, 0, s)) return rc;
-            Prof p(e, s, PROF_OTHER, -1);
-            HIP_TRY(launch_ncsense_misfit(e->ns_samp, e->ns_y, stage_w(e), C, c0, cb, e->nc, e->ns_mpart, N, s));
-        }
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_ncsense_misfit_sum(e->ns_mpart, C, e->nc, dcpart, N, s));
-        return PNP_OK;
-    }
-    case STAGE_NC: {
-        // A x into the sample scratch, then sum_m w_m |(A x)_m - y_m|^2
-        if (int rc = nc_forward(e, nullptr, x, N, e->nc_samp, s)) return rc;
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_nufft_misfit(e->nc_samp, e->nc_y, stage_w(e), e->nc, e->nc_mpart, dcpart, N, s));
-        return PNP_OK;
-    }
+    case STAGE_NC: case STAGE_NS: case STAGE_OR: case STAGE_ORS:
+        return op_misfit(e, live_op(e), x, e->st_y, stage_w(e), e->st_mpart, dcpart, s);
     case STAGE_MC: {
         // the plain transforms of S_c x into the coil scratch, then sum_c ||M (FFT(S_c x) - ys_c)||^2
         {
@@ -1552,14 +1524,14 @@ int pnp_destroy(pnp_handle e) {
     (void)hipFree(e->tz_traj); (void)hipFree(e->tz_k); (void)hipFree(e->tz_w); (void)hipFree(e->tz_tw_h); (void)hipFree(e->tz_tw_w); (void)hipFree(e->tz_grid);
     (void)hipFree(e->orp.tau); (void)hipFree(e->orp.seg); (void)hipFree(e->orp.b0); (void)hipFree(e->orp.b1); (void)hipFree(e->orp.list_off);
     (void)hipFree(e->orp.coef);
-    (void)hipFree(e->orp.list_idx); (void)hipFree(e->or_maps); (void)hipFree(e->or_y); (void)hipFree(e->or_w); (void)hipFree(e->or_mpart); (void)hipFree(e->or_amaps);
-    (void)hipFree(e->om_samp); (void)hipFree(e->om_part); (void)hipFree(e->om_img); (void)hipFree(e->om_line); (void)hipFree(e->om_y);
-    (void)hipFree(e->om_sens); (void)hipFree(e->om_maps); (void)hipFree(e->om_w); (void)hipFree(e->om_mpart); (void)hipFree(e->om_amaps);
+    (void)hipFree(e->orp.list_idx);
+    (void)hipFree(e->om_samp); (void)hipFree(e->om_part); (void)hipFree(e->om_img); (void)hipFree(e->om_line);
     (void)hipFree(e->otz.blk_off); (void)hipFree(e->otz.blk_idx); (void)hipFree(e->otz_traj); (void)hipFree(e->otz_k); (void)hipFree(e->otz_w);
     (void)hipFree(e->otz_tw_h); (void)hipFree(e->otz_tw_w); (void)hipFree(e->otz_img); (void)hipFree(e->otz_x); (void)hipFree(e->otz_y); (void)hipFree(e->otz_cimg);
     (void)hipFree(e->dcf_grid); (void)hipFree(e->dcf_w); (void)hipFree(e->dcf_part); (void)hipFree(e->dcf_max);
-    (void)hipFree(e->ns_grid); (void)hipFree(e->ns_samp); (void)hipFree(e->ns_y); (void)hipFree(e->ns_sens); (void)hipFree(e->ns_w); (void)hipFree(e->ns_mpart);
-    (void)hipFree(e->nc_grid); (void)hipFree(e->nc_samp); (void)hipFree(e->nc_y); (void)hipFree(e->nc_w); (void)hipFree(e->nc_mpart);
+    (void)hipFree(e->ns_grid); (void)hipFree(e->ns_samp);
+    (void)hipFree(e->nc_grid); (void)hipFree(e->nc_samp);
+    (void)hipFree(e->st_y); (void)hipFree(e->st_w); (void)hipFree(e->st_sens); (void)hipFree(e->st_maps); (void)hipFree(e->st_mpart); (void)hipFree(e->acq_maps);
     (void)hipFree(e->plan.tw_h); (void)hipFree(e->plan.tw_w);
     for (auto& p : e->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     delete e;
@@ -2012,40 +1984,188 @@ int tz_ensure(pnp_engine* e, size_t planes, bool coil_images) {
     return ws_grow(e, "Toeplitz scratch", {{(void**)&e->tz_grid, &e->tz_grid_cap, planes * (e->tz_fused ? 2 : 4) * hw * sizeof(float2), false},
                                           {(void**)&e->ns_img, &e->ns_img_cap, coil_images ? planes * hw * sizeof(float2) : 0, false}});
 }
-int nc_check_cg(const char* fn, int cg_iters) {
-    if (cg_iters < 1 || cg_iters > PNP_MC_MAX_CG) return fail(PNP_ERR_INVALID, "%s: cg_iters must be 1..%d (got %d)", fn, PNP_MC_MAX_CG, cg_iters);
+int or_need_plan(const char* fn, const pnp_engine* e) {
+    if (int rc = nc_need_plan(fn, e)) return rc;
+    return e->orp.segments > 0 ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no off-resonance plan (pnp_offres_plan)", fn);
+}
+// the Toeplitz spectra of include/pnpadmm_offres_tz.h, which its installers and applications need
+int otz_need_spectra(const char* fn, const pnp_engine* e) {
+    if (int rc = or_need_plan(fn, e)) return rc;
+    return e->otz_planned ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no Toeplitz off-resonance spectra (pnp_offres_tz_plan)", fn);
+}
+// the pass buffers of that form for applications over `slices` slices and, multi-coil, `cimg_planes` coil images
+int otz_ensure(pnp_engine* e, int slices, size_t cimg_planes) {
+    const size_t hw = (size_t)e->cfg.h * e->cfg.w, planes = (size_t)otz_slice_block(e, slices) * e->orp.segments;
+    return ws_grow(e, "Toeplitz off-resonance scratch", {{(void**)&e->otz_img, &e->otz_img_cap, planes * hw * sizeof(float2), false},
+                                                        {(void**)&e->otz_x, &e->otz_x_cap, planes * 4 * hw * sizeof(float2), false},
+                                                        {(void**)&e->otz_y, &e->otz_y_cap, planes * 4 * hw * sizeof(float2), false},
+                                                        {(void**)&e->otz_cimg, &e->otz_cimg_cap, cimg_planes * hw * sizeof(float2), false}});
+}
+
+// What an entry point's operator takes beyond the NUFFT plan (the arguments' side of NcOp): coil maps, a field map or its segment maps
+enum OpTakes { TAKES_COILS = 1, TAKES_MAPS = 2, TAKES_BOTH = 3 };
+StageKind stage_kind_of(int takes) {
+    static const StageKind kinds[4] = {STAGE_NC, STAGE_NS, STAGE_OR, STAGE_ORS};
+    return kinds[takes & 3];
+}
+// this call's operator: the arguments it was given
+NcOp arg_op(int takes, const float2* sens, int coils, int sens_n, const float2* maps, int map_n) {
+    return {(takes & TAKES_COILS) ? coils : 0, (takes & TAKES_COILS) ? sens : nullptr, sens_n, (takes & TAKES_MAPS) ? maps : nullptr, map_n};
+}
+
+// argument errors shared by the entry points of the non-Cartesian headers, before any HIP call: the scalar ranges need no handle and come
+// first (they are reported whatever else is wrong), then what depends on the handle - the counts, the plan, the launch grids' block limit
+int op_check_scalars(const char* fn, int takes, int coils, int sens_n, int map_n) {
+    if (takes & TAKES_COILS) {
+        if (coils < 1 || coils > PNP_MC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_MC_MAX_COILS, coils);
+        if (sens_n < 1) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n (got %d)", fn, sens_n);
+    }
+    if ((takes & TAKES_MAPS) && map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    return PNP_OK;
+}
+int op_check(const char* fn, const pnp_engine* e, int takes, int coils, int sens_n, int map_n) {
+    const int N = e->cfg.n;
+    if ((takes & TAKES_COILS) && sens_n != 1 && sens_n != N) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n=%d", fn, N);
+    if ((takes & TAKES_MAPS) && map_n != 1 && map_n != N) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n=%d", fn, N);
+    if (int rc = (takes & TAKES_MAPS) ? or_need_plan(fn, e) : nc_need_plan(fn, e)) return rc;
+    if (takes == TAKES_BOTH) {
+        if ((long long)N * om_block_of(e, coils) * or_block_of(e) > 65535)
+            return fail(PNP_ERR_INVALID, "%s: n * min(coils, coil block) * min(segments, block) must be <= 65535 (got %d * %d * %d)", fn, N,
+                        om_block_of(e, coils), or_block_of(e));
+    } else if (takes == TAKES_COILS) {
+        if ((long long)N * ns_block_of(e, coils) > 65535)
+            return fail(PNP_ERR_INVALID, "%s: n * min(coils, block) must be <= 65535 (got %d * %d)", fn, N, ns_block_of(e, coils));
+    } else if (takes == TAKES_MAPS) {
+        if ((long long)N * or_block_of(e) > 65535)
+            return fail(PNP_ERR_INVALID, "%s: n * min(segments, block) must be <= 65535 (got %d * %d)", fn, N, or_block_of(e));
+    }
     return PNP_OK;
 }
 
-// pnp_set_kspace_nc (no iterate) / pnp_reset_nc and, `toeplitz`, their _tz forms (w: the spectrum's weights, whatever is passed): the episode
-// constants of the non-Cartesian stage - y, w, A^H W y - and optionally the iterate.  Every rejection happens before any HIP call
-int nc_install(const char* fn, pnp_engine* e, bool with_iterate, bool toeplitz, const float2* x0, const float2* y, const float* w, int cg_iters,
-               float* x, float2* z, float2* u, hipStream_t s) {
+// The block scratch of an operator that takes coils, maps or both (the plain NUFFT pair's is the plan's own) and `amaps_need` bytes of an
+// acquisition's own segment maps.  The coil-block scratch of the non-Cartesian SENSE stage (ns_grid, ns_samp, ns_img) serves a block of coils,
+// of segments or of coils x segments; the multi-coil off-resonance operator adds its block's samples and the segment chain's partials
+int op_ensure(pnp_engine* e, int takes, int coils, size_t amaps_need = 0) {
+    if (!takes) return PNP_OK;
+    const size_t N = (size_t)e->cfg.n, HW = (size_t)e->cfg.h * e->cfg.w, M = (size_t)e->nc.m;
+    const bool both = takes == TAKES_BOTH;
+    const size_t cbc = both ? (size_t)om_block_of(e, coils) : 0;
+    const size_t planes = both ? N * cbc * or_block_of(e) : takes == TAKES_COILS ? N * ns_block_of(e, coils) : N * or_block_of(e);
+    return ws_grow(e, both ? "multi-coil off-resonance scratch" : takes == TAKES_COILS ? "non-Cartesian SENSE scratch" : "off-resonance scratch",
+                   {{(void**)&e->ns_grid, &e->ns_grid_cap, planes * e->nc.gh * e->nc.gw * sizeof(float2), false},
+                    {(void**)&e->ns_samp, &e->ns_samp_cap, planes * M * sizeof(float2), false},
+                    {(void**)&e->ns_img, &e->ns_img_cap, (e->ns_naive & (NS_PAD | NS_CROP)) ? planes * HW * sizeof(float2) : 0, false},
+                    {(void**)&e->om_samp, &e->om_samp_cap, N * cbc * M * sizeof(float2), false},
+                    // the partials: the fused crop touches them only when the segments do not fit one block; the composed adjoint's coil images
+                    {(void**)&e->om_part, &e->om_part_cap,
+                     both && ((e->om_naive & ORM_CROP) || e->orp.segments > or_block_of(e)) ? N * cbc * HW * sizeof(float2) : 0, false},
+                    {(void**)&e->om_img, &e->om_img_cap, both && e->om_naive ? N * HW * sizeof(float2) : 0, false},
+                    {(void**)&e->om_line, &e->om_line_cap, both && e->om_naive ? N * M * sizeof(float2) : 0, false},
+                    {(void**)&e->acq_maps, &e->acq_maps_cap, amaps_need, false}});
+}
+
+// The twelve pnp_set_kspace_* (no iterate) / pnp_reset_* members of the non-Cartesian headers: the episode constants of the stage `takes`
+// names - y, w, the coil maps, the segment maps of omega, A^H W y - and optionally the iterate.  `toeplitz`: a _tz installer, whose CG runs
+// on the spectrum of the stage's kind (w: the spectrum's weights, whatever is passed).  Every rejection happens before any HIP call.  The
+// constants grow last, after every scratch grow has succeeded: an allocation failure leaves the live stage's constants as they were
+int nc_install(const char* fn, pnp_engine* e, int takes, bool with_iterate, bool toeplitz, const float2* x0, const float2* y, const float2* sens,
+               int coils, int sens_n, const float* omega, int map_n, const float* w, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
+    const bool has_coils = takes & TAKES_COILS, segmented = takes & TAKES_MAPS;
     int rc;
-    if ((rc = nc_check_cg(fn, cg_iters))) return rc;
+    if ((rc = op_check_scalars(fn, takes, coils, sens_n, map_n))) return rc;
+    if (cg_iters < 1 || cg_iters > PNP_MC_MAX_CG) return fail(PNP_ERR_INVALID, "%s: cg_iters must be 1..%d (got %d)", fn, PNP_MC_MAX_CG, cg_iters);
     if (with_iterate && !x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
     if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (has_coils && !sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (segmented && !omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
     if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if ((rc = toeplitz ? tz_need_spectrum(fn, e) : nc_need_plan(fn, e))) return rc;
+    if ((rc = op_check(fn, e, takes, coils, sens_n, map_n))) return rc;
+    if (toeplitz && (rc = segmented ? otz_need_spectra(fn, e) : tz_need_spectrum(fn, e))) return rc;
     PNP_ON_DEVICE(e);
-    if (toeplitz) w = e->tz_has_w ? e->tz_w : nullptr;
-    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
-    const size_t M = (size_t)e->nc.m;
+    if (toeplitz) w = segmented ? (e->otz_has_w ? e->otz_w : nullptr) : (e->tz_has_w ? e->tz_w : nullptr);
+    if (!has_coils) { coils = 0; sens_n = 1; }
+    if (!segmented) map_n = 1;
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, L = e->orp.segments;
+    const size_t M = (size_t)e->nc.m, lines = (size_t)N * (has_coils ? coils : 1), sn = (size_t)sens_n * coils * H * W;
     if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
-    if ((rc = ws_grow(e, "non-Cartesian constants", {{(void**)&e->nc_y, &e->nc_y_cap, (size_t)N * M * sizeof(float2), false},
-                                                     {(void**)&e->nc_w, &e->nc_w_cap, w ? M * sizeof(float) : 0, false},
-                                                     {(void**)&e->nc_mpart, &e->nc_mpart_cap, (size_t)N * nufft_sample_chunks((int64_t)M) * sizeof(double), false}})))
+    if ((rc = op_ensure(e, takes, coils))) return rc;
+    if (toeplitz && segmented) {
+        const int cb = has_coils ? otz_coil_block(e, coils, map_n) : 1;
+        if ((rc = otz_ensure(e, N * cb, has_coils ? (size_t)N * cb : 0))) return rc;
+    } else if (toeplitz && has_coils) {
+        if ((rc = tz_ensure(e, (size_t)N * ns_block_of(e, coils), true))) return rc;
+    }
+    static const char* const labels[4] = {"non-Cartesian constants", "non-Cartesian SENSE constants", "off-resonance constants",
+                                          "multi-coil off-resonance constants"};
+    if ((rc = ws_grow(e, labels[takes & 3],
+                      {{(void**)&e->st_y, &e->st_y_cap, lines * M * sizeof(float2), false},
+                       {(void**)&e->st_sens, &e->st_sens_cap, sn * sizeof(float2), false},
+                       {(void**)&e->st_maps, &e->st_maps_cap, segmented ? (size_t)map_n * L * H * W * sizeof(float2) : 0, false},
+                       {(void**)&e->st_w, &e->st_w_cap, w ? M * sizeof(float) : 0, false},
+                       {(void**)&e->st_mpart, &e->st_mpart_cap, lines * nufft_sample_chunks((int64_t)M) * sizeof(double), false}})))
         return rc;
-    HIP_TRY(hipMemcpyAsync(e->nc_y, y, (size_t)N * M * sizeof(float2), hipMemcpyDeviceToDevice, s));
-    if (w) HIP_TRY(hipMemcpyAsync(e->nc_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->st_y, y, lines * M * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    if (has_coils) HIP_TRY(hipMemcpyAsync(e->st_sens, sens, sn * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    if (w) HIP_TRY(hipMemcpyAsync(e->st_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
-    if ((rc = nc_adjoint(e, e->nc_y, w ? e->nc_w : nullptr, N, nullptr, nullptr, nullptr, mc_aty(e), nullptr, s))) return rc;
+    if (segmented) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, e->st_maps, s));
+    }
+    const NcOp o = arg_op(takes, e->st_sens, coils, sens_n, e->st_maps, map_n);
+    if ((rc = op_adjoint(e, o, e->st_y, w ? e->st_w : nullptr, N, mc_aty(e), s))) return rc;
     if (with_iterate) {
         Prof p(e, s, PROF_OTHER, -1);
         HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
     }
-    commit_stage(e, {STAGE_NC, toeplitz, 0, 1, cg_iters, w != nullptr});
+    commit_stage(e, {stage_kind_of(takes), !toeplitz ? FORM_GRID : segmented ? FORM_OTZ : FORM_TZ, coils, sens_n, cg_iters, w != nullptr, map_n});
+    return PNP_OK;
+}
+
+// The four pnp_acquire_* members of the non-Cartesian headers: y = A gt + noise on the operator `takes` names and, where asked, aty0 = A^H
+// (dcf . y) and x0 = max(aty0, 0).  A segmented acquisition's maps go to a buffer of its own: it disturbs no live episode.  Every rejection
+// happens before any HIP call, and leaves the outputs untouched
+int nc_acquire(const char* fn, pnp_engine* e, int takes, const float* gt, const float* sens, int coils, int sens_n, const float* omega, int map_n,
+               const float* dcf, double sigma_n, uint64_t seed, int flags, float* y, float* aty0, float* x0, hipStream_t s) {
+    const bool has_coils = takes & TAKES_COILS, segmented = takes & TAKES_MAPS;
+    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
+    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "%s: sigma_n must be finite and >= 0 (got %g)", fn, sigma_n);
+    if (int rc = op_check_scalars(fn, takes, coils, sens_n, map_n)) return rc;
+    if (!gt) return fail(PNP_ERR_INVALID, "%s: null gt", fn);
+    if (has_coils && !sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
+    if (segmented && !omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
+    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
+    if (takes) {                                            // (the plain pair's acquisition names no aliasing rule)
+        const auto input = [&](const float* p) { return p == gt || (has_coils && p == sens) || (segmented && p == omega); };
+        if (input(y) || (aty0 && (input(aty0) || aty0 == y)) || (x0 && (input(x0) || x0 == y)))
+            return fail(PNP_ERR_INVALID, "%s: no output may alias gt, %s or another output", fn,
+                        !segmented ? "sens" : has_coils ? "sens, omega" : "omega");
+    }
+    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
+    if (int rc = op_check(fn, e, takes, coils, sens_n, map_n)) return rc;
+    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
+    PNP_ON_DEVICE(e);
+    int rc;
+    if ((rc = op_ensure(e, takes, coils, segmented ? (size_t)map_n * e->orp.segments * H * W * sizeof(float2) : 0))) return rc;
+    if (segmented) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, e->acq_maps, s));
+    }
+    const NcOp o = arg_op(takes, (const float2*)sens, coils, sens_n, e->acq_maps, map_n);
+    if ((rc = op_forward(e, o, nullptr, gt, N, (float2*)y, s))) return rc;
+    if (sigma_n != 0.0) {                                   // a noiseless acquisition draws nothing and keeps the forward's own bits
+        Prof p(e, s, PROF_OTHER, -1);
+        if (has_coils) HIP_TRY(launch_ncsense_noise((float2*)y, sigma_n, seed, coils, e->nc, N, s));
+        else HIP_TRY(launch_nufft_noise((float2*)y, sigma_n, seed, e->nc, N, s));
+    }
+    if (!aty0 && !x0) return PNP_OK;
+    float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the image goes to the data-fidelity stage's scratch plane
+    if ((rc = op_adjoint(e, o, (const float2*)y, dcf, N, a, s))) return rc;
+    if (x0) {
+        Prof p(e, s, PROF_OTHER, -1);
+        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
+    }
     return PNP_OK;
 }
 
@@ -2081,7 +2201,7 @@ int pnp_nufft_plan(pnp_handle e, const double* traj, int64_t m, int gh, int gw, 
     if (D.m > 0) (void)hipDeviceSynchronize();              // no launch still reads the plan being replaced
     // from here on the old plan is gone: its non-Cartesian constants are dropped with it
     D.m = 0;
-    drop_stage(e, false);
+    drop_stage(e, DROP_NONCART);
     e->tz_planned = false;                                  // the spectrum belongs to the plan it was built for
     e->orp.segments = 0;                                    // ... and so does the off-resonance plan
     e->orp.kind = 0;
@@ -2144,13 +2264,15 @@ int pnp_nufft_adjoint(pnp_handle e, const float* samples, const float* weights, 
 
 int pnp_set_kspace_nc(pnp_handle e, const float* y, const float* w, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    return nc_install("pnp_set_kspace_nc", e, false, false, nullptr, (const float2*)y, w, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return nc_install("pnp_set_kspace_nc", e, 0, false, false, nullptr, (const float2*)y, nullptr, 0, 1, nullptr, 1, w, cg_iters, nullptr, nullptr,
+                      nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_nc")
 }
 
 int pnp_reset_nc(pnp_handle e, const float* x0, const float* y, const float* w, int cg_iters, float* x, float* z, float* u, void* stream) {
     PNP_API_BEGIN
-    return nc_install("pnp_reset_nc", e, true, false, (const float2*)x0, (const float2*)y, w, cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
+    return nc_install("pnp_reset_nc", e, 0, true, false, (const float2*)x0, (const float2*)y, nullptr, 0, 1, nullptr, 1, w, cg_iters, x, (float2*)z,
+                      (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_nc")
 }
 
@@ -2169,106 +2291,15 @@ int pnp_nc_normal(pnp_handle e, const float* pv, const float* mu, float* q, void
 int pnp_acquire_nc(pnp_handle e, const float* gt, const float* dcf, double sigma_n, uint64_t seed, int flags, float* y, float* aty0, float* x0,
                    void* stream) {
     PNP_API_BEGIN
-    // every rejection happens before any HIP call, and leaves the outputs untouched
-    if (flags != 0) return fail(PNP_ERR_INVALID, "pnp_acquire_nc: flags must be 0 (got 0x%x)", (unsigned)flags);
-    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "pnp_acquire_nc: sigma_n must be finite and >= 0 (got %g)", sigma_n);
-    if (!gt) return fail(PNP_ERR_INVALID, "pnp_acquire_nc: null gt");
-    if (!y) return fail(PNP_ERR_INVALID, "pnp_acquire_nc: null y");
-    if (!e) return fail(PNP_ERR_INVALID, "pnp_acquire_nc: null handle");
-    if (int rc = nc_need_plan("pnp_acquire_nc", e)) return rc;
-    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
-    PNP_ON_DEVICE(e);
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = nc_forward(e, nullptr, gt, N, (float2*)y, s))) return rc;
-    if (sigma_n != 0.0) {                                   // a noiseless acquisition draws nothing and keeps the forward's own bits
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_nufft_noise((float2*)y, sigma_n, seed, e->nc, N, s));
-    }
-    if (!aty0 && !x0) return PNP_OK;
-    float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the image goes to the data-fidelity stage's scratch plane
-    if ((rc = nc_adjoint(e, (const float2*)y, dcf, N, nullptr, nullptr, nullptr, a, nullptr, s))) return rc;
-    if (x0) {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
-    }
-    return PNP_OK;
+    return nc_acquire("pnp_acquire_nc", e, 0, gt, nullptr, 0, 1, nullptr, 1, dcf, sigma_n, seed, flags, y, aty0, x0, (hipStream_t)stream);
     PNP_API_END("pnp_acquire_nc")
 }
 
 // ---- non-Cartesian SENSE (include/pnpadmm_ncsense.h) ---------------------------------------------------
-namespace {
-
-// the coil-block scratch for `coils` coils: the block's grids and samples
-int ns_ensure(pnp_engine* e, int coils) {
-    const size_t planes = (size_t)e->cfg.n * ns_block_of(e, coils);
-    return ws_grow(e, "non-Cartesian SENSE scratch", {{(void**)&e->ns_grid, &e->ns_grid_cap, planes * e->nc.gh * e->nc.gw * sizeof(float2), false},
-                                                     {(void**)&e->ns_samp, &e->ns_samp_cap, planes * (size_t)e->nc.m * sizeof(float2), false},
-                                                     {(void**)&e->ns_img, &e->ns_img_cap,
-                                                      (e->ns_naive & (NS_PAD | NS_CROP)) ? planes * e->cfg.h * e->cfg.w * sizeof(float2) : 0, false}});
-}
-
-// argument errors shared by the entry points that take maps: the scalar ranges need no handle and come first
-int ns_check_scalars(const char* fn, int coils, int sens_n) {
-    if (coils < 1 || coils > PNP_MC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_MC_MAX_COILS, coils);
-    if (sens_n < 1) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n (got %d)", fn, sens_n);
-    return PNP_OK;
-}
-int ns_check(const char* fn, const pnp_engine* e, int coils, int sens_n) {
-    const int N = e->cfg.n;
-    if (sens_n != 1 && sens_n != N) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n=%d", fn, N);
-    if ((long long)N * ns_block_of(e, coils) > 65535)
-        return fail(PNP_ERR_INVALID, "%s: n * min(coils, block) must be <= 65535 (got %d * %d)", fn, N, ns_block_of(e, coils));
-    return nc_need_plan(fn, e);
-}
-// pnp_set_kspace_ncsense (no iterate) / pnp_reset_ncsense and, `toeplitz`, their _tz forms (w: the spectrum's weights, whatever is passed):
-// the episode constants of the stage - y, w, the maps, A^H W y - and optionally the iterate.  Every rejection happens before any HIP call
-int ns_install(const char* fn, pnp_engine* e, bool with_iterate, bool toeplitz, const float2* x0, const float2* y, const float2* sens, int coils,
-               int sens_n, const float* w, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
-    int rc;
-    if ((rc = ns_check_scalars(fn, coils, sens_n))) return rc;
-    if ((rc = nc_check_cg(fn, cg_iters))) return rc;
-    if (with_iterate && !x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
-    if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if ((rc = ns_check(fn, e, coils, sens_n))) return rc;
-    if (toeplitz && (rc = tz_need_spectrum(fn, e))) return rc;
-    PNP_ON_DEVICE(e);
-    if (toeplitz) {
-        if ((rc = tz_ensure(e, (size_t)e->cfg.n * ns_block_of(e, coils), true))) return rc;
-        w = e->tz_has_w ? e->tz_w : nullptr;
-    }
-    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
-    const size_t M = (size_t)e->nc.m, ym = (size_t)N * coils * M, sn = (size_t)sens_n * coils * H * W;
-    if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
-    if ((rc = ns_ensure(e, coils))) return rc;
-    if ((rc = ws_grow(e, "non-Cartesian SENSE constants",
-                      {{(void**)&e->ns_y, &e->ns_y_cap, ym * sizeof(float2), false},
-                       {(void**)&e->ns_sens, &e->ns_sens_cap, sn * sizeof(float2), false},
-                       {(void**)&e->ns_w, &e->ns_w_cap, w ? M * sizeof(float) : 0, false},
-                       {(void**)&e->ns_mpart, &e->ns_mpart_cap, (size_t)N * coils * nufft_sample_chunks((int64_t)M) * sizeof(double), false}})))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(e->ns_y, y, ym * sizeof(float2), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->ns_sens, sens, sn * sizeof(float2), hipMemcpyDeviceToDevice, s));
-    if (w) HIP_TRY(hipMemcpyAsync(e->ns_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
-    if ((rc = ns_adjoint(e, e->ns_y, w ? e->ns_w : nullptr, e->ns_sens, sens_n, coils, N, mc_aty(e), s))) return rc;
-    if (with_iterate) {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
-    }
-    commit_stage(e, {STAGE_NS, toeplitz, coils, sens_n, cg_iters, w != nullptr});
-    return PNP_OK;
-}
-
-}  // namespace
-
 int pnp_nufft_forward_mc(pnp_handle e, const float* img, const float* sens, int coils, int sens_n, int batch, float* samples, void* stream) {
     PNP_API_BEGIN
     const char* fn = "pnp_nufft_forward_mc";
-    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (int rc = op_check_scalars(fn, TAKES_COILS, coils, sens_n, 0)) return rc;
     if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
     if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
     if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
@@ -2276,9 +2307,9 @@ int pnp_nufft_forward_mc(pnp_handle e, const float* img, const float* sens, int 
     if (samples == img || samples == sens) return fail(PNP_ERR_INVALID, "%s: samples must not alias img or sens", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
-    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    if (int rc = op_check(fn, e, TAKES_COILS, coils, sens_n, 0)) return rc;
     PNP_ON_DEVICE(e);
-    if (int rc = ns_ensure(e, coils)) return rc;
+    if (int rc = op_ensure(e, TAKES_COILS, coils)) return rc;
     return ns_forward(e, (const float2*)img, nullptr, (const float2*)sens, sens_n, coils, batch, (float2*)samples, (hipStream_t)stream);
     PNP_API_END("pnp_nufft_forward_mc")
 }
@@ -2287,7 +2318,7 @@ int pnp_nufft_adjoint_mc(pnp_handle e, const float* samples, const float* weight
                          void* stream) {
     PNP_API_BEGIN
     const char* fn = "pnp_nufft_adjoint_mc";
-    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (int rc = op_check_scalars(fn, TAKES_COILS, coils, sens_n, 0)) return rc;
     if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
     if (!samples) return fail(PNP_ERR_INVALID, "%s: null samples", fn);
     if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
@@ -2295,25 +2326,25 @@ int pnp_nufft_adjoint_mc(pnp_handle e, const float* samples, const float* weight
     if (img == samples || img == sens || (const float*)img == weights) return fail(PNP_ERR_INVALID, "%s: img must not alias samples, weights or sens", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
-    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    if (int rc = op_check(fn, e, TAKES_COILS, coils, sens_n, 0)) return rc;
     PNP_ON_DEVICE(e);
-    if (int rc = ns_ensure(e, coils)) return rc;
+    if (int rc = op_ensure(e, TAKES_COILS, coils)) return rc;
     return ns_adjoint(e, (const float2*)samples, weights, (const float2*)sens, sens_n, coils, batch, (float2*)img, (hipStream_t)stream);
     PNP_API_END("pnp_nufft_adjoint_mc")
 }
 
 int pnp_set_kspace_ncsense(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, const float* w, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    return ns_install("pnp_set_kspace_ncsense", e, false, false, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, w, cg_iters, nullptr,
-                      nullptr, nullptr, (hipStream_t)stream);
+    return nc_install("pnp_set_kspace_ncsense", e, TAKES_COILS, false, false, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, nullptr,
+                      1, w, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_ncsense")
 }
 
 int pnp_reset_ncsense(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, const float* w, int cg_iters, float* x,
                       float* z, float* u, void* stream) {
     PNP_API_BEGIN
-    return ns_install("pnp_reset_ncsense", e, true, false, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, w, cg_iters, x,
-                      (float2*)z, (float2*)u, (hipStream_t)stream);
+    return nc_install("pnp_reset_ncsense", e, TAKES_COILS, true, false, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n,
+                      nullptr, 1, w, cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_ncsense")
 }
 
@@ -2334,126 +2365,13 @@ int pnp_ncsense_normal(pnp_handle e, const float* pv, const float* mu, float* q,
 int pnp_acquire_ncsense(pnp_handle e, const float* gt, const float* sens, int coils, int sens_n, const float* dcf, double sigma_n, uint64_t seed,
                         int flags, float* y, float* aty0, float* x0, void* stream) {
     PNP_API_BEGIN
-    const char* fn = "pnp_acquire_ncsense";
-    // every rejection happens before any HIP call, and leaves the outputs untouched
-    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
-    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "%s: sigma_n must be finite and >= 0 (got %g)", fn, sigma_n);
-    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
-    if (!gt) return fail(PNP_ERR_INVALID, "%s: null gt", fn);
-    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (y == gt || y == sens || (aty0 && (aty0 == gt || aty0 == sens || aty0 == y)) || (x0 && (x0 == gt || x0 == sens || x0 == y)))
-        return fail(PNP_ERR_INVALID, "%s: no output may alias gt, sens or another output", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
-    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
-    PNP_ON_DEVICE(e);
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = ns_ensure(e, coils))) return rc;
-    if ((rc = ns_forward(e, nullptr, gt, (const float2*)sens, sens_n, coils, N, (float2*)y, s))) return rc;
-    if (sigma_n != 0.0) {                                   // a noiseless acquisition draws nothing and keeps the forward's own bits
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_ncsense_noise((float2*)y, sigma_n, seed, coils, e->nc, N, s));
-    }
-    if (!aty0 && !x0) return PNP_OK;
-    float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the image goes to the data-fidelity stage's scratch plane
-    if ((rc = ns_adjoint(e, (const float2*)y, dcf, (const float2*)sens, sens_n, coils, N, a, s))) return rc;
-    if (x0) {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
-    }
-    return PNP_OK;
+    return nc_acquire("pnp_acquire_ncsense", e, TAKES_COILS, gt, sens, coils, sens_n, nullptr, 1, dcf, sigma_n, seed, flags, y, aty0, x0,
+                      (hipStream_t)stream);
     PNP_API_END("pnp_acquire_ncsense")
 }
 
 // ---- off-resonance correction (include/pnpadmm_offres.h) -------------------------------------------------
 static_assert(PNP_MC_MAX_COILS == kOffresMaxSegments, "the header's limit is the plan's");
-
-namespace {
-
-int or_need_plan(const char* fn, const pnp_engine* e) {
-    if (int rc = nc_need_plan(fn, e)) return rc;
-    return e->orp.segments > 0 ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no off-resonance plan (pnp_offres_plan)", fn);
-}
-// the handle-dependent argument errors of the entry points that take a field map or segment maps
-int or_check(const char* fn, const pnp_engine* e, int map_n) {
-    if (map_n != 1 && map_n != e->cfg.n) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n=%d", fn, e->cfg.n);
-    if (int rc = or_need_plan(fn, e)) return rc;
-    if ((long long)e->cfg.n * or_block_of(e) > 65535)
-        return fail(PNP_ERR_INVALID, "%s: n * min(segments, block) must be <= 65535 (got %d * %d)", fn, e->cfg.n, or_block_of(e));
-    return PNP_OK;
-}
-// the segment-block scratch (the coil-block scratch of the non-Cartesian SENSE stage, for a block of segments) and `maps_need` bytes of the
-// acquisition's own segment maps
-int or_ensure(pnp_engine* e, size_t maps_need = 0) {
-    const size_t planes = (size_t)e->cfg.n * or_block_of(e);
-    return ws_grow(e, "off-resonance scratch", {{(void**)&e->ns_grid, &e->ns_grid_cap, planes * e->nc.gh * e->nc.gw * sizeof(float2), false},
-                                               {(void**)&e->ns_samp, &e->ns_samp_cap, planes * (size_t)e->nc.m * sizeof(float2), false},
-                                               {(void**)&e->ns_img, &e->ns_img_cap,
-                                                (e->ns_naive & (NS_PAD | NS_CROP)) ? planes * e->cfg.h * e->cfg.w * sizeof(float2) : 0, false},
-                                               {(void**)&e->or_amaps, &e->or_amaps_cap, maps_need, false}});
-}
-
-// the Toeplitz spectra of include/pnpadmm_offres_tz.h, which its installers and applications need
-int otz_need_spectra(const char* fn, const pnp_engine* e) {
-    if (int rc = or_need_plan(fn, e)) return rc;
-    return e->otz_planned ? PNP_OK : fail(PNP_ERR_STATE, "%s: the handle has no Toeplitz off-resonance spectra (pnp_offres_tz_plan)", fn);
-}
-// the pass buffers of that form for applications over `slices` slices and, multi-coil, `cimg_planes` coil images
-int otz_ensure(pnp_engine* e, int slices, size_t cimg_planes) {
-    const size_t hw = (size_t)e->cfg.h * e->cfg.w, planes = (size_t)otz_slice_block(e, slices) * e->orp.segments;
-    return ws_grow(e, "Toeplitz off-resonance scratch", {{(void**)&e->otz_img, &e->otz_img_cap, planes * hw * sizeof(float2), false},
-                                                        {(void**)&e->otz_x, &e->otz_x_cap, planes * 4 * hw * sizeof(float2), false},
-                                                        {(void**)&e->otz_y, &e->otz_y_cap, planes * 4 * hw * sizeof(float2), false},
-                                                        {(void**)&e->otz_cimg, &e->otz_cimg_cap, cimg_planes * hw * sizeof(float2), false}});
-}
-
-// pnp_set_kspace_offres (no iterate) / pnp_reset_offres and, `toeplitz`, their _tz forms of include/pnpadmm_offres_tz.h (w: the spectra's
-// weights, whatever is passed): the episode constants of the stage - y, w, the segment maps of omega, A^H W y - and optionally the iterate.
-// Every rejection happens before any HIP call
-int or_install(const char* fn, pnp_engine* e, bool with_iterate, bool toeplitz, const float2* x0, const float2* y, const float* omega, int map_n,
-               const float* w, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
-    int rc;
-    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
-    if ((rc = nc_check_cg(fn, cg_iters))) return rc;
-    if (with_iterate && !x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (!omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
-    if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if ((rc = or_check(fn, e, map_n))) return rc;
-    if (toeplitz && (rc = otz_need_spectra(fn, e))) return rc;
-    PNP_ON_DEVICE(e);
-    if (toeplitz) w = e->otz_has_w ? e->otz_w : nullptr;
-    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, L = e->orp.segments;
-    const size_t M = (size_t)e->nc.m;
-    if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
-    if ((rc = or_ensure(e))) return rc;
-    if (toeplitz && (rc = otz_ensure(e, N, 0))) return rc;
-    if ((rc = ws_grow(e, "off-resonance constants",
-                      {{(void**)&e->or_y, &e->or_y_cap, (size_t)N * M * sizeof(float2), false},
-                       {(void**)&e->or_maps, &e->or_maps_cap, (size_t)map_n * L * H * W * sizeof(float2), false},
-                       {(void**)&e->or_w, &e->or_w_cap, w ? M * sizeof(float) : 0, false},
-                       {(void**)&e->or_mpart, &e->or_mpart_cap, (size_t)N * nufft_sample_chunks((int64_t)M) * sizeof(double), false}})))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(e->or_y, y, (size_t)N * M * sizeof(float2), hipMemcpyDeviceToDevice, s));
-    if (w) HIP_TRY(hipMemcpyAsync(e->or_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
-    {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, e->or_maps, s));
-    }
-    if ((rc = or_adjoint(e, e->or_y, w ? e->or_w : nullptr, e->or_maps, map_n, N, nullptr, nullptr, nullptr, mc_aty(e), nullptr, s))) return rc;
-    if (with_iterate) {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
-    }
-    commit_stage(e, {STAGE_OR, false, 0, map_n, cg_iters, w != nullptr, 1, toeplitz});
-    return PNP_OK;
-}
-
-}  // namespace
 
 int pnp_offres_plan(pnp_handle e, const double* t, int segments, int flags) {
     PNP_API_BEGIN
@@ -2483,7 +2401,7 @@ int pnp_offres_plan(pnp_handle e, const double* t, int segments, int flags) {
     D.segments = 0;
     D.kind = 0;
     e->otz_planned = false;                                 // the Toeplitz spectra belong to the plan's coefficients
-    if (e->stage.kind == STAGE_OR || e->stage.kind == STAGE_ORS) drop_stage(e, false);
+    drop_stage(e, DROP_SEGMENTED);
     e->or_seg_h = P.seg;
     HIP_TRY(nc_upload(D.tau, P.tau.data(), P.tau.size() * sizeof(double)));
     HIP_TRY(nc_upload(D.seg, P.seg.data(), M * sizeof(int32_t)));
@@ -2522,7 +2440,7 @@ int pnp_offres_plan_ls(pnp_handle e, const double* t, int segments, double omega
     D.segments = 0;
     D.kind = 0;
     e->otz_planned = false;                                 // the Toeplitz spectra belong to the plan's coefficients
-    if (e->stage.kind == STAGE_OR || e->stage.kind == STAGE_ORS) drop_stage(e, false);
+    drop_stage(e, DROP_SEGMENTED);
     HIP_TRY(nc_upload(D.tau, P.tau.data(), P.tau.size() * sizeof(double)));
     HIP_TRY(nc_upload(D.coef, P.coef.data(), P.coef.size() * sizeof(float)));
     D.segments = P.segments;
@@ -2553,12 +2471,12 @@ int pnp_offres_segments(pnp_handle e) { return e && e->nc.m > 0 ? e->orp.segment
 int pnp_offres_maps(pnp_handle e, const float* omega, int map_n, float* maps, void* stream) {
     PNP_API_BEGIN
     const char* fn = "pnp_offres_maps";
-    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    if (int rc = op_check_scalars(fn, TAKES_MAPS, 0, 0, map_n)) return rc;
     if (!omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
     if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
     if (maps == omega) return fail(PNP_ERR_INVALID, "%s: maps must not alias omega", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if (int rc = or_check(fn, e, map_n)) return rc;
+    if (int rc = op_check(fn, e, TAKES_MAPS, 0, 0, map_n)) return rc;
     PNP_ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     Prof p(e, s, PROF_OTHER, -1);
@@ -2570,7 +2488,7 @@ int pnp_offres_maps(pnp_handle e, const float* omega, int map_n, float* maps, vo
 int pnp_offres_forward(pnp_handle e, const float* img, const float* maps, int map_n, int batch, float* samples, void* stream) {
     PNP_API_BEGIN
     const char* fn = "pnp_offres_forward";
-    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    if (int rc = op_check_scalars(fn, TAKES_MAPS, 0, 0, map_n)) return rc;
     if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
     if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
     if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
@@ -2578,9 +2496,9 @@ int pnp_offres_forward(pnp_handle e, const float* img, const float* maps, int ma
     if (samples == img || samples == maps) return fail(PNP_ERR_INVALID, "%s: samples must not alias img or maps", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
-    if (int rc = or_check(fn, e, map_n)) return rc;
+    if (int rc = op_check(fn, e, TAKES_MAPS, 0, 0, map_n)) return rc;
     PNP_ON_DEVICE(e);
-    if (int rc = or_ensure(e)) return rc;
+    if (int rc = op_ensure(e, TAKES_MAPS, 0)) return rc;
     return or_forward(e, (const float2*)img, nullptr, (const float2*)maps, map_n, batch, (float2*)samples, (hipStream_t)stream);
     PNP_API_END("pnp_offres_forward")
 }
@@ -2588,7 +2506,7 @@ int pnp_offres_forward(pnp_handle e, const float* img, const float* maps, int ma
 int pnp_offres_adjoint(pnp_handle e, const float* samples, const float* weights, const float* maps, int map_n, int batch, float* img, void* stream) {
     PNP_API_BEGIN
     const char* fn = "pnp_offres_adjoint";
-    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    if (int rc = op_check_scalars(fn, TAKES_MAPS, 0, 0, map_n)) return rc;
     if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
     if (!samples) return fail(PNP_ERR_INVALID, "%s: null samples", fn);
     if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
@@ -2596,9 +2514,9 @@ int pnp_offres_adjoint(pnp_handle e, const float* samples, const float* weights,
     if (img == samples || img == maps || (const float*)img == weights) return fail(PNP_ERR_INVALID, "%s: img must not alias samples, weights or maps", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
-    if (int rc = or_check(fn, e, map_n)) return rc;
+    if (int rc = op_check(fn, e, TAKES_MAPS, 0, 0, map_n)) return rc;
     PNP_ON_DEVICE(e);
-    if (int rc = or_ensure(e)) return rc;
+    if (int rc = op_ensure(e, TAKES_MAPS, 0)) return rc;
     return or_adjoint(e, (const float2*)samples, weights, (const float2*)maps, map_n, batch, nullptr, nullptr, nullptr, (float2*)img, nullptr,
                       (hipStream_t)stream);
     PNP_API_END("pnp_offres_adjoint")
@@ -2606,16 +2524,16 @@ int pnp_offres_adjoint(pnp_handle e, const float* samples, const float* weights,
 
 int pnp_set_kspace_offres(pnp_handle e, const float* y, const float* omega, int map_n, const float* w, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    return or_install("pnp_set_kspace_offres", e, false, false, nullptr, (const float2*)y, omega, map_n, w, cg_iters, nullptr, nullptr, nullptr,
-                      (hipStream_t)stream);
+    return nc_install("pnp_set_kspace_offres", e, TAKES_MAPS, false, false, nullptr, (const float2*)y, nullptr, 0, 1, omega, map_n, w, cg_iters,
+                      nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_offres")
 }
 
 int pnp_reset_offres(pnp_handle e, const float* x0, const float* y, const float* omega, int map_n, const float* w, int cg_iters, float* x, float* z,
                      float* u, void* stream) {
     PNP_API_BEGIN
-    return or_install("pnp_reset_offres", e, true, false, (const float2*)x0, (const float2*)y, omega, map_n, w, cg_iters, x, (float2*)z, (float2*)u,
-                      (hipStream_t)stream);
+    return nc_install("pnp_reset_offres", e, TAKES_MAPS, true, false, (const float2*)x0, (const float2*)y, nullptr, 0, 1, omega, map_n, w, cg_iters,
+                      x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_offres")
 }
 
@@ -2636,135 +2554,17 @@ int pnp_offres_normal(pnp_handle e, const float* pv, const float* mu, float* q, 
 int pnp_acquire_offres(pnp_handle e, const float* gt, const float* omega, int map_n, const float* dcf, double sigma_n, uint64_t seed, int flags,
                        float* y, float* aty0, float* x0, void* stream) {
     PNP_API_BEGIN
-    const char* fn = "pnp_acquire_offres";
-    // every rejection happens before any HIP call, and leaves the outputs untouched
-    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
-    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "%s: sigma_n must be finite and >= 0 (got %g)", fn, sigma_n);
-    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
-    if (!gt) return fail(PNP_ERR_INVALID, "%s: null gt", fn);
-    if (!omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (y == gt || y == omega || (aty0 && (aty0 == gt || aty0 == omega || aty0 == y)) || (x0 && (x0 == gt || x0 == omega || x0 == y)))
-        return fail(PNP_ERR_INVALID, "%s: no output may alias gt, omega or another output", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if (int rc = or_check(fn, e, map_n)) return rc;
-    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
-    PNP_ON_DEVICE(e);
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = or_ensure(e, (size_t)map_n * e->orp.segments * H * W * sizeof(float2)))) return rc;
-    {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, e->or_amaps, s));
-    }
-    if ((rc = or_forward(e, nullptr, gt, e->or_amaps, map_n, N, (float2*)y, s))) return rc;
-    if (sigma_n != 0.0) {                                   // a noiseless acquisition draws nothing and keeps the forward's own bits
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_nufft_noise((float2*)y, sigma_n, seed, e->nc, N, s));
-    }
-    if (!aty0 && !x0) return PNP_OK;
-    float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the image goes to the data-fidelity stage's scratch plane
-    if ((rc = or_adjoint(e, (const float2*)y, dcf, e->or_amaps, map_n, N, nullptr, nullptr, nullptr, a, nullptr, s))) return rc;
-    if (x0) {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
-    }
-    return PNP_OK;
+    return nc_acquire("pnp_acquire_offres", e, TAKES_MAPS, gt, nullptr, 0, 1, omega, map_n, dcf, sigma_n, seed, flags, y, aty0, x0,
+                      (hipStream_t)stream);
     PNP_API_END("pnp_acquire_offres")
 }
 
 // ---- off-resonance correction for multi-coil data (include/pnpadmm_offres_mc.h) ----------------------------
-namespace {
-
-// argument errors shared by the entry points of that header: the scalar ranges need no handle and come first
-int om_check_scalars(const char* fn, int coils, int sens_n, int map_n) {
-    if (coils < 1 || coils > PNP_MC_MAX_COILS) return fail(PNP_ERR_INVALID, "%s: coils must be 1..%d (got %d)", fn, PNP_MC_MAX_COILS, coils);
-    if (sens_n < 1) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n (got %d)", fn, sens_n);
-    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
-    return PNP_OK;
-}
-int om_check(const char* fn, const pnp_engine* e, int coils, int sens_n, int map_n) {
-    const int N = e->cfg.n;
-    if (sens_n != 1 && sens_n != N) return fail(PNP_ERR_INVALID, "%s: sens_n must be 1 or n=%d", fn, N);
-    if (map_n != 1 && map_n != N) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n=%d", fn, N);
-    if (int rc = or_need_plan(fn, e)) return rc;
-    if ((long long)N * om_block_of(e, coils) * or_block_of(e) > 65535)
-        return fail(PNP_ERR_INVALID, "%s: n * min(coils, coil block) * min(segments, block) must be <= 65535 (got %d * %d * %d)", fn, N,
-                    om_block_of(e, coils), or_block_of(e));
-    return PNP_OK;
-}
-// the block scratch for `coils` coils - the coil-block scratch of the non-Cartesian SENSE stage for a block of coils x segments, the block's
-// samples and the segment chain's partials - and `amaps_need` bytes of the acquisition's own segment maps
-int om_ensure(pnp_engine* e, int coils, size_t amaps_need = 0) {
-    const size_t N = (size_t)e->cfg.n, cbc = (size_t)om_block_of(e, coils), planes = N * cbc * or_block_of(e);
-    const size_t HW = (size_t)e->cfg.h * e->cfg.w, M = (size_t)e->nc.m;
-    return ws_grow(e, "multi-coil off-resonance scratch",
-                   {{(void**)&e->ns_grid, &e->ns_grid_cap, planes * e->nc.gh * e->nc.gw * sizeof(float2), false},
-                    {(void**)&e->ns_samp, &e->ns_samp_cap, planes * M * sizeof(float2), false},
-                    {(void**)&e->ns_img, &e->ns_img_cap, (e->ns_naive & (NS_PAD | NS_CROP)) ? planes * HW * sizeof(float2) : 0, false},
-                    {(void**)&e->om_samp, &e->om_samp_cap, N * cbc * M * sizeof(float2), false},
-                    // the partials: the fused crop touches them only when the segments do not fit one block; the composed adjoint's coil images
-                    {(void**)&e->om_part, &e->om_part_cap,
-                     ((e->om_naive & ORM_CROP) || e->orp.segments > or_block_of(e)) ? N * cbc * HW * sizeof(float2) : 0, false},
-                    {(void**)&e->om_img, &e->om_img_cap, e->om_naive ? N * HW * sizeof(float2) : 0, false},
-                    {(void**)&e->om_line, &e->om_line_cap, e->om_naive ? N * M * sizeof(float2) : 0, false},
-                    {(void**)&e->om_amaps, &e->om_amaps_cap, amaps_need, false}});
-}
-
-// pnp_set_kspace_offres_mc (no iterate) / pnp_reset_offres_mc and, `toeplitz`, their _tz forms of include/pnpadmm_offres_tz.h (w: the spectra's
-// weights, whatever is passed): the episode constants of the stage - y, w, the coil maps, the segment maps of omega, A^H W y - and optionally
-// the iterate.  Every rejection happens before any HIP call
-int om_install(const char* fn, pnp_engine* e, bool with_iterate, bool toeplitz, const float2* x0, const float2* y, const float2* sens, int coils, int sens_n,
-               const float* omega, int map_n, const float* w, int cg_iters, float* x, float2* z, float2* u, hipStream_t s) {
-    int rc;
-    if ((rc = om_check_scalars(fn, coils, sens_n, map_n))) return rc;
-    if ((rc = nc_check_cg(fn, cg_iters))) return rc;
-    if (with_iterate && !x0) return fail(PNP_ERR_INVALID, "%s: null x0", fn);
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
-    if (!omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
-    if (with_iterate && (!x || !z || !u)) return fail(PNP_ERR_INVALID, "%s: null x, z or u", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if ((rc = om_check(fn, e, coils, sens_n, map_n))) return rc;
-    if (toeplitz && (rc = otz_need_spectra(fn, e))) return rc;
-    PNP_ON_DEVICE(e);
-    if (toeplitz) w = e->otz_has_w ? e->otz_w : nullptr;
-    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w, L = e->orp.segments;
-    const size_t M = (size_t)e->nc.m, ym = (size_t)N * coils * M, sn = (size_t)sens_n * coils * H * W;
-    if ((rc = mc_ensure(e, 0, 0, 0))) return rc;            // the CG vectors, partial sums and scalars: the coil workspace's, coil-independent
-    if ((rc = om_ensure(e, coils))) return rc;
-    if (toeplitz && (rc = otz_ensure(e, N * otz_coil_block(e, coils, map_n), (size_t)N * otz_coil_block(e, coils, map_n)))) return rc;
-    if ((rc = ws_grow(e, "multi-coil off-resonance constants",
-                      {{(void**)&e->om_y, &e->om_y_cap, ym * sizeof(float2), false},
-                       {(void**)&e->om_sens, &e->om_sens_cap, sn * sizeof(float2), false},
-                       {(void**)&e->om_maps, &e->om_maps_cap, (size_t)map_n * L * H * W * sizeof(float2), false},
-                       {(void**)&e->om_w, &e->om_w_cap, w ? M * sizeof(float) : 0, false},
-                       {(void**)&e->om_mpart, &e->om_mpart_cap, (size_t)N * coils * nufft_sample_chunks((int64_t)M) * sizeof(double), false}})))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(e->om_y, y, ym * sizeof(float2), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(e->om_sens, sens, sn * sizeof(float2), hipMemcpyDeviceToDevice, s));
-    if (w) HIP_TRY(hipMemcpyAsync(e->om_w, w, M * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemsetAsync(e->mc_sc, 0, (size_t)N * 8 * sizeof(double), s));
-    {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, e->om_maps, s));
-    }
-    if ((rc = om_adjoint(e, e->om_y, w ? e->om_w : nullptr, e->om_maps, map_n, e->om_sens, sens_n, coils, N, mc_aty(e), s))) return rc;
-    if (with_iterate) {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_sense_iterate(x0, x, z, u, N, H, W, s));
-    }
-    commit_stage(e, {STAGE_ORS, false, coils, sens_n, cg_iters, w != nullptr, map_n, toeplitz});
-    return PNP_OK;
-}
-
-}  // namespace
-
 int pnp_offres_forward_mc(pnp_handle e, const float* img, const float* maps, int map_n, const float* sens, int sens_n, int coils, int batch,
                           float* samples, void* stream) {
     PNP_API_BEGIN
     const char* fn = "pnp_offres_forward_mc";
-    if (int rc = om_check_scalars(fn, coils, sens_n, map_n)) return rc;
+    if (int rc = op_check_scalars(fn, TAKES_BOTH, coils, sens_n, map_n)) return rc;
     if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
     if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
     if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
@@ -2773,9 +2573,9 @@ int pnp_offres_forward_mc(pnp_handle e, const float* img, const float* maps, int
     if (samples == img || samples == maps || samples == sens) return fail(PNP_ERR_INVALID, "%s: samples must not alias img, maps or sens", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
-    if (int rc = om_check(fn, e, coils, sens_n, map_n)) return rc;
+    if (int rc = op_check(fn, e, TAKES_BOTH, coils, sens_n, map_n)) return rc;
     PNP_ON_DEVICE(e);
-    if (int rc = om_ensure(e, coils)) return rc;
+    if (int rc = op_ensure(e, TAKES_BOTH, coils)) return rc;
     return om_forward(e, (const float2*)img, nullptr, (const float2*)maps, map_n, (const float2*)sens, sens_n, coils, batch, (float2*)samples,
                       (hipStream_t)stream);
     PNP_API_END("pnp_offres_forward_mc")
@@ -2785,7 +2585,7 @@ int pnp_offres_adjoint_mc(pnp_handle e, const float* samples, const float* weigh
                           int coils, int batch, float* img, void* stream) {
     PNP_API_BEGIN
     const char* fn = "pnp_offres_adjoint_mc";
-    if (int rc = om_check_scalars(fn, coils, sens_n, map_n)) return rc;
+    if (int rc = op_check_scalars(fn, TAKES_BOTH, coils, sens_n, map_n)) return rc;
     if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
     if (!samples) return fail(PNP_ERR_INVALID, "%s: null samples", fn);
     if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
@@ -2795,9 +2595,9 @@ int pnp_offres_adjoint_mc(pnp_handle e, const float* samples, const float* weigh
         return fail(PNP_ERR_INVALID, "%s: img must not alias samples, weights, maps or sens", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
-    if (int rc = om_check(fn, e, coils, sens_n, map_n)) return rc;
+    if (int rc = op_check(fn, e, TAKES_BOTH, coils, sens_n, map_n)) return rc;
     PNP_ON_DEVICE(e);
-    if (int rc = om_ensure(e, coils)) return rc;
+    if (int rc = op_ensure(e, TAKES_BOTH, coils)) return rc;
     return om_adjoint(e, (const float2*)samples, weights, (const float2*)maps, map_n, (const float2*)sens, sens_n, coils, batch, (float2*)img,
                       (hipStream_t)stream);
     PNP_API_END("pnp_offres_adjoint_mc")
@@ -2806,16 +2606,16 @@ int pnp_offres_adjoint_mc(pnp_handle e, const float* samples, const float* weigh
 int pnp_set_kspace_offres_mc(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, const float* omega, int map_n, const float* w,
                              int cg_iters, void* stream) {
     PNP_API_BEGIN
-    return om_install("pnp_set_kspace_offres_mc", e, false, false, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n, w, cg_iters,
-                      nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return nc_install("pnp_set_kspace_offres_mc", e, TAKES_BOTH, false, false, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, omega,
+                      map_n, w, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_offres_mc")
 }
 
 int pnp_reset_offres_mc(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, const float* omega, int map_n,
                         const float* w, int cg_iters, float* x, float* z, float* u, void* stream) {
     PNP_API_BEGIN
-    return om_install("pnp_reset_offres_mc", e, true, false, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n, w,
-                      cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
+    return nc_install("pnp_reset_offres_mc", e, TAKES_BOTH, true, false, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n,
+                      omega, map_n, w, cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_offres_mc")
 }
 
@@ -2836,42 +2636,8 @@ int pnp_offres_mc_normal(pnp_handle e, const float* pv, const float* mu, float* 
 int pnp_acquire_offres_mc(pnp_handle e, const float* gt, const float* sens, int coils, int sens_n, const float* omega, int map_n, const float* dcf,
                           double sigma_n, uint64_t seed, int flags, float* y, float* aty0, float* x0, void* stream) {
     PNP_API_BEGIN
-    const char* fn = "pnp_acquire_offres_mc";
-    // every rejection happens before any HIP call, and leaves the outputs untouched
-    if (flags != 0) return fail(PNP_ERR_INVALID, "%s: flags must be 0 (got 0x%x)", fn, (unsigned)flags);
-    if (!(sigma_n >= 0.0) || !std::isfinite(sigma_n)) return fail(PNP_ERR_INVALID, "%s: sigma_n must be finite and >= 0 (got %g)", fn, sigma_n);
-    if (int rc = om_check_scalars(fn, coils, sens_n, map_n)) return rc;
-    if (!gt) return fail(PNP_ERR_INVALID, "%s: null gt", fn);
-    if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
-    if (!omega) return fail(PNP_ERR_INVALID, "%s: null omega", fn);
-    if (!y) return fail(PNP_ERR_INVALID, "%s: null y", fn);
-    const auto input = [&](const float* p) { return p == gt || p == sens || p == omega; };
-    if (input(y) || (aty0 && (input(aty0) || aty0 == y)) || (x0 && (input(x0) || x0 == y)))
-        return fail(PNP_ERR_INVALID, "%s: no output may alias gt, sens, omega or another output", fn);
-    if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
-    if (int rc = om_check(fn, e, coils, sens_n, map_n)) return rc;
-    const int N = e->cfg.n, H = e->cfg.h, W = e->cfg.w;
-    PNP_ON_DEVICE(e);
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = om_ensure(e, coils, (size_t)map_n * e->orp.segments * H * W * sizeof(float2)))) return rc;
-    {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_offres_maps(omega, map_n, e->orp, e->nc, e->om_amaps, s));
-    }
-    if ((rc = om_forward(e, nullptr, gt, e->om_amaps, map_n, (const float2*)sens, sens_n, coils, N, (float2*)y, s))) return rc;
-    if (sigma_n != 0.0) {                                   // a noiseless acquisition draws nothing and keeps the forward's own bits
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_ncsense_noise((float2*)y, sigma_n, seed, coils, e->nc, N, s));
-    }
-    if (!aty0 && !x0) return PNP_OK;
-    float2* const a = aty0 ? (float2*)aty0 : e->d_work;     // without aty0 the image goes to the data-fidelity stage's scratch plane
-    if ((rc = om_adjoint(e, (const float2*)y, dcf, e->om_amaps, map_n, (const float2*)sens, sens_n, coils, N, a, s))) return rc;
-    if (x0) {
-        Prof p(e, s, PROF_OTHER, -1);
-        HIP_TRY(launch_acquire_clamp(a, (float2*)x0, N, H, W, s));
-    }
-    return PNP_OK;
+    return nc_acquire("pnp_acquire_offres_mc", e, TAKES_BOTH, gt, sens, coils, sens_n, omega, map_n, dcf, sigma_n, seed, flags, y, aty0, x0,
+                      (hipStream_t)stream);
     PNP_API_END("pnp_acquire_offres_mc")
 }
 
@@ -2913,7 +2679,7 @@ int pnp_toeplitz_plan(pnp_handle e, const float* weights, int flags, void* strea
     if (e->tz_planned) (void)hipDeviceSynchronize();        // no launch still reads the spectrum being replaced
     // from here on the old spectrum is gone: a live Toeplitz stage's constants are dropped with it, as pnp_nufft_plan drops them
     e->tz_planned = false;
-    drop_stage(e, true);
+    drop_stage(e, DROP_FORM, FORM_TZ);
     HIP_TRY(nc_upload(e->tz_traj, e->nc_traj.data(), M * 2 * sizeof(double)));
     HIP_TRY(nc_upload(e->tz_tw_h, twh.data(), twh.size() * sizeof(float2)));
     HIP_TRY(nc_upload(e->tz_tw_w, tww.data(), tww.size() * sizeof(float2)));
@@ -2930,7 +2696,7 @@ int pnp_toeplitz_plan(pnp_handle e, const float* weights, int flags, void* strea
 }
 
 int pnp_toeplitz_planned(pnp_handle e) { return e && e->tz_planned ? 1 : 0; }
-int pnp_toeplitz_live(pnp_handle e) { return e && e->stage.toeplitz ? 1 : 0; }
+int pnp_toeplitz_live(pnp_handle e) { return e && e->stage.form == FORM_TZ ? 1 : 0; }
 
 int pnp_toeplitz_spectrum(pnp_handle e, float* out, void* stream) {
     PNP_API_BEGIN
@@ -2962,7 +2728,7 @@ int pnp_toeplitz_apply(pnp_handle e, const float* img, int batch, float* out, vo
 int pnp_toeplitz_apply_mc(pnp_handle e, const float* img, const float* sens, int coils, int sens_n, int batch, float* out, void* stream) {
     PNP_API_BEGIN
     const char* fn = "pnp_toeplitz_apply_mc";
-    if (int rc = ns_check_scalars(fn, coils, sens_n)) return rc;
+    if (int rc = op_check_scalars(fn, TAKES_COILS, coils, sens_n, 0)) return rc;
     if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
     if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
     if (!sens) return fail(PNP_ERR_INVALID, "%s: null sens", fn);
@@ -2970,7 +2736,7 @@ int pnp_toeplitz_apply_mc(pnp_handle e, const float* img, const float* sens, int
     if (out == img || out == sens) return fail(PNP_ERR_INVALID, "%s: out must not alias img or sens", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
-    if (int rc = ns_check(fn, e, coils, sens_n)) return rc;
+    if (int rc = op_check(fn, e, TAKES_COILS, coils, sens_n, 0)) return rc;
     if (int rc = tz_need_spectrum(fn, e)) return rc;
     PNP_ON_DEVICE(e);
     if (int rc = tz_ensure(e, (size_t)e->cfg.n * ns_block_of(e, coils), true)) return rc;
@@ -2981,29 +2747,30 @@ int pnp_toeplitz_apply_mc(pnp_handle e, const float* img, const float* sens, int
 
 int pnp_set_kspace_nc_tz(pnp_handle e, const float* y, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    return nc_install("pnp_set_kspace_nc_tz", e, false, true, nullptr, (const float2*)y, nullptr, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return nc_install("pnp_set_kspace_nc_tz", e, 0, false, true, nullptr, (const float2*)y, nullptr, 0, 1, nullptr, 1, nullptr, cg_iters, nullptr,
+                      nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_nc_tz")
 }
 
 int pnp_reset_nc_tz(pnp_handle e, const float* x0, const float* y, int cg_iters, float* x, float* z, float* u, void* stream) {
     PNP_API_BEGIN
-    return nc_install("pnp_reset_nc_tz", e, true, true, (const float2*)x0, (const float2*)y, nullptr, cg_iters, x, (float2*)z, (float2*)u,
-                      (hipStream_t)stream);
+    return nc_install("pnp_reset_nc_tz", e, 0, true, true, (const float2*)x0, (const float2*)y, nullptr, 0, 1, nullptr, 1, nullptr, cg_iters, x,
+                      (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_nc_tz")
 }
 
 int pnp_set_kspace_ncsense_tz(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    return ns_install("pnp_set_kspace_ncsense_tz", e, false, true, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, nullptr, cg_iters,
-                      nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return nc_install("pnp_set_kspace_ncsense_tz", e, TAKES_COILS, false, true, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n,
+                      nullptr, 1, nullptr, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_ncsense_tz")
 }
 
 int pnp_reset_ncsense_tz(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, int cg_iters, float* x, float* z,
                          float* u, void* stream) {
     PNP_API_BEGIN
-    return ns_install("pnp_reset_ncsense_tz", e, true, true, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, nullptr, cg_iters,
-                      x, (float2*)z, (float2*)u, (hipStream_t)stream);
+    return nc_install("pnp_reset_ncsense_tz", e, TAKES_COILS, true, true, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n,
+                      nullptr, 1, nullptr, cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_ncsense_tz")
 }
 
@@ -3043,7 +2810,7 @@ int pnp_offres_tz_plan(pnp_handle e, const float* weights, int flags, void* stre
     // from here on the old spectra are gone: a live stage that runs on them loses its constants, as pnp_offres_plan drops them
     e->otz_planned = false;
     e->otz.pairs = 0;
-    if (e->stage.offres_tz) e->stage = LiveStage{};
+    drop_stage(e, DROP_FORM, FORM_OTZ);
     HIP_TRY(nc_upload(e->otz_traj, e->nc_traj.data(), M * 2 * sizeof(double)));
     HIP_TRY(nc_upload(e->otz_tw_h, twh.data(), twh.size() * sizeof(float2)));
     HIP_TRY(nc_upload(e->otz_tw_w, tww.data(), tww.size() * sizeof(float2)));
@@ -3066,7 +2833,7 @@ int pnp_offres_tz_plan(pnp_handle e, const float* weights, int flags, void* stre
 }
 
 int pnp_offres_tz_planned(pnp_handle e) { return e && e->otz_planned ? 1 : 0; }
-int pnp_offres_tz_live(pnp_handle e) { return e && e->stage.offres_tz ? 1 : 0; }
+int pnp_offres_tz_live(pnp_handle e) { return e && e->stage.form == FORM_OTZ ? 1 : 0; }
 int pnp_offres_tz_spectra(pnp_handle e) { return e && e->otz_planned ? e->otz.pairs : 0; }
 
 int pnp_offres_tz_spectrum(pnp_handle e, float* out, void* stream) {
@@ -3084,7 +2851,7 @@ int pnp_offres_tz_spectrum(pnp_handle e, float* out, void* stream) {
 int pnp_offres_tz_apply(pnp_handle e, const float* img, const float* maps, int map_n, int batch, float* out, void* stream) {
     PNP_API_BEGIN
     const char* fn = "pnp_offres_tz_apply";
-    if (map_n < 1) return fail(PNP_ERR_INVALID, "%s: map_n must be 1 or n (got %d)", fn, map_n);
+    if (int rc = op_check_scalars(fn, TAKES_MAPS, 0, 0, map_n)) return rc;
     if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
     if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
     if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
@@ -3092,7 +2859,7 @@ int pnp_offres_tz_apply(pnp_handle e, const float* img, const float* maps, int m
     if (out == img || out == maps) return fail(PNP_ERR_INVALID, "%s: out must not alias img or maps", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
-    if (int rc = or_check(fn, e, map_n)) return rc;
+    if (int rc = op_check(fn, e, TAKES_MAPS, 0, 0, map_n)) return rc;
     if (int rc = otz_need_spectra(fn, e)) return rc;
     PNP_ON_DEVICE(e);
     if (int rc = otz_ensure(e, e->cfg.n, 0)) return rc;
@@ -3104,7 +2871,7 @@ int pnp_offres_tz_apply_mc(pnp_handle e, const float* img, const float* maps, in
                            float* out, void* stream) {
     PNP_API_BEGIN
     const char* fn = "pnp_offres_tz_apply_mc";
-    if (int rc = om_check_scalars(fn, coils, sens_n, map_n)) return rc;
+    if (int rc = op_check_scalars(fn, TAKES_BOTH, coils, sens_n, map_n)) return rc;
     if (batch < 1) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n (got %d)", fn, batch);
     if (!img) return fail(PNP_ERR_INVALID, "%s: null img", fn);
     if (!maps) return fail(PNP_ERR_INVALID, "%s: null maps", fn);
@@ -3113,7 +2880,7 @@ int pnp_offres_tz_apply_mc(pnp_handle e, const float* img, const float* maps, in
     if (out == img || out == maps || out == sens) return fail(PNP_ERR_INVALID, "%s: out must not alias img, maps or sens", fn);
     if (!e) return fail(PNP_ERR_INVALID, "%s: null handle", fn);
     if (batch > e->cfg.n) return fail(PNP_ERR_INVALID, "%s: batch must be 1..n=%d (got %d)", fn, e->cfg.n, batch);
-    if (int rc = om_check(fn, e, coils, sens_n, map_n)) return rc;
+    if (int rc = op_check(fn, e, TAKES_BOTH, coils, sens_n, map_n)) return rc;
     if (int rc = otz_need_spectra(fn, e)) return rc;
     PNP_ON_DEVICE(e);
     const int cb = otz_coil_block(e, coils, map_n);
@@ -3125,32 +2892,32 @@ int pnp_offres_tz_apply_mc(pnp_handle e, const float* img, const float* maps, in
 
 int pnp_set_kspace_offres_tz(pnp_handle e, const float* y, const float* omega, int map_n, int cg_iters, void* stream) {
     PNP_API_BEGIN
-    return or_install("pnp_set_kspace_offres_tz", e, false, true, nullptr, (const float2*)y, omega, map_n, nullptr, cg_iters, nullptr, nullptr, nullptr,
-                      (hipStream_t)stream);
+    return nc_install("pnp_set_kspace_offres_tz", e, TAKES_MAPS, false, true, nullptr, (const float2*)y, nullptr, 0, 1, omega, map_n, nullptr,
+                      cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_offres_tz")
 }
 
 int pnp_reset_offres_tz(pnp_handle e, const float* x0, const float* y, const float* omega, int map_n, int cg_iters, float* x, float* z, float* u,
                         void* stream) {
     PNP_API_BEGIN
-    return or_install("pnp_reset_offres_tz", e, true, true, (const float2*)x0, (const float2*)y, omega, map_n, nullptr, cg_iters, x, (float2*)z,
-                      (float2*)u, (hipStream_t)stream);
+    return nc_install("pnp_reset_offres_tz", e, TAKES_MAPS, true, true, (const float2*)x0, (const float2*)y, nullptr, 0, 1, omega, map_n, nullptr,
+                      cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_offres_tz")
 }
 
 int pnp_set_kspace_offres_mc_tz(pnp_handle e, const float* y, const float* sens, int coils, int sens_n, const float* omega, int map_n, int cg_iters,
                                 void* stream) {
     PNP_API_BEGIN
-    return om_install("pnp_set_kspace_offres_mc_tz", e, false, true, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n,
-                      nullptr, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    return nc_install("pnp_set_kspace_offres_mc_tz", e, TAKES_BOTH, false, true, nullptr, (const float2*)y, (const float2*)sens, coils, sens_n,
+                      omega, map_n, nullptr, cg_iters, nullptr, nullptr, nullptr, (hipStream_t)stream);
     PNP_API_END("pnp_set_kspace_offres_mc_tz")
 }
 
 int pnp_reset_offres_mc_tz(pnp_handle e, const float* x0, const float* y, const float* sens, int coils, int sens_n, const float* omega, int map_n,
                            int cg_iters, float* x, float* z, float* u, void* stream) {
     PNP_API_BEGIN
-    return om_install("pnp_reset_offres_mc_tz", e, true, true, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n, omega, map_n,
-                      nullptr, cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
+    return nc_install("pnp_reset_offres_mc_tz", e, TAKES_BOTH, true, true, (const float2*)x0, (const float2*)y, (const float2*)sens, coils, sens_n,
+                      omega, map_n, nullptr, cg_iters, x, (float2*)z, (float2*)u, (hipStream_t)stream);
     PNP_API_END("pnp_reset_offres_mc_tz")
 }
 

@@ -216,44 +216,69 @@ class PnPEngine:
         """Install the non-Cartesian constants (y complex64 [N,M] or [N,1,M], w float32 [M] or None) and start an episode from x0
         complex64 [N,1,H,W] (pnp_reset_nc).  Returns fresh (x f32, z c64, u c64); steps then solve the k-space subproblem by `cg_iters`
         CG iterations on the NUFFT normal operator."""
-        return self._reset_nc(x0, y, w, cg_iters, False)
+        return self._install_nc("nc", True, False, x0, y, None, None, w, cg_iters)
 
     def reset_nc_tz(self, x0: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor] = None,
                     cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """`reset_nc` with the CG on the Toeplitz form of A^H W A (pnp_reset_nc_tz): the spectrum is planned here when none exists for these
         weights, which are then the weights of aty and of the DC column too."""
-        return self._reset_nc(x0, y, w, cg_iters, True)
+        return self._install_nc("nc", True, True, x0, y, None, None, w, cg_iters)
 
-    def _reset_nc(self, x0, y, w, cg_iters, toeplitz):
-        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
-        yp, wp = self._nc_args(y, w)
-        x, z, u = self._iterate()
-        if toeplitz:
-            self._toeplitz_for(w)
-            _lib.check(self.lib.pnp_reset_nc_tz(self._h, x0.data_ptr(), yp, int(cg_iters), x.data_ptr(), z.data_ptr(), u.data_ptr(),
-                                                self._stream()), "pnp_reset_nc_tz")
+    def _install_nc(self, stem, reset, toeplitz, x0, y, sens, omega, w, cg_iters, episode=0):
+        """The twelve installers of the non-Cartesian stages: `reset`: pnp_reset_<stem>[_tz] from x0 (returns the fresh iterate), else
+        pnp_set_kspace_<stem>[_tz] for `episode`.  stem "nc", "ncsense" (takes sens), "offres" (takes omega) or "offres_mc" (both); a _tz form
+        plans the spectrum of its family for w first and passes no weights."""
+        coils, segmented = stem in ("ncsense", "offres_mc"), stem.startswith("offres")
+        name = f"pnp_{'reset' if reset else 'set_kspace'}_{stem}{'_tz' if toeplitz else ''}"
+        if reset:
+            x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
+        if coils:
+            yp, *mid, wp = self._ncsense_args(y, sens, w)
         else:
-            _lib.check(self.lib.pnp_reset_nc(self._h, x0.data_ptr(), yp, wp, int(cg_iters), x.data_ptr(), z.data_ptr(), u.data_ptr(),
-                                             self._stream()), "pnp_reset_nc")
-        self.live_episode = _next_episode()
-        return x, z, u
+            yp, wp = self._nc_args(y, w)
+            mid = []
+        if segmented:
+            omega, map_n = self._omega(omega)
+            mid += [omega.data_ptr(), map_n]
+        it = self._iterate() if reset else ()
+        if toeplitz:
+            (self._offres_tz_for if segmented else self._toeplitz_for)(w)
+        else:
+            mid.append(wp)
+        args = ([x0.data_ptr()] if reset else []) + [yp] + mid + [int(cg_iters)] + [t.data_ptr() for t in it]
+        _lib.check(getattr(self.lib, name)(self._h, *args, self._stream()), name)
+        self.live_episode = _next_episode() if reset else (episode or _next_episode())
+        return it
+
+    def _acquire_nc(self, stem, gt, sens, omega, sigma_n, seed, dcf):
+        """The four simulated acquisitions of the non-Cartesian stages (pnp_acquire_<stem>, stems as in `_install_nc`): returns (y, aty0, x0)."""
+        coils, segmented = stem in ("ncsense", "offres_mc"), stem.startswith("offres")
+        name = f"pnp_acquire_{stem}"
+        gt = self._chk(gt, torch.float32, self.n * self.h * self.w, "gt")
+        mid, lines = [], (self.n,)
+        if coils:
+            sens, c, sens_n = self._sens(sens)
+            mid, lines = [sens.data_ptr(), c, sens_n], (self.n, c)
+        if segmented:
+            omega, map_n = self._omega(omega)
+            mid += [omega.data_ptr(), map_n]
+        m = self.nufft_samples
+        if dcf is not None:
+            self._chk(dcf, torch.float32, m, "dcf")
+        y = torch.empty(lines + (max(m, 1),), dtype=torch.complex64, device=self.device)
+        aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
+        x0 = torch.empty_like(aty0)
+        _lib.check(getattr(self.lib, name)(self._h, gt.data_ptr(), *mid, _ptr(dcf), float(sigma_n), int(seed) & (2 ** 64 - 1), 0, y.data_ptr(),
+                                           aty0.data_ptr(), x0.data_ptr(), self._stream()), name)
+        return y, aty0, x0
 
     def set_kspace_nc(self, y: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0, cg_iters: int = 8) -> None:
         """Re-install the non-Cartesian constants of another episode without touching any iterate (pnp_set_kspace_nc)."""
-        self._set_kspace_nc(y, w, episode, cg_iters, False)
+        self._install_nc("nc", False, False, None, y, None, None, w, cg_iters, episode)
 
     def set_kspace_nc_tz(self, y: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0, cg_iters: int = 8) -> None:
         """`set_kspace_nc` for an episode whose CG runs the Toeplitz operator (pnp_set_kspace_nc_tz; the spectrum as in `reset_nc_tz`)."""
-        self._set_kspace_nc(y, w, episode, cg_iters, True)
-
-    def _set_kspace_nc(self, y, w, episode, cg_iters, toeplitz):
-        yp, wp = self._nc_args(y, w)
-        if toeplitz:
-            self._toeplitz_for(w)
-            _lib.check(self.lib.pnp_set_kspace_nc_tz(self._h, yp, int(cg_iters), self._stream()), "pnp_set_kspace_nc_tz")
-        else:
-            _lib.check(self.lib.pnp_set_kspace_nc(self._h, yp, wp, int(cg_iters), self._stream()), "pnp_set_kspace_nc")
-        self.live_episode = episode or _next_episode()
+        self._install_nc("nc", False, True, None, y, None, None, w, cg_iters, episode)
 
     # -- Toeplitz normal operator (include/pnpadmm_toeplitz.h) ----------------------------------
     _tz_weights = None           # (the weights tensor the live spectrum was planned from, or None for unit weights,)
@@ -353,17 +378,7 @@ class PnPEngine:
                    dcf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Simulated non-Cartesian acquisition on the planned trajectory (pnp_acquire_nc): gt float32 [N,1,H,W]; returns
         (y complex64 [N,M], aty0 = A^H (dcf . y) complex64 [N,1,H,W], x0 = max(aty0, 0))."""
-        gt = self._chk(gt, torch.float32, self.n * self.h * self.w, "gt")
-        m = self.nufft_samples
-        if dcf is not None:
-            self._chk(dcf, torch.float32, m, "dcf")
-        y = torch.empty((self.n, max(m, 1)), dtype=torch.complex64, device=self.device)
-        aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
-        x0 = torch.empty_like(aty0)
-        _lib.check(self.lib.pnp_acquire_nc(self._h, gt.data_ptr(), dcf.data_ptr() if dcf is not None else None, float(sigma_n),
-                                           int(seed) & (2 ** 64 - 1), 0, y.data_ptr(), aty0.data_ptr(), x0.data_ptr(), self._stream()),
-                   "pnp_acquire_nc")
-        return y, aty0, x0
+        return self._acquire_nc("nc", gt, None, None, sigma_n, seed, dcf)
 
     # -- non-Cartesian SENSE (include/pnpadmm_ncsense.h) --------------------------------------
     @property
@@ -409,47 +424,24 @@ class PnPEngine:
         """Install the non-Cartesian SENSE constants (y complex64 [N,C,M], sens complex64 [C,H,W] or [N,C,H,W], w float32 [M] or None) and
         start an episode from x0 complex64 [N,1,H,W] (pnp_reset_ncsense).  Returns fresh (x f32, z c64, u c64); steps then solve the
         k-space subproblem by `cg_iters` CG iterations on A^H W A + mu I, A p = [F_nu(S_c . p)]_c."""
-        return self._reset_ncsense(x0, y, sens, w, cg_iters, False)
+        return self._install_nc("ncsense", True, False, x0, y, sens, None, w, cg_iters)
 
     def reset_ncsense_tz(self, x0: torch.Tensor, y: torch.Tensor, sens: torch.Tensor, w: Optional[torch.Tensor] = None,
                          cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """`reset_ncsense` with the CG on the Toeplitz form of each coil's A^H W A (pnp_reset_ncsense_tz; the spectrum as in `reset_nc_tz`)."""
-        return self._reset_ncsense(x0, y, sens, w, cg_iters, True)
+        return self._install_nc("ncsense", True, True, x0, y, sens, None, w, cg_iters)
 
-    def _reset_ncsense(self, x0, y, sens, w, cg_iters, toeplitz):
-        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
-        yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
-        x, z, u = self._iterate()
-        if toeplitz:
-            self._toeplitz_for(w)
-            _lib.check(self.lib.pnp_reset_ncsense_tz(self._h, x0.data_ptr(), yp, sp, coils, sens_n, int(cg_iters), x.data_ptr(), z.data_ptr(),
-                                                     u.data_ptr(), self._stream()), "pnp_reset_ncsense_tz")
-        else:
-            _lib.check(self.lib.pnp_reset_ncsense(self._h, x0.data_ptr(), yp, sp, coils, sens_n, wp, int(cg_iters), x.data_ptr(), z.data_ptr(),
-                                                  u.data_ptr(), self._stream()), "pnp_reset_ncsense")
-        self.live_episode = _next_episode()
-        return x, z, u
 
     def set_kspace_ncsense(self, y: torch.Tensor, sens: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0,
                            cg_iters: int = 8) -> None:
         """Re-install the non-Cartesian SENSE constants of another episode without touching any iterate (pnp_set_kspace_ncsense)."""
-        self._set_kspace_ncsense(y, sens, w, episode, cg_iters, False)
+        self._install_nc("ncsense", False, False, None, y, sens, None, w, cg_iters, episode)
 
     def set_kspace_ncsense_tz(self, y: torch.Tensor, sens: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0,
                               cg_iters: int = 8) -> None:
         """`set_kspace_ncsense` for an episode whose CG runs the Toeplitz operator (pnp_set_kspace_ncsense_tz)."""
-        self._set_kspace_ncsense(y, sens, w, episode, cg_iters, True)
+        self._install_nc("ncsense", False, True, None, y, sens, None, w, cg_iters, episode)
 
-    def _set_kspace_ncsense(self, y, sens, w, episode, cg_iters, toeplitz):
-        yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
-        if toeplitz:
-            self._toeplitz_for(w)
-            _lib.check(self.lib.pnp_set_kspace_ncsense_tz(self._h, yp, sp, coils, sens_n, int(cg_iters), self._stream()),
-                       "pnp_set_kspace_ncsense_tz")
-        else:
-            _lib.check(self.lib.pnp_set_kspace_ncsense(self._h, yp, sp, coils, sens_n, wp, int(cg_iters), self._stream()),
-                       "pnp_set_kspace_ncsense")
-        self.live_episode = episode or _next_episode()
 
     def ncsense_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
         """q = A^H W A p + mu p with the installed non-Cartesian SENSE constants (pnp_ncsense_normal); p complex64 [N,1,H,W], mu float32 [N]."""
@@ -463,18 +455,7 @@ class PnPEngine:
                         dcf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Simulated multi-coil acquisition on the planned trajectory (pnp_acquire_ncsense): gt float32 [N,1,H,W]; returns
         (y complex64 [N,C,M], aty0 = A^H (dcf . y) complex64 [N,1,H,W], x0 = max(aty0, 0))."""
-        gt = self._chk(gt, torch.float32, self.n * self.h * self.w, "gt")
-        sens, coils, sens_n = self._sens(sens)
-        m = self.nufft_samples
-        if dcf is not None:
-            self._chk(dcf, torch.float32, m, "dcf")
-        y = torch.empty((self.n, coils, max(m, 1)), dtype=torch.complex64, device=self.device)
-        aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
-        x0 = torch.empty_like(aty0)
-        _lib.check(self.lib.pnp_acquire_ncsense(self._h, gt.data_ptr(), sens.data_ptr(), coils, sens_n, dcf.data_ptr() if dcf is not None else None,
-                                                float(sigma_n), int(seed) & (2 ** 64 - 1), 0, y.data_ptr(), aty0.data_ptr(), x0.data_ptr(),
-                                                self._stream()), "pnp_acquire_ncsense")
-        return y, aty0, x0
+        return self._acquire_nc("ncsense", gt, sens, None, sigma_n, seed, dcf)
 
     # -- off-resonance correction (include/pnpadmm_offres.h) ------------------------------------
     def offres_plan(self, times, segments: int) -> None:
@@ -597,23 +578,12 @@ class PnPEngine:
         """Install the off-resonance constants (y complex64 [N,M], omega float32 [H,W] or [N,H,W] in rad/s, w float32 [M] or None) and start an
         episode from x0 complex64 [N,1,H,W] (pnp_reset_offres).  Returns fresh (x f32, z c64, u c64); steps then solve the k-space subproblem
         by `cg_iters` CG iterations on A^H W A + mu I with the time-segmented A."""
-        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
-        yp, wp = self._nc_args(y, w)
-        omega, map_n = self._omega(omega)
-        x, z, u = self._iterate()
-        _lib.check(self.lib.pnp_reset_offres(self._h, x0.data_ptr(), yp, omega.data_ptr(), map_n, wp, int(cg_iters), x.data_ptr(), z.data_ptr(),
-                                             u.data_ptr(), self._stream()), "pnp_reset_offres")
-        self.live_episode = _next_episode()
-        return x, z, u
+        return self._install_nc("offres", True, False, x0, y, None, omega, w, cg_iters)
 
     def set_kspace_offres(self, y: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0,
                           cg_iters: int = 8) -> None:
         """Re-install the off-resonance constants of another episode without touching any iterate (pnp_set_kspace_offres)."""
-        yp, wp = self._nc_args(y, w)
-        omega, map_n = self._omega(omega)
-        _lib.check(self.lib.pnp_set_kspace_offres(self._h, yp, omega.data_ptr(), map_n, wp, int(cg_iters), self._stream()),
-                   "pnp_set_kspace_offres")
-        self.live_episode = episode or _next_episode()
+        self._install_nc("offres", False, False, None, y, None, omega, w, cg_iters, episode)
 
     def offres_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
         """q = A^H W A p + mu p with the installed off-resonance constants (pnp_offres_normal); p complex64 [N,1,H,W], mu float32 [N]."""
@@ -627,18 +597,7 @@ class PnPEngine:
                        dcf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Simulated acquisition under the field map on the planned trajectory and times (pnp_acquire_offres): gt float32 [N,1,H,W]; returns
         (y complex64 [N,M], aty0 = A^H (dcf . y) complex64 [N,1,H,W], x0 = max(aty0, 0))."""
-        gt = self._chk(gt, torch.float32, self.n * self.h * self.w, "gt")
-        omega, map_n = self._omega(omega)
-        m = self.nufft_samples
-        if dcf is not None:
-            self._chk(dcf, torch.float32, m, "dcf")
-        y = torch.empty((self.n, max(m, 1)), dtype=torch.complex64, device=self.device)
-        aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
-        x0 = torch.empty_like(aty0)
-        _lib.check(self.lib.pnp_acquire_offres(self._h, gt.data_ptr(), omega.data_ptr(), map_n, dcf.data_ptr() if dcf is not None else None,
-                                               float(sigma_n), int(seed) & (2 ** 64 - 1), 0, y.data_ptr(), aty0.data_ptr(), x0.data_ptr(),
-                                               self._stream()), "pnp_acquire_offres")
-        return y, aty0, x0
+        return self._acquire_nc("offres", gt, None, omega, sigma_n, seed, dcf)
 
     # -- off-resonance correction for multi-coil data (include/pnpadmm_offres_mc.h) -----------
     @property
@@ -681,23 +640,12 @@ class PnPEngine:
         [N,H,W] in rad/s, w float32 [M] or None) and start an episode from x0 complex64 [N,1,H,W] (pnp_reset_offres_mc).  Returns fresh
         (x f32, z c64, u c64); steps then solve the k-space subproblem by `cg_iters` CG iterations on A^H W A + mu I with the coils times
         segments operator A."""
-        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
-        yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
-        omega, map_n = self._omega(omega)
-        x, z, u = self._iterate()
-        _lib.check(self.lib.pnp_reset_offres_mc(self._h, x0.data_ptr(), yp, sp, coils, sens_n, omega.data_ptr(), map_n, wp, int(cg_iters),
-                                                x.data_ptr(), z.data_ptr(), u.data_ptr(), self._stream()), "pnp_reset_offres_mc")
-        self.live_episode = _next_episode()
-        return x, z, u
+        return self._install_nc("offres_mc", True, False, x0, y, sens, omega, w, cg_iters)
 
     def set_kspace_offres_mc(self, y: torch.Tensor, sens: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None,
                              episode: int = 0, cg_iters: int = 8) -> None:
         """Re-install the multi-coil off-resonance constants of another episode without touching any iterate (pnp_set_kspace_offres_mc)."""
-        yp, sp, coils, sens_n, wp = self._ncsense_args(y, sens, w)
-        omega, map_n = self._omega(omega)
-        _lib.check(self.lib.pnp_set_kspace_offres_mc(self._h, yp, sp, coils, sens_n, omega.data_ptr(), map_n, wp, int(cg_iters), self._stream()),
-                   "pnp_set_kspace_offres_mc")
-        self.live_episode = episode or _next_episode()
+        self._install_nc("offres_mc", False, False, None, y, sens, omega, w, cg_iters, episode)
 
     def offres_mc_normal(self, p: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
         """q = A^H W A p + mu p with the installed multi-coil off-resonance constants (pnp_offres_mc_normal); p complex64 [N,1,H,W], mu
@@ -712,19 +660,7 @@ class PnPEngine:
                           dcf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Simulated multi-coil acquisition under the field map on the planned trajectory and times (pnp_acquire_offres_mc): gt float32
         [N,1,H,W]; returns (y complex64 [N,C,M], aty0 = A^H (dcf . y) complex64 [N,1,H,W], x0 = max(aty0, 0))."""
-        gt = self._chk(gt, torch.float32, self.n * self.h * self.w, "gt")
-        sens, coils, sens_n = self._sens(sens)
-        omega, map_n = self._omega(omega)
-        m = self.nufft_samples
-        if dcf is not None:
-            self._chk(dcf, torch.float32, m, "dcf")
-        y = torch.empty((self.n, coils, max(m, 1)), dtype=torch.complex64, device=self.device)
-        aty0 = torch.empty((self.n, 1, self.h, self.w), dtype=torch.complex64, device=self.device)
-        x0 = torch.empty_like(aty0)
-        _lib.check(self.lib.pnp_acquire_offres_mc(self._h, gt.data_ptr(), sens.data_ptr(), coils, sens_n, omega.data_ptr(), map_n,
-                                                  dcf.data_ptr() if dcf is not None else None, float(sigma_n), int(seed) & (2 ** 64 - 1), 0,
-                                                  y.data_ptr(), aty0.data_ptr(), x0.data_ptr(), self._stream()), "pnp_acquire_offres_mc")
-        return y, aty0, x0
+        return self._acquire_nc("offres_mc", gt, sens, omega, sigma_n, seed, dcf)
 
     # -- Toeplitz form of the off-resonance operator (include/pnpadmm_offres_tz.h) -------------
     _otz_weights = None          # (the weights tensor the live spectra were planned from, or None for unit weights,)
@@ -800,48 +736,22 @@ class PnPEngine:
                         cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """`reset_offres` with the CG on the Toeplitz form of A^H W A (pnp_reset_offres_tz): the spectra are planned here when none exist
         for these weights and the live plans; the weights are then those of aty and of the DC column too."""
-        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
-        yp, _ = self._nc_args(y, w)
-        omega, map_n = self._omega(omega)
-        x, z, u = self._iterate()
-        self._offres_tz_for(w)
-        _lib.check(self.lib.pnp_reset_offres_tz(self._h, x0.data_ptr(), yp, omega.data_ptr(), map_n, int(cg_iters), x.data_ptr(), z.data_ptr(),
-                                                u.data_ptr(), self._stream()), "pnp_reset_offres_tz")
-        self.live_episode = _next_episode()
-        return x, z, u
+        return self._install_nc("offres", True, True, x0, y, None, omega, w, cg_iters)
 
     def set_kspace_offres_tz(self, y: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None, episode: int = 0,
                              cg_iters: int = 8) -> None:
         """`set_kspace_offres` for an episode whose CG runs the Toeplitz form (pnp_set_kspace_offres_tz; the spectra as in `reset_offres_tz`)."""
-        yp, _ = self._nc_args(y, w)
-        omega, map_n = self._omega(omega)
-        self._offres_tz_for(w)
-        _lib.check(self.lib.pnp_set_kspace_offres_tz(self._h, yp, omega.data_ptr(), map_n, int(cg_iters), self._stream()),
-                   "pnp_set_kspace_offres_tz")
-        self.live_episode = episode or _next_episode()
+        self._install_nc("offres", False, True, None, y, None, omega, w, cg_iters, episode)
 
     def reset_offres_mc_tz(self, x0: torch.Tensor, y: torch.Tensor, sens: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None,
                            cg_iters: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """`reset_offres_mc` with the CG on the Toeplitz form of A^H W A (pnp_reset_offres_mc_tz; the spectra as in `reset_offres_tz`)."""
-        x0 = self._chk(x0, torch.complex64, self.n * self.h * self.w, "x0")
-        yp, sp, coils, sens_n, _ = self._ncsense_args(y, sens, w)
-        omega, map_n = self._omega(omega)
-        x, z, u = self._iterate()
-        self._offres_tz_for(w)
-        _lib.check(self.lib.pnp_reset_offres_mc_tz(self._h, x0.data_ptr(), yp, sp, coils, sens_n, omega.data_ptr(), map_n, int(cg_iters),
-                                                   x.data_ptr(), z.data_ptr(), u.data_ptr(), self._stream()), "pnp_reset_offres_mc_tz")
-        self.live_episode = _next_episode()
-        return x, z, u
+        return self._install_nc("offres_mc", True, True, x0, y, sens, omega, w, cg_iters)
 
     def set_kspace_offres_mc_tz(self, y: torch.Tensor, sens: torch.Tensor, omega: torch.Tensor, w: Optional[torch.Tensor] = None,
                                 episode: int = 0, cg_iters: int = 8) -> None:
         """`set_kspace_offres_mc` for an episode whose CG runs the Toeplitz form (pnp_set_kspace_offres_mc_tz)."""
-        yp, sp, coils, sens_n, _ = self._ncsense_args(y, sens, w)
-        omega, map_n = self._omega(omega)
-        self._offres_tz_for(w)
-        _lib.check(self.lib.pnp_set_kspace_offres_mc_tz(self._h, yp, sp, coils, sens_n, omega.data_ptr(), map_n, int(cg_iters), self._stream()),
-                   "pnp_set_kspace_offres_mc_tz")
-        self.live_episode = episode or _next_episode()
+        self._install_nc("offres_mc", False, True, None, y, sens, omega, w, cg_iters, episode)
 
     # -- field map estimation (include/pnpadmm_fieldmap.h) ----------------------------------
     def _echoes(self, x1: torch.Tensor, x2: torch.Tensor) -> int:

@@ -130,8 +130,9 @@ def test_build_files_the_units_and_the_python_layers():
     internal = open(os.path.join(CSRC, "pnp_internal.h")).read()
     assert "kOffresTzPlanes = 512" in internal
     capi = open(os.path.join(CSRC, "pnp_capi.hip")).read()
-    assert "bool offres_tz = false;" in capi and "bool toeplitz = false;" in capi     # a bit of its own in LiveStage, beside the existing one
-    assert "return e && e->stage.toeplitz ? 1 : 0; }" in capi                        # pnp_toeplitz_live reads the old bit alone
+    assert "enum StageForm { FORM_GRID, FORM_TZ, FORM_OTZ };" in capi                # a form of its own in LiveStage, beside the existing one
+    assert "return e && e->stage.form == FORM_TZ ? 1 : 0; }" in capi                 # pnp_toeplitz_live reads the old form alone
+    assert "return e && e->stage.form == FORM_OTZ ? 1 : 0; }" in capi                # ... and pnp_offres_tz_live this header's
     P = engine.PnPEngine
     for name, params in (("offres_tz_plan", ["self", "weights"]), ("offres_tz_spectrum", ["self"]), ("offres_tz_apply", ["self", "img", "maps"]),
                          ("offres_tz_apply_mc", ["self", "img", "maps", "sens"]), ("reset_offres_tz", ["self", "x0", "y", "omega", "w", "cg_iters"]),
